@@ -35,6 +35,10 @@ Also on the JSON line:
                  (zimg is not buildable here) and is labelled as such.
   pcie_inclusive the same chain through the hb_filter_object_t surface with host hb_buffer_t in and
                  out (upload adapter ... download adapter) — PCIe included.  Never `value`.
+
+--dump-outputs DIR writes the frames the last timed step handed back, plane by plane, as DIR/<plane>.npy (float32,
+frames x rows x columns, or a seeded sample of each frame when the whole would pass 64 MB - see dump_outputs()).  The
+inputs are the same from run to run for the same arguments, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -67,6 +71,33 @@ WORKLOADS = {
                     text="BASELINE configs[1]: nlmeans medium (patch 7, range 3, 2 frames) 1920x1080 YUV420P "
                          "8-bit, inputs resident in HBM"),
 }
+
+
+DUMP_BUDGET = 64 << 20     # bytes: every file --dump-outputs writes, all ranks together
+
+
+def dump_outputs(path, planes, budget=DUMP_BUDGET):
+    """--dump-outputs: `planes` maps a name to the list of (rows x columns) device tensors of one plane, one per output frame
+    of the last timed step.  Each name becomes <path>/<name>.npy in float32: frames x rows x columns when everything fits in
+    `budget`, else frames x k - the same k positions of every frame, drawn without replacement by a generator seeded with the
+    name (sorted flat indices into the plane), k in proportion to the plane's size.  Runs after the timed region."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    total = sum(len(ts) * ts[0].numel() for ts in planes.values() if ts)
+    room = max(budget - 256 * len(planes), 0) // 4                       # float32 values, less the .npy headers
+    for name, ts in planes.items():
+        if not ts:
+            continue
+        full = torch.stack([t.contiguous() for t in ts])
+        if total > room:
+            n = ts[0].numel()
+            k = max(1, n * room // total)
+            rng = np.random.default_rng(zlib.crc32(name.encode()))
+            idx = torch.from_numpy(np.sort(rng.choice(n, size=k, replace=False))).to(full.device)
+            full = full.reshape(len(ts), n)[:, idx]
+        np.save(os.path.join(path, name + ".npy"), full.cpu().numpy().astype(np.float32))
 
 
 def frame_bytes(w, h):
@@ -299,6 +330,10 @@ def run_nlmeans(args, world, rank, local_rank):
     ctx.sync()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        pre = f"rank{rank}_" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {pre + p: [f[c] for f in dev_out] for c, p in enumerate(("y", "cb", "cr"))},
+                     DUMP_BUDGET // world)
     if world > 1:
         dist.barrier()
     # the kernel's launch time: the same steps once more with every launch bracketed by HIP events on its stream (kept out
@@ -550,6 +585,7 @@ def run_chain(args, world, rank, local_rank):
             self.out_arr = (hip.DevFrame * self.cap)(*[hip.dev_frame(t) for t in self.out_t])
             self.produced = 0
             self.fed = 0
+            self.last = 0                                 # output frames of the latest step: out_t[:last]
 
         def combed_for(self, i0, n):
             """comb_detect_work (comb_detect.c:1537-1583): frame i is classified from the luma of i-1, i, i+1 (the first
@@ -560,8 +596,9 @@ def run_chain(args, world, rank, local_rank):
 
         def step(self):
             combed = self.combed_for(self.fed, B) if self.comb else [2] * B
-            self.produced += self.chain.process_dev(in_arrs[(self.fed // B) % nphase], self.out_arr, tag0=self.fed, flags=flags,
-                                                    combed=combed)
+            self.last = self.chain.process_dev(in_arrs[(self.fed // B) % nphase], self.out_arr, tag0=self.fed, flags=flags,
+                                               combed=combed)
+            self.produced += self.last
             self.fed += B
 
         def sync(self):
@@ -600,6 +637,13 @@ def run_chain(args, world, rank, local_rank):
     t_enq = time.perf_counter() - t0                     # host time to enqueue the timed steps (nothing waited for yet)
     sync_all()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump = {}
+        for i, ln in enumerate(lanes):
+            pre = (f"rank{rank}_" if world > 1 else "") + (f"stream{i}_" if len(lanes) > 1 else "")
+            for c, p in enumerate(("y", "cb", "cr")):
+                dump[pre + p] = [ln.out_t[j][c] for j in range(ln.last)]
+        dump_outputs(args.dump_outputs, dump, DUMP_BUDGET // world)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
@@ -807,10 +851,17 @@ def main():
                          "(eedi2_template.c:371, :392-393), so the rate depends on it: config.eedi2_mask_density says how much")
     ap.add_argument("--stream-frames", type=int, default=0,
                     help="chain workloads: length of the synthetic stream the steps walk through (default 3 batches; 2160p: 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output frames of the last one as DIR/<plane>.npy (float32, "
+                         "at most 64 MB in all: a fixed seeded sample of each frame when the whole is larger)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU, no kernels: the rank plumbing of the multi-GPU launch only (gloo on the CPU) - see "
                          "dry_run(); the line it prints is labelled and is not a measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs: a dry run computes nothing")
     if args.stage_streams is None:
         args.stage_streams = 2 if args.depth == 8 else 0
 

@@ -57,3 +57,27 @@ def test_issue_floors_of_the_dominant_kernels():
         assert f and f["bound"] == bound and 0.3 < f["floor_frac"] <= 1.0, (name, f)
         assert max(f["valu_us"], f["salu_us"], f["lds_us"], f["hbm_us"]) <= f["profiled_launch_us"]
     assert bench.issue_floors("no_such_kernel") is None
+
+
+def test_dump_outputs_whole_planes_and_bounded_sample(tmp_path):
+    """--dump-outputs: planes that fit are written whole, in float32; larger ones as the same seeded positions of every
+    frame, within the budget, identical from call to call."""
+    import numpy as np
+    import torch
+    small = {"y": [torch.arange(12, dtype=torch.uint8).reshape(3, 4) + i for i in range(2)]}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    y = np.load(tmp_path / "small" / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (2, 3, 4) and y[1, 2, 3] == 12.0
+    g = torch.Generator().manual_seed(1)
+    big = {p: [torch.randint(0, 1024, (h, w), dtype=torch.int16, generator=g) for _ in range(4)]
+           for p, (h, w) in (("y", (256, 512)), ("cb", (128, 256)), ("cr", (128, 256)))}
+    budget = 1 << 20
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big, budget)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= budget
+    for p, ts in big.items():
+        a, b = np.load(tmp_path / "a" / f"{p}.npy"), np.load(tmp_path / "b" / f"{p}.npy")
+        assert a.dtype == np.float32 and a.shape[0] == 4 and 0 < a.shape[1] < ts[0].numel()
+        assert np.array_equal(a, b)
+        for i, t in enumerate(ts):
+            assert np.isin(a[i], t.numpy()).all()

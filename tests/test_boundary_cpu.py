@@ -6,7 +6,9 @@ re-declaration (include/hbhip_libhb.h): every libhb type, field, enum and functi
 compatible type.  libav* / jansson are not in this image; tests/libhb_stubs/ stands in for the handful of their
 names libhb's headers mention (opaque types - only names and kinds matter for a syntax + type check, nothing links).
 The three enumerators INTEGRATION.md adds to libhb come in as -D, exactly as the patch there spells them.
-Skipped where /root/reference does not exist (the GPU box)."""
+The compile checks are skipped where /root/reference does not exist (the GPU box); the layout check runs everywhere,
+against the reference header's layout stored in tests/golden/filter_object_layout.txt (and, where the tree exists,
+that file against the header itself)."""
 import glob
 import os
 import subprocess
@@ -15,7 +17,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/libhb"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree")
+needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree")
+LAYOUT = os.path.join(ROOT, "tests", "golden", "filter_object_layout.txt")
 
 # what INTEGRATION.md section 1 adds to libhb: a storage type next to COREMEDIA (internal.h:152-153) and two filter ids
 # behind the last one (common.h:1729-1778)
@@ -27,6 +30,7 @@ SOURCES = sorted(glob.glob(os.path.join(ROOT, "handbrake_amd", "libhb", "*_hip.c
     [os.path.join(ROOT, "handbrake_amd", "libhb", f) for f in ("hip_common.c", "hbhip_registry.c")]
 
 
+@needs_ref
 @pytest.mark.parametrize("src", SOURCES, ids=[os.path.basename(s) for s in SOURCES])
 def test_drop_in_compiles_against_the_real_libhb_headers(src):
     r = subprocess.run(["gcc"] + FLAGS + [src], capture_output=True, text=True)
@@ -50,15 +54,25 @@ int main(void)
 """
 
 
+def _layout(tmp_path, tag, inc, flags):
+    c = tmp_path / f"off_{tag}.c"
+    c.write_text(OFFSETS % inc)
+    exe = tmp_path / f"off_{tag}"
+    subprocess.check_call(["gcc", "-std=gnu99"] + flags + [str(c), "-o", str(exe)])
+    return subprocess.check_output([str(exe)], text=True)
+
+
 def test_filter_object_layout_equals_the_reference(tmp_path):
-    """struct hb_filter_object_s (common.h:1670-1711) field for field: the same offsets in the reference's header and
-    in include/hbhip_libhb.h - the object files of the two worlds could be linked against each other."""
-    outs = []
-    for tag, inc, flags in (("real", '#include "handbrake/handbrake.h"', ["-D__LIBHB__", f"-I{ROOT}/tests/libhb_stubs", f"-I{REF}"]),
-                            ("ours", '#include "hbhip_libhb.h"', [f"-I{ROOT}/include"])):
-        c = tmp_path / f"off_{tag}.c"
-        c.write_text(OFFSETS % inc)
-        exe = tmp_path / f"off_{tag}"
-        subprocess.check_call(["gcc", "-std=gnu99"] + flags + [str(c), "-o", str(exe)])
-        outs.append(subprocess.check_output([str(exe)], text=True))
-    assert outs[0] == outs[1], f"reference:\n{outs[0]}\nours:\n{outs[1]}"
+    """struct hb_filter_object_s (common.h:1670-1711) field for field: the same offsets in the reference's header (as
+    stored in tests/golden/filter_object_layout.txt) and in include/hbhip_libhb.h - the object files of the two worlds
+    could be linked against each other."""
+    want = open(LAYOUT).read()
+    ours = _layout(tmp_path, "ours", '#include "hbhip_libhb.h"', [f"-I{ROOT}/include"])
+    assert ours == want, f"reference:\n{want}\nours:\n{ours}"
+
+
+@needs_ref
+def test_stored_layout_is_the_reference_header(tmp_path):
+    """tests/golden/filter_object_layout.txt is what the reference's own header gives."""
+    real = _layout(tmp_path, "real", '#include "handbrake/handbrake.h"', ["-D__LIBHB__", f"-I{ROOT}/tests/libhb_stubs", f"-I{REF}"])
+    assert real == open(LAYOUT).read()
