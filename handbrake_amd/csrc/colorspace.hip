@@ -182,6 +182,7 @@ __device__ __forceinline__ float to_gamma_dev(int cls, float x)
 __device__ __forceinline__ float hable_dev(float in)
 {
     const float a = 0.15f, b = 0.50f, c = 0.10f, d = 0.20f, e = 0.02f, f = 0.30f;
+    if (in > 1e18f) in = 1e18f;          // flat long before; beyond ~5e19 in * in * a overflows (the oracle's hable())
     return __fdiv_rn(in * (in * a + b * c) + d * e, in * (in * a + b) + d * f) - __fdiv_rn(e, f);
 }
 

@@ -35,6 +35,10 @@
  * written as an explicit chain of fmaf() for the same reason (round 5; before, every product was rounded on its own);
  * tests/test_colorspace_cpu.py holds them against libm.  What still separates this file from real zimg is that
  * rounding - not modelling: no tables, no clipping of super-whites.
+ * Hable's curve takes its argument clipped to 1e18: beyond the PQ pole (E' above ~1.99, out-of-gamut Y'CbCr
+ * only) the linear light reaches ~1e35, where the curve's products overflowed single range and inf / inf made the
+ * sample NaN, pinned to [max, mid, 0] instead of the saturated colour (tests/test_colour_model_cpu.py found it:
+ * HDR10 Y 868 Cb 1023 Cr 0 at 10 bits gave 1023 / 512 / 0, the float64 model 131 / 988 / 468).
  * The HIP path is tested bit-for-bit against THIS file, never against FFmpeg/zimg.
  */
 #include "oracle.h"
@@ -307,6 +311,7 @@ static inline float to_gamma(int cls, float x)
 static inline float hable(float in)
 {
     const float a = 0.15f, b = 0.50f, c = 0.10f, d = 0.20f, e = 0.02f, f = 0.30f;
+    if (in > 1e18f) in = 1e18f;          /* the curve is flat (1 - e / f) long before; beyond ~5e19 in * in * a overflows */
     return (in * (in * a + b * c) + d * e) / (in * (in * a + b) + d * f) - e / f;
 }
 
