@@ -103,6 +103,24 @@ __device__ __forceinline__ PL plane_ptrs(const P3 &P, int pl, size_t off)
 __device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
 __device__ __forceinline__ int hbhip_align_up_dev(int v, int a) { return (v + a - 1) / a * a; }
 
+// Slots in an LDS list for the `n` (0..7) entries of each lane, in lane order, with ONE atomic per wave: the lanes' counts
+// as three ballots of their bits, the slots below a lane as mbcnt of those.  An atomicAdd of a value that differs between
+// lanes compiles to a scalar loop over the active lanes (readlane, add, writelane: nine instructions a lane, one after the
+// other) ahead of the atomic.  Call with every lane of the wave active.
+__device__ __forceinline__ int wave_list_slots(int *counter, unsigned n)
+{
+    const uint64_t b0 = __ballot(n & 1u), b1 = __ballot(n & 2u), b2 = __ballot(n & 4u);
+    const int total = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
+    auto below = [](uint64_t m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); };
+    int base = 0;
+    if (total)
+    {
+        if ((threadIdx.x & 63) == 0) base = atomicAdd(counter, total);
+        base = __builtin_amdgcn_readfirstlane(base);
+    }
+    return base + below(b0) + 2 * below(b1) + 4 * below(b2);
+}
+
 __device__ __forceinline__ int sad3(const uint8_t *a, int ai, const uint8_t *b, int bi)
 {
     return iabs((int)a[ai - 1] - (int)b[bi - 1]) + iabs((int)a[ai] - (int)b[bi]) + iabs((int)a[ai + 1] - (int)b[bi + 1]);
@@ -2226,30 +2244,29 @@ __global__ __launch_bounds__(FG_T) void k_fill_gaps_b(P3 P)
     if (maskless)
     {
         // no mask pixel in the plane, no gap to fill (:1048-1050): the pass is its bit_blit of a map of peaks (k_dir_map4)
-        if (x < width)
+        if (x + 3 < width)
         {
 #pragma unroll
-            for (int i = 0; i < 2 * FG_R; i++)
-            {
-                const int y = ya + i;
-                if (y >= height) break;
-                uint8_t *o = Q.c + (size_t)y * pitch + x;
-                if (x + 3 < width) *reinterpret_cast<uint32_t *>(o) = 0xffffffffu;
-                else for (int k = 0; k < 4 && x + k < width; k++) o[k] = (uint8_t)PEAK;
-            }
+            for (int i = 0; i < 2 * FG_R && ya + i < height; i++)
+                *reinterpret_cast<uint32_t *>(Q.c + (size_t)(ya + i) * pitch + x) = 0xffffffffu;
         }
+        else if (x < width)
+            for (int i = 0; i < 2 * FG_R && ya + i < height; i++)
+                for (int k = 0; k < 4 && x + k < width; k++) Q.c[(size_t)(ya + i) * pitch + x + k] = (uint8_t)PEAK;
         return;
     }
     auto rebuilt = [&](int y) { return y >= y0 && y < height - 1; };
     // the rows that are only copied (the reference's bit_blit): the other parity, and what lies outside y0 .. height - 2
-    uint32_t vcopy[2 * FG_R];
-#pragma unroll
-    for (int i = 0; i < 2 * FG_R; i++)
+    uint32_t vcopy[2 * FG_R] = {};
+    if (x < width)                                                 // (the lane's test once, the rows' tests are uniform)
     {
-        const int y = ya + i;
-        vcopy[i] = 0;
-        if (x < width && y < height && !((((y - y0) & 1) == 0) && rebuilt(y)))
-            vcopy[i] = *reinterpret_cast<const uint32_t *>(Q.b + (size_t)y * pitch + x);
+#pragma unroll
+        for (int i = 0; i < 2 * FG_R; i++)
+        {
+            const int y = ya + i;
+            if (y < height && !((((y - y0) & 1) == 0) && rebuilt(y)))
+                vcopy[i] = *reinterpret_cast<const uint32_t *>(Q.b + (size_t)y * pitch + x);
+        }
     }
     if (tid == 0) s_count = 0;
     const int lo = x0 - FG_HALO;                                   // column of staged byte 0 (a multiple of 4)
@@ -2257,25 +2274,22 @@ __global__ __launch_bounds__(FG_T) void k_fill_gaps_b(P3 P)
     {
         // all loads of a thread in flight before its first LDS store (ndw <= 288: two dwords per row and thread); rows
         // outside the plane are rows no pixel's tests reach (:1076, :1090): they are read from the nearest row inside
+        // (no branch around the loads: a lane past the span reads its last dword again and does not store it - behind a
+        // branch per column the compiler waited for the first column's loads before it issued the second's)
         const bool h0 = tid < ndw, h1 = tid + FG_T < ndw;
-        uint32_t vd[FG_ND][2] = {}, vm[FG_NM][2] = {};
-        if (h0)
+        const int i0 = min(tid, ndw - 1), i1 = min(tid + FG_T, ndw - 1);
+        uint32_t vd[FG_ND][2], vm[FG_NM][2];
+#pragma unroll
+        for (int r = 0; r < FG_ND; r++)
         {
-#pragma unroll
-            for (int r = 0; r < FG_ND; r++)
-                vd[r][0] = reinterpret_cast<const uint32_t *>(Q.b + (size_t)min(max(yb - 2 + 2 * r, 0), height - 1) * pitch + lo)[tid];
-#pragma unroll
-            for (int r = 0; r < FG_NM; r++)
-                vm[r][0] = reinterpret_cast<const uint32_t *>(Q.a + (size_t)min(max(yb - 3 + 2 * r, 0), height - 1) * pitch + lo)[tid];
+            const uint32_t *row = reinterpret_cast<const uint32_t *>(Q.b + (size_t)min(max(yb - 2 + 2 * r, 0), height - 1) * pitch + lo);
+            vd[r][0] = row[i0]; vd[r][1] = row[i1];
         }
-        if (h1)
+#pragma unroll
+        for (int r = 0; r < FG_NM; r++)
         {
-#pragma unroll
-            for (int r = 0; r < FG_ND; r++)
-                vd[r][1] = reinterpret_cast<const uint32_t *>(Q.b + (size_t)min(max(yb - 2 + 2 * r, 0), height - 1) * pitch + lo)[tid + FG_T];
-#pragma unroll
-            for (int r = 0; r < FG_NM; r++)
-                vm[r][1] = reinterpret_cast<const uint32_t *>(Q.a + (size_t)min(max(yb - 3 + 2 * r, 0), height - 1) * pitch + lo)[tid + FG_T];
+            const uint32_t *row = reinterpret_cast<const uint32_t *>(Q.a + (size_t)min(max(yb - 3 + 2 * r, 0), height - 1) * pitch + lo);
+            vm[r][0] = row[i0]; vm[r][1] = row[i1];
         }
         if (h0)
         {
@@ -2300,22 +2314,22 @@ __global__ __launch_bounds__(FG_T) void k_fill_gaps_b(P3 P)
     for (int r = 0; r < FG_R; r++)
     {
         const int y = yb + 2 * r;
-        if (x < width && y < height && rebuilt(y))                              // (rows that are copied have their dword in vcopy)
+        if (y < height && rebuilt(y))                                           // (rows that are copied have their dword in vcopy)
         {
-            const int c = 4 * tid + FG_HALO;
-            const uint32_t cw = *reinterpret_cast<const uint32_t *>(&s_d[r + 1][c]);
-            const uint32_t mcw = *reinterpret_cast<const uint32_t *>(&s_m[r + 1][c]), mnw = *reinterpret_cast<const uint32_t *>(&s_m[r + 2][c]);
-            *reinterpret_cast<uint32_t *>(&s_out[r][4 * tid]) = cw;
-            // the gap pixels among the four (direction unknown, inside the mask: :1046-1050) as byte arithmetic, one atomic
-            // for all of them
-            const uint32_t gap = ((ff_bytes(cw) & (ff_bytes(mcw) | ff_bytes(mnw))) >> 7) & mf_bytes_in(x, 1, width - 1);
-            if (gap)
+            uint32_t gap = 0u;
+            if (x < width)
             {
-                int at = atomicAdd(&s_count, __popc(gap));
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                    if ((gap >> (8 * k)) & 1u) s_list[at++] = (uint16_t)((r << 12) | (4 * tid + k));
+                const int c = 4 * tid + FG_HALO;
+                const uint32_t cw = *reinterpret_cast<const uint32_t *>(&s_d[r + 1][c]);
+                const uint32_t mcw = *reinterpret_cast<const uint32_t *>(&s_m[r + 1][c]), mnw = *reinterpret_cast<const uint32_t *>(&s_m[r + 2][c]);
+                *reinterpret_cast<uint32_t *>(&s_out[r][4 * tid]) = cw;
+                // the gap pixels among the four (direction unknown, inside the mask: :1046-1050) as byte arithmetic
+                gap = ((ff_bytes(cw) & (ff_bytes(mcw) | ff_bytes(mnw))) >> 7) & mf_bytes_in(x, 1, width - 1);
             }
+            int at = wave_list_slots(&s_count, (unsigned)__popc(gap));
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if ((gap >> (8 * k)) & 1u) s_list[at++] = (uint16_t)((r << 12) | (4 * tid + k));
         }
     }
     __syncthreads();
@@ -2331,16 +2345,16 @@ __global__ __launch_bounds__(FG_T) void k_fill_gaps_b(P3 P)
         // once per staged row, then the four combinations per rebuilt row as word arithmetic.
         for (int k = 0; k < (FG_LW + FG_T - 1) / FG_T; k++)
         {
-            // (no branch: the bytes are read whatever they hold - from the last staged column for the lanes past it, whose
-            // bits are then cleared)
+            // (no branch: the bytes are read whatever they hold - from the last staged column for the lanes past it.  The
+            // bits of columns past the staged span are never read: every scan and any_in below stays below `staged`, so
+            // they are left as they come, and each ballot is one compare - masking them cost a scalar AND per ballot and
+            // per combination, the larger part of the kernel's scalar instructions)
             const unsigned col = tid + FG_T * k, cc = min(col, staged - 1u);
-            const bool in = col < staged;
             uint64_t nd[FG_ND], pm[FG_NM];
     #pragma unroll
-            for (int r = 0; r < FG_ND; r++) nd[r] = __ballot(in & (s_d[r][cc] != PEAK));       // direction known
+            for (int r = 0; r < FG_ND; r++) nd[r] = __ballot(s_d[r][cc] != PEAK);       // direction known
     #pragma unroll
-            for (int r = 0; r < FG_NM; r++) pm[r] = __ballot(in & (s_m[r][cc] == PEAK));       // on the mask
-            const uint64_t inw = __ballot(in);
+            for (int r = 0; r < FG_NM; r++) pm[r] = __ballot(s_m[r][cc] == PEAK);       // on the mask
             if ((tid & 63) == 0 && (col >> 6) < (unsigned)FG_WORDS)
             {
     #pragma unroll
@@ -2348,9 +2362,9 @@ __global__ __launch_bounds__(FG_T) void k_fill_gaps_b(P3 P)
                 {
                     const uint64_t mc = pm[r + 1], mn = pm[r + 2];
                     s_np[r][col >> 6] = nd[r + 1];
-                    s_stop[r][col >> 6] = nd[r + 1] | (inw & ~mc & ~mn);
-                    s_bt[r][col >> 6] = inw & (~nd[r] | (~pm[r] & ~mc));
-                    s_bb[r][col >> 6] = inw & (~nd[r + 2] | (~mn & ~pm[r + 3]));
+                    s_stop[r][col >> 6] = nd[r + 1] | ~(mc | mn);
+                    s_bt[r][col >> 6] = ~(nd[r] & (pm[r] | mc));
+                    s_bb[r][col >> 6] = ~(nd[r + 2] & (mn | pm[r + 3]));
                 }
             }
         }
@@ -2465,18 +2479,26 @@ __global__ __launch_bounds__(FG_T) void k_fill_gaps_b(P3 P)
         }
     }
     __syncthreads();
-    if (x < width)
+    // (the row loop inside the lane's one test of the row's end, not that test inside the loop: a divergent branch per
+    // row cost the scalar unit as much as the rows' stores cost the vector unit)
+    auto out_word = [&](int i) -> uint32_t {
+        const int y = ya + i;
+        const bool work = (((y - y0) & 1) == 0) && rebuilt(y);
+        return work ? *reinterpret_cast<const uint32_t *>(&s_out[(i - (y0 & 1)) >> 1][4 * tid]) : vcopy[i];
+    };
+    if (x + 3 < width)
     {
 #pragma unroll
-        for (int i = 0; i < 2 * FG_R; i++)
+        for (int i = 0; i < 2 * FG_R && ya + i < height; i++)
+            *reinterpret_cast<uint32_t *>(Q.c + (size_t)(ya + i) * pitch + x) = out_word(i);
+    }
+    else if (x < width)
+    {
+        for (int i = 0; i < 2 * FG_R && ya + i < height; i++)
         {
-            const int y = ya + i;
-            if (y >= height) break;
-            const bool work = (((y - y0) & 1) == 0) && rebuilt(y);
-            const uint32_t v = work ? *reinterpret_cast<const uint32_t *>(&s_out[(i - (y0 & 1)) >> 1][4 * tid]) : vcopy[i];
-            uint8_t *o = Q.c + (size_t)y * pitch + x;
-            if (x + 3 < width) *reinterpret_cast<uint32_t *>(o) = v;
-            else for (int k = 0; k < 4 && x + k < width; k++) o[k] = (uint8_t)(v >> (8 * k));
+            const uint32_t v = out_word(i);
+            uint8_t *o = Q.c + (size_t)(ya + i) * pitch + x;
+            for (int k = 0; k < 4 && x + k < width; k++) o[k] = (uint8_t)(v >> (8 * k));
         }
     }
 }
@@ -2786,6 +2808,7 @@ __global__ __launch_bounds__(256) void k_lattice_cand_q(P3 P, uint32_t *__restri
     {
         // every pixel's word, the variance and the edge test included, four pixels per thread out of the rows' dwords
         const int x = x0 + 4 * t;
+        uint32_t queue = 0;
         if (x < width)
         {
             const uint32_t *T = reinterpret_cast<const uint32_t *>(s_rows[0]) + LC_HALO / 4 + t;   // T[0]: columns x .. x + 3
@@ -2795,7 +2818,7 @@ __global__ __launch_bounds__(256) void k_lattice_cand_q(P3 P, uint32_t *__restri
             const uint32_t d4 = D[0], dn = D[1] & 0xffu;
             uint32_t w[4], base[4];
             int lim[4];
-            uint32_t queue = 0, searching = 0;
+            uint32_t searching = 0;
 #pragma unroll
             for (int k = 0; k < 4; k++)
             {
@@ -2825,14 +2848,11 @@ __global__ __launch_bounds__(256) void k_lattice_cand_q(P3 P, uint32_t *__restri
                 }
             }
             *reinterpret_cast<uint4 *>(&s_cand[4 * t]) = make_uint4(w[0], w[1], w[2], w[3]);
-            if (queue)
-            {
-                int at = atomicAdd(&s_count[1], __popc(queue));
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                    if ((queue >> k) & 1u) s_list[1][at++] = (uint16_t)(4 * t + k);
-            }
         }
+        int at = wave_list_slots(&s_count[1], (unsigned)__popc(queue));
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if ((queue >> k) & 1u) s_list[1][at++] = (uint16_t)(4 * t + k);
     }
     __syncthreads();
     // a stage's lanes all run the same code: the 5-step search, then the short search
@@ -2865,47 +2885,59 @@ __global__ __launch_bounds__(256) void k_lattice_cand_q(P3 P, uint32_t *__restri
     }
 }
 
-// grid.y = processed rows (+1 for the border-row copy); one workgroup of LR_T threads per row, FOUR pixels per thread
-// and pass over the row (LR_PX pixels).  Which outcome a pixel takes depends only on which outcome its left neighbour
-// took (that decides the value left standing at x-1, :1194), so every pixel is a 2-state map (bit s = its outcome when
-// the left pixel took outcome s).  A thread composes the maps of its four pixels, the threads' maps are composed by a
-// prefix scan inside each wave, the wave maps are chained by one thread, and the state entering the next LR_PX pixels
-// is the outcome of the last one.  Candidates come in as one 16-byte load, the direction row as a dword, both rows
-// leave as dwords (one pixel per thread, byte loads and stores: 144 us per 16 fields).
-constexpr int LR_T = 256, LR_PX = 4 * LR_T;
+// grid.y = (processed rows + 1 for the border-row copy) / LR_ROWS; one WAVE per row, LR_ROWS rows per workgroup, FOUR
+// pixels per lane and pass over the row (LR_PX pixels).  Which outcome a pixel takes depends only on which outcome its
+// left neighbour took (that decides the value left standing at x-1, :1194), so every pixel is a 2-state map (bit s = its
+// outcome when the left pixel took outcome s).  A lane composes the maps of its four pixels, the lanes' maps are composed
+// by a prefix scan inside the wave, and the state entering the next LR_PX pixels is the last lane's map applied to the
+// state that entered this pass - a register, no barrier and no chaining of waves through LDS.  Candidates come in as one
+// 16-byte load, the direction row as a dword, both rows leave as dwords.  (A workgroup per row, its four waves chained
+// through LDS and two barriers per 1024-pixel pass: 43.3 us per 16 fields, 0.62 of its issue floor.)
+constexpr int LR_T = 256, LR_ROWS = LR_T / 64, LR_PX = 4 * 64;
 
-// later o earlier: the map that applies `earlier` first (the thread / wave / pass composition against the pixel-by-pixel
-// walk: tests/test_eedi2_identities_cpu.py::test_lattice_resolve_scan_equals_the_serial_walk)
+// later o earlier: the map that applies `earlier` first (the lane / pass composition against the pixel-by-pixel
+// walk: tests/test_eedi2_identities_cpu.py::test_lattice_resolve_scan_equals_the_serial_walk,
+// tests/test_eedi2_resolve_wave_cpu.py)
 __device__ __forceinline__ unsigned lr_compose(unsigned later, unsigned earlier)
 {
     return ((later >> (earlier & 1u)) & 1u) | (((later >> ((earlier >> 1) & 1u)) & 1u) << 1);
 }
 
+// the value of the lane to the left (wave_shr:1); lane 0 gets `first`.  Call it where every lane is active.
+__device__ __forceinline__ uint32_t lr_shr1(uint32_t v, uint32_t first)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)first, (int)v, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+}
+
 __global__ __launch_bounds__(LR_T) void k_lattice_resolve(P3 P, const uint32_t *__restrict__ cand, int cand_pitch,
                                                           int cand_plane_stride)
 {
-    __shared__ uint8_t s_wmap[LR_T / 64];        // composed map of each wave
-    __shared__ uint8_t s_win[LR_T / 64];         // resolved state entering each wave
-    __shared__ uint8_t s_lim[36];                // eedi2_limlut in LDS: four look-ups per thread and pass
-    __shared__ int s_carry;                      // outcome of the last pixel of the previous pass
+    __shared__ uint8_t s_lim[LIM_PAD];           // eedi2_limlut in LDS: four look-ups per lane and pass
     FIELD_PLANE(P);
     const int field = tff;
     cand += (size_t)fld * (P.fstride / sizeof(uint32_t));
     const int pitch = P.pitch[pl], width = P.width[pl], height = P.height[pl];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int t = threadIdx.x, lane = t & 63;
+    const int ri = (int)blockIdx.y * LR_ROWS + __builtin_amdgcn_readfirstlane(t >> 6);   // this wave's row
     const int nrows = (height - (2 - field)) / 2;                // rows y0, y0+2, ... < height-1
+    lim_fill(s_lim, t);
+    __syncthreads();                                             // the only barrier: every wave of the workgroup passes it
     uint8_t *dst = Q.b;
-    if ((int)blockIdx.y >= nrows)
+    if (ri >= nrows)
     {
-        if ((int)blockIdx.y == nrows)                              // the one-row blit (:1162-1179)
-            for (int xx = t; xx < width; xx += LR_T)
+        if (ri == nrows)                                           // the one-row blit (:1162-1179)
+        {
+            uint8_t *o = field == 1 ? dst + (size_t)(height - 1) * pitch : dst;
+            const uint8_t *s = field == 1 ? dst + (size_t)(height - 2) * pitch : dst + pitch;
+            for (int x = 4 * lane; x < width; x += LR_PX)
             {
-                if (field == 1) dst[(size_t)(height - 1) * pitch + xx] = dst[(size_t)(height - 2) * pitch + xx];
-                else            dst[xx] = dst[pitch + xx];
+                if (x + 3 < width) *reinterpret_cast<uint32_t *>(o + x) = *reinterpret_cast<const uint32_t *>(s + x);
+                else for (int k = 0; k < 4 && x + k < width; k++) o[x + k] = s[x + k];
             }
+        }
         return;
     }
-    const int y = (2 - field) + 2 * blockIdx.y;
+    const int y = (2 - field) + 2 * ri;
     uint8_t *mid = dst + (size_t)y * pitch;
     uint8_t *dm = Q.a + (size_t)y * pitch;
     if (maskless)
@@ -2914,7 +2946,7 @@ __global__ __launch_bounds__(LR_T) void k_lattice_resolve(P3 P, const uint32_t *
         // above and below it (:1192-1197), the direction row stays as it is.  Four pixels per operation:
         // (a + b + 1) >> 1 = (a | b) - (((a ^ b) >> 1) & 0x7f) per byte
         const uint8_t *top = mid - pitch, *bot = mid + pitch;
-        for (int x = 4 * t; x < width; x += 4 * LR_T)
+        for (int x = 4 * lane; x < width; x += LR_PX)
         {
             const uint32_t a = *reinterpret_cast<const uint32_t *>(top + x), b = *reinterpret_cast<const uint32_t *>(bot + x);
             const uint32_t v = (a | b) - (((a ^ b) >> 1) & 0x7f7f7f7fu);
@@ -2923,18 +2955,17 @@ __global__ __launch_bounds__(LR_T) void k_lattice_resolve(P3 P, const uint32_t *
         }
         return;
     }
-    const uint32_t *cr = cand + (size_t)pl * cand_plane_stride + (size_t)blockIdx.y * cand_pitch;
-    const bool cr16 = ((reinterpret_cast<uintptr_t>(cr)) & 15u) == 0;      // block-uniform: the row of candidates starts on 16 bytes
+    const uint32_t *cr = cand + (size_t)pl * cand_plane_stride + (size_t)ri * cand_pitch;
+    const bool cr16 = ((reinterpret_cast<uintptr_t>(cr)) & 15u) == 0;      // wave-uniform: the row of candidates starts on 16 bytes
     // value standing at dm[x-1] for x == 0: memory just before the row, never written by this pass
     const int before_row = dm[-1];
-    if (t == 0) s_carry = 0;
-    if (t < 33) s_lim[t] = c_limlut[t];
-    __syncthreads();
+    unsigned carry = 0u;                                         // outcome of pixel x0 - 1 (irrelevant for x0 == 0)
+    uint32_t cprev = 0u;                                         // candidate word of pixel x0 - 1
 
     for (int x0 = 0; x0 < width; x0 += LR_PX)
     {
-        const int x = x0 + 4 * t;
-        const int nlive = min(max(width - x, 0), 4);             // pixels of this thread inside the row
+        const int x = x0 + 4 * lane;
+        const int nlive = min(max(width - x, 0), 4);             // pixels of this lane inside the row
         uint32_t c[4] = { 0u, 0u, 0u, 0u }, d4 = 0u;
         if (nlive == 4 && cr16)
         {
@@ -2944,20 +2975,12 @@ __global__ __launch_bounds__(LR_T) void k_lattice_resolve(P3 P, const uint32_t *
         else
             for (int k = 0; k < nlive; k++) c[k] = cr[x + k];
         if (nlive) d4 = *reinterpret_cast<const uint32_t *>(dm + x);     // the row's pitch is a multiple of 4: the dword is inside it
-        // what the last pixel of the thread to the left can leave behind (pa: outcome A, pb: outcome B); the first lane
-        // of a wave reads that pixel's candidate word; nothing has been written to this row yet
-        const uint32_t cl3 = c[3];
-        int pa = __shfl_up((cl3 >> 24) & 1u ? PEAK : NEUTRAL, 1, 64), pb = __shfl_up((int)((cl3 >> 16) & 0xffu), 1, 64);
-        if (lane == 0 && nlive)
-        {
-            if (x == 0) { pa = before_row; pb = before_row; }
-            else
-            {
-                const uint32_t cl = cr[x - 1];
-                pa = ((cl >> 24) & 1u) ? PEAK : NEUTRAL;
-                pb = (int)((cl >> 16) & 0xffu);
-            }
-        }
+        // what the last pixel of the lane to the left can leave behind (pa: outcome A, pb: outcome B); the first lane
+        // takes the last pixel of the previous pass; nothing has been written to this row yet
+        const uint32_t cl = lr_shr1(c[3], cprev);                   // (with every lane active: DPP reads a lane that EXEC
+                                                                     // leaves out as if it were outside the wave)
+        int pa = ((cl >> 24) & 1u) ? PEAK : NEUTRAL, pb = (int)((cl >> 16) & 0xffu);
+        if (lane == 0 && x0 == 0) { pa = before_row; pb = before_row; }
         unsigned m[4], pm[4];
 #pragma unroll
         for (int k = 0; k < 4; k++)
@@ -2973,37 +2996,25 @@ __global__ __launch_bounds__(LR_T) void k_lattice_resolve(P3 P, const uint32_t *
                 const unsigned ob2 = (right && iabs(d - pb) > lim) ? 0u : 1u;
                 m[k] = oa | (ob2 << 1);
             }
-            pm[k] = k == 0 ? m[0] : lr_compose(m[k], pm[k - 1]);    // the thread's pixels 0..k, earlier first
+            pm[k] = k == 0 ? m[0] : lr_compose(m[k], pm[k - 1]);    // the lane's pixels 0..k, earlier first
             pa = always_a ? PEAK : NEUTRAL;                          // what pixel k leaves for k + 1
             pb = (int)((ck >> 16) & 0xffu);
         }
-        // inclusive prefix composition of the threads' maps inside the wave (earlier map first)
+        // inclusive prefix composition of the lanes' maps inside the wave (earlier map first), on DPP moves: shifts
+        // inside each row of 16 lanes, then lane 15 / lane 31 broadcast to the rows after them.  A lane whose source
+        // lies outside the wave or the row keeps `old`, the identity map 2, and lr_compose(tm, 2) == tm.
         unsigned tm = pm[3];
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1)
-        {
-            const unsigned e = __shfl_up(tm, off, 64);
-            if (lane >= off) tm = lr_compose(tm, e);
-        }
-        if (lane == 63) s_wmap[wave] = (uint8_t)tm;
-        unsigned before = __shfl_up(tm, 1, 64);                      // everything left of this thread inside the wave
-        if (lane == 0) before = 2u;                                  // the identity map
-        __syncthreads();
-        if (t == 0)
-        {
-            unsigned state = (unsigned)s_carry;                      // outcome of pixel x0 - 1 (irrelevant for x0 == 0)
-            for (int w = 0; w < LR_T / 64; w++)
-            {
-                s_win[w] = (uint8_t)state;
-                state = (s_wmap[w] >> state) & 1u;
-            }
-        }
-        __syncthreads();
-        const unsigned sin = (before >> s_win[wave]) & 1u;           // outcome of the pixel left of this thread's first
+        tm = lr_compose(tm, (unsigned)__builtin_amdgcn_update_dpp(2, (int)tm, 0x111 /* row_shr:1 */, 0xf, 0xf, false));
+        tm = lr_compose(tm, (unsigned)__builtin_amdgcn_update_dpp(2, (int)tm, 0x112 /* row_shr:2 */, 0xf, 0xf, false));
+        tm = lr_compose(tm, (unsigned)__builtin_amdgcn_update_dpp(2, (int)tm, 0x114 /* row_shr:4 */, 0xf, 0xf, false));
+        tm = lr_compose(tm, (unsigned)__builtin_amdgcn_update_dpp(2, (int)tm, 0x118 /* row_shr:8 */, 0xf, 0xf, false));
+        tm = lr_compose(tm, (unsigned)__builtin_amdgcn_update_dpp(2, (int)tm, 0x142 /* row_bcast:15 */, 0xa, 0xf, false));
+        tm = lr_compose(tm, (unsigned)__builtin_amdgcn_update_dpp(2, (int)tm, 0x143 /* row_bcast:31 */, 0xc, 0xf, false));
+        const unsigned before = lr_shr1(tm, 2u);                     // everything left of this lane inside the pass (lane 0: identity)
+        const unsigned sin = (before >> carry) & 1u;                 // outcome of the pixel left of this lane's first
         if (nlive)
         {
             uint32_t mid4 = 0u, dm4 = 0u;
-            unsigned last = 0u;
 #pragma unroll
             for (int k = 0; k < 4; k++)
             {
@@ -3013,7 +3024,6 @@ __global__ __launch_bounds__(LR_T) void k_lattice_resolve(P3 P, const uint32_t *
                 const uint32_t nd = outcome ? (ck >> 16) & 0xffu : (((ck >> 24) & 1u) ? (uint32_t)PEAK : (uint32_t)NEUTRAL);
                 mid4 |= val << (8 * k);
                 dm4 |= nd << (8 * k);
-                if (k == nlive - 1) last = outcome;
             }
             if (nlive == 4)
             {
@@ -3022,9 +3032,10 @@ __global__ __launch_bounds__(LR_T) void k_lattice_resolve(P3 P, const uint32_t *
             }
             else
                 for (int k = 0; k < nlive; k++) { mid[x + k] = (uint8_t)(mid4 >> (8 * k)); dm[x + k] = (uint8_t)(dm4 >> (8 * k)); }
-            if (x + nlive == min(x0 + LR_PX, width)) s_carry = (int)last;
         }
-        __syncthreads();
+        // the state entering the next pass; a pass that is not the last one is full, so lane 63 holds its last pixel
+        carry = (__builtin_amdgcn_readlane(tm, 63) >> carry) & 1u;
+        cprev = __builtin_amdgcn_readlane(c[3], 63);
     }
 }
 
@@ -3733,7 +3744,7 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
         const int nt = par_.noise_threshold;
         HBHIP_LAUNCH_ON(lc, st, "eedi2_lattice_candidates", k_lattice_cand_q, dim3(hbhip_grid_x((dst2p.width[0] + LQ_W - 1) / LQ_W), nrows, gz),
                      dim3(256), 0, P, cand, cand_pitch_, cand_plane_stride_, (nt * 4) & 0xff, (nt * 7) & 0xff, (nt * 8) & 0xff, nt);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_lattice_resolve", k_lattice_resolve, dim3(1, nrows + 1, gz), dim3(LR_T), 0, P,
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_lattice_resolve", k_lattice_resolve, dim3(1, (nrows + 1 + LR_ROWS - 1) / LR_ROWS, gz), dim3(LR_T), 0, P,
                      (const uint32_t *)cand, cand_pitch_, cand_plane_stride_);
     }
     if (swapped)
