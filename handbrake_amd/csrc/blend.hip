@@ -351,6 +351,7 @@ extern "C" int hbhip_blend_apply(hbhip_blend *b, const hbhip_host_frame *frame)
     rc = hbhip_frame_describe(b->staging, &d, nullptr, nullptr);
     if (rc != HBHIP_OK) return rc;
     rc = hbhip_blend_apply_dev(b, &d);
+    if (rc == HBHIP_OK) rc = hbhip_frame_mark_ready(b->staging);        // the download waits for the compositor
     if (rc != HBHIP_OK) return rc;
     return hbhip_frame_download(b->staging, frame);
 }

@@ -91,28 +91,49 @@ void hbhip_ctx::close_mark()
     if (m) m->record_now();
 }
 
-void hbhip_pic_mark_idle(hbhip_ctx *ctx, DevPicture *p)
+// ctx's stream as it stands: its open mark.  No event to be had: the stream is waited out here and there is nothing to
+// wait for (null).
+static std::shared_ptr<IdleMark> stream_now(hbhip_ctx *ctx)
 {
-    if (!ctx || !p) return;
-    p->idle = ctx->mark();
-    // no event to be had: the next user could not wait for this one's work, so it is waited out here
-    if (!p->idle) (void)hipStreamSynchronize(ctx->stream);
+    std::shared_ptr<IdleMark> m = ctx->mark();
+    if (!m) (void)hipStreamSynchronize(ctx->stream);
+    return m;
 }
 
-bool hbhip_pic_idle_done(DevPicture *p)
+static bool mark_passed(const std::shared_ptr<IdleMark> &m)
 {
-    if (!p || !p->idle) return true;
-    p->idle->record_now();
-    if (hipEventQuery(p->idle->ev) == hipSuccess) return true;
+    if (!m) return true;
+    m->record_now();
+    if (hipEventQuery(m->ev) == hipSuccess) return true;
     (void)hipGetLastError();                           // hipErrorNotReady
     return false;
 }
 
+// `stream` behind the point `m` (nothing to do without one, or on m's own stream): every wait on a mark of a picture or a
+// frame goes through here
+static hipError_t wait_mark(hipStream_t stream, const std::shared_ptr<IdleMark> &m)
+{
+    if (!m || m->stream == stream) return hipSuccess;
+    m->record_now();
+    return hipStreamWaitEvent(stream, m->ev, 0);
+}
+
+void hbhip_pic_mark_idle(hbhip_ctx *ctx, DevPicture *p)
+{
+    if (ctx && p) p->idle = stream_now(ctx);
+}
+
+bool hbhip_pic_idle_done(DevPicture *p)
+{
+    return !p || (mark_passed(p->idle) && (!p->frame || mark_passed(p->frame->reader_idle)));
+}
+
 hipError_t hbhip_pic_wait_idle(hipStream_t stream, DevPicture *p)
 {
-    if (!p || !p->idle || p->idle->stream == stream) return hipSuccess;
-    p->idle->record_now();
-    return hipStreamWaitEvent(stream, p->idle->ev, 0);
+    if (!p) return hipSuccess;
+    hipError_t e = wait_mark(stream, p->idle);
+    if (e == hipSuccess && p->frame) e = wait_mark(stream, p->frame->reader_idle);
+    return e;
 }
 
 int hbhip_ctx::prof_name(const char *name)
@@ -747,6 +768,44 @@ int hbhip_dev_download(hbhip_ctx *ctx, void *dst, const void *src, size_t bytes)
 }
 
 // ---- device-resident frames -----------------------------------------------------
+// How frames are ordered.  A job may run its filters on more than one context of a GPU (hbhip_host_ctx_for_role), so a
+// frame may be written and read on several streams.  The rule, kept by the helpers below - the only code that touches
+// `ready`, `complete`, `last_user` and `owner_used`, under the owner's frame_lock:
+//  * The contents are complete behind the ready mark; without one, at once after a synchronous upload, else behind what
+//    the current user - the context that last took the frame through hbhip_frame_use_on, or the owner - has queued so far.
+//    A reader waits for that point and nothing else: a second stream is not to wait for what the first queued since.
+//  * A context that reads or writes the frame takes it through hbhip_frame_use_on and becomes its current user, behind
+//    the previous user's stream as it stands if that was another foreign context.  A writer marks the contents ready on
+//    the current user's stream.
+//  * The last reference gone, the frame goes idle behind its last foreign user's stream and behind its owner's (unless
+//    only foreign contexts took it), as they stand then; it is filled again behind both marks.
+static hbhip_ctx *current_user(const hbhip_frame *fr) { return fr->last_user ? fr->last_user : fr->ctx; }
+
+static hipError_t order_after_contents(hbhip_frame *fr, hipStream_t stream)
+{
+    if (fr->ready) return wait_mark(stream, fr->ready);
+    hbhip_ctx *user = current_user(fr);
+    return fr->complete || user->stream == stream ? hipSuccess : wait_mark(stream, stream_now(user));
+}
+
+static hipError_t note_user(hbhip_frame *fr, hbhip_ctx *ctx)
+{
+    hbhip_ctx *prev = fr->last_user;
+    const hipError_t e = prev && prev != fr->ctx && prev != ctx ? wait_mark(ctx->stream, stream_now(prev)) : hipSuccess;
+    if (e == hipSuccess) { fr->last_user = ctx; fr->owner_used |= ctx == fr->ctx; }
+    return e;
+}
+
+// null `ready`: a copy that has finished filled the frame
+static void set_contents(hbhip_frame *fr, std::shared_ptr<IdleMark> ready) { fr->complete = !ready; fr->ready = std::move(ready); }
+
+static void frame_idle(hbhip_frame *fr)
+{
+    hbhip_ctx *foreign = fr->last_user != fr->ctx ? fr->last_user : nullptr;
+    fr->pic.idle = !foreign || fr->owner_used ? stream_now(fr->ctx) : nullptr;
+    fr->reader_idle = foreign ? stream_now(foreign) : nullptr;
+}
+
 hbhip_ctx *hbhip_frame_context(hbhip_frame *fr)
 {
     return fr ? fr->ctx : nullptr;
@@ -778,14 +837,12 @@ int hbhip_frame_alloc(hbhip_ctx *ctx, int width, int height, int depth, int lcw,
             hbhip_frame *fr = ctx->frame_pool[pick];
             ctx->frame_pool.erase(ctx->frame_pool.begin() + pick);
             fr->refs = 1;
-            fr->ready.reset();
-            fr->last_user = nullptr;
-            fr->complete = false;
+            fr->ready.reset(); fr->last_user = nullptr; fr->complete = fr->owner_used = false;
             fr->pic.frame = fr;
             fr->pic.refs = 0; fr->pic.flags = 0; fr->pic.combed = 0; fr->pic.aux = 0; fr->pic.tag = 0;
-            // taken although its last reader may still be running (the pool is at its bound): whoever fills it on this
-            // context's stream does so behind that reader, which may sit on another context's stream (hbhip_frame_use_on)
-            if (fr->pic.idle && fr->pic.idle->stream != ctx->stream) (void)hbhip_pic_wait_idle(ctx->stream, &fr->pic);
+            // taken although its users may still be running (the pool is at its bound): whoever fills it on this
+            // context's stream does so behind them
+            (void)hbhip_pic_wait_idle(ctx->stream, &fr->pic);
             *out = fr;
             return HBHIP_OK;
         }
@@ -837,52 +894,18 @@ void hbhip_frame_release(hbhip_frame *fr)
     std::lock_guard<std::mutex> lk(fr->ctx->frame_lock);
     if (--fr->refs > 0) return;
     (void)hipSetDevice(fr->ctx->device);
-    // its users are all queued by now: on the context's stream, or on the stream of the context that read it last
-    hbhip_pic_mark_idle(fr->last_user ? fr->last_user : fr->ctx, &fr->pic);
-    fr->ctx->frame_pool.push_back(fr);        // reuse is ordered by that event (uploads) or by the stream itself
+    frame_idle(fr);                           // its users are all queued by now
+    fr->ctx->frame_pool.push_back(fr);
 }
 
-// A filter on another context of the same GPU is about to queue work that reads the frame (a job whose filters run on
-// more than one HIP stream: libhb/hbhip_registry.c, hbhip_host_ctx_for_role).  Orders `ctx`'s stream behind the frame's
-// producer - its ready mark, nothing else of the owner's stream: the point of a second stream is not to wait for what
-// the first has queued since - and notes `ctx` as the stream the frame goes idle behind.  A frame that a second foreign
-// context (or its owner again) reads after the first is ordered behind that first reader's stream as it stands, so
-// that one idle mark still covers every reader.  No-op on the owner's context while nobody else has read the frame.
 int hbhip_frame_use_on(hbhip_frame *fr, hbhip_ctx *ctx)
 {
     if (!fr || !ctx || ctx->device != fr->ctx->device) return HBHIP_ERR_ARG;
-    std::lock_guard<std::mutex> lk(fr->ctx->frame_lock);
     (void)hipSetDevice(ctx->device);
-    bool waited_ready = false;
-    if (fr->ready && fr->ready->stream != ctx->stream)
-    {
-        // the producer sits on another stream: the owner's (a foreign reader), or the upload stream (every reader, the
-        // owner's context included: hbhip_frame_upload_async)
-        fr->ready->record_now();
-        const hipError_t e = hipStreamWaitEvent(ctx->stream, fr->ready->ev, 0);
-        if (e != hipSuccess) return ctx->fail(e, "use_on: order behind the frame's producer");
-        waited_ready = true;
-    }
-    hbhip_ctx *prev = fr->last_user ? fr->last_user : fr->ctx;
-    if (prev == ctx) return HBHIP_OK;
-    auto behind = [&](hbhip_ctx *of) -> int {          // ctx->stream behind everything queued on of->stream so far
-        hipEvent_t ev = of->sync_ev_get();
-        if (!ev) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(use_on)");
-        hipError_t e = hipEventRecord(ev, of->stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ev, 0);
-        of->sync_ev_put(ev);                              // (the wait holds the event's state as recorded here)
-        return e == hipSuccess ? HBHIP_OK : ctx->fail(e, "use_on: order behind the frame's earlier users");
-    };
-    int rc = HBHIP_OK;
-    if (fr->last_user == nullptr || fr->last_user == fr->ctx)
-    {
-        // (the owner as the last user: it has written the frame again - the compositor - and marked it ready behind that)
-        if (!waited_ready && !fr->ready && !fr->complete) rc = behind(fr->ctx);     // no mark to go by: the owner's stream as it stands
-    }
-    else
-        rc = behind(prev);
-    if (rc == HBHIP_OK) fr->last_user = ctx;
-    return rc;
+    std::lock_guard<std::mutex> lk(fr->ctx->frame_lock);
+    hipError_t e = order_after_contents(fr, ctx->stream);
+    if (e == hipSuccess) e = note_user(fr, ctx);
+    return e == hipSuccess ? HBHIP_OK : ctx->fail(e, "use_on: order behind the frame's contents and earlier users");
 }
 
 // The writability test of a device picture (fifo.c:624-639 asks av_buffer_is_writable the same thing): a holder that
@@ -892,6 +915,15 @@ int hbhip_frame_refs(hbhip_frame *fr)
     if (!fr) return 0;
     std::lock_guard<std::mutex> lk(fr->ctx->frame_lock);
     return fr->refs;
+}
+
+// that test and a reference more in one step: taken only by the frame's one holder
+static bool retain_if_sole(hbhip_frame *fr)
+{
+    std::lock_guard<std::mutex> lk(fr->ctx->frame_lock);
+    if (fr->refs != 1) return false;
+    fr->refs++;
+    return true;
 }
 
 int hbhip_frame_describe(hbhip_frame *fr, hbhip_dev_frame *out, int *width, int *height)
@@ -909,19 +941,14 @@ int hbhip_frame_describe(hbhip_frame *fr, hbhip_dev_frame *out, int *width, int 
 
 int hbhip_frame_copy(hbhip_frame *dst, hbhip_frame *src)
 {
-    if (!dst || !src || dst->ctx != src->ctx) return HBHIP_ERR_ARG;
+    if (!dst || !src) return HBHIP_ERR_ARG;
     if (dst->width != src->width || dst->height != src->height || dst->depth != src->depth ||
         dst->lcw != src->lcw || dst->lch != src->lch)
         return HBHIP_ERR_ARG;
-    (void)hipSetDevice(dst->ctx->device);
-    if (src->ready && src->ready->stream != dst->ctx->stream)              // (a frame whose upload is still in flight)
-    {
-        src->ready->record_now();
-        const hipError_t e = hipStreamWaitEvent(dst->ctx->stream, src->ready->ev, 0);
-        if (e != hipSuccess) return dst->ctx->fail(e, "frame_copy: order behind the source's producer");
-    }
+    const int rc = hbhip_frame_use_on(src, dst->ctx);            // the copy reads src on dst's stream
+    if (rc != HBHIP_OK) return rc;
     hbhip_dev_frame d;
-    for (int c = 0; c < 3; c++) { d.plane[c] = src->pic.plane[c]; d.stride[c] = src->pic.pitch[c]; }
+    hbhip_frame_describe(src, &d, nullptr, nullptr);
     return hbhip_copy_d2d_in(dst->ctx, &dst->pic, &d);
 }
 
@@ -930,14 +957,15 @@ int hbhip_frame_upload(hbhip_frame *fr, const hbhip_host_frame *src)
     if (!fr || !src) return HBHIP_ERR_ARG;
     (void)hipSetDevice(fr->ctx->device);
     const int rc = hbhip_copy_h2d(fr->ctx, &fr->pic, src);      // returns when the copy has finished
-    if (rc == HBHIP_OK && !fr->ready) fr->complete = true;
-    return rc;
+    if (rc != HBHIP_OK) return rc;
+    std::lock_guard<std::mutex> lk(fr->ctx->frame_lock);
+    set_contents(fr, nullptr);
+    return HBHIP_OK;
 }
 
 // The pipelined H2D (the upload adapter keeps a few in flight, as the download adapter does with its copies): the copy is
 // queued on the upload stream and the call returns; `src` must stay valid until hbhip_ctx_upload_done(token) says so.  The
-// frame's ready mark is the copy's event, so whoever reads the frame - on any context: hbhip_frame_use_on,
-// hbhip_frame_copy, a download - waits for the copy and for nothing else.
+// frame's ready mark is the copy's event.
 int hbhip_frame_upload_async(hbhip_frame *fr, const hbhip_host_frame *src, void **token)
 {
     if (!fr || !src || !token) return HBHIP_ERR_ARG;
@@ -963,8 +991,7 @@ int hbhip_frame_upload_async(hbhip_frame *fr, const hbhip_host_frame *src, void 
     }
     m->recorded = true;
     m->closed.store(true, std::memory_order_release);
-    fr->ready = m;
-    fr->complete = false;
+    { std::lock_guard<std::mutex> lk(ctx->frame_lock); set_contents(fr, std::move(m)); }
     *token = done;
     return HBHIP_OK;
 }
@@ -993,15 +1020,14 @@ int hbhip_frame_download(hbhip_frame *fr, const hbhip_host_frame *dst)
 int hbhip_frame_mark_ready(hbhip_frame *fr)
 {
     if (!fr) return HBHIP_ERR_ARG;
-    hbhip_ctx *ctx = fr->ctx;
-    (void)hipSetDevice(ctx->device);
-    fr->ready = ctx->mark();
-    if (!fr->ready) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(ready)");
+    (void)hipSetDevice(fr->ctx->device);
+    std::lock_guard<std::mutex> lk(fr->ctx->frame_lock);
+    set_contents(fr, stream_now(current_user(fr)));
     return HBHIP_OK;
 }
 
-// D2H on the download stream behind the frame's ready point (or, without one, behind everything queued on the
-// context's stream so far).  Several in flight keep the bus busy while the kernels of later frames run.
+// D2H on the download stream behind the frame's contents.  Several in flight keep the bus busy while the kernels of
+// later frames run.
 int hbhip_frame_download_async(hbhip_frame *fr, const hbhip_host_frame *dst, void **token)
 {
     if (!fr || !dst || !token) return HBHIP_ERR_ARG;
@@ -1014,18 +1040,10 @@ int hbhip_frame_download_async(hbhip_frame *fr, const hbhip_host_frame *dst, voi
     hipEvent_t ev = ctx->sync_ev_get();
     if (!ev) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(download)");
     auto fail = [&](hipError_t e, const char *what) { ctx->sync_ev_put(ev); return ctx->fail(e, what); };
-    hipError_t e;
-    if (fr->ready)
-    {
-        fr->ready->record_now();
-        e = hipStreamWaitEvent(ctx->down(), fr->ready->ev, 0);
-    }
-    else
-    {
-        e = hipEventRecord(ev, ctx->stream);           // the picture's producers are on ctx->stream, all queued by now
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->down(), ev, 0);
-    }
-    if (e != hipSuccess) return fail(e, "download: order behind the frame's producers");
+    std::unique_lock<std::mutex> lk(ctx->frame_lock);
+    hipError_t e = order_after_contents(fr, ctx->down());
+    lk.unlock();
+    if (e != hipSuccess) return fail(e, "download: order behind the frame's contents");
     if (same_layout(src, dst->plane, dst->stride))
     {
         e = hipMemcpyAsync(dst->plane[0], src->plane[0], layout_bytes(src), hipMemcpyDeviceToHost, ctx->down());
@@ -1115,13 +1133,12 @@ int hbhip_filter_push_frame(hbhip_filter *f, hbhip_frame *fr, int64_t tag)
     if (rc != HBHIP_OK) return rc;
     const PicGeometry &g = f->in_geo;
     const bool fits = fr->width == g.width && fr->height == g.height && fr->depth == g.depth && fr->lcw == g.log2_cw && fr->lch == g.log2_ch;
-    if (!f->frames_mode || !fits || hbhip_frame_refs(fr) != 1)
+    if (!f->frames_mode || !fits || !retain_if_sole(fr))
     {
         hbhip_dev_frame d;
         hbhip_frame_describe(fr, &d, nullptr, nullptr);
         return hbhip_filter_push_dev(f, &d, tag);
     }
-    hbhip_frame_retain(fr);
     DevPicture *pic = &fr->pic;
     pic->tag = tag;
     f->adopt_input(pic);

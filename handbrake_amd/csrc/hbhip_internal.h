@@ -189,7 +189,7 @@ struct DevPicture
     int      combed = 0;     // HB_COMB_* of the source buffer
     int      aux = 0;        // filter specific (decomb: which field of a bob pair)
     std::shared_ptr<IdleMark> idle;  // set when the picture goes back to its pool: everything that used it has been queued
-                                     // on idle->stream ahead of that mark (null: never used)
+                                     // on idle->stream ahead of that mark (null: never used; a frame's: see reader_idle)
     class PicturePool *owner = nullptr;   // the pool the picture goes back to (hbhip_pic_release)
     struct hbhip_frame *frame = nullptr;  // the picture IS a frame's (hbhip_frame::pic): it goes back through hbhip_frame_release
 };
@@ -201,14 +201,13 @@ struct hbhip_frame
     DevPicture  pic;
     int         width = 0, height = 0, depth = 8, lcw = 1, lch = 1;
     int         refs = 1;
-    // hbhip_frame_mark_ready: the point of the context's stream behind which the frame's contents are complete -
-    // a download waits for this point, not for whatever other filter threads have queued since
-    std::shared_ptr<IdleMark> ready;      // (shared by the frames marked between two launches, like `idle`)
-    // A job may run its filters on more than one context of a GPU (hbhip_frame_use_on): the context whose stream the
-    // frame's newest reader sits on, if that is not the owner's - the frame goes idle behind THAT stream's work
-    // (frame_lock of the owner)
-    hbhip_ctx  *last_user = nullptr;
-    bool        complete = false;         // filled by a copy that has finished (hbhip_frame_upload): no producer to wait for
+    // Ordering state.  The rule, and the only code that touches these four, is in hbhip_core.hip (order_after_contents
+    // and its neighbours), under the owner's frame_lock.
+    std::shared_ptr<IdleMark> ready;      // the contents are complete behind this point (shared like `idle`)
+    bool        complete = false;         // ... or at once: a copy that has finished filled the frame
+    hbhip_ctx  *last_user = nullptr;      // its current user: the context that last took it through hbhip_frame_use_on
+    bool        owner_used = false;       // the owner has taken it so
+    std::shared_ptr<IdleMark> reader_idle;   // the second idle mark (pic.idle: the owner's): its last foreign user's
 };
 
 // Geometry of a planar YUV picture.
@@ -263,7 +262,7 @@ private:
 void hbhip_frame_release(struct hbhip_frame *fr);
 inline void hbhip_pic_release(DevPicture *p, hbhip_ctx *last_user = nullptr)
 {
-    if (p && p->frame) hbhip_frame_release(p->frame);        // (its reader's stream is on record: hbhip_frame_use_on)
+    if (p && p->frame) hbhip_frame_release(p->frame);        // (its users' streams are on record: hbhip_frame_use_on)
     else if (p && p->owner) p->owner->release(p, last_user);
 }
 
@@ -273,9 +272,9 @@ int hbhip_copy_h2d(hbhip_ctx *ctx, DevPicture *dst, const hbhip_host_frame *src)
 int hbhip_copy_d2h(hbhip_ctx *ctx, const hbhip_host_frame *dst, const DevPicture *src);
 // attach `p` to the context's open mark (the picture is being recycled; its users are all queued on ctx->stream)
 void hbhip_pic_mark_idle(hbhip_ctx *ctx, DevPicture *p);
-// has everything that used `p` run? (records the mark if it still is open)
+// has everything that used `p` run? (records the mark if it still is open; a frame's picture: both of its marks)
 bool hbhip_pic_idle_done(DevPicture *p);
-// make `stream` wait for everything that used `p` (nothing to do when that was queued on `stream` itself)
+// make `stream` wait for everything that used `p` (nothing to do for what was queued on `stream` itself)
 hipError_t hbhip_pic_wait_idle(hipStream_t stream, DevPicture *p);
 // Device <-> device copies (2-D, any pitch on either side) on ctx->stream.
 int hbhip_copy_d2d_in(hbhip_ctx *ctx, DevPicture *dst, const hbhip_dev_frame *src);

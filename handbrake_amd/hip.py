@@ -112,6 +112,18 @@ def lib() -> C.CDLL:
         L.hbhip_chain_sync.argtypes = [C.c_void_p]
         L.hbhip_chain_destroy.argtypes = [C.c_void_p]
         L.hbhip_chain_destroy.restype = None
+        L.hbhip_frame_alloc.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)]
+        for fn in ("hbhip_frame_retain", "hbhip_frame_release"):
+            getattr(L, fn).argtypes = [C.c_void_p]
+            getattr(L, fn).restype = None
+        L.hbhip_frame_refs.argtypes = [C.c_void_p]
+        L.hbhip_frame_copy.argtypes = [C.c_void_p, C.c_void_p]
+        for fn in ("hbhip_frame_upload", "hbhip_frame_download"):
+            getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(HostFrame)]
+        L.hbhip_frame_upload_async.argtypes = [C.c_void_p, C.POINTER(HostFrame), C.POINTER(C.c_void_p)]
+        L.hbhip_ctx_upload_done.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.hbhip_filter_use_frames.argtypes = [C.c_void_p]
+        L.hbhip_decomb_push_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
         _lib = L
     return _lib
 
@@ -207,6 +219,56 @@ def dev_frame(tensors) -> DevFrame:
         f.plane[i] = t.data_ptr()
         f.stride[i] = t.stride(0) * t.element_size()
     return f
+
+
+class Frame:
+    """A device-resident frame (hbhip_frame_*) from a context's pool, holding one reference until close()."""
+
+    def __init__(self, ctx: Ctx, width, height, depth=8, lcw=1, lch=1):
+        h = C.c_void_p()
+        check(lib().hbhip_frame_alloc(ctx.h, width, height, depth, lcw, lch, C.byref(h)), ctx.h, "frame_alloc")
+        self.ctx, self.h, self.shape = ctx, h, (width, height, depth, lcw, lch)
+
+    def planes(self):
+        """zeroed host planes of the frame's geometry"""
+        import numpy as np
+        w, h, depth, lcw, lch = self.shape
+        dt = np.uint8 if depth == 8 else np.uint16
+        return [np.zeros((h, w), dt), np.zeros((-(-h >> lch), -(-w >> lcw)), dt), np.zeros((-(-h >> lch), -(-w >> lcw)), dt)]
+
+    def upload(self, planes):
+        check(lib().hbhip_frame_upload(self.h, C.byref(host_frame(planes))), self.ctx.h, "frame_upload")
+
+    def upload_async(self, planes):
+        """queued on the upload stream; `planes` must stay alive until upload_done(token) has returned"""
+        token = C.c_void_p()
+        check(lib().hbhip_frame_upload_async(self.h, C.byref(host_frame(planes)), C.byref(token)), self.ctx.h, "frame_upload_async")
+        return token
+
+    def upload_done(self, token):
+        check(lib().hbhip_ctx_upload_done(self.ctx.h, token, 1), self.ctx.h, "upload_done")
+
+    def download(self):
+        out = self.planes()
+        check(lib().hbhip_frame_download(self.h, C.byref(host_frame(out))), self.ctx.h, "frame_download")
+        return out
+
+    def copy_from(self, src: "Frame"):
+        check(lib().hbhip_frame_copy(self.h, src.h), self.ctx.h, "frame_copy")
+
+    def refs(self) -> int:
+        return lib().hbhip_frame_refs(self.h)
+
+    def retain(self):
+        lib().hbhip_frame_retain(self.h)
+
+    def release(self):
+        lib().hbhip_frame_release(self.h)
+
+    def close(self):
+        if self.h:
+            self.release()
+            self.h = None
 
 
 class DeviceFilter:
@@ -389,6 +451,13 @@ class DecombDevice:
         keep = [np.ascontiguousarray(p) for p in planes]
         fr = host_frame(keep)
         check(lib().hbhip_decomb_push(self.h, C.byref(fr), self.tag, flags, combed), self.ctx.h, "decomb_push")
+        self.tag += 1
+
+    def use_frames(self):
+        check(lib().hbhip_filter_use_frames(self.h), self.ctx.h, "use_frames")
+
+    def push_frame(self, frame: Frame, flags=0x0008, combed=2):
+        check(lib().hbhip_decomb_push_frame(self.h, frame.h, self.tag, flags, combed), self.ctx.h, "decomb_push_frame")
         self.tag += 1
 
     def pull(self):

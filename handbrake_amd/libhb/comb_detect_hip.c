@@ -178,14 +178,13 @@ static hb_buffer_t *overlay_copy(hb_filter_private_t *pv, hb_buffer_t *src)
         const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(pv->input.pix_fmt);
         hbhip_frame *dst = NULL;
         if (desc == NULL) return NULL;
-        const int arc = hbhip_frame_alloc(hbhip_frame_context(fr), src->f.width, src->f.height, desc->comp[0].depth,
+        const int arc = hbhip_frame_alloc(hbhip_filter_context(pv->dev), src->f.width, src->f.height, desc->comp[0].depth,
                                           desc->log2_chroma_w, desc->log2_chroma_h, &dst);
         if (arc != HBHIP_OK) return NULL;
         hbhip_dev_frame d;
         hbhip_frame_describe(dst, &d, NULL, NULL);
-        /* (the copy is made on the frame's context, the mask drawn on the filter's: ordered behind the copy) */
-        if (hbhip_frame_copy(dst, fr) != HBHIP_OK || hbhip_frame_use_on(dst, hbhip_filter_context(pv->dev)) != HBHIP_OK ||
-            hbhip_comb_detect_overlay_dev(pv->dev, &d, pw, ph) != HBHIP_OK)
+        if (hbhip_frame_copy(dst, fr) != HBHIP_OK || hbhip_comb_detect_overlay_dev(pv->dev, &d, pw, ph) != HBHIP_OK ||
+            hbhip_frame_mark_ready(dst) != HBHIP_OK)
         {
             hbhip_frame_release(dst);
             return NULL;

@@ -117,10 +117,10 @@ hbhip_ctx *hbhip_host_ctx_for(const hb_filter_init_t *init)
  * list - comb detect, decomb, yadif, bwdif: ids 4 - 9, always at the head of a device-resident run - gets a context of its
  * own beside the job's, so that EEDI2 of the next frames runs beside NLMeans / scaler / sharpen of the current ones the way
  * bench.py's device-resident line runs them (--stage-streams 2).  Frames then cross contexts: every consumer of a device
- * frame orders its stream behind the frame's producer (hbhip_frame_use_on) - behind the producer only, not behind what
- * the other stream has queued since - and the frame goes idle behind its last reader's stream.  Measured through the
- * plugin surface (python -m handbrake_amd.hostpath): a list that ends in a 2160p download is bound by the bus
- * either way (3 900 fps); the same list at 1080p out runs at 5 957 fps on one stream and 7 111 on two. */
+ * frame takes it through hbhip_frame_use_on first (the ordering rule: csrc/hbhip_core.hip, "How frames are ordered").
+ * Measured through the plugin surface (python -m handbrake_amd.hostpath): a list that ends in a 2160p
+ * download is bound by the bus either way (3 900 fps); the same list at 1080p out runs at 5 957 fps on one stream and
+ * 7 111 on two. */
 #define HBHIP_ROLE_MAIN        0
 #define HBHIP_ROLE_DEINTERLACE 1
 static int job_streams(void)

@@ -114,25 +114,27 @@ int  hbhip_frame_alloc(hbhip_ctx *ctx, int width, int height, int depth,
                        int log2_chroma_w, int log2_chroma_h, hbhip_frame **out);
 void hbhip_frame_retain(hbhip_frame *fr);
 void hbhip_frame_release(hbhip_frame *fr);            /* back to the pool at refcount 0 */
-/* A filter on ANOTHER context of the same GPU is about to queue work that reads the frame: its stream is ordered behind
- * the frame's producer (the ready mark only) and the frame goes idle behind that stream (a job with more than one HIP
- * stream, libhb/hbhip_registry.c).  No-op for the owner's context while nobody else has read the frame. */
+/* A frame may be read and written on more than one context of its GPU (a job with more than one HIP stream,
+ * libhb/hbhip_registry.c).  Before a context queues work on a frame it takes it through hbhip_frame_use_on: its stream
+ * waits for the frame's contents (the ready mark, nothing else of another stream) and the context becomes the frame's
+ * current user.  The rule in full, idle marks included: hbhip_core.hip, "How frames are ordered". */
 int  hbhip_frame_use_on(hbhip_frame *fr, hbhip_ctx *ctx);
 int  hbhip_frame_refs(hbhip_frame *fr);               /* holders right now; 1 = the caller is the only one (it may write in place) */
 int  hbhip_frame_describe(hbhip_frame *fr, hbhip_dev_frame *out, int *width, int *height);
 hbhip_ctx *hbhip_frame_context(hbhip_frame *fr);      /* the context (device, stream) whose pool the frame belongs to */
-int  hbhip_frame_copy(hbhip_frame *dst, hbhip_frame *src);                  /* same geometry; stream-ordered D2D */
+int  hbhip_frame_copy(hbhip_frame *dst, hbhip_frame *src);                  /* same geometry, one GPU; D2D on dst's stream (use_on) */
 int  hbhip_frame_upload(hbhip_frame *fr, const hbhip_host_frame *src);      /* H2D, returns when src is consumed */
 int  hbhip_frame_download(hbhip_frame *fr, const hbhip_host_frame *dst);    /* D2H, synchronous */
 /* The pipelined H2D: the copy is queued on the context's upload stream and the call returns; `src` must stay valid until
  * hbhip_ctx_upload_done(ctx, token, block) has answered HBHIP_OK (HBHIP_AGAIN: not yet; block != 0 waits).  The frame's
- * ready mark is the copy itself: readers (hbhip_frame_use_on, hbhip_frame_copy, a download) wait for it and nothing else. */
+ * ready mark is the copy itself. */
 int  hbhip_frame_upload_async(hbhip_frame *fr, const hbhip_host_frame *src, void **token);
 int  hbhip_ctx_upload_done(hbhip_ctx *ctx, void *token, int block);
-/* The producer of a frame marks the point of the context's stream behind which its contents are complete; a
- * download then waits for that point only (not for what other filter threads have queued since).  The pipelined
- * D2H: queue the copy on the download stream and return; `dst` and the frame must stay valid until
- * hbhip_frame_download_wait(fr, token) has returned.  A few in flight keep the bus busy (the download adapter). */
+/* Whoever writes a frame marks its contents complete: the ready mark goes on the stream of the frame's current user
+ * (the context that last took it through hbhip_frame_use_on, else its owner), and readers - a download among them -
+ * wait for that point only, not for what other filter threads have queued since.  The pipelined D2H: queue the copy on
+ * the download stream and return; `dst` and the frame must stay valid until hbhip_frame_download_wait(fr, token) has
+ * returned.  A few in flight keep the bus busy (the download adapter). */
 int  hbhip_frame_mark_ready(hbhip_frame *fr);
 int  hbhip_frame_download_async(hbhip_frame *fr, const hbhip_host_frame *dst, void **token);
 int  hbhip_frame_download_wait(hbhip_frame *fr, void *token);
