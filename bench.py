@@ -23,13 +23,17 @@ Multi-GPU (--gpus N under torch.distributed.run): every rank filters its own ind
 on its own GPU (frames shard by stream); no data-path collective; RCCL only reduces
 {frames, seconds}: value = total output frames of all ranks / max-over-ranks time.  scaling = weak.
 
-Also on the JSON line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the line: the headline
+(`value`, `ms_per_step`, ...) and what follows from the timed steps alone (input_fps, the chain's algorithmic HBM rate,
+host_enqueue_ms_per_step_timed_region).  Everything else runs after the timed region and only with --full:
   roofline       dominant kernel of the workload (largest share of GPU time): algorithmic bytes per
                  launch / its mean launch time.  Launch times come from a pass right after the timed
                  region in which the same launches are bracketed by HIP events on the stream they run
                  on; `kernels` lists the rest.  `roofline.valu` prices the kernel's vector instructions with its own mix,
                  `roofline.issue_floors` carries the committed vector / scalar / LDS / HBM floors of that kernel
                  (tools/kernel_bounds.py on the newest counter passes under profiles/ - evidence, not a measurement of this run).
+                 `roofline.measured_peak` is the on-box copy ceiling, `config.eedi2_mask_density` the share of each plane
+                 EEDI2 works on, `host_enqueue_ms_per_step` the host's time for a step into an empty queue.
   cpu_baseline   the reference's own C filters (oracle/_ref, threaded by its own taskset.c as libhb
                  does) on this box's host cores, bounded sample; the scaler leg is our restatement
                  (zimg is not buildable here) and is labelled as such.
@@ -336,25 +340,20 @@ def run_nlmeans(args, world, rank, local_rank):
                      DUMP_BUDGET // world)
     if world > 1:
         dist.barrier()
-    # the kernel's launch time: the same steps once more with every launch bracketed by HIP events on its stream (kept out
-    # of the timed region: an event record costs the queue ~4.5 us)
-    ctx.profile(True)
-    ctx.profile_reset()
-    for i in range(args.steps):
-        step(args.warmup + args.steps + i)
-    ctx.sync()
-    stats = ctx.profile_stats()
-    ctx.profile(False)
+    if args.full:
+        # the kernel's launch time: the same steps once more with every launch bracketed by HIP events on its stream (kept
+        # out of the timed region: an event record costs the queue ~4.5 us)
+        ctx.profile(True)
+        ctx.profile_reset()
+        for i in range(args.steps):
+            step(args.warmup + args.steps + i)
+        ctx.sync()
+        stats = ctx.profile_stats()
+        ctx.profile(False)
 
     frames_local = float(args.steps * B)
     frames_total, dt_max = shard.reduce_throughput(frames_local, dt, device="cuda")
     if rank == 0:
-        kname, (launches, total_ms) = max(stats.items(), key=lambda kv: kv[1][1])
-        avg_s = total_ms / launches / 1e3
-        frames_per_launch = frames_local / launches
-        algo_bytes = 3 * frame_bytes(W, H) * frames_per_launch * (2 if args.depth > 8 else 1)
-        achieved = algo_bytes / avg_s / 1e9
-        traffic, valu_insts = pmc_record(kname, B)
         out = {
             "metric": "filtered frames/sec, 1080p YUV420p NLMeans (medium) alone [the NLMeans+decomb chain is the default workload]",
             "value": round(frames_total / dt_max, 2), "unit": "frames/s", "n_gpus": world,
@@ -364,17 +363,24 @@ def run_nlmeans(args, world, rank, local_rank):
             "data": "synthetic",
             "config": {"workload": wl["text"], "frames_per_step": B, "width": W, "height": H,
                        "parallelism": f"{world} independent stream(s), one per GPU", "device": ctx.name()},
-            "roofline": {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 2),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": traffic, "launch_us": round(avg_s * 1e6, 2), "launches": launches,
-                         "algorithmic_bytes_per_launch": int(algo_bytes),
-                         "note": "NLMeans is VALU-bound (about 320 integer/float lane-ops per pixel); "
-                                 "'valu' prices the same launch against the measured vector-ALU issue rate"},
         }
-        if valu_insts:
-            out["roofline"]["valu"] = valu_roofline(valu_insts, avg_s, "nlmeans_plane_n7")
-        if world == 1 and not args.no_cpu_baseline and args.depth == 8:
-            out["cpu_baseline"] = cpu_baseline_nlmeans(frames_np)
+        if args.full:
+            kname, (launches, total_ms) = max(stats.items(), key=lambda kv: kv[1][1])
+            avg_s = total_ms / launches / 1e3
+            frames_per_launch = frames_local / launches
+            algo_bytes = 3 * frame_bytes(W, H) * frames_per_launch * (2 if args.depth > 8 else 1)
+            achieved = algo_bytes / avg_s / 1e9
+            traffic, valu_insts = pmc_record(kname, B)
+            out["roofline"] = {"bound": "hbm", "kernel": kname, "achieved": round(achieved, 2),
+                               "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5),
+                               "traffic": traffic, "launch_us": round(avg_s * 1e6, 2), "launches": launches,
+                               "algorithmic_bytes_per_launch": int(algo_bytes),
+                               "note": "NLMeans is VALU-bound (about 320 integer/float lane-ops per pixel); "
+                                       "'valu' prices the same launch against the measured vector-ALU issue rate"}
+            if valu_insts:
+                out["roofline"]["valu"] = valu_roofline(valu_insts, avg_s, "nlmeans_plane_n7")
+            if world == 1 and not args.no_cpu_baseline and args.depth == 8:
+                out["cpu_baseline"] = cpu_baseline_nlmeans(frames_np)
         print(json.dumps(out), flush=True)
     flt.close()
     ctx.close()
@@ -649,18 +655,19 @@ def run_chain(args, world, rank, local_rank):
         dist.barrier()
     out_frames = sum(ln.produced for ln in lanes) - start
     frames_total, dt_max = shard.reduce_throughput(float(out_frames), dt, device="cuda")
-    # host time to enqueue a step when nothing holds the host back: three steps into an empty queue (in the timed
-    # region the host runs ahead of the GPU until a filter's ring of job tables / pictures makes it wait)
-    t1 = time.perf_counter()
-    for _ in range(3):
-        for ln in lanes:
-            ln.step()
-    t_enq_free = (time.perf_counter() - t1) / 3
-    sync_all()
+    if args.full:
+        # host time to enqueue a step when nothing holds the host back: three steps into an empty queue (in the timed
+        # region the host runs ahead of the GPU until a filter's ring of job tables / pictures makes it wait)
+        t1 = time.perf_counter()
+        for _ in range(3):
+            for ln in lanes:
+                ln.step()
+        t_enq_free = (time.perf_counter() - t1) / 3
+        sync_all()
 
     # per-kernel launch times: same launches, bracketed by HIP events on their stream, right after the timed region
     stats = {}
-    if not args.no_kernel_timer:
+    if args.full and not args.no_kernel_timer:
         # on one stream (a lane of its own, all stages on one context) so that every launch is timed alone
         pl = Lane(False)
         for _ in range(2):
@@ -727,11 +734,11 @@ def run_chain(args, world, rank, local_rank):
                        "stage_streams": int(args.stage_streams),
                        "parallelism": f"{world} GPU(s) x {len(lanes)} independent stream(s)", "device": ctx.name()},
             "input_fps": round(frames_total / dt_max / 2, 2),
-            "host_enqueue_ms_per_step": round(t_enq_free * 1e3, 4),
+            **({"host_enqueue_ms_per_step": round(t_enq_free * 1e3, 4)} if args.full else {}),
             "host_enqueue_ms_per_step_timed_region": round(t_enq / args.steps * 1e3, 4),
             "chain_hbm_GBps_algorithmic": round(per_out * frames_total / dt_max / 1e9, 2),
             "chain_frac_of_hbm_peak": round(per_out * frames_total / dt_max / 1e9 / HBM_PEAK_GBS, 5),
-            "roofline": roof, "kernels": kernels,
+            **({"roofline": roof, "kernels": kernels} if args.full else {}),
         }
         if roof is not None and not args.no_kernel_timer:
             try:
@@ -742,20 +749,21 @@ def run_chain(args, world, rank, local_rank):
             except Exception as e:
                 roof["measured_peak"] = None
                 roof["measured_peak_error"] = repr(e)
-        if not args.no_kernel_timer:
+        if args.full and not args.no_kernel_timer:
             try:
                 line["config"]["eedi2_mask_density"] = mask_density(hip, local_rank, frames_np, W, H, depth)
             except Exception as e:
                 line["config"]["eedi2_mask_density"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
-            line["cpu_baseline"] = cpu_baseline_chain(args.workload, frames_np, scale)
-        else:
-            line["cpu_baseline"] = None
+        if args.full:
+            if world == 1 and not args.no_cpu_baseline:
+                line["cpu_baseline"] = cpu_baseline_chain(args.workload, frames_np, scale)
+            else:
+                line["cpu_baseline"] = None
     # The same chain through the plugin surface, host frames in and out: on EVERY rank at the same time (each on its
     # own GPU with its own pinned buffers), so that an N-GPU run shows what the host's PCIe root complex and memory
     # give N streams at once - the resident rate above cannot.
     pcie = None
-    if not args.no_pcie:
+    if args.full and not args.no_pcie:
         if world > 1:
             import torch.distributed as dist
             dist.barrier()
@@ -777,7 +785,9 @@ def dry_run(args, world, rank):
     the CPU with gloo in place of RCCL (tests/test_dist_gloo.py runs it at world sizes 2 and 4): RANK / WORLD_SIZE /
     MASTER_* from the environment, the process group, the barrier + max-over-ranks timing, the stream -> rank sharding,
     the SUM / MAX reduction and ONE line from rank 0.  A "step" here credits the frames a real step would put out and
-    sleeps - nothing is filtered, the line says so (`data`), `value` is not a throughput of anything."""
+    sleeps - nothing is filtered, the line says so (`data`), `value` is not a throughput of anything.  It always goes through
+    the host path's reduction too (`pcie_inclusive`), which a real run does only with --full: free here, and it keeps that
+    plumbing covered."""
     import torch.distributed as dist
     from handbrake_amd import shard
     wl = WORKLOADS[args.workload]
@@ -822,15 +832,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=0,
                     help="input frames per step (default: per workload - chain 16, chain2160 4, nlmeans 32)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive pass of the chain workloads")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: per-kernel launch times "
+                         "and the roofline, the on-box copy ceiling, EEDI2's mask density, the host's enqueue time, the "
+                         "CPU baseline and the PCIe-inclusive pass (about 40 s more; the --no-* switches below trim it)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: skip the PCIe-inclusive pass of the chain workloads")
     ap.add_argument("--depth", type=int, default=8, choices=[8, 10, 12],
                     help="nlmeans and decomb_eedi2 workloads: sample depth (10 / 12 = 16-bit containers)")
     ap.add_argument("--comb-detect", action="store_true",
                     help="chain workloads: run comb detection in front of the (then selective) decomb, "
                          "as BASELINE configs[2] words it")
     ap.add_argument("--no-kernel-timer", action="store_true",
-                    help="chain workloads: skip the event-bracketed pass after the timed region (roofline = null)")
+                    help="with --full, chain workloads: skip the event-bracketed pass after the timed region (roofline = null)")
     ap.add_argument("--stage-streams", type=int, default=None,
                     help="chain workloads: 2 = decomb on one HIP stream, the stages behind it on a second (default at 8 bits; at 10 / 12 "
                          "bits, where it costs 3 %%, the default is 0: the next "

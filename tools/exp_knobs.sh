@@ -12,7 +12,7 @@ i=0
 for KN in "$@"; do
   i=$((i+1))
   for WL in chain decomb_eedi2; do
-    env $KN timeout 120 python bench.py --workload $WL --no-cpu-baseline --no-pcie --steps 20 --warmup 5 > $O/${WL}_$i.json 2> $O/${WL}_$i.err
+    env $KN timeout 120 python bench.py --workload $WL --full --no-cpu-baseline --no-pcie --steps 20 --warmup 5 > $O/${WL}_$i.json 2> $O/${WL}_$i.err
     python - <<PY
 import json
 try:

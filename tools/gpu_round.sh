@@ -17,23 +17,23 @@ if [ "$MODE" = "tests" ]; then
 fi
 # (valu_rate: run once per round, profiles/r02_valu_rate.json)
 # the driver's command line first (defaults), then the other workloads
-timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 head -c 1200 $OUT/bench_default.json; echo
 for C in corners random; do
-  timeout 300 python bench.py --content $C --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_chain_$C.json 2> $OUT/bench_chain_$C.err
+  timeout 300 python bench.py --content $C --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/bench_chain_$C.json 2> $OUT/bench_chain_$C.err
   head -c 400 $OUT/bench_chain_$C.json; echo
 done
 for WL in chain2160 decomb_eedi2 nlmeans; do
-  timeout 240 python bench.py --workload $WL --steps 20 --warmup 3 --no-pcie > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err
+  timeout 240 python bench.py --workload $WL --steps 20 --warmup 3 --full --no-pcie > $OUT/bench_$WL.json 2> $OUT/bench_$WL.err
   head -c 600 $OUT/bench_$WL.json; echo
 done
-timeout 200 python bench.py --workload decomb_eedi2 --depth 10 --no-cpu-baseline --no-pcie > $OUT/bench_decomb_eedi2_10bit.json 2> $OUT/bench_decomb_eedi2_10bit.err
-timeout 200 python bench.py --workload chain --depth 10 --no-cpu-baseline --no-pcie > $OUT/bench_chain_10bit.json 2> $OUT/bench_chain_10bit.err
-timeout 200 python bench.py --workload nlmeans --depth 10 --no-cpu-baseline --no-pcie > $OUT/bench_nlmeans_10bit.json 2> $OUT/bench_nlmeans_10bit.err
-timeout 200 python bench.py --workload chain --stage-streams 1 --no-cpu-baseline --no-pcie --no-kernel-timer > $OUT/bench_chain_stage_streams.json 2>> $OUT/bench_default.err
-timeout 200 python bench.py --workload chain --stage-streams 0 --no-cpu-baseline --no-pcie --no-kernel-timer > $OUT/bench_chain_one_stream.json 2>> $OUT/bench_default.err
-timeout 200 python bench.py --workload chain --streams 2 --stage-streams 0 --no-cpu-baseline --no-pcie --no-kernel-timer > $OUT/bench_chain_2streams.json 2>> $OUT/bench_default.err
-timeout 200 python bench.py --workload chain --comb-detect --no-cpu-baseline --no-pcie --no-kernel-timer > $OUT/bench_chain_combdetect.json 2>> $OUT/bench_default.err
+timeout 200 python bench.py --workload decomb_eedi2 --depth 10 --full --no-cpu-baseline --no-pcie > $OUT/bench_decomb_eedi2_10bit.json 2> $OUT/bench_decomb_eedi2_10bit.err
+timeout 200 python bench.py --workload chain --depth 10 --full --no-cpu-baseline --no-pcie > $OUT/bench_chain_10bit.json 2> $OUT/bench_chain_10bit.err
+timeout 200 python bench.py --workload nlmeans --depth 10 --full --no-cpu-baseline --no-pcie > $OUT/bench_nlmeans_10bit.json 2> $OUT/bench_nlmeans_10bit.err
+timeout 200 python bench.py --workload chain --stage-streams 1 --full --no-cpu-baseline --no-pcie --no-kernel-timer > $OUT/bench_chain_stage_streams.json 2>> $OUT/bench_default.err
+timeout 200 python bench.py --workload chain --stage-streams 0 --full --no-cpu-baseline --no-pcie --no-kernel-timer > $OUT/bench_chain_one_stream.json 2>> $OUT/bench_default.err
+timeout 200 python bench.py --workload chain --streams 2 --stage-streams 0 --full --no-cpu-baseline --no-pcie --no-kernel-timer > $OUT/bench_chain_2streams.json 2>> $OUT/bench_default.err
+timeout 200 python bench.py --workload chain --comb-detect --full --no-cpu-baseline --no-pcie --no-kernel-timer > $OUT/bench_chain_combdetect.json 2>> $OUT/bench_default.err
 timeout 240 python tools/kernel_rooflines.py > $OUT/kernel_rooflines.json 2> $OUT/kernel_rooflines.err
 # the same table on 2160p frames: the 16 frames of a batched launch (199 MB in, 199 MB out) are past the 256 MB Infinity Cache
 KR_W=3840 KR_H=2160 timeout 400 python tools/kernel_rooflines.py > $OUT/kernel_rooflines_2160p.json 2> $OUT/kernel_rooflines_2160p.err

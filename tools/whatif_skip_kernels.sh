@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out/whatif; O=$R/gpurun_out/whatif
 run() { # tag, workload, env...
   tag=$1; wl=$2; shift 2
-  env "$@" timeout 200 python bench.py --workload $wl --no-cpu-baseline --no-pcie --no-kernel-timer --steps 12 --warmup 3 > $O/$tag.json 2> $O/$tag.err
+  env "$@" timeout 200 python bench.py --workload $wl --full --no-cpu-baseline --no-pcie --no-kernel-timer --steps 12 --warmup 3 > $O/$tag.json 2> $O/$tag.err
   python - <<PY
 import json
 try:
