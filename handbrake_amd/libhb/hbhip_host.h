@@ -108,6 +108,7 @@ extern hb_blend_object_t  hb_blend_hip;
 extern hb_motion_metric_object_t hb_motion_metric_hip;
 extern hb_filter_object_t hb_filter_decomb_hip;
 extern hb_filter_object_t hb_filter_comb_detect_hip;
+extern hb_filter_object_t hb_filter_detelecine_hip;
 
 #ifndef HBHIP_IN_LIBHB
 void hbhip_nlmeans_params_from_settings(const char *settings, int depth, hbhip_nlmeans_params *p);   /* bench / tests only */

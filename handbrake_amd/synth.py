@@ -201,3 +201,71 @@ def overlays(w: int, h: int, count: int, seed: int = 1, subsampled: bool = False
             cb, cr = cb[::2, ::2], cr[::2, ::2]
         out.append((x, y, (yy.copy(), np.ascontiguousarray(cb), np.ascontiguousarray(cr), a)))
     return out
+
+
+# ---- telecined streams (detelecine / pullup) -------------------------------------------------------------------------
+PIC_FLAG_REPEAT_FIRST_FIELD = 0x0100
+_CHROMA = {"2x2": (1, 1), "2x1": (1, 0), "1x1": (0, 0)}       # log2 chroma subsampling (w, h) of each layout
+
+
+def picture(model: str, w: int, h: int, t: int, cfg: int = 2, depth: int = 8, chroma: str = "2x2"):
+    """Frame t of `model` ("progressive" / "interlaced") in any of the three chroma layouts and 8 / 10 / 12 bits.  4:2:2
+    and 4:4:4 chroma come from the model drawn at twice the height (and width): the same kind of picture in every plane.
+    Wider samples carry the 8-bit model in their high bits and LCG detail below, as in stream()."""
+    gen = {"progressive": progressive_frame, "interlaced": interlaced_frame}[model]
+    lcw, lch = _CHROMA[chroma]
+    y = gen(w, h, t, cfg=cfg)[0]
+    cb, cr = gen(w << (1 - lcw), h << (1 - lch), t, cfg=cfg)[1:]
+    planes = [y, cb[: -((-h) >> lch), : -((-w) >> lcw)], cr[: -((-h) >> lch), : -((-w) >> lcw)]]
+    if depth == 8:
+        return tuple(np.ascontiguousarray(p) for p in planes)
+    extra = depth - 8
+    lows = lcg_stream(frame_seed(cfg ^ 0x2e, t) ^ 0x5bd1e995, sum(p.size for p in planes))
+    out, at = [], 0
+    for p in planes:
+        lo = ((lows[at:at + p.size] >> 9) & ((1 << extra) - 1)).astype(np.uint16).reshape(p.shape)
+        at += p.size
+        out.append((p.astype(np.uint16) << extra) | lo)
+    return tuple(out)
+
+
+def _weave(top, bottom):
+    """A picture whose even rows come from `top` and odd rows from `bottom`, plane by plane."""
+    out = []
+    for a, b in zip(top, bottom):
+        p = a.copy()
+        p[1::2] = b[1::2]
+        out.append(p)
+    return tuple(out)
+
+
+def telecine_stream(w: int, h: int, durations, soft=None, cuts=(), top_first: bool = True, depth: int = 8,
+                    chroma: str = "2x2", cfg: int = 2):
+    """Film turned into interlaced video: source frame k of the progressive model is shown for durations[k] fields (2 or
+    3; 3, 2, 3, 2, ... is 3:2 pulldown).  Hard telecine (the default) weaves the field sequence into pictures two fields
+    at a time, every picture starting on the same parity (`top_first`); a source frame with soft[k] true is instead
+    coded as itself, with PIC_FLAG_REPEAT_FIRST_FIELD for three fields and PIC_FLAG_TOP_FIELD_FIRST by the running field
+    parity - MPEG-2 soft pulldown (a soft frame that would start on a pending field is woven as hard).  At each source
+    index in `cuts` the scene changes.  Returns (pictures, per-picture flags)."""
+    scene, base = cfg, 0
+    pics, flags = [], []
+    pending = []                       # fields not yet in a picture: (source picture, parity)
+    parity = 0 if top_first else 1     # parity of the next field in display order
+    for k, d in enumerate(durations):
+        if k in cuts:
+            scene, base = scene + 7, k
+        src = picture("progressive", w, h, k - base + (scene - cfg) * 5, cfg=scene, depth=depth, chroma=chroma)
+        if soft is not None and soft[k] and not pending:
+            pics.append(src)
+            flags.append((PIC_FLAG_TOP_FIELD_FIRST if parity == 0 else 0) | (PIC_FLAG_REPEAT_FIRST_FIELD if d == 3 else 0))
+            parity ^= d & 1
+            continue
+        for _ in range(d):
+            pending.append((src, parity))
+            parity ^= 1
+            if len(pending) == 2:
+                (a, pa), (b, _) = pending
+                pics.append(_weave(a, b) if pa == 0 else _weave(b, a))
+                flags.append(PIC_FLAG_TOP_FIELD_FIRST if pa == 0 else 0)
+                pending = []
+    return pics, flags

@@ -301,6 +301,28 @@ int hbhip_bwdif_create(hbhip_ctx *ctx, int bob, int selective, int parity,
 int hbhip_decomb_debug_eedi_plane(hbhip_filter *f, int buffer, int plane, uint8_t *dst, int dst_stride,
                                   int *stride, int *height);
 
+/* ---- Detelecine / pullup (replaces detelecine.c:159-999 pullup and :1116-1275 hb_detelecine_work) --------------------
+ * The field queue, breaks / affinity and the frame-length decision run on the host side of this library; the block
+ * metrics, their maxima and the weave are kernels.  Push one picture at a time with its PIC_FLAG_* (top field first,
+ * repeat first field); a pull then yields at most one frame, tagged with the pushed picture's tag: the first picture
+ * itself, a frame woven from the queue, or nothing (a dropped or not yet complete frame).  The same picture may come
+ * out again later as the frame of its own two fields - then without a copy, as a frame both sides hold.  At most ten
+ * pictures are held; HBHIP_ERR_STATE where the reference would run out of its ten buffers.
+ * Margins below the reference's safety zones (1, 1, 4, 4) are raised to them and a plane out of range means plane 0
+ * (detelecine.c:1035-1039, 1074-1077).  HBHIP_ERR_UNSUPPORTED where the reference has no defined result: a plane with
+ * an odd number of rows, margins wider than the metric plane. */
+typedef struct hbhip_detelecine_params
+{
+    int skip_left, skip_right, skip_top, skip_bottom;   /* in 8-sample columns / field-line pairs (junk_*)          */
+    int strict_breaks;                                  /* -1 default, 0, 1                                        */
+    int plane;                                          /* metric plane 0..2                                       */
+    int parity;                                         /* -1 = from the picture flags, 0 = top first, 1 = bottom  */
+} hbhip_detelecine_params;
+int hbhip_detelecine_create(hbhip_ctx *ctx, const hbhip_detelecine_params *p, int width, int height, int depth,
+                            int log2_chroma_w, int log2_chroma_h, hbhip_filter **out);
+int hbhip_detelecine_push(hbhip_filter *f, const hbhip_host_frame *in, int64_t tag, int pic_flags);
+int hbhip_detelecine_push_frame(hbhip_filter *f, hbhip_frame *fr, int64_t tag, int pic_flags);   /* as hbhip_filter_push_frame */
+
 /* ---- Comb detect (replaces comb_detect.c:1051-1072 comb_segmenter and the passes it
  *      runs: comb_detect_template.c:288-402/789-933, comb_detect.c:221-276, 384-454,
  *      556-622, 726-792, 901-966, 1029-1049) ------------------------------------------ */
