@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "hbhip_blend_create", "hbhip_blend_set_overlays", "hbhip_blend_apply", "hbhip_blend_apply_dev", "hbhip_blend_destroy",
     "hbhip_motion_metric_create", "hbhip_motion_metric_run", "hbhip_motion_metric_run_dev", "hbhip_motion_metric_destroy",
     "hbhip_detelecine_create", "hbhip_detelecine_push", "hbhip_detelecine_push_frame",
+    "hbhip_deblock_create", "hbhip_deblock_set_warmup",
 ]
 
 
@@ -54,6 +55,10 @@ class NLMeansParams(C.Structure):
                 ("nframes", C.c_int * 3), ("prefilter", C.c_int * 3),
                 ("exptable", (C.c_float * 128) * 3), ("weight_fact_table", C.c_float * 3),
                 ("diff_max", C.c_int * 3)]
+
+
+class DeblockParams(C.Structure):
+    _fields_ = [("strong", C.c_int), ("block", C.c_int), ("ath", C.c_int), ("bth", C.c_int), ("gth", C.c_int), ("dth", C.c_int)]
 
 
 _lib = None

@@ -144,11 +144,35 @@ def corners_frame(w: int, h: int, t: int, cfg: int = 11):
     return clip(luma), clip(cb), clip(cr)
 
 
+def _blocky_plane(w: int, h: int, seed: int, t: int, noise):
+    """Block-constant areas of 4 / 8 / 16 samples (by 48-sample region), each block a level whose step to its
+    neighbours ranges from 0 to past every deblock threshold, drifting 1 px / frame, plus `noise`."""
+    x = np.arange(w, dtype=np.int64)[None, :] + t
+    y = np.arange(h, dtype=np.int64)[:, None]
+    region = ((y // 48) * 7 + (x // 48) * 3 + seed) % 3
+    bs = np.array([4, 8, 16], dtype=np.int64)[region]
+    bx, by = x // bs, y // bs
+    hsh = ((bx * 2654435761 + by * 40503 + region * 97 + seed * 12345) >> 3) & 0xFFFFFF
+    steps = np.array([0, 2, 5, 9, 14, 20, 28, 40, 56, 80, 100, 125], dtype=np.int64)
+    level = 124 + steps[hsh % 12] * np.where((hsh >> 4) & 1, 1, -1)
+    return level + noise
+
+
+def blocky_frame(w: int, h: int, t: int, cfg: int = 13):
+    """(Y, Cb, Cr) of frame t of the blocky model: what an MPEG-2 / low-bitrate source looks like to a deblocker -
+    flat blocks of 4, 8 and 16 samples with steps below and above the thresholds, +-1 LSB noise."""
+    cw, ch = _chroma_dims(w, h)
+    ny, ncb, ncr = _noise(frame_seed(cfg, t), [(h, w), (ch, cw), (ch, cw)], 1)
+    clip = lambda a: np.clip(a, 0, 255).astype(np.uint8)
+    return (clip(_blocky_plane(w, h, cfg, t, ny)), clip(_blocky_plane(cw, ch, cfg + 1, t, ncb)),
+            clip(_blocky_plane(cw, ch, cfg + 2, t, ncr)))
+
+
 def stream(model: str, w: int, h: int, nframes: int, cfg: int | None = None, depth: int = 8):
     """List of (Y, Cb, Cr) tuples.  depth 10 / 12: uint16 planes - the 8-bit model in the high
     bits, the low depth-8 bits drawn from the same LCG (so wider samples carry real detail)."""
     gen = {"progressive": progressive_frame, "interlaced": interlaced_frame,
-           "random": random_frame, "corners": corners_frame}[model]
+           "random": random_frame, "corners": corners_frame, "blocky": blocky_frame}[model]
     kw = {} if cfg is None else {"cfg": cfg}
     frames = [gen(w, h, t, **kw) for t in range(nframes)]
     if depth == 8:
@@ -212,7 +236,7 @@ def picture(model: str, w: int, h: int, t: int, cfg: int = 2, depth: int = 8, ch
     """Frame t of `model` ("progressive" / "interlaced") in any of the three chroma layouts and 8 / 10 / 12 bits.  4:2:2
     and 4:4:4 chroma come from the model drawn at twice the height (and width): the same kind of picture in every plane.
     Wider samples carry the 8-bit model in their high bits and LCG detail below, as in stream()."""
-    gen = {"progressive": progressive_frame, "interlaced": interlaced_frame}[model]
+    gen = {"progressive": progressive_frame, "interlaced": interlaced_frame, "blocky": blocky_frame}[model]
     lcw, lch = _CHROMA[chroma]
     y = gen(w, h, t, cfg=cfg)[0]
     cb, cr = gen(w << (1 - lcw), h << (1 - lch), t, cfg=cfg)[1:]

@@ -390,6 +390,23 @@ typedef struct hbhip_pad_params
 } hbhip_pad_params;
 int hbhip_pad_create(hbhip_ctx *ctx, const hbhip_pad_params *p, int width, int height, int depth,
                      int log2_chroma_w, int log2_chroma_h, hbhip_filter **out);
+/* FFmpeg `deblock=filter=..:block=..:alpha=..:beta=..:gamma=..:delta=..` as deblock_init sets it up (deblock.c:37-86):
+ * strong (1) or weak (0), the block size 4..512 shared by every plane, and the integer thresholds FFmpeg derives from
+ * the float options, (int)(option * ((1 << depth) - 1)) - the caller resolves them (libhb/deblock_hip.c).  Out of place:
+ * every output sample is made from the input frame.  8/10/12-bit.  HBHIP_ERR_UNSUPPORTED for a plane whose last edge's
+ * window would reach past it (size % block in {1, 2} strong, 1 weak, with an edge in the plane).  Arithmetic restated
+ * (parity unpinned). */
+typedef struct hbhip_deblock_params
+{
+    int strong;                          /* 1 = `strong` (six taps), 0 = `weak` (four)   */
+    int block;                           /* `block`, 4..512                              */
+    int ath, bth, gth, dth;              /* integer alpha / beta / gamma / delta         */
+} hbhip_deblock_params;
+int hbhip_deblock_create(hbhip_ctx *ctx, const hbhip_deblock_params *p, int width, int height, int depth,
+                         int log2_chroma_w, int log2_chroma_h, hbhip_filter **out);
+/* test hook: warm-up edges of the speculative row segments of the strong b = 4 / 5 kernel (default 4; 0 = every segment
+ * starts cold, so that every boundary whose edge fires goes through the repair walk).  The result is the same for any value. */
+int hbhip_deblock_set_warmup(hbhip_filter *f, int edges);
 /* `format=pix_fmts=<fmt>` as format_init sets it up (format.c:13-111): libavfilter then converts with a same-size
  * `scale`, i.e. libswscale's unscaled planar copy.  Built: planar YUV depth changes 8 / 10 / 12 -> 8 / 10 / 12 with the
  * chroma subsampling unchanged (up: shift, full-range luma replicates the top bits; down: ordered dither - the

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times one stateless filter's batch path (16 device-resident 1080p frames per call) with the context's kernel timer.
-usage: quick_filter.py unsharp|chroma_smooth|lapsharp|colorspace_sdr|colorspace_matrix|grayscale|rotate|scale<W>x<H> [reps]
+usage: quick_filter.py unsharp|chroma_smooth|lapsharp|colorspace_sdr|colorspace_matrix|grayscale|rotate|scale<W>x<H>|
+                      deblock_<preset>_<tune>[_10] [reps]
 Prints one line per kernel: name, launches, average us.  For knob experiments with tools/dev_run.sh."""
 import ctypes as C, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -60,6 +61,7 @@ def main():
                            ctx.h, C.byref(p), W, H, 8, 1, 1)
     ow, oh = W, H
     depth_in = depth_out = 8
+    picture = "progressive"
     if what == "unsharp": make = lambda: mk_blur("hbhip_unsharp_create")
     elif what == "unsharp5": make = lambda: mk_blur("hbhip_unsharp_create", size=5)
     elif what == "chroma_smooth": make = lambda: mk_blur("hbhip_chroma_smooth_create", 0)
@@ -88,11 +90,25 @@ def main():
         pp = PP(W + 128, H + 72, 64, 36, (C.c_int * 3)(16, 128, 128))
         make = lambda: hip._create("hbhip_pad_create", ctx, [C.c_void_p, C.POINTER(PP)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)], ctx.h, C.byref(pp), W, H, 8, 1, 1)
         ow, oh = W + 128, H + 72
+    elif what.startswith("deblock"):                   # deblock_<preset>_<tune>[_10]: deblock_medium_medium, deblock_medium_small_10 ...
+        parts = what.split("_")
+        tunes = {"small": ":blocksize=4", "medium": "", "large": ":blocksize=16"}
+        presets = {"ultralight": "strength=weak:thresh=20", "light": "strength=weak:thresh=50", "medium": "strength=strong:thresh=20",
+                   "strong": "strength=strong:thresh=50", "stronger": "strength=strong:thresh=75", "verystrong": "strength=strong:thresh=100"}
+        depth_in = depth_out = 10 if parts[-1] == "10" else 8
+        dp = hip.DeblockParams()
+        F = hip.filters()
+        F.hbhip_deblock_params_from_settings.argtypes = [C.c_char_p] + [C.c_int] * 5 + [C.POINTER(hip.DeblockParams)]
+        if F.hbhip_deblock_params_from_settings((presets[parts[1]] + tunes[parts[2]]).encode(), depth_in, W, H, 1, 1, C.byref(dp)):
+            raise SystemExit("deblock declines " + what)
+        make = lambda: hip._create("hbhip_deblock_create", ctx, [C.c_void_p, C.POINTER(hip.DeblockParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
+                                   ctx.h, C.byref(dp), W, H, depth_in, 1, 1)
+        picture = "blocky"
     elif what in ("yadif", "yadif_bob", "bwdif"):
         return deint(ctx, what, reps)
     else:
         raise SystemExit("unknown filter " + what)
-    frames = synth.stream("progressive", W, H, 4, depth=depth_in) if depth_in != 8 else synth.stream("progressive", W, H, 4)
+    frames = synth.stream(picture, W, H, 4, depth=depth_in) if depth_in != 8 else synth.stream(picture, W, H, 4)
     dev_in = [[torch.from_numpy(p.view(np.int16) if depth_in != 8 else p).cuda() for p in fr] for fr in frames]
     outs = [planes(ow, oh, torch.int16 if depth_out != 8 else torch.uint8) for _ in range(NB)]
     torch.cuda.synchronize()
