@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "hbhip_motion_metric_create", "hbhip_motion_metric_run", "hbhip_motion_metric_run_dev", "hbhip_motion_metric_destroy",
     "hbhip_detelecine_create", "hbhip_detelecine_push", "hbhip_detelecine_push_frame",
     "hbhip_deblock_create", "hbhip_deblock_set_warmup",
+    "hbhip_deband_create", "hbhip_deband_offsets", "hbhip_deband_set_kernel",
 ]
 
 
@@ -59,6 +60,10 @@ class NLMeansParams(C.Structure):
 
 class DeblockParams(C.Structure):
     _fields_ = [("strong", C.c_int), ("block", C.c_int), ("ath", C.c_int), ("bth", C.c_int), ("gth", C.c_int), ("dth", C.c_int)]
+
+
+class DebandParams(C.Structure):
+    _fields_ = [("thr", C.c_int * 3), ("blur", C.c_int), ("range", C.c_int), ("direction", C.c_float)]
 
 
 _lib = None

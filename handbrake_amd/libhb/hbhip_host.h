@@ -110,11 +110,13 @@ extern hb_filter_object_t hb_filter_decomb_hip;
 extern hb_filter_object_t hb_filter_comb_detect_hip;
 extern hb_filter_object_t hb_filter_detelecine_hip;
 extern hb_filter_object_t hb_filter_deblock_hip;
+extern hb_filter_object_t hb_filter_deband_hip;
 
 #ifndef HBHIP_IN_LIBHB
 void hbhip_nlmeans_params_from_settings(const char *settings, int depth, hbhip_nlmeans_params *p);   /* bench / tests only */
 int  hbhip_deblock_params_from_settings(const char *settings, int depth, int width, int height, int log2_cw, int log2_ch,
                                         hbhip_deblock_params *p);                                    /* tests / tools only */
+int  hbhip_deband_params_from_settings(const char *settings, int depth, hbhip_deband_params *p);  /* tests / tools only */
 #endif
 
 /* hb_filter_get() analogue (common.c:5331-5495) for the HIP drop-ins. */

@@ -168,11 +168,36 @@ def blocky_frame(w: int, h: int, t: int, cfg: int = 13):
             clip(_blocky_plane(cw, ch, cfg + 2, t, ncr)))
 
 
+def _banded_plane(w: int, h: int, seed: int, t: int, noise):
+    """Slow 2-D gradients quantised into steps of 1, 2 or 3 codes (by 96 x 128 region), some regions overlaid with a
+    +-24 texture, and 48-code edges every 256 columns, drifting 1 px / frame, plus `noise`."""
+    x = np.arange(w, dtype=np.int64)[None, :] + t
+    y = np.arange(h, dtype=np.int64)[:, None]
+    region = ((y // 96) * 5 + (x // 128) * 3 + seed) % 4
+    grad = 40 + (x * 3) // 80 + (y * 2) // 45 + ((x // 64) * (y // 64) * (seed % 3 + 1)) // 16
+    q = np.array([1, 2, 3, 2], dtype=np.int64)[region]
+    level = grad // q * q
+    tex = np.where(region == 3, np.where(((x // 3) + (y // 3)) & 1, 24, -24), 0)
+    edge = np.where(((x + 37 * seed) // 256) & 1, 48, 0)
+    return level + tex + edge + noise
+
+
+def banded_frame(w: int, h: int, t: int, cfg: int = 17):
+    """(Y, Cb, Cr) of frame t of the banded model: what a debander meets - smooth gradients quantised into visible
+    bands of 1 - 3 codes, textured regions and hard edges well above the thresholds, +-1 LSB noise."""
+    cw, ch = _chroma_dims(w, h)
+    ny, ncb, ncr = _noise(frame_seed(cfg, t), [(h, w), (ch, cw), (ch, cw)], 1)
+    clip = lambda a: np.clip(a, 0, 255).astype(np.uint8)
+    return (clip(_banded_plane(w, h, cfg, t, ny)), clip(_banded_plane(cw, ch, cfg + 1, t, ncb)),
+            clip(_banded_plane(cw, ch, cfg + 2, t, ncr)))
+
+
 def stream(model: str, w: int, h: int, nframes: int, cfg: int | None = None, depth: int = 8):
     """List of (Y, Cb, Cr) tuples.  depth 10 / 12: uint16 planes - the 8-bit model in the high
     bits, the low depth-8 bits drawn from the same LCG (so wider samples carry real detail)."""
     gen = {"progressive": progressive_frame, "interlaced": interlaced_frame,
-           "random": random_frame, "corners": corners_frame, "blocky": blocky_frame}[model]
+           "random": random_frame, "corners": corners_frame, "blocky": blocky_frame,
+           "banded": banded_frame}[model]
     kw = {} if cfg is None else {"cfg": cfg}
     frames = [gen(w, h, t, **kw) for t in range(nframes)]
     if depth == 8:
@@ -236,7 +261,8 @@ def picture(model: str, w: int, h: int, t: int, cfg: int = 2, depth: int = 8, ch
     """Frame t of `model` ("progressive" / "interlaced") in any of the three chroma layouts and 8 / 10 / 12 bits.  4:2:2
     and 4:4:4 chroma come from the model drawn at twice the height (and width): the same kind of picture in every plane.
     Wider samples carry the 8-bit model in their high bits and LCG detail below, as in stream()."""
-    gen = {"progressive": progressive_frame, "interlaced": interlaced_frame, "blocky": blocky_frame}[model]
+    gen = {"progressive": progressive_frame, "interlaced": interlaced_frame, "blocky": blocky_frame,
+           "banded": banded_frame}[model]
     lcw, lch = _CHROMA[chroma]
     y = gen(w, h, t, cfg=cfg)[0]
     cb, cr = gen(w << (1 - lcw), h << (1 - lch), t, cfg=cfg)[1:]

@@ -407,6 +407,27 @@ int hbhip_deblock_create(hbhip_ctx *ctx, const hbhip_deblock_params *p, int widt
 /* test hook: warm-up edges of the speculative row segments of the strong b = 4 / 5 kernel (default 4; 0 = every segment
  * starts cold, so that every boundary whose edge fires goes through the repair walk).  The result is the same for any value. */
 int hbhip_deblock_set_warmup(hbhip_filter *f, int edges);
+/* FFmpeg `deband=1thr=..:2thr=..:3thr=..:4thr=..:range=..:blur=..` as deband_init sets it up (deband.c:35-80):
+ * `direction` and `coupling` keep FFmpeg's defaults.  thr[p] are the integer thresholds FFmpeg derives from the float
+ * options, (int)(((1 << depth) - 1) * option) - the caller resolves them (libhb/deband_hip.c).  The per-position offset
+ * table is built once, on the host, with libm (hbhip_deband_offsets).  Out of place: every output sample is made from
+ * the input frame.  8/10/12-bit planar 4:2:0 / 4:2:2 / 4:4:4.  Arithmetic restated (parity unpinned). */
+typedef struct hbhip_deband_params
+{
+    int   thr[3];                        /* integer 1thr / 2thr / 3thr                    */
+    int   blur;                          /* 1: against the average, 0: against each ref   */
+    int   range;                         /* |range| <= 2^30                               */
+    float direction;                     /* FFmpeg's default: (float)(2 * M_PI)           */
+} hbhip_deband_params;
+int hbhip_deband_create(hbhip_ctx *ctx, const hbhip_deband_params *p, int width, int height, int depth,
+                        int log2_chroma_w, int log2_chroma_h, hbhip_filter **out);
+/* FFmpeg's offset table for a width x height luma plane (config_input), exactly: x_pos / y_pos[y * width + x], built
+ * with the host's sinf / cosf / floorf in float, without contraction.  Needs no device.  HBHIP_ERR_ARG for a size < 1
+ * or |range| > 2^30. */
+int hbhip_deband_offsets(int width, int height, int range, float direction, int *x_pos, int *y_pos);
+/* test / tool hook: which kernel runs - 0 the automatic choice (the LDS tile where its halo fits), 1 the
+ * LDS tile (HBHIP_ERR_UNSUPPORTED where the halo does not fit), 2 the direct global gather.  The result is the same. */
+int hbhip_deband_set_kernel(hbhip_filter *f, int kernel);
 /* `format=pix_fmts=<fmt>` as format_init sets it up (format.c:13-111): libavfilter then converts with a same-size
  * `scale`, i.e. libswscale's unscaled planar copy.  Built: planar YUV depth changes 8 / 10 / 12 -> 8 / 10 / 12 with the
  * chroma subsampling unchanged (up: shift, full-range luma replicates the top bits; down: ordered dither - the

@@ -1,0 +1,230 @@
+"""GPU: the deband drop-in (csrc/deband.hip, libhb/deband_hip.c) is bit-exact with the numpy model
+(tests/deband_model.py) - the defaults at 1080p, blur on and off, the thresholds' range, per-plane thresholds, 8/10/12
+bits on 4:2:0/4:2:2/4:4:4 with odd and tiny sizes, every range of the table test on both kernels, bursts with mixed
+pitches - and inside a device-resident job between VFR and NLMeans."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import deband_model as dm
+from handbrake_amd import hbrt, hip, synth
+
+pytestmark = pytest.mark.gpu
+DROPIN = "hb_filter_deband_hip"
+LCW = {"2x2": (1, 1), "2x1": (1, 0), "1x1": (0, 0)}
+
+
+def model(frames, settings, depth=8):
+    return [dm.deband_frame(fr, settings, depth) for fr in frames]
+
+
+def check(got, want, what=""):
+    assert len(got) == len(want) > 0
+    for t in range(len(want)):
+        for c in range(3):
+            g = got[t].planes[c] if hasattr(got[t], "planes") else got[t][c]
+            assert g.shape == want[t][c].shape, f"{what} frame {t} plane {c} shape"
+            np.testing.assert_array_equal(g, want[t][c], err_msg=f"{what} frame {t} plane {c}")
+
+
+def test_defaults_1080p(built):
+    frames = synth.stream("banded", 1920, 1080, 2)
+    got = hbrt.run_stream(hip.filters(), [(DROPIN, "")], frames)
+    check(got, model(frames, ""), "defaults")
+    for c in range(3):
+        diff = got[0].planes[c] != frames[0][c]
+        assert diff.any() and not diff.all(), c
+
+
+@pytest.mark.parametrize("thr", [0.00003, 0.02, 0.1, 0.5])
+@pytest.mark.parametrize("blur", [0, 1])
+def test_thresholds_and_blur(built, thr, blur):
+    frames = synth.stream("banded", 352, 200, 3, cfg=5)
+    st = f"1thr={thr}:2thr={thr}:3thr={thr}:blur={blur}"
+    check(hbrt.run_stream(hip.filters(), [(DROPIN, st)], frames), model(frames, st), st)
+
+
+@pytest.mark.parametrize("blur", [0, 1])
+def test_per_plane_thresholds(built, blur):
+    """three different thresholds in one run: a plane mix-up changes the picture"""
+    frames = synth.stream("banded", 320, 184, 2, cfg=7)
+    st = f"1thr=0.005:2thr=0.04:3thr=0.2:range=12:blur={blur}"
+    want = model(frames, st)
+    check(hbrt.run_stream(hip.filters(), [(DROPIN, st)], frames), want, st)
+    for perm in ("1thr=0.04:2thr=0.2:3thr=0.005", "1thr=0.2:2thr=0.005:3thr=0.04"):
+        other = model(frames, f"{perm}:range=12:blur={blur}")
+        assert any(not np.array_equal(other[0][c], want[0][c]) for c in range(3))
+
+
+def _format_cases():
+    out = []
+    for w, h in [(637, 359), (640, 360), (24, 18)]:
+        for sub in ("2x2", "2x1", "1x1"):
+            for depth in (8, 10, 12):
+                out.append((w, h, sub, depth))
+    return out
+
+
+@pytest.mark.parametrize("w,h,sub,depth", _format_cases())
+def test_depths_and_layouts(built, w, h, sub, depth):
+    frames = [synth.picture("banded", w, h, t, cfg=21, depth=depth, chroma=sub) for t in range(2)]
+    for st in ("", "blur=0:range=7"):
+        got = hbrt.run_stream(hip.filters(), [(DROPIN, st)], frames, pix_fmt=hbrt.PIX_FMT[(sub, depth)])
+        check(got, model(frames, st, depth), f"{w}x{h} {sub} {depth} {st!r}")
+
+
+# ---- the C ABI directly: both kernels, bursts ------------------------------------------------------------------------
+def _make(ctx, settings, w, h, depth=8):
+    p = hip.DebandParams()
+    F = hip.filters()
+    F.hbhip_deband_params_from_settings.argtypes = [C.c_char_p, C.c_int, C.POINTER(hip.DebandParams)]
+    assert F.hbhip_deband_params_from_settings(settings.encode(), depth, C.byref(p)) == 0
+    return hip._create("hbhip_deband_create", ctx, [C.c_void_p, C.POINTER(hip.DebandParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
+                       ctx.h, C.byref(p), w, h, depth, 1, 1)
+
+
+def _bursts(settings, frames, sizes, kernel=0, pads=(0,)):
+    """frames through one filter in device-resident bursts of the given sizes (one process_dev call each); input i's
+    rows are padded by pads[i % len(pads)] samples, so that pitches mix inside a burst"""
+    import torch
+    h, w = frames[0][0].shape
+    wide = frames[0][0].dtype == np.uint16
+    depth = 10 if wide else 8
+    tdt = torch.int16 if wide else torch.uint8
+    ctx = hip.Ctx(0)
+    flt = _make(ctx, settings, w, h, depth)
+    out = []
+    try:
+        hip.lib().hbhip_deband_set_kernel.argtypes = [C.c_void_p, C.c_int]
+        rc = hip.lib().hbhip_deband_set_kernel(flt.h, kernel)
+        if rc != 0:
+            return None
+        at = 0
+        for n in sizes:
+            part = frames[at:at + n]
+            dev_in, keep = [], []
+            for i, f in enumerate(part):
+                pad = pads[(at + i) % len(pads)]
+                planes = []
+                for p in f:
+                    full = torch.zeros((p.shape[0], p.shape[1] + pad), dtype=tdt, device="cuda")
+                    full[:, :p.shape[1]] = torch.from_numpy(p.view(np.int16) if wide else p).cuda()
+                    keep.append(full)
+                    planes.append(full[:, :p.shape[1]])
+                dev_in.append(planes)
+            at += n
+            outs = [[torch.full(p.shape, 7, dtype=tdt, device="cuda") for p in f] for f in part]
+            torch.cuda.synchronize()
+            arr_in = (hip.DevFrame * n)(*[hip.dev_frame(f) for f in dev_in])
+            arr_out = (hip.DevFrame * n)(*[hip.dev_frame(o) for o in outs])
+            assert flt.process_dev(arr_in, 0, arr_out) == n
+            ctx.sync()
+            conv = (lambda t: t.cpu().numpy().view(np.uint16)) if wide else (lambda t: t.cpu().numpy())
+            out += [[conv(p) for p in o] for o in outs]
+            for f, d in zip(part, dev_in):                               # out of place: the inputs are untouched
+                for c in range(3):
+                    np.testing.assert_array_equal(conv(d[c]), f[c])
+        return out
+    finally:
+        flt.close()
+        ctx.close()
+
+
+@pytest.mark.parametrize("rng", [16, 0, 1, -1, -16, 127, 128, 200, 5000, 1 << 30])
+def test_ranges_on_both_kernels(built, rng):
+    """every range of the CPU table test: int8 and int16 tables, the clamp, the LDS tile where its halo fits and the
+    global gather everywhere"""
+    frames = synth.stream("banded", 256, 144, 3, cfg=9)
+    st = f"range={rng}:1thr=0.05:2thr=0.05:3thr=0.05"
+    want = model(frames, st)
+    gather = _bursts(st, frames, [3], kernel=2, pads=(0, 3))
+    check(gather, want, f"gather range {rng}")
+    tile = _bursts(st, frames, [3], kernel=1, pads=(0, 3))
+    if abs(rng) <= 16:
+        assert tile is not None                                          # the default range's halo fits the tile
+    if tile is not None:
+        check(tile, want, f"tile range {rng}")
+    auto = _bursts(st, frames, [3], kernel=0)
+    check(auto, want, f"auto range {rng}")
+
+
+@pytest.mark.parametrize("st", ["", "blur=0:range=24", "range=-9:blur=1"])
+@pytest.mark.parametrize("depth", [8, 10])
+def test_bursts_equal_frame_by_frame(built, st, depth):
+    frames = synth.stream("banded", 320, 200, 20, depth=depth)
+    want = model(frames, st, depth)
+    for kernel in (0, 2):
+        check(_bursts(st, frames, [1, 3, 16], kernel=kernel, pads=(0, 0, 64, 5)), want, f"bursts 1/3/16 kernel {kernel}")
+    check(_bursts(st, frames, [1] * 20), want, "frame by frame")
+
+
+# ---- inside device-resident runs --------------------------------------------------------------------------------------
+def test_device_run_between_decomb_and_nlmeans(built):
+    """[upload, decomb, deband, nlmeans, download] equals decomb and nlmeans on host frames with the model between"""
+    TFF = 0x0008
+    frames = synth.stream("interlaced", 320, 184, 6)
+    st = ""
+    UP, DOWN = ("hb_filter_hip_upload", ""), ("hb_filter_hip_download", "")
+    dev = hbrt.run_stream(hip.filters(), [UP, ("hb_filter_decomb_hip", "mode=31"), (DROPIN, st),
+                                          ("hb_filter_nlmeans_hip", hip.NLMEANS_MEDIUM), DOWN], frames, flags=TFF)
+    mid = hbrt.run_stream(hip.filters(), [("hb_filter_decomb_hip", "mode=31")], frames, flags=TFF)
+    deb = [dm.deband_frame(m.planes, st, 8) for m in mid]
+    assert any(not np.array_equal(d[0], m.planes[0]) for d, m in zip(deb, mid))
+    want = hbrt.run_stream(hip.filters(), [("hb_filter_nlmeans_hip", hip.NLMEANS_MEDIUM)], deb, flags=TFF)
+    check(dev, [w.planes for w in want], "device run")
+
+
+VFR = 11
+UPN, DOWNN = "HIP upload adapter", "HIP download adapter"
+
+
+@pytest.fixture()
+def job_filters(built):
+    import oracle_lib as ol
+    if ol.ref() is None:
+        pytest.skip("oracle/_ref not built (no /root/reference)")
+    from test_job_swap_cpu import REF
+    hip.filters()
+    hbrt.register_filters(ol.ref(), REF)
+    hbrt.register_filters(ol.ref(), {VFR: "hb_filter_vfr"})
+    # crop/scale and deband are alias filters in the reference (settings for the combined avfilter graph; FFmpeg is
+    # not in the image): the ids resolve to the drop-ins themselves, which the swap then leaves in place
+    hbrt.register_filters(hip.filters(), {hbrt.FILTER_ID["crop_scale"]: "hb_filter_crop_scale_hip", 13: DROPIN})
+    yield ol
+    hbrt.register_filters(ol.ref(), {VFR: None})
+    hbrt.register_filters(ol.ref(), {k: None for k in REF})
+    hbrt.register_filters(hip.filters(), {hbrt.FILTER_ID["crop_scale"]: None, 13: None})
+
+
+@pytest.mark.parametrize("vfr", ["mode=0:rate=30000/1001", "mode=1:rate=90000/1001"], ids=["same_as_source", "constant_dup"])
+def test_job_with_deband_stays_one_device_run(job_filters, vfr):
+    """[decomb 31, vfr, deband, nlmeans, crop_scale, lapsharp] through the plugin surface: one upload / download pair
+    around all six, and the pictures of the CPU job before deband, the model, and the CPU job after it.  With vfr
+    duplicating frames (one shared device picture) no picture is debanded twice."""
+    ol = job_filters
+    F = hbrt.FILTER_ID
+    TFF = 0x0008
+    NLM = hip.NLMEANS_MEDIUM + ":threads=2"
+    LAP = "y-strength=0.2:y-kernel=isolap:cb-strength=0.2:cb-kernel=isolap"
+    st = "1thr=0.02:2thr=0.02:3thr=0.02:4thr=0.02:range=16:blur=1"
+    frames = synth.stream("interlaced", 320, 184, 9, cfg=3)
+    filters = [(F["decomb"], "mode=31"), (VFR, vfr), (F["deband"], st), (F["nlmeans"], NLM),
+               (F["crop_scale"], "width=640:height=368"), (F["lapsharp"], LAP)]
+    with hbrt.Job(filters, 320, 184, use_hip=True) as job:
+        names = job.stages()
+    assert names.count(UPN) == 1 and names.count(DOWNN) == 1 and names[0] == UPN and names[-1] == DOWNN
+    assert "Deband (HIP)" in names and len(names) == 8
+    _, out = hbrt.run_job(filters, frames, flags=TFF, use_hip=True)
+    _, mid = hbrt.run_job([(F["decomb"], "mode=31"), (VFR, vfr)], frames, flags=TFF, use_hip=False)
+    deb = [dm.deband_frame(m.planes, st, 8) for m in mid]
+    den = hbrt.run_stream(ol.ref(), [("hb_filter_nlmeans", NLM)], deb, flags=TFF)
+    scaled = [ol.orc_cropscale_frame(d.planes, width=640, height=368) for d in den]
+    want = hbrt.run_stream(ol.ref(), [("hb_filter_lapsharp", LAP)], scaled)
+    assert len(out) == len(want) == len(mid) > 0
+    if vfr.startswith("mode=1"):
+        assert len(mid) > len(frames)                                    # vfr did duplicate
+    for o, wt, m in zip(out, want, mid):
+        assert (o.start, o.stop) == (m.start, m.stop)
+        for c in range(3):
+            np.testing.assert_array_equal(o.planes[c], wt.planes[c])

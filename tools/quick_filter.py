@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times one stateless filter's batch path (16 device-resident 1080p frames per call) with the context's kernel timer.
 usage: quick_filter.py unsharp|chroma_smooth|lapsharp|colorspace_sdr|colorspace_matrix|grayscale|rotate|scale<W>x<H>|
-                      deblock_<preset>_<tune>[_10] [reps]
+                      deblock_<preset>_<tune>[_10]|deband[_<range>][_10][_tile|_gather] [reps]
 Prints one line per kernel: name, launches, average us.  For knob experiments with tools/dev_run.sh."""
 import ctypes as C, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -104,6 +104,29 @@ def main():
         make = lambda: hip._create("hbhip_deblock_create", ctx, [C.c_void_p, C.POINTER(hip.DeblockParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
                                    ctx.h, C.byref(dp), W, H, depth_in, 1, 1)
         picture = "blocky"
+    elif what.startswith("deband"):                    # deband[_<range>][_10][_tile|_gather]: deband, deband_10, deband_64_gather ...
+        parts = what.split("_")[1:]
+        kernel = {"tile": 1, "gather": 2}.get(parts[-1], 0) if parts else 0
+        if kernel:
+            parts = parts[:-1]
+        depth_in = depth_out = 10 if parts and parts[-1] == "10" else 8
+        if depth_in == 10:
+            parts = parts[:-1]
+        rng = int(parts[0]) if parts else 16
+        bp = hip.DebandParams()
+        F = hip.filters()
+        F.hbhip_deband_params_from_settings.argtypes = [C.c_char_p, C.c_int, C.POINTER(hip.DebandParams)]
+        if F.hbhip_deband_params_from_settings(f"range={rng}".encode(), depth_in, C.byref(bp)):
+            raise SystemExit("deband declines " + what)
+
+        def make():
+            f = hip._create("hbhip_deband_create", ctx, [C.c_void_p, C.POINTER(hip.DebandParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
+                            ctx.h, C.byref(bp), W, H, depth_in, 1, 1)
+            hip.lib().hbhip_deband_set_kernel.argtypes = [C.c_void_p, C.c_int]
+            if hip.lib().hbhip_deband_set_kernel(f.h, kernel):
+                raise SystemExit("no such kernel for " + what)
+            return f
+        picture = "banded"
     elif what in ("yadif", "yadif_bob", "bwdif"):
         return deint(ctx, what, reps)
     else:
