@@ -32,6 +32,7 @@
 // the chain is resolved with a prefix composition of 2-state maps, the carry running
 // from chunk to chunk.
 #include "eedi2_vote.h"
+#include "eedi2_dense.h"
 #include "eedi2_engine.h"
 
 #include <atomic>
@@ -880,9 +881,13 @@ __device__ __forceinline__ int calc_dir_search(const uint32_t *tr, PASS pass, in
 // Keys as in calc_dir_search, the tag riding in every P and Q (v_sad_hi_u8's addend): b, d and e collect four tags,
 // a and c six.  A step a pixel does not take (PRED: its bit in `up` / `dn` - the complement of the step set, bit d for
 // u = +d / -d) gets 2^30 added to its five sums and cannot win; a wave whose pixels all take every step skips that.
+// A trip walks the rows top to bottom (CdRun, eedi2_dense.h): one table row in, the four SADs of a row pair, the partial
+// sums that end at it, and the ten candidates of the row they complete folded into its five keys.  What lives across the
+// walk is the keys, the thread's own triples and a window of four row pairs, not every row's SADs and candidates at once:
+// 89 registers at R = 4 (121 when a trip built whole arrays), 106 - 119 at R = 8 (203).
 // At R = 8 that is 199 vector instructions a trip (two steps of 8 x 64 pixels) = 41 vector-ALU cycles per 64 pixel-steps
-// by the instruction classes of tools/valu_rate.hip, against 103 in the list form; at R = 4 (what runs: registers, see
-// the launch) 128 a trip = 53.
+// by the instruction classes of tools/valu_rate.hip, against 103 in the list form; at R = 4 (what runs, see the launch)
+// 128 a trip = 53.
 template <int R, bool PRED>
 __device__ __forceinline__ void calc_dir_dense(const uint32_t *tr, int maxdt, const uint32_t (&up)[R], const uint32_t (&dn)[R],
                                                int nt13, int nt19, uint32_t (&ka)[R], uint32_t (&kb)[R], uint32_t (&kc)[R],
@@ -901,137 +906,73 @@ __device__ __forceinline__ void calc_dir_dense(const uint32_t *tr, int maxdt, co
         kb[j] = (uint32_t)min(nt13, vert * 6) << 16; ka[j] = (uint32_t)min(nt19, vert * 9) << 16;
         kc[j] = ka[j]; kd[j] = kb[j]; ke[j] = kb[j];
     }
-    // the five sums of every row from the P / Q of one step; X: the poison of the rows that do not take it
-    auto sums = [&](const uint32_t (&Pv)[NE], const uint32_t (&Qv)[NE], const uint32_t (&X)[R], uint32_t (&ca)[R], uint32_t (&cb)[R],
-                    uint32_t (&cc)[R], uint32_t (&cd)[R], uint32_t (&ce)[R]) {
-        uint32_t S[NE], P2[NE - 1], Q2[NE - 1];
-#pragma unroll
-        for (int r = 0; r < NE; r++) S[r] = Pv[r] + Qv[r];
-#pragma unroll
-        for (int r = 0; r < NE - 1; r++) { P2[r] = Pv[r] + Pv[r + 1]; Q2[r] = Qv[r] + Qv[r + 1]; }
-        if (PRED)
-        {
-#pragma unroll
-            for (int j = 0; j < R; j++)
-            {
-                cb[j] = S[j + 1] + S[j + 2] + X[j]; ca[j] = cb[j] + S[j]; cc[j] = cb[j] + S[j + 3];
-                ce[j] = P2[j] + P2[j + 2] + X[j];   cd[j] = Q2[j] + Q2[j + 2] + X[j];
-            }
-        }
-        else
-        {
-            // diffc of a row is diffa of the next one
-            uint32_t S2[NE - 1], S3[NE - 2];
-#pragma unroll
-            for (int r = 0; r < NE - 1; r++) S2[r] = S[r] + S[r + 1];
-#pragma unroll
-            for (int r = 0; r < NE - 2; r++) S3[r] = S2[r] + S[r + 2];
-#pragma unroll
-            for (int j = 0; j < R; j++)
-            {
-                cb[j] = S2[j + 1]; ca[j] = S3[j]; cc[j] = S3[j + 1];
-                ce[j] = P2[j] + P2[j + 2]; cd[j] = Q2[j] + Q2[j + 2];
-            }
-        }
-    };
-    uint32_t X1[R], X2[R];
-#pragma unroll
-    for (int j = 0; j < R; j++) { X1[j] = 0; X2[j] = 0; }
+    // u = 0: both sides are the thread's own column, one direction
     {
-        // u = 0: both sides are the thread's own column
-        uint32_t Pv[NE], ca[R], cb[R], cc[R], cd[R], ce[R];
+        CdRun<R, PRED> run;
 #pragma unroll
-        for (int r = 0; r < NE; r++) Pv[r] = SADH(T[r], T[r + 1], 32u);
-        if (PRED)
+        for (int r = 0; r < NE; r++)
         {
-#pragma unroll
-            for (int j = 0; j < R; j++) X1[j] = (up[j] << 30) & 0x40000000u;
-        }
-        sums(Pv, Pv, X1, ca, cb, cc, cd, ce);
-#pragma unroll
-        for (int j = 0; j < R; j++)
-        {
-            ka[j] = min(ka[j], ca[j]); kb[j] = min(kb[j], cb[j]); kc[j] = min(kc[j], cc[j]);
-            kd[j] = min(kd[j], cd[j]); ke[j] = min(ke[j], ce[j]);
+            const uint32_t Pv = SADH(T[r], T[r + 1], 32u);
+            run.push(r, Pv, Pv);
+            if (r >= 3)
+            {
+                const int j = r - 3;
+                const uint32_t X = PRED ? (up[j] << 30) & 0x40000000u : 0u;
+                uint32_t ca, cb, cc, cd, ce;
+                run.cands(j, X, ca, cb, cc, cd, ce);
+                ka[j] = min(ka[j], ca); kb[j] = min(kb[j], cb); kc[j] = min(kc[j], cc); kd[j] = min(kd[j], cd); ke[j] = min(ke[j], ce);
+                CD_FENCE_KEYS(j);
+            }
         }
     }
     for (int d = 1; d <= maxdt; d++)
     {
         const uint32_t *tp = tr + d, *tm = tr - d;
-        uint32_t Pl[NS], Mi[NS];
-#pragma unroll
-        for (int r = 0; r < NS; r++) { Pl[r] = tp[r * CD_LW]; Mi[r] = tm[r * CD_LW]; }
-        const uint32_t t1 = 32u + (uint32_t)d, t2 = 32u - (uint32_t)d;
-        uint32_t P1[NE], Q1[NE], Pn[NE], Qn[NE];
+        const uint32_t t1 = 32u + (uint32_t)d, t2 = 32u - (uint32_t)d, sh = 30u - (uint32_t)d;
+        CdRun<R, PRED> pos, neg;                                          // u = +d, u = -d
+        uint32_t Pl0 = tp[0], Mi0 = tm[0], Pl1 = tp[CD_LW], Mi1 = tm[CD_LW];
 #pragma unroll
         for (int r = 0; r < NE; r++)
         {
-            P1[r] = SADH(T[r], Mi[r + 1], t1); Q1[r] = SADH(Pl[r], T[r + 1], t1);      // u = +d: x - u left, x + u right
-            Pn[r] = SADH(T[r], Pl[r + 1], t2); Qn[r] = SADH(Mi[r], T[r + 1], t2);      // u = -d: the sides change places
-        }
-        if (PRED)
-        {
-            const uint32_t sh = 30u - (uint32_t)d;
-#pragma unroll
-            for (int j = 0; j < R; j++) { X1[j] = (up[j] << sh) & 0x40000000u; X2[j] = (dn[j] << sh) & 0x40000000u; }
-        }
-#ifdef CD_SEQ
-        // development form: u = +d and u = -d one after the other, so that only one direction's SADs
-        // and candidates are live at a time (5 R more v_min, ~5 R + 2 (R + 3) fewer live registers); measured in
-        // profiles/r6Z_calcdir_seq.log
-        (void)P1; (void)Q1; (void)Pn; (void)Qn;
-        {
-            uint32_t Pa[NE], Qa[NE], ca[R], cb[R], cc[R], cd[R], ce[R];
-#pragma unroll
-            for (int r = 0; r < NE; r++) { Pa[r] = SADH(T[r], Mi[r + 1], t1); Qa[r] = SADH(Pl[r], T[r + 1], t1); }
-            if (PRED)
+            // one table row in (read a row ahead), the four SADs of a row pair, the partial sums ending at it, and the ten
+            // candidates of the row they complete
+            uint32_t Pl2 = 0, Mi2 = 0;
+            if (r + 2 < NS) { Pl2 = tp[(r + 2) * CD_LW]; Mi2 = tm[(r + 2) * CD_LW]; }
+            pos.push(r, SADH(T[r], Mi1, t1), SADH(Pl0, T[r + 1], t1));      // u = +d: x - u left, x + u right
+            neg.push(r, SADH(T[r], Pl1, t2), SADH(Mi0, T[r + 1], t2));      // u = -d: the sides change places
+            Pl0 = Pl1; Mi0 = Mi1; Pl1 = Pl2; Mi1 = Mi2;
+            if (r >= 3)
             {
-                const uint32_t sh = 30u - (uint32_t)d;
-#pragma unroll
-                for (int j = 0; j < R; j++) X1[j] = (up[j] << sh) & 0x40000000u;
+                const int j = r - 3;
+                const uint32_t X1 = PRED ? (up[j] << sh) & 0x40000000u : 0u, X2 = PRED ? (dn[j] << sh) & 0x40000000u : 0u;
+                uint32_t ca, cb, cc, cd, ce, na, nb, nc, nd, ne;
+                pos.cands(j, X1, ca, cb, cc, cd, ce);
+                neg.cands(j, X2, na, nb, nc, nd, ne);
+                ka[j] = min(ka[j], min(ca, na)); kb[j] = min(kb[j], min(cb, nb)); kc[j] = min(kc[j], min(cc, nc));
+                kd[j] = min(kd[j], min(cd, nd)); ke[j] = min(ke[j], min(ce, ne));
+                CD_FENCE_KEYS(j);
             }
-            sums(Pa, Qa, X1, ca, cb, cc, cd, ce);
-#pragma unroll
-            for (int j = 0; j < R; j++)
-            {
-                ka[j] = min(ka[j], ca[j]); kb[j] = min(kb[j], cb[j]); kc[j] = min(kc[j], cc[j]);
-                kd[j] = min(kd[j], cd[j]); ke[j] = min(ke[j], ce[j]);
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < R; j++) asm volatile("" : "+v"(ka[j]), "+v"(kb[j]), "+v"(kc[j]), "+v"(kd[j]), "+v"(ke[j]));
-        __builtin_amdgcn_sched_barrier(0);
-        {
-            uint32_t Pa[NE], Qa[NE], ca[R], cb[R], cc[R], cd[R], ce[R];
-#pragma unroll
-            for (int r = 0; r < NE; r++) { Pa[r] = SADH(T[r], Pl[r + 1], t2); Qa[r] = SADH(Mi[r], T[r + 1], t2); }
-            if (PRED)
-            {
-                const uint32_t sh = 30u - (uint32_t)d;
-#pragma unroll
-                for (int j = 0; j < R; j++) X2[j] = (dn[j] << sh) & 0x40000000u;
-            }
-            sums(Pa, Qa, X2, ca, cb, cc, cd, ce);
-#pragma unroll
-            for (int j = 0; j < R; j++)
-            {
-                ka[j] = min(ka[j], ca[j]); kb[j] = min(kb[j], cb[j]); kc[j] = min(kc[j], cc[j]);
-                kd[j] = min(kd[j], cd[j]); ke[j] = min(ke[j], ce[j]);
-            }
-        }
-        continue;
-#endif
-        uint32_t ca[R], cb[R], cc[R], cd[R], ce[R], na[R], nb[R], nc[R], nd[R], ne[R];
-        sums(P1, Q1, X1, ca, cb, cc, cd, ce);
-        sums(Pn, Qn, X2, na, nb, nc, nd, ne);
-#pragma unroll
-        for (int j = 0; j < R; j++)
-        {
-            ka[j] = min(ka[j], min(ca[j], na[j])); kb[j] = min(kb[j], min(cb[j], nb[j])); kc[j] = min(kc[j], min(cc[j], nc[j]));
-            kd[j] = min(kd[j], min(cd[j], nd[j])); ke[j] = min(ke[j], min(ce[j], ne[j]));
         }
     }
 #undef SADH
+}
+
+// The dense search of rows J0 .. J0 + N - 1 of a column of RD rows (tr: the table at row 0) and the votes of its listed
+// pixels into out[j * CD_W]
+template <int N, bool PRED, int RD, int J0>
+__device__ __forceinline__ void calc_dir_dense_vote(const uint32_t *tr, int maxdt, const uint32_t (&up)[RD], const uint32_t (&dn)[RD],
+                                                    uint32_t act, int nt13, int nt19, uint8_t *out)
+{
+    uint32_t u[N], v[N], ka[N], kb[N], kc[N], kd[N], ke[N];
+#pragma unroll
+    for (int j = 0; j < N; j++) { u[j] = up[J0 + j]; v[j] = dn[J0 + j]; }
+    calc_dir_dense<N, PRED>(tr + J0 * CD_LW, maxdt, u, v, nt13, nt19, ka, kb, kc, kd, ke);
+#pragma unroll
+    for (int j = 0; j < N; j++)
+        if ((act >> (J0 + j)) & 1u)
+            // b, d and e hold four tags, a and c six (calc_dir_dense)
+            out[(J0 + j) * CD_W] = (uint8_t)calc_dir_vote((int)((ka[j] & 0xffffu) / 6u), (int)((kb[j] & 0xffffu) >> 2), (int)((kc[j] & 0xffffu) / 6u),
+                                                          (int)((kd[j] & 0xffffu) >> 2), (int)((ke[j] & 0xffffu) >> 2));
 }
 
 // bit t of a mask row's window: a peak among columns start + t .. + 2 (len + 2 <= 63 bits of the row's bitmap)
@@ -1192,16 +1133,17 @@ __global__ __launch_bounds__(CD_W) CD_WAVES_ATTR void k_calc_dir_rows(P3 P, int 
         }
         if (__any(act != 0))                                           // wave-uniform
         {
-            uint32_t ka[RD], kb[RD], kc[RD], kd[RD], ke[RD];
             const uint32_t *tr = &s_tri[0][b];
-            if (__all(inactive == 0)) calc_dir_dense<RD, false>(tr, maxdt, up, dn, nt13, nt19, ka, kb, kc, kd, ke);
-            else                      calc_dir_dense<RD, true>(tr, maxdt, up, dn, nt13, nt19, ka, kb, kc, kd, ke);
-#pragma unroll
-            for (int j = 0; j < RD; j++)
-                if ((act >> j) & 1u)
-                    // b, d and e hold four tags, a and c six (calc_dir_dense)
-                    s_out[j][lx] = (uint8_t)calc_dir_vote((int)((ka[j] & 0xffffu) / 6u), (int)((kb[j] & 0xffffu) >> 2), (int)((kc[j] & 0xffffu) / 6u),
-                                                          (int)((kd[j] & 0xffffu) >> 2), (int)((ke[j] & 0xffffu) >> 2));
+            if (__all(inactive == 0))
+                calc_dir_dense_vote<RD, false, RD, 0>(tr, maxdt, up, dn, act, nt13, nt19, &s_out[0][lx]);
+            else
+            {
+                // a wave with steps to leave out (5 % of the dense waves at four rows) walks its rows in halves: the
+                // poison masks of a whole column would not fit beside its keys
+                constexpr int RH = RD >= 8 ? RD / 2 : RD;
+                calc_dir_dense_vote<RH, true, RD, 0>(tr, maxdt, up, dn, act, nt13, nt19, &s_out[0][lx]);
+                if constexpr (RH < RD) calc_dir_dense_vote<RD - RH, true, RD, RH>(tr, maxdt, up, dn, act, nt13, nt19, &s_out[0][lx]);
+            }
 #ifdef HBHIP_DEV_STATS
             if (lane == 0) { CD_STAT(8, 1); CD_STAT(9, __all(inactive == 0)); }
 #endif
@@ -3641,6 +3583,9 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
         // (161), 417 at 8 (202 registers, two waves: fewer instructions - 2.75 SADs a pixel-step against 3.5 - but the
         // LDS latency of a trip shows; forced to 128 registers with spills: 334).  Thresholds of 3/8 .. 3/4 of a block's
         // pixels measure alike (the blocks are either nearly full or far from it); below 1/4 the dense form loses.
+        // The dense form as a row walk (eedi2_dense.h), per launch of 16 fields on decomb_eedi2: 317 -> 287 at 4 rows
+        // (89 registers, five waves), 295 - 299 at 8 (106 - 119, four waves: the list form of the upper half's blocks is
+        // slower at 8 rows and eats the dense form's gain).  12 rows would not leave LDS for four workgroups per CU.
         int dense_min = CD_W * 4 / 2;
 #ifdef HBHIP_DEV
         const int rows = hbhip_dev_int("HBHIP_EEDI2_CALCDIR_ROWS", 4);
