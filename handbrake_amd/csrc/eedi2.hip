@@ -22,18 +22,21 @@
 //   k_lattice_cand_q / k_lattice_resolve   eedi2_interpolate_lattice   :1148-1335
 //   k_post             eedi2_post_process :1349-1378 (normally folded into the last expand_dir_map_2x; the
 //                      eedi2_bit_blit before it, :46-68, into the dir-map filter that follows it)
-//   k_blur1 / k_derivatives / k_blur_sqrt2 / k_post_corner   post-processing 2/3: eedi2_gaussian_blur1
-//                      :1391-1527, eedi2_calc_derivatives :1760-1848, eedi2_gaussian_blur_sqrt2 :1539-1748,
-//                      eedi2_post_process_corner :1864-1904
+//   eedi_blur1 / eedi_derivatives / eedi_blur_sqrt2 / eedi_post_corner (eedi2_corner.h, shared with the 16-bit engine)
+//                      post-processing 2/3: eedi2_gaussian_blur1 :1391-1527, eedi2_calc_derivatives :1760-1848,
+//                      eedi2_gaussian_blur_sqrt2 :1539-1748, eedi2_post_process_corner :1864-1904
 //
 // interpolate_lattice rewrites its direction row in place and tests the value it
 // just wrote at x-1 (:1194), a left-to-right dependency.  Each row is given to one
 // workgroup: lanes evaluate both possible outcomes of their pixel in parallel and
 // the chain is resolved with a prefix composition of 2-state maps, the carry running
 // from chunk to chunk.
+#include "eedi2_common.h"
 #include "eedi2_vote.h"
 #include "eedi2_dense.h"
 #include "eedi2_engine.h"
+#include "eedi2_mask_cells.h"
+#include "eedi2_corner.h"
 
 #include <atomic>
 #include <algorithm>
@@ -101,7 +104,6 @@ __device__ __forceinline__ PL plane_ptrs(const P3 &P, int pl, size_t off)
     const bool maskless = (P).pflags[blockIdx.z] != (P).pepoch;             \
     (void)tff; (void)maskless
 
-__device__ __forceinline__ int iabs(int v) { return v < 0 ? -v : v; }
 __device__ __forceinline__ int hbhip_align_up_dev(int v, int a) { return (v + a - 1) / a * a; }
 
 // Slots in an LDS list for the `n` (0..7) entries of each lane, in lane order, with ONE atomic per wave: the lanes' counts
@@ -127,31 +129,9 @@ __device__ __forceinline__ int sad3(const uint8_t *a, int ai, const uint8_t *b, 
     return iabs((int)a[ai - 1] - (int)b[bi - 1]) + iabs((int)a[ai] - (int)b[bi]) + iabs((int)a[ai + 1] - (int)b[bi + 1]);
 }
 
-// insertion sort + midpoint rule (eedi2.c:65-80)
-__device__ __forceinline__ int sorted_mid(int *v, int n)
-{
-    for (int i = 1; i < n; i++)
-    {
-        const int t = v[i];
-        int j = i;
-        while (j > 0 && v[j - 1] > t) { v[j] = v[j - 1]; j--; }
-        v[j] = t;
-    }
-    return (n & 1) ? v[n >> 1] : (v[(n - 1) >> 1] + v[n >> 1] + 1) >> 1;
-}
-
-
-// Register-only variant of the two helpers above for the dir-map kernels: the candidates sit in
-// fixed slots (an absent one holds ABSENT, larger than any value and farther from any midpoint
-// than any vote limit), a sorting network orders them, and the n present values are then the
-// first n -- no data-dependent loop, no indexed register file.
+// The dir-map kernels keep their candidates in fixed slots for the sorting networks (cswap, eedi2_common.h): an absent
+// one holds ABSENT, larger than any value and farther from any midpoint than any vote limit.
 constexpr int ABSENT = 1000;
-
-__device__ __forceinline__ void cswap(int &a, int &b)
-{
-    const int lo = min(a, b), hi = max(a, b);
-    a = lo; b = hi;
-}
 
 // midpoint of the n present values among 9 slots (n >= 4); the slots end up sorted
 __device__ __forceinline__ int mid9(int &v0, int &v1, int &v2, int &v3, int &v4, int &v5, int &v6, int &v7, int &v8, int n)
@@ -169,20 +149,6 @@ __device__ __forceinline__ int mid9(int &v0, int &v1, int &v2, int &v3, int &v4,
     const bool n5 = n <= 5, n7 = n <= 7;
     const int hi = n5 ? v2 : (n7 ? v3 : v4);
     const int lo = n5 ? v1 : (n7 ? v2 : v3);
-    return (n & 1) ? hi : (lo + hi + 1) >> 1;
-}
-
-// midpoint of the n present values among 6 slots (n >= 3)
-__device__ __forceinline__ int mid6(int &v0, int &v1, int &v2, int &v3, int &v4, int &v5, int n)
-{
-    cswap(v0, v5); cswap(v1, v3); cswap(v2, v4);
-    cswap(v1, v2); cswap(v3, v4);
-    cswap(v0, v3); cswap(v2, v5);
-    cswap(v0, v1); cswap(v2, v3); cswap(v4, v5);
-    cswap(v1, v2); cswap(v3, v4);
-    // n = 3..6: lower middle index 1,1,2,2 ; upper 1,2,2,3
-    const int lo = n <= 4 ? v1 : v2;
-    const int hi = n <= 3 ? v1 : (n <= 5 ? v2 : v3);
     return (n & 1) ? hi : (lo + hi + 1) >> 1;
 }
 
@@ -266,22 +232,6 @@ __device__ __forceinline__ void st4(uint8_t *dst_at_x, const int (&out)[4], int 
 #ifndef MF_TILE_W
 #define MF_TILE_W 64
 #endif
-constexpr int MF_W = MF_TILE_W, MF_H = MF_TILE_H, MF_OX = 8, MF_OY = 4;      // tile and the LDS frame's origin offset
-constexpr int MF_LP = MF_W + 2 * MF_OX, MF_LR = MF_H + 2 * MF_OY; // the LDS frame: 80 x 24
-
-
-// The passes work on dwords.  Every value of the mask is 0 or 255, so inside the kernel a mask
-// pixel is one byte holding 0 / 1 and four of them are handled by one 32-bit operation: the 8-neighbour
-// count of erode / dilate is a sum of byte-shifted dwords (at most 8 per byte, no carries), the
-// threshold test one add (bit 7 of count + 0x80 - thr), remove_small_gaps a handful of ANDs / ORs of
-// shifted dwords.  A thread owns one dword column of the LDS frame and a strip of 4 rows; it loads the
-// 6 rows x 3 dwords around the strip once and keeps the per-row partial sums in registers.  Each pass
-// computes the whole frame minus one more row top and bottom; the cells next to the frame's left / right
-// edge come out wrong by design (they read the unwritten pad column), one byte further in per pass,
-// which the 8-byte column halo absorbs (the tile needs x0 - 3 .. x0 + MF_W + 2 from the last erode).
-constexpr int MF_DW = MF_LP / 4;                 // 20 dwords per LDS row
-constexpr int MF_DP = MF_DW + 2;                 // + one pad dword either side
-constexpr int MF_SR = MF_STRIP_ROWS;             // rows per thread and pass
 // The chain link's round trips (build knob, bits: 1 = the look at the flags of the field before goes out in front of the
 // tile's own loads, 2 = the edge tests are computed while the old mask is on its way, 4 = no look at the plane flag at the
 // tile's end - a word per tile, folded into the plane flags by the pass behind the launch).  Measured, us per 16 fields
@@ -293,63 +243,19 @@ constexpr int MF_SR = MF_STRIP_ROWS;             // rows per thread and pass
 #ifndef MF_THREADS
 #define MF_THREADS 256
 #endif
-constexpr int MF_T = MF_THREADS;                // threads: 11 strips of MF_SR rows x 20 dword columns = 220 of them work in a pass
+// the tile and its LDS frame of mask cells (eedi2_mask_cells.h, with the passes on it): 80 x 24 cells, 20 dwords a row; 11
+// strips of MF::SR rows x 20 dword columns = 220 of the threads work in a pass
+using MF = EediMaskGeo<MF_TILE_W, MF_TILE_H, MF_STRIP_ROWS, MF_THREADS>;
 // (round 2, on the 128-pixel tile as a launch per field: 4 rows per thread and 256 threads 15.0 us per launch, 2 rows and
 // 512 threads 12.6 us, 1 row and 1024 threads 12.6 us - with the all-fields launch of the upper part at 55 / 57 / 77 us
 // per 16 fields)
-
-// 0xff in byte k when lo <= X + k < hi
-__device__ __forceinline__ uint32_t mf_bytes_in(int X, int lo, int hi)
-{
-    uint32_t m = 0xffffffffu;
-    const int a = lo - X, b = hi - X;
-    if (a > 0) m = a >= 4 ? 0u : (m << (8 * a));
-    if (b < 4) m = b <= 0 ? 0u : (m & (0xffffffffu >> (8 * (4 - b))));
-    return m;
-}
 
 // the four bytes at columns X .. X + 3 with those at or beyond `width` (the row's padding) replaced by padv's: the reference's
 // memset(dstp, 255, pitch * height) writes the padding, its bit_blit of `width` columns does not
 __device__ __forceinline__ uint32_t pad_bytes(uint32_t v, int X, int width, uint32_t padv)
 {
-    const uint32_t in = mf_bytes_in(X, 0, width);
+    const uint32_t in = bytes_in(X, 0, width);
     return (v & in) | (padv & ~in);
-}
-
-// erode (GROW = false) / dilate (GROW = true) of LDS rows ra .. rb
-template <bool GROW>
-__device__ __forceinline__ void mf_morph4(const uint32_t (*src)[MF_DP], uint32_t (*dst)[MF_DP], int c4, int strip,
-                                          int ra, int rb, int thr, uint32_t px1, int fy, int height)
-{
-    const int r0 = ra + strip * MF_SR;
-    if (r0 <= rb)
-    {
-        const uint32_t K = (uint32_t)(0x80 - min(max(thr, 0), 9)) * 0x01010101u;
-        uint32_t S2[MF_SR + 2], S3[MF_SR + 2], C[MF_SR + 2];
-#pragma unroll
-        for (int i = 0; i < MF_SR + 2; i++)
-        {
-            const int r = min(r0 - 1 + i, MF_LR - 1);
-            const uint32_t l = src[r][c4], c = src[r][c4 + 1], rr = src[r][c4 + 2];
-            const uint32_t lb = __builtin_amdgcn_alignbyte(c, l, 3), rbv = __builtin_amdgcn_alignbyte(rr, c, 1);
-            C[i] = c;
-            S2[i] = lb + rbv;
-            S3[i] = S2[i] + c;
-        }
-#pragma unroll
-        for (int i = 0; i < MF_SR; i++)
-        {
-            const int r = r0 + i;
-            if (r > rb) break;
-            const int y = fy + r;
-            const uint32_t count = S3[i] + S2[i + 1] + S3[i + 2];
-            const uint32_t ge = ((count + K) >> 7) & 0x01010101u;          // count >= thr, per byte
-            const uint32_t pm = (y >= 1 && y < height - 1) ? px1 : 0u;
-            const uint32_t c = C[i + 1];
-            dst[r][c4 + 1] = GROW ? (c | (ge & pm)) : (c & ~((ge ^ 0x01010101u) & pm));
-        }
-    }
-    __syncthreads();
 }
 
 // The field extraction (eedi2_fill_half, decomb_template.c:455-473) rides along: the source rows are read from the
@@ -367,23 +273,22 @@ struct MaskSrc { const uint8_t *frame[EEDI_MAX_FIELDS][3]; int spitch[3]; };
 template <bool CHAIN>
 __device__ __forceinline__ void mask_tile(const P3 &P, const MaskSrc &S, const MaskChain &C, int fld, int pl, int bx, int by,
                                           int mth, int vth, int lth, int erode_thr, int dilate_thr,
-                                          uint32_t (*s_src)[MF_DP], uint32_t (*s_a)[MF_DP], uint32_t (*s_b)[MF_DP])
+                                          uint32_t (*s_src)[MF::DP], uint32_t (*s_a)[MF::DP], uint32_t (*s_b)[MF::DP])
 {
     const int pitch = P.pitch[pl], width = P.width[pl], height = P.height[pl];
-    const int x0 = bx * MF_W, y0 = by * MF_H;
-    const bool upper = y0 + MF_H + MF_OY <= height / 2;            // no row of the LDS frame reaches the kept half
+    const int x0 = bx * MF::W, y0 = by * MF::H;
+    const bool upper = y0 + MF::H + MF::OY <= height / 2;            // no row of the LDS frame reaches the kept half
     const size_t foff = (size_t)fld * P.fstride;
     const uint8_t *oldm = fld == 0 ? P.b[pl] : P.c[pl] + foff - P.fstride;
     const uint8_t *frame = S.frame[fld][pl];
     const int start_line = (int)(((P.tffbits >> fld) & 1u) ^ 1u);
     uint8_t *srcp = P.a[pl] + foff, *newm = P.c[pl] + foff;
-    const int t = threadIdx.x, fx = x0 - MF_OX, fy = y0 - MF_OY;
+    const int t = threadIdx.x, fx = x0 - MF::OX, fy = y0 - MF::OY;
 
-    // The LDS frame is MF_LR x MF_DW = 480 dwords for 256 threads: two per thread (MF_LD).  All loads of a thread go out before
+    // The LDS frame is MF::LR x MF::DW = 480 dwords for 256 threads: two per thread (MF_LD).  All loads of a thread go out before
     // anything is done with the first (as a loop, the store of SRCPF between them made the second wait for the first:
     // two round trips in a row, and again for the old mask - on the chain's critical path from tile to tile).
-    constexpr int MF_LD = (MF_LR * MF_DW + MF_T - 1) / MF_T;     // frame dwords per thread (two for the 16-row tile)
-    static_assert(((MF_LR - 2 + MF_SR - 1) / MF_SR) * MF_DW <= MF_T, "a thread per strip and dword column");
+    constexpr int MF_LD = (MF::LR * MF::DW + MF::T - 1) / MF::T;     // frame dwords per thread (two for the 16-row tile)
     int fr[MF_LD], fc[MF_LD], fyy[MF_LD], fxx[MF_LD];
     bool fin[MF_LD];
     uint32_t sv[MF_LD];
@@ -400,9 +305,9 @@ __device__ __forceinline__ void mask_tile(const P3 &P, const MaskSrc &S, const M
 #pragma unroll
     for (int k = 0; k < MF_LD; k++)
     {
-        const int i = t + MF_T * k;
-        fin[k] = i < MF_LR * MF_DW;
-        fr[k] = i / MF_DW; fc[k] = i - fr[k] * MF_DW;
+        const int i = t + MF::T * k;
+        fin[k] = i < MF::LR * MF::DW;
+        fr[k] = i / MF::DW; fc[k] = i - fr[k] * MF::DW;
         fyy[k] = fy + fr[k]; fxx[k] = fx + 4 * fc[k];
         sv[k] = 0;
         if (fin[k] && fyy[k] >= 0 && fyy[k] < height && fxx[k] >= 0 && fxx[k] < width)
@@ -416,7 +321,7 @@ __device__ __forceinline__ void mask_tile(const P3 &P, const MaskSrc &S, const M
         if (x + 3 >= width && x < width) sv[k] &= 0xffffffffu >> (8 * (x + 4 - width));
         // the tile's own cells go out as SRCPF (every cell of the plane belongs to exactly one tile)
         if (y >= 0 && y < height && x >= 0 && x < pitch &&
-            r >= MF_OY && r < MF_OY + MF_H && c4 >= MF_OX / 4 && c4 < (MF_OX + MF_W) / 4)
+            r >= MF::OY && r < MF::OY + MF::H && c4 >= MF::OX / 4 && c4 < (MF::OX + MF::W) / 4)
             *reinterpret_cast<uint32_t *>(srcp + (size_t)y * pitch + x) = sv[k];
         s_src[r][c4 + 1] = sv[k];
     }
@@ -445,23 +350,23 @@ __device__ __forceinline__ void mask_tile(const P3 &P, const MaskSrc &S, const M
         __syncthreads();
     }
 
-    const int c4 = t % MF_DW, strip = t / MF_DW;               // strips past the frame have no rows in any pass
+    const int c4 = t % MF::DW, strip = t / MF::DW;               // strips past the frame have no rows in any pass
     const int X = fx + 4 * c4;
-    const uint32_t px1 = mf_bytes_in(X, 1, width - 1) & 0x01010101u;
+    const uint32_t px1 = bytes_in(X, 1, width - 1) & 0x01010101u;
 
     // build_edge_mask (:122-195), in place on the old mask; LDS rows 1 .. 22
-    uint32_t edges[MF_SR];
+    uint32_t edges[MF::SR];
 #pragma unroll
-    for (int i = 0; i < MF_SR; i++) edges[i] = 0;
+    for (int i = 0; i < MF::SR; i++) edges[i] = 0;
     {
-        const int r0 = 1 + strip * MF_SR;
-        if (r0 <= MF_LR - 2)
+        const int r0 = 1 + strip * MF::SR;
+        if (r0 <= MF::LR - 2)
         {
-            int b[MF_SR + 2][6], q[MF_SR + 2][6];
+            int b[MF::SR + 2][6], q[MF::SR + 2][6];
 #pragma unroll
-            for (int i = 0; i < MF_SR + 2; i++)
+            for (int i = 0; i < MF::SR + 2; i++)
             {
-                const int r = min(r0 - 1 + i, MF_LR - 1);
+                const int r = min(r0 - 1 + i, MF::LR - 1);
                 const uint32_t l = s_src[r][c4], c = s_src[r][c4 + 1], rr = s_src[r][c4 + 2];
                 b[i][0] = (int)(l >> 24);
                 b[i][1] = (int)(c & 0xffu); b[i][2] = (int)((c >> 8) & 0xffu); b[i][3] = (int)((c >> 16) & 0xffu); b[i][4] = (int)(c >> 24);
@@ -470,10 +375,10 @@ __device__ __forceinline__ void mask_tile(const P3 &P, const MaskSrc &S, const M
                 for (int j = 0; j < 6; j++) q[i][j] = b[i][j] * b[i][j];
             }
 #pragma unroll
-            for (int i = 0; i < MF_SR; i++)
+            for (int i = 0; i < MF::SR; i++)
             {
                 const int r = r0 + i;
-                if (r > MF_LR - 2) break;
+                if (r > MF::LR - 2) break;
                 const int y = fy + r;
                 const int (&Pr)[6] = b[i], (&Cr)[6] = b[i + 1], (&Nr)[6] = b[i + 2];
                 // the three samples of a column: all pairwise differences below 10 (:157-160) is max - min < 10, and the largest
@@ -526,14 +431,14 @@ __device__ __forceinline__ void mask_tile(const P3 &P, const MaskSrc &S, const M
         // (an upper tile: zeros in those two rows, the edges everywhere else - no cell is written twice, no barrier)
 #pragma unroll
         for (int k = 0; k < MF_LD; k++)
-            if (fin[k] && (!upper || fr[k] == 0 || fr[k] == MF_LR - 1)) s_a[fr[k]][fc[k] + 1] = upper ? 0u : mv[k] & 0x01010101u;
+            if (fin[k] && (!upper || fr[k] == 0 || fr[k] == MF::LR - 1)) s_a[fr[k]][fc[k] + 1] = upper ? 0u : mv[k] & 0x01010101u;
         if (!upper) __syncthreads();
-        const int r0 = 1 + strip * MF_SR;
+        const int r0 = 1 + strip * MF::SR;
 #pragma unroll
-        for (int i = 0; i < MF_SR; i++)
+        for (int i = 0; i < MF::SR; i++)
         {
             const int r = r0 + i;
-            if (r > MF_LR - 2) break;
+            if (r > MF::LR - 2) break;
             if (upper) { s_a[r][c4 + 1] = edges[i]; continue; }
             const uint32_t keep = (fy + r < height / 2) ? 0u : s_a[r][c4 + 1];
             s_a[r][c4 + 1] = keep | edges[i];
@@ -541,24 +446,26 @@ __device__ __forceinline__ void mask_tile(const P3 &P, const MaskSrc &S, const M
     }
     __syncthreads();
 
-    mf_morph4<false>(s_a, s_b, c4, strip, 2, MF_LR - 3, erode_thr, px1, fy, height);
-    mf_morph4<true>(s_b, s_a, c4, strip, 3, MF_LR - 4, dilate_thr, px1, fy, height);
-    mf_morph4<false>(s_a, s_b, c4, strip, 4, MF_LR - 5, erode_thr, px1, fy, height);
+    morph4<MF, false>(s_a, s_b, c4, strip, 2, MF::LR - 3, erode_thr, px1, fy, height);
+    morph4<MF, true>(s_b, s_a, c4, strip, 3, MF::LR - 4, dilate_thr, px1, fy, height);
+    morph4<MF, false>(s_a, s_b, c4, strip, 4, MF::LR - 5, erode_thr, px1, fy, height);
 
     // remove_small_gaps (:308-342) on the tile's 16 rows x 32 dwords, straight to the new mask
     uint32_t anyset = 0;
-    for (int i = t; i < MF_H * (MF_W / 4); i += MF_T)
+    for (int i = t; i < MF::H * (MF::W / 4); i += MF::T)
     {
-        const int r = MF_OY + i / (MF_W / 4), g4 = MF_OX / 4 + (i & (MF_W / 4 - 1));
+        const int r = MF::OY + i / (MF::W / 4), g4 = MF::OX / 4 + (i & (MF::W / 4 - 1));
         const int y = fy + r, x = fx + 4 * g4;
         if (y >= height || x >= width) continue;
         const uint32_t l = s_b[r][g4], c = s_b[r][g4 + 1], rr = s_b[r][g4 + 2];
+        // small_gaps4 (eedi2_mask_cells.h) written out: behind the call this loop's instructions come out in another order
+        // and with other scalar registers, and this kernel is held to the machine code it was measured with
         const uint32_t a1 = __builtin_amdgcn_alignbyte(c, l, 3), a2 = __builtin_amdgcn_alignbyte(c, l, 2), a3 = __builtin_amdgcn_alignbyte(c, l, 1);
         const uint32_t b1 = __builtin_amdgcn_alignbyte(rr, c, 1), b2 = __builtin_amdgcn_alignbyte(rr, c, 2), b3 = __builtin_amdgcn_alignbyte(rr, c, 3);
         const uint32_t a12 = a1 | a2, a123 = a12 | a3;
         const uint32_t set = c & (a123 | b1 | b2 | b3);                               // a set pixel survives with any neighbour set
         const uint32_t fill = ((b1 & a123) | (b2 & a12) | (b3 & a1)) & (c ^ 0x01010101u);
-        const uint32_t pm = (y >= 1 && y < height - 1) ? (mf_bytes_in(x, 3, width - 3) & 0x01010101u) : 0u;
+        const uint32_t pm = (y >= 1 && y < height - 1) ? (bytes_in(x, 3, width - 3) & 0x01010101u) : 0u;
         const uint32_t res = (((set | fill) & pm) | (c & ~pm)) * 255u;
         anyset |= x + 3 < width ? res : res & (0xffffffffu >> (8 * (x + 4 - width)));
         uint8_t *d = newm + (size_t)y * pitch + x;
@@ -578,16 +485,16 @@ __device__ __forceinline__ void mask_tile(const P3 &P, const MaskSrc &S, const M
     eedi_chain_note_has(C, fld, pl, bx, by, has);
 }
 
-__global__ __launch_bounds__(MF_T) void k_mask_fused4(P3 P, MaskSrc S, int f0, int part, int mth, int vth, int lth, int erode_thr, int dilate_thr,
+__global__ __launch_bounds__(MF::T) void k_mask_fused4(P3 P, MaskSrc S, int f0, int part, int mth, int vth, int lth, int erode_thr, int dilate_thr,
                                                       uint32_t *pflags, uint32_t epoch)
 {
-    __shared__ uint32_t s_src[MF_LR][MF_DP];
-    __shared__ uint32_t s_a[MF_LR][MF_DP];
-    __shared__ uint32_t s_b[MF_LR][MF_DP];
+    __shared__ uint32_t s_src[MF::LR][MF::DP];
+    __shared__ uint32_t s_a[MF::LR][MF::DP];
+    __shared__ uint32_t s_b[MF::LR][MF::DP];
     const int zf = (int)blockIdx.z / 3, pl = (int)blockIdx.z - 3 * zf, fld = f0 + zf;   // f0: first field of this launch
-    const int x0 = blockIdx.x * MF_W, y0 = blockIdx.y * MF_H;
+    const int x0 = blockIdx.x * MF::W, y0 = blockIdx.y * MF::H;
     if (x0 >= P.width[pl] || y0 >= P.height[pl]) return;
-    const bool upper = y0 + MF_H + MF_OY <= P.height[pl] / 2;
+    const bool upper = y0 + MF::H + MF::OY <= P.height[pl] / 2;
     if (part != 0 && upper != (part == 1)) return;
     MaskChain none;
     none.pflags = pflags; none.epoch = epoch; none.has = nullptr;
@@ -595,11 +502,11 @@ __global__ __launch_bounds__(MF_T) void k_mask_fused4(P3 P, MaskSrc S, int f0, i
 }
 
 // blockIdx.x = field * C.ntiles + tile: field-major, see MaskChain
-__global__ __launch_bounds__(MF_T) void k_mask_chain(P3 P, MaskSrc S, MaskChain C, int mth, int vth, int lth, int erode_thr, int dilate_thr)
+__global__ __launch_bounds__(MF::T) void k_mask_chain(P3 P, MaskSrc S, MaskChain C, int mth, int vth, int lth, int erode_thr, int dilate_thr)
 {
-    __shared__ uint32_t s_src[MF_LR][MF_DP];
-    __shared__ uint32_t s_a[MF_LR][MF_DP];
-    __shared__ uint32_t s_b[MF_LR][MF_DP];
+    __shared__ uint32_t s_src[MF::LR][MF::DP];
+    __shared__ uint32_t s_a[MF::LR][MF::DP];
+    __shared__ uint32_t s_b[MF::LR][MF::DP];
     int fld, pl, bx, by;
     if (eedi_chain_tile(C, fld, pl, bx, by))                      // block-uniform
         mask_tile<true>(P, S, C, fld, pl, bx, by, mth, vth, lth, erode_thr, dilate_thr, s_src, s_a, s_b);
@@ -607,26 +514,16 @@ __global__ __launch_bounds__(MF_T) void k_mask_chain(P3 P, MaskSrc S, MaskChain 
         mask_tile<false>(P, S, C, fld, pl, bx, by, mth, vth, lth, erode_thr, dilate_thr, s_src, s_a, s_b);
 }
 
-// Queued behind every k_mask_chain launch, a workgroup per field and plane.
-//  * Each folds the words its plane's tiles left in C.has into the plane flag (P3::pflags: the passes behind the mask take
-//    a shortcut for a plane without a mask pixel) - the tiles themselves no longer look at the flag, which cost every
-//    workgroup of the chain a round trip at its end.
-//  * Workgroup 0 then has nothing to do unless a wait of the chain ran out (C.err).  Then the launch's lower tiles are
-//    recomputed field after field, tile after tile, by this one workgroup - program order is the dependency order, every
-//    flag already carries the epoch (each tile publishes itself, timed out or not), so the waits inside mask_tile<true>
-//    pass at once - from the same sources with the same arithmetic: the new masks end up as the per-field launches would
-//    have left them.  (The upper tiles and SRCPF never depended on another field.)  A plane flag that went up for a mask the
-//    repair empties only costs the shortcut.
-__global__ __launch_bounds__(MF_T) void k_mask_chain_repair(P3 P, MaskSrc S, MaskChain C, int nfields, int mth, int vth, int lth,
+// Queued behind every k_mask_chain launch, a workgroup per field and plane: the plane flags out of the tiles' words, and
+// the repair of a launch in which a wait of the chain ran out (eedi_chain_repair_begin, eedi2_engine.h).
+__global__ __launch_bounds__(MF::T) void k_mask_chain_repair(P3 P, MaskSrc S, MaskChain C, int nfields, int mth, int vth, int lth,
                                                             int erode_thr, int dilate_thr)
 {
-    __shared__ uint32_t s_src[MF_LR][MF_DP];
-    __shared__ uint32_t s_a[MF_LR][MF_DP];
-    __shared__ uint32_t s_b[MF_LR][MF_DP];
-    eedi_chain_fold_has(C, MF_T);
-    if (blockIdx.x != 0 || __hip_atomic_load(C.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;      // block-uniform
-    MaskChain R = C;
-    R.has = nullptr;                                               // the repaired tiles raise the plane flags themselves
+    __shared__ uint32_t s_src[MF::LR][MF::DP];
+    __shared__ uint32_t s_a[MF::LR][MF::DP];
+    __shared__ uint32_t s_b[MF::LR][MF::DP];
+    MaskChain R;
+    if (!eedi_chain_repair_begin(C, MF::T, R)) return;
     for (int fld = 0; fld < nfields; fld++)
         for (int tile = 0; tile < C.ntiles; tile++)
         {
@@ -635,11 +532,7 @@ __global__ __launch_bounds__(MF_T) void k_mask_chain_repair(P3 P, MaskSrc S, Mas
             mask_tile<true>(P, S, R, fld, pl, bx, by, mth, vth, lth, erode_thr, dilate_thr, s_src, s_a, s_b);
             __syncthreads();
         }
-    if (threadIdx.x == 0)
-    {
-        __hip_atomic_store(C.err, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(C.fallbacks, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    eedi_chain_repair_end(C);
 }
 
 // calc_directions in two launches so that no lane idles while its neighbour walks the
@@ -975,15 +868,6 @@ __device__ __forceinline__ void calc_dir_dense_vote(const uint32_t *tr, int maxd
                                                           (int)((kd[j] & 0xffffu) >> 2), (int)((ke[j] & 0xffffu) >> 2));
 }
 
-// bit t of a mask row's window: a peak among columns start + t .. + 2 (len + 2 <= 63 bits of the row's bitmap)
-__device__ __forceinline__ uint64_t calc_dir_window(const uint64_t *bits, int start, uint64_t lenmask)
-{
-    const int wq = start >> 6, sh = start & 63;
-    const uint64_t lo = bits[wq], hi = bits[wq + 1];
-    const uint64_t w = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-    return (w | (w >> 1) | (w >> 2)) & lenmask;
-}
-
 // dense_min: a block whose list holds at least this many pixels (and that touches neither the first nor the last row)
 // takes the dense form of the search (R >= 4)
 #ifndef CD_WAVES_ATTR
@@ -1245,20 +1129,8 @@ __device__ __forceinline__ uint32_t ff_bytes(uint32_t v)          // 0x80 in eve
 // network once for both), v_pk_sub / add / mad_u16 and v_bfi_b32 selects.  A slot that holds no value (the reference
 // leaves peaks out of order[], :659-668) carries PK_ABSENT, above every value and farther from every midpoint than any
 // limit (also the 255 of limlut's last entries, eedi2.c:24).
-typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
-typedef int16_t i16x2 __attribute__((ext_vector_type(2)));
+// (u16x2 and pk / un / pk1 / pk_lt / cswap2: eedi2_common.h)
 constexpr uint32_t PK_ABSENT_HI = 0x7f00u;                            // 0x00ff + 0x7f00 = 0x7fff
-__device__ __forceinline__ u16x2 pk(uint32_t v) { return __builtin_bit_cast(u16x2, v); }
-__device__ __forceinline__ uint32_t un(u16x2 v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ u16x2 pk1(uint32_t both) { return pk(both * 0x00010001u); }
-// [a < b] per half as 0 / 1 for halves below 2^15: the borrow of a - b (two packed instructions; written as a comparison
-// or as min(saturated difference, 1) the compiler unpacks it into a compare and a select per half)
-__device__ __forceinline__ u16x2 pk_lt(u16x2 a, u16x2 b) { return (u16x2)((u16x2)(a - b) >> 15); }
-__device__ __forceinline__ void cswap2(u16x2 &a, u16x2 &b)
-{
-    const u16x2 lo = __builtin_elementwise_min(a, b), hi = __builtin_elementwise_max(a, b);
-    a = lo; b = hi;
-}
 // limlut[i] (eedi2.c:21-25 as 8-bit pixels: 6 6 7 7 8 8 9 9 9 10 10 11 11 12 ... 12, then 255 255 for i = 31, 32) in
 // closed form, both halves: min(12, 6 + ((i - [i >= 8]) >> 1)), 255 from 31 on
 // (tests/test_eedi2_identities_cpu.py::test_limlut_closed_form)
@@ -1423,7 +1295,7 @@ __global__ __launch_bounds__(256) void k_dir_map4(P3 P, int step, int expand)
     const uint32_t m1 = step == 1 ? 0u : *reinterpret_cast<const uint32_t *>(mk + pitch);
     const bool up_ok = step == 1 || y > 1, dn_ok = step == 1 || y < height - 2;
     // the pixels the pass works on, one flag byte each (:658 / :738): inside the row, on the mask, and for expand a peak
-    uint32_t work = ((ff_bytes(m0) | ff_bytes(m1)) >> 7) & mf_bytes_in(x, 1, width - 1);
+    uint32_t work = ((ff_bytes(m0) | ff_bytes(m1)) >> 7) & bytes_in(x, 1, width - 1);
     if (expand) work &= ff_bytes(own) >> 7;
     uint32_t res = own;
     if (work)
@@ -1547,7 +1419,7 @@ __global__ __launch_bounds__(256) void k_dir_map_c(P3 P, int step, int expand, i
         wc[h] = wu[h] = wd[h] = Win12{ 0u, 0u, 0u };
         if (inside && row_ok)
         {
-            cand[h] = ((ff_bytes(m0[h]) | ff_bytes(m1[h])) >> 7) & mf_bytes_in(x, 1, width - 1);
+            cand[h] = ((ff_bytes(m0[h]) | ff_bytes(m1[h])) >> 7) & bytes_in(x, 1, width - 1);
             if (expand) cand[h] &= ff_bytes(own[h]) >> 7;                                  // expand only fills peak pixels
             if (cand[h])
             {
@@ -1749,7 +1621,7 @@ __global__ __launch_bounds__(256) void k_dir_map_fe(P3 P, uint32_t padv)
         const uint8_t *mk = Q.a + (size_t)y * pitch + xx;
         const uint32_t m0 = *reinterpret_cast<const uint32_t *>(STEP == 1 ? mk : mk - (ptrdiff_t)pitch);
         const uint32_t m1 = STEP == 1 ? 0u : *reinterpret_cast<const uint32_t *>(mk + pitch);
-        uint32_t work = ((ff_bytes(m0) | ff_bytes(m1)) >> 7) & mf_bytes_in(xx, 1, width - 1);
+        uint32_t work = ((ff_bytes(m0) | ff_bytes(m1)) >> 7) & bytes_in(xx, 1, width - 1);
         if (SIDE < 0) work &= 0xff000000u;
         if (SIDE > 0) work &= 0x000000ffu;
         uint32_t res = own;
@@ -1781,7 +1653,7 @@ __global__ __launch_bounds__(256) void k_dir_map_fe(P3 P, uint32_t padv)
             const uint8_t *mk = Q.a + (size_t)y * pitch + x;
             const uint32_t m0 = *reinterpret_cast<const uint32_t *>(STEP == 1 ? mk : mk - (ptrdiff_t)pitch);
             const uint32_t m1 = STEP == 1 ? 0u : *reinterpret_cast<const uint32_t *>(mk + pitch);
-            cand = ((ff_bytes(m0) | ff_bytes(m1)) >> 7) & mf_bytes_in(x, 1, width - 1);
+            cand = ((ff_bytes(m0) | ff_bytes(m1)) >> 7) & bytes_in(x, 1, width - 1);
         }
         fe_expand_row(s_f, lr, threadIdx.x, cand, STEP == 1 || y > 1, STEP == 1 || y < height - 2, s_out, s_list, &s_count);
     }
@@ -1902,7 +1774,7 @@ __global__ __launch_bounds__(256) void k_filter_map(P3 P)
         own = *reinterpret_cast<const uint32_t *>(Q.b + (size_t)y * pitch + x);
         if (y >= 1 && y < height - 1) m4 = *reinterpret_cast<const uint32_t *>(Q.a + (size_t)y * pitch + x);   // (m4 stays 0 on the first / last row)
     }
-    uint32_t cand = ((ff_bytes(m4) & ~ff_bytes(own)) >> 7) & mf_bytes_in(x, 1, width - 1);
+    uint32_t cand = ((ff_bytes(m4) & ~ff_bytes(own)) >> 7) & bytes_in(x, 1, width - 1);
     if (!__syncthreads_or(cand != 0u))                           // block-uniform
     {
         if (inside)
@@ -2092,7 +1964,7 @@ __global__ __launch_bounds__(256) void k_mark_2x4(P3 P, uint32_t padv)
     }
     // the mask first: a thread none of whose four pixels sits under or above a mask pixel writes peaks and never fetches the
     // direction rows (k_dir_map4)
-    const bool vote = rebuilt && ((ff_bytes(k0w) | ff_bytes(k1w)) & mf_bytes_in(x, 1, width - 1)) != 0u;
+    const bool vote = rebuilt && ((ff_bytes(k0w) | ff_bytes(k1w)) & bytes_in(x, 1, width - 1)) != 0u;
     Win12 wa = { 0u, 0u, 0u }, wbn = { 0u, 0u, 0u };
     if (vote)
     {
@@ -2123,7 +1995,7 @@ __global__ __launch_bounds__(256) void k_mark_2x4(P3 P, uint32_t padv)
     }
     {
         // the pixels under or above a mask pixel, one flag byte each; the vote on pixel pairs (mark_pair)
-        const uint32_t work = ((ff_bytes(k0w) | ff_bytes(k1w)) >> 7) & mf_bytes_in(x, 1, width - 1);
+        const uint32_t work = ((ff_bytes(k0w) | ff_bytes(k1w)) >> 7) & bytes_in(x, 1, width - 1);
         asm volatile("" ::: "memory");                            // keep the branch above (see k_dir_map4)
         const uint32_t p01 = mark_pair<0>(wa, wbn), p23 = mark_pair<2>(wa, wbn);
         const uint32_t votes = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
@@ -2266,7 +2138,7 @@ __global__ __launch_bounds__(FG_T) void k_fill_gaps_b(P3 P)
                 const uint32_t mcw = *reinterpret_cast<const uint32_t *>(&s_m[r + 1][c]), mnw = *reinterpret_cast<const uint32_t *>(&s_m[r + 2][c]);
                 *reinterpret_cast<uint32_t *>(&s_out[r][4 * tid]) = cw;
                 // the gap pixels among the four (direction unknown, inside the mask: :1046-1050) as byte arithmetic
-                gap = ((ff_bytes(cw) & (ff_bytes(mcw) | ff_bytes(mnw))) >> 7) & mf_bytes_in(x, 1, width - 1);
+                gap = ((ff_bytes(cw) & (ff_bytes(mcw) | ff_bytes(mnw))) >> 7) & bytes_in(x, 1, width - 1);
             }
             int at = wave_list_slots(&s_count, (unsigned)__popc(gap));
 #pragma unroll
@@ -2837,14 +2709,6 @@ __global__ __launch_bounds__(256) void k_lattice_cand_q(P3 P, uint32_t *__restri
 // through LDS and two barriers per 1024-pixel pass: 43.3 us per 16 fields, 0.62 of its issue floor.)
 constexpr int LR_T = 256, LR_ROWS = LR_T / 64, LR_PX = 4 * 64;
 
-// later o earlier: the map that applies `earlier` first (the lane / pass composition against the pixel-by-pixel
-// walk: tests/test_eedi2_identities_cpu.py::test_lattice_resolve_scan_equals_the_serial_walk,
-// tests/test_eedi2_resolve_wave_cpu.py)
-__device__ __forceinline__ unsigned lr_compose(unsigned later, unsigned earlier)
-{
-    return ((later >> (earlier & 1u)) & 1u) | (((later >> ((earlier >> 1) & 1u)) & 1u) << 1);
-}
-
 // the value of the lane to the left (wave_shr:1); lane 0 gets `first`.  Call it where every lane is active.
 __device__ __forceinline__ uint32_t lr_shr1(uint32_t v, uint32_t first)
 {
@@ -3006,118 +2870,6 @@ __global__ void k_post(P3 P)
     if (any) st4(d, out, x, width);
 }
 
-// ------------------------------------------------------------------------------------------
-// Post-processing 2/3: junctions and corners (eedi2_template.c:1391-1904; decomb_template.c:432-441).
-// The reference's three plane threads share ONE set of derivative arrays (decomb.c:398-403), so
-// its own result is a data race; what is reproduced here is the defined order "Y, Cb, Cr one
-// after the other" on the same flat arrays (oracle/ref_wrap/wrap_decomb.c:hbref_eedi2_run_serial).
-// The flat layout matters: the horizontal pass of gaussian_blur_sqrt2 reads src[x+3] instead of
-// src[x-3] at x == width-2 (:1589) — the next row, the row padding, or whatever another plane
-// left there — so the planes run one after the other and index the arrays exactly as it does.
-// Both blurs are symmetric FIRs whose out-of-range taps are mirrored about the centre (written
-// in the reference as doubled coefficients on the surviving side).
-struct CornerArgs
-{
-    uint8_t *src, *tmp;          // srcp (blurred in place) and tmpp of one plane
-    int     *c[3];               // cx2, cy2, cxy (shared by the planes)
-    int     *t[3];               // tmpc, one per array (the reference reuses one; nothing of it outlives a blur)
-    int      pitch, width, height;   // half-height geometry of the plane
-};
-
-__device__ __forceinline__ int fold_tap(int centre, int d, int n, int &hi)
-{
-    int lo = centre - d;
-    hi = centre + d;
-    if (lo < 0) lo = hi;
-    if (hi >= n) hi = lo;
-    return lo;
-}
-
-// eedi2_gaussian_blur1 (:1391-1527), one axis per launch: VERT = false src -> tmp, true tmp -> src
-template <bool VERT>
-__global__ void k_blur1(CornerArgs A)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const uint8_t *in = VERT ? A.tmp : A.src;
-    uint8_t *out = VERT ? A.src : A.tmp;
-    const int W[4] = { 26152, 15862, 3539, 291 };
-    int acc = in[(size_t)y * A.pitch + x] * W[0] + 32768;
-#pragma unroll
-    for (int d = 1; d <= 3; d++)
-    {
-        int hi;
-        const int lo = fold_tap(VERT ? y : x, d, VERT ? A.height : A.width, hi);
-        const size_t il = VERT ? (size_t)lo * A.pitch + x : (size_t)y * A.pitch + lo;
-        const size_t ih = VERT ? (size_t)hi * A.pitch + x : (size_t)y * A.pitch + hi;
-        acc += ((int)in[il] + (int)in[ih]) * W[d];
-    }
-    out[(size_t)y * A.pitch + x] = (uint8_t)(acc >> 16);
-}
-
-// eedi2_calc_derivatives (:1760-1848): differences against clamped neighbours
-__global__ void k_derivatives(CornerArgs A)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const uint8_t *s = A.src + (size_t)y * A.pitch;
-    const uint8_t *up = A.src + (size_t)max(y - 1, 0) * A.pitch, *dn = A.src + (size_t)min(y + 1, A.height - 1) * A.pitch;
-    const int ix = (int)s[min(x + 1, A.width - 1)] - (int)s[max(x - 1, 0)];
-    const int iy = (int)up[x] - (int)dn[x];
-    const size_t at = (size_t)y * A.pitch + x;
-    A.c[0][at] = (ix * ix) >> 1;
-    A.c[1][at] = (iy * iy) >> 1;
-    A.c[2][at] = (ix * iy) >> 1;
-}
-
-// eedi2_gaussian_blur_sqrt2 (:1539-1748), one axis per launch, the three arrays in blockIdx.z:
-// VERT = false c -> t (>> 16, with the x+3 read of :1589), true t -> c (>> 18)
-template <bool VERT>
-__global__ void k_blur_sqrt2(CornerArgs A)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const int *in = VERT ? A.t[blockIdx.z] : A.c[blockIdx.z];
-    int *out = VERT ? A.c[blockIdx.z] : A.t[blockIdx.z];
-    const int W[5] = { 18508, 14415, 6809, 1951, 339 };
-    int acc = in[(size_t)y * A.pitch + x] * W[0] + 32768;
-#pragma unroll
-    for (int d = 1; d <= 4; d++)
-    {
-        int hi;
-        int lo = fold_tap(VERT ? y : x, d, VERT ? A.height : A.width, hi);
-        if (!VERT && d == 3 && x == A.width - 2) lo = hi = x + 3;
-        const size_t il = VERT ? (size_t)lo * A.pitch + x : (size_t)y * A.pitch + lo;
-        const size_t ih = VERT ? (size_t)hi * A.pitch + x : (size_t)y * A.pitch + hi;
-        acc += (in[il] + in[ih]) * W[d];
-    }
-    out[(size_t)y * A.pitch + x] = acc >> (VERT ? 18 : 16);
-}
-
-// eedi2_post_process_corner (:1864-1904): msk = tmp2p2, dst = dst2p (row y from rows y+-1, which
-// belong to the kept field and are never written here).  The response is evaluated in double, in
-// the reference's operation order (int products, 0.09 * s * s, one subtraction, truncation).
-__global__ void k_post_corner(CornerArgs A, const uint8_t *msk, uint8_t *dst, int field, int height)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y * blockDim.y + threadIdx.y;
-    const int y = 8 - field + 2 * r;
-    if (x < 4 || x >= A.width - 4 || y >= height - 7) return;
-    const size_t at = (size_t)y * A.pitch + x;
-    const int m = msk[at];
-    if (m == PEAK || m == NEUTRAL) return;
-    bool hit = false;
-#pragma unroll
-    for (int k = 0; k < 2; k++)
-    {
-        const size_t i = (size_t)(3 + r + k) * A.pitch + x;
-        const int a = A.c[0][i], b = A.c[1][i], c = A.c[2][i];
-        const double s = (double)(a + b);
-        const double resp = (double)(a * b - c * c) - 0.09 * s * s;
-        hit |= (int)resp > 775;
-    }
-    if (hit) dst[at] = (uint8_t)(((int)dst[at - A.pitch] + (int)dst[at + A.pitch] + 1) >> 1);
-}
-
 } // namespace
 
 // ---- MaskChainGuard (eedi2_engine.h): what happens when a wait of the mask chain runs out ------------------------
@@ -3230,6 +2982,7 @@ int EediEngineBase::init_slots(const EediLayout &L)
     if (geo_.height % (2 << geo_.log2_ch) != 0 || geo_.height < 16 || geo_.width < 16)
         return HBHIP_ERR_UNSUPPORTED;
     if (par_.post_processing < 0 || par_.post_processing > 3) return HBHIP_ERR_UNSUPPORTED;
+    layout_ = L;
     size_t at = L.guard;
     for (auto &f : half_) at = place_frame(f, geo_.width, geo_.height / 2, at) + L.guard;     // decomb.c:291-296
     for (auto &f : full_) at = place_frame(f, geo_.width, geo_.height, at) + L.guard;         // decomb.c:299-303
@@ -3333,6 +3086,29 @@ int EediEngineBase::next_epoch(hbhip_ctx *lc, uint32_t *epoch)
     return HBHIP_OK;
 }
 
+// A mask launch for fields f0 .. of the batch: takes its number (C->epoch; for a single-field launch that and C->pflags
+// are all that means anything - with capacity 1 there are no flags and the guard is never set up) and describes its chain - the tiles of the engine's layout, field-major with a field's upper tiles behind its
+// lower ones (group), the flags, the tiles' words when `has`, and what happens when a wait runs out (guard_).
+int EediEngineBase::begin_mask(hbhip_ctx *lc, int f0, bool has, MaskChain *C)
+{
+    uint32_t epoch = 0;
+    { const int erc = next_epoch(lc, &epoch); if (erc != HBHIP_OK) return erc; }
+    *C = eedi_mask_chain_tiles(half_[0], layout_.tile_w, layout_.tile_h, layout_.tile_oy);
+    C->flags = chain_flags_;
+    C->pflags = plane_flags_ + 3 * f0;
+    C->epoch = epoch;
+    C->group = C->ntiles + C->nupper;
+    C->has = has ? chain_has_ + (size_t)f0 * C->group : nullptr;
+    guard_.bind(*C);
+    return HBHIP_OK;
+}
+
+EediMaskThresholds EediEngineBase::mask_thresholds() const
+{
+    // sic: variance and laplacian swapped (decomb_template.c:390)
+    return { par_.magnitude_threshold * 10, par_.laplacian_threshold * 81, par_.variance_threshold };
+}
+
 // ---- the 8-bit engine
 Eedi2Engine::Eedi2Engine(hbhip_ctx *ctx, const PicGeometry &geo, const Eedi2Params &p, int capacity)
     : EediEngineBase(ctx, geo, p, capacity, "decomb EEDI2")
@@ -3350,7 +3126,7 @@ int Eedi2Engine::init()
 {
     if (geo_.bps != 1) return HBHIP_ERR_UNSUPPORTED;
     if (geo_.width >= (1 << 14) || geo_.height >= (1 << 14)) return HBHIP_ERR_UNSUPPORTED;
-    const int rc = init_slots({ GUARD, sizeof(uint32_t), MF_W, MF_H, MF_OY });
+    const int rc = init_slots({ GUARD, sizeof(uint32_t), MF::W, MF::H, MF::OY });
     if (rc != HBHIP_OK) return rc;
     if (par_.maximum_search_distance > CD_HALO - 2)
     {
@@ -3490,33 +3266,24 @@ int Eedi2Engine::enqueue_mask(int f0, int n, hbhip_ctx *lc, hipStream_t st, uint
     for (int f = 0; f < n; f++) for (int c = 0; c < 3; c++) S.frame[f][c] = src_frame_[f0 + f][c];
     P.fstride = slot_bytes_;
     P.tffbits = tffbits_ >> f0;
-    const int mth = par_.magnitude_threshold * 10, vth = par_.laplacian_threshold * 81, lth = par_.variance_threshold;   // sic: swapped (decomb_template.c:390)
-    const unsigned gx = (srcp.width[0] + MF_W - 1) / MF_W, gy = (srcp.height[0] + MF_H - 1) / MF_H;
-    uint32_t epoch = 0;
-    { const int erc = next_epoch(lc, &epoch); if (erc != HBHIP_OK) return erc; }
-    *epoch_out = epoch;
-    uint32_t *pflags = plane_flags_ + 3 * f0;
+    MaskChain C;
+    { const int erc = begin_mask(lc, f0, (MF_OPT & 4) != 0, &C); if (erc != HBHIP_OK) return erc; }
+    *epoch_out = C.epoch;
+    const EediMaskThresholds th = mask_thresholds();
     if (n == 1)
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_mask_passes", k_mask_fused4, dim3(gx, gy, 3), dim3(MF_T), 0, P, S, 0, 0, mth, vth, lth,
-                        par_.erosion_threshold, par_.dilation_threshold, pflags, epoch);
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_mask_passes", k_mask_fused4, dim3((srcp.width[0] + MF::W - 1) / MF::W, (srcp.height[0] + MF::H - 1) / MF::H, 3),
+                        dim3(MF::T), 0, P, S, 0, 0, th.mth, th.vth, th.lth, par_.erosion_threshold, par_.dilation_threshold, C.pflags, C.epoch);
     else
     {
         // One launch: the tiles no earlier field can influence (upper) and the chain through the fields (lower, MaskChain),
         // field-major - a field's lower tiles, then its upper ones.  As two launches (all upper tiles, then the chain) the
         // chain ran alone at a third of the GPU: it is 16 links of latency, not work (58 + 139 us per 16 fields).
-        MaskChain C = eedi_mask_chain_tiles(srcp, MF_W, MF_H, MF_OY);
-        C.flags = chain_flags_;
-        C.pflags = pflags;
-        C.epoch = epoch;
-        C.group = C.ntiles + C.nupper;
-        C.has = (MF_OPT & 4) ? chain_has_ + (size_t)f0 * C.group : nullptr;
-        guard_.bind(C);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_mask_passes", k_mask_chain, dim3((unsigned)(C.group * n)), dim3(MF_T), 0, P, S, C, mth, vth, lth,
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_mask_passes", k_mask_chain, dim3((unsigned)(C.group * n)), dim3(MF::T), 0, P, S, C, th.mth, th.vth, th.lth,
                      par_.erosion_threshold, par_.dilation_threshold);
         // the plane flags out of the tiles' words; and one workgroup that returns at once unless a wait above ran out
         // (MaskChain): no abort, no host round trip
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_mask_repair", k_mask_chain_repair, dim3(C.has ? 3u * (unsigned)n : 1u), dim3(MF_T), 0, P, S, C, n, mth, vth, lth,
-                        par_.erosion_threshold, par_.dilation_threshold);
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_mask_repair", k_mask_chain_repair, dim3(C.has ? 3u * (unsigned)n : 1u), dim3(MF::T), 0, P, S, C, n,
+                        th.mth, th.vth, th.lth, par_.erosion_threshold, par_.dilation_threshold);
     }
     HBHIP_CHECK(lc, hipGetLastError());
     return HBHIP_OK;
@@ -3716,30 +3483,9 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
     }
     if (par_.post_processing == 2 || par_.post_processing == 3)
     {
-        // junctions and corners, field after field and plane after plane (see CornerArgs: the derivative arrays carry
-        // values from plane to plane and from field to field)
-        for (int f = 0; f < n; f++)
-        {
-            const int tff = (int)((tffbits >> f) & 1u);
-            const size_t foff = (size_t)f * slot_bytes_;
-            for (int c = 0; c < 3; c++)
-            {
-                CornerArgs A;
-                A.src = srcp.plane[c] + foff; A.tmp = tmpp.plane[c] + foff;
-                for (int i = 0; i < 3; i++) { A.c[i] = deriv_[i]; A.t[i] = deriv_tmp_[i]; }
-                A.pitch = srcp.stride[c]; A.width = srcp.width[c]; A.height = srcp.height[c];
-                const dim3 g1((A.width + 63) / 64, (A.height + 3) / 4, 1), g3(g1.x, g1.y, 3);
-                HBHIP_LAUNCH_ON(lc, st, "eedi2_gaussian_blur1_h", k_blur1<false>, g1, blk, 0, A);
-                HBHIP_LAUNCH_ON(lc, st, "eedi2_gaussian_blur1_v", k_blur1<true>, g1, blk, 0, A);
-                HBHIP_LAUNCH_ON(lc, st, "eedi2_calc_derivatives", k_derivatives, g1, blk, 0, A);
-                HBHIP_LAUNCH_ON(lc, st, "eedi2_gaussian_blur_sqrt2_h", k_blur_sqrt2<false>, g3, blk, 0, A);
-                HBHIP_LAUNCH_ON(lc, st, "eedi2_gaussian_blur_sqrt2_v", k_blur_sqrt2<true>, g3, blk, 0, A);
-                const int rows = (dst2p.height[c] - 7 - (8 - tff) + 1) / 2;      // y = 8-field, 10-field, ... < height-7
-                if (rows > 0)
-                    HBHIP_LAUNCH_ON(lc, st, "eedi2_post_process_corner", k_post_corner, dim3((A.width + 63) / 64, (rows + 3) / 4, 1), blk, 0, A,
-                                 (const uint8_t *)(tmp2p2.plane[c] + foff), dst2p.plane[c] + foff, tff, dst2p.height[c]);
-            }
-        }
+        static const char *const names[6] = { "eedi2_gaussian_blur1_h", "eedi2_gaussian_blur1_v", "eedi2_calc_derivatives",
+                                              "eedi2_gaussian_blur_sqrt2_h", "eedi2_gaussian_blur_sqrt2_v", "eedi2_post_process_corner" };
+        enqueue_corner<uint8_t>(f0, n, lc, st, names);
     }
     HBHIP_CHECK(lc, hipGetLastError());
     return HBHIP_OK;

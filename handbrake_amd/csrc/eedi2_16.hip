@@ -10,7 +10,10 @@
 // layout hb_frame_buffer_init gives a 16-bit frame (stride = 2*width rounded up to 64 bytes), inside
 // zeroed guards, because the passes index flat buffers and read outside rows / planes.
 // All pitches inside the kernels are in SAMPLES.
+#include "eedi2_common.h"
 #include "eedi2_engine.h"
+#include "eedi2_mask_cells.h"
+#include "eedi2_corner.h"
 #include <algorithm>
 
 namespace {
@@ -54,32 +57,16 @@ __device__ __forceinline__ QL plane_ptrs16(const Q3 &P, int pl, size_t off)
     const int pitch = (P).pitch[pl], width = (P).width[pl], height = (P).height[pl]; \
     (void)width; (void)height; (void)pitch
 
-__device__ __forceinline__ int iabs16(int v) { return v < 0 ? -v : v; }
-
 __device__ __forceinline__ int sad3w(const uint16_t *a, int ai, const uint16_t *b, int bi)
 {
-    return iabs16((int)a[ai - 1] - (int)b[bi - 1]) + iabs16((int)a[ai] - (int)b[bi]) + iabs16((int)a[ai + 1] - (int)b[bi + 1]);
-}
-
-// insertion sort + midpoint rule (eedi2.c:65-80)
-__device__ __forceinline__ int sorted_mid16(int *v, int n)
-{
-    for (int i = 1; i < n; i++)
-    {
-        const int t = v[i];
-        int j = i;
-        while (j > 0 && v[j - 1] > t) { v[j] = v[j - 1]; j--; }
-        v[j] = t;
-    }
-    return (n & 1) ? v[n >> 1] : (v[(n - 1) >> 1] + v[n >> 1] + 1) >> 1;
+    return iabs((int)a[ai - 1] - (int)b[bi - 1]) + iabs((int)a[ai] - (int)b[bi]) + iabs((int)a[ai + 1] - (int)b[bi + 1]);
 }
 
 // ---- the field extraction and the five mask passes in one launch, as for 8-bit samples (eedi2.hip: k_mask_fused4) ----
 // build_edge_mask -> erode -> dilate -> erode -> remove_small_gaps each look one sample (three along x for the last)
 // around themselves, so a workgroup carries a 128 x 16 tile of the final mask through all of them in LDS with a
-// shrinking halo.  Only build_edge_mask sees samples; the mask itself is 0 / peak at any depth, so inside the kernel a
-// mask cell is a byte holding 0 / 1 and the morphology runs on four cells per 32-bit operation exactly as in the 8-bit
-// kernel.  a = SRCPF (written: the tile's part of the extracted field), b = the finished mask of the field before
+// shrinking halo.  Only build_edge_mask sees samples; behind it the mask is cells of 0 / 1 and the passes on them are the
+// 8-bit kernel's (eedi2_mask_cells.h).  a = SRCPF (written: the tile's part of the extracted field), b = the finished mask of the field before
 // field 0 of the launch, c = MSKPF.  `part`: 0 = every tile, 1 = only the tiles whose LDS frame stays above height / 2
 // (independent of the previous field: all fields of a batch in one launch), 2 = only the others (the chain).
 #ifndef QM_TILE_W
@@ -88,53 +75,7 @@ __device__ __forceinline__ int sorted_mid16(int *v, int n)
 #ifndef QM_THREADS
 #define QM_THREADS 512
 #endif
-constexpr int QM_W = QM_TILE_W, QM_H = 16, QM_OX = 8, QM_OY = 4;
-constexpr int QM_LP = QM_W + 2 * QM_OX, QM_LR = QM_H + 2 * QM_OY;      // 144 x 24
-constexpr int QM_DW = QM_LP / 4, QM_DP = QM_DW + 2, QM_SR = 2, QM_T = QM_THREADS;
-static_assert(((QM_LR - 2 + QM_SR - 1) / QM_SR) * QM_DW <= QM_T, "a thread per strip and dword column");
-
-__device__ __forceinline__ uint32_t qm_bytes_in(int X, int lo, int hi)        // 0xff in byte k when lo <= X + k < hi
-{
-    uint32_t m = 0xffffffffu;
-    const int a = lo - X, b = hi - X;
-    if (a > 0) m = a >= 4 ? 0u : (m << (8 * a));
-    if (b < 4) m = b <= 0 ? 0u : (m & (0xffffffffu >> (8 * (4 - b))));
-    return m;
-}
-
-template <bool GROW>
-__device__ __forceinline__ void qm_morph4(const uint32_t (*src)[QM_DP], uint32_t (*dst)[QM_DP], int c4, int strip,
-                                          int ra, int rb, int thr, uint32_t px1, int fy, int height)
-{
-    const int r0 = ra + strip * QM_SR;
-    if (r0 <= rb)
-    {
-        const uint32_t K = (uint32_t)(0x80 - min(max(thr, 0), 9)) * 0x01010101u;
-        uint32_t S2[QM_SR + 2], S3[QM_SR + 2], C[QM_SR + 2];
-#pragma unroll
-        for (int i = 0; i < QM_SR + 2; i++)
-        {
-            const int r = min(r0 - 1 + i, QM_LR - 1);
-            const uint32_t l = src[r][c4], c = src[r][c4 + 1], rr = src[r][c4 + 2];
-            C[i] = c;
-            S2[i] = __builtin_amdgcn_alignbyte(c, l, 3) + __builtin_amdgcn_alignbyte(rr, c, 1);
-            S3[i] = S2[i] + c;
-        }
-#pragma unroll
-        for (int i = 0; i < QM_SR; i++)
-        {
-            const int r = r0 + i;
-            if (r > rb) break;
-            const int y = fy + r;
-            const uint32_t count = S3[i] + S2[i + 1] + S3[i + 2];
-            const uint32_t ge = ((count + K) >> 7) & 0x01010101u;          // count >= thr, per cell
-            const uint32_t pm = (y >= 1 && y < height - 1) ? px1 : 0u;
-            const uint32_t c = C[i + 1];
-            dst[r][c4 + 1] = GROW ? (c | (ge & pm)) : (c & ~((ge ^ 0x01010101u) & pm));
-        }
-    }
-    __syncthreads();
-}
+using QM = EediMaskGeo<QM_TILE_W, 16, 2, QM_THREADS>;          // the LDS frame: 144 x 24
 
 struct MaskSrc16 { const uint16_t *frame[EEDI_MAX_BATCH][3]; int sp[3]; };     // sp: frame pitch in samples
 
@@ -143,22 +84,22 @@ struct MaskSrc16 { const uint16_t *frame[EEDI_MAX_BATCH][3]; int sp[3]; };     /
 template <bool CHAIN>
 __device__ __forceinline__ void qmask_tile(const Q3 &P, const MaskSrc16 &S, const K16 &k, const MaskChain &C, int fld, int pl, int bx, int by,
                                            int mth, int vth, int lth, int erode_thr, int dilate_thr,
-                                           uint16_t (*s_src)[QM_LP + 8], uint32_t (*s_a)[QM_DP], uint32_t (*s_b)[QM_DP])
+                                           uint16_t (*s_src)[QM::LP + 8], uint32_t (*s_a)[QM::DP], uint32_t (*s_b)[QM::DP])
 {
     const int pitch = P.pitch[pl], width = P.width[pl], height = P.height[pl];
-    const int x0 = bx * QM_W, y0 = by * QM_H;
-    const bool upper = y0 + QM_H + QM_OY <= height / 2;            // no row of the LDS frame reaches the kept half
+    const int x0 = bx * QM::W, y0 = by * QM::H;
+    const bool upper = y0 + QM::H + QM::OY <= height / 2;            // no row of the LDS frame reaches the kept half
     const size_t foff = (size_t)fld * P.fstride;
     const uint16_t *oldm = fld == 0 ? P.b[pl] : P.c[pl] + foff - P.fstride;
     const uint16_t *frame = S.frame[fld][pl];
     const int start_line = (int)(((P.tffbits >> fld) & 1u) ^ 1u);
     uint16_t *srcp = P.a[pl] + foff, *newm = P.c[pl] + foff;
-    const int t = threadIdx.x, fx = x0 - QM_OX, fy = y0 - QM_OY;
+    const int t = threadIdx.x, fx = x0 - QM::OX, fy = y0 - QM::OY;
     const int peak = k.peak, sh = k.shift;
 
-    for (int i = t; i < QM_LR * QM_DW; i += QM_T)
+    for (int i = t; i < QM::LR * QM::DW; i += QM::T)
     {
-        const int r = i / QM_DW, c4 = i - r * QM_DW;
+        const int r = i / QM::DW, c4 = i - r * QM::DW;
         const int y = fy + r, x = fx + 4 * c4;
         uint2 sv = make_uint2(0u, 0u);
         if (y >= 0 && y < height && x >= 0 && x < pitch)
@@ -175,15 +116,15 @@ __device__ __forceinline__ void qmask_tile(const Q3 &P, const MaskSrc16 &S, cons
                 }
             }
             // the tile's own cells go out as SRCPF (every cell of the plane belongs to exactly one tile)
-            if (r >= QM_OY && r < QM_OY + QM_H && c4 >= QM_OX / 4 && c4 < (QM_OX + QM_W) / 4)
+            if (r >= QM::OY && r < QM::OY + QM::H && c4 >= QM::OX / 4 && c4 < (QM::OX + QM::W) / 4)
                 *reinterpret_cast<uint2 *>(srcp + (size_t)y * pitch + x) = sv;
         }
         *reinterpret_cast<uint2 *>(&s_src[r][4 * c4 + 4]) = sv;
     }
     if (CHAIN && fld > 0) eedi_chain_wait(C, fld, pl, bx, by);    // (the source rows above are already on their way)
-    for (int i = t; i < QM_LR * QM_DW; i += QM_T)
+    for (int i = t; i < QM::LR * QM::DW; i += QM::T)
     {
-        const int r = i / QM_DW, c4 = i - r * QM_DW;
+        const int r = i / QM::DW, c4 = i - r * QM::DW;
         const int y = fy + r, x = fx + 4 * c4;
         uint32_t mv = 0;
         // (only the rows of the kept half are used, and those were written by lower tiles)
@@ -204,21 +145,21 @@ __device__ __forceinline__ void qmask_tile(const Q3 &P, const MaskSrc16 &S, cons
     }
     __syncthreads();
 
-    const int c4 = t % QM_DW, strip = t / QM_DW;               // strips past the frame have no rows in any pass
+    const int c4 = t % QM::DW, strip = t / QM::DW;               // strips past the frame have no rows in any pass
     const int X = fx + 4 * c4;
-    const uint32_t px1 = qm_bytes_in(X, 1, width - 1) & 0x01010101u;
+    const uint32_t px1 = bytes_in(X, 1, width - 1) & 0x01010101u;
 
     // build_edge_mask (:122-195), in place on the old mask; LDS rows 1 .. 22
     {
-        const int r0 = 1 + strip * QM_SR;
-        if (r0 <= QM_LR - 2)
+        const int r0 = 1 + strip * QM::SR;
+        if (r0 <= QM::LR - 2)
         {
             const int ten = (uint16_t)(10 << sh);
-            int b[QM_SR + 2][6], q[QM_SR + 2][6];
+            int b[QM::SR + 2][6], q[QM::SR + 2][6];
 #pragma unroll
-            for (int i = 0; i < QM_SR + 2; i++)
+            for (int i = 0; i < QM::SR + 2; i++)
             {
-                const int r = min(r0 - 1 + i, QM_LR - 1);
+                const int r = min(r0 - 1 + i, QM::LR - 1);
                 const uint16_t *row = &s_src[r][4 * c4 + 4];      // samples X .. X + 3 at row[0 .. 3]
                 const uint2 c = *reinterpret_cast<const uint2 *>(row);
                 b[i][0] = (int)row[-1];                            // column X - 1 (c4 = 0: a pad column, its cells are masked out)
@@ -228,10 +169,10 @@ __device__ __forceinline__ void qmask_tile(const Q3 &P, const MaskSrc16 &S, cons
                 for (int j = 0; j < 6; j++) q[i][j] = (b[i][j] >> sh) * (b[i][j] >> sh);
             }
 #pragma unroll
-            for (int i = 0; i < QM_SR; i++)
+            for (int i = 0; i < QM::SR; i++)
             {
                 const int r = r0 + i;
-                if (r > QM_LR - 2) break;
+                if (r > QM::LR - 2) break;
                 const int y = fy + r;
                 const int (&Pr)[6] = b[i], (&Cr)[6] = b[i + 1], (&Nr)[6] = b[i + 2];
                 // (max - min of a column's three samples serves the flatness test and Iy: eedi2.hip, mask_tile)
@@ -258,7 +199,7 @@ __device__ __forceinline__ void qmask_tile(const Q3 &P, const MaskSrc16 &S, cons
                     const bool notflat = !(fl[kk + 1] | (fl[kk] & fl[kk + 2]));
                     const bool var = !(9 * sumsq - sum * sum < vth);
                     const bool mag = ix * ix + iy * iy >= mth;
-                    const bool e = notflat & var & (mag | (iabs16(ixx) + iabs16(iyy) >= lth));
+                    const bool e = notflat & var & (mag | (iabs(ixx) + iabs(iyy) >= lth));
                     edge |= (e ? 1u : 0u) << (8 * kk);
                 }
                 const uint32_t keep = (y < height / 2) ? 0u : s_a[r][c4 + 1];
@@ -269,29 +210,24 @@ __device__ __forceinline__ void qmask_tile(const Q3 &P, const MaskSrc16 &S, cons
     }
     __syncthreads();
 
-    qm_morph4<false>(s_a, s_b, c4, strip, 2, QM_LR - 3, erode_thr, px1, fy, height);
-    qm_morph4<true>(s_b, s_a, c4, strip, 3, QM_LR - 4, dilate_thr, px1, fy, height);
-    qm_morph4<false>(s_a, s_b, c4, strip, 4, QM_LR - 5, erode_thr, px1, fy, height);
+    morph4<QM, false>(s_a, s_b, c4, strip, 2, QM::LR - 3, erode_thr, px1, fy, height);
+    morph4<QM, true>(s_b, s_a, c4, strip, 3, QM::LR - 4, dilate_thr, px1, fy, height);
+    morph4<QM, false>(s_a, s_b, c4, strip, 4, QM::LR - 5, erode_thr, px1, fy, height);
 
     // remove_small_gaps (:308-342) on the tile's 16 rows x 32 cell dwords, straight to the new mask
     uint32_t anyset = 0;
-    for (int i = t; i < QM_H * (QM_W / 4); i += QM_T)
+    for (int i = t; i < QM::H * (QM::W / 4); i += QM::T)
     {
-        const int r = QM_OY + i / (QM_W / 4), g4 = QM_OX / 4 + (i & (QM_W / 4 - 1));
+        const int r = QM::OY + i / (QM::W / 4), g4 = QM::OX / 4 + (i & (QM::W / 4 - 1));
         const int y = fy + r, x = fx + 4 * g4;
         if (y >= height || x >= width) continue;
         const uint32_t l = s_b[r][g4], c = s_b[r][g4 + 1], rr = s_b[r][g4 + 2];
-        const uint32_t a1 = __builtin_amdgcn_alignbyte(c, l, 3), a2 = __builtin_amdgcn_alignbyte(c, l, 2), a3 = __builtin_amdgcn_alignbyte(c, l, 1);
-        const uint32_t b1 = __builtin_amdgcn_alignbyte(rr, c, 1), b2 = __builtin_amdgcn_alignbyte(rr, c, 2), b3 = __builtin_amdgcn_alignbyte(rr, c, 3);
-        const uint32_t a12 = a1 | a2, a123 = a12 | a3;
-        const uint32_t set = c & (a123 | b1 | b2 | b3);                               // a set cell survives with any neighbour set
-        const uint32_t fill = ((b1 & a123) | (b2 & a12) | (b3 & a1)) & (c ^ 0x01010101u);
-        const uint32_t pm = (y >= 1 && y < height - 1) ? (qm_bytes_in(x, 3, width - 3) & 0x01010101u) : 0u;
-        const uint32_t res = ((set | fill) & pm) | (c & ~pm);                         // 0 / 1 per cell
+        const uint32_t pm = (y >= 1 && y < height - 1) ? (bytes_in(x, 3, width - 3) & 0x01010101u) : 0u;
+        const uint32_t res = small_gaps4(l, c, rr, pm);                                // 0 / 1 per cell
         anyset |= x + 3 < width ? res : res & (0xffffffffu >> (8 * (x + 4 - width)));
-        const uint32_t pk = (uint32_t)peak;
-        const uint2 out = make_uint2(((res & 1u) ? pk : 0u) | ((res & 0x100u) ? pk << 16 : 0u),
-                                     ((res & 0x10000u) ? pk : 0u) | ((res & 0x1000000u) ? pk << 16 : 0u));
+        const uint32_t pkv = (uint32_t)peak;
+        const uint2 out = make_uint2(((res & 1u) ? pkv : 0u) | ((res & 0x100u) ? pkv << 16 : 0u),
+                                     ((res & 0x10000u) ? pkv : 0u) | ((res & 0x1000000u) ? pkv << 16 : 0u));
         uint16_t *d = newm + (size_t)y * pitch + x;
         if (x + 3 < width)
         {
@@ -317,16 +253,16 @@ __device__ __forceinline__ void qmask_tile(const Q3 &P, const MaskSrc16 &S, cons
     eedi_chain_note_has(C, fld, pl, bx, by, has);
 }
 
-__global__ __launch_bounds__(QM_T) void q_mask_fused(Q3 P, MaskSrc16 S, K16 k, int f0, int part, int mth, int vth, int lth,
+__global__ __launch_bounds__(QM::T) void q_mask_fused(Q3 P, MaskSrc16 S, K16 k, int f0, int part, int mth, int vth, int lth,
                                                      int erode_thr, int dilate_thr, uint32_t *pflags, uint32_t epoch)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t s_src[QM_LR][QM_LP + 8];   // sample column = frame column + 4
-    __shared__ uint32_t s_a[QM_LR][QM_DP];
-    __shared__ uint32_t s_b[QM_LR][QM_DP];
+    __shared__ __attribute__((aligned(16))) uint16_t s_src[QM::LR][QM::LP + 8];   // sample column = frame column + 4
+    __shared__ uint32_t s_a[QM::LR][QM::DP];
+    __shared__ uint32_t s_b[QM::LR][QM::DP];
     const int zf = (int)blockIdx.z / 3, pl = (int)blockIdx.z - 3 * zf, fld = f0 + zf;   // f0: first field of this launch
-    const int x0 = blockIdx.x * QM_W, y0 = blockIdx.y * QM_H;
+    const int x0 = blockIdx.x * QM::W, y0 = blockIdx.y * QM::H;
     if (x0 >= P.width[pl] || y0 >= P.height[pl]) return;
-    const bool upper = y0 + QM_H + QM_OY <= P.height[pl] / 2;
+    const bool upper = y0 + QM::H + QM::OY <= P.height[pl] / 2;
     if (part != 0 && upper != (part == 1)) return;
     MaskChain none;
     none.pflags = pflags; none.epoch = epoch; none.has = nullptr;
@@ -334,12 +270,12 @@ __global__ __launch_bounds__(QM_T) void q_mask_fused(Q3 P, MaskSrc16 S, K16 k, i
 }
 
 // blockIdx.x = field * C.ntiles + tile: field-major, see MaskChain
-__global__ __launch_bounds__(QM_T) void q_mask_chain(Q3 P, MaskSrc16 S, K16 k, MaskChain C, int mth, int vth, int lth,
+__global__ __launch_bounds__(QM::T) void q_mask_chain(Q3 P, MaskSrc16 S, K16 k, MaskChain C, int mth, int vth, int lth,
                                                      int erode_thr, int dilate_thr)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t s_src[QM_LR][QM_LP + 8];
-    __shared__ uint32_t s_a[QM_LR][QM_DP];
-    __shared__ uint32_t s_b[QM_LR][QM_DP];
+    __shared__ __attribute__((aligned(16))) uint16_t s_src[QM::LR][QM::LP + 8];
+    __shared__ uint32_t s_a[QM::LR][QM::DP];
+    __shared__ uint32_t s_b[QM::LR][QM::DP];
     int fld, pl, bx, by;
     if (eedi_chain_tile(C, fld, pl, bx, by))                      // block-uniform: a link of the chain, or an upper tile riding along
         qmask_tile<true>(P, S, k, C, fld, pl, bx, by, mth, vth, lth, erode_thr, dilate_thr, s_src, s_a, s_b);
@@ -347,18 +283,16 @@ __global__ __launch_bounds__(QM_T) void q_mask_chain(Q3 P, MaskSrc16 S, K16 k, M
         qmask_tile<false>(P, S, k, C, fld, pl, bx, by, mth, vth, lth, erode_thr, dilate_thr, s_src, s_a, s_b);
 }
 
-// the pass behind q_mask_chain (k_mask_chain_repair, eedi2.hip, says what it is for): the plane flags out of the tiles'
+// the pass behind q_mask_chain (eedi_chain_repair_begin, eedi2_engine.h, says what it is for): the plane flags out of the tiles'
 // words, a workgroup per field and plane; the first one then repairs - a no-op unless a wait of the chain ran out
-__global__ __launch_bounds__(QM_T) void q_mask_chain_repair(Q3 P, MaskSrc16 S, K16 k, MaskChain C, int nfields, int mth, int vth, int lth,
+__global__ __launch_bounds__(QM::T) void q_mask_chain_repair(Q3 P, MaskSrc16 S, K16 k, MaskChain C, int nfields, int mth, int vth, int lth,
                                                             int erode_thr, int dilate_thr)
 {
-    __shared__ __attribute__((aligned(16))) uint16_t s_src[QM_LR][QM_LP + 8];
-    __shared__ uint32_t s_a[QM_LR][QM_DP];
-    __shared__ uint32_t s_b[QM_LR][QM_DP];
-    eedi_chain_fold_has(C, QM_T);
-    if (blockIdx.x != 0 || __hip_atomic_load(C.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;      // block-uniform
-    MaskChain R = C;
-    R.has = nullptr;                                               // the repaired tiles raise the plane flags themselves
+    __shared__ __attribute__((aligned(16))) uint16_t s_src[QM::LR][QM::LP + 8];
+    __shared__ uint32_t s_a[QM::LR][QM::DP];
+    __shared__ uint32_t s_b[QM::LR][QM::DP];
+    MaskChain R;
+    if (!eedi_chain_repair_begin(C, QM::T, R)) return;
     for (int fld = 0; fld < nfields; fld++)
         for (int tile = 0; tile < C.ntiles; tile++)
         {
@@ -367,11 +301,7 @@ __global__ __launch_bounds__(QM_T) void q_mask_chain_repair(Q3 P, MaskSrc16 S, K
             qmask_tile<true>(P, S, k, R, fld, pl, bx, by, mth, vth, lth, erode_thr, dilate_thr, s_src, s_a, s_b);
             __syncthreads();
         }
-    if (threadIdx.x == 0)
-    {
-        __hip_atomic_store(C.err, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_fetch_add(C.fallbacks, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    eedi_chain_repair_end(C);
 }
 
 // eedi2_calc_directions (:358-525): a = mskp, b = srcp, c = out (whole pitch pre-filled with PEAK)
@@ -388,7 +318,7 @@ __global__ void q_calc_dir(Q3 P, K16 k, int maxd, int nt)
         const int nt13 = (uint16_t)((nt << k.shift) * 13), nt19 = (uint16_t)((nt << k.shift) * 19);
         const int maxdt = pl == 0 ? maxd : (maxd >> 1);
         const int startu = max(-x + 1, -maxdt), stopu = min(width - 2 - x, maxdt);
-        const int vert = iabs16((int)sc[x] - (int)sn[x]) + iabs16((int)sc[x] - (int)sp[x]);
+        const int vert = iabs((int)sc[x] - (int)sn[x]) + iabs((int)sc[x] - (int)sp[x]);
         int minb = min(nt13, vert * 6), mina = min(nt19, vert * 9);
         int minc = mina, mind = minb, mine = minb;
         int dira = -5000, dirb = -5000, dirc = -5000, dird = -5000, dire = -5000;
@@ -433,11 +363,11 @@ __global__ void q_calc_dir(Q3 P, K16 k, int maxd, int nt)
         out = k.neutral;
         if (n > 1)
         {
-            const int mid = sorted_mid16(order, n);
-            const int tlim = max(k.limlut[iabs16(mid)] >> 2, 2);
+            const int mid = sorted_mid(order, n);
+            const int tlim = max(k.limlut[iabs(mid)] >> 2, 2);
             int sum = 0, count = 0;
             for (int i = 0; i < n; i++)
-                if (iabs16(order[i] - mid) <= tlim) { count++; sum += order[i]; }
+                if (iabs(order[i] - mid) <= tlim) { count++; sum += order[i]; }
             if (count > 1) out = (uint16_t)(k.neutral + ((int)((float)sum / (float)count) << (2 + k.shift)));
         }
     }
@@ -471,17 +401,17 @@ __device__ __forceinline__ int calc_dir_vote16(int ta, int tb, int tc, int td, i
     int out = neutral;
     if (n > 1)
     {
-        // sorted_mid16's midpoint rule: odd n -> v[n/2], even n -> (v[(n-1)/2] + v[n/2] + 1) >> 1; one formula serves both
+        // sorted_mid's midpoint rule: odd n -> v[n/2], even n -> (v[(n-1)/2] + v[n/2] + 1) >> 1; one formula serves both
         const int lo = n == 2 ? v0 : (n == 5 ? v2 : v1);
         const int hi = n >= 4 ? v2 : v1;
         const int mid = (lo + hi + 1) >> 1;
-        const int tlim = max(limlut[iabs16(mid)] >> 2, 2);
+        const int tlim = max(limlut[iabs(mid)] >> 2, 2);
         int sum = 0, cnt = 0;
-        if (iabs16(v0 - mid) <= tlim) { cnt++; sum += v0; }          // the sentinels fail the test by themselves
-        if (iabs16(v1 - mid) <= tlim) { cnt++; sum += v1; }
-        if (iabs16(v2 - mid) <= tlim) { cnt++; sum += v2; }
-        if (iabs16(v3 - mid) <= tlim) { cnt++; sum += v3; }
-        if (iabs16(v4 - mid) <= tlim) { cnt++; sum += v4; }
+        if (iabs(v0 - mid) <= tlim) { cnt++; sum += v0; }          // the sentinels fail the test by themselves
+        if (iabs(v1 - mid) <= tlim) { cnt++; sum += v1; }
+        if (iabs(v2 - mid) <= tlim) { cnt++; sum += v2; }
+        if (iabs(v3 - mid) <= tlim) { cnt++; sum += v3; }
+        if (iabs(v4 - mid) <= tlim) { cnt++; sum += v4; }
         if (cnt > 1) out = (uint16_t)(neutral + ((int)((float)sum / (float)cnt) << (2 + shift)));
     }
     return out;
@@ -505,7 +435,7 @@ __device__ __forceinline__ void calc_dir_dense16(const uint2 *tr, int maxdt, con
     for (int j = 0; j < R; j++)
     {
         const int ctr = (int)(T[j + 2].x >> 16);
-        const int vert = iabs16(ctr - (int)(T[j + 3].x >> 16)) + iabs16(ctr - (int)(T[j + 1].x >> 16));
+        const int vert = iabs(ctr - (int)(T[j + 3].x >> 16)) + iabs(ctr - (int)(T[j + 1].x >> 16));
         kb[j] = (uint32_t)min(nt13, vert * 6) << 9; ka[j] = (uint32_t)min(nt19, vert * 9) << 9;
         kc[j] = ka[j]; kd[j] = kb[j]; ke[j] = kb[j];
     }
@@ -593,15 +523,6 @@ __device__ __forceinline__ void calc_dir_dense16(const uint2 *tr, int maxdt, con
     }
 }
 
-// bit t of a mask row's window: a peak among columns start + t .. + 2
-__device__ __forceinline__ uint64_t calc_dir_window16(const uint64_t *bits, int start, uint64_t lenmask)
-{
-    const int wq = start >> 6, sh = start & 63;
-    const uint64_t lo = bits[wq], hi = bits[wq + 1];
-    const uint64_t w = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-    return (w | (w >> 1) | (w >> 2)) & lenmask;
-}
-
 template <bool EDGE>
 __device__ __forceinline__ int calc_dir_search16(const uint2 *tr, uint64_t pass, int maxdt, bool first, bool last, int nt13, int nt19,
                                                  const int *limlut, int neutral, int shift)
@@ -609,7 +530,7 @@ __device__ __forceinline__ int calc_dir_search16(const uint2 *tr, uint64_t pass,
     // tr = &s_tri[j][b]: row r of the table is r * QLW further (r = 0..4: rows y-2 .. y+2)
     const uint2 F2p = tr[0], Fp = tr[QLW], Fc = tr[2 * QLW], Fn = tr[3 * QLW], F2n = tr[4 * QLW];
     const int ctr = (int)(Fc.x >> 16);
-    const int vert = iabs16(ctr - (int)(Fn.x >> 16)) + iabs16(ctr - (int)(Fp.x >> 16));
+    const int vert = iabs(ctr - (int)(Fn.x >> 16)) + iabs(ctr - (int)(Fp.x >> 16));
     // keys: (running minimum << 6) | (u + 32), low six bits 0 = unset (the reference's -5000)
     uint32_t kb = (uint32_t)min(nt13, vert * 6) << 6, ka = (uint32_t)min(nt19, vert * 9) << 6;
     uint32_t kc = ka, kd = kb, ke = kb;
@@ -762,7 +683,7 @@ __global__ __launch_bounds__(QW) void q_calc_dir_rows(Q3 P, K16 k, int maxd, int
         }
         uint64_t win[RD + 2];
 #pragma unroll
-        for (int m = 0; m < RD + 2; m++) win[m] = calc_dir_window16(s_pk[m], b - maxdt, lenmask);
+        for (int m = 0; m < RD + 2; m++) win[m] = calc_dir_window(s_pk[m], b - maxdt, lenmask);
         uint32_t up[RD], dn[RD], act = 0, inactive = 0;
 #pragma unroll
         for (int j = 0; j < RD; j++)
@@ -836,48 +757,28 @@ __global__ __launch_bounds__(QW) void q_calc_dir_rows(Q3 P, K16 k, int maxd, int
 // step 2: rows y0, y0+2, ... looking at rows y+-2 and mask rows y-1 / y+1.
 // (the candidates sit in nine fixed slots - an absent one holds ABSENT16, larger than any sample and farther from any
 // midpoint than any vote limit - and a sorting network orders them: no data-dependent loop, no indexed array; the
-// midpoint and the vote are sorted_mid16's / vote16's, as in the 8-bit k_dir_map)
+// midpoint and the vote are sorted_mid's / vote16's, as in the 8-bit k_dir_map)
 constexpr int ABSENT16 = 1 << 20;
-
-__device__ __forceinline__ void cswap16(int &a, int &b)
-{
-    const int lo = min(a, b), hi = max(a, b);
-    a = lo; b = hi;
-}
 
 // midpoint of the n present values among 9 slots (n >= 4)
 __device__ __forceinline__ int mid9q(int &v0, int &v1, int &v2, int &v3, int &v4, int &v5, int &v6, int &v7, int &v8, int n)
 {
-    cswap16(v0, v3); cswap16(v1, v7); cswap16(v2, v5); cswap16(v4, v8);
-    cswap16(v0, v7); cswap16(v2, v4); cswap16(v3, v8); cswap16(v5, v6);
-    cswap16(v0, v2); cswap16(v1, v3); cswap16(v4, v5); cswap16(v7, v8);
-    cswap16(v1, v4); cswap16(v3, v6); cswap16(v5, v7);
-    cswap16(v0, v1); cswap16(v2, v4); cswap16(v3, v5); cswap16(v6, v8);
-    cswap16(v2, v3); cswap16(v4, v5); cswap16(v6, v7);
-    cswap16(v1, v2); cswap16(v3, v4); cswap16(v5, v6);
+    cswap(v0, v3); cswap(v1, v7); cswap(v2, v5); cswap(v4, v8);
+    cswap(v0, v7); cswap(v2, v4); cswap(v3, v8); cswap(v5, v6);
+    cswap(v0, v2); cswap(v1, v3); cswap(v4, v5); cswap(v7, v8);
+    cswap(v1, v4); cswap(v3, v6); cswap(v5, v7);
+    cswap(v0, v1); cswap(v2, v4); cswap(v3, v5); cswap(v6, v8);
+    cswap(v2, v3); cswap(v4, v5); cswap(v6, v7);
+    cswap(v1, v2); cswap(v3, v4); cswap(v5, v6);
     // n = 4..9: lower middle index (n-1)>>1 = 1,2,2,3,3,4 ; upper n>>1 = 2,2,3,3,4,4
     const int lo = n <= 4 ? v1 : (n <= 6 ? v2 : (n <= 8 ? v3 : v4));
     const int hi = n <= 5 ? v2 : (n <= 7 ? v3 : v4);
     return (n & 1) ? hi : (lo + hi + 1) >> 1;
 }
 
-// midpoint of the n present values among 6 slots (n >= 3)
-__device__ __forceinline__ int mid6q(int &v0, int &v1, int &v2, int &v3, int &v4, int &v5, int n)
-{
-    cswap16(v0, v5); cswap16(v1, v3); cswap16(v2, v4);
-    cswap16(v1, v2); cswap16(v3, v4);
-    cswap16(v0, v3); cswap16(v2, v5);
-    cswap16(v0, v1); cswap16(v2, v3); cswap16(v4, v5);
-    cswap16(v1, v2); cswap16(v3, v4);
-    // n = 3..6: lower middle index 1,1,2,2 ; upper 1,2,2,3
-    const int lo = n <= 4 ? v1 : v2;
-    const int hi = n <= 3 ? v1 : (n <= 5 ? v2 : v3);
-    return (n & 1) ? hi : (lo + hi + 1) >> 1;
-}
-
 __device__ __forceinline__ void vote1q(int v, int mid, int lim, int &sum, int &cnt)
 {
-    const bool in = iabs16(v - mid) <= lim;      // never true for ABSENT16
+    const bool in = iabs(v - mid) <= lim;      // never true for ABSENT16
     cnt += in;
     sum += in ? v : 0;
 }
@@ -895,7 +796,7 @@ __device__ __forceinline__ int dir_map_px16(int u0, int u1, int u2, int c0, int 
     int v3 = h3 ? c0 : ABSENT16, v4 = h4 ? c1 : ABSENT16, v5 = h5 ? c2 : ABSENT16;
     int v6 = h6 ? n0 : ABSENT16, v7 = h7 ? n1 : ABSENT16, v8 = h8 ? n2 : ABSENT16;
     const int mid = mid9q(v0, v1, v2, v3, v4, v5, v6, v7, v8, u);
-    const int lim = limlut[iabs16(mid - neutral) >> sh2];
+    const int lim = limlut[iabs(mid - neutral) >> sh2];
     int sum = 0, count = 0;
     vote1q(v0, mid, lim, sum, count); vote1q(v1, mid, lim, sum, count); vote1q(v2, mid, lim, sum, count);
     vote1q(v3, mid, lim, sum, count); vote1q(v4, mid, lim, sum, count); vote1q(v5, mid, lim, sum, count);
@@ -911,24 +812,14 @@ __device__ __forceinline__ int dir_map_px16(int u0, int u1, int u2, int c0, int 
 // in the halves of a dword - which is how 16-bit samples lie in memory, so the nine slots of a pair are three dwords of
 // each row as they are or realigned by two bytes, no unpacking.  An absent slot (a peak; a row that does not count)
 // holds 0x7fff: above every sample and 0x7000 or more from every midpoint, the cap of the vote's limit.
-typedef uint16_t u16x2d __attribute__((ext_vector_type(2)));
-typedef int16_t i16x2d __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u16x2d pkd(uint32_t v) { return __builtin_bit_cast(u16x2d, v); }
-__device__ __forceinline__ uint32_t und(u16x2d v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ u16x2d pkd1(uint32_t both) { return pkd(both * 0x00010001u); }
-__device__ __forceinline__ u16x2d pkd_lt(u16x2d a, u16x2d b) { return (u16x2d)((u16x2d)(a - b) >> 15); }   // halves below 2^15
-__device__ __forceinline__ void cswap2d(u16x2d &a, u16x2d &b)
-{
-    const u16x2d lo = __builtin_elementwise_min(a, b), hi = __builtin_elementwise_max(a, b);
-    a = lo; b = hi;
-}
+// (u16x2 and pk / un / pk1 / pk_lt / cswap2: eedi2_common.h)
 struct Win16 { uint32_t w0, w1, w2, w3; };       // samples x-2 .. x+5 of a row
 
 // the pair of samples at columns K, K + 1 of the thread's four (K = 0 or 2); returns the pass's values for both halves
 template <int K>
 __device__ __forceinline__ uint32_t dir_map_pair16(const Win16 &wu, const Win16 &wc, const Win16 &wd, int expand, int peak, int neutral, int shift)
 {
-    u16x2d v[9];
+    u16x2 v[9];
     {
         const Win16 *rows[3] = { &wu, &wc, &wd };
 #pragma unroll
@@ -937,64 +828,64 @@ __device__ __forceinline__ uint32_t dir_map_pair16(const Win16 &wu, const Win16 
             const Win16 &w = *rows[r];
             if (K == 0)
             {
-                v[3 * r + 0] = pkd(__builtin_amdgcn_alignbyte(w.w1, w.w0, 2u));       // columns -1, 0
-                v[3 * r + 1] = pkd(w.w1);                                             // 0, 1
-                v[3 * r + 2] = pkd(__builtin_amdgcn_alignbyte(w.w2, w.w1, 2u));       // 1, 2
+                v[3 * r + 0] = pk(__builtin_amdgcn_alignbyte(w.w1, w.w0, 2u));       // columns -1, 0
+                v[3 * r + 1] = pk(w.w1);                                             // 0, 1
+                v[3 * r + 2] = pk(__builtin_amdgcn_alignbyte(w.w2, w.w1, 2u));       // 1, 2
             }
             else
             {
-                v[3 * r + 0] = pkd(__builtin_amdgcn_alignbyte(w.w2, w.w1, 2u));       // 1, 2
-                v[3 * r + 1] = pkd(w.w2);                                             // 2, 3
-                v[3 * r + 2] = pkd(__builtin_amdgcn_alignbyte(w.w3, w.w2, 2u));       // 3, 4
+                v[3 * r + 0] = pk(__builtin_amdgcn_alignbyte(w.w2, w.w1, 2u));       // 1, 2
+                v[3 * r + 1] = pk(w.w2);                                             // 2, 3
+                v[3 * r + 2] = pk(__builtin_amdgcn_alignbyte(w.w3, w.w2, 2u));       // 3, 4
             }
         }
     }
-    const u16x2d c1 = v[4];
+    const u16x2 c1 = v[4];
     // (a direction value can lie ABOVE the peak: neutral + (32 << (2 + shift)) is one more than it - a search distance of 32 gets
     // there - so the peak is found by equality)
-    const u16x2d peakv = pkd1((uint32_t)peak), lift = pkd1(0x7fffu - (uint32_t)peak);
+    const u16x2 peakv = pk1((uint32_t)peak), lift = pk1(0x7fffu - (uint32_t)peak);
     uint32_t absent = 0;
 #pragma unroll
     for (int i = 0; i < 9; i++)
     {
-        const u16x2d a = pkd_lt(v[i] ^ peakv, pkd1(1));                 // 1 per half that holds the peak
-        absent += und(a);
+        const u16x2 a = pk_lt(v[i] ^ peakv, pk1(1));                 // 1 per half that holds the peak
+        absent += un(a);
         v[i] = v[i] + a * lift;
     }
-    u16x2d s0 = v[0], s1 = v[1], s2 = v[2], s3 = v[3], s4 = v[4], s5 = v[5], s6 = v[6], s7 = v[7], s8 = v[8];
-    cswap2d(s0, s3); cswap2d(s1, s7); cswap2d(s2, s5); cswap2d(s4, s8);
-    cswap2d(s0, s7); cswap2d(s2, s4); cswap2d(s3, s8); cswap2d(s5, s6);
-    cswap2d(s0, s2); cswap2d(s1, s3); cswap2d(s4, s5); cswap2d(s7, s8);
-    cswap2d(s1, s4); cswap2d(s3, s6); cswap2d(s5, s7);
-    cswap2d(s0, s1); cswap2d(s2, s4); cswap2d(s3, s5); cswap2d(s6, s8);
-    cswap2d(s2, s3); cswap2d(s4, s5); cswap2d(s6, s7);
-    cswap2d(s1, s2); cswap2d(s3, s4); cswap2d(s5, s6);
-    const u16x2d ab = pkd(absent), one = pkd1(1), zero = pkd1(0);
-    const uint32_t m5 = und(zero - pkd_lt(pkd1(3), ab));                // n <= 5 <=> absent >= 4
-    const uint32_t m7 = und(zero - pkd_lt(one, ab));                    // n <= 7 <=> absent >= 2
-    const uint32_t modd = und((ab & one) - one);                        // n odd <=> absent even
+    u16x2 s0 = v[0], s1 = v[1], s2 = v[2], s3 = v[3], s4 = v[4], s5 = v[5], s6 = v[6], s7 = v[7], s8 = v[8];
+    cswap2(s0, s3); cswap2(s1, s7); cswap2(s2, s5); cswap2(s4, s8);
+    cswap2(s0, s7); cswap2(s2, s4); cswap2(s3, s8); cswap2(s5, s6);
+    cswap2(s0, s2); cswap2(s1, s3); cswap2(s4, s5); cswap2(s7, s8);
+    cswap2(s1, s4); cswap2(s3, s6); cswap2(s5, s7);
+    cswap2(s0, s1); cswap2(s2, s4); cswap2(s3, s5); cswap2(s6, s8);
+    cswap2(s2, s3); cswap2(s4, s5); cswap2(s6, s7);
+    cswap2(s1, s2); cswap2(s3, s4); cswap2(s5, s6);
+    const u16x2 ab = pk(absent), one = pk1(1), zero = pk1(0);
+    const uint32_t m5 = un(zero - pk_lt(pk1(3), ab));                // n <= 5 <=> absent >= 4
+    const uint32_t m7 = un(zero - pk_lt(one, ab));                    // n <= 7 <=> absent >= 2
+    const uint32_t modd = un((ab & one) - one);                        // n odd <=> absent even
 #define PKD_SEL(m, x, y) (((m) & (x)) | (~(m) & (y)))
-    const uint32_t hi = PKD_SEL(m5, und(s2), PKD_SEL(m7, und(s3), und(s4)));
-    const uint32_t lo = PKD_SEL(m5, und(s1), PKD_SEL(m7, und(s2), und(s3)));
-    const u16x2d mid = pkd(PKD_SEL(modd, hi, und((u16x2d)((pkd(lo) + pkd(hi) + one) >> 1))));
+    const uint32_t hi = PKD_SEL(m5, un(s2), PKD_SEL(m7, un(s3), un(s4)));
+    const uint32_t lo = PKD_SEL(m5, un(s1), PKD_SEL(m7, un(s2), un(s3)));
+    const u16x2 mid = pk(PKD_SEL(modd, hi, un((u16x2)((pk(lo) + pk(hi) + one) >> 1))));
 #undef PKD_SEL
     // the limit: (limlut[i] << shift) with limlut in closed form (eedi2.hip: limlut2), i = |mid - neutral| >> (2 + shift); the two
     // last entries (a -1 stored as a sample: every present value is in) capped at 0x7000
-    const i16x2d t = __builtin_bit_cast(i16x2d, (u16x2d)(mid - pkd1((uint32_t)neutral)));
-    const u16x2d ii = __builtin_bit_cast(u16x2d, __builtin_elementwise_max(t, (i16x2d)(-t))) >> (uint16_t)(2 + shift);
-    const u16x2d g = pkd_lt(pkd1(7), ii);
-    const u16x2d l8 = __builtin_elementwise_min((u16x2d)(((ii - g) >> 1) + pkd1(6)), pkd1(12));
-    const u16x2d lim1 = __builtin_elementwise_max((u16x2d)((l8 << (uint16_t)shift) + one), (u16x2d)(pkd_lt(pkd1(30), ii) * pkd1(0x7000)));
-    u16x2d sum = zero, cnt = zero;
+    const i16x2 t = __builtin_bit_cast(i16x2, (u16x2)(mid - pk1((uint32_t)neutral)));
+    const u16x2 ii = __builtin_bit_cast(u16x2, __builtin_elementwise_max(t, (i16x2)(-t))) >> (uint16_t)(2 + shift);
+    const u16x2 g = pk_lt(pk1(7), ii);
+    const u16x2 l8 = __builtin_elementwise_min((u16x2)(((ii - g) >> 1) + pk1(6)), pk1(12));
+    const u16x2 lim1 = __builtin_elementwise_max((u16x2)((l8 << (uint16_t)shift) + one), (u16x2)(pk_lt(pk1(30), ii) * pk1(0x7000)));
+    u16x2 sum = zero, cnt = zero;
 #pragma unroll
     for (int i = 0; i < 9; i++)
     {
-        const u16x2d d = __builtin_elementwise_max(v[i], mid) - __builtin_elementwise_min(v[i], mid);
-        const u16x2d in = pkd_lt(d, lim1);
+        const u16x2 d = __builtin_elementwise_max(v[i], mid) - __builtin_elementwise_min(v[i], mid);
+        const u16x2 in = pk_lt(d, lim1);
         cnt += in;
         sum += in * v[i];
     }
-    const uint32_t sm = und((u16x2d)(sum + mid)), ct = und(cnt);
+    const uint32_t sm = un((u16x2)(sum + mid)), ct = un(cnt);
     uint32_t out = 0;
 #pragma unroll
     for (int h = 0; h < 2; h++)
@@ -1002,7 +893,7 @@ __device__ __forceinline__ uint32_t dir_map_pair16(const Win16 &wu, const Win16 
         const int n = 9 - (int)((absent >> (16 * h)) & 0xffffu);
         const int count = n >= 4 ? (int)((ct >> (16 * h)) & 0xffffu) : 0;              // (fewer: the midpoint may be an absent slot)
         const int val = (int)(((float)((sm >> (16 * h)) & 0xffffu) / (float)(count + 1)) + 0.5f);
-        const int c = (int)((und(c1) >> (16 * h)) & 0xffffu);
+        const int c = (int)((un(c1) >> (16 * h)) & 0xffffu);
         int res;
         if (expand) res = count >= 5 ? val : c;
         else        res = (count < 4 || (count < 5 && c == peak)) ? peak : val;
@@ -1223,8 +1114,8 @@ __global__ __launch_bounds__(256) void q_dir_map(Q3 P, K16 k, int step, int expa
             for (int j = 0; j < 4; j++)
             {
                 const int nm = s4(v, j), om = s4(om4, j);
-                const int lim = s_lim[iabs16(nm - k.neutral) >> (2 + k.shift)];
-                const bool fix = iabs16(nm - om) > lim && om != k.peak && om != k.neutral;
+                const int lim = s_lim[iabs(nm - k.neutral) >> (2 + k.shift)];
+                const bool fix = iabs(nm - om) > lim && om != k.peak && om != k.neutral;
                 out[j] = fix ? (uint32_t)((s4(up4, j) + s4(dn4, j) + 1) >> 1) : (uint32_t)s4(cur4, j);
                 any |= fix;
             }
@@ -1445,8 +1336,8 @@ __global__ __launch_bounds__(256) void q_dir_map_fe(Q3 P, K16 k, int padv)
                 for (int j = 0; j < 4; j++)
                 {
                     const int nm = s4(v, j), om = s4(om4, j);
-                    const int lim = s_lim[iabs16(nm - k.neutral) >> (2 + k.shift)];
-                    const bool fix = iabs16(nm - om) > lim && om != k.peak && om != k.neutral;
+                    const int lim = s_lim[iabs(nm - k.neutral) >> (2 + k.shift)];
+                    const bool fix = iabs(nm - om) > lim && om != k.peak && om != k.neutral;
                     out[j] = fix ? (uint32_t)((s4(up4, j) + s4(dn4, j) + 1) >> 1) : (uint32_t)s4(cur4, j);
                     any |= fix;
                 }
@@ -1536,7 +1427,7 @@ __global__ __launch_bounds__(256) void q_filter_map(Q3 P, K16 k)
         const uint16_t *dc = rc + j, *dp = dc - QFM_LW, *dn = dc + QFM_LW;
         const uint32_t ref = dc[0];
         int dir = ((int)ref - k.neutral) >> 2;
-        const int lim = max(iabs16(dir) * 2, 12 << (2 + k.shift));
+        const int lim = max(iabs(dir) * 2, 12 << (2 + k.shift));
         dir >>= 2 + k.shift;
         // the four ranges of :565-620 with neg = min(dir, 0), pos = max(dir, 0): [max(-x, neg), min(w - x - 1, pos)] above,
         // [max(-x, -pos), min(w - x - 1, -neg)] below; the shorter walk repeats its last step
@@ -1629,12 +1520,12 @@ __global__ __launch_bounds__(256) void q_mark_2x(Q3 P, K16 k, int padv)
             {
                 int v0 = h0 ? a0 : ABSENT16, v1 = h1 ? a1 : ABSENT16, v2 = h2 ? a2 : ABSENT16;
                 int v3 = h3 ? b0 : ABSENT16, v4 = h4 ? b1 : ABSENT16, v5 = h5 ? b2 : ABSENT16;
-                const int mid = mid6q(v0, v1, v2, v3, v4, v5, n);
-                const int lim = k.limlut[iabs16(mid - k.neutral) >> (2 + k.shift)];
+                const int mid = mid6(v0, v1, v2, v3, v4, v5, n);
+                const int lim = k.limlut[iabs(mid - k.neutral) >> (2 + k.shift)];
                 int u = 0;
-                if (iabs16(a0 - b0) <= lim || !h0 || !h3) u++;
-                if (iabs16(a1 - b1) <= lim || !h1 || !h4) u++;
-                if (iabs16(a2 - b0) <= lim || !h2 || !h5) u++;                                   // sic (:835)
+                if (iabs(a0 - b0) <= lim || !h0 || !h3) u++;
+                if (iabs(a1 - b1) <= lim || !h1 || !h4) u++;
+                if (iabs(a2 - b0) <= lim || !h2 || !h5) u++;                                   // sic (:835)
                 if (u >= 2)
                 {
                     int sum = 0, count = 0;
@@ -1875,10 +1766,10 @@ __global__ __launch_bounds__(256) void q_fill_gaps_b(Q3 P, K16 k)
         }
         if (maxt == -twenty) maxt = mint = twenty;
         if (maxb == -twenty) maxb = minb = twenty;
-        const int far = max(iabs16(forward - k.neutral), iabs16(back - k.neutral));
-        const int thresh = max(max(far >> 2, eight), max(iabs16(mint - maxt), iabs16(minb - maxb)));
+        const int far = max(iabs(forward - k.neutral), iabs(back - k.neutral));
+        const int thresh = max(max(far >> 2, eight), max(iabs(mint - maxt), iabs(minb - maxb)));
         const int flim = min(far >> (2 + k.shift), 6);
-        if (iabs16(forward - back) <= thresh && (v - u - 1 <= flim || tc || bc))
+        if (iabs(forward - back) <= thresh && (v - u - 1 <= flim || tc || bc))
         {
             const double step = (double)(forward - back) / (double)(v - u);
             const int j = px - u - 1;
@@ -1948,13 +1839,13 @@ __device__ __forceinline__ unsigned long long lat16_stage_b(const uint16_t *top,
                                                             const uint16_t *dm, int x, int width, unsigned long long base, const Lat16 &L)
 {
     const int here = dm[x], peak = L.peak;
-    const int lim = L.lim[iabs16(here - L.neutral) >> L.sh2];
+    const int lim = L.lim[iabs(here - L.neutral) >> L.sh2];
     int dir = (here - L.neutral + (1 << (L.sh2 - 1))) >> L.sh2;
     int val = (int)(base & 0xffffu);
     const int startu = (dir - 2 < 0) ? max(-x + 1, max(dir - 2, -width + 2 + x)) : min(x - 1, min(dir - 2, width - 2 - x));
     const int stopu = (dir + 2 < 0) ? max(-x + 1, max(dir + 2, -width + 2 + x)) : min(x - 1, min(dir + 2, width - 2 - x));
     int mn = L.nt8;
-    auto near = [&](const uint16_t *row, int i) { return row[i] != peak && iabs16((int)row[i] - here) <= lim; };
+    auto near = [&](const uint16_t *row, int i) { return row[i] != peak && iabs((int)row[i] - here) <= lim; };
     for (int u = startu; u <= stopu; u++)
     {
         const int diff = sad3w(top, x, bot, x - u) + sad3w(bot, x, top, x + u);
@@ -1964,10 +1855,10 @@ __device__ __forceinline__ unsigned long long lat16_stage_b(const uint16_t *top,
         const int h0 = u >> 1, h1 = (u + 1) >> 1;
         const int diff2 = sad3w(top, x + h0, bot, x - h0);
         const int o0 = ot[x + h0], o1 = ot[x + h1], q0 = ob[x - h0], q1 = ob[x - h1];
-        if (!(diff2 < L.nt4 && (((iabs16(o0 - q0) <= lim || iabs16(o0 - q1) <= lim) && o0 != peak) ||
-                                ((iabs16(o1 - q0) <= lim || iabs16(o1 - q1) <= lim) && o1 != peak))))
+        if (!(diff2 < L.nt4 && (((iabs(o0 - q0) <= lim || iabs(o0 - q1) <= lim) && o0 != peak) ||
+                                ((iabs(o1 - q0) <= lim || iabs(o1 - q1) <= lim) && o1 != peak))))
             continue;
-        if ((iabs16(here - o0) <= lim || iabs16(here - o1) <= lim) && (iabs16(here - q0) <= lim || iabs16(here - q1) <= lim))
+        if ((iabs(here - o0) <= lim || iabs(here - o1) <= lim) && (iabs(here - q0) <= lim || iabs(here - q1) <= lim))
         {
             val = ((int)top[x + h0] + (int)top[x + h1] + (int)bot[x - h0] + (int)bot[x - h1] + 2) >> 2;
             mn = diff;
@@ -1981,12 +1872,6 @@ __device__ __forceinline__ unsigned long long lat16_stage_b(const uint16_t *top,
 // ---- the forms of eedi2.hip's k_lattice_cand_q for 16-bit samples: the tests out of registers, the search out of
 // windows of eight samples with its steps side by side (see there for the why; here a window is four dwords, a step's
 // three samples a pair and a single through v_sad_u16, and two samples ride in a packed operation as they lie)
-typedef uint16_t u16x2q __attribute__((ext_vector_type(2)));
-typedef int16_t i16x2q __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ u16x2q pkq(uint32_t v) { return __builtin_bit_cast(u16x2q, v); }
-__device__ __forceinline__ uint32_t unq(u16x2q v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ u16x2q pkq1(uint32_t both) { return pkq(both * 0x00010001u); }
-__device__ __forceinline__ u16x2q pkq_lt(u16x2q a, u16x2q b) { return (u16x2q)((u16x2q)(a - b) >> 15); }   // halves below 2^15
 
 // the variance and the edge test on the fixed 2 x 5 neighbourhood (:1213-1240), on values (T0 .. T4 / B0 .. B4: the samples
 // x - 2 .. x + 2 of the rows above / below)
@@ -2045,16 +1930,16 @@ template <int G, int N> __device__ __forceinline__ uint32_t lat16_one(const uint
 #define LAT16_SAD3(wa, GA, wb, GB) \
     __builtin_amdgcn_sad_u16(lat16_pair<GA>(wa), lat16_pair<GB>(wb), __builtin_amdgcn_sad_u16(lat16_one<(GA) + 2>(wa), lat16_one<(GB) + 2>(wb), 0u))
 // which of a window's eight samples are a direction (not the peak) within lim of d: sample 2i at bit i, 2i + 1 at bit 16 + i
-__device__ __forceinline__ uint32_t lat16_near8(const uint32_t (&w)[4], u16x2q d2, u16x2q lim1, u16x2q peak2)
+__device__ __forceinline__ uint32_t lat16_near8(const uint32_t (&w)[4], u16x2 d2, u16x2 lim1, u16x2 peak2)
 {
     uint32_t m = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++)
     {
-        const u16x2q h = pkq(w[i]);
-        const i16x2q t = __builtin_bit_cast(i16x2q, (u16x2q)(h - d2));
-        const u16x2q a = __builtin_bit_cast(u16x2q, __builtin_elementwise_max(t, (i16x2q)(-t)));
-        m |= unq(pkq_lt(a, lim1) & (pkq_lt(h ^ peak2, pkq1(1)) ^ pkq1(1))) << i;      // (not the peak: by equality - a value can lie above it)
+        const u16x2 h = pk(w[i]);
+        const i16x2 t = __builtin_bit_cast(i16x2, (u16x2)(h - d2));
+        const u16x2 a = __builtin_bit_cast(u16x2, __builtin_elementwise_max(t, (i16x2)(-t)));
+        m |= un(pk_lt(a, lim1) & (pk_lt(h ^ peak2, pk1(1)) ^ pk1(1))) << i;      // (not the peak: by equality - a value can lie above it)
     }
     return m;
 }
@@ -2066,7 +1951,7 @@ __device__ __forceinline__ unsigned long long lat16_stage_b_win(const Lat16Rows 
                                                                 unsigned long long base, const Lat16 &L)
 {
     const int here = dm[x];
-    const int lim = L.lim[iabs16(here - L.neutral) >> L.sh2];
+    const int lim = L.lim[iabs(here - L.neutral) >> L.sh2];
     const int dir = (here - L.neutral + (1 << (L.sh2 - 1))) >> L.sh2;
     const int startu = (dir - 2 < 0) ? max(-x + 1, max(dir - 2, -width + 2 + x)) : min(x - 1, min(dir - 2, width - 2 - x));
     const int stopu = (dir + 2 < 0) ? max(-x + 1, max(dir + 2, -width + 2 + x)) : min(x - 1, min(dir + 2, width - 2 - x));
@@ -2084,7 +1969,7 @@ __device__ __forceinline__ unsigned long long lat16_stage_b_win(const Lat16Rows 
     lat16_window4(R.ob, lx - hb - 3, q2);                    // x - (u >> 1) at sample 3 - (i >> 1)
     lat16_window4(R.top, lx - 1, tcw);
     lat16_window4(R.bot, lx - 1, bcw);
-    const u16x2q d2 = pkq1((uint32_t)here), lim1 = pkq1((uint32_t)min(lim + 1, 0x7fff)), peak2 = pkq1((uint32_t)L.peak);
+    const u16x2 d2 = pk1((uint32_t)here), lim1 = pk1((uint32_t)min(lim + 1, 0x7fff)), peak2 = pk1((uint32_t)L.peak);
     const uint32_t near_t = lat16_near8(ow, d2, lim1, peak2), near_b = lat16_near8(qw, d2, lim1, peak2);
     const uint32_t ulim = (uint32_t)lim, ulim2 = 2u * ulim;
     auto within = [&](uint32_t a, uint32_t b) { return a - b + ulim <= ulim2; };              // |a - b| <= lim
@@ -2131,7 +2016,7 @@ __device__ __forceinline__ unsigned long long lat16_stage_c(const uint16_t *top,
         const int h0 = u >> 1, h1 = (u + 1) >> 1;
         const int p1 = (int)top[x + h0] + (int)top[x + h1];
         const int p2 = (int)bot[x - h0] + (int)bot[x - h1];
-        const int diff = sad3w(top, x, bot, x - u) + sad3w(bot, x, top, x + u) + iabs16(p1 - p2);
+        const int diff = sad3w(top, x, bot, x - u) + sad3w(bot, x, top, x + u) + iabs(p1 - p2);
         if (diff < mn)
         {
             const int valt = (p1 + p2 + 2) >> 2;
@@ -2230,8 +2115,8 @@ __global__ __launch_bounds__(256) void q_lattice_cand(Q3 P, K16 k, int nt, unsig
             {
                 const int d = dv[j], dr = dv[j + 1];
                 const int avg = (tv[j + 2] + bv[j + 2] + 1) >> 1;
-                lim[j] = s_lim[iabs16(d - L.neutral) >> L.sh2];
-                const unsigned long long right = iabs16(d - dr) > lim[j] ? 1ull << 49 : 0ull;
+                lim[j] = s_lim[iabs(d - L.neutral) >> L.sh2];
+                const unsigned long long right = iabs(d - dr) > lim[j] ? 1ull << 49 : 0ull;
                 if (d != L.peak && x + j < width) searching |= 1u << j;
                 base[j] = (unsigned long long)(uint16_t)avg | right;
                 w[j] = base[j] | lat16_word(avg, L.neutral) | (1ull << 48);                  // the word of a sample without a direction
@@ -2297,11 +2182,6 @@ __global__ __launch_bounds__(256) void q_lattice_cand(Q3 P, K16 k, int nt, unsig
 // thread come in as two 16-byte loads, the direction row as 8 bytes, a thread composes the 2-state maps of its four samples
 // before the wave scan, both rows leave as 8 bytes, limlut sits in LDS.
 constexpr int LR16_T = 256, LR16_PX = 4 * LR16_T;
-
-__device__ __forceinline__ unsigned lr16_compose(unsigned later, unsigned earlier)     // later o earlier (earlier applies first)
-{
-    return ((later >> (earlier & 1u)) & 1u) | (((later >> ((earlier >> 1) & 1u)) & 1u) << 1);
-}
 
 __global__ __launch_bounds__(LR16_T) void q_lattice_resolve16(Q3 P, K16 k, const unsigned long long *__restrict__ cand,
                                                               int cand_pitch, int cand_plane_stride)
@@ -2385,16 +2265,16 @@ __global__ __launch_bounds__(LR16_T) void q_lattice_resolve16(Q3 P, K16 k, const
         for (int j = 0; j < 4; j++)
         {
             const unsigned long long cj = c[j];
-            const int lim = s_lim[min(iabs16(d[j] - k.neutral) >> sh2, 32)];
+            const int lim = s_lim[min(iabs(d[j] - k.neutral) >> sh2, 32)];
             const bool always_a = (cj >> 48) & 1ull, right = (cj >> 49) & 1ull;
             if (j >= nlive || always_a) m[j] = 0u;
             else
             {
-                const unsigned oa = (right && iabs16(d[j] - pa) > lim) ? 0u : 1u;
-                const unsigned ob2 = (right && iabs16(d[j] - pb) > lim) ? 0u : 1u;
+                const unsigned oa = (right && iabs(d[j] - pa) > lim) ? 0u : 1u;
+                const unsigned ob2 = (right && iabs(d[j] - pb) > lim) ? 0u : 1u;
                 m[j] = oa | (ob2 << 1);
             }
-            pm[j] = j == 0 ? m[0] : lr16_compose(m[j], pm[j - 1]);
+            pm[j] = j == 0 ? m[0] : lr_compose(m[j], pm[j - 1]);
             pa = always_a ? k.peak : k.neutral;
             pb = (int)((cj >> 32) & 0xffffull);
         }
@@ -2403,7 +2283,7 @@ __global__ __launch_bounds__(LR16_T) void q_lattice_resolve16(Q3 P, K16 k, const
         for (int off = 1; off < 64; off <<= 1)
         {
             const unsigned e = __shfl_up(tm, off, 64);
-            if (lane >= off) tm = lr16_compose(tm, e);
+            if (lane >= off) tm = lr_compose(tm, e);
         }
         if (lane == 63) s_wmap[wave] = (uint8_t)tm;
         unsigned before = __shfl_up(tm, 1, 64);
@@ -2446,101 +2326,6 @@ __global__ __launch_bounds__(LR16_T) void q_lattice_resolve16(Q3 P, K16 k, const
     }
 }
 
-// ---- post-processing 2/3 (:1391-1904), as in eedi2.hip but on uint16 samples -----------------------
-struct Corner16
-{
-    uint16_t *src, *tmp;
-    int      *c[3], *t[3];
-    int       pitch, width, height;
-};
-
-__device__ __forceinline__ int fold16(int centre, int d, int n, int &hi)
-{
-    int lo = centre - d;
-    hi = centre + d;
-    if (lo < 0) lo = hi;
-    if (hi >= n) hi = lo;
-    return lo;
-}
-
-template <bool VERT>
-__global__ void q_blur1(Corner16 A)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const uint16_t *in = VERT ? A.tmp : A.src;
-    uint16_t *out = VERT ? A.src : A.tmp;
-    const int W[4] = { 26152, 15862, 3539, 291 };
-    int acc = (int)in[(size_t)y * A.pitch + x] * W[0] + 32768;
-#pragma unroll
-    for (int d = 1; d <= 3; d++)
-    {
-        int hi;
-        const int lo = fold16(VERT ? y : x, d, VERT ? A.height : A.width, hi);
-        const size_t il = VERT ? (size_t)lo * A.pitch + x : (size_t)y * A.pitch + lo;
-        const size_t ih = VERT ? (size_t)hi * A.pitch + x : (size_t)y * A.pitch + hi;
-        acc += ((int)in[il] + (int)in[ih]) * W[d];
-    }
-    out[(size_t)y * A.pitch + x] = (uint16_t)(acc >> 16);
-}
-
-__global__ void q_derivatives(Corner16 A, int shift)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const uint16_t *s = A.src + (size_t)y * A.pitch;
-    const uint16_t *up = A.src + (size_t)max(y - 1, 0) * A.pitch, *dn = A.src + (size_t)min(y + 1, A.height - 1) * A.pitch;
-    const int ix = ((int)s[min(x + 1, A.width - 1)] - (int)s[max(x - 1, 0)]) >> shift;
-    const int iy = ((int)up[x] - (int)dn[x]) >> shift;
-    const size_t at = (size_t)y * A.pitch + x;
-    A.c[0][at] = (ix * ix) >> 1;
-    A.c[1][at] = (iy * iy) >> 1;
-    A.c[2][at] = (ix * iy) >> 1;
-}
-
-template <bool VERT>
-__global__ void q_blur_sqrt2(Corner16 A)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= A.width || y >= A.height) return;
-    const int *in = VERT ? A.t[blockIdx.z] : A.c[blockIdx.z];
-    int *out = VERT ? A.c[blockIdx.z] : A.t[blockIdx.z];
-    const int W[5] = { 18508, 14415, 6809, 1951, 339 };
-    int acc = in[(size_t)y * A.pitch + x] * W[0] + 32768;
-#pragma unroll
-    for (int d = 1; d <= 4; d++)
-    {
-        int hi;
-        int lo = fold16(VERT ? y : x, d, VERT ? A.height : A.width, hi);
-        if (!VERT && d == 3 && x == A.width - 2) lo = hi = x + 3;                  // :1589
-        const size_t il = VERT ? (size_t)lo * A.pitch + x : (size_t)y * A.pitch + lo;
-        const size_t ih = VERT ? (size_t)hi * A.pitch + x : (size_t)y * A.pitch + hi;
-        acc += (in[il] + in[ih]) * W[d];
-    }
-    out[(size_t)y * A.pitch + x] = acc >> (VERT ? 18 : 16);
-}
-
-__global__ void q_post_corner(Corner16 A, const uint16_t *msk, uint16_t *dst, int field, int height, int peak, int neutral)
-{
-    const int x = blockIdx.x * blockDim.x + threadIdx.x, r = blockIdx.y * blockDim.y + threadIdx.y;
-    const int y = 8 - field + 2 * r;
-    if (x < 4 || x >= A.width - 4 || y >= height - 7) return;
-    const size_t at = (size_t)y * A.pitch + x;
-    const int m = msk[at];
-    if (m == peak || m == neutral) return;
-    bool hit = false;
-#pragma unroll
-    for (int q = 0; q < 2; q++)
-    {
-        const size_t i = (size_t)(3 + r + q) * A.pitch + x;
-        const int a = A.c[0][i], b = A.c[1][i], c = A.c[2][i];
-        const double s = (double)(a + b);
-        const double resp = (double)(a * b - c * c) - 0.09 * s * s;
-        hit |= (int)resp > 775;
-    }
-    if (hit) dst[at] = (uint16_t)(((int)dst[at - A.pitch] + (int)dst[at + A.pitch] + 1) >> 1);
-}
-
 } // namespace
 
 // ------------------------------------------------------------------- engine
@@ -2556,7 +2341,7 @@ Eedi2Engine16::Eedi2Engine16(hbhip_ctx *ctx, const PicGeometry &geo, const Eedi2
 int Eedi2Engine16::init()
 {
     if (geo_.bps != 2 || geo_.depth < 9 || geo_.depth > 16) return HBHIP_ERR_UNSUPPORTED;
-    const int rc = init_slots({ 2 * GUARD16, sizeof(unsigned long long), QM_W, QM_H, QM_OY });     // (guard in bytes)
+    const int rc = init_slots({ 2 * GUARD16, sizeof(unsigned long long), QM::W, QM::H, QM::OY });     // (guard in bytes)
     if (rc != HBHIP_OK) return rc;
     HBHIP_CHECK(ctx_, hipStreamSynchronize(ctx_->stream));
     return HBHIP_OK;
@@ -2595,28 +2380,19 @@ int Eedi2Engine16::enqueue_mask(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
         P.a[c] = (uint16_t *)srcp.plane[c]; P.b[c] = (uint16_t *)old.plane[c]; P.c[c] = (uint16_t *)mskp.plane[c];
         S.sp[c] = src_pitch_[c] / 2;
     }
-    const int mth = par_.magnitude_threshold * 10, vth = par_.laplacian_threshold * 81, lth = par_.variance_threshold;   // sic: swapped (decomb_template.c:390)
-    const unsigned gx = (srcp.width[0] + QM_W - 1) / QM_W, gy = (srcp.height[0] + QM_H - 1) / QM_H;
-    uint32_t epoch = 0;
-    { const int erc = next_epoch(lc, &epoch); if (erc != HBHIP_OK) return erc; }
-    *epoch_out = epoch;
-    uint32_t *pflags = plane_flags_ + 3 * f0;
+    MaskChain C;
+    { const int erc = begin_mask(lc, f0, true, &C); if (erc != HBHIP_OK) return erc; }
+    *epoch_out = C.epoch;
+    const EediMaskThresholds th = mask_thresholds();
     if (n == 1)
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_mask_passes", q_mask_fused, dim3(gx, gy, 3), dim3(QM_T), 0, P, S, k, 0, 0, mth, vth, lth,
-                        par_.erosion_threshold, par_.dilation_threshold, pflags, epoch);
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_mask_passes", q_mask_fused, dim3((srcp.width[0] + QM::W - 1) / QM::W, (srcp.height[0] + QM::H - 1) / QM::H, 3),
+                        dim3(QM::T), 0, P, S, k, 0, 0, th.mth, th.vth, th.lth, par_.erosion_threshold, par_.dilation_threshold, C.pflags, C.epoch);
     else
     {
         // one launch, field-major: a field's chain tiles, then its upper tiles (see Eedi2Engine::enqueue_mask)
-        MaskChain C = eedi_mask_chain_tiles(srcp, QM_W, QM_H, QM_OY);
-        C.flags = chain_flags_;
-        C.pflags = pflags;
-        C.epoch = epoch;
-        C.group = C.ntiles + C.nupper;
-        C.has = chain_has_ + (size_t)f0 * C.group;
-        guard_.bind(C);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_mask_passes", q_mask_chain, dim3((unsigned)(C.group * n)), dim3(QM_T), 0, P, S, k, C, mth, vth, lth,
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_mask_passes", q_mask_chain, dim3((unsigned)(C.group * n)), dim3(QM::T), 0, P, S, k, C, th.mth, th.vth, th.lth,
                         par_.erosion_threshold, par_.dilation_threshold);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_mask_repair", q_mask_chain_repair, dim3(3u * (unsigned)n), dim3(QM_T), 0, P, S, k, C, n, mth, vth, lth,
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_mask_repair", q_mask_chain_repair, dim3(3u * (unsigned)n), dim3(QM::T), 0, P, S, k, C, n, th.mth, th.vth, th.lth,
                         par_.erosion_threshold, par_.dilation_threshold);
     }
     HBHIP_CHECK(lc, hipGetLastError());
@@ -2746,29 +2522,9 @@ int Eedi2Engine16::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, 
     }
     if (par_.post_processing == 2 || par_.post_processing == 3)
     {
-        // field after field, plane after plane: the derivative arrays carry values along (eedi2.hip, CornerArgs)
-        for (int f = 0; f < n; f++)
-        {
-            const int tff = (int)((tffbits_ >> (f0 + f)) & 1u);
-            const size_t foff = (size_t)f * slot_bytes_;
-            for (int c = 0; c < 3; c++)
-            {
-                Corner16 A;
-                A.src = (uint16_t *)(srcp.plane[c] + foff); A.tmp = (uint16_t *)(tmpp.plane[c] + foff);
-                for (int i = 0; i < 3; i++) { A.c[i] = deriv_[i]; A.t[i] = deriv_tmp_[i]; }
-                A.pitch = srcp.stride[c] / 2; A.width = srcp.width[c]; A.height = srcp.height[c];
-                const dim3 g1((A.width + 63) / 64, (A.height + 3) / 4, 1), g3(g1.x, g1.y, 3);
-                HBHIP_LAUNCH_ON(lc, st, "eedi2_16_gaussian_blur1_h", q_blur1<false>, g1, blk, 0, A);
-                HBHIP_LAUNCH_ON(lc, st, "eedi2_16_gaussian_blur1_v", q_blur1<true>, g1, blk, 0, A);
-                HBHIP_LAUNCH_ON(lc, st, "eedi2_16_calc_derivatives", q_derivatives, g1, blk, 0, A, k.shift);
-                HBHIP_LAUNCH_ON(lc, st, "eedi2_16_gaussian_blur_sqrt2_h", q_blur_sqrt2<false>, g3, blk, 0, A);
-                HBHIP_LAUNCH_ON(lc, st, "eedi2_16_gaussian_blur_sqrt2_v", q_blur_sqrt2<true>, g3, blk, 0, A);
-                const int rows = (dst2p.height[c] - 7 - (8 - tff) + 1) / 2;
-                if (rows > 0)
-                    HBHIP_LAUNCH_ON(lc, st, "eedi2_16_post_process_corner", q_post_corner, dim3((A.width + 63) / 64, (rows + 3) / 4, 1), blk, 0, A,
-                                 (const uint16_t *)(tmp2p2.plane[c] + foff), (uint16_t *)(dst2p.plane[c] + foff), tff, dst2p.height[c], k.peak, k.neutral);
-            }
-        }
+        static const char *const names[6] = { "eedi2_16_gaussian_blur1_h", "eedi2_16_gaussian_blur1_v", "eedi2_16_calc_derivatives",
+                                              "eedi2_16_gaussian_blur_sqrt2_h", "eedi2_16_gaussian_blur_sqrt2_v", "eedi2_16_post_process_corner" };
+        enqueue_corner<uint16_t>(f0, n, lc, st, names);
     }
     HBHIP_CHECK(lc, hipGetLastError());
     return HBHIP_OK;

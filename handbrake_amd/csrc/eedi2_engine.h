@@ -37,8 +37,8 @@ struct EediFrame
 // field-major and dispatched in that order, so a waiting workgroup only ever waits for one that is already resident
 // or done; the wait is bounded all the same.  When it runs out the tile does NOT abort anything: it raises the launch's
 // error word, goes on with the mask as it finds it (atomic loads: a defined value) and publishes itself like every
-// other tile, so the launch always ends; a repair pass queued behind the launch - its workgroup 0 - (eedi_chain_repair_tile
-// loop: k_mask_chain_repair / q_mask_chain_repair) looks at the word and, only if it is up, recomputes the lower tiles
+// other tile, so the launch always ends; a repair pass queued behind the launch - its workgroup 0 -
+// (k_mask_chain_repair / q_mask_chain_repair: eedi_chain_repair_begin, the loop, eedi_chain_repair_end) looks at the word and, only if it is up, recomputes the lower tiles
 // of the launch's fields serially in field order - the per-field form of the same arithmetic, no waits - and counts the
 // event for the host, which logs it once (MaskChainGuard).  Two workgroups on different XCDs do not share
 // an L2: the chain's mask words and flags therefore move as agent-scope relaxed atomics (sc1 loads and write-through
@@ -262,6 +262,38 @@ __device__ __forceinline__ void eedi_chain_lower_tile(const MaskChain &C, int ti
     by = C.ty0[pl] + ry;
 }
 
+// The pass queued behind every chain launch (k_mask_chain_repair / q_mask_chain_repair), a workgroup of `nthreads` per
+// field and plane: eedi_chain_repair_begin, the engine's loop over the launch's lower tiles, eedi_chain_repair_end.
+//  * Each workgroup folds the words its plane's tiles left in C.has into the plane flag (P3::pflags: the passes behind the
+//    mask take a shortcut for a plane without a mask pixel) - the tiles themselves no longer look at the flag, which cost
+//    every workgroup of the chain a round trip at its end.
+//  * Workgroup 0 then has nothing to do unless a wait of the chain ran out (C.err): begin returns false.  Otherwise R is
+//    the chain the repair runs on, and the kernel recomputes the launch's lower tiles field after field, tile after tile
+//    (eedi_chain_lower_tile, then its chain tile - mask_tile<true> / qmask_tile<true> - on R and a barrier), in this one
+//    workgroup; program order is the dependency order, every flag already carries the epoch (each tile publishes itself,
+//    timed out or not), so the waits inside it pass at once - from the same sources with the same arithmetic: the new
+//    masks end up as the per-field launches would have left them.  (The upper tiles and SRCPF never depended on another
+//    field.)  A plane flag that went up for a mask the repair empties only costs the shortcut.  end clears the error word
+//    and counts the event for the host.
+//  (The loop stays in the two kernels: handed to a shared function as a callable, the tile is optimised on its own before
+//  it is inlined, and both kernels came out with other instructions and registers than the ones they were tested with.)
+__device__ __forceinline__ bool eedi_chain_repair_begin(const MaskChain &C, int nthreads, MaskChain &R)
+{
+    eedi_chain_fold_has(C, nthreads);
+    if (blockIdx.x != 0 || __hip_atomic_load(C.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return false;   // block-uniform
+    R = C;
+    R.has = nullptr;                                               // the repaired tiles raise the plane flags themselves
+    return true;
+}
+__device__ __forceinline__ void eedi_chain_repair_end(const MaskChain &C)
+{
+    if (threadIdx.x == 0)
+    {
+        __hip_atomic_store(C.err, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(C.fallbacks, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 // HBHIP_EEDI2_FORK=0: the passes of a whole batch on the caller's stream, one launch per pass (profiling runs: a launch then
 // covers all fields of the batch, as the counters' bookkeeping and the kernel-timer pass of bench.py assume)
 static inline bool eedi_fork_enabled()
@@ -291,6 +323,7 @@ struct EediLayout
     size_t cand_elem;                 // bytes per lattice candidate word
     int    tile_w, tile_h, tile_oy;   // the mask kernel's tile (eedi_mask_chain_tiles)
 };
+struct EediMaskThresholds { int mth, vth, lth; };   // build_edge_mask's magnitude, variance and laplacian tests
 class EediEngineBase
 {
 public:
@@ -314,6 +347,10 @@ protected:
     size_t place_frame(EediFrame &f, int width, int height, size_t at) const;
     EediFrame at_slot(const EediFrame &f, int slot) const;
     int  next_epoch(hbhip_ctx *lc, uint32_t *epoch);
+    int  begin_mask(hbhip_ctx *lc, int f0, bool has, MaskChain *C);   // the next mask launch: its number and its chain, bound
+    EediMaskThresholds mask_thresholds() const;                       // Eedi2Params as the mask kernels take them
+    // post-processing 2/3 of fields f0 .. f0 + n - 1 on st (eedi2_corner.h); PIX: the engine's sample type
+    template <typename PIX> void enqueue_corner(int f0, int n, hbhip_ctx *lc, hipStream_t st, const char *const (&name)[6]);
     virtual bool may_fork() const { return true; } // beyond what launch() itself rules out
     virtual bool mask_ahead() const { return false; }   // the next part's mask on a stream of its own (launch())
     // the five mask passes (+ the field extraction) of fields f0 .. f0 + n - 1 of the batch on st; *epoch: the launch's number
@@ -331,6 +368,7 @@ protected:
     int         src_pitch_[3] = {0, 0, 0};
     uint8_t    *slab_ = nullptr;
     size_t      slot_bytes_ = 0;
+    EediLayout  layout_ = {};
     EediFrame   half_[4];    // slot 0's SRCPF, MSKPF, TMPPF, DSTPF          (decomb.c:64-68)
     EediFrame   full_[5];    // slot 0's DST2PF, TMP2PF2, MSK2PF, TMP2PF, DST2MPF (decomb.c:69-74)
     uint8_t    *cand_raw_ = nullptr;    // slot 0's interpolate_lattice candidates (cand_pitch_ words a row, per plane cand_plane_stride_)
