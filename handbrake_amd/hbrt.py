@@ -211,7 +211,7 @@ class Chain:
 
 
 # hb_filter_object_t ids (handbrake/common.h:1729-1778; include/hbhip_libhb.h)
-FILTER_ID = {"detelecine": 3, "comb_detect": 4, "decomb": 6, "yadif": 7, "bwdif": 9, "vfr": 11, "deblock": 12, "deband": 13, "render_sub": 21, "denoise": 14, "nlmeans": 16, "chroma_smooth": 17,
+FILTER_ID = {"detelecine": 3, "comb_detect": 4, "decomb": 6, "yadif": 7, "bwdif": 9, "vfr": 11, "deblock": 12, "deband": 13, "bm3d": 15, "render_sub": 21, "denoise": 14, "nlmeans": 16, "chroma_smooth": 17,
              "rotate": 19, "crop_scale": 22, "lapsharp": 24, "unsharp": 26, "grayscale": 28, "pad": 30,
              "colorspace": 32, "format": 33}
 

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "hbhip_detelecine_create", "hbhip_detelecine_push", "hbhip_detelecine_push_frame",
     "hbhip_deblock_create", "hbhip_deblock_set_warmup",
     "hbhip_deband_create", "hbhip_deband_offsets", "hbhip_deband_set_kernel",
+    "hbhip_bm3d_params_from_settings", "hbhip_bm3d_create",
 ]
 
 
@@ -64,6 +65,12 @@ class DeblockParams(C.Structure):
 
 class DebandParams(C.Structure):
     _fields_ = [("thr", C.c_int * 3), ("blur", C.c_int), ("range", C.c_int), ("direction", C.c_float)]
+
+
+class Bm3dParams(C.Structure):
+    _fields_ = [("sigma", C.c_float)] + [(n, C.c_int) for n in ("block", "bstep", "group", "range", "mstep")] + \
+               [("thmse", C.c_float), ("hdthr", C.c_float), ("estim", C.c_int), ("planes", C.c_int),
+                ("thr", C.c_float * 3), ("dct", C.c_float * 256)]
 
 
 _lib = None
@@ -135,6 +142,7 @@ def lib() -> C.CDLL:
         L.hbhip_ctx_upload_done.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.hbhip_filter_use_frames.argtypes = [C.c_void_p]
         L.hbhip_decomb_push_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
+        L.hbhip_bm3d_params_from_settings.argtypes = [C.c_char_p, C.c_int, C.POINTER(Bm3dParams)]
         _lib = L
     return _lib
 

@@ -111,6 +111,7 @@ extern hb_filter_object_t hb_filter_comb_detect_hip;
 extern hb_filter_object_t hb_filter_detelecine_hip;
 extern hb_filter_object_t hb_filter_deblock_hip;
 extern hb_filter_object_t hb_filter_deband_hip;
+extern hb_filter_object_t hb_filter_bm3d_hip;
 
 #ifndef HBHIP_IN_LIBHB
 void hbhip_nlmeans_params_from_settings(const char *settings, int depth, hbhip_nlmeans_params *p);   /* bench / tests only */

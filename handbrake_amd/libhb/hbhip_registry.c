@@ -208,6 +208,7 @@ hb_filter_object_t *hbhip_filter_get(int filter_id)
         case HB_FILTER_DETELECINE:    return &hb_filter_detelecine_hip;
         case HB_FILTER_DEBLOCK:       return &hb_filter_deblock_hip;
         case HB_FILTER_DEBAND:        return &hb_filter_deband_hip;
+        case HB_FILTER_BM3D:          return &hb_filter_bm3d_hip;
         case HB_FILTER_HIP_UPLOAD:    return &hb_filter_hip_upload;
         case HB_FILTER_HIP_DOWNLOAD:  return &hb_filter_hip_download;
         default:                      return NULL;

@@ -428,6 +428,28 @@ int hbhip_deband_offsets(int width, int height, int range, float direction, int 
 /* test / tool hook: which kernel runs - 0 the automatic choice (the LDS tile where its halo fits), 1 the
  * LDS tile (HBHIP_ERR_UNSUPPORTED where the halo does not fit), 2 the direct global gather.  The result is the same. */
 int hbhip_deband_set_kernel(hbhip_filter *f, int kernel);
+/* FFmpeg `bm3d=sigma=..` as bm3d_init sets it up (bm3d.c:44-57): every other option keeps FFmpeg's default, so the group
+ * size is 1 and the filter is a sliding 16 x 16 DCT with a hard threshold and weighted aggregation over all three planes.
+ * The fields after sigma are those defaults (recalled; the one table of csrc/bm3d.hip) and what follows from them: thr[z],
+ * the threshold of a coefficient with z of its two frequencies zero, and dct[k * 16 + n] = cos(pi (2n + 1) k / 32), built
+ * in double and rounded once.  Out of place.  8/10/12-bit planar 4:2:0 / 4:2:2 / 4:4:4; HBHIP_ERR_UNSUPPORTED for a plane
+ * narrower or lower than 16 samples and for options other than the defaults.  Arithmetic restated (parity unpinned,
+ * DESIGN.md §4.18). */
+typedef struct hbhip_bm3d_params
+{
+    float sigma;                         /* as FFmpeg holds it: the "%g" text parsed into a float option */
+    int   block, bstep, group, range, mstep;   /* 16, 4, 1, 9, 1                               */
+    float thmse, hdthr;                  /* 0, 2.7                                        */
+    int   estim, planes;                 /* 0 = basic, 7                                  */
+    float thr[3];                        /* hdthr sigma sqrt2 16 16 2^(depth - 8) / 255 * sqrt2^(1 + z) */
+    float dct[256];
+} hbhip_bm3d_params;
+/* `settings` ("sigma=3"; absent: 1, bm3d.c:46) -> parameters, through the "%g" text bm3d.c's double becomes on its way
+ * into FFmpeg.  Needs no device.  HBHIP_OK, or HBHIP_ERR_UNSUPPORTED where FFmpeg's graph would fail (sigma NaN, negative
+ * or above 99999.9) or for a depth other than 8 / 10 / 12. */
+int hbhip_bm3d_params_from_settings(const char *settings, int depth, hbhip_bm3d_params *out);
+int hbhip_bm3d_create(hbhip_ctx *ctx, const hbhip_bm3d_params *p, int width, int height, int depth,
+                      int log2_chroma_w, int log2_chroma_h, hbhip_filter **out);
 /* `format=pix_fmts=<fmt>` as format_init sets it up (format.c:13-111): libavfilter then converts with a same-size
  * `scale`, i.e. libswscale's unscaled planar copy.  Built: planar YUV depth changes 8 / 10 / 12 -> 8 / 10 / 12 with the
  * chroma subsampling unchanged (up: shift, full-range luma replicates the top bits; down: ordered dither - the

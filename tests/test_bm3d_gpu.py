@@ -1,0 +1,233 @@
+"""GPU: the BM3D drop-in (csrc/bm3d.hip, libhb/bm3d_hip.c).  Where the definition leaves no room - sigma 0, constant
+planes, repetition, bursts, tile positions, a device-resident run - the bytes are exact; against the float64 model
+(tests/bm3d_model.py) every plane is within one code value and within twice the share of differing samples that the
+float32 restatement of the model shows (bm3d_model.ALLOW_*: measured by tests/test_bm3d_cpu.py on these same cases)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import bm3d_cases as bc
+import bm3d_model as bm
+from handbrake_amd import hbrt, hip, synth
+
+pytestmark = pytest.mark.gpu
+DROPIN = "hb_filter_bm3d_hip"
+LCW = bc.LCW
+
+
+def run(frames, sigma, sub="2x2", depth=8):
+    got = hbrt.run_stream(hip.filters(), [(DROPIN, f"sigma={sigma}")], frames, pix_fmt=hbrt.PIX_FMT[(sub, depth)])
+    assert len(got) == len(frames)
+    return [g.planes for g in got]
+
+
+def same(got, want, what=""):
+    assert len(got) == len(want) > 0
+    for t in range(len(want)):
+        for c in range(3):
+            assert got[t][c].shape == want[t][c].shape, f"{what} frame {t} plane {c} shape"
+            np.testing.assert_array_equal(got[t][c], want[t][c], err_msg=f"{what} frame {t} plane {c}")
+
+
+# ---- exact ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("w,h,sub", [(16, 16, "1x1"), (64, 48, "2x2")])
+@pytest.mark.parametrize("depth", [8, 10])
+def test_sigma_zero_is_the_identity(built, w, h, sub, depth):
+    frames = [bc.content("random", w, h, sub, depth, t)[0] for t in range(2)]
+    same(run(frames, 0, sub, depth), frames, "sigma 0")
+
+
+@pytest.mark.parametrize("depth,values", [(8, (0, 37, 255)), (12, (4095, 2049, 5))])
+def test_constant_planes_are_unchanged(built, depth, values):
+    """a constant plane is its DC coefficient alone, 256 v, and comes back as it went in while that passes the threshold:
+    at sigma 6 from v = 1 at 8 bits and v = 5 at 12 bits (thr[2] = 65.1 and 1040.9); below, the plane is 0 by definition"""
+    dt = np.uint8 if depth == 8 else np.uint16
+    frames = [tuple(np.full(s, v, dt) for s in bc.plane_shapes(70, 50, "2x2")) for v in values]
+    for sigma in (1, 6):
+        same(run(frames, sigma, "2x2", depth), frames, f"constant sigma {sigma}")
+    low = [tuple(np.full(s, 4, np.uint16) for s in bc.plane_shapes(70, 50, "2x2"))]
+    if depth == 12:
+        same(run(low, 6, "2x2", 12), [tuple(np.zeros_like(p) for p in low[0])], "a constant below the threshold")
+
+
+def test_twice_the_same_bytes(built):
+    frames = [bc.content("noisy", 200, 120, "2x2", 8, t)[0] for t in range(2)]
+    a = run(frames, 6)
+    b = run(frames, 6)
+    same(a, b, "second run")
+    assert not np.array_equal(a[0][0], frames[0][0])
+
+
+# ---- the C ABI directly: bursts, pitches, shared frames ---------------------------------------------------------------------
+def _make(ctx, sigma, w, h, depth=8, lcw=1, lch=1):
+    p = hip.Bm3dParams()
+    assert hip.lib().hbhip_bm3d_params_from_settings(f"sigma={sigma}".encode(), depth, C.byref(p)) == 0
+    return hip._create("hbhip_bm3d_create", ctx, [C.c_void_p, C.POINTER(hip.Bm3dParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
+                       ctx.h, C.byref(p), w, h, depth, lcw, lch)
+
+
+def _bursts(sigma, frames, sizes, pads=(0,), depth=8):
+    """frames through one filter in device-resident bursts of the given sizes (one process_dev call each); input i's rows
+    are padded by pads[i % len(pads)] samples, so that pitches mix inside a burst"""
+    import torch
+    h, w = frames[0][0].shape
+    wide = depth > 8
+    tdt = torch.int16 if wide else torch.uint8
+    ctx = hip.Ctx(0)
+    flt = _make(ctx, sigma, w, h, depth)
+    out = []
+    try:
+        at = 0
+        for n in sizes:
+            part = frames[at:at + n]
+            dev_in, keep = [], []
+            for i, f in enumerate(part):
+                pad = pads[(at + i) % len(pads)]
+                planes = []
+                for p in f:
+                    full = torch.zeros((p.shape[0], p.shape[1] + pad), dtype=tdt, device="cuda")
+                    full[:, :p.shape[1]] = torch.from_numpy(p.view(np.int16) if wide else p).cuda()
+                    keep.append(full)
+                    planes.append(full[:, :p.shape[1]])
+                dev_in.append(planes)
+            at += n
+            outs = [[torch.full(p.shape, 7, dtype=tdt, device="cuda") for p in f] for f in part]
+            torch.cuda.synchronize()
+            arr_in = (hip.DevFrame * n)(*[hip.dev_frame(f) for f in dev_in])
+            arr_out = (hip.DevFrame * n)(*[hip.dev_frame(o) for o in outs])
+            assert flt.process_dev(arr_in, 0, arr_out) == n
+            ctx.sync()
+            conv = (lambda t: t.cpu().numpy().view(np.uint16)) if wide else (lambda t: t.cpu().numpy())
+            out += [[conv(p) for p in o] for o in outs]
+            for f, d in zip(part, dev_in):                               # out of place: the inputs are untouched
+                for c in range(3):
+                    np.testing.assert_array_equal(conv(d[c]), f[c])
+        return out
+    finally:
+        flt.close()
+        ctx.close()
+
+
+@pytest.mark.parametrize("depth", [8, 10])
+def test_burst_with_two_pitches_equals_frame_by_frame(built, depth):
+    frames = [bc.content("noisy", 72, 56, "2x2", depth, t)[0] for t in range(5)]
+    one = _bursts(3, frames, [1] * 5, depth=depth)
+    same(_bursts(3, frames, [5], pads=(0, 0, 64, 5, 0), depth=depth), one, "a burst of 5, three pitches apart")
+    same(_bursts(3, frames, [5], pads=(0, 16), depth=depth), one, "a burst of 5, two pitches")
+    same(run(frames, 3, "2x2", depth), one, "through the drop-in")
+
+
+def test_a_shared_input_frame_is_not_written(built):
+    """a vfr duplicate shares its device picture (hbhip_frame_refs > 1): the filter reads it and writes elsewhere"""
+    L = hip.lib()
+    L.hbhip_filter_push_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+    L.hbhip_filter_pull_frame.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]
+    w, h = 72, 56
+    planes = [np.ascontiguousarray(p) for p in bc.content("noisy", w, h, "2x2", 8)[0]]
+    ctx = hip.Ctx(0)
+    flt = _make(ctx, 6, w, h)
+    fr = hip.Frame(ctx, w, h)
+    try:
+        hip.check(L.hbhip_filter_use_frames(flt.h), ctx.h, "use_frames")
+        fr.upload(planes)
+        fr.retain()                                                      # a second holder, as a duplicate's buffer is
+        outs = []
+        for tag in range(2):
+            assert fr.refs() >= 2
+            hip.check(L.hbhip_filter_push_frame(flt.h, fr.h, tag), ctx.h, "push_frame")
+            o, t = C.c_void_p(), C.c_int64()
+            hip.check(L.hbhip_filter_pull_frame(flt.h, C.byref(o), C.byref(t)), ctx.h, "pull_frame")
+            out = hip.Frame.__new__(hip.Frame)
+            out.ctx, out.h, out.shape = ctx, o, (w, h, 8, 1, 1)
+            assert o.value != fr.h.value
+            outs.append(out)
+        ctx.sync()
+        back = fr.download()
+        got = [o.download() for o in outs]
+        for o in outs:
+            o.close()
+        fr.release()
+        for c in range(3):
+            np.testing.assert_array_equal(back[c], planes[c])
+        same(got, [got[0], got[0]], "both pushes of the shared frame")
+        same(got[:1], run([tuple(planes)], 6), "the shared frame's output")
+        assert not np.array_equal(got[0][0], planes[0])
+    finally:
+        fr.close()
+        flt.close()
+        ctx.close()
+
+
+# ---- against the float64 model ----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sigma", [1, 6])
+@pytest.mark.parametrize("depth", bc.DEPTHS)
+@pytest.mark.parametrize("w,h,sub", bc.SHAPES)
+def test_against_the_float64_model(built, w, h, sub, depth, sigma):
+    frames = [bc.content(kind, w, h, sub, depth)[0] for kind in bc.CONTENTS]
+    got = run(frames, sigma, sub, depth)
+    for kind, g, src in zip(bc.CONTENTS, got, frames):
+        want = bc.reference(kind, w, h, sub, depth, sigma)
+        for c, (mx, share) in enumerate(bc.differences(g, want)):
+            print(f"bm3d {w}x{h} {sub} {depth} bits sigma {sigma} {kind} plane {c}: max |diff| {mx}, share {share:.6g}")
+            assert mx <= bm.ALLOW_MAX_ABS, (kind, c, mx)
+            assert share <= bm.GPU_SHARE_FACTOR * bm.ALLOW_SHARE, (kind, c, share)
+        if sigma == 6 and kind == "noisy":
+            clean = bc.content(kind, w, h, sub, depth)[1]
+            for c in range(3):
+                e_in = np.mean((src[c].astype(np.float64) - clean[c]) ** 2)
+                e_out = np.mean((g[c].astype(np.float64) - clean[c]) ** 2)
+                assert not np.array_equal(g[c], src[c]) and e_out < e_in, (c, e_in, e_out)
+        if sigma == 6:
+            assert any(not np.array_equal(g[c], src[c]) for c in range(3)), kind
+
+
+# ---- tile seams -------------------------------------------------------------------------------------------------------------
+def test_tile_position_does_not_show(built):
+    """A 200 x 120 frame alone and the same samples 32 into a 264 x 168 frame (16 in chroma): the tiles' seams fall on other
+    samples, the blocks and the order they are added in do not change (the offset is a multiple of 16), so every sample
+    whose blocks all lie in the region - 15 from its top and left, 15 from its bottom and right - has the same bytes."""
+    small = bc.content("noisy", 200, 120, "2x2", 8)[0]
+    big = [p.copy() for p in bc.content("random", 264, 168, "2x2", 8)[0]]
+    for c, off in enumerate((32, 16, 16)):
+        hh, ww = small[c].shape
+        big[c][off:off + hh, off:off + ww] = small[c]
+    a = run([small], 6)[0]
+    b = run([tuple(big)], 6)[0]
+    for c, off in enumerate((32, 16, 16)):
+        hh, ww = small[c].shape
+        inner = b[c][off:off + hh, off:off + ww]
+        np.testing.assert_array_equal(inner[15:hh - 15, 15:ww - 15], a[c][15:hh - 15, 15:ww - 15], err_msg=f"plane {c}")
+        assert not np.array_equal(inner, a[c])                           # the rim does see its neighbours
+
+
+# ---- declines ---------------------------------------------------------------------------------------------------------------
+def test_declined_keep_the_cpu_filter(built):
+    for st, w, h in [("sigma=3", 24, 18), ("sigma=-1", 64, 48), ("sigma=100000", 64, 48)]:
+        with pytest.raises(RuntimeError):
+            hbrt.Chain(hip.filters(), [(DROPIN, st)], w, h)
+    hbrt.Chain(hip.filters(), [(DROPIN, "sigma=3")], 32, 32).close()                 # chroma 16 x 16: one block
+
+
+# ---- inside a device-resident run -------------------------------------------------------------------------------------------
+def test_device_run_with_vfr_duplicates(built):
+    """[upload, decomb 7, vfr, bm3d, lapsharp, download] equals the same list with BM3D as a stage of its own on downloaded
+    frames: vfr doubles the rate, so every other frame BM3D meets shares its device picture with the one before."""
+    TFF = 0x0008
+    LAP = "y-strength=0.2:y-kernel=isolap:cb-strength=0.2:cb-kernel=isolap"
+    VFRS = "mode=1:rate=60000/1001"
+    UP, DOWN = ("hb_filter_hip_upload", ""), ("hb_filter_hip_download", "")
+    F = hip.filters()
+    frames = synth.stream("interlaced", 128, 72, 9)
+    head = [("hb_filter_decomb_hip", "mode=7"), ("hb_filter_vfr_standin", VFRS)]
+    dev = hbrt.run_stream(F, [UP] + head + [(DROPIN, "sigma=3"), ("hb_filter_lapsharp_hip", LAP), DOWN], frames, flags=TFF)
+    mid = hbrt.run_stream(F, [UP] + head + [DOWN], frames, flags=TFF)
+    assert len(mid) > len(frames)                                        # vfr did duplicate
+    den = hbrt.run_stream(F, [(DROPIN, "sigma=3")], [m.planes for m in mid])
+    assert any(not np.array_equal(d.planes[0], m.planes[0]) for d, m in zip(den, mid))
+    want = hbrt.run_stream(F, [("hb_filter_lapsharp_hip", LAP)], [d.planes for d in den])
+    assert len(dev) == len(want) == len(mid)
+    for o, wt, m in zip(dev, want, mid):
+        assert (o.start, o.stop) == (m.start, m.stop)
+        for c in range(3):
+            np.testing.assert_array_equal(o.planes[c], wt.planes[c])

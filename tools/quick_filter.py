@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Times one stateless filter's batch path (16 device-resident 1080p frames per call) with the context's kernel timer.
 usage: quick_filter.py unsharp|chroma_smooth|lapsharp|colorspace_sdr|colorspace_matrix|grayscale|rotate|scale<W>x<H>|
-                      deblock_<preset>_<tune>[_10]|deband[_<range>][_10][_tile|_gather] [reps]
+                      deblock_<preset>_<tune>[_10]|deband[_<range>][_10][_tile|_gather]|bm3d[_<sigma>][_10] [reps]
 Prints one line per kernel: name, launches, average us.  For knob experiments with tools/dev_run.sh."""
 import ctypes as C, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -127,6 +127,16 @@ def main():
                 raise SystemExit("no such kernel for " + what)
             return f
         picture = "banded"
+    elif what.startswith("bm3d"):                      # bm3d[_<sigma>][_10]: bm3d (sigma 3), bm3d_6, bm3d_10, bm3d_6_10
+        parts = what.split("_")[1:]
+        depth_in = depth_out = 10 if parts and parts[-1] == "10" else 8
+        if depth_in == 10:
+            parts = parts[:-1]
+        mp = hip.Bm3dParams()
+        if hip.lib().hbhip_bm3d_params_from_settings(f"sigma={parts[0] if parts else 3}".encode(), depth_in, C.byref(mp)):
+            raise SystemExit("bm3d declines " + what)
+        make = lambda: hip._create("hbhip_bm3d_create", ctx, [C.c_void_p, C.POINTER(hip.Bm3dParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
+                                   ctx.h, C.byref(mp), W, H, depth_in, 1, 1)
     elif what in ("yadif", "yadif_bob", "bwdif"):
         return deint(ctx, what, reps)
     else:
