@@ -1,7 +1,7 @@
 """GPU: the deband drop-in (csrc/deband.hip, libhb/deband_hip.c) is bit-exact with the numpy model
 (tests/deband_model.py) - the defaults at 1080p, blur on and off, the thresholds' range, per-plane thresholds, 8/10/12
-bits on 4:2:0/4:2:2/4:4:4 with odd and tiny sizes, every range of the table test on both kernels, bursts with mixed
-pitches - and inside a device-resident job between VFR and NLMeans."""
+bits on 4:2:0/4:2:2/4:4:4 with odd and tiny sizes, every range of the table test on both kernels, the tile kernel at
+its largest halo and the cut-over past it, bursts with mixed pitches - and inside a device-resident job between VFR and NLMeans."""
 import ctypes as C
 
 import numpy as np
@@ -84,13 +84,13 @@ def _make(ctx, settings, w, h, depth=8):
                        ctx.h, C.byref(p), w, h, depth, 1, 1)
 
 
-def _bursts(settings, frames, sizes, kernel=0, pads=(0,)):
+def _bursts(settings, frames, sizes, kernel=0, pads=(0,), depth=8):
     """frames through one filter in device-resident bursts of the given sizes (one process_dev call each); input i's
-    rows are padded by pads[i % len(pads)] samples, so that pitches mix inside a burst"""
+    rows are padded by pads[i % len(pads)] samples, so that pitches mix inside a burst.  None: the filter refuses `kernel`"""
     import torch
     h, w = frames[0][0].shape
-    wide = frames[0][0].dtype == np.uint16
-    depth = 10 if wide else 8
+    wide = depth > 8
+    assert frames[0][0].dtype == (np.uint16 if wide else np.uint8)
     tdt = torch.int16 if wide else torch.uint8
     ctx = hip.Ctx(0)
     flt = _make(ctx, settings, w, h, depth)
@@ -155,8 +155,75 @@ def test_bursts_equal_frame_by_frame(built, st, depth):
     frames = synth.stream("banded", 320, 200, 20, depth=depth)
     want = model(frames, st, depth)
     for kernel in (0, 2):
-        check(_bursts(st, frames, [1, 3, 16], kernel=kernel, pads=(0, 0, 64, 5)), want, f"bursts 1/3/16 kernel {kernel}")
-    check(_bursts(st, frames, [1] * 20), want, "frame by frame")
+        check(_bursts(st, frames, [1, 3, 16], kernel=kernel, pads=(0, 0, 64, 5), depth=depth), want, f"bursts 1/3/16 kernel {kernel}")
+    check(_bursts(st, frames, [1] * 20, depth=depth), want, "frame by frame")
+
+
+# ---- the tile kernel's capacity -------------------------------------------------------------------------------------------
+# The tile kernel holds (32 + 2R) rows of (128 + 2RP) / 4 four-sample groups, RP = R rounded up to 4, and a thread fetches
+# at most 16 of them: (32 + 2R) * (128 + 2RP) / 4 <= 16 * 256 holds up to R = 28 (4 048 groups; R = 29: 4 320).
+# `range` settings whose 256 x 144 table has a largest |offset| R of 27, 28 and 29: a negative range is a constant
+# distance, a positive one a spread of distances and directions.
+TILE_W, TILE_H = 256, 144
+RANGES_FOR_R = {27: (-27, 29), 28: (-28, 30), 29: (-29, 31)}
+THR = "1thr=0.05:2thr=0.05:3thr=0.05"
+
+
+def _table_R(w, h, rng):
+    """the largest |offset| of the model's table as the drop-in keeps it: clamped to +-max(w, h)"""
+    lim = max(w, h)
+    return max(int(np.abs(np.clip(t, -lim, lim)).max()) for t in dm.offsets(w, h, rng))
+
+
+def _tile_groups(R):
+    return (32 + 2 * R) * ((128 + 2 * ((R + 3) & ~3)) // 4)
+
+
+@pytest.mark.parametrize("blur", [0, 1])
+@pytest.mark.parametrize("depth", [8, 10, 12])
+@pytest.mark.parametrize("R,rng", [(R, rng) for R in (27, 28) for rng in RANGES_FOR_R[R]])
+def test_tile_kernel_at_its_largest_halo(built, R, rng, depth, blur):
+    """R = 27 and R = 28, the last halo that fits (all 16 fetch slots of a thread live, 32 KB of LDS at 10 / 12 bits):
+    the tile kernel, the gather and the automatic choice equal the model, on aligned and on sample stores"""
+    assert _table_R(TILE_W, TILE_H, rng) == R and _tile_groups(R) <= 16 * 256
+    assert _tile_groups(28) > 15 * 256 and _tile_groups(29) > 16 * 256
+    frames = synth.stream("banded", TILE_W, TILE_H, 2, cfg=9, depth=depth)
+    st = f"range={rng}:{THR}:blur={blur}"
+    want = model(frames, st, depth)
+    assert any(not np.array_equal(want[0][c], frames[0][c]) for c in range(3))
+    for kernel in (1, 2, 0):
+        got = _bursts(st, frames, [2], kernel=kernel, pads=(0, 3), depth=depth)
+        assert got is not None, f"kernel {kernel} refused at R = {R}"
+        check(got, want, f"kernel {kernel} R {R} depth {depth} blur {blur}")
+
+
+@pytest.mark.parametrize("depth", [8, 10, 12])
+@pytest.mark.parametrize("rng", RANGES_FOR_R[29])
+def test_past_the_tile_kernels_capacity(built, rng, depth):
+    """R = 29: the tile kernel is refused, the automatic choice falls to the gather"""
+    assert _table_R(TILE_W, TILE_H, rng) == 29 and _tile_groups(29) > 16 * 256
+    frames = synth.stream("banded", TILE_W, TILE_H, 2, cfg=9, depth=depth)
+    st = f"range={rng}:{THR}"
+    want = model(frames, st, depth)
+    assert _bursts(st, frames, [2], kernel=1, depth=depth) is None
+    for kernel in (0, 2):
+        check(_bursts(st, frames, [2], kernel=kernel, pads=(0, 3), depth=depth), want, f"kernel {kernel} R 29 depth {depth}")
+
+
+@pytest.mark.parametrize("depth", [8, 10, 12])
+@pytest.mark.parametrize("rng", RANGES_FOR_R[28])
+def test_tile_kernel_on_a_frame_inside_its_halo(built, rng, depth):
+    """24 x 18 on 4:2:0 with R = 28's ranges: the table is clamped to +-24, at least the size of every plane both ways, so
+    the tile kernel's halo fetches are all clamped ones"""
+    w, h = 24, 18
+    R = _table_R(w, h, rng)
+    assert R >= h and (R + 3) & ~3 >= w and _tile_groups(R) <= 16 * 256
+    frames = [synth.picture("banded", w, h, t, cfg=21, depth=depth, chroma="2x2") for t in range(2)]
+    for blur in (0, 1):
+        st = f"range={rng}:{THR}:blur={blur}"
+        got = _bursts(st, frames, [2], kernel=1, pads=(0, 3), depth=depth)
+        assert got is not None
+        check(got, model(frames, st, depth), f"tile kernel, {w}x{h}, depth {depth}, blur {blur}")
 
 
 # ---- inside device-resident runs --------------------------------------------------------------------------------------

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import deblock_cases as dc
 import deblock_model as dm
 from handbrake_amd import hbrt, hip, synth
 
@@ -39,6 +40,34 @@ def test_model_forms_agree(b, strong, depth):
                 got = dm.deblock_plane(pl, b, strong, thr, depth, stats)
                 np.testing.assert_array_equal(got, want, err_msg=f"{kind} {w}x{h} b={b} strong={strong}")
     assert stats["fired"] > 0.15 * stats["edges"], stats
+
+
+def _gpu_groups():
+    groups = {}
+    for b, strong, depth, thresh, w, h in dc.model_cases():
+        groups.setdefault((b, strong, depth, thresh), []).append((w, h))
+    return sorted(groups.items())
+
+
+@pytest.mark.parametrize("key,sizes", _gpu_groups(), ids=lambda v: "-".join(map(str, v)) if isinstance(v[0], int) else f"{len(v)}sizes")
+def test_model_forms_agree_on_the_gpu_cases(key, sizes):
+    """the GPU tests compare against the block-row form, which rests on the same dependency argument as the kernels; this
+    holds it to the literal raster transcription at every (b, strength, depth, thresh) they run, on their own plane sizes
+    (tests/deblock_cases.py: large planes cut to three edges with the same remainder) - on blocky content, on near-flat
+    content where nearly every edge fires, and at thresh=100 on near-white and near-black content where taps clip"""
+    b, strong, depth, thresh = key
+    thr = dm.thresholds(thresh, depth)
+    stats = {}
+    for w, h in sizes:
+        planes = [synth.picture("blocky", w, h, 0, cfg=13 + b, depth=depth, chroma="1x1")[0], dc.near_flat(w, h, "1x1", depth, b)[0]]
+        if thresh == 100:
+            planes += [dc.near_white(w, h, "1x1", depth, b)[0], dc.near_white(w, h, "1x1", depth, b, mirror=True)[0]]
+        for k, pl in enumerate(planes):
+            want = dm.deblock_plane_raster(pl, b, strong, thr, depth)
+            got = dm.deblock_plane(pl, b, strong, thr, depth, stats)
+            np.testing.assert_array_equal(got, want, err_msg=f"content {k} {w}x{h} b={b} strong={strong} depth={depth}")
+    if any(dc.edges(w, b) + dc.edges(h, b) for w, h in sizes):
+        assert stats["fired"] > 0.15 * stats["edges"], stats
 
 
 @pytest.mark.parametrize("preset", sorted(dm.PRESETS))

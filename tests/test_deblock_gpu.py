@@ -1,17 +1,21 @@
 """GPU: the deblock drop-in (csrc/deblock.hip, libhb/deblock_hip.c) is bit-exact with the numpy model
-(tests/deblock_model.py) - every preset and tune, 8/10/12 bits, 4:2:0/4:2:2/4:4:4, the threshold boundaries, the forced
-repair path of the strong b = 4 / 5 kernel, bursts - and inside a device-resident job between VFR and NLMeans."""
+(tests/deblock_model.py) - every preset and tune, 8/10/12 bits, 4:2:0/4:2:2/4:4:4, the threshold boundaries, block sizes
+that put edges everywhere in the local kernel's tile and halo, the web kernel's chunked block row, edge counts and forced
+repair path, bursts with mixed pitches and past 16 frames, the clip - and inside a device-resident job between VFR and
+NLMeans.  The case lists are tests/deblock_cases.py."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 
+import deblock_cases as dc
 import deblock_model as dm
 from handbrake_amd import hbrt, hip, synth
 
 pytestmark = pytest.mark.gpu
 DROPIN = "hb_filter_deblock_hip"
-LCW = {"2x2": (1, 1), "2x1": (1, 0), "1x1": (0, 0)}
+LCW = dc.LCW
 
 
 def model(frames, settings, depth=8):
@@ -37,26 +41,7 @@ def test_presets_and_tunes_1080p(built, preset, tune):
     assert not np.array_equal(got[0].planes[0], frames[0][0])
 
 
-def _format_cases():
-    out = []
-    for w, h in [(638, 362), (1918, 1078), (64, 48)]:
-        for sub in ("2x2", "2x1", "1x1"):
-            for depth in (10, 12) if sub == "2x2" else (8, 10, 12):
-                lcw, lch = LCW[sub]
-                sizes = [(w, h), (-((-w) >> lcw), -((-h) >> lch))]
-                for st in ("strength=weak:thresh=50", "strength=strong:thresh=20", "strength=strong:thresh=50:blocksize=16",
-                           "strength=strong:thresh=75:blocksize=4", "strength=strong:thresh=20:blocksize=5"):
-                    if w > 1000 and "blocksize=16" not in st:
-                        continue                  # (the large size: one case per layout keeps the numpy model's time down)
-                    try:
-                        dm.resolve(st, depth, sizes)
-                    except dm.Declined:
-                        continue
-                    out.append((w, h, sub, depth, st))
-    return out
-
-
-@pytest.mark.parametrize("w,h,sub,depth,st", _format_cases())
+@pytest.mark.parametrize("w,h,sub,depth,st", dc.FORMAT_CASES)
 def test_depths_and_layouts(built, w, h, sub, depth, st):
     frames = [synth.picture("blocky", w, h, t, cfg=21, depth=depth, chroma=sub) for t in range(1 if w > 1000 else 2)]
     got = hbrt.run_stream(hip.filters(), [(DROPIN, st)], frames, pix_fmt=hbrt.PIX_FMT[(sub, depth)])
@@ -99,22 +84,27 @@ def test_threshold_boundaries(built, depth, strong):
     assert any(changed) and not all(changed)
 
 
-# ---- the C ABI directly: bursts and the repair path ------------------------------------------------------------------
-def _make(ctx, settings, w, h):
+# ---- the C ABI directly: block sizes, the web kernel's shapes, bursts, the clip ----------------------------------------------
+def _make(ctx, settings, w, h, depth=8, sub="2x2"):
     p = hip.DeblockParams()
     F = hip.filters()
+    lcw, lch = LCW[sub]
     F.hbhip_deblock_params_from_settings.argtypes = [C.c_char_p] + [C.c_int] * 5 + [C.POINTER(hip.DeblockParams)]
-    assert F.hbhip_deblock_params_from_settings(settings.encode(), 8, w, h, 1, 1, C.byref(p)) == 0
+    assert F.hbhip_deblock_params_from_settings(settings.encode(), depth, w, h, lcw, lch, C.byref(p)) == 0
     return hip._create("hbhip_deblock_create", ctx, [C.c_void_p, C.POINTER(hip.DeblockParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
-                       ctx.h, C.byref(p), w, h, 8, 1, 1)
+                       ctx.h, C.byref(p), w, h, depth, lcw, lch)
 
 
-def _bursts(settings, frames, sizes, warmup=None):
-    """frames through one filter in device-resident bursts of the given sizes (one process_dev call each)"""
+def _bursts(settings, frames, sizes, warmup=None, pads=(0,), depth=8, sub="2x2"):
+    """frames through one filter in device-resident bursts of the given sizes (one process_dev call each); input i's
+    rows are padded by pads[i % len(pads)] samples, so that pitches mix inside a burst"""
     import torch
     h, w = frames[0][0].shape
+    wide = depth > 8
+    assert frames[0][0].dtype == (np.uint16 if wide else np.uint8)
+    tdt = torch.int16 if wide else torch.uint8
     ctx = hip.Ctx(0)
-    flt = _make(ctx, settings, w, h)
+    flt = _make(ctx, settings, w, h, depth, sub)
     out = []
     try:
         if warmup is not None:
@@ -123,22 +113,66 @@ def _bursts(settings, frames, sizes, warmup=None):
         at = 0
         for n in sizes:
             part = frames[at:at + n]
+            dev_in, keep = [], []
+            for i, f in enumerate(part):
+                pad = pads[(at + i) % len(pads)]
+                planes = []
+                for p in f:
+                    full = torch.zeros((p.shape[0], p.shape[1] + pad), dtype=tdt, device="cuda")
+                    full[:, :p.shape[1]] = torch.from_numpy(np.array(p).view(np.int16) if wide else np.array(p)).cuda()
+                    keep.append(full)
+                    planes.append(full[:, :p.shape[1]])
+                dev_in.append(planes)
             at += n
-            dev_in = [[torch.from_numpy(np.ascontiguousarray(p)).cuda() for p in f] for f in part]
-            outs = [[torch.full(p.shape, 7, dtype=torch.uint8, device="cuda") for p in f] for f in part]
+            outs = [[torch.full(p.shape, 7, dtype=tdt, device="cuda") for p in f] for f in part]
             torch.cuda.synchronize()
             arr_in = (hip.DevFrame * n)(*[hip.dev_frame(f) for f in dev_in])
             arr_out = (hip.DevFrame * n)(*[hip.dev_frame(o) for o in outs])
             assert flt.process_dev(arr_in, 0, arr_out) == n
             ctx.sync()
-            out += [[p.cpu().numpy() for p in o] for o in outs]
+            conv = (lambda t: t.cpu().numpy().view(np.uint16)) if wide else (lambda t: t.cpu().numpy())
+            out += [[conv(p) for p in o] for o in outs]
             for f, d in zip(part, dev_in):                               # out of place: the inputs are untouched
                 for c in range(3):
-                    np.testing.assert_array_equal(d[c].cpu().numpy(), f[c])
+                    np.testing.assert_array_equal(conv(d[c]), f[c])
         return out
     finally:
         flt.close()
         ctx.close()
+
+
+@functools.lru_cache(maxsize=None)
+def _case(kind, w, h, sub, depth, st, n=2):
+    """(frames, the model's frames, the model's edge statistics) of a case, computed once; leave them unchanged"""
+    if kind == "blocky+flat":          # blocky content skips edges, the near-flat frame fires nearly all of them
+        frames = [synth.picture("blocky", w, h, 0, cfg=21, depth=depth, chroma=sub), dc.near_flat(w, h, sub, depth, w + h)]
+    elif kind == "flat":
+        frames = [dc.near_flat(w, h, sub, depth, w + h)]
+    elif kind == "stream":
+        frames = synth.stream("blocky", w, h, n, depth=depth)
+    elif kind == "white+black":
+        frames = [dc.near_white(w, h, sub, depth, depth), dc.near_white(w, h, sub, depth, depth + 1, mirror=True)]
+    stats = {}
+    want = [dm.deblock_frame(fr, st, depth, stats) for fr in frames]
+    for fr in list(frames) + want:
+        for p in fr:
+            p.setflags(write=False)
+    return frames, want, stats
+
+
+@pytest.mark.parametrize("w,h,sub,depth,st", dc.LOCAL_CASES)
+def test_block_sizes_on_the_local_kernel(built, w, h, sub, depth, st):
+    """block sizes that do not divide the 128 x 32 tile (edges at every position of tile and halo), the tightest
+    non-overlapping windows (strong b = 6 / 7), b past the tile's height and width (tiles without an edge), b past the
+    plane (a copy), last windows that end on the plane's last sample - at every depth and layout, through the C ABI"""
+    frames, want, stats = _case("blocky+flat", w, h, sub, depth, st)
+    check(_bursts(st, list(frames), [2], depth=depth, sub=sub), want, f"{w}x{h} {sub} {depth} {st}")
+    if dc.has_edge(w, h, sub, st):
+        assert 0 < stats["fired"] < stats["edges"], stats
+        assert any(not np.array_equal(wt[0], fr[0]) for wt, fr in zip(want, frames))
+    else:
+        assert stats["edges"] == 0
+        check(want, frames, "no edge: the model's output is its input")
 
 
 @pytest.mark.parametrize("st", ["strength=strong:thresh=20", "strength=weak:thresh=20",
@@ -148,6 +182,36 @@ def test_bursts_equal_frame_by_frame(built, st):
     want = model(frames, st)
     check(_bursts(st, frames, [1, 3, 16]), want, "bursts 1/3/16")
     check(_bursts(st, frames, [1] * 20), want, "frame by frame")
+
+
+@pytest.mark.parametrize("w,h,sub,depth,st", dc.PITCH_CASES)
+def test_mixed_pitches_in_a_burst(built, w, h, sub, depth, st):
+    """process_many groups the frames of a burst by equal pitches: bursts whose input pitches differ (and the uint16
+    kernels through the C ABI) equal the model and the frame-by-frame result"""
+    frames, want, _ = _case("stream", w, h, sub, depth, st, 5)
+    single = _bursts(st, list(frames), [1] * 5, depth=depth)
+    check(single, want, "frame by frame")
+    for pads in ((0, 0, 64, 5, 0), (0, 16)):
+        got = _bursts(st, list(frames), [5], pads=pads, depth=depth)
+        check(got, want, f"pads {pads}")
+        check(got, single, f"pads {pads} against frame by frame")
+
+
+@pytest.mark.parametrize("w,h,sub,depth,st", dc.CUT_CASES)
+def test_bursts_past_16_frames(built, w, h, sub, depth, st):
+    """a launch takes 16 frames: a burst of 20 at one pitch is cut at 16, one whose pitch changes at frame 9 at 9"""
+    frames, want, _ = _case("stream", w, h, sub, depth, st, 20)
+    single = _bursts(st, list(frames), [1] * 20)
+    check(single, want, "frame by frame")
+    for pads in ((0,), (0,) * 9 + (64,) * 11):
+        got = _bursts(st, list(frames), [20], pads=pads)
+        check(got, want, f"burst of 20, pads {set(pads)}")
+        check(got, single, "against frame by frame")
+
+
+def _repair_frames(w, h, sub, depth, seed):
+    frames = [dc.near_flat(w, h, sub, depth, seed + t, t) for t in range(3)]
+    return frames + [synth.picture("blocky", w, h, t, cfg=13, depth=depth, chroma=sub) for t in range(2)]
 
 
 @pytest.mark.parametrize("b", [4, 5])
@@ -166,6 +230,88 @@ def test_repair_path_forced(built, b):
     want = model(frames, st)
     for warmup in (0, 1, 64):
         check(_bursts(st, frames, [len(frames)], warmup=warmup), want, f"warmup {warmup}")
+
+
+@pytest.mark.parametrize("depth,sub", [(10, "2x2"), (8, "1x1")])
+@pytest.mark.parametrize("b", [4, 5])
+def test_repair_path_forced_deep_and_444(built, b, depth, sub):
+    """the same through the uint16 kernel, and with chroma planes as wide as luma"""
+    w, h = 160, 80
+    frames = _repair_frames(w, h, sub, depth, b)
+    st = dc.settings(True, b, 50)
+    want = model(frames, st, depth)
+    for warmup in (0, 1, 64):
+        check(_bursts(st, frames, [len(frames)], warmup=warmup, depth=depth, sub=sub), want, f"warmup {warmup}")
+
+
+@pytest.mark.parametrize("depth", dc.WEB_DEPTHS)
+@pytest.mark.parametrize("w,h,sub,b", dc.WEB_WIDE)
+def test_web_block_row_in_chunks(built, w, h, sub, b, depth):
+    """a luma row so wide that LDS holds fewer rows than a block row has: the walk of a block row takes several chunks"""
+    # DeblockFilter::web_rows: 48 KiB / (2 w + 8 ceil(floor((w - 1) / b) / 8)) rows of the luma width fit, at most b
+    nseg = -(-((w - 1) // b) // 8)
+    rows_lds = min(b, 48 * 1024 // (2 * w + 8 * nseg))
+    assert 1 <= rows_lds < b and rows_lds == dc.web_rows(w, b)
+    st = dc.settings(True, b, dc.WEB_THRESH)
+    frames, want, stats = _case("flat", w, h, sub, depth, st)
+    assert stats["fired"] > 0.9 * stats["edges"], stats                  # the chains do not forget
+    for warmup in (0, None):
+        check(_bursts(st, list(frames), [1], warmup=warmup, depth=depth, sub=sub), want, f"{w}x{h} warmup {warmup}")
+
+
+def _web_shape(w, h, sub, b):
+    st = dc.settings(True, b, dc.WEB_THRESH)
+    for depth in dc.WEB_DEPTHS:
+        frames, want, stats = _case("blocky+flat", w, h, sub, depth, st)
+        if dc.has_edge(w, h, sub, st):
+            assert stats["fired"] > 0, stats
+        for warmup in (0, None):
+            check(_bursts(st, list(frames), [2], warmup=warmup, depth=depth, sub=sub), want, f"{w}x{h} {sub} {depth} warmup {warmup}")
+
+
+@pytest.mark.parametrize("tall", [False, True], ids=["h<=b", "h=b+3"])
+@pytest.mark.parametrize("ne", [0, 1, 7, 8, 9, 16])
+@pytest.mark.parametrize("b", [4, 5])
+def test_web_edge_counts(built, b, ne, tall):
+    """rows of no edge (only horizontal edges exist), one, fewer than one 8-edge segment, exactly one, one more, exactly
+    two; planes of one block row (only vertical edges exist) and of two - on all three planes (4:4:4)"""
+    w, h = dc.WEB_WIDTHS[b][ne], dc.web_heights(b)[tall]
+    assert (w - 1) // b == ne and (h > b) == tall
+    _web_shape(w, h, "1x1", b)
+
+
+@pytest.mark.parametrize("w,h,b", sorted(dc.WEB_SPLIT))
+def test_web_luma_and_chroma_differ_in_segments(built, w, h, b):
+    """4:2:0: one launch whose luma rows have more segments than its chroma rows (the LDS layout is per plane)"""
+    ny, nc = (w - 1) // b, (-(-w // 2) - 1) // b
+    assert -(-ny // 8) > -(-nc // 8) >= 1
+    _web_shape(w, h, "2x2", b)
+
+
+def _unclipped_first_block_row(plane, b, strong, thr):
+    """the taps, before the clip, of every fired vertical edge of block row 0 - from the input and the model's arithmetic
+    (block row 0 has no horizontal edge before it and at b = 8 no two windows overlap, so its edges see the input)"""
+    L = 3 if strong else 2
+    cols = np.arange(b, plane.shape[1], b)[:, None] + np.arange(-L, L)[None, :]
+    win = plane.astype(np.int64)[:b][:, cols]
+    _, fire = dm.edge(win, strong, thr, 1 << 20)
+    d = win[..., L] - win[..., L - 1]
+    div = dm.STRONG_DIV if strong else dm.WEAK_DIV
+    taps = np.stack([win[..., k] + (1 if k < L else -1) * dm._div(d, div[k]) for k in range(2 * L)], axis=-1)
+    return taps[fire]
+
+
+@pytest.mark.parametrize("w,h,sub,depth,st", dc.CLIP_CASES)
+def test_clip_at_both_ends(built, w, h, sub, depth, st):
+    """thresh=100 on content next to the top of the range and on its mirror next to 0: fired edges push taps past
+    both ends, and the clipped result is the model's"""
+    frames, want, _ = _case("white+black", w, h, sub, depth, st)
+    p = dm.resolve(st, depth)
+    maxv = (1 << depth) - 1
+    white = _unclipped_first_block_row(frames[0][0], p["block"], p["strong"], p["thr"])
+    black = _unclipped_first_block_row(frames[1][0], p["block"], p["strong"], p["thr"])
+    assert white.size and (white > maxv).any() and black.size and (black < 0).any()
+    check(_bursts(st, list(frames), [2], depth=depth, sub=sub), want, st)
 
 
 # ---- inside device-resident runs --------------------------------------------------------------------------------------
