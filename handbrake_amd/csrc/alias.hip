@@ -1422,50 +1422,28 @@ __global__ __launch_bounds__(256) void pad_kernel(PadArgs a, int bps)
     else for (int k = 0; ob + k < a.dw[c]; k++) drow[ob + k] = (uint8_t)(v >> (8 * k));
 }
 
-class PadFilter : public SimpleFilter
+class PadFilter : public BurstFilter
 {
 public:
-    PadFilter(hbhip_ctx *c, const hbhip_pad_params &p) : SimpleFilter(c), par(p) {}
+    PadFilter(hbhip_ctx *c, const hbhip_pad_params &p) : BurstFilter(c), par(p) {}
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
         const int bps = in_geo.bps;
-        int at = 0;
-        while (at < n)
-        {
-            int nf = 1;
-            auto same = [&](int i) {
-                for (int c = 0; c < 3; c++)
-                    if (ins[i]->pitch[c] != ins[at]->pitch[c] || outs[i]->pitch[c] != outs[at]->pitch[c]) return false;
-                return true;
-            };
-            while (at + nf < n && nf < PAD_FRAMES && same(at + nf)) nf++;
-            PadArgs a;
-            memset(&a, 0, sizeof(a));
-            bool aligned = true;
+        return hbhip_for_each_burst<PAD_FRAMES, PadArgs>(ctx, ins, outs, n, [&](PadArgs &a, int nf, int at, uintptr_t bits) {
+            if ((bits & 3) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
             for (int c = 0; c < 3; c++)
             {
                 DevPicture *in = ins[at], *out = outs[at];
-                a.spitch[c] = in->pitch[c]; a.dpitch[c] = out->pitch[c];
                 a.sw[c] = in->width[c] * bps; a.sh[c] = in->height[c]; a.dw[c] = out->width[c] * bps; a.dh[c] = out->height[c];
                 a.x[c] = (c ? par.x >> in_geo.log2_cw : par.x) * bps;
                 a.y[c] = c ? par.y >> in_geo.log2_ch : par.y;
                 a.fill[c] = par.fill[c];
-                aligned = aligned && ((a.spitch[c] | a.dpitch[c]) & 3) == 0;
-                for (int f = 0; f < nf; f++)
-                {
-                    a.src[f][c] = ins[at + f]->plane[c]; a.dst[f][c] = outs[at + f]->plane[c];
-                    aligned = aligned && (((uintptr_t)a.src[f][c] | (uintptr_t)a.dst[f][c]) & 3) == 0;
-                }
             }
-            if (!aligned) return HBHIP_ERR_ARG;                              // planes and pitches of this library are 64-byte aligned
             const dim3 grid(hbhip_grid_x(((a.dw[0] + 3) / 4 + 63) / 64), (a.dh[0] + 3) / 4, 3 * nf);
             HBHIP_LAUNCH(ctx, "pad", pad_kernel, grid, dim3(64, 4), 0, a, bps);
-            HBHIP_CHECK(ctx, hipGetLastError());
-            at += nf;
-        }
-        return HBHIP_OK;
+            return HBHIP_OK;
+        });
     }
-    int process(DevPicture *in, DevPicture *out) override { return process_many(&in, &out, 1); }
     hbhip_pad_params par;
 };
 
@@ -1550,49 +1528,24 @@ __global__ __launch_bounds__(256) void format_kernel(FormatArgs a)
         for (int i = 0; x0 + i < a.w[c]; i++) d[x0 + i] = (DST)o4[i];
 }
 
-class FormatFilter : public SimpleFilter
+class FormatFilter : public BurstFilter
 {
 public:
-    FormatFilter(hbhip_ctx *c, int full) : SimpleFilter(c), full_range(full) {}
+    FormatFilter(hbhip_ctx *c, int full) : BurstFilter(c), full_range(full) {}
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
-        int at = 0;
-        while (at < n)
-        {
-            int nf = 1;
-            auto same = [&](int i) {
-                for (int c = 0; c < 3; c++)
-                    if (ins[i]->pitch[c] != ins[at]->pitch[c] || outs[i]->pitch[c] != outs[at]->pitch[c]) return false;
-                return true;
-            };
-            while (at + nf < n && nf < FMT_FRAMES && same(at + nf)) nf++;
-            FormatArgs a;
-            memset(&a, 0, sizeof(a));
-            bool aligned = true;
-            for (int c = 0; c < 3; c++)
-            {
-                a.spitch[c] = ins[at]->pitch[c]; a.dpitch[c] = outs[at]->pitch[c];
-                a.w[c] = in_geo.pw[c]; a.h[c] = in_geo.ph[c];
-                aligned = aligned && ((a.spitch[c] | a.dpitch[c]) & 7) == 0;
-                for (int f = 0; f < nf; f++)
-                {
-                    a.src[f][c] = ins[at + f]->plane[c]; a.dst[f][c] = outs[at + f]->plane[c];
-                    aligned = aligned && (((uintptr_t)a.src[f][c] | (uintptr_t)a.dst[f][c]) & 7) == 0;
-                }
-            }
-            if (!aligned) return HBHIP_ERR_ARG;                              // planes and pitches of this library are 64-byte aligned
+        return hbhip_for_each_burst<FMT_FRAMES, FormatArgs>(ctx, ins, outs, n, [&](FormatArgs &a, int nf, int, uintptr_t bits) {
+            if ((bits & 7) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
+            for (int c = 0; c < 3; c++) { a.w[c] = in_geo.pw[c]; a.h[c] = in_geo.ph[c]; }
             a.sdepth = in_geo.depth; a.ddepth = out_geo.depth; a.full_range = full_range;
             const dim3 grid(hbhip_grid_x((a.w[0] + 255) / 256), (a.h[0] + 3) / 4, 3 * nf);
             if (in_geo.bps == 1 && out_geo.bps == 1)      HBHIP_LAUNCH(ctx, "format", (format_kernel<uint8_t, uint8_t>), grid, dim3(64, 4), 0, a);
             else if (in_geo.bps == 1)                     HBHIP_LAUNCH(ctx, "format", (format_kernel<uint8_t, uint16_t>), grid, dim3(64, 4), 0, a);
             else if (out_geo.bps == 1)                    HBHIP_LAUNCH(ctx, "format", (format_kernel<uint16_t, uint8_t>), grid, dim3(64, 4), 0, a);
             else                                          HBHIP_LAUNCH(ctx, "format", (format_kernel<uint16_t, uint16_t>), grid, dim3(64, 4), 0, a);
-            HBHIP_CHECK(ctx, hipGetLastError());
-            at += nf;
-        }
-        return HBHIP_OK;
+            return HBHIP_OK;
+        });
     }
-    int process(DevPicture *in, DevPicture *out) override { return process_many(&in, &out, 1); }
     int full_range;
 };
 
@@ -1606,15 +1559,11 @@ extern "C" int hbhip_format_create(hbhip_ctx *ctx, int width, int height, int sr
     for (int d : {src_depth, dst_depth})
         if (d != 8 && d != 10 && d != 12) return HBHIP_ERR_UNSUPPORTED;
     if (width < 1 || height < 1) return HBHIP_ERR_ARG;
-    (void)hipSetDevice(ctx->device);
-    FormatFilter *f = new (std::nothrow) FormatFilter(ctx, full_range);
-    if (!f) return HBHIP_ERR_NOMEM;
     PicGeometry gi, go;
     gi.set(width, height, src_depth, log2_chroma_w, log2_chroma_h);
     go.set(width, height, dst_depth, log2_chroma_w, log2_chroma_h);
-    f->configure(gi, go);
-    *out = f;
-    return HBHIP_OK;
+    *out = hbhip_make_filter<FormatFilter>(ctx, gi, go, full_range);
+    return *out ? HBHIP_OK : HBHIP_ERR_NOMEM;
 }
 
 extern "C" int hbhip_pad_create(hbhip_ctx *ctx, const hbhip_pad_params *p, int width, int height, int depth,
@@ -1627,15 +1576,11 @@ extern "C" int hbhip_pad_create(hbhip_ctx *ctx, const hbhip_pad_params *p, int w
         p->x + width > p->width || p->y + height > p->height) return HBHIP_ERR_ARG;
     // vf_pad rounds the offsets down to the chroma subsampling; the caller has done so
     if ((p->x & ((1 << log2_chroma_w) - 1)) || (p->y & ((1 << log2_chroma_h) - 1))) return HBHIP_ERR_ARG;
-    (void)hipSetDevice(ctx->device);
-    PadFilter *f = new (std::nothrow) PadFilter(ctx, *p);
-    if (!f) return HBHIP_ERR_NOMEM;
     PicGeometry gi, go;
     gi.set(width, height, depth, log2_chroma_w, log2_chroma_h);
     go.set(p->width, p->height, depth, log2_chroma_w, log2_chroma_h);
-    f->configure(gi, go);
-    *out = f;
-    return HBHIP_OK;
+    *out = hbhip_make_filter<PadFilter>(ctx, gi, go, *p);
+    return *out ? HBHIP_OK : HBHIP_ERR_NOMEM;
 }
 
 extern "C" int hbhip_rotate_create(hbhip_ctx *ctx, int angle, int hflip, int width, int height, int depth,

@@ -251,38 +251,19 @@ __global__ __launch_bounds__(BM_THREADS) void bm3d_kernel(Bm3dArgs a)
     }
 }
 
-class Bm3dFilter : public SimpleFilter
+class Bm3dFilter : public BurstFilter
 {
 public:
-    Bm3dFilter(hbhip_ctx *c, const hbhip_bm3d_params &p) : SimpleFilter(c), par(p) {}
+    Bm3dFilter(hbhip_ctx *c, const hbhip_bm3d_params &p) : BurstFilter(c), par(p) {}
     ~Bm3dFilter() override { if (dct) (void)hipFree(dct); }
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
-        int at = 0;
-        while (at < n)
-        {
-            int nf = 1;
-            auto same = [&](int i) {
-                for (int c = 0; c < 3; c++)
-                    if (ins[i]->pitch[c] != ins[at]->pitch[c] || outs[i]->pitch[c] != outs[at]->pitch[c]) return false;
-                return true;
-            };
-            while (at + nf < n && nf < BM_FRAMES && same(at + nf)) nf++;
-            Bm3dArgs a;
-            memset(&a, 0, sizeof(a));
-            uintptr_t bits = 0;
+        return hbhip_for_each_burst<BM_FRAMES, Bm3dArgs>(ctx, ins, outs, n, [&](Bm3dArgs &a, int nf, int, uintptr_t bits) {
             for (int c = 0; c < 3; c++)
             {
-                a.spitch[c] = ins[at]->pitch[c]; a.dpitch[c] = outs[at]->pitch[c];
                 a.w[c] = in_geo.pw[c]; a.h[c] = in_geo.ph[c];
                 a.thr[c] = par.thr[c];
                 if (((a.spitch[c] | a.dpitch[c]) & (in_geo.bps - 1)) != 0) return HBHIP_ERR_ARG;
-                bits |= (uintptr_t)(a.spitch[c] | a.dpitch[c]);
-                for (int f = 0; f < nf; f++)
-                {
-                    a.src[f][c] = ins[at + f]->plane[c]; a.dst[f][c] = outs[at + f]->plane[c];
-                    bits |= (uintptr_t)a.src[f][c] | (uintptr_t)a.dst[f][c];
-                }
             }
             a.dct = dct;
             a.maxv = (1 << in_geo.depth) - 1;
@@ -290,12 +271,9 @@ public:
             const dim3 grid(hbhip_grid_x((a.w[0] + BM_TW - 1) / BM_TW), (a.h[0] + BM_TH - 1) / BM_TH, 3 * nf);
             if (in_geo.bps == 2) HBHIP_LAUNCH(ctx, "bm3d", (bm3d_kernel<uint16_t>), grid, dim3(BM_THREADS), 0, a);
             else                 HBHIP_LAUNCH(ctx, "bm3d", (bm3d_kernel<uint8_t>), grid, dim3(BM_THREADS), 0, a);
-            HBHIP_CHECK(ctx, hipGetLastError());
-            at += nf;
-        }
-        return HBHIP_OK;
+            return HBHIP_OK;
+        });
     }
-    int process(DevPicture *in, DevPicture *out) override { return process_many(&in, &out, 1); }
     hbhip_bm3d_params par;
     float *dct = nullptr;
 };
@@ -345,8 +323,7 @@ extern "C" int hbhip_bm3d_create(hbhip_ctx *ctx, const hbhip_bm3d_params *p, int
     if (!ctx || !p || !out) return HBHIP_ERR_ARG;
     *out = nullptr;
     if (depth != 8 && depth != 10 && depth != 12) return HBHIP_ERR_UNSUPPORTED;
-    if (!((log2_chroma_w == 1 && log2_chroma_h == 1) || (log2_chroma_w == 1 && log2_chroma_h == 0) ||
-          (log2_chroma_w == 0 && log2_chroma_h == 0))) return HBHIP_ERR_UNSUPPORTED;
+    if (!hbhip_yuv_layout_ok(log2_chroma_w, log2_chroma_h)) return HBHIP_ERR_UNSUPPORTED;
     // the kernel is the filter at FFmpeg's defaults: anything else is another filter
     if (p->block != BM_BLOCK || p->bstep != BM_BSTEP || p->group != BM_GROUP || p->estim != BM_ESTIM || p->planes != BM_PLANES)
         return HBHIP_ERR_UNSUPPORTED;
@@ -356,10 +333,8 @@ extern "C" int hbhip_bm3d_create(hbhip_ctx *ctx, const hbhip_bm3d_params *p, int
     g.set(width, height, depth, log2_chroma_w, log2_chroma_h);
     for (int c = 0; c < 3; c++)
         if (g.pw[c] < BM_BLOCK || g.ph[c] < BM_BLOCK) return HBHIP_ERR_UNSUPPORTED;      // the clamped origin would be negative
-    (void)hipSetDevice(ctx->device);
-    Bm3dFilter *f = new (std::nothrow) Bm3dFilter(ctx, *p);
+    Bm3dFilter *f = hbhip_make_filter<Bm3dFilter>(ctx, g, g, *p);
     if (!f) return HBHIP_ERR_NOMEM;
-    f->configure(g, g);
     hipError_t e = hipMalloc(&f->dct, sizeof(p->dct));
     if (e == hipSuccess) e = hipMemcpy(f->dct, p->dct, sizeof(p->dct), hipMemcpyHostToDevice);
     if (e != hipSuccess)

@@ -617,10 +617,10 @@ float hable_host(float in)
     return (in * (in * a + b * c) + d * e) / (in * (in * a + b) + d * f) - e / f;
 }
 
-class ColorspaceFilter : public SimpleFilter
+class ColorspaceFilter : public BurstFilter
 {
 public:
-    ColorspaceFilter(hbhip_ctx *c, const hbhip_colorspace_params &p) : SimpleFilter(c), par(p) {}
+    ColorspaceFilter(hbhip_ctx *c, const hbhip_colorspace_params &p) : BurstFilter(c), par(p) {}
     int setup(int depth)
     {
         memset(&plan, 0, sizeof(plan));
@@ -741,33 +741,12 @@ public:
     // the frames of a batch (a chain batch, a device-resident batch) in one launch where their pitches agree
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
-        int at = 0;
-        while (at < n)
-        {
-            int nf = 1;
-            auto same = [&](int i) {
-                for (int c = 0; c < 3; c++)
-                    if (ins[i]->pitch[c] != ins[at]->pitch[c] || outs[i]->pitch[c] != outs[at]->pitch[c]) return false;
-                return true;
-            };
-            while (at + nf < n && nf < CS_FRAMES && same(at + nf)) nf++;
-            CsBatch B;
-            memset(&B, 0, sizeof(B));
-            for (int f = 0; f < nf; f++)
-                for (int c = 0; c < 3; c++) { B.src[f][c] = ins[at + f]->plane[c]; B.dst[f][c] = outs[at + f]->plane[c]; }
-            for (int c = 0; c < 3; c++) { B.spitch[c] = ins[at]->pitch[c]; B.dpitch[c] = outs[at]->pitch[c]; }
+        return hbhip_for_each_burst<CS_FRAMES, CsBatch>(ctx, ins, outs, n, [&](CsBatch &B, int nf, int at, uintptr_t) {
             B.w = ins[at]->width[0]; B.h = ins[at]->height[0]; B.cw = ins[at]->width[1]; B.ch = ins[at]->height[1];
             if (in_geo.bps == 1) launch<uint8_t>(B, nf);
             else                 launch<uint16_t>(B, nf);
-            HBHIP_CHECK(ctx, hipGetLastError());
-            at += nf;
-        }
-        return HBHIP_OK;
-    }
-    int process(DevPicture *in, DevPicture *out) override
-    {
-        DevPicture *i1[1] = { in }, *o1[1] = { out };
-        return process_many(i1, o1, 1);
+            return HBHIP_OK;
+        });
     }
     hbhip_colorspace_params par;
     CsPlan plan;
@@ -783,12 +762,10 @@ extern "C" int hbhip_colorspace_create(hbhip_ctx *ctx, const hbhip_colorspace_pa
     if (depth != 8 && depth != 10 && depth != 12) return HBHIP_ERR_UNSUPPORTED;
     if (log2_chroma_w < 0 || log2_chroma_w > 1 || log2_chroma_h < 0 || log2_chroma_h > 1) return HBHIP_ERR_UNSUPPORTED;
     if (width < 2 || height < 2 || !(p->npl > 0)) return HBHIP_ERR_ARG;
-    (void)hipSetDevice(ctx->device);
-    ColorspaceFilter *f = new (std::nothrow) ColorspaceFilter(ctx, *p);
-    if (!f) return HBHIP_ERR_NOMEM;
     PicGeometry g;
     g.set(width, height, depth, log2_chroma_w, log2_chroma_h);
-    f->configure(g, g);
+    ColorspaceFilter *f = hbhip_make_filter<ColorspaceFilter>(ctx, g, g, *p);
+    if (!f) return HBHIP_ERR_NOMEM;
     int rc = f->setup(depth);
     if (rc != HBHIP_OK) { delete f; return rc; }
     *out = f;

@@ -244,10 +244,10 @@ __global__ __launch_bounds__(DB_THREADS) void deband_gather_kernel(DebandArgs a)
     }
 }
 
-class DebandFilter : public SimpleFilter
+class DebandFilter : public BurstFilter
 {
 public:
-    DebandFilter(hbhip_ctx *c, const hbhip_deband_params &p) : SimpleFilter(c), par(p) {}
+    DebandFilter(hbhip_ctx *c, const hbhip_deband_params &p) : BurstFilter(c), par(p) {}
     ~DebandFilter() override { if (table) (void)hipFree(table); }
     // the tile kernel's LDS bytes (0: its halo does not fit)
     int tile_bytes() const
@@ -275,31 +275,12 @@ public:
     }
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
-        int at = 0;
-        while (at < n)
-        {
-            int nf = 1;
-            auto same = [&](int i) {
-                for (int c = 0; c < 3; c++)
-                    if (ins[i]->pitch[c] != ins[at]->pitch[c] || outs[i]->pitch[c] != outs[at]->pitch[c]) return false;
-                return true;
-            };
-            while (at + nf < n && nf < DB_FRAMES && same(at + nf)) nf++;
-            DebandArgs a;
-            memset(&a, 0, sizeof(a));
-            uintptr_t bits = 0;
+        return hbhip_for_each_burst<DB_FRAMES, DebandArgs>(ctx, ins, outs, n, [&](DebandArgs &a, int nf, int, uintptr_t bits) {
             for (int c = 0; c < 3; c++)
             {
-                a.spitch[c] = ins[at]->pitch[c]; a.dpitch[c] = outs[at]->pitch[c];
                 a.w[c] = in_geo.pw[c]; a.h[c] = in_geo.ph[c];
                 a.thr[c] = par.thr[c];
                 if (((a.spitch[c] | a.dpitch[c]) & (in_geo.bps - 1)) != 0) return HBHIP_ERR_ARG;
-                bits |= (uintptr_t)(a.spitch[c] | a.dpitch[c]);
-                for (int f = 0; f < nf; f++)
-                {
-                    a.src[f][c] = ins[at + f]->plane[c]; a.dst[f][c] = outs[at + f]->plane[c];
-                    bits |= (uintptr_t)a.src[f][c] | (uintptr_t)a.dst[f][c];
-                }
             }
             a.nf = nf;
             a.aligned = (bits & 7) == 0;
@@ -309,12 +290,9 @@ public:
             const dim3 grid(hbhip_grid_x((a.w[0] + DB_TW - 1) / DB_TW), (a.h[0] + DB_TH - 1) / DB_TH, 3);
             if (wide_table) { if (par.blur) launch<true, true>(a, grid);  else launch<true, false>(a, grid); }
             else            { if (par.blur) launch<false, true>(a, grid); else launch<false, false>(a, grid); }
-            HBHIP_CHECK(ctx, hipGetLastError());
-            at += nf;
-        }
-        return HBHIP_OK;
+            return HBHIP_OK;
+        });
     }
-    int process(DevPicture *in, DevPicture *out) override { return process_many(&in, &out, 1); }
     hbhip_deband_params par;
     void *table = nullptr;
     bool wide_table = false;
@@ -350,8 +328,7 @@ extern "C" int hbhip_deband_create(hbhip_ctx *ctx, const hbhip_deband_params *p,
     if (!ctx || !p || !out) return HBHIP_ERR_ARG;
     *out = nullptr;
     if (depth != 8 && depth != 10 && depth != 12) return HBHIP_ERR_UNSUPPORTED;
-    if (!((log2_chroma_w == 1 && log2_chroma_h == 1) || (log2_chroma_w == 1 && log2_chroma_h == 0) ||
-          (log2_chroma_w == 0 && log2_chroma_h == 0))) return HBHIP_ERR_UNSUPPORTED;
+    if (!hbhip_yuv_layout_ok(log2_chroma_w, log2_chroma_h)) return HBHIP_ERR_UNSUPPORTED;
     if (width < 1 || height < 1 || (p->blur != 0 && p->blur != 1)) return HBHIP_ERR_ARG;
     if (p->range > (1 << 30) || p->range < -(1 << 30)) return HBHIP_ERR_ARG;
     // the table, clamped to +-max(W, H): any |offset| >= a plane's size clips to the same edge in either sign
@@ -375,12 +352,10 @@ extern "C" int hbhip_deband_create(hbhip_ctx *ctx, const hbhip_deband_params *p,
     for (size_t i = 0; i < n; i++)
         if (wide) { t16[2 * i] = (int16_t)xp[i]; t16[2 * i + 1] = (int16_t)yp[i]; }
         else      { t8[2 * i] = (int8_t)xp[i];   t8[2 * i + 1] = (int8_t)yp[i]; }
-    (void)hipSetDevice(ctx->device);
-    DebandFilter *f = new (std::nothrow) DebandFilter(ctx, *p);
-    if (!f) return HBHIP_ERR_NOMEM;
     PicGeometry g;
     g.set(width, height, depth, log2_chroma_w, log2_chroma_h);
-    f->configure(g, g);
+    DebandFilter *f = hbhip_make_filter<DebandFilter>(ctx, g, g, *p);
+    if (!f) return HBHIP_ERR_NOMEM;
     f->wide_table = wide;
     f->R = R;
     f->RP = (R + 3) & ~3;

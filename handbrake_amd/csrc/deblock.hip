@@ -278,10 +278,10 @@ __global__ __launch_bounds__(DB_WEB_THREADS) void deblock_web_kernel(DeblockArgs
 constexpr int DB_WEB_SEG = 8;           // edges per segment
 constexpr int DB_WEB_LDS = 48 * 1024;   // bytes of LDS the web kernel takes at most
 
-class DeblockFilter : public SimpleFilter
+class DeblockFilter : public BurstFilter
 {
 public:
-    DeblockFilter(hbhip_ctx *c, const hbhip_deblock_params &p) : SimpleFilter(c), par(p) {}
+    DeblockFilter(hbhip_ctx *c, const hbhip_deblock_params &p) : BurstFilter(c), par(p) {}
     bool web() const { return par.strong && par.block < 6; }
     // LDS of the web kernel for planes up to `w` samples wide: rows of the block row it holds at once (0: none fits)
     static int web_rows(int w, int b, int *bytes)
@@ -294,24 +294,11 @@ public:
     }
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
-        int at = 0;
-        while (at < n)
-        {
-            int nf = 1;
-            auto same = [&](int i) {
-                for (int c = 0; c < 3; c++)
-                    if (ins[i]->pitch[c] != ins[at]->pitch[c] || outs[i]->pitch[c] != outs[at]->pitch[c]) return false;
-                return true;
-            };
-            while (at + nf < n && nf < DB_FRAMES && same(at + nf)) nf++;
-            DeblockArgs a;
-            memset(&a, 0, sizeof(a));
+        return hbhip_for_each_burst<DB_FRAMES, DeblockArgs>(ctx, ins, outs, n, [&](DeblockArgs &a, int nf, int, uintptr_t) {
             for (int c = 0; c < 3; c++)
             {
-                a.spitch[c] = ins[at]->pitch[c]; a.dpitch[c] = outs[at]->pitch[c];
                 a.w[c] = in_geo.pw[c]; a.h[c] = in_geo.ph[c];
                 if (((a.spitch[c] | a.dpitch[c]) & (in_geo.bps - 1)) != 0) return HBHIP_ERR_ARG;
-                for (int f = 0; f < nf; f++) { a.src[f][c] = ins[at + f]->plane[c]; a.dst[f][c] = outs[at + f]->plane[c]; }
             }
             a.block = par.block;
             a.thr = { par.ath, par.bth, par.gth, par.dth, (1 << in_geo.depth) - 1 };
@@ -338,12 +325,9 @@ public:
                     else      HBHIP_LAUNCH(ctx, "deblock", (deblock_local_kernel<uint8_t, false>), grid, dim3(256), 0, a);
                 }
             }
-            HBHIP_CHECK(ctx, hipGetLastError());
-            at += nf;
-        }
-        return HBHIP_OK;
+            return HBHIP_OK;
+        });
     }
-    int process(DevPicture *in, DevPicture *out) override { return process_many(&in, &out, 1); }
     hbhip_deblock_params par;
     int warmup = 4;                     // the web kernel's warm-up edges (hbhip_deblock_set_warmup)
 };
@@ -375,13 +359,10 @@ extern "C" int hbhip_deblock_create(hbhip_ctx *ctx, const hbhip_deblock_params *
         int bytes = 0;
         if (DeblockFilter::web_rows(width, p->block, &bytes) < 1) return HBHIP_ERR_UNSUPPORTED;
     }
-    (void)hipSetDevice(ctx->device);
-    DeblockFilter *f = new (std::nothrow) DeblockFilter(ctx, *p);
-    if (!f) return HBHIP_ERR_NOMEM;
-    f->par.strong = p->strong != 0;
-    f->configure(g, g);
-    *out = f;
-    return HBHIP_OK;
+    hbhip_deblock_params q = *p;
+    q.strong = p->strong != 0;
+    *out = hbhip_make_filter<DeblockFilter>(ctx, g, g, q);
+    return *out ? HBHIP_OK : HBHIP_ERR_NOMEM;
 }
 
 extern "C" int hbhip_deblock_set_warmup(hbhip_filter *f, int edges)

@@ -11,7 +11,9 @@
 #include <atomic>
 #include <memory>
 #include <mutex>
+#include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "hbhip.h"
@@ -344,7 +346,8 @@ struct SimpleFilter : hbhip_filter
     std::deque<DevPicture *> outq;
     explicit SimpleFilter(hbhip_ctx *c) : hbhip_filter(c) {}
 
-    void configure(const PicGeometry &gin, const PicGeometry &gout)
+    // (out of line: one copy in the library, not one in every create function)
+    __attribute__((noinline)) void configure(const PicGeometry &gin, const PicGeometry &gout)
     {
         in_geo = gin;
         out_geo = gout;
@@ -471,3 +474,80 @@ struct SimpleFilter : hbhip_filter
         return HBHIP_OK;
     }
 };
+
+// ---- bursts: the frames of a process_many() that go out in one launch ----
+// The rule, here and nowhere else: a launch takes up to MAXF consecutive frames whose three input and three output pitches
+// equal those of the first of them (the kernels take one pitch per plane for the whole launch).
+static inline bool hbhip_same_pitches(DevPicture *const *ins, DevPicture *const *outs, int i, int k)
+{
+    for (int c = 0; c < 3; c++)
+        if (ins[i]->pitch[c] != ins[k]->pitch[c] || outs[i]->pitch[c] != outs[k]->pitch[c]) return false;
+    return true;
+}
+
+// Cuts ins / outs [0, n) into such runs.  For the run [at, at + nf) a zeroed Args gets src[f][c], dst[f][c], spitch[c] and
+// dpitch[c], `bits` is every one of those addresses and pitches ORed together (the caller's alignment test), and
+// launch(a, nf, at, bits) fills in the rest and launches: anything but HBHIP_OK from it ends the walk with that code.
+template <int MAXF, class Args, class Fn>
+static int hbhip_for_each_burst(hbhip_ctx *ctx, DevPicture *const *ins, DevPicture *const *outs, int n, Fn &&launch)
+{
+    for (int at = 0, nf; at < n; at += nf)
+    {
+        for (nf = 1; at + nf < n && nf < MAXF && hbhip_same_pitches(ins, outs, at, at + nf); ) nf++;
+        Args a;
+        memset(&a, 0, sizeof(a));
+        uintptr_t bits = 0;
+        for (int c = 0; c < 3; c++)
+        {
+            a.spitch[c] = ins[at]->pitch[c]; a.dpitch[c] = outs[at]->pitch[c];
+            bits |= (uintptr_t)(a.spitch[c] | a.dpitch[c]);
+            for (int f = 0; f < nf; f++)
+            {
+                a.src[f][c] = ins[at + f]->plane[c]; a.dst[f][c] = outs[at + f]->plane[c];
+                bits |= (uintptr_t)a.src[f][c] | (uintptr_t)a.dst[f][c];
+            }
+        }
+        const int rc = launch(a, nf, at, bits);
+        if (rc != HBHIP_OK) return rc;
+        HBHIP_CHECK(ctx, hipGetLastError());
+    }
+    return HBHIP_OK;
+}
+
+// A SimpleFilter whose process_many() is such a walk: a single frame is a burst of one.  (File-local like the filters that
+// derive from it: the library exports nothing for it.)
+namespace {
+struct BurstFilter : SimpleFilter
+{
+    using SimpleFilter::SimpleFilter;
+    int process(DevPicture *in, DevPicture *out) override { return process_many(&in, &out, 1); }
+};
+}
+
+// ---- create functions ----
+// planar 4:2:0, 4:2:2 or 4:4:4
+static inline bool hbhip_yuv_layout_ok(int lcw, int lch) { return (lcw == 1 && (lch == 1 || lch == 0)) || (lcw == 0 && lch == 0); }
+
+// The tail of a create function, behind its checks: the device, the instance, its two geometries.  nullptr: HBHIP_ERR_NOMEM.
+template <class F, class... A>
+static F *hbhip_make_filter(hbhip_ctx *ctx, const PicGeometry &gin, const PicGeometry &gout, A &&...args)
+{
+    (void)hipSetDevice(ctx->device);
+    F *f = new (std::nothrow) F(ctx, std::forward<A>(args)...);
+    if (f) f->configure(gin, gout);
+    return f;
+}
+
+// A whole create function for a filter that needs no check of its own between these: null pointers, depth, size, in this order.
+template <class F, class... A>
+static int create_simple(hbhip_ctx *ctx, int width, int height, int depth, int lcw, int lch, hbhip_filter **out, A &&...args)
+{
+    if (!ctx || !out) return HBHIP_ERR_ARG;
+    *out = nullptr;
+    if (depth != 8 && depth != 10 && depth != 12) return HBHIP_ERR_UNSUPPORTED;
+    if (width < 1 || height < 1) return HBHIP_ERR_ARG;
+    PicGeometry g;
+    g.set(width, height, depth, lcw, lch);
+    *out = hbhip_make_filter<F>(ctx, g, g, std::forward<A>(args)...);
+    return *out ? HBHIP_OK : HBHIP_ERR_NOMEM;
+}

@@ -1105,23 +1105,6 @@ public:
     const char *name;
 };
 
-template <class F, class... A>
-int create_simple(hbhip_ctx *ctx, int width, int height, int depth, int lcw, int lch, hbhip_filter **out, A &&...args)
-{
-    if (!ctx || !out) return HBHIP_ERR_ARG;
-    *out = nullptr;
-    if (depth != 8 && depth != 10 && depth != 12) return HBHIP_ERR_UNSUPPORTED;
-    if (width < 1 || height < 1) return HBHIP_ERR_ARG;
-    (void)hipSetDevice(ctx->device);
-    F *f = new (std::nothrow) F(ctx, std::forward<A>(args)...);
-    if (!f) return HBHIP_ERR_NOMEM;
-    PicGeometry g;
-    g.set(width, height, depth, lcw, lch);
-    f->configure(g, g);
-    *out = f;
-    return HBHIP_OK;
-}
-
 } // namespace
 
 extern "C" int hbhip_lapsharp_create(hbhip_ctx *ctx, const hbhip_lapsharp_params *p, int width, int height,

@@ -15,54 +15,7 @@
  */
 #include "hbhip_host.h"
 
-struct hb_filter_private_s
-{
-    hbhip_filter    *dev;
-    hb_filter_init_t input;
-    hb_filter_init_t output;
-    int              dev_io;
-};
-
-static void alias_hip_close(hb_filter_object_t *filter)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    if (pv == NULL) return;
-    hbhip_host_simple_destroy(pv->dev);
-    free(pv);
-    filter->private_data = NULL;
-}
-
-static int alias_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    return hbhip_host_simple_work(pv->dev, &pv->output, filter->short_name, pv->dev_io, buf_in, buf_out);
-}
-
-static hb_filter_private_t *alias_begin(hb_filter_object_t *filter, hb_filter_init_t *init,
-                                        const AVPixFmtDescriptor **desc)
-{
-    hb_filter_private_t *pv = calloc(1, sizeof(*pv));
-    filter->private_data = pv;
-    if (pv == NULL) return NULL;
-    pv->input = *init;
-    pv->dev_io = hbhip_host_dev_io(init);
-    *desc = av_pix_fmt_desc_get(init->pix_fmt);
-    if (*desc == NULL)
-    {
-        free(pv);
-        filter->private_data = NULL;
-        return NULL;
-    }
-    return pv;
-}
-
-static int alias_fail(hb_filter_object_t *filter, int rc)
-{
-    hb_error("%s(hip): %s", filter->short_name, hbhip_strerror(rc));
-    free(filter->private_data);
-    filter->private_data = NULL;
-    return 1;
-}
+struct hb_filter_private_s { hbhip_host_simple_t s; };
 
 /* ---- crop + scale ------------------------------------------------------------------ */
 static int crop_scale_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
@@ -80,8 +33,8 @@ hb_filter_object_t hb_filter_crop_scale_hip =
     .short_name        = "cropscale",
     .settings          = NULL,
     .init              = crop_scale_hip_init,
-    .work              = alias_hip_work,
-    .close             = alias_hip_close,
+    .work              = hbhip_host_simple_filter_work,
+    .close             = hbhip_host_simple_close,
     .settings_template = crop_scale_hip_template,
 };
 
@@ -121,8 +74,8 @@ static void limit_rational(int *x, int *y, int64_t num, int64_t den, int limit)
 static int crop_scale_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
     const AVPixFmtDescriptor *desc;
-    hb_filter_private_t *pv = alias_begin(filter, init, &desc);
-    if (pv == NULL) return 1;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
+    if (pv == NULL || desc == NULL) { hbhip_host_simple_close(filter); return 1; }   /* (no message) */
 
     hbhip_cropscale_params p;
     memset(&p, 0, sizeof(p));
@@ -149,16 +102,16 @@ static int crop_scale_hip_init(hb_filter_object_t *filter, hb_filter_init_t *ini
     if (odd)
     {
         const char *sws = getenv("HBHIP_SWSCALE");
-        if (sws == NULL || atoi(sws) == 0) return alias_fail(filter, HBHIP_ERR_UNSUPPORTED);
+        if (sws == NULL || atoi(sws) == 0) return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
     }
 
     hbhip_ctx *ctx = hbhip_host_ctx_for(init);
-    if (ctx == NULL) return alias_fail(filter, HBHIP_ERR_NODEVICE);
+    if (ctx == NULL) return hbhip_host_simple_fail(filter, HBHIP_ERR_NODEVICE);
     int rc = odd ? hbhip_cropscale_sws_create(ctx, &p, init->geometry.width, init->geometry.height, desc->comp[0].depth,
-                                              desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev)
+                                              desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev)
                  : hbhip_cropscale_create(ctx, &p, init->geometry.width, init->geometry.height, desc->comp[0].depth,
-                                          desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev);
-    if (rc != HBHIP_OK) return alias_fail(filter, rc);
+                                          desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev);
+    if (rc != HBHIP_OK) return hbhip_host_simple_fail(filter, rc);
 
     init->crop[0] = p.crop_top;                                              /* :168-178 */
     init->crop[1] = p.crop_bottom;
@@ -169,7 +122,7 @@ static int crop_scale_hip_init(hb_filter_object_t *filter, hb_filter_init_t *ini
                    (int64_t)init->geometry.par.den * p.width * cropped_height, 65535);
     init->geometry.width = p.width;
     init->geometry.height = p.height;
-    pv->output = *init;
+    pv->s.output = *init;
     return 0;
 }
 
@@ -187,27 +140,27 @@ hb_filter_object_t hb_filter_grayscale_hip =
     .short_name        = "grayscale",
     .settings          = NULL,
     .init              = grayscale_hip_init,
-    .work              = alias_hip_work,
-    .close             = alias_hip_close,
+    .work              = hbhip_host_simple_filter_work,
+    .close             = hbhip_host_simple_close,
     .settings_template = grayscale_hip_template,
 };
 
 static int grayscale_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
     const AVPixFmtDescriptor *desc;
-    hb_filter_private_t *pv = alias_begin(filter, init, &desc);
-    if (pv == NULL) return 1;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
+    if (pv == NULL || desc == NULL) { hbhip_host_simple_close(filter); return 1; }   /* (no message) */
     double cb = 0, cr = 0, size = 1, high = 0;                               /* grayscale.c:43-48 */
     hb_dict_extract_double(&cb, filter->settings, "cb");
     hb_dict_extract_double(&cr, filter->settings, "cr");
     hb_dict_extract_double(&size, filter->settings, "size");
     hb_dict_extract_double(&high, filter->settings, "high");
     hbhip_ctx *ctx = hbhip_host_ctx_for(init);
-    if (ctx == NULL) return alias_fail(filter, HBHIP_ERR_NODEVICE);
+    if (ctx == NULL) return hbhip_host_simple_fail(filter, HBHIP_ERR_NODEVICE);
     int rc = hbhip_grayscale_create(ctx, cb, cr, size, high, init->geometry.width, init->geometry.height,
-                                    desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev);
-    if (rc != HBHIP_OK) return alias_fail(filter, rc);
-    pv->output = *init;
+                                    desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev);
+    if (rc != HBHIP_OK) return hbhip_host_simple_fail(filter, rc);
+    pv->s.output = *init;
     return 0;
 }
 
@@ -225,24 +178,24 @@ hb_filter_object_t hb_filter_rotate_hip =
     .short_name        = "rotate",
     .settings          = NULL,
     .init              = rotate_hip_init,
-    .work              = alias_hip_work,
-    .close             = alias_hip_close,
+    .work              = hbhip_host_simple_filter_work,
+    .close             = hbhip_host_simple_close,
     .settings_template = rotate_hip_template,
 };
 
 static int rotate_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
     const AVPixFmtDescriptor *desc;
-    hb_filter_private_t *pv = alias_begin(filter, init, &desc);
-    if (pv == NULL) return 1;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
+    if (pv == NULL || desc == NULL) { hbhip_host_simple_close(filter); return 1; }   /* (no message) */
     int angle = 0, flip = 0;
     hb_dict_extract_int(&angle, filter->settings, "angle");                  /* rotate.c:166-167 */
     hb_dict_extract_bool(&flip, filter->settings, "hflip");
     hbhip_ctx *ctx = hbhip_host_ctx_for(init);
-    if (ctx == NULL) return alias_fail(filter, HBHIP_ERR_NODEVICE);
+    if (ctx == NULL) return hbhip_host_simple_fail(filter, HBHIP_ERR_NODEVICE);
     int rc = hbhip_rotate_create(ctx, angle, flip, init->geometry.width, init->geometry.height,
-                                 desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev);
-    if (rc != HBHIP_OK) return alias_fail(filter, rc);
+                                 desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev);
+    if (rc != HBHIP_OK) return hbhip_host_simple_fail(filter, rc);
     if (angle == 90 || angle == 270)                                         /* rotate.c:195-214, 261-263 */
     {
         const int w = init->geometry.width, n = init->geometry.par.num;
@@ -251,7 +204,7 @@ static int rotate_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
         init->geometry.par.num = init->geometry.par.den;
         init->geometry.par.den = n;
     }
-    pv->output = *init;
+    pv->s.output = *init;
     return 0;
 }
 
@@ -277,20 +230,20 @@ hb_filter_object_t hb_filter_format_hip =
     .settings          = NULL,
     .init              = format_hip_init,
     .work              = format_hip_work,
-    .close             = alias_hip_close,
+    .close             = hbhip_host_simple_close,
     .settings_template = format_hip_template,
 };
 
 static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
     const AVPixFmtDescriptor *desc;
-    hb_filter_private_t *pv = alias_begin(filter, init, &desc);
-    if (pv == NULL) return 1;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
+    if (pv == NULL || desc == NULL) { hbhip_host_simple_close(filter); return 1; }   /* (no message) */
     char *format = NULL;
     hb_dict_extract_string(&format, filter->settings, "format");              /* format.c:46-52 */
     if (format == NULL)
     {
-        pv->output = *init;                                                   /* nothing to do: frames pass through */
+        pv->s.output = *init;                                                   /* nothing to do: frames pass through */
         return 0;
     }
     const int dst_fmt = av_get_pix_fmt(format);                               /* :107 */
@@ -298,26 +251,26 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     const AVPixFmtDescriptor *dd = av_pix_fmt_desc_get(dst_fmt);
     if (dd == NULL || dd->nb_components != desc->nb_components || desc->nb_components < 3 ||
         dd->log2_chroma_w != desc->log2_chroma_w || dd->log2_chroma_h != desc->log2_chroma_h)
-        return alias_fail(filter, HBHIP_ERR_UNSUPPORTED);
+        return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
     hbhip_ctx *ctx = hbhip_host_ctx_for(init);
-    if (ctx == NULL) return alias_fail(filter, HBHIP_ERR_NODEVICE);
+    if (ctx == NULL) return hbhip_host_simple_fail(filter, HBHIP_ERR_NODEVICE);
     int rc = hbhip_format_create(ctx, init->geometry.width, init->geometry.height, desc->comp[0].depth,
                                  dd->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h,
-                                 init->color_range == 2 /* AVCOL_RANGE_JPEG */, &pv->dev);
-    if (rc != HBHIP_OK) return alias_fail(filter, rc);
+                                 init->color_range == 2 /* AVCOL_RANGE_JPEG */, &pv->s.dev);
+    if (rc != HBHIP_OK) return hbhip_host_simple_fail(filter, rc);
     init->pix_fmt = dst_fmt;
-    pv->output = *init;
+    pv->s.output = *init;
     return 0;
 }
 
 static int format_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out)
 {
     hb_filter_private_t *pv = filter->private_data;
-    if (pv->dev == NULL)
+    if (pv->s.dev == NULL)
     {
         *buf_out = *buf_in;
         *buf_in = NULL;
         return ((*buf_out)->s.flags & HB_BUF_FLAG_EOF) ? HB_FILTER_DONE : HB_FILTER_OK;
     }
-    return hbhip_host_simple_work(pv->dev, &pv->output, filter->short_name, pv->dev_io, buf_in, buf_out);
+    return hbhip_host_simple_filter_work(filter, buf_in, buf_out);
 }

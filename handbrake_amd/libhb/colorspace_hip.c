@@ -13,17 +13,10 @@
 #include <math.h>
 #include <string.h>
 
-struct hb_filter_private_s
-{
-    hbhip_filter    *dev;         /* NULL: pass-through (colorspace.c:87-90, 122-126) */
-    hb_filter_init_t input;
-    hb_filter_init_t output;
-    int              dev_io;
-};
+struct hb_filter_private_s { hbhip_host_simple_t s; };    /* s.dev NULL: pass-through (colorspace.c:87-90, 122-126) */
 
 static int colorspace_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
 static int colorspace_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
-static void colorspace_hip_close(hb_filter_object_t *filter);
 
 static const char colorspace_hip_template[] =
     "primaries=^"HB_ALL_REG"$:transfer=^"HB_ALL_REG"$:matrix=^"HB_ALL_REG"$:range=^"HB_ALL_REG"$:"
@@ -38,7 +31,7 @@ hb_filter_object_t hb_filter_colorspace_hip =
     .settings          = NULL,
     .init              = colorspace_hip_init,
     .work              = colorspace_hip_work,
-    .close             = colorspace_hip_close,
+    .close             = hbhip_host_simple_close,
     .settings_template = colorspace_hip_template,
 };
 
@@ -95,18 +88,15 @@ static double signal_peak(const hb_filter_init_t *init)
 
 static int colorspace_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
-    hb_filter_private_t *pv = calloc(1, sizeof(*pv));
-    filter->private_data = pv;
+    const AVPixFmtDescriptor *desc;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
     if (pv == NULL) return 1;
-    pv->input = *init;
-    pv->output = *init;
-    pv->dev_io = hbhip_host_dev_io(init);
+    pv->s.output = *init;
 
     if (init->color_prim == 2 || init->color_transfer == 2 || init->color_matrix == 2)      /* HB_COLR_*_UNDEF, :62-68 */
     {
         hb_error("colorspace(hip): input color space undefined");
-        free(pv);
-        filter->private_data = NULL;
+        hbhip_host_simple_close(filter);
         return -1;
     }
 
@@ -146,64 +136,46 @@ static int colorspace_hip_init(hb_filter_object_t *filter, hb_filter_init_t *ini
             p.desat = desat;
             p.npl = npl;
             p.peak = signal_peak(init);
-            const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(init->pix_fmt);
             hbhip_ctx *ctx = desc != NULL && p.tonemap >= 0 ? hbhip_host_ctx_for(init) : NULL;
             int err = ctx == NULL ? HBHIP_ERR_NODEVICE
                                   : hbhip_colorspace_create(ctx, &p, init->geometry.width, init->geometry.height,
                                                             desc->comp[0].depth, desc->log2_chroma_w,
-                                                            desc->log2_chroma_h, &pv->dev);
+                                                            desc->log2_chroma_h, &pv->s.dev);
             if (err != HBHIP_OK)
-            {
-                hb_error("colorspace(hip): %s", hbhip_strerror(err));
-                rc = 1;
-            }
+                rc = hbhip_host_simple_fail(filter, err);                                     /* (pv is gone) */
             else
             {
                 init->color_prim = p.out_prim;                                                /* :195-198 */
                 init->color_transfer = p.out_transfer;
                 init->color_matrix = p.out_matrix;
                 init->color_range = p.out_range;
-                pv->output = *init;
+                pv->s.output = *init;
             }
         }
     }
     free(range); free(primaries); free(transfer); free(matrix); free(tonemap);
-    if (rc != 0)
-    {
-        free(pv);
-        filter->private_data = NULL;
-    }
     return rc;
 }
 
 static int colorspace_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out)
 {
     hb_filter_private_t *pv = filter->private_data;
-    if (pv->dev == NULL)
+    if (pv->s.dev == NULL)
     {
         /* nothing to convert: the reference adds no avfilter at all in this case */
         *buf_out = *buf_in;
         *buf_in = NULL;
         return ((*buf_out)->s.flags & HB_BUF_FLAG_EOF) ? HB_FILTER_DONE : HB_FILTER_OK;
     }
-    const int status = hbhip_host_simple_work(pv->dev, &pv->output, filter->short_name, pv->dev_io, buf_in, buf_out);
+    const int status = hbhip_host_simple_filter_work(filter, buf_in, buf_out);
     if (status == HB_FILTER_OK || status == HB_FILTER_DONE)
         for (hb_buffer_t *b = *buf_out; b != NULL; b = b->next)    /* a burst, or the frames an EOF drains, come as a list */
         {
             if (b->s.flags & HB_BUF_FLAG_EOF) continue;
-            b->f.color_prim = pv->output.color_prim;
-            b->f.color_transfer = pv->output.color_transfer;
-            b->f.color_matrix = pv->output.color_matrix;
-            b->f.color_range = pv->output.color_range;
+            b->f.color_prim = pv->s.output.color_prim;
+            b->f.color_transfer = pv->s.output.color_transfer;
+            b->f.color_matrix = pv->s.output.color_matrix;
+            b->f.color_range = pv->s.output.color_range;
         }
     return status;
-}
-
-static void colorspace_hip_close(hb_filter_object_t *filter)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    if (pv == NULL) return;
-    if (pv->dev != NULL) hbhip_host_simple_destroy(pv->dev);
-    free(pv);
-    filter->private_data = NULL;
 }

@@ -20,17 +20,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-struct hb_filter_private_s
-{
-    hbhip_filter    *dev;
-    hb_filter_init_t input;
-    hb_filter_init_t output;
-    int              dev_io;
-};
+struct hb_filter_private_s { hbhip_host_simple_t s; };
 
 static int deband_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
-static int deband_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
-static void deband_hip_close(hb_filter_object_t *filter);
 
 static const char deband_hip_template[] =                                    /* deband.c:15-18 */
     "1thr=^"HB_FLOAT_REG"$:2thr=^"HB_FLOAT_REG"$:"
@@ -45,8 +37,8 @@ hb_filter_object_t hb_filter_deband_hip =
     .short_name        = "deband",
     .settings          = NULL,
     .init              = deband_hip_init,
-    .work              = deband_hip_work,
-    .close             = deband_hip_close,
+    .work              = hbhip_host_simple_filter_work,
+    .close             = hbhip_host_simple_close,
     .settings_template = deband_hip_template,
 };
 
@@ -96,56 +88,21 @@ int hbhip_deband_params_from_settings(const char *settings, int depth, hbhip_deb
 }
 #endif
 
-/* planar YUV 4:2:0 / 4:2:2 / 4:4:4 at 8 / 10 / 12 bits */
-static int format_ok(const AVPixFmtDescriptor *desc)
-{
-    if (desc == NULL || desc->nb_components != 3) return 0;
-    for (int i = 0; i < 3; i++)
-        if (desc->comp[i].plane != i || desc->comp[i].depth != desc->comp[0].depth) return 0;
-    const int d = desc->comp[0].depth, lw = desc->log2_chroma_w, lh = desc->log2_chroma_h;
-    return (d == 8 || d == 10 || d == 12) && ((lw == 1 && lh == 1) || (lw == 1 && lh == 0) || (lw == 0 && lh == 0));
-}
-
 static int deband_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
-    hb_filter_private_t *pv = calloc(1, sizeof(*pv));
-    filter->private_data = pv;
+    const AVPixFmtDescriptor *desc;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
     if (pv == NULL) return 1;
-    pv->input = *init;
-    pv->dev_io = hbhip_host_dev_io(init);
-
-    const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(init->pix_fmt);
     hbhip_deband_params p;
-    int rc = format_ok(desc) ? HBHIP_OK : HBHIP_ERR_UNSUPPORTED;
+    int rc = hbhip_host_planar_yuv(desc) ? HBHIP_OK : HBHIP_ERR_UNSUPPORTED;
     if (rc == HBHIP_OK && deband_hip_params(filter->settings, desc->comp[0].depth, &p) != 0)
         rc = HBHIP_ERR_UNSUPPORTED;
     hbhip_ctx *ctx = rc == HBHIP_OK ? hbhip_host_ctx_for(init) : NULL;
     if (rc == HBHIP_OK && ctx == NULL) rc = HBHIP_ERR_NODEVICE;
     if (rc == HBHIP_OK)
         rc = hbhip_deband_create(ctx, &p, init->geometry.width, init->geometry.height, desc->comp[0].depth,
-                                 desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev);
-    if (rc != HBHIP_OK)
-    {
-        hb_error("deband(hip): %s", hbhip_strerror(rc));
-        free(pv);
-        filter->private_data = NULL;
-        return 1;
-    }
-    pv->output = *init;
+                                 desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev);
+    if (rc != HBHIP_OK) return hbhip_host_simple_fail(filter, rc);
+    pv->s.output = *init;
     return 0;
-}
-
-static int deband_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    return hbhip_host_simple_work(pv->dev, &pv->output, filter->short_name, pv->dev_io, buf_in, buf_out);
-}
-
-static void deband_hip_close(hb_filter_object_t *filter)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    if (pv == NULL) return;
-    hbhip_host_simple_destroy(pv->dev);
-    free(pv);
-    filter->private_data = NULL;
 }

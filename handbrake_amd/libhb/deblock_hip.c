@@ -18,17 +18,9 @@
 #include <stdio.h>
 #include <string.h>
 
-struct hb_filter_private_s
-{
-    hbhip_filter    *dev;
-    hb_filter_init_t input;
-    hb_filter_init_t output;
-    int              dev_io;
-};
+struct hb_filter_private_s { hbhip_host_simple_t s; };
 
 static int deblock_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
-static int deblock_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
-static void deblock_hip_close(hb_filter_object_t *filter);
 
 static const char deblock_hip_template[] =                                   /* deblock.c:15-17 */
     "strength=^"HB_ALL_REG"$:thresh=^"HB_INT_REG"$:blocksize=^"HB_INT_REG"$:"
@@ -42,8 +34,8 @@ hb_filter_object_t hb_filter_deblock_hip =
     .short_name        = "deblock",
     .settings          = NULL,
     .init              = deblock_hip_init,
-    .work              = deblock_hip_work,
-    .close             = deblock_hip_close,
+    .work              = hbhip_host_simple_filter_work,
+    .close             = hbhip_host_simple_close,
     .settings_template = deblock_hip_template,
 };
 
@@ -122,13 +114,9 @@ int hbhip_deblock_params_from_settings(const char *settings, int depth, int widt
 
 static int deblock_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
-    hb_filter_private_t *pv = calloc(1, sizeof(*pv));
-    filter->private_data = pv;
+    const AVPixFmtDescriptor *desc;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
     if (pv == NULL) return 1;
-    pv->input = *init;
-    pv->dev_io = hbhip_host_dev_io(init);
-
-    const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(init->pix_fmt);
     hbhip_deblock_params p;
     int rc = desc == NULL ? HBHIP_ERR_ARG : HBHIP_OK;
     if (rc == HBHIP_OK &&
@@ -139,29 +127,8 @@ static int deblock_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     if (rc == HBHIP_OK && ctx == NULL) rc = HBHIP_ERR_NODEVICE;
     if (rc == HBHIP_OK)
         rc = hbhip_deblock_create(ctx, &p, init->geometry.width, init->geometry.height, desc->comp[0].depth,
-                                  desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev);
-    if (rc != HBHIP_OK)
-    {
-        hb_error("deblock(hip): %s", hbhip_strerror(rc));
-        free(pv);
-        filter->private_data = NULL;
-        return 1;
-    }
-    pv->output = *init;
+                                  desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev);
+    if (rc != HBHIP_OK) return hbhip_host_simple_fail(filter, rc);
+    pv->s.output = *init;
     return 0;
-}
-
-static int deblock_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    return hbhip_host_simple_work(pv->dev, &pv->output, filter->short_name, pv->dev_io, buf_in, buf_out);
-}
-
-static void deblock_hip_close(hb_filter_object_t *filter)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    if (pv == NULL) return;
-    hbhip_host_simple_destroy(pv->dev);
-    free(pv);
-    filter->private_data = NULL;
 }

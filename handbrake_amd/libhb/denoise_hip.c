@@ -9,16 +9,11 @@
 
 struct hb_filter_private_s
 {
+    hbhip_host_simple_t s;
     hbhip_hqdn3d_params par;
-    hbhip_filter       *dev;
-    hb_filter_init_t    input;
-    hb_filter_init_t    output;
-    int                 dev_io;
 };
 
 static int  denoise_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
-static int  denoise_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
-static void denoise_hip_close(hb_filter_object_t *filter);
 
 static const char denoise_hip_template[] =
     "y-spatial=^"HB_FLOAT_REG"$:cb-spatial=^"HB_FLOAT_REG"$:"
@@ -34,8 +29,8 @@ hb_filter_object_t hb_filter_denoise_hip =
     .short_name        = "hqdn3d",
     .settings          = NULL,
     .init              = denoise_hip_init,
-    .work              = denoise_hip_work,
-    .close             = denoise_hip_close,
+    .work              = hbhip_host_simple_filter_work,
+    .close             = hbhip_host_simple_close,
     .settings_template = denoise_hip_template,
 };
 
@@ -55,14 +50,9 @@ static void precalc_coef(int16_t *ct, double dist25)
 
 static int denoise_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
-    hb_filter_private_t *pv = calloc(1, sizeof(*pv));
-    if (pv == NULL) return -1;
-    filter->private_data = pv;
-    pv->input = *init;
-    pv->dev_io = hbhip_host_dev_io(init);
-
-    const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(init->pix_fmt);
-    if (desc == NULL || (desc->comp[0].depth != 8 && desc->comp[0].depth != 10 && desc->comp[0].depth != 12)) goto fail;
+    const AVPixFmtDescriptor *desc;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
+    if (pv == NULL || desc == NULL || (desc->comp[0].depth != 8 && desc->comp[0].depth != 10 && desc->comp[0].depth != 12)) goto fail;
 
     double sy, scb, scr, ty, tcb, tcr;                      /* denoise.c:228-256 */
     if (!hb_dict_extract_double(&sy, filter->settings, "y-spatial"))    sy = 4.0;
@@ -81,31 +71,11 @@ static int denoise_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     hbhip_ctx *ctx = hbhip_host_ctx_for(init);
     if (ctx == NULL) goto fail;
     int rc = hbhip_hqdn3d_create(ctx, &pv->par, init->geometry.width, init->geometry.height,
-                                 desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev);
-    if (rc != HBHIP_OK)
-    {
-        hb_error("hqdn3d(hip): %s", hbhip_strerror(rc));
-        goto fail;
-    }
-    pv->output = *init;
+                                 desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev);
+    if (rc != HBHIP_OK) { hbhip_host_simple_fail(filter, rc); return -1; }
+    pv->s.output = *init;
     return 0;
-fail:
-    free(pv);
-    filter->private_data = NULL;
+fail:                                                       /* (no message) */
+    hbhip_host_simple_close(filter);
     return -1;
-}
-
-static void denoise_hip_close(hb_filter_object_t *filter)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    if (pv == NULL) return;
-    hbhip_host_simple_destroy(pv->dev);
-    free(pv);
-    filter->private_data = NULL;
-}
-
-static int denoise_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    return hbhip_host_simple_work(pv->dev, &pv->output, "hqdn3d", pv->dev_io, buf_in, buf_out);
 }

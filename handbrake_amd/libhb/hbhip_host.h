@@ -87,6 +87,27 @@ extern hb_filter_object_t hb_filter_hip_download;
 int hbhip_host_simple_work(hbhip_filter *dev, const hb_filter_init_t *output, const char *who,
                            int dev_io, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
 
+/* The skeleton of such a drop-in: the FIRST member of its hb_filter_private_s (`s`), so that the four functions below find
+ * it behind filter->private_data.
+ *   begin  allocates `size` zeroed bytes as the private data, fills input and dev_io from `init` and fetches the pixel
+ *          format's descriptor (NULL when there is none: the caller decides what that means).  NULL: out of memory.
+ *   fail   init() declines with an HBHIP_ERR_*: "<short_name>(hip): <hbhip_strerror>", the private data freed.  Returns 1.
+ *   filter_work / close   what .work and .close point at; close alone is also the silent way out of a failed init(). */
+typedef struct
+{
+    hbhip_filter    *dev;
+    hb_filter_init_t input;
+    hb_filter_init_t output;
+    int              dev_io;
+} hbhip_host_simple_t;
+void *hbhip_host_simple_begin(hb_filter_object_t *filter, const hb_filter_init_t *init, size_t size,
+                              const AVPixFmtDescriptor **desc);
+int   hbhip_host_simple_fail(hb_filter_object_t *filter, int rc);
+int   hbhip_host_simple_filter_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
+void  hbhip_host_simple_close(hb_filter_object_t *filter);
+/* planar YUV 4:2:0 / 4:2:2 / 4:4:4 at 8 / 10 / 12 bits */
+int   hbhip_host_planar_yuv(const AVPixFmtDescriptor *desc);
+
 /* The HIP drop-ins registered by this library (ids = the CPU filters' ids,
  * SURVEY Appendix D). */
 extern hb_filter_object_t hb_filter_nlmeans_hip;

@@ -605,6 +605,49 @@ int hbhip_host_simple_work(hbhip_filter *dev, const hb_filter_init_t *output, co
     return HB_FILTER_OK;
 }
 
+void *hbhip_host_simple_begin(hb_filter_object_t *filter, const hb_filter_init_t *init, size_t size,
+                              const AVPixFmtDescriptor **desc)
+{
+    hbhip_host_simple_t *s = calloc(1, size);
+    filter->private_data = (hb_filter_private_t *)s;
+    if (s == NULL) return NULL;
+    s->input = *init;
+    s->dev_io = hbhip_host_dev_io(init);
+    *desc = av_pix_fmt_desc_get(init->pix_fmt);
+    return s;
+}
+
+int hbhip_host_simple_fail(hb_filter_object_t *filter, int rc)
+{
+    hb_error("%s(hip): %s", filter->short_name, hbhip_strerror(rc));
+    hbhip_host_simple_close(filter);
+    return 1;
+}
+
+int hbhip_host_simple_filter_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out)
+{
+    hbhip_host_simple_t *s = (hbhip_host_simple_t *)filter->private_data;
+    return hbhip_host_simple_work(s->dev, &s->output, filter->short_name, s->dev_io, buf_in, buf_out);
+}
+
+void hbhip_host_simple_close(hb_filter_object_t *filter)
+{
+    hbhip_host_simple_t *s = (hbhip_host_simple_t *)filter->private_data;
+    if (s == NULL) return;
+    hbhip_host_simple_destroy(s->dev);
+    free(s);
+    filter->private_data = NULL;
+}
+
+int hbhip_host_planar_yuv(const AVPixFmtDescriptor *desc)
+{
+    if (desc == NULL || desc->nb_components != 3) return 0;
+    for (int i = 0; i < 3; i++)
+        if (desc->comp[i].plane != i || desc->comp[i].depth != desc->comp[0].depth) return 0;
+    const int d = desc->comp[0].depth, lw = desc->log2_chroma_w, lh = desc->log2_chroma_h;
+    return (d == 8 || d == 10 || d == 12) && ((lw == 1 && lh == 1) || (lw == 1 && lh == 0) || (lw == 0 && lh == 0));
+}
+
 /* ---- adapters: host <-> device at the ends of a run of HIP filters ----------------------
  * (the reference's analogue is HB_FILTER_ADAPTER_VT, platform/macosx/adapter_vt.c) */
 /* The download adapter keeps DL_DEPTH copies in flight on the context's download stream: the D2H of frame n runs

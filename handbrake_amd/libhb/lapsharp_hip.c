@@ -6,16 +6,12 @@
 
 struct hb_filter_private_s
 {
+    hbhip_host_simple_t   s;
     hbhip_lapsharp_params par;
-    hbhip_filter         *dev;
-    hb_filter_init_t      input;
-    hb_filter_init_t      output;
-    int                   dev_io;
 };
 
 static int  lapsharp_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
 static int  lapsharp_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
-static void lapsharp_hip_close(hb_filter_object_t *filter);
 
 static const char lapsharp_hip_template[] =
     "y-strength=^"HB_FLOAT_REG"$:y-kernel=^"HB_ALL_REG"$:"
@@ -31,7 +27,7 @@ hb_filter_object_t hb_filter_lapsharp_hip =
     .settings          = NULL,
     .init              = lapsharp_hip_init,
     .work              = lapsharp_hip_work,
-    .close             = lapsharp_hip_close,
+    .close             = hbhip_host_simple_close,
     .settings_template = lapsharp_hip_template,
 };
 
@@ -46,14 +42,9 @@ static int kernel_id(const char *s)
 
 static int lapsharp_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
-    hb_filter_private_t *pv = calloc(1, sizeof(*pv));
-    if (pv == NULL) return -1;
-    filter->private_data = pv;
-    pv->input = *init;
-    pv->dev_io = hbhip_host_dev_io(init);
-
-    const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(init->pix_fmt);
-    if (desc == NULL) goto fail;
+    const AVPixFmtDescriptor *desc;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
+    if (pv == NULL || desc == NULL) goto fail;
 
     static const char *pfx[3] = { "y", "cb", "cr" };
     char key[32];
@@ -89,33 +80,18 @@ static int lapsharp_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     hbhip_ctx *ctx = hbhip_host_ctx_for(init);
     if (ctx == NULL) goto fail;
     int rc = hbhip_lapsharp_create(ctx, &pv->par, init->geometry.width, init->geometry.height,
-                                   desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev);
-    if (rc != HBHIP_OK)
-    {
-        hb_error("lapsharp(hip): %s", hbhip_strerror(rc));
-        goto fail;
-    }
-    pv->output = *init;
+                                   desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev);
+    if (rc != HBHIP_OK) { hbhip_host_simple_fail(filter, rc); return -1; }
+    pv->s.output = *init;
     return 0;
-fail:
-    free(pv);
-    filter->private_data = NULL;
+fail:                                                                       /* (no message) */
+    hbhip_host_simple_close(filter);
     return -1;
-}
-
-static void lapsharp_hip_close(hb_filter_object_t *filter)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    if (pv == NULL) return;
-    hbhip_host_simple_destroy(pv->dev);
-    free(pv);
-    filter->private_data = NULL;
 }
 
 static int lapsharp_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out)
 {
-    hb_filter_private_t *pv = filter->private_data;
     if (!((*buf_in)->s.flags & HB_BUF_FLAG_EOF) && hbhip_host_frame_of(*buf_in) == NULL)
         hb_frame_buffer_mirror_stride(*buf_in);                             /* lapsharp.c:333 */
-    return hbhip_host_simple_work(pv->dev, &pv->output, "lapsharp", pv->dev_io, buf_in, buf_out);
+    return hbhip_host_simple_filter_work(filter, buf_in, buf_out);
 }

@@ -14,17 +14,9 @@
 #include <string.h>
 #include <strings.h>
 
-struct hb_filter_private_s
-{
-    hbhip_filter    *dev;
-    hb_filter_init_t input;
-    hb_filter_init_t output;
-    int              dev_io;
-};
+struct hb_filter_private_s { hbhip_host_simple_t s; };
 
 static int pad_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
-static int pad_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
-static void pad_hip_close(hb_filter_object_t *filter);
 
 static const char pad_hip_template[] =
     "width=^"HB_INT_REG"$:height=^"HB_INT_REG"$:color=^"HB_ALL_REG"$:"
@@ -40,8 +32,8 @@ hb_filter_object_t hb_filter_pad_hip =
     .short_name        = "pad",
     .settings          = NULL,
     .init              = pad_hip_init,
-    .work              = pad_hip_work,
-    .close             = pad_hip_close,
+    .work              = hbhip_host_simple_filter_work,
+    .close             = hbhip_host_simple_close,
     .settings_template = pad_hip_template,
 };
 
@@ -93,11 +85,9 @@ static void fill_from_rgb(int rgb, int matrix, int range, int depth, int fill[3]
 
 static int pad_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
-    hb_filter_private_t *pv = calloc(1, sizeof(*pv));
-    filter->private_data = pv;
+    const AVPixFmtDescriptor *desc;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
     if (pv == NULL) return 1;
-    pv->input = *init;
-    pv->dev_io = hbhip_host_dev_io(init);
 
     int width = -1, height = -1, rgb = 0;
     int top = -1, bottom = -1, left = -1, right = -1, x = -1, y = -1;
@@ -125,7 +115,6 @@ static int pad_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     if (width < init->geometry.width)   width = init->geometry.width;         /* :119-126 */
     if (height < init->geometry.height) height = init->geometry.height;
 
-    const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(init->pix_fmt);
     hbhip_ctx *ctx = desc != NULL ? hbhip_host_ctx_for(init) : NULL;
     int rc = ctx == NULL ? HBHIP_ERR_NODEVICE : HBHIP_OK;
     if (rc == HBHIP_OK)
@@ -144,32 +133,11 @@ static int pad_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
         if (p.y + init->geometry.height > height) p.y = (height - init->geometry.height) & ~((1 << desc->log2_chroma_h) - 1);
         fill_from_rgb(rgb, init->color_matrix, init->color_range, desc->comp[0].depth, p.fill);
         rc = hbhip_pad_create(ctx, &p, init->geometry.width, init->geometry.height, desc->comp[0].depth,
-                              desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev);
+                              desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev);
     }
-    if (rc != HBHIP_OK)
-    {
-        hb_error("pad(hip): %s", hbhip_strerror(rc));
-        free(pv);
-        filter->private_data = NULL;
-        return 1;
-    }
+    if (rc != HBHIP_OK) return hbhip_host_simple_fail(filter, rc);
     init->geometry.width = width;                                             /* :143-145 */
     init->geometry.height = height;
-    pv->output = *init;
+    pv->s.output = *init;
     return 0;
-}
-
-static int pad_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    return hbhip_host_simple_work(pv->dev, &pv->output, filter->short_name, pv->dev_io, buf_in, buf_out);
-}
-
-static void pad_hip_close(hb_filter_object_t *filter)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    if (pv == NULL) return;
-    hbhip_host_simple_destroy(pv->dev);
-    free(pv);
-    filter->private_data = NULL;
 }

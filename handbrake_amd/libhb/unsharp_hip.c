@@ -8,17 +8,12 @@
 
 struct hb_filter_private_s
 {
-    hbhip_blur_params par;
-    hbhip_filter     *dev;
-    hb_filter_init_t  input;
-    hb_filter_init_t  output;
-    int               dev_io;
+    hbhip_host_simple_t s;
+    hbhip_blur_params   par;
 };
 
 static int  unsharp_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
 static int  chroma_smooth_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
-static int  blur_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
-static void blur_hip_close(hb_filter_object_t *filter);
 
 static const char unsharp_hip_template[] =
     "y-strength=^"HB_FLOAT_REG"$:y-size=^"HB_INT_REG"$:"
@@ -37,8 +32,8 @@ hb_filter_object_t hb_filter_unsharp_hip =
     .short_name        = "unsharp",
     .settings          = NULL,
     .init              = unsharp_hip_init,
-    .work              = blur_hip_work,
-    .close             = blur_hip_close,
+    .work              = hbhip_host_simple_filter_work,
+    .close             = hbhip_host_simple_close,
     .settings_template = unsharp_hip_template,
 };
 
@@ -50,22 +45,17 @@ hb_filter_object_t hb_filter_chroma_smooth_hip =
     .short_name        = "chromasmooth",
     .settings          = NULL,
     .init              = chroma_smooth_hip_init,
-    .work              = blur_hip_work,
-    .close             = blur_hip_close,
+    .work              = hbhip_host_simple_filter_work,
+    .close             = hbhip_host_simple_close,
     .settings_template = chroma_smooth_hip_template,
 };
 
 static int blur_hip_init_common(hb_filter_object_t *filter, hb_filter_init_t *init,
                                 int first_plane, double max_strength, int chroma_only)
 {
-    hb_filter_private_t *pv = calloc(1, sizeof(*pv));
-    if (pv == NULL) return -1;
-    filter->private_data = pv;
-    pv->input = *init;
-    pv->dev_io = hbhip_host_dev_io(init);
-
-    const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(init->pix_fmt);
-    if (desc == NULL) goto fail;
+    const AVPixFmtDescriptor *desc;
+    hb_filter_private_t *pv = hbhip_host_simple_begin(filter, init, sizeof(*pv), &desc);
+    if (pv == NULL || desc == NULL) goto fail;
 
     static const char *pfx[3] = { "y", "cb", "cr" };
     double strength[3] = { -1, -1, -1 };
@@ -104,19 +94,14 @@ static int blur_hip_init_common(hb_filter_object_t *filter, hb_filter_init_t *in
     if (ctx == NULL) goto fail;
     int rc = chroma_only
         ? hbhip_chroma_smooth_create(ctx, &pv->par, init->geometry.width, init->geometry.height,
-                                     desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev)
+                                     desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev)
         : hbhip_unsharp_create(ctx, &pv->par, init->geometry.width, init->geometry.height,
-                               desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->dev);
-    if (rc != HBHIP_OK)
-    {
-        hb_error("%s(hip): %s", filter->short_name, hbhip_strerror(rc));
-        goto fail;
-    }
-    pv->output = *init;
+                               desc->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev);
+    if (rc != HBHIP_OK) { hbhip_host_simple_fail(filter, rc); return -1; }
+    pv->s.output = *init;
     return 0;
-fail:
-    free(pv);
-    filter->private_data = NULL;
+fail:                                                      /* (no message) */
+    hbhip_host_simple_close(filter);
     return -1;
 }
 
@@ -128,19 +113,4 @@ static int unsharp_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 static int chroma_smooth_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
 {
     return blur_hip_init_common(filter, init, 1, 3.0, 1);   /* chroma_smooth.c:247-248 */
-}
-
-static void blur_hip_close(hb_filter_object_t *filter)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    if (pv == NULL) return;
-    hbhip_host_simple_destroy(pv->dev);
-    free(pv);
-    filter->private_data = NULL;
-}
-
-static int blur_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out)
-{
-    hb_filter_private_t *pv = filter->private_data;
-    return hbhip_host_simple_work(pv->dev, &pv->output, filter->short_name, pv->dev_io, buf_in, buf_out);
 }

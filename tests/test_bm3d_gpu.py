@@ -9,6 +9,7 @@ import pytest
 
 import bm3d_cases as bc
 import bm3d_model as bm
+from burst_util import bursts
 from handbrake_amd import hbrt, hip, synth
 
 pytestmark = pytest.mark.gpu
@@ -68,45 +69,8 @@ def _make(ctx, sigma, w, h, depth=8, lcw=1, lch=1):
 
 
 def _bursts(sigma, frames, sizes, pads=(0,), depth=8):
-    """frames through one filter in device-resident bursts of the given sizes (one process_dev call each); input i's rows
-    are padded by pads[i % len(pads)] samples, so that pitches mix inside a burst"""
-    import torch
     h, w = frames[0][0].shape
-    wide = depth > 8
-    tdt = torch.int16 if wide else torch.uint8
-    ctx = hip.Ctx(0)
-    flt = _make(ctx, sigma, w, h, depth)
-    out = []
-    try:
-        at = 0
-        for n in sizes:
-            part = frames[at:at + n]
-            dev_in, keep = [], []
-            for i, f in enumerate(part):
-                pad = pads[(at + i) % len(pads)]
-                planes = []
-                for p in f:
-                    full = torch.zeros((p.shape[0], p.shape[1] + pad), dtype=tdt, device="cuda")
-                    full[:, :p.shape[1]] = torch.from_numpy(p.view(np.int16) if wide else p).cuda()
-                    keep.append(full)
-                    planes.append(full[:, :p.shape[1]])
-                dev_in.append(planes)
-            at += n
-            outs = [[torch.full(p.shape, 7, dtype=tdt, device="cuda") for p in f] for f in part]
-            torch.cuda.synchronize()
-            arr_in = (hip.DevFrame * n)(*[hip.dev_frame(f) for f in dev_in])
-            arr_out = (hip.DevFrame * n)(*[hip.dev_frame(o) for o in outs])
-            assert flt.process_dev(arr_in, 0, arr_out) == n
-            ctx.sync()
-            conv = (lambda t: t.cpu().numpy().view(np.uint16)) if wide else (lambda t: t.cpu().numpy())
-            out += [[conv(p) for p in o] for o in outs]
-            for f, d in zip(part, dev_in):                               # out of place: the inputs are untouched
-                for c in range(3):
-                    np.testing.assert_array_equal(conv(d[c]), f[c])
-        return out
-    finally:
-        flt.close()
-        ctx.close()
+    return bursts(lambda ctx: _make(ctx, sigma, w, h, depth), frames, sizes, pads=pads, depth=depth)
 
 
 @pytest.mark.parametrize("depth", [8, 10])

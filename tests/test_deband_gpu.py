@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import deband_model as dm
+from burst_util import bursts
 from handbrake_amd import hbrt, hip, synth
 
 pytestmark = pytest.mark.gpu
@@ -85,50 +86,11 @@ def _make(ctx, settings, w, h, depth=8):
 
 
 def _bursts(settings, frames, sizes, kernel=0, pads=(0,), depth=8):
-    """frames through one filter in device-resident bursts of the given sizes (one process_dev call each); input i's
-    rows are padded by pads[i % len(pads)] samples, so that pitches mix inside a burst.  None: the filter refuses `kernel`"""
-    import torch
+    """burst_util.bursts through the deband filter with hbhip_deband_set_kernel(kernel).  None: the filter refuses `kernel`"""
     h, w = frames[0][0].shape
-    wide = depth > 8
-    assert frames[0][0].dtype == (np.uint16 if wide else np.uint8)
-    tdt = torch.int16 if wide else torch.uint8
-    ctx = hip.Ctx(0)
-    flt = _make(ctx, settings, w, h, depth)
-    out = []
-    try:
-        hip.lib().hbhip_deband_set_kernel.argtypes = [C.c_void_p, C.c_int]
-        rc = hip.lib().hbhip_deband_set_kernel(flt.h, kernel)
-        if rc != 0:
-            return None
-        at = 0
-        for n in sizes:
-            part = frames[at:at + n]
-            dev_in, keep = [], []
-            for i, f in enumerate(part):
-                pad = pads[(at + i) % len(pads)]
-                planes = []
-                for p in f:
-                    full = torch.zeros((p.shape[0], p.shape[1] + pad), dtype=tdt, device="cuda")
-                    full[:, :p.shape[1]] = torch.from_numpy(p.view(np.int16) if wide else p).cuda()
-                    keep.append(full)
-                    planes.append(full[:, :p.shape[1]])
-                dev_in.append(planes)
-            at += n
-            outs = [[torch.full(p.shape, 7, dtype=tdt, device="cuda") for p in f] for f in part]
-            torch.cuda.synchronize()
-            arr_in = (hip.DevFrame * n)(*[hip.dev_frame(f) for f in dev_in])
-            arr_out = (hip.DevFrame * n)(*[hip.dev_frame(o) for o in outs])
-            assert flt.process_dev(arr_in, 0, arr_out) == n
-            ctx.sync()
-            conv = (lambda t: t.cpu().numpy().view(np.uint16)) if wide else (lambda t: t.cpu().numpy())
-            out += [[conv(p) for p in o] for o in outs]
-            for f, d in zip(part, dev_in):                               # out of place: the inputs are untouched
-                for c in range(3):
-                    np.testing.assert_array_equal(conv(d[c]), f[c])
-        return out
-    finally:
-        flt.close()
-        ctx.close()
+    hip.lib().hbhip_deband_set_kernel.argtypes = [C.c_void_p, C.c_int]
+    return bursts(lambda ctx: _make(ctx, settings, w, h, depth), frames, sizes, pads=pads, depth=depth,
+                  setup=lambda flt: hip.lib().hbhip_deband_set_kernel(flt.h, kernel))
 
 
 @pytest.mark.parametrize("rng", [16, 0, 1, -1, -16, 127, 128, 200, 5000, 1 << 30])

@@ -11,6 +11,7 @@ import pytest
 
 import deblock_cases as dc
 import deblock_model as dm
+from burst_util import bursts
 from handbrake_amd import hbrt, hip, synth
 
 pytestmark = pytest.mark.gpu
@@ -95,50 +96,17 @@ def _make(ctx, settings, w, h, depth=8, sub="2x2"):
                        ctx.h, C.byref(p), w, h, depth, lcw, lch)
 
 
+def _set_warmup(flt, warmup):
+    hip.lib().hbhip_deblock_set_warmup.argtypes = [C.c_void_p, C.c_int]
+    assert hip.lib().hbhip_deblock_set_warmup(flt.h, warmup) == 0
+    return 0
+
+
 def _bursts(settings, frames, sizes, warmup=None, pads=(0,), depth=8, sub="2x2"):
-    """frames through one filter in device-resident bursts of the given sizes (one process_dev call each); input i's
-    rows are padded by pads[i % len(pads)] samples, so that pitches mix inside a burst"""
-    import torch
+    """burst_util.bursts through the deblock filter, with hbhip_deblock_set_warmup(warmup) where one is given"""
     h, w = frames[0][0].shape
-    wide = depth > 8
-    assert frames[0][0].dtype == (np.uint16 if wide else np.uint8)
-    tdt = torch.int16 if wide else torch.uint8
-    ctx = hip.Ctx(0)
-    flt = _make(ctx, settings, w, h, depth, sub)
-    out = []
-    try:
-        if warmup is not None:
-            hip.lib().hbhip_deblock_set_warmup.argtypes = [C.c_void_p, C.c_int]
-            assert hip.lib().hbhip_deblock_set_warmup(flt.h, warmup) == 0
-        at = 0
-        for n in sizes:
-            part = frames[at:at + n]
-            dev_in, keep = [], []
-            for i, f in enumerate(part):
-                pad = pads[(at + i) % len(pads)]
-                planes = []
-                for p in f:
-                    full = torch.zeros((p.shape[0], p.shape[1] + pad), dtype=tdt, device="cuda")
-                    full[:, :p.shape[1]] = torch.from_numpy(np.array(p).view(np.int16) if wide else np.array(p)).cuda()
-                    keep.append(full)
-                    planes.append(full[:, :p.shape[1]])
-                dev_in.append(planes)
-            at += n
-            outs = [[torch.full(p.shape, 7, dtype=tdt, device="cuda") for p in f] for f in part]
-            torch.cuda.synchronize()
-            arr_in = (hip.DevFrame * n)(*[hip.dev_frame(f) for f in dev_in])
-            arr_out = (hip.DevFrame * n)(*[hip.dev_frame(o) for o in outs])
-            assert flt.process_dev(arr_in, 0, arr_out) == n
-            ctx.sync()
-            conv = (lambda t: t.cpu().numpy().view(np.uint16)) if wide else (lambda t: t.cpu().numpy())
-            out += [[conv(p) for p in o] for o in outs]
-            for f, d in zip(part, dev_in):                               # out of place: the inputs are untouched
-                for c in range(3):
-                    np.testing.assert_array_equal(conv(d[c]), f[c])
-        return out
-    finally:
-        flt.close()
-        ctx.close()
+    return bursts(lambda ctx: _make(ctx, settings, w, h, depth, sub), frames, sizes, pads=pads, depth=depth,
+                  setup=None if warmup is None else (lambda flt: _set_warmup(flt, warmup)))
 
 
 @functools.lru_cache(maxsize=None)
