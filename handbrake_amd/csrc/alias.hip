@@ -571,6 +571,7 @@ __global__ __launch_bounds__(256) void scale8_up_kernel(ScaleBatch8 B)
     __shared__ uint32_t s_src[SU_MAXR][SU_SRC_DW];
     __shared__ __attribute__((aligned(16))) uint32_t s_h[SU_PAIRS][SU_TW];
     __shared__ uint4 s_v[TH];
+    __shared__ int s_vo[TH];
     const int f = (int)blockIdx.z / 3, pl = (int)blockIdx.z - 3 * f;
     const ScalePlane8 &P = B.p[pl];
     if (!P.active) return;
@@ -587,10 +588,15 @@ __global__ __launch_bounds__(256) void scale8_up_kernel(ScaleBatch8 B)
     const int bxh = P.bx[xh];
     const uint32_t hc01 = P.qx[3 * (size_t)xh], hc23 = P.qx[3 * (size_t)xh + 1], hc45 = P.qx[3 * (size_t)xh + 2];
     // the vertical pass's rows: first tapped row and the three coefficient pairs of the tile's output rows
+    // in the form the row's window wants: an even first row takes (c0, c1) (c2, c3) (c4, c5) over three row pairs, an odd one
+    // (0, c0) (c1, c2) (c3, c4) (c5, 0) over four - shifted here once, by one lane per row, not by every thread of every row
     if (t < TH && y0 + t <= ye)
     {
-        const int y = y0 + t;
-        s_v[t] = make_uint4((uint32_t)(P.by[y] - rmin), P.qy[3 * (size_t)y], P.qy[3 * (size_t)y + 1], P.qy[3 * (size_t)y + 2]);
+        const int y = y0 + t, ob = P.by[y] - rmin;
+        const uint32_t c01 = P.qy[3 * (size_t)y], c23 = P.qy[3 * (size_t)y + 1], c45 = P.qy[3 * (size_t)y + 2];
+        s_vo[t] = ob;
+        s_v[t] = (ob & 1) ? make_uint4(c01 << 16, (c01 >> 16) | (c23 << 16), (c23 >> 16) | (c45 << 16), c45 >> 16)
+                          : make_uint4(c01, c23, c45, 0u);
     }
     {
         const uint8_t *src = B.src[f][pl];
@@ -642,47 +648,66 @@ __global__ __launch_bounds__(256) void scale8_up_kernel(ScaleBatch8 B)
         const uint32_t sel01 = (uint32_t)ob | 0x0c000c00u | ((uint32_t)(ob + 1) << 16);
         const uint32_t sel23 = (uint32_t)(ob + 2) | 0x0c000c00u | ((uint32_t)(ob + 3) << 16);
         const uint32_t c01 = hc01, c23 = hc23, c45 = hc45;
-        uint16_t *hp = reinterpret_cast<uint16_t *>(&s_h[0][0]) + 2 * t;
-        for (int rr = 0; rr < nr; rr++)
-        {
-            const uint32_t d0 = s_src[rr][dq], d1 = s_src[rr][dq + 1], d2 = s_src[rr][dq + 2];
-            int s = dot2(__builtin_amdgcn_perm(d1, d0, sel01), c01, 32);             // + 32: the rounding of (s + 32) >> 6
+        // Two staged rows a trip, one dword of s_h a trip.  The 16-bit plane between the passes, biased as zimg holds it, is
+        // clamp(s >> 6, 0, 65535) - 32768 = clamp((s - (32768 << 6)) >> 6, -32768, 32767): the sums start at the bias and
+        // the rounding, and v_cvt_pk_i16_i32 clamps and packs both rows at once.  The trip count is a compile-time bound
+        // with a uniform exit, so the LDS offsets are immediates; an odd nr computes one half-row from a row nothing
+        // staged, which no output row taps (a window that ends on row nr - 1 and starts odd multiplies it by zero).
+        constexpr int HB = 32 - (32768 << 6);                        // + 32: the rounding of (s + 32) >> 6
+        const uint32_t *sp = &s_src[0][dq];
+        uint32_t *hp = &s_h[0][t];
+        const int npair = (nr + 1) >> 1;
+        auto hrow = [&](const uint32_t *r) {
+            const uint32_t d0 = r[0], d1 = r[1], d2 = r[2];
+            int s = dot2(__builtin_amdgcn_perm(d1, d0, sel01), c01, HB);
             s = dot2(__builtin_amdgcn_perm(d1, d0, sel23), c23, s);
-            s = dot2(__builtin_amdgcn_perm(d2, d1, sel01), c45, s);
-            const int h = min(max(s >> 6, 0), 65535);                // the 16-bit plane between the passes
-            hp[(size_t)(rr >> 1) * (2 * SU_TW) + (rr & 1)] = (uint16_t)(h ^ 0x8000);    // biased, as zimg holds it
+            return dot2(__builtin_amdgcn_perm(d2, d1, sel01), c45, s) >> 6;
+        };
+#pragma unroll
+        for (int p = 0; p < SU_MAXR / 2; p++)
+        {
+            if (p >= npair) break;
+            const int ha = hrow(sp + (2 * p) * SU_SRC_DW), hb = hrow(sp + (2 * p + 1) * SU_SRC_DW);
+            hp[p * SU_TW] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_pk_i16(ha, hb));
         }
     }
     __syncthreads();
     const int xq = x0 + 4 * lane;
     if (xq >= P.dw) return;
-    for (int y = y0 + wave; y <= ye; y += 4)
+    // the row pointer and the store's shape are the wave's: a tile away from the right edge of a plane whose rows
+    // start on dwords stores dwords, with nothing decided per row
+    uint8_t *drow = B.dst[f][pl] + (size_t)(y0 + wave) * B.dpitch[pl];
+    const size_t dstep = 4 * (size_t)B.dpitch[pl];
+    const bool dwords = ((((uintptr_t)B.dst[f][pl]) | (uintptr_t)B.dpitch[pl]) & 3) == 0 && xq + 3 < P.dw;
+    const int nrow = ye - y0 + 1;
+    const uint4 *hq0 = reinterpret_cast<const uint4 *>(&s_h[0][4 * lane]);
+#pragma unroll
+    for (int k = 0; k < TH / 4; k++)
     {
-        const uint4 vt = s_v[y - y0];
-        const int ob = __builtin_amdgcn_readfirstlane((int)vt.x);
-        const uint32_t c01 = vt.y, c23 = vt.z, c45 = vt.w;
+        const int r = wave + 4 * k;
+        if (r >= nrow) break;
+        const uint4 cv = s_v[r];
+        const int ob = __builtin_amdgcn_readfirstlane(s_vo[r]);
         // fx_to8(fx_round14(acc)) = clamp((((acc + 8192) >> 14) + 32768 + 128) >> 8, 0, 255) with the 16-bit clamp folded in
         // (a value outside 0 .. 65535 lands outside 0 .. 255 either way) = clamp((acc + K) >> 22, 0, 255): the sums start at K
         constexpr int K = 8192 + (32768 << 14) + (128 << 14);       // |acc| < 2^30, so acc + K stays inside int
         int acc[4] = {K, K, K, K};
-        const uint4 *hq = reinterpret_cast<const uint4 *>(&s_h[ob >> 1][4 * lane]);
+        const uint4 *hq = hq0 + (size_t)(ob >> 1) * (SU_TW / 4);
         auto tap = [&](int pair_row, uint32_t cpair) {
             const uint4 q = hq[(size_t)pair_row * (SU_TW / 4)];
             acc[0] = dot2(q.x, cpair, acc[0]); acc[1] = dot2(q.y, cpair, acc[1]);
             acc[2] = dot2(q.z, cpair, acc[2]); acc[3] = dot2(q.w, cpair, acc[3]);
         };
-        if (!(ob & 1)) { tap(0, c01); tap(1, c23); tap(2, c45); }
-        else
-        {
-            // rows ob .. ob + 5 against the pairs (ob - 1, ob) (ob + 1, ob + 2) (ob + 3, ob + 4) (ob + 5, ob + 6)
-            tap(0, c01 << 16); tap(1, (c01 >> 16) | (c23 << 16)); tap(2, (c23 >> 16) | (c45 << 16)); tap(3, c45 >> 16);
-        }
-        uint32_t out = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) out |= (uint32_t)min(max(acc[k] >> 22, 0), 255) << (8 * k);
-        uint8_t *d = B.dst[f][pl] + (size_t)y * B.dpitch[pl] + xq;
-        if (xq + 3 < P.dw && (((uintptr_t)d) & 3) == 0) *reinterpret_cast<uint32_t *>(d) = out;
-        else for (int k = 0; k < 4 && xq + k < P.dw; k++) d[k] = (uint8_t)(out >> (8 * k));
+        tap(0, cv.x); tap(1, cv.y); tap(2, cv.z);
+        if (ob & 1) tap(3, cv.w);                                    // an odd first row: a fourth pair, (c5, 0)
+        // v_ashr_pk_u8_i32: two sums shifted, clamped to a byte and packed into the low half of its result - the HIGH half
+        // is not part of the result, so the two halves are joined by a v_perm that reads low halves only (never OR-ed)
+        const uint32_t lo = __builtin_amdgcn_ashr_pk_u8_i32((uint32_t)acc[0], (uint32_t)acc[1], 22);
+        const uint32_t hi = __builtin_amdgcn_ashr_pk_u8_i32((uint32_t)acc[2], (uint32_t)acc[3], 22);
+        const uint32_t out = __builtin_amdgcn_perm(hi, lo, 0x05040100u);
+        if (dwords) *reinterpret_cast<uint32_t *>(drow + xq) = out;
+        else for (int j = 0; j < 4 && xq + j < P.dw; j++) drow[xq + j] = (uint8_t)(out >> (8 * j));
+        drow += dstep;
     }
 }
 
