@@ -2,7 +2,7 @@
 // decomb.c:324-331), first correct form: one thread per sample and pass, no LDS tiling, the
 // in-place lattice pass walked serially per row.  The tuned 8-bit kernels of eedi2.hip lean on byte
 // packing (packed SAD, 4 samples per dword) and do not carry over; this file follows the pinned
-// restatement oracle/eedi2_16_oracle.c pass by pass instead.
+// restatement oracle/eedi2_oracle.c (its uint16 instantiation) pass by pass instead.
 //
 // What the reference does differently above 8 bits (all marked "16:" in the oracle): thresholds shifted
 // by depth-8 or typed `pixel` = uint16 so that they wrap at 16 bits, limlut << (depth-8), PEAK / NEUTRAL

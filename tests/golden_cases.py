@@ -142,7 +142,7 @@ CASES = {
                                           orc=[("nlmeans", [nlm(prefilter=2049, depth=12),
                                                             nlm(origin_tune=0.8, prefilter=1028, depth=12),
                                                             nlm(origin_tune=0.8, prefilter=800, depth=12)])]),
-    # 10 / 12-bit EEDI2 (oracle eedi2_16_oracle.c, kernels csrc/eedi2_16.hip)
+    # 10 / 12-bit EEDI2 (oracle eedi2_oracle.c, its uint16 instantiation, kernels csrc/eedi2_16.hip)
     "decomb_eedi2_bob_10bit_128x64": dict(model="interlaced", w=128, h=64, n=3, depth=10,
                                           chain=[("hb_filter_decomb", "mode=31")],
                                           hip=[("hb_filter_decomb_hip", "mode=31")],

@@ -329,33 +329,35 @@ def _planes3(frame):
     return keep, ptrs, strides
 
 
-class OrcEedi2:
-    """Stateful oracle EEDI2 (the edge mask carries over between runs)."""
+class _OrcEedi2Base:
+    """Stateful oracle EEDI2 (the edge mask carries over between runs): oracle/eedi2_oracle.c, whose passes
+    (eedi2_oracle_px.h) are instantiated for uint8 and for uint16 samples.  Strides are passed in samples."""
+    _prefix = _ctype = _pad = None          # exported prefix, sample type, input padding: set by the two classes below
 
-    def __init__(self, width, height, magnitude=10, variance=20, laplacian=20, dilation=4, erosion=2,
+    def __init__(self, width, height, depth, magnitude=10, variance=20, laplacian=20, dilation=4, erosion=2,
                  noise=50, search=24, postproc=1):
         lib = oracle()
-        lib.orc_eedi2_new.restype = C.c_void_p
-        lib.orc_eedi2_new.argtypes = [C.c_int, C.c_int, C.POINTER(Eedi2Params)]
-        lib.orc_eedi2_run.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_uint8)), C.POINTER(C.c_int), C.c_int]
-        lib.orc_eedi2_run_partial.argtypes = lib.orc_eedi2_run.argtypes + [C.c_int]
-        lib.orc_eedi2_plane.restype = C.POINTER(C.c_uint8)
-        lib.orc_eedi2_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        lib.orc_eedi2_free.argtypes = [C.c_void_p]
+        fn = {n: getattr(lib, self._prefix + n) for n in ("new", "run_partial", "plane", "free")}
+        depth_arg = [depth] if self._ctype is C.c_uint16 else []        # the exported 8-bit `new` takes no depth
+        fn["new"].restype = C.c_void_p
+        fn["new"].argtypes = [C.c_int, C.c_int] + [C.c_int] * len(depth_arg) + [C.POINTER(Eedi2Params)]
+        fn["run_partial"].argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int]
+        fn["plane"].restype = C.POINTER(self._ctype)
+        fn["plane"].argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        fn["free"].argtypes = [C.c_void_p]
         p = Eedi2Params(magnitude, variance, laplacian, dilation, erosion, noise, search, postproc)
-        self.lib, self.w, self.h = lib, width, height
-        self.e = lib.orc_eedi2_new(width, height, C.byref(p))
+        self.fn, self.w, self.h = fn, width, height
+        self.e = fn["new"](width, height, *depth_arg, C.byref(p))
 
     def run(self, frame, tff, npasses=None):
-        keep, ptrs, strides = _planes3(frame)
-        if npasses is None:
-            self.lib.orc_eedi2_run(self.e, ptrs, strides, int(tff))
-        else:
-            self.lib.orc_eedi2_run_partial(self.e, ptrs, strides, int(tff), npasses)
+        keep = [self._pad(p) for p in frame]
+        ptrs = (C.c_void_p * 3)(*[k.ctypes.data for k in keep])
+        strides = (C.c_int * 3)(*[k.strides[0] // k.itemsize for k in keep])
+        self.fn["run_partial"](self.e, ptrs, strides, int(tff), 1000 if npasses is None else npasses)
 
     def plane(self, buffer, plane):
         st, ht = C.c_int(), C.c_int()
-        ptr = self.lib.orc_eedi2_plane(self.e, buffer, plane, C.byref(st), C.byref(ht))
+        ptr = self.fn["plane"](self.e, buffer, plane, C.byref(st), C.byref(ht))
         return np.ctypeslib.as_array(ptr, shape=(ht.value, st.value)).copy()
 
     def guess(self):
@@ -368,8 +370,21 @@ class OrcEedi2:
 
     def close(self):
         if self.e:
-            self.lib.orc_eedi2_free(self.e)
+            self.fn["free"](self.e)
             self.e = None
+
+
+class OrcEedi2(_OrcEedi2Base):
+    """The 8-bit instantiation; planes are uint8."""
+    _prefix, _ctype, _pad = "orc_eedi2_", C.c_uint8, staticmethod(padded)
+
+    def __init__(self, width, height, *args, **kw):
+        super().__init__(width, height, 8, *args, **kw)
+
+
+class OrcEedi2_16(_OrcEedi2Base):
+    """The 16-bit instantiation; planes are uint16, depth 10 / 12."""
+    _prefix, _ctype, _pad = "orc_eedi2_16_", C.c_uint16, staticmethod(padded16)
 
 
 class RefEedi2:
@@ -685,39 +700,6 @@ def orc_bwdif_plane(prev, cur, nxt, parity, tff, field_end, depth=8):
     fn(p.ctypes.data, c.ctypes.data, n.ctypes.data, c.strides[0], w, h, dst.ctypes.data, dst.strides[0],
        int(parity), int(tff), int(field_end), c.itemsize, depth)
     return dst
-
-
-class OrcEedi2_16:
-    """The 16-bit EEDI2 restatement (oracle/eedi2_16_oracle.c); planes are uint16, depth 10 / 12."""
-
-    def __init__(self, width, height, depth, magnitude=10, variance=20, laplacian=20, dilation=4, erosion=2,
-                 noise=50, search=24, postproc=1):
-        lib = oracle()
-        lib.orc_eedi2_16_new.restype = C.c_void_p
-        lib.orc_eedi2_16_new.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(Eedi2Params)]
-        lib.orc_eedi2_16_run_partial.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int]
-        lib.orc_eedi2_16_plane.restype = C.POINTER(C.c_uint16)
-        lib.orc_eedi2_16_plane.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        lib.orc_eedi2_16_free.argtypes = [C.c_void_p]
-        p = Eedi2Params(magnitude, variance, laplacian, dilation, erosion, noise, search, postproc)
-        self.lib, self.w, self.h = lib, width, height
-        self.e = lib.orc_eedi2_16_new(width, height, depth, C.byref(p))
-
-    def run(self, frame, tff, npasses=1000):
-        keep = [padded16(p) for p in frame]
-        ptrs = (C.c_void_p * 3)(*[k.ctypes.data for k in keep])
-        strides = (C.c_int * 3)(*[k.strides[0] // 2 for k in keep])        # samples
-        self.lib.orc_eedi2_16_run_partial(self.e, ptrs, strides, int(tff), npasses)
-
-    def plane(self, buffer, plane):
-        st, ht = C.c_int(), C.c_int()
-        ptr = self.lib.orc_eedi2_16_plane(self.e, buffer, plane, C.byref(st), C.byref(ht))
-        return np.ctypeslib.as_array(ptr, shape=(ht.value, st.value)).copy()
-
-    def close(self):
-        if self.e:
-            self.lib.orc_eedi2_16_free(self.e)
-            self.e = None
 
 
 class RefEedi2Fmt:

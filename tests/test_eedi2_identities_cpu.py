@@ -351,3 +351,30 @@ def test_edge_mask_laplacian_as_two_unsigned_sads():
     sad = lambda a, b, acc: np.abs(a.astype(np.uint32).astype(np.int64) - b.astype(np.uint32).astype(np.int64)) + acc
     got = sad(c0 + c2, 2 * c1, sad(cs - c1, 2 * c1, 0))
     assert np.array_equal(want, got)
+
+
+def test_oracle_depth_constants_belong_to_the_object(built):
+    """The plain-C oracle the kernels are held to (oracle/eedi2_oracle.c) keeps peak, neutral, shift and the scaled
+    limlut in each object: a 10-bit and a 12-bit object run in turn, field by field, must each leave every scratch
+    plane as the same object type leaves it when it runs alone on the same inputs."""
+    from handbrake_amd import synth
+    import oracle_lib as ol
+    w, h, fields = 128, 72, (1, 0, 1)
+    frames = {d: synth.stream("corners", w, h, len(fields), depth=d) for d in (10, 12)}
+    mixed = {d: ol.OrcEedi2_16(w, h, d, postproc=3) for d in (10, 12)}
+    alone = {d: ol.OrcEedi2_16(w, h, d, postproc=3) for d in (10, 12)}
+    try:
+        for d in (10, 12):
+            for fr, tff in zip(frames[d], fields):
+                alone[d].run(fr, tff)
+        for i, tff in enumerate(fields):
+            for d in (10, 12):
+                mixed[d].run(frames[d][i], tff)
+        for d in (10, 12):
+            for b in range(9):
+                for c in range(3):
+                    np.testing.assert_array_equal(mixed[d].plane(b, c), alone[d].plane(b, c),
+                                                  err_msg=f"depth {d} {ol.EEDI2_BUFFERS[b]} plane {c}")
+    finally:
+        for o in list(mixed.values()) + list(alone.values()):
+            o.close()

@@ -259,7 +259,7 @@ def test_eedi2_corner_postprocessing_matches_reference(built, w, h, postproc):
     ("mode=8:postproc=2", dict(postproc=2), "corners"),
     ("mode=8:postproc=3", dict(postproc=3), "corners")])
 def test_eedi2_16bit_every_scratch_buffer_matches_reference(built, depth, w, h, settings, par, model):
-    """The 16-bit restatement (oracle/eedi2_16_oracle.c) against the reference's _16 template functions:
+    """The 16-bit restatement (oracle/eedi2_oracle.c, the uint16 instantiation) against the reference's _16 template functions:
     all nine scratch frames, three planes, consecutive stateful runs.  Groundwork - the HIP EEDI2
     passes are 8-bit only so far.  postproc 2/3 plane-serial, as for 8 bits."""
     from handbrake_amd import hbrt
