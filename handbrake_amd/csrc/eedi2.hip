@@ -33,6 +33,7 @@
 // from chunk to chunk.
 #include "eedi2_common.h"
 #include "eedi2_vote.h"
+#include "eedi2_dirmap_vote.h"
 #include "eedi2_dense.h"
 #include "eedi2_engine.h"
 #include "eedi2_mask_cells.h"
@@ -1111,7 +1112,7 @@ __device__ __forceinline__ int dir_map_px(int u0, int u1, int u2, int c0, int c1
     vote1(v0, mid, lim, sum, count); vote1(v1, mid, lim, sum, count); vote1(v2, mid, lim, sum, count);
     vote1(v3, mid, lim, sum, count); vote1(v4, mid, lim, sum, count); vote1(v5, mid, lim, sum, count);
     vote1(v6, mid, lim, sum, count); vote1(v7, mid, lim, sum, count); vote1(v8, mid, lim, sum, count);
-    const int val = vote_avg(sum + mid, count + 1);              // (int)((float)(sum + mid) / (float)(count + 1) + 0.5f)
+    const int val = dmv_vote_avg(sum + mid, count + 1);          // (int)((float)(sum + mid) / (float)(count + 1) + 0.5f)
     if (expand) return count >= 5 ? (val & 0xff) : c1;
     if (count < 4 || (count < 5 && c1 == PEAK)) return PEAK;
     return val & 0xff;
@@ -1144,99 +1145,18 @@ __device__ __forceinline__ u16x2 limlut2(u16x2 i)
 // two bytes of the 8-byte window {hi, lo} as the halves of a dword (v_perm_b32; selector bytes: 0-3 = lo, 4-7 = hi, 12 = 0)
 #define PK_BYTES(hi, lo, a, b) __builtin_amdgcn_perm((hi), (lo), 0x0c000c00u | ((uint32_t)(b) << 16) | (uint32_t)(a))
 
-// The two pixels at columns k and k + 1 of a thread's dword (k = 0 or 2; windows wu / wc / wd = rows above, own, below as
-// the bytes x-4 .. x+7, rows that do not count - first / last rows of the _2x forms - already all 0xff).
-// Returns the pass's values for both (low byte of each half): filter_dir_map :649-707 (expand == 0) or expand_dir_map
-// :722-773 (expand != 0; the caller only takes them for pixels the pass works on).
-template <int K>
-__device__ __forceinline__ uint32_t dir_map_pair(const Win12 &wu, const Win12 &wc, const Win12 &wd, int expand)
+// eedi2_filter_dir_map's vote itself, for the four pixels of a thread's dword at once: dir_map_quad, eedi2_dirmap_vote.h
+// (what the pixel pairs (0, 1) and (2, 3) share - the unpacked rows, the peaks, the sorted columns - is made once).
+template <int PAIRS>
+__device__ __forceinline__ uint32_t dir_map_quad(const Win12 &wu, const Win12 &wc, const Win12 &wd)
 {
-    // slot s of pixel k is byte k - 1 + s % 3 of its row: the pairs (k-1, k), (k, k+1), (k+1, k+2); window byte index = column + 4
-    u16x2 v[9];
-    {
-        const Win12 *rows[3] = { &wu, &wc, &wd };
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-        {
-            const uint32_t w0 = rows[r]->w0, w1 = rows[r]->w1, w2 = rows[r]->w2;
-            if (K == 0)
-            {
-                v[3 * r + 0] = pk(PK_BYTES(w1, w0, 3, 4));            // columns -1, 0
-                v[3 * r + 1] = pk(PK_BYTES(w1, w0, 4, 5));            // 0, 1
-                v[3 * r + 2] = pk(PK_BYTES(w1, w0, 5, 6));            // 1, 2
-            }
-            else
-            {
-                v[3 * r + 0] = pk(PK_BYTES(w1, w0, 5, 6));            // 1, 2
-                v[3 * r + 1] = pk(PK_BYTES(w1, w0, 6, 7));            // 2, 3
-                v[3 * r + 2] = pk(PK_BYTES(w2, w1, 3, 4));            // 3, 4
-            }
-        }
-    }
-    const u16x2 c1 = v[4];
-    // absent slots: 1 per half that holds a peak (a pixel expand works on has a peak in its centre: left out as :739-746
-    // leave it out), the value pushed up to PK_ABSENT
-    u16x2 a[9];
-    uint32_t absent = 0;
-#pragma unroll
-    for (int i = 0; i < 9; i++)
-    {
-        a[i] = (u16x2)((v[i] + pk1(1)) >> 8);
-        absent += un(a[i]);
-        v[i] = v[i] + a[i] * pk1(PK_ABSENT_HI);
-    }
-    // midpoint of the n = 9 - absent present values (mid9's selection with masks): n <= 5 <=> absent >= 4, n <= 7 <=> absent >= 2
-    u16x2 s0 = v[0], s1 = v[1], s2 = v[2], s3 = v[3], s4 = v[4], s5 = v[5], s6 = v[6], s7 = v[7], s8 = v[8];
-    cswap2(s0, s3); cswap2(s1, s7); cswap2(s2, s5); cswap2(s4, s8);
-    cswap2(s0, s7); cswap2(s2, s4); cswap2(s3, s8); cswap2(s5, s6);
-    cswap2(s0, s2); cswap2(s1, s3); cswap2(s4, s5); cswap2(s7, s8);
-    cswap2(s1, s4); cswap2(s3, s6); cswap2(s5, s7);
-    cswap2(s0, s1); cswap2(s2, s4); cswap2(s3, s5); cswap2(s6, s8);
-    cswap2(s2, s3); cswap2(s4, s5); cswap2(s6, s7);
-    cswap2(s1, s2); cswap2(s3, s4); cswap2(s5, s6);
-    const u16x2 ab = pk(absent), one = pk1(1), zero = pk1(0);
-    const uint32_t m5 = un(zero - pk_lt(pk1(3), ab));
-    const uint32_t m7 = un(zero - pk_lt(one, ab));
-    const uint32_t modd = un((ab & one) - one);                        // n odd <=> absent even
-#define PK_SEL(m, x, y) (((m) & (x)) | (~(m) & (y)))                    /* v_bfi_b32 */
-    const uint32_t hi = PK_SEL(m5, un(s2), PK_SEL(m7, un(s3), un(s4)));
-    const uint32_t lo = PK_SEL(m5, un(s1), PK_SEL(m7, un(s2), un(s3)));
-    const u16x2 mid = pk(PK_SEL(modd, hi, un((u16x2)((pk(lo) + pk(hi) + one) >> 1))));
-    // the vote (:685-697): values within limlut[|mid - neutral| >> 2] of the midpoint
-    const i16x2 t = __builtin_bit_cast(i16x2, (u16x2)(mid - pk1(NEUTRAL)));
-    const u16x2 lim1 = limlut2(__builtin_bit_cast(u16x2, __builtin_elementwise_max(t, (i16x2)(-t))) >> 2) + one;
-    u16x2 sum = zero, cnt = zero;
-#pragma unroll
-    for (int i = 0; i < 9; i++)
-    {
-        const u16x2 d = __builtin_elementwise_max(v[i], mid) - __builtin_elementwise_min(v[i], mid);
-        const u16x2 in = pk_lt(d, lim1);
-        cnt += in;
-        sum += in * v[i];
-    }
-    const uint32_t sm = un((u16x2)(sum + mid)), ct = un(cnt);
-    uint32_t out = 0;
-#pragma unroll
-    for (int h = 0; h < 2; h++)
-    {
-        // too few values (:669-673 / :747): the midpoint above may be a PK_ABSENT then, so the count says nothing
-        const int n = 9 - (int)((absent >> (16 * h)) & 0xffffu);
-        const int count = n >= 4 ? (int)((ct >> (16 * h)) & 0xffffu) : 0;
-        const int val = vote_avg((int)((sm >> (16 * h)) & 0xffffu), count + 1) & 0xff;
-        const int c = (int)((un(c1) >> (16 * h)) & 0xffu);
-        int res;
-        if (expand) res = count >= 5 ? val : c;
-        else        res = (count < 4 || (count < 5 && c == PEAK)) ? PEAK : val;
-        out |= (uint32_t)res << (16 * h);
-    }
-#undef PK_SEL
-    return out;
+    return ::dir_map_quad<PAIRS>(wu.w0, wu.w1, wu.w2, wc.w0, wc.w1, wc.w2, wd.w0, wd.w1, wd.w2);
 }
 
 // In the _2x forms a thread takes the rows 2r and 2r + 1 of its dword column: the one with the parity of the rebuilt rows
 // is worked on, the other only copied (a wave per copied row spent more on finding its plane and field - scalar
 // instructions - than on its dword).
-__global__ __launch_bounds__(256) void k_dir_map4(P3 P, int step, int expand)
+__global__ __launch_bounds__(256) void k_dir_map4(P3 P, int step)
 {
     FIELD_PLANE(P);
     const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
@@ -1294,9 +1214,8 @@ __global__ __launch_bounds__(256) void k_dir_map4(P3 P, int step, int expand)
     const uint32_t m0 = *reinterpret_cast<const uint32_t *>(step == 1 ? mk : mk - (ptrdiff_t)pitch);
     const uint32_t m1 = step == 1 ? 0u : *reinterpret_cast<const uint32_t *>(mk + pitch);
     const bool up_ok = step == 1 || y > 1, dn_ok = step == 1 || y < height - 2;
-    // the pixels the pass works on, one flag byte each (:658 / :738): inside the row, on the mask, and for expand a peak
-    uint32_t work = ((ff_bytes(m0) | ff_bytes(m1)) >> 7) & bytes_in(x, 1, width - 1);
-    if (expand) work &= ff_bytes(own) >> 7;
+    // the pixels the pass works on, one flag byte each (:658): inside the row, on the mask
+    const uint32_t work = ((ff_bytes(m0) | ff_bytes(m1)) >> 7) & bytes_in(x, 1, width - 1);
     uint32_t res = own;
     if (work)
     {
@@ -1304,9 +1223,8 @@ __global__ __launch_bounds__(256) void k_dir_map4(P3 P, int step, int expand)
         const Win12 wc = ldwin(dc), wu = ldwin(dc - (ptrdiff_t)step * pitch), wd = ldwin(dc + (ptrdiff_t)step * pitch);
         const Win12 none = { 0xffffffffu, 0xffffffffu, 0xffffffffu };
         const Win12 eu = up_ok ? wu : none, ed = dn_ok ? wd : none;
-        const uint32_t p01 = dir_map_pair<0>(eu, wc, ed, expand), p23 = dir_map_pair<2>(eu, wc, ed, expand);
-        const uint32_t votes = __builtin_amdgcn_perm(p23, p01, 0x06040200u);     // the low bytes of the four halves
-        const uint32_t sel = work * 255u;
+        const uint32_t votes = dir_map_quad<3>(eu, wc, ed);
+        const uint32_t sel = (work << 8) - work;                     // 255 per flag byte
         res = (res & ~sel) | (votes & sel);
     }
     int out[4] = { (int)(res & 0xff), (int)((res >> 8) & 0xff), (int)((res >> 16) & 0xff), (int)(res >> 24) };
@@ -1631,9 +1549,8 @@ __global__ __launch_bounds__(256) void k_dir_map_fe(P3 P, uint32_t padv)
             const bool up_ok = STEP == 1 || y > 1, dn_ok = STEP == 1 || y < height - 2;
             const Win12 none = { 0xffffffffu, 0xffffffffu, 0xffffffffu };
             const Win12 wc = ldwin(dc), wu = up_ok ? ldwin(dc - (ptrdiff_t)STEP * pitch) : none, wd = dn_ok ? ldwin(dc + (ptrdiff_t)STEP * pitch) : none;
-            const uint32_t p01 = SIDE < 0 ? 0u : dir_map_pair<0>(wu, wc, wd, 0), p23 = SIDE > 0 ? 0u : dir_map_pair<2>(wu, wc, wd, 0);
-            const uint32_t votes = __builtin_amdgcn_perm(p23, p01, 0x06040200u);
-            const uint32_t sel = work * 255u;
+            const uint32_t votes = dir_map_quad<(SIDE < 0 ? 2 : SIDE > 0 ? 1 : 3)>(wu, wc, wd);
+            const uint32_t sel = (work << 8) - work;                 // 255 per flag byte
             res = (res & ~sel) | (votes & sel);
         }
         return res;
@@ -1837,7 +1754,7 @@ __global__ __launch_bounds__(256) void k_filter_map(P3 P)
 }
 
 // eedi2_mark_directions_2x's vote (:800-868) for the two pixels at columns K and K + 1 of a thread's dword (K = 0 or 2), the
-// way dir_map_pair votes: wa / wb = the half-height direction rows above and below the rebuilt row (bytes x - 4 .. x + 7), six
+// way the dir-map vote rides on pixel pairs (eedi2_dirmap_vote.h): wa / wb = the half-height direction rows above and below the rebuilt row (bytes x - 4 .. x + 7), six
 // slots, an absent one (a peak) lifted to PK_ABSENT; returns the pass's value (or PEAK) in the low byte of each half.
 template <int K>
 __device__ __forceinline__ uint32_t mark_pair(const Win12 &wa, const Win12 &wb)
@@ -3313,7 +3230,7 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
         // filter_dir_map sorts at most masked pixels, there the in-place form is ahead
         // step 2: a thread row per PAIR of rows (the rebuilt one and the copied one)
         const int trows = step == 1 ? f.height[0] : (f.height[0] + 1) / 2;             // thread rows
-        if (!expand) HBHIP_LAUNCH_ON(lc, st, name, k_dir_map4, dim3(hbhip_grid_x((f.width[0] + 255) / 256), (trows + 3) / 4, gz), blk, 0, Pv, step, expand);
+        if (!expand) HBHIP_LAUNCH_ON(lc, st, name, k_dir_map4, dim3(hbhip_grid_x((f.width[0] + 255) / 256), (trows + 3) / 4, gz), blk, 0, Pv, step);
         else
         {
             HBHIP_LAUNCH_ON(lc, st, name, k_dir_map_c, dim3(hbhip_grid_x((f.width[0] + 255) / 256), (trows + DC_ROWS - 1) / DC_ROWS, gz), blk, 0, Pv, step, expand, post);
