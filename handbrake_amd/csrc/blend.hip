@@ -16,131 +16,29 @@
 // Not reproduced: the reference's stray chroma writes one sample before the row when a
 // same-subsampling overlay hangs over the left / top edge by an odd amount (:485-505), and its
 // running past the row / plane when an overlay sticks out to the right / bottom (:74-75): writes stop
-// at the frame edge.  Biplanar (NV12 / P010) frames are refused (planar frames only).
+// at the frame edge.  The kernel bodies are in blend_body.h, shared with the biplanar (NV12 / P010LE) forms of biplanar.hip;
+// an object made by hbhip_blend_create_biplanar composites those on a staging buffer in the host picture's own layout.
 #include "hbhip_internal.h"
 
 #include <algorithm>
 #include <vector>
 
+#include "blend_body.h"
+
 namespace {
-
-struct OverlayDev
-{
-    const uint8_t *plane[4];
-    int stride[4];
-    int x, y, width, height;
-};
-
-constexpr int BL_GROUP = 8;          // overlays per launch
-struct OverlayGroup
-{
-    OverlayDev o[BL_GROUP];
-    int bx0[BL_GROUP], by0[BL_GROUP];    // blend_subsample_kernel: the first frame chroma sample the overlay touches
-};
-
-struct BlendArgs
-{
-    uint8_t *dst[3];
-    int pitch[3];
-    int width, height, cw, ch;       // frame luma and chroma dimensions
-    int wshift, hshift, shift;
-    unsigned coeff[2][2];            // chroma-location weights of the samples under one chroma sample
-};
-
-template <typename PIX> __device__ __forceinline__ PIX *row_of(uint8_t *plane, int pitch, int y)
-{
-    return reinterpret_cast<PIX *>(plane + (size_t)y * pitch);
-}
 
 // grid: overlay chroma samples (xx, yy) in the overlay's own coordinates
 template <typename PIX>
 __global__ __launch_bounds__(256) void blend_same_kernel(BlendArgs a, OverlayGroup G)
 {
-    const OverlayDev &o = G.o[blockIdx.z];
-    const int xx = blockIdx.x * blockDim.x + threadIdx.x, yy = blockIdx.y * blockDim.y + threadIdx.y;
-    const int left = o.x, top = o.y;
-    const int x0 = left < 0 ? -left : 0, y0 = top < 0 ? -top : 0;
-    int ww = o.width, hh = o.height;
-    if (o.width - x0 > a.width - left) ww = a.width - left + x0;
-    if (o.height - y0 > a.height - top) hh = a.height - top + y0;
-    const unsigned max = (256u << a.shift) - 1;
-
-    // the luma samples of this block
-    for (int j = 0; j < (1 << a.hshift); j++)
-        for (int i = 0; i < (1 << a.wshift); i++)
-        {
-            const int lx = (xx << a.wshift) + i, ly = (yy << a.hshift) + j;
-            if (lx < x0 || lx >= ww || ly < y0 || ly >= hh) continue;
-            const int dx = left + lx, dy = top + ly;
-            if (dx >= a.width || dy >= a.height) continue;
-            const unsigned al = (unsigned)o.plane[3][(size_t)ly * o.stride[3] + lx] << a.shift;
-            const unsigned s = (unsigned)o.plane[0][(size_t)ly * o.stride[0] + lx] << a.shift;
-            PIX *d = row_of<PIX>(a.dst[0], a.pitch[0], dy) + dx;
-            *d = (PIX)(((unsigned)*d * (max - al) + s * al) / max);
-        }
-    // its chroma sample
-    if (xx < (x0 >> a.wshift) || xx >= (ww >> a.wshift) || yy < (y0 >> a.hshift) || yy >= (hh >> a.hshift)) return;
-    const int dx = (left >> a.wshift) + xx, dy = yy + (top >> a.hshift);
-    if (dx < 0 || dy < 0 || dx >= a.cw || dy >= a.ch) return;
-    const unsigned al = (unsigned)o.plane[3][(size_t)(yy << a.hshift) * o.stride[3] + (xx << a.wshift)] << a.shift;
-#pragma unroll
-    for (int c = 1; c < 3; c++)
-    {
-        const unsigned s = (unsigned)o.plane[c][(size_t)yy * o.stride[c] + xx] << a.shift;
-        PIX *d = row_of<PIX>(a.dst[c], a.pitch[c], dy) + dx;
-        *d = (PIX)(((unsigned)*d * (max - al) + s * al) / max);
-    }
+    blend_same_body<PIX, false>(a, G);
 }
 
 // grid: frame chroma samples starting at (bx0, by0) = the first one the overlay touches
 template <typename PIX>
 __global__ __launch_bounds__(256) void blend_subsample_kernel(BlendArgs a, OverlayGroup G)
 {
-    const OverlayDev &o = G.o[blockIdx.z];
-    const int bx0 = G.bx0[blockIdx.z], by0 = G.by0[blockIdx.z];
-    const int cx = bx0 + blockIdx.x * blockDim.x + threadIdx.x, cy = by0 + blockIdx.y * blockDim.y + threadIdx.y;
-    const int x0 = o.x, y0 = o.y;
-    const int ow = o.width <= a.width ? o.width : a.width;          // :74-75 with left == x0
-    const int oh = o.height <= a.height ? o.height : a.height;
-    const int xx = cx << a.wshift, yy = cy << a.hshift;
-    const int ox = xx - x0, oy = yy - y0;
-    if (cx >= a.cw || cy >= a.ch || ox >= ow || oy >= oh) return;
-    const unsigned max = (256u << a.shift) - 1;
-
-    PIX *du = row_of<PIX>(a.dst[1], a.pitch[1], cy) + cx, *dv = row_of<PIX>(a.dst[2], a.pitch[2], cy) + cx;
-    const unsigned cur_u = *du, cur_v = *dv;
-    unsigned acc_u = 0, acc_v = 0, total = 0;
-    for (int yz = 0; yz < (1 << a.hshift) && oy + yz < oh; yz++)
-        for (int xz = 0; xz < (1 << a.wshift) && ox + xz < ow; xz++)
-        {
-            const unsigned coeff = a.coeff[0][xz] * a.coeff[1][yz];
-            unsigned ru = cur_u, rv = cur_v;
-            if (ox + xz >= 0 && oy + yz >= 0)
-            {
-                const size_t row = (size_t)(oy + yz);
-                const int col = ox + xz;
-                const unsigned al = (unsigned)o.plane[3][row * o.stride[3] + col] << a.shift;
-                const unsigned su = (unsigned)o.plane[1][row * o.stride[1] + col] << a.shift;
-                const unsigned sv = (unsigned)o.plane[2][row * o.stride[2] + col] << a.shift;
-                ru = (ru * (max - al) + su * al + (max >> 1)) / max;
-                rv = (rv * (max - al) + sv * al + (max >> 1)) / max;
-                // the luma sample at the same place
-                if (xx + xz < a.width && yy + yz < a.height)
-                {
-                    const unsigned sy = (unsigned)o.plane[0][row * o.stride[0] + col] << a.shift;
-                    PIX *d = row_of<PIX>(a.dst[0], a.pitch[0], yy + yz) + xx + xz;
-                    *d = (PIX)(((unsigned)*d * (max - al) + sy * al + (max >> 1)) / max);
-                }
-            }
-            acc_u += coeff * ru;
-            acc_v += coeff * rv;
-            total += coeff;
-        }
-    if (total)
-    {
-        *du = (PIX)((acc_u + (total >> 1)) / total);
-        *dv = (PIX)((acc_v + (total >> 1)) / total);
-    }
+    blend_subsample_body<PIX, false>(a, G);
 }
 
 } // namespace
@@ -158,10 +56,13 @@ struct hbhip_blend
     struct Launch { OverlayGroup g; int n; dim3 grid; };
     std::vector<Launch> launches;        // the overlays in list order, grouped (build_launches)
     hbhip_frame *staging = nullptr;      // device frame of the host-frame entry point
+    bool biplanar = false;               // made by hbhip_blend_create_biplanar
+    uint8_t *bi_stage = nullptr;         // its staging buffer: the host picture as it is (BiLayout)
 
     ~hbhip_blend()
     {
         if (d_store) (void)hipFree(d_store);
+        if (bi_stage) (void)hipFree(bi_stage);
         if (staging) hbhip_frame_release(staging);
     }
 };
@@ -310,7 +211,7 @@ extern "C" int hbhip_blend_set_overlays(hbhip_blend *b, const hbhip_overlay *ov,
 
 extern "C" int hbhip_blend_apply_dev(hbhip_blend *b, const hbhip_dev_frame *frame)
 {
-    if (!b || !frame) return HBHIP_ERR_ARG;
+    if (!b || !frame || b->biplanar) return HBHIP_ERR_ARG;
     hbhip_ctx *ctx = b->ctx;
     (void)hipSetDevice(ctx->device);
     BlendArgs a;
@@ -338,7 +239,7 @@ extern "C" int hbhip_blend_apply_dev(hbhip_blend *b, const hbhip_dev_frame *fram
 
 extern "C" int hbhip_blend_apply(hbhip_blend *b, const hbhip_host_frame *frame)
 {
-    if (!b || !frame) return HBHIP_ERR_ARG;
+    if (!b || !frame || b->biplanar) return HBHIP_ERR_ARG;
     if (b->overlays.empty()) return HBHIP_OK;
     if (!b->staging)
     {
@@ -354,4 +255,51 @@ extern "C" int hbhip_blend_apply(hbhip_blend *b, const hbhip_host_frame *frame)
     if (rc == HBHIP_OK) rc = hbhip_frame_mark_ready(b->staging);        // the download waits for the compositor
     if (rc != HBHIP_OK) return rc;
     return hbhip_frame_download(b->staging, frame);
+}
+
+extern "C" int hbhip_blend_create_biplanar(hbhip_ctx *ctx, int width, int height, int depth, int chroma_location,
+                                           int overlay_log2_chroma_w, int overlay_log2_chroma_h, hbhip_blend **out)
+{
+    if (!ctx || !out) return HBHIP_ERR_ARG;
+    *out = nullptr;
+    if ((depth != 8 && depth != 10) || width < 2 || height < 2) return HBHIP_ERR_UNSUPPORTED;
+    const int rc = hbhip_blend_create(ctx, width, height, depth, 1, 1, chroma_location, overlay_log2_chroma_w,
+                                      overlay_log2_chroma_h, out);
+    if (rc == HBHIP_OK) (*out)->biplanar = true;
+    return rc;
+}
+
+// H2D into the staging buffer, the overlays in list order on it in place (hb_blend_work :866-869), D2H
+extern "C" int hbhip_blend_apply_biplanar(hbhip_blend *b, const hbhip_host_biplanar *frame)
+{
+    if (!b || !frame || !b->biplanar) return HBHIP_ERR_ARG;
+    BiLayout l;
+    hbhip_bi_layout(b->geo.width, b->geo.height, b->geo.depth, &l);
+    for (int p = 0; p < 2; p++)
+        if (frame->plane[p] == nullptr || frame->stride[p] < l.row_bytes[p]) return HBHIP_ERR_ARG;
+    if (b->overlays.empty()) return HBHIP_OK;
+    hbhip_ctx *ctx = b->ctx;
+    (void)hipSetDevice(ctx->device);
+    if (!b->bi_stage) HBHIP_CHECK(ctx, hipMalloc((void **)&b->bi_stage, l.bytes));
+    uint8_t *plane[2] = { b->bi_stage, b->bi_stage + (size_t)l.pitch[0] * l.rows[0] };
+    for (int p = 0; p < 2; p++)
+        HBHIP_CHECK(ctx, hipMemcpy2DAsync(plane[p], l.pitch[p], frame->plane[p], frame->stride[p], l.row_bytes[p], l.rows[p],
+                                          hipMemcpyHostToDevice, ctx->stream));
+    BlendArgs a;
+    a.dst[0] = plane[0]; a.dst[1] = plane[1]; a.dst[2] = plane[1] + b->geo.bps;      // Cb Cr Cb Cr ...
+    a.pitch[0] = l.pitch[0]; a.pitch[1] = a.pitch[2] = l.pitch[1];
+    a.width = b->geo.width; a.height = b->geo.height; a.cw = b->geo.pw[1]; a.ch = b->geo.ph[1];
+    a.wshift = a.hshift = 1; a.shift = b->geo.depth - 8;
+    for (int i = 0; i < 2; i++) { a.coeff[0][i] = b->coeff[0][i]; a.coeff[1][i] = b->coeff[1][i]; }
+    for (const hbhip_blend::Launch &ln : b->launches)
+    {
+        const int rc = hbhip_bi_blend_launch(ctx, b->subsample, b->geo.bps, ln.grid, a, ln.g);
+        if (rc != HBHIP_OK) return rc;
+    }
+    HBHIP_CHECK(ctx, hipGetLastError());
+    for (int p = 0; p < 2; p++)
+        HBHIP_CHECK(ctx, hipMemcpy2DAsync(frame->plane[p], frame->stride[p], plane[p], l.pitch[p], l.row_bytes[p], l.rows[p],
+                                          hipMemcpyDeviceToHost, ctx->stream));
+    HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return HBHIP_OK;
 }

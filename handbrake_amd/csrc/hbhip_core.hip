@@ -595,6 +595,8 @@ void hbhip_ctx_destroy(hbhip_ctx *ctx)
         if (fr->pic.base) (void)hipFree(fr->pic.base);
         delete fr;
     }
+    for (int i = 0; i < 2; i++)
+        if (ctx->bi_stage[i]) (void)hipFree(ctx->bi_stage[i]);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (int i = 0; i < HBHIP_MAX_MARKS; i++)
         if (ctx->marks[i]) (void)hipEventDestroy(ctx->marks[i]);
@@ -1076,6 +1078,154 @@ int hbhip_frame_download_wait(hbhip_frame *fr, void *token)
     const hipError_t e = hipEventSynchronize(ev);
     ctx->sync_ev_put(ev);
     return e == hipSuccess ? HBHIP_OK : ctx->fail(e, "hipEventSynchronize(download)");
+}
+
+// ---- biplanar host pictures (NV12 / P010LE) at the two ends of a run ----------------------------------------------
+// The frame stays planar; the host picture goes through a staging buffer in its own layout and a repack kernel
+// (biplanar.hip).  Same ordering rule as the planar copies: the split runs behind the H2D copy on the upload stream and
+// the frame's ready mark is the split; the merge runs on the download stream behind the frame's contents and the D2H
+// copy behind the merge.
+static int bi_check(const hbhip_frame *fr, const hbhip_host_biplanar *hb, BiLayout *l)
+{
+    if ((fr->depth != 8 && fr->depth != 10) || fr->lcw != 1 || fr->lch != 1 || fr->width < 2 || fr->height < 2)
+        return HBHIP_ERR_UNSUPPORTED;
+    hbhip_bi_layout(fr->width, fr->height, fr->depth, l);
+    for (int p = 0; p < 2; p++)
+        if (hb->plane[p] == nullptr || hb->stride[p] < l->row_bytes[p]) return HBHIP_ERR_ARG;
+    return HBHIP_OK;
+}
+
+// the context's staging buffer of direction `dir`, at least `bytes` long (bi_lock[dir] held).  Growing it waits the stream
+// that uses it out first: earlier pairs may still be running.
+static uint8_t *bi_stage(hbhip_ctx *ctx, int dir, size_t bytes, hipStream_t stream)
+{
+    if (ctx->bi_stage_bytes[dir] >= bytes) return ctx->bi_stage[dir];
+    if (ctx->bi_stage[dir])
+    {
+        (void)hipStreamSynchronize(stream);
+        (void)hipFree(ctx->bi_stage[dir]);
+        ctx->bi_stage[dir] = nullptr;
+        ctx->bi_stage_bytes[dir] = 0;
+    }
+    if (hipMalloc((void **)&ctx->bi_stage[dir], bytes) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        ctx->bi_stage[dir] = nullptr;
+        return nullptr;
+    }
+    ctx->bi_stage_bytes[dir] = bytes;
+    return ctx->bi_stage[dir];
+}
+
+// host picture <-> staging buffer: one 1-D copy when the host picture has the staging layout, else a 2-D copy per plane
+static hipError_t bi_copy(uint8_t *stage, const BiLayout &l, const hbhip_host_biplanar *hb, bool to_device, hipStream_t stream)
+{
+    const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    if (hb->stride[0] == l.pitch[0] && hb->stride[1] == l.pitch[1] &&
+        hb->plane[1] == hb->plane[0] + (size_t)l.pitch[0] * l.rows[0])
+        return to_device ? hipMemcpyAsync(stage, hb->plane[0], l.bytes, kind, stream)
+                         : hipMemcpyAsync(hb->plane[0], stage, l.bytes, kind, stream);
+    hipError_t e = hipSuccess;
+    uint8_t *at = stage;
+    for (int p = 0; p < 2 && e == hipSuccess; p++)
+    {
+        // up: the caller's row padding travels too (up to our pitch), as in the planar upload - the split hands it on to
+        // the frame, whose readers read it; down: the samples only, as in the planar download
+        const size_t up_row = (size_t)std::min(hb->stride[p], l.pitch[p]);
+        e = to_device ? hipMemcpy2DAsync(at, l.pitch[p], hb->plane[p], hb->stride[p], up_row, l.rows[p], kind, stream)
+                      : hipMemcpy2DAsync(hb->plane[p], hb->stride[p], at, l.pitch[p], l.row_bytes[p], l.rows[p], kind, stream);
+        at += (size_t)l.pitch[p] * l.rows[p];
+    }
+    return e;
+}
+
+// `src` must stay valid until hbhip_ctx_upload_done(token) says so, as with hbhip_frame_upload_async
+int hbhip_frame_upload_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *src, void **token)
+{
+    if (!fr || !src || !token) return HBHIP_ERR_ARG;
+    *token = nullptr;
+    hbhip_ctx *ctx = fr->ctx;
+    BiLayout l;
+    int rc = bi_check(fr, src, &l);
+    if (rc != HBHIP_OK) return rc;
+    (void)hipSetDevice(ctx->device);
+    std::shared_ptr<IdleMark> m = std::make_shared<IdleMark>();
+    if (hipEventCreateWithFlags(&m->ev, hipEventDisableTiming) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(upload ready)");
+    }
+    hipEvent_t done = ctx->sync_ev_get();
+    if (!done) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(upload)");
+    hipStream_t up = ctx->up();
+    {
+        std::lock_guard<std::mutex> lk(ctx->bi_lock[0]);
+        uint8_t *stage = bi_stage(ctx, 0, l.bytes, up);
+        hipError_t e = stage ? hbhip_pic_wait_idle(up, &fr->pic) : hipErrorOutOfMemory;
+        if (e == hipSuccess) e = bi_copy(stage, l, src, true, up);
+        if (e == hipSuccess) e = hipEventRecord(done, up);                    // the host picture is free behind the copy
+        if (e == hipSuccess) rc = hbhip_bi_repack_launch(ctx, up, false, stage, fr);
+        if (e == hipSuccess && rc == HBHIP_OK) e = hipEventRecord(m->ev, up);
+        if (e != hipSuccess || rc != HBHIP_OK)
+        {
+            (void)hipStreamSynchronize(up);                                   // what is queued must not outlive the call
+            ctx->sync_ev_put(done);
+            return e != hipSuccess ? ctx->fail(e, "upload (biplanar)") : rc;
+        }
+    }
+    m->stream = up;
+    m->recorded = true;
+    m->closed.store(true, std::memory_order_release);
+    { std::lock_guard<std::mutex> lk(ctx->frame_lock); set_contents(fr, std::move(m)); }
+    *token = done;
+    return HBHIP_OK;
+}
+
+int hbhip_frame_upload_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *src)
+{
+    void *token = nullptr;
+    const int rc = hbhip_frame_upload_biplanar_async(fr, src, &token);
+    return rc != HBHIP_OK ? rc : hbhip_ctx_upload_done(fr->ctx, token, 1);
+}
+
+// `dst` and the frame must stay valid until hbhip_frame_download_wait(fr, token) has returned
+int hbhip_frame_download_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *dst, void **token)
+{
+    if (!fr || !dst || !token) return HBHIP_ERR_ARG;
+    *token = nullptr;
+    hbhip_ctx *ctx = fr->ctx;
+    BiLayout l;
+    int rc = bi_check(fr, dst, &l);
+    if (rc != HBHIP_OK) return rc;
+    (void)hipSetDevice(ctx->device);
+    hipEvent_t ev = ctx->sync_ev_get();
+    if (!ev) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(download)");
+    hipStream_t down = ctx->down();
+    hipError_t e;
+    { std::lock_guard<std::mutex> lk(ctx->frame_lock); e = order_after_contents(fr, down); }
+    {
+        std::lock_guard<std::mutex> lk(ctx->bi_lock[1]);
+        uint8_t *stage = e == hipSuccess ? bi_stage(ctx, 1, l.bytes, down) : nullptr;
+        if (e == hipSuccess && !stage) e = hipErrorOutOfMemory;
+        if (e == hipSuccess) rc = hbhip_bi_repack_launch(ctx, down, true, stage, fr);
+        if (e == hipSuccess && rc == HBHIP_OK) e = bi_copy(stage, l, dst, false, down);
+        if (e == hipSuccess && rc == HBHIP_OK) e = hipEventRecord(ev, down);
+        if (e != hipSuccess || rc != HBHIP_OK)
+        {
+            (void)hipStreamSynchronize(down);
+            ctx->sync_ev_put(ev);
+            return e != hipSuccess ? ctx->fail(e, "download (biplanar)") : rc;
+        }
+    }
+    *token = ev;
+    return HBHIP_OK;
+}
+
+int hbhip_frame_download_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *dst)
+{
+    void *token = nullptr;
+    const int rc = hbhip_frame_download_biplanar_async(fr, dst, &token);
+    return rc != HBHIP_OK ? rc : hbhip_frame_download_wait(fr, token);
 }
 
 // ---- generic filter surface -------------------------------------------------

@@ -85,6 +85,13 @@ struct hbhip_ctx
     // pool of device-resident frames handed between filters (hbhip_frame_*)
     std::vector<struct hbhip_frame *> frame_pool;
     std::mutex frame_lock;          // filters of one job run on different host threads
+    // staging buffers of the biplanar (NV12 / P010LE) uploads [0] and downloads [1]: one each, reused - the copy and the
+    // repack kernel of a frame are queued as a pair under the direction's bi_lock on the upload / download stream, whose
+    // order then keeps a frame's pair ahead of the next one's (hbhip_frame_upload_biplanar_async, hbhip_core.hip).  A lock
+    // a direction: the two adapters of a run work on different threads, streams and buffers and share nothing here.
+    std::mutex bi_lock[2];
+    uint8_t   *bi_stage[2] = {nullptr, nullptr};
+    size_t     bi_stage_bytes[2] = {0, 0};
     // last_error and the profiler's bookkeeping are written from whichever filter thread fails / launches:
     // libhb runs every filter of a job on its own thread (work.c:2527-2600) and they share this context
     std::recursive_mutex state_lock;
@@ -211,6 +218,17 @@ struct hbhip_frame
     bool        owner_used = false;       // the owner has taken it so
     std::shared_ptr<IdleMark> reader_idle;   // the second idle mark (pic.idle: the owner's): its last foreign user's
 };
+
+// A biplanar 4:2:0 picture (NV12 / P010LE) the way hb_frame_buffer_init lays it out: plane 1 is interleaved Cb Cr, rows
+// rounded up to 64 bytes, plane 1 right behind plane 0 (biplanar.hip)
+struct BiLayout
+{
+    int    pitch[2], row_bytes[2], rows[2];
+    size_t bytes;
+};
+void hbhip_bi_layout(int width, int height, int depth, BiLayout *l);
+// the repack kernel between a staging buffer of that layout and the planar 4:2:0 frame `fr` (depth 8 or 10), on `stream`
+int hbhip_bi_repack_launch(hbhip_ctx *ctx, hipStream_t stream, bool merge, uint8_t *stage, const hbhip_frame *fr);
 
 // Geometry of a planar YUV picture.
 struct PicGeometry

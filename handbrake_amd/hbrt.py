@@ -22,6 +22,11 @@ PIX_FMT_FOR_DEPTH = {8: AV_PIX_FMT_YUV420P, 10: AV_PIX_FMT_YUV420P10, 12: AV_PIX
 PIX_FMT = {("2x2", 8): 0, ("2x1", 8): 4, ("1x1", 8): 5, ("2x2", 10): 62, ("2x1", 10): 64, ("1x1", 10): 68,
            ("2x2", 12): 123, ("2x1", 12): 127, ("1x1", 12): 131}
 
+# biplanar 4:2:0: frames are two arrays, Y and the interleaved CbCr rows of shape (ceil(h / 2), 2 * ceil(w / 2)); P010LE
+# samples are uint16 with their 10 bits in the high end
+AV_PIX_FMT_NV12, AV_PIX_FMT_P010LE = 23, 158
+BIPLANAR = (AV_PIX_FMT_NV12, AV_PIX_FMT_P010LE)
+
 HB_COMB_NONE, HB_COMB_LIGHT, HB_COMB_HEAVY = 0, 1, 2
 
 
@@ -80,7 +85,7 @@ def runtime() -> C.CDLL:
 
 @dataclass
 class OutFrame:
-    planes: tuple          # (Y, Cb, Cr) uint8 arrays, cropped to plane width
+    planes: tuple          # (Y, Cb, Cr) uint8 arrays, cropped to plane width; (Y, CbCr) for NV12 / P010LE
     start: int
     stop: int
     flags: int
@@ -127,10 +132,10 @@ class Chain:
         hb_buffer_t's by `threads` C threads and pushed in order (hbh_chain_feed) - a source that keeps up"""
         n = len(frames)
         keep = [[np.ascontiguousarray(p) for p in fr] for fr in frames]
-        ptrs = (C.c_void_p * (3 * n))(*[p.ctypes.data for fr in keep for p in fr])
+        ptrs = (C.c_void_p * (3 * n))(*[fr[k].ctypes.data if k < len(fr) else None for fr in keep for k in range(3)])
         strides = (C.c_int * 3)(*[p.strides[0] for p in keep[0]])
         for fr in keep:
-            assert [p.strides[0] for p in fr] == list(strides)
+            assert [p.strides[0] for p in fr] == list(strides)[:len(fr)]      # (two planes: NV12 / P010LE)
         self._rt.hbh_chain_feed.restype = C.c_int
         self._rt.hbh_chain_feed.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int,
                                             C.c_int64, C.c_int, C.c_int]
@@ -166,14 +171,16 @@ class Chain:
         ptrs = (C.c_void_p * 3)()
         strides = (C.c_int * 3)()
         arrs = []
-        for p in range(3):
+        for p in range(info.nplanes):
             a = np.empty((info.plane_height[p], info.plane_stride[p]), dtype=np.uint8)
             arrs.append(a)
             ptrs[p] = a.ctypes.data
             strides[p] = a.strides[0]
         self._rt.hbh_chain_pop(self._h, ptrs, strides)
-        bps = 2 if info.fmt in (62, 123, 64, 68, 127, 131) else 1
-        planes = tuple(a[:, : info.plane_width[p] * bps] for p, a in enumerate(arrs))
+        bps = 2 if info.fmt in (62, 123, 64, 68, 127, 131, AV_PIX_FMT_P010LE) else 1
+        # plane 1 of a biplanar frame holds two samples, Cb and Cr, per chroma position
+        per = [2 if info.fmt in BIPLANAR and p == 1 else 1 for p in range(info.nplanes)]
+        planes = tuple(a[:, : info.plane_width[p] * bps * per[p]] for p, a in enumerate(arrs))
         if bps == 2:                      # 10 / 12-bit samples in 16-bit containers
             planes = tuple(np.ascontiguousarray(p).view(np.uint16) for p in planes)
         return OutFrame(planes, info.start, info.stop, info.flags, info.combed,
@@ -208,6 +215,18 @@ class Chain:
             self.close()
         except Exception:
             pass
+
+
+def frame_layout(pix_fmt: int, width: int, height: int) -> FrameInfo:
+    """What hb_frame_buffer_init makes of a format: nplanes (max_plane + 1), plane_width / _height / _stride per plane;
+    plane_width[3] is the byte distance from plane 0 to the last plane."""
+    rt = runtime()
+    rt.hbh_frame_layout.restype = C.c_int
+    rt.hbh_frame_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(FrameInfo)]
+    info = FrameInfo()
+    if rt.hbh_frame_layout(pix_fmt, width, height, C.byref(info)) != 0:
+        raise RuntimeError(f"no frame layout for pix_fmt {pix_fmt}")
+    return info
 
 
 # hb_filter_object_t ids (handbrake/common.h:1729-1778; include/hbhip_libhb.h)

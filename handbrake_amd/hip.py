@@ -23,6 +23,7 @@ ABI_SYMBOLS = [
     "hbhip_dev_alloc", "hbhip_dev_free", "hbhip_dev_upload", "hbhip_dev_download",
     "hbhip_frame_alloc", "hbhip_frame_retain", "hbhip_frame_release", "hbhip_frame_refs", "hbhip_frame_use_on", "hbhip_frame_describe", "hbhip_frame_copy",
     "hbhip_frame_upload", "hbhip_frame_upload_async", "hbhip_ctx_upload_done", "hbhip_frame_download", "hbhip_frame_mark_ready", "hbhip_frame_download_async", "hbhip_frame_download_wait",
+    "hbhip_frame_upload_biplanar", "hbhip_frame_download_biplanar", "hbhip_frame_upload_biplanar_async", "hbhip_frame_download_biplanar_async",
     "hbhip_filter_use_frames", "hbhip_filter_push_frame", "hbhip_filter_pull_frame", "hbhip_filter_push", "hbhip_filter_push_dev", "hbhip_filter_pull", "hbhip_filter_pull_dev",
     "hbhip_filter_process_dev", "hbhip_filter_submit_async", "hbhip_filter_wait", "hbhip_filter_inflight", "hbhip_filter_flush", "hbhip_filter_pending", "hbhip_filter_defer", "hbhip_filter_kick", "hbhip_filter_destroy",
     "hbhip_filter_out_geometry",
@@ -35,6 +36,7 @@ ABI_SYMBOLS = [
     "hbhip_comb_detect_classify", "hbhip_comb_detect_classify_many_dev", "hbhip_comb_detect_overlay", "hbhip_comb_detect_overlay_dev",
     "hbhip_rotate_create", "hbhip_grayscale_create", "hbhip_cropscale_create", "hbhip_colorspace_create", "hbhip_pad_create", "hbhip_yadif_create", "hbhip_bwdif_create", "hbhip_format_create",
     "hbhip_blend_create", "hbhip_blend_set_overlays", "hbhip_blend_apply", "hbhip_blend_apply_dev", "hbhip_blend_destroy",
+    "hbhip_blend_create_biplanar", "hbhip_blend_apply_biplanar",
     "hbhip_motion_metric_create", "hbhip_motion_metric_run", "hbhip_motion_metric_run_dev", "hbhip_motion_metric_destroy",
     "hbhip_detelecine_create", "hbhip_detelecine_push", "hbhip_detelecine_push_frame",
     "hbhip_deblock_create", "hbhip_deblock_set_warmup",
@@ -45,6 +47,11 @@ ABI_SYMBOLS = [
 
 class HostFrame(C.Structure):
     _fields_ = [("plane", C.c_void_p * 3), ("stride", C.c_int * 3)]
+
+
+class HostBiplanar(C.Structure):
+    """hbhip_host_biplanar: an NV12 / P010LE host picture (luma, interleaved Cb Cr)"""
+    _fields_ = [("plane", C.c_void_p * 2), ("stride", C.c_int * 2)]
 
 
 class DevFrame(C.Structure):
@@ -139,6 +146,11 @@ def lib() -> C.CDLL:
         for fn in ("hbhip_frame_upload", "hbhip_frame_download"):
             getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(HostFrame)]
         L.hbhip_frame_upload_async.argtypes = [C.c_void_p, C.POINTER(HostFrame), C.POINTER(C.c_void_p)]
+        for fn in ("hbhip_frame_upload_biplanar", "hbhip_frame_download_biplanar"):
+            getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(HostBiplanar)]
+        for fn in ("hbhip_frame_upload_biplanar_async", "hbhip_frame_download_biplanar_async"):
+            getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(HostBiplanar), C.POINTER(C.c_void_p)]
+        L.hbhip_frame_download_wait.argtypes = [C.c_void_p, C.c_void_p]
         L.hbhip_ctx_upload_done.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.hbhip_filter_use_frames.argtypes = [C.c_void_p]
         L.hbhip_decomb_push_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]

@@ -252,6 +252,10 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     if (dd == NULL || dd->nb_components != desc->nb_components || desc->nb_components < 3 ||
         dd->log2_chroma_w != desc->log2_chroma_w || dd->log2_chroma_h != desc->log2_chroma_h)
         return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
+    /* a component per plane on both sides: NV12 / P010 (Cb and Cr on plane 1) are the adapters' business, not this filter's */
+    for (int c = 0; c < 3; c++)
+        if (dd->comp[c].plane != c || desc->comp[c].plane != c)
+            return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
     hbhip_ctx *ctx = hbhip_host_ctx_for(init);
     if (ctx == NULL) return hbhip_host_simple_fail(filter, HBHIP_ERR_NODEVICE);
     int rc = hbhip_format_create(ctx, init->geometry.width, init->geometry.height, desc->comp[0].depth,

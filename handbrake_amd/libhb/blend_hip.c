@@ -9,6 +9,8 @@
  * frame that is not writable is duplicated first; overlays are composited in list order.
  * The bitmaps are uploaded only when `changed` says the list is new.  Frames already in HBM
  * (storage_type HBHIP_DEVICE) are composited in place without leaving the device.
+ * Host frames in NV12 / P010LE (two planes, 4:2:0, 8 or 10 bits) take the biplanar forms (blend8onbi*, csrc/biplanar.hip)
+ * through hbhip_blend_create_biplanar / _apply_biplanar; every other two-plane format is refused in init().
  */
 #include "hbhip_host.h"
 
@@ -17,6 +19,7 @@ struct hb_blend_private_s
     hbhip_blend *dev;                /* made on the first frame: on the GPU that frame lives on */
     int          have_overlays;      /* the device holds the current list */
     int          width, height, depth, lcw, lch, chroma_location, ov_lcw, ov_lch;
+    int          biplanar;           /* NV12 / P010LE host frames */
 };
 
 /* hb_blend_object_t.init gets no hb_filter_init_t (common.h:1813-1828), so it cannot ask which GPU the job runs on
@@ -28,6 +31,10 @@ static int blend_hip_device(hb_blend_private_t *pv, const hb_buffer_t *in)
     hbhip_frame *fr = hbhip_host_frame_of(in);
     hbhip_ctx *ctx = fr != NULL ? hbhip_frame_context(fr) : hbhip_host_ctx();
     if (ctx == NULL) return HBHIP_ERR_NODEVICE;
+    if (pv->biplanar)
+        return fr != NULL ? HBHIP_ERR_ARG                   /* frames in HBM are planar */
+                          : hbhip_blend_create_biplanar(ctx, pv->width, pv->height, pv->depth, pv->chroma_location,
+                                                        pv->ov_lcw, pv->ov_lch, &pv->dev);
     return hbhip_blend_create(ctx, pv->width, pv->height, pv->depth, pv->lcw, pv->lch, pv->chroma_location,
                               pv->ov_lcw, pv->ov_lch, &pv->dev);
 }
@@ -49,8 +56,15 @@ static int blend_hip_init(hb_blend_object_t *object, int in_width, int in_height
      * (rendersub.c:1129-1161), not at the first frame in the middle of an encode */
     int rc = in_desc == NULL || ov_desc == NULL || hbhip_device_count() <= 0 || hbhip_host_ctx() == NULL
              ? HBHIP_ERR_NODEVICE : HBHIP_OK;
-    if (rc == HBHIP_OK && av_pix_fmt_count_planes(in_pix_fmt) != 3)
-        rc = HBHIP_ERR_UNSUPPORTED;                     /* NV12 / P010: blend8onbi*, not built */
+    const int planes = rc == HBHIP_OK ? av_pix_fmt_count_planes(in_pix_fmt) : 0;
+    if (rc == HBHIP_OK && planes != 3 && planes != 2)
+        rc = HBHIP_ERR_UNSUPPORTED;
+    /* two planes: NV12 and P010LE only - NV16, NV24, P012, P016, P21x, P41x have no kernels */
+    if (rc == HBHIP_OK && planes == 2 &&
+        (in_desc->log2_chroma_w != 1 || in_desc->log2_chroma_h != 1 || in_width < 2 || in_height < 2 ||
+         (in_desc->comp[0].depth != 8 && in_desc->comp[0].depth != 10) ||
+         in_desc->comp[0].shift != (in_desc->comp[0].depth == 8 ? 0 : 6)))
+        rc = HBHIP_ERR_UNSUPPORTED;
     if (rc == HBHIP_OK)
     {
         /* what hbhip_blend_create would refuse on the first frame is refused here, where rendersub can still react */
@@ -65,6 +79,7 @@ static int blend_hip_init(hb_blend_object_t *object, int in_width, int in_height
         pv->width = in_width; pv->height = in_height; pv->depth = in_desc->comp[0].depth;
         pv->lcw = in_desc->log2_chroma_w; pv->lch = in_desc->log2_chroma_h; pv->chroma_location = in_chroma_location;
         pv->ov_lcw = ov_desc->log2_chroma_w; pv->ov_lch = ov_desc->log2_chroma_h;
+        pv->biplanar = planes == 2;
     }
     if (rc != HBHIP_OK)
     {
@@ -154,9 +169,18 @@ static hb_buffer_t *blend_hip_work(hb_blend_object_t *object, hb_buffer_t *in, h
                 hb_buffer_close(&in);
                 if (out == NULL) return NULL;
             }
-            hbhip_host_frame f;
-            hbhip_host_frame_from_buf(&f, out);
-            rc = hbhip_blend_apply(pv->dev, &f);
+            if (pv->biplanar)
+            {
+                hbhip_host_biplanar f;
+                hbhip_host_biplanar_from_buf(&f, out);
+                rc = hbhip_blend_apply_biplanar(pv->dev, &f);
+            }
+            else
+            {
+                hbhip_host_frame f;
+                hbhip_host_frame_from_buf(&f, out);
+                rc = hbhip_blend_apply(pv->dev, &f);
+            }
         }
     }
     if (rc != HBHIP_OK)

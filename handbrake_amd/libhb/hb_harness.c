@@ -610,6 +610,28 @@ int hbh_chain_peek(hbh_chain_t *c, hbh_frame_info_t *info)
     return 0;
 }
 
+/* what hb_frame_buffer_init makes of (pix_fmt, width, height): plane count, sizes and strides; plane_width[3] is the
+ * distance in bytes from plane 0 to the last plane (the planes lie back to back).  -1: no such format. */
+int hbh_frame_layout(int pix_fmt, int width, int height, hbh_frame_info_t *info)
+{
+    hb_buffer_t *b = hb_frame_buffer_init(pix_fmt, width, height);
+    if (b == NULL || info == NULL) { hb_buffer_close(&b); return -1; }
+    memset(info, 0, sizeof(*info));
+    info->width = b->f.width;
+    info->height = b->f.height;
+    info->fmt = b->f.fmt;
+    info->nplanes = b->f.max_plane + 1;
+    for (int p = 0; p < info->nplanes; p++)
+    {
+        info->plane_width[p] = b->plane[p].width;
+        info->plane_height[p] = b->plane[p].height;
+        info->plane_stride[p] = b->plane[p].stride;
+    }
+    if (info->nplanes < 4) info->plane_width[3] = (int)(b->plane[b->f.max_plane].data - b->plane[0].data);
+    hb_buffer_close(&b);
+    return 0;
+}
+
 int hbh_chain_pop(hbh_chain_t *c, uint8_t *const plane[3], const int stride[3])
 {
     hb_buffer_t *b = c ? hb_buffer_list_rem_head(&c->out) : NULL;

@@ -65,6 +65,8 @@ int  hbh_chain_push_eof(hbh_chain_t *c);
 int  hbh_chain_pending(hbh_chain_t *c);
 int  hbh_chain_peek(hbh_chain_t *c, hbh_frame_info_t *info);
 int  hbh_chain_pop(hbh_chain_t *c, uint8_t *const plane[3], const int stride[3]);
+/* the layout hb_frame_buffer_init gives a frame (no chain needed); plane_width[3]: bytes from plane 0 to the last plane */
+int  hbh_frame_layout(int pix_fmt, int width, int height, hbh_frame_info_t *info);
 void hbh_chain_output_geometry(hbh_chain_t *c, int *width, int *height, int *vrate_num, int *vrate_den);
 void hbh_chain_close(hbh_chain_t *c);
 

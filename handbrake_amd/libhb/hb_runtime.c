@@ -92,10 +92,34 @@ DESC16(k_desc_yuv444p10, "yuv444p10le", 0, 0, 10);
 DESC16(k_desc_yuv422p12, "yuv422p12le", 1, 0, 12);
 DESC16(k_desc_yuv444p12, "yuv444p12le", 0, 0, 12);
 
+/* The two biplanar 4:2:0 formats (libavutil/pixdesc.c): Cb and Cr interleaved on plane 1; P010LE keeps its 10 bits in
+ * the high end of 16.  23 and 158 are FFmpeg's numbers (tests/libhb_stubs/libav_stub.h has them), under names of this
+ * file: the oracle's wrappers declare AV_PIX_FMT_NV12 / AV_PIX_FMT_P010 themselves next to include/hbhip_libhb.h (the
+ * filters' names for them: hbhip_host.h).  101 and 207 are numbers of this stand-in only - nothing in the tree pins
+ * FFmpeg's for NV16 / P012LE, and nothing but the refusal tests uses them. */
+enum { RT_PIX_FMT_NV12 = 23, RT_PIX_FMT_P010LE = 158, RT_PIX_FMT_NV16 = 101, RT_PIX_FMT_P012LE = 207 };
+static const AVPixFmtDescriptor k_desc_nv12 = {
+    "nv12", 3, 1, 1, 0,
+    { {0, 1, 0, 0, 8}, {1, 2, 0, 0, 8}, {1, 2, 1, 0, 8}, {0, 0, 0, 0, 0} } };
+static const AVPixFmtDescriptor k_desc_p010 = {
+    "p010le", 3, 1, 1, 0,
+    { {0, 2, 0, 6, 10}, {1, 4, 0, 6, 10}, {1, 4, 2, 6, 10}, {0, 0, 0, 0, 0} } };
+/* two more of the family, known so that what declines them declines them by rule and not for want of a descriptor */
+static const AVPixFmtDescriptor k_desc_nv16 = {
+    "nv16", 3, 1, 0, 0,
+    { {0, 1, 0, 0, 8}, {1, 2, 0, 0, 8}, {1, 2, 1, 0, 8}, {0, 0, 0, 0, 0} } };
+static const AVPixFmtDescriptor k_desc_p012 = {
+    "p012le", 3, 1, 1, 0,
+    { {0, 2, 0, 4, 12}, {1, 4, 0, 4, 12}, {1, 4, 2, 4, 12}, {0, 0, 0, 0, 0} } };
+
 const AVPixFmtDescriptor *av_pix_fmt_desc_get(int pix_fmt)
 {
     switch (pix_fmt)
     {
+        case RT_PIX_FMT_NV16:        return &k_desc_nv16;
+        case RT_PIX_FMT_P012LE:      return &k_desc_p012;
+        case RT_PIX_FMT_NV12:        return &k_desc_nv12;
+        case RT_PIX_FMT_P010LE:      return &k_desc_p010;
         case AV_PIX_FMT_YUV420P:     return &k_desc_yuv420p;
         case AV_PIX_FMT_YUV422P:     return &k_desc_yuv422p;
         case AV_PIX_FMT_YUV444P:     return &k_desc_yuv444p;
@@ -118,7 +142,8 @@ int av_get_pix_fmt(const char *name)
     static const int known[] = { AV_PIX_FMT_YUV420P, AV_PIX_FMT_YUV422P, AV_PIX_FMT_YUV444P, AV_PIX_FMT_GRAY8,
                                  AV_PIX_FMT_YUVA420P, AV_PIX_FMT_YUVA422P, AV_PIX_FMT_YUVA444P,
                                  AV_PIX_FMT_YUV420P10LE, AV_PIX_FMT_YUV420P12LE, AV_PIX_FMT_YUV422P10LE, AV_PIX_FMT_YUV444P10LE,
-                                 AV_PIX_FMT_YUV422P12LE, AV_PIX_FMT_YUV444P12LE };
+                                 AV_PIX_FMT_YUV422P12LE, AV_PIX_FMT_YUV444P12LE, RT_PIX_FMT_NV12, RT_PIX_FMT_P010LE,
+                                 RT_PIX_FMT_NV16, RT_PIX_FMT_P012LE };
     if (name == NULL) return AV_PIX_FMT_NONE;
     for (size_t i = 0; i < sizeof(known) / sizeof(known[0]); i++)
     {
@@ -145,10 +170,16 @@ int av_image_get_linesize(int pix_fmt, int width, int plane)
 {
     const AVPixFmtDescriptor *d = av_pix_fmt_desc_get(pix_fmt);
     if (d == NULL) return -1;
-    int w = width;
-    if (plane == 1 || plane == 2)
-        w = -((-width) >> d->log2_chroma_w);
-    return w * d->comp[plane].step;
+    /* libavutil/imgutils.c: the widest step among the components that live on `plane`; components 1 and 2 are the
+     * subsampled ones wherever they live (plane 1 of a biplanar format holds both) */
+    int linesize = 0;
+    for (int c = 0; c < d->nb_components; c++)
+    {
+        if (d->comp[c].plane != plane) continue;
+        const int w = (c == 1 || c == 2) ? -((-width) >> d->log2_chroma_w) : width;
+        if (w * d->comp[c].step > linesize) linesize = w * d->comp[c].step;
+    }
+    return linesize;
 }
 
 void *av_malloc(size_t size)

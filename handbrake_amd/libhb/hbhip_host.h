@@ -27,6 +27,20 @@ int        hbhip_host_use_frame(hbhip_ctx *ctx, const hb_buffer_t *in);
 hbhip_ctx *hbhip_host_ctx(void);                                 /* the process default's context */
 void       hbhip_host_ctx_release(void);
 
+/* The biplanar 4:2:0 formats the adapters and the compositor take (FFmpeg's numbers; names of this project's own, the
+ * stand-in header has no enumerators for them) */
+#define HBHIP_PIX_FMT_NV12   23
+#define HBHIP_PIX_FMT_P010LE 158
+static inline int hbhip_host_is_biplanar(int pix_fmt) { return pix_fmt == HBHIP_PIX_FMT_NV12 || pix_fmt == HBHIP_PIX_FMT_P010LE; }
+static inline void hbhip_host_biplanar_from_buf(hbhip_host_biplanar *f, const hb_buffer_t *b)
+{
+    for (int p = 0; p < 2; p++)
+    {
+        f->plane[p]  = b->plane[p].data;
+        f->stride[p] = b->plane[p].stride;
+    }
+}
+
 static inline void hbhip_host_frame_from_buf(hbhip_host_frame *f, const hb_buffer_t *b)
 {
     for (int p = 0; p < 3; p++)
@@ -79,6 +93,7 @@ void hbhip_host_simple_destroy(hbhip_filter *dev);
 
 extern hb_filter_object_t hb_filter_hip_upload;
 extern hb_filter_object_t hb_filter_hip_download;
+int hbhip_host_adapter_input_pix_fmt(const hb_filter_object_t *adapter);   /* AV_PIX_FMT_NONE before its init() */
 
 /* Shared body of the stateless (one in, one out) HIP filters: EOF is forwarded
  * (e.g. lapsharp.c:326-331), otherwise the frame goes through the device filter

@@ -671,6 +671,7 @@ struct hb_filter_private_s
     hb_filter_init_t input;
     hb_filter_init_t output;
     int              depth, lcw, lch;
+    int              biplanar;            /* the host side of this adapter is NV12 / P010LE: repacked on the GPU */
     hbhip_ctx       *ctx;                 /* the job's GPU (hbhip_host_ctx_for) */
     dl_slot_t        dl[DL_DEPTH + 1];
     int              dl_head, dl_count;
@@ -678,14 +679,19 @@ struct hb_filter_private_s
     int              ul_head, ul_count;
 };
 
+/* Biplanar host pictures exist at the two ends of a run only: device frames are planar (the one layout every kernel here
+ * reads).  The upload adapter takes NV12 / P010LE as the stream's format and hands YUV420P / YUV420P10LE on; the download
+ * adapter's one setting, format=nv12 | p010le, makes it emit those from a 4:2:0 run of 8 / 10 bits. */
 static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int to_device)
 {
     hb_filter_private_t *pv = calloc(1, sizeof(*pv));
     if (pv == NULL) return 1;
     const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(init->pix_fmt);
     pv->ctx = hbhip_host_ctx_for(init);
+    /* three planes, or one of the two biplanar formats that are repacked here: NV16, P012 and the rest of that family are
+     * nobody's to move */
     if (desc == NULL || (desc->comp[0].depth != 8 && desc->comp[0].depth != 10 && desc->comp[0].depth != 12) ||
-        pv->ctx == NULL)
+        (av_pix_fmt_count_planes(init->pix_fmt) != 3 && !hbhip_host_is_biplanar(init->pix_fmt)) || pv->ctx == NULL)
     {
         free(pv);
         return 1;
@@ -694,10 +700,43 @@ static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int 
     pv->lcw = desc->log2_chroma_w;
     pv->lch = desc->log2_chroma_h;
     pv->input = *init;
+    int host_fmt = to_device ? init->pix_fmt : AV_PIX_FMT_NONE;
+    char *want = NULL;
+    if (!to_device && hb_dict_extract_string(&want, filter->settings, "format") && want != NULL && want[0] != 0)
+    {
+        host_fmt = av_get_pix_fmt(want);
+        const int ok = hbhip_host_is_biplanar(host_fmt) && hbhip_host_planar_yuv(desc) && pv->lcw == 1 && pv->lch == 1 &&
+                       pv->depth == (host_fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10);
+        if (!ok)
+        {
+            hb_error("hipdownload: format=%s does not fit a run of %s", want, desc->name);
+            free(want);
+            free(pv);
+            return 1;
+        }
+    }
+    free(want);
+    if (hbhip_host_is_biplanar(host_fmt))
+    {
+        if (init->geometry.width < 2 || init->geometry.height < 2)
+        {
+            free(pv);
+            return 1;
+        }
+        pv->biplanar = 1;
+        init->pix_fmt = to_device ? (pv->depth == 8 ? AV_PIX_FMT_YUV420P : AV_PIX_FMT_YUV420P10) : host_fmt;
+    }
     init->hw_pix_fmt = to_device ? AV_PIX_FMT_HBHIP : AV_PIX_FMT_NONE;
     pv->output = *init;
     filter->private_data = pv;
     return 0;
+}
+
+/* the stream's format in front of an initialised adapter (hip_common.c undoes an upload adapter with it) */
+int hbhip_host_adapter_input_pix_fmt(const hb_filter_object_t *adapter)
+{
+    const hb_filter_private_t *pv = adapter != NULL ? adapter->private_data : NULL;
+    return pv != NULL ? pv->input.pix_fmt : AV_PIX_FMT_NONE;
 }
 
 static int ul_retire(hb_filter_private_t *pv, int all);
@@ -766,7 +805,10 @@ static int upload_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buff
     if (hbhip_frame_alloc(pv->ctx, in->f.width, in->f.height, pv->depth, pv->lcw, pv->lch, &fr) != HBHIP_OK)
         return HB_FILTER_FAILED;
     void *token = NULL;
-    if (hbhip_frame_upload_async(fr, &hf, &token) != HBHIP_OK)
+    hbhip_host_biplanar hb;
+    hbhip_host_biplanar_from_buf(&hb, in);
+    if ((pv->biplanar ? hbhip_frame_upload_biplanar_async(fr, &hb, &token)
+                      : hbhip_frame_upload_async(fr, &hf, &token)) != HBHIP_OK)
     {
         hbhip_frame_release(fr);
         return HB_FILTER_FAILED;
@@ -816,7 +858,10 @@ static int download_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_bu
     hbhip_host_frame hf;
     hbhip_host_frame_from_buf(&hf, out);
     void *token = NULL;
-    if (hbhip_frame_download_async(fr, &hf, &token) != HBHIP_OK)
+    hbhip_host_biplanar hb;
+    hbhip_host_biplanar_from_buf(&hb, out);
+    if ((pv->biplanar ? hbhip_frame_download_biplanar_async(fr, &hb, &token)
+                      : hbhip_frame_download_async(fr, &hf, &token)) != HBHIP_OK)
     {
         hb_buffer_close(&out);
         return HB_FILTER_FAILED;
@@ -849,6 +894,7 @@ hb_filter_object_t hb_filter_hip_download =
     .enforce_order = 0,
     .name          = "HIP download adapter",
     .short_name    = "hipdownload",
+    .settings_template = "format=^(nv12|p010le)$",
     .init          = download_init,
     .work          = download_work,
     .close         = adapter_close,

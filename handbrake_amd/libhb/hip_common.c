@@ -21,6 +21,10 @@
 #include "hbhip_host.h"
 #include "hip_common.h"
 
+#ifndef HBHIP_IN_LIBHB
+#define hb_dict_set_string(dict, key, val) hbhip_dict_set(dict, key, val)     /* hb_dict.h:164 */
+#endif
+
 static int is_adapter(const hb_filter_object_t *f)
 {
     return f->id == HB_FILTER_HIP_UPLOAD || f->id == HB_FILTER_HIP_DOWNLOAD;
@@ -47,10 +51,23 @@ static int hip_enabled(void)
     return hbhip_device_count() > 0;
 }
 
-static hb_filter_object_t *new_adapter(int id)
+/* the format a job's runs give back: its own when that is NV12 / P010LE - unless the list holds a `format` filter, which
+ * says itself what the frames are to become (the runs then end planar, as they always did) */
+static int job_host_fmt(const hb_job_t *job)
+{
+    if (!hbhip_host_is_biplanar(job->input_pix_fmt) || hb_filter_find(job->list_filter, HB_FILTER_FORMAT) != NULL)
+        return AV_PIX_FMT_NONE;
+    return job->input_pix_fmt;
+}
+
+/* `host_fmt`: the job's own format when that is NV12 / P010LE.  The upload adapter sees it as the stream's format; the
+ * download adapter is told to give it back (format=), so that what leaves the run is what the job's encoder expects. */
+static hb_filter_object_t *new_adapter(int id, int host_fmt)
 {
     hb_filter_object_t *a = hb_filter_copy(hbhip_filter_get(id));
     if (a != NULL && a->settings == NULL) a->settings = hb_dict_init();
+    if (a != NULL && id == HB_FILTER_HIP_DOWNLOAD && hbhip_host_is_biplanar(host_fmt))
+        hb_dict_set_string(a->settings, "format", host_fmt == HBHIP_PIX_FMT_NV12 ? "nv12" : "p010le");
     return a;
 }
 
@@ -85,8 +102,10 @@ int hb_hip_filter_is_hw_transparent(const hb_filter_object_t *f)
 /* Bracket, from position `from` on, every run [drop-in (drop-in | transparent)* drop-in] that holds at least two
  * drop-ins with hb_filter_hip_upload / hb_filter_hip_download (a lone drop-in moves its own frames; adapters would only
  * add two threads).  Transparent filters at either end of a run stay outside: nothing is gained by uploading for them. */
-static void bracket_runs(hb_list_t *list, int from)
+static void bracket_runs(hb_list_t *list, int from, int host_fmt)
 {
+    /* a drop-in cannot move biplanar frames itself: in an NV12 / P010LE job a lone one gets its adapters too */
+    const int least = hbhip_host_is_biplanar(host_fmt) ? 1 : 2;
     for (int i = from; i < hb_list_count(list);)
     {
         if (!hb_hip_filter_is_hip(hb_list_item(list, i)) || is_adapter(hb_list_item(list, i))) { i++; continue; }
@@ -98,10 +117,10 @@ static void bracket_runs(hb_list_t *list, int from)
             if (hb_hip_filter_is_hip(f)) { last = j; n++; }
             else if (!hb_hip_filter_is_hw_transparent(f)) break;
         }
-        if (n >= 2)
+        if (n >= least)
         {
-            hb_list_insert(list, last + 1, new_adapter(HB_FILTER_HIP_DOWNLOAD));
-            hb_list_insert(list, i, new_adapter(HB_FILTER_HIP_UPLOAD));
+            hb_list_insert(list, last + 1, new_adapter(HB_FILTER_HIP_DOWNLOAD, host_fmt));
+            hb_list_insert(list, i, new_adapter(HB_FILTER_HIP_UPLOAD, host_fmt));
             last += 2;
         }
         i = last + 1;
@@ -126,7 +145,7 @@ void hb_hip_setup_hw_filters(hb_job_t *job)
         hb_filter_object_t *proto = hbhip_filter_get(f->id);
         if (proto != NULL) replace_at(list, i, proto);
     }
-    bracket_runs(list, 0);
+    bracket_runs(list, 0, job_host_fmt(job));
 }
 
 int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
@@ -165,6 +184,8 @@ int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
         if (prev != NULL && prev->id == HB_FILTER_HIP_UPLOAD)
         {
             /* the run's own upload sits right in front: undo it instead of downloading straight again */
+            const int host_fmt = hbhip_host_adapter_input_pix_fmt(prev);      /* NV12 / P010LE: the adapter had rewritten it */
+            if (host_fmt != AV_PIX_FMT_NONE) init->pix_fmt = host_fmt;
             if (prev->close != NULL) prev->close(prev);
             hb_list_rem(list, prev);
             hb_filter_close(&prev);
@@ -173,9 +194,9 @@ int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
             ret = 2;                                          /* the CPU filter now sits one slot earlier */
         }
         else
-            hb_list_insert(list, pos++, new_adapter(HB_FILTER_HIP_DOWNLOAD));
+            hb_list_insert(list, pos++, new_adapter(HB_FILTER_HIP_DOWNLOAD, job_host_fmt(job)));
     }
     hb_list_insert(list, pos, cpu);
-    bracket_runs(list, pos + 1);
+    bracket_runs(list, pos + 1, job_host_fmt(job));
     return ret;
 }

@@ -138,6 +138,22 @@ int  hbhip_ctx_upload_done(hbhip_ctx *ctx, void *token, int block);
 int  hbhip_frame_mark_ready(hbhip_frame *fr);
 int  hbhip_frame_download_async(hbhip_frame *fr, const hbhip_host_frame *dst, void **token);
 int  hbhip_frame_download_wait(hbhip_frame *fr, void *token);
+/* Biplanar host pictures, NV12 and P010LE (what AMD's decoder hands out and its encoder takes in): plane 0 is luma,
+ * plane 1 interleaved Cb Cr.  The frame itself stays planar - `fr` is a planar 4:2:0 frame of depth 8 (NV12) or 10 (P010LE:
+ * samples >> 6 on the way in, << 6 on the way out) - and the repack is a kernel next to the copy, through a staging buffer
+ * the context keeps.  The async forms follow the ordering rule above: the split runs behind the H2D copy and is the
+ * frame's ready mark, the merge waits for the ready mark and the D2H copy for the merge; their tokens are finished with
+ * hbhip_ctx_upload_done / hbhip_frame_download_wait.  HBHIP_ERR_UNSUPPORTED: another depth, a frame that is not 4:2:0, a
+ * width or height below 2.
+ * An upload reads min(stride, row bytes rounded up to 64) bytes of EVERY row of `src`, the last row of each plane
+ * included - the row padding travels with the samples, as with hbhip_frame_upload - so each plane of `src` must be
+ * readable for stride * rows bytes.  A download writes the samples of each row only, or, where `dst` has the layout of
+ * hb_frame_buffer_init (64-byte rows, plane 1 right behind plane 0), the whole rows in one copy. */
+typedef struct hbhip_host_biplanar { uint8_t *plane[2]; int stride[2]; } hbhip_host_biplanar;
+int  hbhip_frame_upload_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *src);
+int  hbhip_frame_download_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *dst);
+int  hbhip_frame_upload_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *src, void **token);
+int  hbhip_frame_download_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *dst, void **token);
 
 /* ---- frames in, frames out: what a drop-in inside a device-resident run uses instead of push_dev / pull_dev -----------
  * hbhip_filter_use_frames(f) (once, before the first push): the filter's pictures are frames of its context's pool.
@@ -514,6 +530,14 @@ int  hbhip_blend_set_overlays(hbhip_blend *b, const hbhip_overlay *ov, int n);
 int  hbhip_blend_apply(hbhip_blend *b, const hbhip_host_frame *frame);       /* H2D, blend, D2H; synchronous */
 int  hbhip_blend_apply_dev(hbhip_blend *b, const hbhip_dev_frame *frame);    /* frame already in HBM */
 void hbhip_blend_destroy(hbhip_blend *b);                                    /* hb_blend_close (:875-885) */
+/* The same object for biplanar 4:2:0 host frames, depth 8 (NV12) or 10 (P010LE): blend8onbi8 / blend8onbi1x (:606-786) and
+ * blend_subsample_8onbi8 / _8onbi1x (:142-234, :330-423) on the samples as stored - P010 is composited MSB-aligned, not as
+ * planar 10-bit.  Overlays are set with hbhip_blend_set_overlays.  Such an object answers HBHIP_ERR_ARG to hbhip_blend_apply
+ * and _apply_dev, and one made by hbhip_blend_create answers it to hbhip_blend_apply_biplanar.  HBHIP_ERR_UNSUPPORTED:
+ * another depth, a width or height below 2. */
+int  hbhip_blend_create_biplanar(hbhip_ctx *ctx, int width, int height, int depth, int chroma_location,
+                                 int overlay_log2_chroma_w, int overlay_log2_chroma_h, hbhip_blend **out);
+int  hbhip_blend_apply_biplanar(hbhip_blend *b, const hbhip_host_biplanar *frame);   /* H2D, blend, D2H; synchronous */
 
 /* ---- test hook ------------------------------------------------------------------------------
  * The EEDI2 mask passes of a batch run as ONE launch whose tiles wait for the previous field's tiles (csrc/eedi2_engine.h:
