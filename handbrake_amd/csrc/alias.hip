@@ -19,6 +19,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -1032,7 +1033,11 @@ int lanczos_table(int src_dim, int dst_dim, double shift, std::vector<int> &idx,
 
 // libswscale's filter of one dimension for SWS_LANCZOS (utils.c:initFilter), formula for formula as oracle/alias_oracle.c:
 // orc_sws_filter states it (same libm, same expression order: the tables come out equal).  Returns the tap count.
-int sws_filter(int src, int dst, int one, int src_pos, int dst_pos, std::vector<int> &pos, std::vector<short> &coef)
+// bicubic: SWS_BICUBIC at its default parameters instead (B = 0, C = 0.6: the flags of libavfilter's auto-inserted `scale`;
+// the format filter's chroma down-sampling) - its own size factor, 4, and initFilter's integer cubic in d, in units of
+// 6 * fone; the normalisation, the cut-off trimming and the edge folding are the same code.
+int sws_filter(int src, int dst, int one, int src_pos, int dst_pos, std::vector<int> &pos, std::vector<short> &coef,
+               bool bicubic = false)
 {
     auto ilog2 = [](unsigned v) { int n = 0; while (v >>= 1) n++; return n; };
     const int64_t fone = 1LL << (54 - std::min(ilog2((unsigned)(src / dst)), 8));
@@ -1048,7 +1053,7 @@ int sws_filter(int src, int dst, int one, int src_pos, int dst_pos, std::vector<
     }
     else
     {
-        const int size_factor = 6;
+        const int size_factor = bicubic ? 4 : 6;
         size = x_inc <= (1 << 16) ? 1 + size_factor : 1 + (size_factor * src + dst - 1) / dst;
         size = std::max(std::min(size, src - 2), 1);
         f.assign((size_t)dst * size, 0);
@@ -1062,6 +1067,20 @@ int sws_filter(int src, int dst, int one, int src_pos, int dst_pos, std::vector<
                 int64_t d = std::llabs(((int64_t)xx * (1 << 17)) - x_dst_in_src) << 13;
                 if (x_inc > (1 << 16)) d = d * dst / src;
                 const double fd = (double)d * (1.0 / (1 << 30));
+                if (bicubic)
+                {
+                    const int64_t C = (int64_t)(0.6 * (1 << 24)), U = 1LL << 24;          // (B = 0 drops out of both arms)
+                    int64_t c = 0;
+                    if (d < (1LL << 31))
+                    {
+                        const int64_t dd = (d * d) >> 30, ddd = (dd * d) >> 30;
+                        c = d < (1LL << 30) ? (12 * U - 6 * C) * ddd + (-18 * U + 6 * C) * dd + 6 * U * (1LL << 30)
+                                            : -6 * C * ddd + 30 * C * dd - 48 * C * d + 24 * C * (1LL << 30);
+                    }
+                    f[(size_t)i * size + j] = c / ((1LL << 54) / fone);
+                    xx++;
+                    continue;
+                }
                 int64_t c = (int64_t)((d ? std::sin(fd * M_PI) * std::sin(fd * M_PI / 3.0) / (fd * fd * M_PI * M_PI / 3.0) : 1.0) * (double)fone);
                 if (fd > 3.0) c = 0;
                 f[(size_t)i * size + j] = c;
@@ -1574,6 +1593,313 @@ public:
     int full_range;
 };
 
+// ------------------------------------------------------------------ format (chroma down-sampling at equal depth)
+// `format=pix_fmts=...` when the target has fewer chroma samples than the stream (4:2:2 -> 4:2:0, 4:4:4 -> 4:2:2 / 4:2:0):
+// libavfilter's auto-inserted `scale` is then libswscale's general scaler at its default flags, bicubic.  Luma runs through
+// its identity filters and is a copy; Cb and Cr are filtered with the tables of sws_filter(bicubic) - 14-bit horizontal,
+// 12-bit vertical coefficients - and the intermediates of scale_sws_h_kernel / scale_sws_v_kernel (hScale8To15 /
+// hScale16To15, yuv2planeX_8 / _10 / _12).  PARITY UNPINNED like the rest of the family: libswscale is outside the
+// reference tree; the model is tests/format_resample_model.py.
+// Siting: vertically target row j lies midway between source rows 2j and 2j + 1 (srcPos = dstPos = 128); horizontally
+// target column i is co-sited with source column 2i (left-sited chroma: srcPos 128, dstPos 64), whatever the stream's
+// chroma_location says - the rule of the crop/scale drop-in's swscale branch.
+//
+// The kernel reads the tables in a NOMINAL form: output row / column j taps the FR_TAPS source rows / columns from
+// 2j + FR_BASE on, sws_filter's (position, coefficients) rows moved into that frame with zeros around them (a 2:1 bicubic
+// filter is 7 - 9 taps at 2j - 3 or, for an odd source size, one sample further left; create() checks that every row
+// fits).  That makes every window a compile-time offset that starts on an even sample, so both passes take their taps
+// two at a time (v_dot2_i32_i16): a thread owns four adjacent output columns (a dword of bytes, a qword of 16-bit
+// samples) and FR_ROWS (both passes: FR_ROWS_HV) output rows; the source rows under them are loaded ONCE, taken through
+// the horizontal pass (or the identity's shift) and kept in registers as 15-bit intermediates, a PAIR OF ROWS to a
+// dword; the vertical pass reads registers only.  No LDS.  The vertical coefficients of a row are the same for a whole wave (a wave is one
+// threadIdx.y) and come through scalar loads.
+//   4:2:2 -> 4:2:0   all FR_ROWS + FR_TAPS / 2 - 1 row pairs are loaded ahead of the arithmetic;
+//   4:4:4 -> 4:2:0   the window of FR_TAPS / 2 row pairs rolls down one pair an output row (the horizontal pass needs
+//                    the registers the whole window would take);
+//   4:4:4 -> 4:2:2   two rows a turn, the vertical identity applied to each half.
+constexpr int FR_TAPS = 10, FR_BASE = -4, FR_ROWS = 8, FR_ROWS_HV = 16, FR_LROWS = 4;
+struct FormatResampleArgs
+{
+    const uint8_t *src[FMT_FRAMES][3];
+    uint8_t       *dst[FMT_FRAMES][3];
+    int spitch[3], dpitch[3];
+    int w, h, scw, sch, dcw, dch, depth;      // luma size; chroma size of the source and of the target
+    int ly, cy;                               // grid.y: ly workgroup rows of luma, then cy of Cb, then cy of Cr
+    const short *hq, *vq;                     // [column][FR_TAPS] (columns padded to 4), [row][FR_TAPS]
+};
+
+// samples x0 .. x0 + 3 of a row (x0 a multiple of 4, possibly negative) as two dwords of 16-bit pairs; those outside
+// [0, w) read as 0 and are never loaded
+template <typename PIX>
+__device__ __forceinline__ void fr_load_pairs(const PIX *row, int x0, int w, uint32_t *p)
+{
+    if (x0 >= 0 && x0 + 3 < w)
+    {
+        if (sizeof(PIX) == 1)
+        {
+            const uint32_t d = *reinterpret_cast<const uint32_t *>(row + x0);
+            p[0] = __builtin_amdgcn_perm(0u, d, 0x0c010c00u);
+            p[1] = __builtin_amdgcn_perm(0u, d, 0x0c030c02u);
+        }
+        else
+        {
+            const uint2 d = *reinterpret_cast<const uint2 *>(row + x0);
+            p[0] = d.x; p[1] = d.y;
+        }
+    }
+    else
+    {
+        uint32_t v[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) v[i] = (x0 + i >= 0 && x0 + i < w) ? (uint32_t)row[x0 + i] : 0u;
+        p[0] = v[0] | (v[1] << 16); p[1] = v[2] | (v[3] << 16);
+    }
+}
+
+template <typename PIX>
+__device__ __forceinline__ void fr_store4(PIX *row, int x0, int w, const int *o)
+{
+    if (x0 + 3 < w)
+    {
+        if (sizeof(PIX) == 1) *reinterpret_cast<uint32_t *>(row + x0) = (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)o[3] << 24);
+        else                  *reinterpret_cast<uint2 *>(row + x0) = make_uint2((uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16));
+    }
+    else
+        for (int i = 0; x0 + i < w; i++) row[x0 + i] = (PIX)o[i];
+}
+
+// HP / VP: the chroma planes take a horizontal / a vertical pass.  grid.z = frame: the frames of a burst in one launch;
+// grid.y = the workgroup rows of luma (a thread moves four samples of FR_LROWS rows as dwords / qwords, the accesses of
+// format_kernel), then those of Cb, then those of Cr (a chroma thread row is FR_ROWS / FR_ROWS_HV output rows); grid.x
+// is sized for luma and the workgroups beyond a chroma plane return at once.
+template <typename PIX, bool HP, bool VP>
+__global__ __launch_bounds__(256, 4) void format_resample_kernel(FormatResampleArgs a)
+{
+    const int f = blockIdx.z;
+    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if ((int)blockIdx.y < a.ly)
+    {
+        const int y0 = (blockIdx.y * blockDim.y + threadIdx.y) * FR_LROWS;
+        if (x0 >= a.w) return;
+        const uint8_t *s = a.src[f][0];
+        uint8_t *d = a.dst[f][0];
+        if (x0 + 3 < a.w)
+        {
+            typedef typename std::conditional<sizeof(PIX) == 1, uint32_t, uint2>::type V;
+            V v[FR_LROWS];
+#pragma unroll
+            for (int r = 0; r < FR_LROWS; r++)
+                if (y0 + r < a.h) v[r] = *reinterpret_cast<const V *>(s + (size_t)(y0 + r) * a.spitch[0] + (size_t)x0 * sizeof(PIX));
+#pragma unroll
+            for (int r = 0; r < FR_LROWS; r++)
+                if (y0 + r < a.h) *reinterpret_cast<V *>(d + (size_t)(y0 + r) * a.dpitch[0] + (size_t)x0 * sizeof(PIX)) = v[r];
+        }
+        else
+            for (int r = 0; r < FR_LROWS && y0 + r < a.h; r++)
+                for (int i = 0; x0 + i < a.w; i++)
+                    reinterpret_cast<PIX *>(d + (size_t)(y0 + r) * a.dpitch[0])[x0 + i] = reinterpret_cast<const PIX *>(s + (size_t)(y0 + r) * a.spitch[0])[x0 + i];
+        return;
+    }
+    const int cby = (int)blockIdx.y - a.ly, c = 1 + cby / a.cy;
+    constexpr int ROWS = HP && VP ? FR_ROWS_HV : FR_ROWS;                    // output rows a thread
+    const int j0 = __builtin_amdgcn_readfirstlane((cby % a.cy) * blockDim.y + threadIdx.y) * ROWS;      // the first one: one value a wave
+    if (x0 >= a.dcw || j0 >= a.dch) return;
+    const int sh = sizeof(PIX) == 1 ? 7 : a.depth - 1;                       // hScale8To15_c / hScale16To15_c
+    // yuv2planeX_8_c: the flat dither of 64 (round = 64 << 12, shift 19); yuv2planeX_10 / _12: half of the shift 27 - depth
+    const int shift = sizeof(PIX) == 1 ? 19 : 27 - a.depth, round = sizeof(PIX) == 1 ? 64 << 12 : 1 << (shift - 1);
+    const int vmax = (1 << a.depth) - 1;
+    const uint8_t *sp = a.src[f][c];
+    const int spitch = a.spitch[c];
+    uint32_t hc[HP ? 2 * FR_TAPS : 1];                                       // the four columns' coefficients, in pairs
+    if (HP)
+    {
+        const uint4 *q = reinterpret_cast<const uint4 *>(a.hq + (size_t)x0 * FR_TAPS);      // 80 bytes a thread, 16-byte aligned
+#pragma unroll
+        for (int k = 0; k < FR_TAPS / 2; k++)
+        {
+            const uint4 t = q[k];
+            hc[4 * k] = t.x; hc[4 * k + 1] = t.y; hc[4 * k + 2] = t.z; hc[4 * k + 3] = t.w;
+        }
+    }
+    // source rows sr, sr + 1 (clamped into the plane: the rows outside of it have coefficient 0) -> the four columns'
+    // intermediates, row sr in the low and row sr + 1 in the high half of e[column]
+    auto hpair = [&](int sr, uint32_t *e) {
+        const PIX *ra = reinterpret_cast<const PIX *>(sp + (size_t)min(max(sr, 0), a.sch - 1) * spitch);
+        const PIX *rb = reinterpret_cast<const PIX *>(sp + (size_t)min(max(sr + 1, 0), a.sch - 1) * spitch);
+        if (HP)
+        {
+            uint32_t pa[8], pb[8];                                           // the sixteen samples under the four columns, in pairs
+#pragma unroll
+            for (int g = 0; g < 4; g++)
+            {
+                fr_load_pairs(ra, 2 * x0 + FR_BASE + 4 * g, a.scw, pa + 2 * g);
+                fr_load_pairs(rb, 2 * x0 + FR_BASE + 4 * g, a.scw, pb + 2 * g);
+            }
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+            {
+                int va = 0, vb = 0;
+#pragma unroll
+                for (int u = 0; u < FR_TAPS / 2; u++)
+                {
+                    va = dot2(pa[i + u], hc[i * (FR_TAPS / 2) + u], va);
+                    vb = dot2(pb[i + u], hc[i * (FR_TAPS / 2) + u], vb);
+                }
+                va = min(va >> sh, (1 << 15) - 1);
+                vb = min(vb >> sh, (1 << 15) - 1);
+                e[i] = ((uint32_t)va & 0xffffu) | ((uint32_t)vb << 16);
+            }
+        }
+        else
+        {
+            // the identity filter, one tap of 1 << 14: (s << 14) >> sh, below 1 << 15 for every sample - both halves in one shift
+            uint32_t pa[2], pb[2];
+            fr_load_pairs(ra, x0, a.scw, pa);
+            fr_load_pairs(rb, x0, a.scw, pb);
+#pragma unroll
+            for (int g = 0; g < 2; g++)
+            {
+                e[2 * g]     = __builtin_amdgcn_perm(pb[g], pa[g], 0x05040100u) << (14 - sh);
+                e[2 * g + 1] = __builtin_amdgcn_perm(pb[g], pa[g], 0x07060302u) << (14 - sh);
+            }
+        }
+    };
+    auto put = [&](int j, const int *acc) {
+        int o[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) o[i] = min(max(acc[i] >> shift, 0), vmax);
+        fr_store4(reinterpret_cast<PIX *>(a.dst[f][c] + (size_t)j * a.dpitch[c]), x0, a.dcw, o);
+    };
+    // output row j from the FR_TAPS / 2 row pairs at win
+    auto vrow = [&](int j, const uint32_t (*win)[4]) {
+        const uint32_t *vq = reinterpret_cast<const uint32_t *>(a.vq + (size_t)j * FR_TAPS);
+        int acc[4] = { round, round, round, round };
+#pragma unroll
+        for (int u = 0; u < FR_TAPS / 2; u++)
+        {
+            const uint32_t q = vq[u];
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc[i] = dot2(win[u][i], q, acc[i]);
+        }
+        put(j, acc);
+    };
+    if (!HP)
+    {
+        constexpr int NP = FR_ROWS + FR_TAPS / 2 - 1;
+        uint32_t hp[NP][4];
+#pragma unroll
+        for (int k = 0; k < NP; k++) hpair(2 * (j0 + k) + FR_BASE, hp[k]);
+#pragma unroll
+        for (int r = 0; r < FR_ROWS; r++)
+            if (j0 + r < a.dch) vrow(j0 + r, hp + r);
+    }
+    else if (!VP)
+    {
+#pragma unroll
+        for (int r = 0; r < ROWS; r += 2)
+        {
+            if (j0 + r >= a.dch) break;
+            uint32_t e[4];
+            hpair(j0 + r, e);
+            int lo[4], hi[4];                                                // the identity filter: one tap of 1 << 12
+#pragma unroll
+            for (int i = 0; i < 4; i++) { lo[i] = round + ((int)(short)(e[i] & 0xffffu) << 12); hi[i] = round + (((int)e[i] >> 16) << 12); }
+            put(j0 + r, lo);
+            if (j0 + r + 1 < a.dch) put(j0 + r + 1, hi);
+        }
+    }
+    else
+    {
+        uint32_t win[FR_TAPS / 2][4] = {};
+#pragma unroll 2
+        for (int r = 1 - FR_TAPS / 2; r < ROWS && j0 + r < a.dch; r++)        // (the first FR_TAPS / 2 - 1 turns only fill the window)
+        {
+#pragma unroll
+            for (int u = 0; u < FR_TAPS / 2 - 1; u++)
+#pragma unroll
+                for (int i = 0; i < 4; i++) win[u][i] = win[u + 1][i];
+            hpair(2 * (j0 + r) + FR_BASE + FR_TAPS - 2, win[FR_TAPS / 2 - 1]);
+            if (r >= 0) vrow(j0 + r, win);
+        }
+    }
+}
+
+class FormatResampleFilter : public BurstFilter
+{
+public:
+    using BurstFilter::BurstFilter;
+    ~FormatResampleFilter() override
+    {
+        if (d_hq) (void)hipFree(d_hq);
+        if (d_vq) (void)hipFree(d_vq);
+    }
+    // sws_filter's rows in the kernel's nominal frame; false: a row has a tap outside of it
+    static bool nominal(int src, int dst, int one, int src_pos, int dst_pos, int pad, std::vector<short> &out)
+    {
+        std::vector<int> pos;
+        std::vector<short> coef;
+        const int taps = sws_filter(src, dst, one, src_pos, dst_pos, pos, coef, true);
+        out.assign((size_t)((dst + pad - 1) / pad * pad) * FR_TAPS, 0);
+        for (int i = 0; i < dst; i++)
+            for (int t = 0; t < taps; t++)
+            {
+                const short q = coef[(size_t)i * taps + t];
+                if (q == 0) continue;
+                const int k = pos[i] + t - (2 * i + FR_BASE);
+                if (k < 0 || k >= FR_TAPS || pos[i] + t >= src) return false;
+                out[(size_t)i * FR_TAPS + k] = q;
+            }
+        return true;
+    }
+    int setup()
+    {
+        hpass = out_geo.log2_cw > in_geo.log2_cw;
+        vpass = out_geo.log2_ch > in_geo.log2_ch;
+        auto up = [&](short *&dptr, const std::vector<short> &v) -> int {
+            HBHIP_CHECK(ctx, hipMalloc((void **)&dptr, sizeof(short) * v.size()));
+            HBHIP_CHECK(ctx, hipMemcpy(dptr, v.data(), sizeof(short) * v.size(), hipMemcpyHostToDevice));
+            return HBHIP_OK;
+        };
+        std::vector<short> q;
+        // left-sited chroma: source position 128 (4:4:4 has no siting), target position 128 >> 1; rows: centred, 128 both
+        if (hpass)
+        {
+            if (!nominal(in_geo.pw[1], out_geo.pw[1], 1 << 14, 128, 64, 4, q)) return HBHIP_ERR_UNSUPPORTED;
+            const int rc = up(d_hq, q);
+            if (rc != HBHIP_OK) return rc;
+        }
+        if (vpass)
+        {
+            if (!nominal(in_geo.ph[1], out_geo.ph[1], 1 << 12, 128, 128, 1, q)) return HBHIP_ERR_UNSUPPORTED;
+            const int rc = up(d_vq, q);
+            if (rc != HBHIP_OK) return rc;
+        }
+        return HBHIP_OK;
+    }
+    int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
+    {
+        return hbhip_for_each_burst<FMT_FRAMES, FormatResampleArgs>(ctx, ins, outs, n, [&](FormatResampleArgs &a, int nf, int, uintptr_t bits) {
+            if ((bits & 7) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
+            a.w = in_geo.width; a.h = in_geo.height; a.depth = in_geo.depth;
+            a.scw = in_geo.pw[1]; a.sch = in_geo.ph[1]; a.dcw = out_geo.pw[1]; a.dch = out_geo.ph[1];
+            a.hq = d_hq; a.vq = d_vq;
+            a.ly = (a.h + 4 * FR_LROWS - 1) / (4 * FR_LROWS);
+            const int rows = 4 * (hpass && vpass ? FR_ROWS_HV : FR_ROWS);     // output rows a workgroup
+            a.cy = (a.dch + rows - 1) / rows;
+            const dim3 grid(hbhip_grid_x((a.w + 255) / 256), a.ly + 2 * a.cy, nf);
+#define FR_GO(PIX, HP, VP) HBHIP_LAUNCH(ctx, "format_resample", (format_resample_kernel<PIX, HP, VP>), grid, dim3(64, 4), 0, a)
+#define FR_PICK(PIX) do { if (hpass && vpass) FR_GO(PIX, true, true); else if (hpass) FR_GO(PIX, true, false); else FR_GO(PIX, false, true); } while (0)
+            if (in_geo.bps == 1) FR_PICK(uint8_t);
+            else                 FR_PICK(uint16_t);
+#undef FR_PICK
+#undef FR_GO
+            return HBHIP_OK;
+        });
+    }
+    bool hpass = false, vpass = false;
+    short *d_hq = nullptr, *d_vq = nullptr;
+};
+
 } // namespace
 
 extern "C" int hbhip_format_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth,
@@ -1589,6 +1915,33 @@ extern "C" int hbhip_format_create(hbhip_ctx *ctx, int width, int height, int sr
     go.set(width, height, dst_depth, log2_chroma_w, log2_chroma_h);
     *out = hbhip_make_filter<FormatFilter>(ctx, gi, go, full_range);
     return *out ? HBHIP_OK : HBHIP_ERR_NOMEM;
+}
+
+extern "C" int hbhip_format_resample_create(hbhip_ctx *ctx, int width, int height, int depth, int src_log2_cw, int src_log2_ch,
+                                            int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out)
+{
+    if (!ctx || !out) return HBHIP_ERR_ARG;
+    *out = nullptr;
+    if (depth != 8 && depth != 10 && depth != 12) return HBHIP_ERR_UNSUPPORTED;
+    if (width < 1 || height < 1) return HBHIP_ERR_ARG;
+    if (!hbhip_yuv_layout_ok(src_log2_cw, src_log2_ch) || !hbhip_yuv_layout_ok(dst_log2_cw, dst_log2_ch)) return HBHIP_ERR_UNSUPPORTED;
+    // down only: no dimension gains chroma samples and one loses some
+    if (dst_log2_cw < src_log2_cw || dst_log2_ch < src_log2_ch ||
+        (dst_log2_cw == src_log2_cw && dst_log2_ch == src_log2_ch)) return HBHIP_ERR_UNSUPPORTED;
+    (void)chroma_location;                      // every value is taken as left-sited (the crop/scale drop-in's rule)
+    PicGeometry gi, go;
+    gi.set(width, height, depth, src_log2_cw, src_log2_ch);
+    go.set(width, height, depth, dst_log2_cw, dst_log2_ch);
+    // a chroma plane so small that initFilter's clamp (size = min(size, src - 2)) cuts the nine taps short: swscale's
+    // filter is then something else than a bicubic, and nobody's to restate
+    if ((dst_log2_cw > src_log2_cw && gi.pw[1] - 2 < 9) || (dst_log2_ch > src_log2_ch && gi.ph[1] - 2 < 9))
+        return HBHIP_ERR_UNSUPPORTED;
+    FormatResampleFilter *f = hbhip_make_filter<FormatResampleFilter>(ctx, gi, go);
+    if (!f) return HBHIP_ERR_NOMEM;
+    const int rc = f->setup();
+    if (rc != HBHIP_OK) { delete f; return rc; }
+    *out = f;
+    return HBHIP_OK;
 }
 
 extern "C" int hbhip_pad_create(hbhip_ctx *ctx, const hbhip_pad_params *p, int width, int height, int depth,

@@ -213,9 +213,15 @@ static int rotate_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
  * libavfilter (:97-100) and sets init->pix_fmt (:107); the conversion itself is the `scale` filter
  * libavfilter auto-inserts, i.e. libswscale.  work.c adds it when the encoder wants another pixel format
  * than the pipeline's (work.c:1530-1549), typically 8 <-> 10 bits.  Here it is a real filter for what that
- * use needs - planar YUV depth changes with the subsampling unchanged (csrc/alias.hip:format_kernel,
- * parity unpinned); any other target (different subsampling, semi-planar, RGB) makes init() fail, which
- * keeps the CPU filter (work.c:1861-1868). */
+ * use needs (parity unpinned):
+ *   - planar YUV depth changes with the subsampling unchanged (csrc/alias.hip:format_kernel);
+ *   - planar YUV chroma DOWN-sampling at equal depth, 4:2:2 -> 4:2:0, 4:4:4 -> 4:2:2, 4:4:4 -> 4:2:0
+ *     (format_resample_kernel): hb_get_best_pix_fmt never goes below the title's chroma (common.c:7516-7604), so a 4:2:2
+ *     source in front of a 4:2:0-only encoder gets `format=yuv420p10le` behind its yuv422p10le chain (work.c:1525-1552).
+ * Any other target makes init() fail, which keeps the CPU filter (work.c:1861-1868): more chroma samples than the
+ * stream has (the rule above never asks for it), a subsampling change together with a depth change (swscale does both
+ * in one scaler pass with a dither of its own), semi-planar and RGB targets, a chroma plane too small for swscale's nine
+ * taps. */
 static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
 static int format_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
 
@@ -249,18 +255,25 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     const int dst_fmt = av_get_pix_fmt(format);                               /* :107 */
     free(format);
     const AVPixFmtDescriptor *dd = av_pix_fmt_desc_get(dst_fmt);
-    if (dd == NULL || dd->nb_components != desc->nb_components || desc->nb_components < 3 ||
-        dd->log2_chroma_w != desc->log2_chroma_w || dd->log2_chroma_h != desc->log2_chroma_h)
+    if (dd == NULL || dd->nb_components != desc->nb_components || desc->nb_components < 3)
         return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
     /* a component per plane on both sides: NV12 / P010 (Cb and Cr on plane 1) are the adapters' business, not this filter's */
     for (int c = 0; c < 3; c++)
         if (dd->comp[c].plane != c || desc->comp[c].plane != c)
             return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
+    const int resample = dd->log2_chroma_w != desc->log2_chroma_w || dd->log2_chroma_h != desc->log2_chroma_h;
+    /* fewer chroma samples AND another depth: one swscale pass with its own dither, not these two filters in a row */
+    if (resample && dd->comp[0].depth != desc->comp[0].depth)
+        return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
     hbhip_ctx *ctx = hbhip_host_ctx_for(init);
     if (ctx == NULL) return hbhip_host_simple_fail(filter, HBHIP_ERR_NODEVICE);
-    int rc = hbhip_format_create(ctx, init->geometry.width, init->geometry.height, desc->comp[0].depth,
-                                 dd->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h,
-                                 init->color_range == 2 /* AVCOL_RANGE_JPEG */, &pv->s.dev);
+    /* (the create functions decline what is left: upsampling, other depths, planes too small) */
+    int rc = resample ? hbhip_format_resample_create(ctx, init->geometry.width, init->geometry.height, desc->comp[0].depth,
+                                                     desc->log2_chroma_w, desc->log2_chroma_h, dd->log2_chroma_w,
+                                                     dd->log2_chroma_h, init->chroma_location, &pv->s.dev)
+                      : hbhip_format_create(ctx, init->geometry.width, init->geometry.height, desc->comp[0].depth,
+                                            dd->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h,
+                                            init->color_range == 2 /* AVCOL_RANGE_JPEG */, &pv->s.dev);
     if (rc != HBHIP_OK) return hbhip_host_simple_fail(filter, rc);
     init->pix_fmt = dst_fmt;
     pv->s.output = *init;

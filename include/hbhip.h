@@ -474,6 +474,16 @@ int hbhip_bm3d_create(hbhip_ctx *ctx, const hbhip_bm3d_params *p, int width, int
  * oracle/alias_oracle.c:orc_format_plane only (parity unpinned). */
 int hbhip_format_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth,
                         int log2_chroma_w, int log2_chroma_h, int full_range, hbhip_filter **out);
+/* The same filter when the target has FEWER chroma samples than the stream, at equal depth (8 / 10 / 12): 4:2:2 -> 4:2:0,
+ * 4:4:4 -> 4:2:2, 4:4:4 -> 4:2:0.  libavfilter's `scale` is then libswscale's general scaler at its default flags: luma a
+ * copy, Cb and Cr through the bicubic (B = 0, C = 0.6) integer tables - 14-bit horizontal, 12-bit vertical coefficients,
+ * 15-bit intermediates.  Target row j lies midway between source rows 2j and 2j + 1, target column i on source column 2i
+ * (left-sited chroma); `chroma_location` is accepted and every value is taken as left-sited, as the crop/scale filter's
+ * swscale form does.  HBHIP_ERR_UNSUPPORTED: upsampling in either direction, equal subsampling, a depth outside
+ * 8 / 10 / 12, a chroma plane under 11 samples in a direction that is resampled (libswscale shortens its filter there).
+ * Arithmetic pinned to tests/format_resample_model.py only (parity unpinned). */
+int hbhip_format_resample_create(hbhip_ctx *ctx, int width, int height, int depth, int src_log2_cw, int src_log2_ch,
+                                 int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out);
 /* The zscale [-> format=gbrpf32le -> tonemap] -> zscale -> format graph colorspace_init builds
  * (colorspace.c:126-193): matrix / range / transfer / primaries conversion, with tone mapping
  * when the source transfer is SMPTE 2084 or ARIB STD-B67 and the transfer changes.  Colour ids

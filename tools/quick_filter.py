@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Times one stateless filter's batch path (16 device-resident 1080p frames per call) with the context's kernel timer.
 usage: quick_filter.py unsharp|chroma_smooth|lapsharp|colorspace_sdr|colorspace_matrix|grayscale|rotate|scale<W>x<H>|
+                      format8to10|format10to8|format_422_420[_10]|format_444_422[_10]|format_444_420[_10]|
                       deblock_<preset>_<tune>[_10]|deband[_<range>][_10][_tile|_gather]|bm3d[_<sigma>][_10] [reps]
 Prints one line per kernel: name, launches, average us.  For knob experiments with tools/dev_run.sh."""
 import ctypes as C, json, os, sys
@@ -11,10 +12,10 @@ from handbrake_amd import hip, synth
 W, H, NB = int(os.environ.get("QF_W", 1920)), int(os.environ.get("QF_H", 1080)), 16
 
 
-def planes(w, h, dtype=torch.uint8):
+def planes(w, h, dtype=torch.uint8, sub=(1, 1)):
     def plane(pw, ph):
         return torch.empty((ph, (pw + 63) // 64 * 64), dtype=dtype, device="cuda")[:, :pw]
-    return [plane(w, h), plane(w // 2, h // 2), plane(w // 2, h // 2)]
+    return [plane(w, h), plane(w >> sub[0], h >> sub[1]), plane(w >> sub[0], h >> sub[1])]
 
 
 def deint(ctx, what, reps):
@@ -62,6 +63,7 @@ def main():
     ow, oh = W, H
     depth_in = depth_out = 8
     picture = "progressive"
+    sub_in = sub_out = (1, 1)                          # log2 chroma subsampling of the frames going in / coming out
     if what == "unsharp": make = lambda: mk_blur("hbhip_unsharp_create")
     elif what == "unsharp5": make = lambda: mk_blur("hbhip_unsharp_create", size=5)
     elif what == "chroma_smooth": make = lambda: mk_blur("hbhip_chroma_smooth_create", 0)
@@ -81,6 +83,12 @@ def main():
         sd, dd = (8, 10) if what == "format8to10" else (10, 8)
         make = lambda: hip._create("hbhip_format_create", ctx, [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_void_p)], ctx.h, W, H, sd, dd, 1, 1, 0)
         depth_in, depth_out = sd, dd
+    elif what.startswith("format_"):                   # format_422_420, format_444_420_10 ...: chroma down-sampling at equal depth
+        parts = what.split("_")
+        subs = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
+        sub_in, sub_out = subs[parts[1]], subs[parts[2]]
+        depth_in = depth_out = 10 if parts[-1] == "10" else 8
+        make = lambda: hip.format_resample_device_filter(ctx, W, H, sub_in, sub_out, depth_in)
     elif what.startswith("scale"):                     # scale960x540, scale1280x720, scale3840x2160 ...
         ow, oh = (int(v) for v in what[5:].split("x"))
         make = lambda: hip.cropscale_device_filter(ctx, W, H, ow, oh)
@@ -141,9 +149,13 @@ def main():
         return deint(ctx, what, reps)
     else:
         raise SystemExit("unknown filter " + what)
-    frames = synth.stream(picture, W, H, 4, depth=depth_in) if depth_in != 8 else synth.stream(picture, W, H, 4)
+    if sub_in != (1, 1):
+        chroma = {(1, 0): "2x1", (0, 0): "1x1"}[sub_in]
+        frames = [synth.picture(picture, W, H, t, depth=depth_in, chroma=chroma) for t in range(4)]
+    else:
+        frames = synth.stream(picture, W, H, 4, depth=depth_in) if depth_in != 8 else synth.stream(picture, W, H, 4)
     dev_in = [[torch.from_numpy(p.view(np.int16) if depth_in != 8 else p).cuda() for p in fr] for fr in frames]
-    outs = [planes(ow, oh, torch.int16 if depth_out != 8 else torch.uint8) for _ in range(NB)]
+    outs = [planes(ow, oh, torch.int16 if depth_out != 8 else torch.uint8, sub_out) for _ in range(NB)]
     torch.cuda.synchronize()
     flt = make()
     arr_in = (hip.DevFrame * NB)(*[hip.dev_frame(dev_in[i % 4]) for i in range(NB)])
