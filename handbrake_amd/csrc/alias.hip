@@ -1628,6 +1628,25 @@ struct FormatResampleArgs
     const short *hq, *vq;                     // [column][FR_TAPS] (columns padded to 4), [row][FR_TAPS]
 };
 
+// The scaled form's extra arguments.  dither: libswscale's ff_dither_8x8_128, row r in dwords 2r (columns 0 .. 3, a byte
+// each) and 2r + 1 (columns 4 .. 7).
+struct FormatScaledArgs : FormatResampleArgs
+{
+    int ddepth;                               // the target's depth (`depth` is the source's)
+    uint32_t dither[16];
+};
+__device__ __forceinline__ int fr_ddepth(const FormatResampleArgs &a) { return a.depth; }
+__device__ __forceinline__ int fr_ddepth(const FormatScaledArgs &a) { return a.ddepth; }
+
+// the dither bytes of output row y, columns x0 .. x0 + 3 (x0 a multiple of 4): Y and Cb read the table at column x, Cr at
+// x + 3 (yuv2planeX_8_c's offset argument, yuv2nv12cX_c's two halves) - bytes 3 .. 6, or 7, 0, 1, 2, of the row's eight
+__device__ __forceinline__ uint32_t fr_dither4(const FormatScaledArgs &a, int y, int x0, bool cr)
+{
+    const uint32_t lo = a.dither[2 * (y & 7)], hi = a.dither[2 * (y & 7) + 1];
+    const uint32_t p = (x0 & 4) ? hi : lo, q = (x0 & 4) ? lo : hi;
+    return cr ? __builtin_amdgcn_alignbyte(q, p, 3u) : p;
+}
+
 // samples x0 .. x0 + 3 of a row (x0 a multiple of 4, possibly negative) as two dwords of 16-bit pairs; those outside
 // [0, w) read as 0 and are never loaded
 template <typename PIX>
@@ -1668,16 +1687,68 @@ __device__ __forceinline__ void fr_store4(PIX *row, int x0, int w, const int *o)
         for (int i = 0; x0 + i < w; i++) row[x0 + i] = (PIX)o[i];
 }
 
+// The scaler on identity filters, rows y0 .. y0 + FR_LROWS - 1 of plane c (w x h), columns x0 .. x0 + 3 < w + 3:
+// hScale16To15's one tap, v << (15 - depth), then yuv2plane1_8 - (t + dither) >> 7 - or yuv2plane1_10, (t + 16) >> 5,
+// clipped at the top (nothing is negative here).  The loads go ahead of the arithmetic; a qword in, a dword or a qword out.
+template <typename DPIX>
+__device__ __forceinline__ void fr_identity_rows(const FormatScaledArgs &a, int f, int c, int x0, int y0, int w, int h)
+{
+    const uint8_t *s = a.src[f][c];
+    uint8_t *d = a.dst[f][c];
+    const int up = 15 - a.depth, vmax = (1 << a.ddepth) - 1;
+    uint32_t p[FR_LROWS][2];
+#pragma unroll
+    for (int r = 0; r < FR_LROWS; r++)
+        if (y0 + r < h) fr_load_pairs(reinterpret_cast<const uint16_t *>(s + (size_t)(y0 + r) * a.spitch[c]), x0, w, p[r]);
+#pragma unroll
+    for (int r = 0; r < FR_LROWS; r++)
+    {
+        if (y0 + r >= h) break;
+        const uint32_t dm = sizeof(DPIX) == 1 ? fr_dither4(a, y0 + r, x0, c == 2) : 0u;
+        int o[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+        {
+            const int t = (int)((p[r][i >> 1] >> (16 * (i & 1))) & 0xffffu) << up;
+            o[i] = sizeof(DPIX) == 1 ? min((t + (int)((dm >> (8 * i)) & 0xffu)) >> 7, vmax) : min((t + 16) >> 5, vmax);
+        }
+        fr_store4(reinterpret_cast<DPIX *>(d + (size_t)(y0 + r) * a.dpitch[c]), x0, w, o);
+    }
+}
+
 // HP / VP: the chroma planes take a horizontal / a vertical pass.  grid.z = frame: the frames of a burst in one launch;
 // grid.y = the workgroup rows of luma (a thread moves four samples of FR_LROWS rows as dwords / qwords, the accesses of
 // format_kernel), then those of Cb, then those of Cr (a chroma thread row is FR_ROWS / FR_ROWS_HV output rows); grid.x
 // is sized for luma and the workgroups beyond a chroma plane return at once.
-template <typename PIX, bool HP, bool VP>
-__global__ __launch_bounds__(256, 4) void format_resample_kernel(FormatResampleArgs a)
+//
+// SC: the scaled form, a LOWER target depth - 10 -> 8, 12 -> 8, 12 -> 10 bits (DPIX: the target's sample type; Args:
+// FormatScaledArgs).  The chroma passes are the same; what changes is the intermediate's shift (the source depth), the output
+// stage (the target depth: to 8 bits its round term is the 8 x 8 ordered dither, a byte a column) and the store type.
+// Luma is no copy then but the identity filter and the output stage, and so are Cb and Cr where neither pass is taken
+// (4:2:0 -> 4:2:0, the planar step in front of the NV12 / P010LE repack).  The model is tests/format_scaled_model.py.
+// The equal-depth instantiations take the defaults and compile to the instructions they had before the form existed.
+template <typename PIX, bool HP, bool VP, typename DPIX = PIX, bool SC = false, class Args = FormatResampleArgs>
+__global__ __launch_bounds__(256, 4) void format_resample_kernel(Args a)
 {
+    static_assert(SC || ((HP || VP) && std::is_same<PIX, DPIX>::value), "equal depth: one pass at least, one sample type");
     const int f = blockIdx.z;
     const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if ((int)blockIdx.y < a.ly)
+    if constexpr (SC)
+    {
+        // the planes that take no pass: a thread row is FR_LROWS rows (one value a wave, as the dither's row has to be)
+        const bool luma = (int)blockIdx.y < a.ly;
+        if (luma || (!HP && !VP))
+        {
+            const int cby = (int)blockIdx.y - a.ly, c = luma ? 0 : 1 + cby / a.cy;
+            const int wy = luma ? (int)blockIdx.y : cby % a.cy;
+            const int y0 = __builtin_amdgcn_readfirstlane(wy * blockDim.y + threadIdx.y) * FR_LROWS;
+            const int w = luma ? a.w : a.dcw, h = luma ? a.h : a.dch;
+            if (x0 >= w || y0 >= h) return;
+            fr_identity_rows<DPIX>(a, f, c, x0, y0, w, h);
+            return;
+        }
+    }
+    else if ((int)blockIdx.y < a.ly)
     {
         const int y0 = (blockIdx.y * blockDim.y + threadIdx.y) * FR_LROWS;
         if (x0 >= a.w) return;
@@ -1706,8 +1777,10 @@ __global__ __launch_bounds__(256, 4) void format_resample_kernel(FormatResampleA
     if (x0 >= a.dcw || j0 >= a.dch) return;
     const int sh = sizeof(PIX) == 1 ? 7 : a.depth - 1;                       // hScale8To15_c / hScale16To15_c
     // yuv2planeX_8_c: the flat dither of 64 (round = 64 << 12, shift 19); yuv2planeX_10 / _12: half of the shift 27 - depth
-    const int shift = sizeof(PIX) == 1 ? 19 : 27 - a.depth, round = sizeof(PIX) == 1 ? 64 << 12 : 1 << (shift - 1);
-    const int vmax = (1 << a.depth) - 1;
+    // (the scaled form: yuv2planeX_8_c's round term is the dither, seed() below; to 10 bits it is the flat half as well)
+    const int ddepth = fr_ddepth(a);
+    const int shift = sizeof(DPIX) == 1 ? 19 : 27 - ddepth, round = sizeof(DPIX) == 1 ? 64 << 12 : 1 << (shift - 1);
+    const int vmax = (1 << ddepth) - 1;
     const uint8_t *sp = a.src[f][c];
     const int spitch = a.spitch[c];
     uint32_t hc[HP ? 2 * FR_TAPS : 1];                                       // the four columns' coefficients, in pairs
@@ -1768,12 +1841,27 @@ __global__ __launch_bounds__(256, 4) void format_resample_kernel(FormatResampleA
         int o[4];
 #pragma unroll
         for (int i = 0; i < 4; i++) o[i] = min(max(acc[i] >> shift, 0), vmax);
-        fr_store4(reinterpret_cast<PIX *>(a.dst[f][c] + (size_t)j * a.dpitch[c]), x0, a.dcw, o);
+        fr_store4(reinterpret_cast<DPIX *>(a.dst[f][c] + (size_t)j * a.dpitch[c]), x0, a.dcw, o);
+    };
+    // the round term of output row j's four columns
+    auto seed = [&](int j, int *acc) {
+        if constexpr (SC && sizeof(DPIX) == 1)
+        {
+            const uint32_t dm = fr_dither4(a, j, x0, c == 2);
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc[i] = (int)((dm >> (8 * i)) & 0xffu) << 12;
+        }
+        else
+        {
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc[i] = round;
+        }
     };
     // output row j from the FR_TAPS / 2 row pairs at win
     auto vrow = [&](int j, const uint32_t (*win)[4]) {
         const uint32_t *vq = reinterpret_cast<const uint32_t *>(a.vq + (size_t)j * FR_TAPS);
         int acc[4] = { round, round, round, round };
+        if constexpr (SC) seed(j, acc);
 #pragma unroll
         for (int u = 0; u < FR_TAPS / 2; u++)
         {
@@ -1804,6 +1892,14 @@ __global__ __launch_bounds__(256, 4) void format_resample_kernel(FormatResampleA
             int lo[4], hi[4];                                                // the identity filter: one tap of 1 << 12
 #pragma unroll
             for (int i = 0; i < 4; i++) { lo[i] = round + ((int)(short)(e[i] & 0xffffu) << 12); hi[i] = round + (((int)e[i] >> 16) << 12); }
+            if constexpr (SC)
+            {
+                int da[4], db[4];
+                seed(j0 + r, da);
+                seed(j0 + r + 1, db);
+#pragma unroll
+                for (int i = 0; i < 4; i++) { lo[i] += da[i] - round; hi[i] += db[i] - round; }
+            }
             put(j0 + r, lo);
             if (j0 + r + 1 < a.dch) put(j0 + r + 1, hi);
         }
@@ -1876,8 +1972,39 @@ public:
         }
         return HBHIP_OK;
     }
+    // the scaled form: a lower target depth, with or without a pass
+    int process_scaled(DevPicture *const *ins, DevPicture *const *outs, int n)
+    {
+        // libswscale's ff_dither_8x8_128
+        static const uint8_t dither[8][8] = {
+            {  36,  68,  60,  92,  34,  66,  58,  90 }, { 100,   4, 124,  28,  98,   2, 122,  26 },
+            {  52,  84,  44,  76,  50,  82,  42,  74 }, { 116,  20, 108,  12, 114,  18, 106,  10 },
+            {  32,  64,  56,  88,  38,  70,  62,  94 }, {  96,   0, 120,  24, 102,   6, 126,  30 },
+            {  48,  80,  40,  72,  54,  86,  46,  78 }, { 112,  16, 104,   8, 118,  22, 110,  14 } };
+        return hbhip_for_each_burst<FMT_FRAMES, FormatScaledArgs>(ctx, ins, outs, n, [&](FormatScaledArgs &a, int nf, int, uintptr_t bits) {
+            if ((bits & 7) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
+            a.w = in_geo.width; a.h = in_geo.height; a.depth = in_geo.depth; a.ddepth = out_geo.depth;
+            a.scw = in_geo.pw[1]; a.sch = in_geo.ph[1]; a.dcw = out_geo.pw[1]; a.dch = out_geo.ph[1];
+            a.hq = d_hq; a.vq = d_vq;
+            for (int r = 0; r < 8; r++)
+                for (int k = 0; k < 8; k++) a.dither[2 * r + k / 4] |= (uint32_t)dither[r][k] << (8 * (k & 3));
+            a.ly = (a.h + 4 * FR_LROWS - 1) / (4 * FR_LROWS);
+            const int rows = 4 * (hpass && vpass ? FR_ROWS_HV : hpass || vpass ? FR_ROWS : FR_LROWS);     // output rows a workgroup
+            a.cy = (a.dch + rows - 1) / rows;
+            const dim3 grid(hbhip_grid_x((a.w + 255) / 256), a.ly + 2 * a.cy, nf);
+#define FS_GO(DPIX, HP, VP) HBHIP_LAUNCH(ctx, "format_scaled", (format_resample_kernel<uint16_t, HP, VP, DPIX, true, FormatScaledArgs>), grid, dim3(64, 4), 0, a)
+#define FS_PICK(DPIX) do { if (hpass && vpass) FS_GO(DPIX, true, true); else if (hpass) FS_GO(DPIX, true, false); \
+                           else if (vpass) FS_GO(DPIX, false, true); else FS_GO(DPIX, false, false); } while (0)
+            if (out_geo.bps == 1) FS_PICK(uint8_t);
+            else                  FS_PICK(uint16_t);
+#undef FS_PICK
+#undef FS_GO
+            return HBHIP_OK;
+        });
+    }
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
+        if (out_geo.depth != in_geo.depth) return process_scaled(ins, outs, n);
         return hbhip_for_each_burst<FMT_FRAMES, FormatResampleArgs>(ctx, ins, outs, n, [&](FormatResampleArgs &a, int nf, int, uintptr_t bits) {
             if ((bits & 7) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
             a.w = in_geo.width; a.h = in_geo.height; a.depth = in_geo.depth;
@@ -1917,21 +2044,22 @@ extern "C" int hbhip_format_create(hbhip_ctx *ctx, int width, int height, int sr
     return *out ? HBHIP_OK : HBHIP_ERR_NOMEM;
 }
 
-extern "C" int hbhip_format_resample_create(hbhip_ctx *ctx, int width, int height, int depth, int src_log2_cw, int src_log2_ch,
-                                            int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out)
+// the chroma down-sampling and the scaled form behind both create functions: src_depth == dst_depth is the former
+static int format_resample_make(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
+                                int src_log2_ch, int dst_log2_cw, int dst_log2_ch, hbhip_filter **out)
 {
     if (!ctx || !out) return HBHIP_ERR_ARG;
     *out = nullptr;
-    if (depth != 8 && depth != 10 && depth != 12) return HBHIP_ERR_UNSUPPORTED;
+    for (int d : {src_depth, dst_depth})
+        if (d != 8 && d != 10 && d != 12) return HBHIP_ERR_UNSUPPORTED;
     if (width < 1 || height < 1) return HBHIP_ERR_ARG;
     if (!hbhip_yuv_layout_ok(src_log2_cw, src_log2_ch) || !hbhip_yuv_layout_ok(dst_log2_cw, dst_log2_ch)) return HBHIP_ERR_UNSUPPORTED;
-    // down only: no dimension gains chroma samples and one loses some
-    if (dst_log2_cw < src_log2_cw || dst_log2_ch < src_log2_ch ||
-        (dst_log2_cw == src_log2_cw && dst_log2_ch == src_log2_ch)) return HBHIP_ERR_UNSUPPORTED;
-    (void)chroma_location;                      // every value is taken as left-sited (the crop/scale drop-in's rule)
+    // down only: no dimension gains chroma samples, the depth does not grow, and one of the three shrinks
+    if (dst_log2_cw < src_log2_cw || dst_log2_ch < src_log2_ch || dst_depth > src_depth ||
+        (dst_log2_cw == src_log2_cw && dst_log2_ch == src_log2_ch && dst_depth == src_depth)) return HBHIP_ERR_UNSUPPORTED;
     PicGeometry gi, go;
-    gi.set(width, height, depth, src_log2_cw, src_log2_ch);
-    go.set(width, height, depth, dst_log2_cw, dst_log2_ch);
+    gi.set(width, height, src_depth, src_log2_cw, src_log2_ch);
+    go.set(width, height, dst_depth, dst_log2_cw, dst_log2_ch);
     // a chroma plane so small that initFilter's clamp (size = min(size, src - 2)) cuts the nine taps short: swscale's
     // filter is then something else than a bicubic, and nobody's to restate
     if ((dst_log2_cw > src_log2_cw && gi.pw[1] - 2 < 9) || (dst_log2_ch > src_log2_ch && gi.ph[1] - 2 < 9))
@@ -1942,6 +2070,21 @@ extern "C" int hbhip_format_resample_create(hbhip_ctx *ctx, int width, int heigh
     if (rc != HBHIP_OK) { delete f; return rc; }
     *out = f;
     return HBHIP_OK;
+}
+
+// (chroma_location: every value is taken as left-sited, the crop/scale drop-in's rule)
+extern "C" int hbhip_format_resample_create(hbhip_ctx *ctx, int width, int height, int depth, int src_log2_cw, int src_log2_ch,
+                                            int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out)
+{
+    (void)chroma_location;
+    return format_resample_make(ctx, width, height, depth, depth, src_log2_cw, src_log2_ch, dst_log2_cw, dst_log2_ch, out);
+}
+
+extern "C" int hbhip_format_scaled_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
+                                          int src_log2_ch, int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out)
+{
+    (void)chroma_location;
+    return format_resample_make(ctx, width, height, src_depth, dst_depth, src_log2_cw, src_log2_ch, dst_log2_cw, dst_log2_ch, out);
 }
 
 extern "C" int hbhip_pad_create(hbhip_ctx *ctx, const hbhip_pad_params *p, int width, int height, int depth,

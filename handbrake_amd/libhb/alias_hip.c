@@ -215,13 +215,19 @@ static int rotate_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
  * than the pipeline's (work.c:1530-1549), typically 8 <-> 10 bits.  Here it is a real filter for what that
  * use needs (parity unpinned):
  *   - planar YUV depth changes with the subsampling unchanged (csrc/alias.hip:format_kernel);
- *   - planar YUV chroma DOWN-sampling at equal depth, 4:2:2 -> 4:2:0, 4:4:4 -> 4:2:2, 4:4:4 -> 4:2:0
- *     (format_resample_kernel): hb_get_best_pix_fmt never goes below the title's chroma (common.c:7516-7604), so a 4:2:2
- *     source in front of a 4:2:0-only encoder gets `format=yuv420p10le` behind its yuv422p10le chain (work.c:1525-1552).
+ *   - planar YUV chroma DOWN-sampling, 4:2:2 -> 4:2:0, 4:4:4 -> 4:2:2, 4:4:4 -> 4:2:0, at equal depth or together with a
+ *     LOWER depth (format_resample_kernel, its scaled form): hb_get_best_pix_fmt never goes below the title's chroma or
+ *     depth (common.c:7516-7604), so a 10-bit 4:2:2 source in front of an 8-bit 4:2:0 encoder gets `format=yuv420p` behind
+ *     its yuv422p10le chain (work.c:1525-1552);
+ *   - the PLANAR STEP of `format=nv12` / `format=p010le`, when hip_common.c has marked the entry with
+ *     HBHIP_FORMAT_PLANAR_STEP: the frames become yuv420p / yuv420p10le here and the run's download adapter repacks them.
+ *     libswscale takes every semi-planar target but the two exact repacks through its scaler, so a depth change alone is
+ *     the scaled form too (yuv420p10le -> nv12 is NOT format_kernel's 10 -> 8); a stream that already is the planar
+ *     step passes through.
  * Any other target makes init() fail, which keeps the CPU filter (work.c:1861-1868): more chroma samples than the
- * stream has (the rule above never asks for it), a subsampling change together with a depth change (swscale does both
- * in one scaler pass with a dither of its own), semi-planar and RGB targets, a chroma plane too small for swscale's nine
- * taps. */
+ * stream has (the rule above never asks for it), fewer chroma samples together with a HIGHER depth, semi-planar targets
+ * that nobody marked (a lone `format=nv12` has no adapter to repack for it), RGB, a chroma plane too small for
+ * swscale's nine taps. */
 static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
 static int format_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
 
@@ -252,8 +258,13 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
         pv->s.output = *init;                                                   /* nothing to do: frames pass through */
         return 0;
     }
-    const int dst_fmt = av_get_pix_fmt(format);                               /* :107 */
+    int dst_fmt = av_get_pix_fmt(format);                                     /* :107 */
     free(format);
+    /* hip_common.c's mark on a `format=nv12 | p010le` entry inside a run: make the planar frame the download adapter repacks */
+    int planar_step = 0;
+    hb_dict_extract_bool(&planar_step, filter->settings, HBHIP_FORMAT_PLANAR_STEP);
+    planar_step = planar_step && pv->s.dev_io && hbhip_host_is_biplanar(dst_fmt);     /* (no run, no adapter to repack) */
+    if (planar_step) dst_fmt = dst_fmt == HBHIP_PIX_FMT_NV12 ? AV_PIX_FMT_YUV420P : AV_PIX_FMT_YUV420P10;
     const AVPixFmtDescriptor *dd = av_pix_fmt_desc_get(dst_fmt);
     if (dd == NULL || dd->nb_components != desc->nb_components || desc->nb_components < 3)
         return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
@@ -262,17 +273,28 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
         if (dd->comp[c].plane != c || desc->comp[c].plane != c)
             return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
     const int resample = dd->log2_chroma_w != desc->log2_chroma_w || dd->log2_chroma_h != desc->log2_chroma_h;
-    /* fewer chroma samples AND another depth: one swscale pass with its own dither, not these two filters in a row */
-    if (resample && dd->comp[0].depth != desc->comp[0].depth)
+    const int sdepth = desc->comp[0].depth, ddepth = dd->comp[0].depth;
+    /* fewer chroma samples AND a higher depth: nothing asks for it; a biplanar target above the stream's depth neither */
+    if ((resample || planar_step) && ddepth > sdepth)
         return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
+    if (planar_step && !resample && ddepth == sdepth)
+    {
+        pv->s.output = *init;                                                   /* the stream is the planar step already */
+        return 0;
+    }
     hbhip_ctx *ctx = hbhip_host_ctx_for(init);
     if (ctx == NULL) return hbhip_host_simple_fail(filter, HBHIP_ERR_NODEVICE);
+    /* the scaler's path at a lower depth: with fewer chroma samples, or (semi-planar target) on its own */
+    const int scaled = ddepth < sdepth && (resample || planar_step);
     /* (the create functions decline what is left: upsampling, other depths, planes too small) */
-    int rc = resample ? hbhip_format_resample_create(ctx, init->geometry.width, init->geometry.height, desc->comp[0].depth,
+    int rc = scaled   ? hbhip_format_scaled_create(ctx, init->geometry.width, init->geometry.height, sdepth, ddepth,
+                                                   desc->log2_chroma_w, desc->log2_chroma_h, dd->log2_chroma_w,
+                                                   dd->log2_chroma_h, init->chroma_location, &pv->s.dev)
+           : resample ? hbhip_format_resample_create(ctx, init->geometry.width, init->geometry.height, sdepth,
                                                      desc->log2_chroma_w, desc->log2_chroma_h, dd->log2_chroma_w,
                                                      dd->log2_chroma_h, init->chroma_location, &pv->s.dev)
-                      : hbhip_format_create(ctx, init->geometry.width, init->geometry.height, desc->comp[0].depth,
-                                            dd->comp[0].depth, desc->log2_chroma_w, desc->log2_chroma_h,
+                      : hbhip_format_create(ctx, init->geometry.width, init->geometry.height, sdepth,
+                                            ddepth, desc->log2_chroma_w, desc->log2_chroma_h,
                                             init->color_range == 2 /* AVCOL_RANGE_JPEG */, &pv->s.dev);
     if (rc != HBHIP_OK) return hbhip_host_simple_fail(filter, rc);
     init->pix_fmt = dst_fmt;

@@ -329,6 +329,20 @@ void hbhip_dict_set(hb_dict_t *d, const char *key, const char *value)
     d->tail = e;
 }
 
+int hb_dict_remove(hb_dict_t *d, const char *key)
+{
+    if (d == NULL || key == NULL) return 0;
+    for (kv_t *e = d->head, *prev = NULL; e; prev = e, e = e->next)
+    {
+        if (strcmp(e->k, key)) continue;
+        if (prev) prev->next = e->next; else d->head = e->next;
+        if (d->tail == e) d->tail = prev;
+        free(e->k); free(e->v); free(e);
+        return 1;
+    }
+    return 0;
+}
+
 hb_dict_t *hbhip_dict_from_string(const char *settings)
 {
     hb_dict_t *d = hb_dict_init();

@@ -32,6 +32,10 @@ void       hbhip_host_ctx_release(void);
 #define HBHIP_PIX_FMT_NV12   23
 #define HBHIP_PIX_FMT_P010LE 158
 static inline int hbhip_host_is_biplanar(int pix_fmt) { return pix_fmt == HBHIP_PIX_FMT_NV12 || pix_fmt == HBHIP_PIX_FMT_P010LE; }
+/* The key hip_common.c adds to the settings of a `format=nv12 | p010le` entry inside a device-resident run (never a value of
+ * the public `format=`): the Format drop-in then makes the planar step only, yuv420p / yuv420p10le, and the run's download
+ * adapter repacks it.  hb_hip_filter_init_failed() strips it before the CPU filter sees the settings. */
+#define HBHIP_FORMAT_PLANAR_STEP "hip-planar-step"
 static inline void hbhip_host_biplanar_from_buf(hbhip_host_biplanar *f, const hb_buffer_t *b)
 {
     for (int p = 0; p < 2; p++)

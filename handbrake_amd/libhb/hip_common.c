@@ -9,6 +9,9 @@
  *   2. every run of two or more drop-ins - adjacent, or with only "hw-transparent" filters between them (vfr,
  *      rendersub, rpu: hb_hip_filter_is_hw_transparent) - is bracketed by hb_filter_hip_upload / hb_filter_hip_download,
  *      so frames stay in HBM inside the run (a lone drop-in moves its own frames; adapters would only add two threads).
+ *   3. a `format=nv12 | p010le` entry behind a drop-in of a planar YUV job is split: the Format drop-in is told (through
+ *      HBHIP_FORMAT_PLANAR_STEP in its settings, never through the public `format=` value) to make yuv420p / yuv420p10le,
+ *      and the run's download adapter gets format=nv12 | p010le and repacks on the GPU (mark_planar_steps).
  * And one thing the VideoToolbox path does not need: a drop-in's init() may refuse settings it has no kernels for.
  * work.c drops a filter whose init fails (:1861-1868) - for a drop-in that would silently lose the filter, so the init
  * loop calls hb_hip_filter_init_failed() first, which puts the CPU filter back (and re-brackets the run around it).
@@ -71,6 +74,47 @@ static hb_filter_object_t *new_adapter(int id, int host_fmt)
     return a;
 }
 
+/* the NV12 / P010LE target of a Format drop-in entry that mark_planar_steps() has marked, else AV_PIX_FMT_NONE */
+static int planar_step_target(const hb_filter_object_t *f)
+{
+    int marked = 0, fmt = AV_PIX_FMT_NONE;
+    char *name = NULL;
+    if (f == NULL || f->id != HB_FILTER_FORMAT || !hb_hip_filter_is_hip(f) || f->settings == NULL) return AV_PIX_FMT_NONE;
+    if (!hb_dict_extract_bool(&marked, f->settings, HBHIP_FORMAT_PLANAR_STEP) || !marked) return AV_PIX_FMT_NONE;
+    if (hb_dict_extract_string(&name, f->settings, "format") && name != NULL) fmt = av_get_pix_fmt(name);
+    free(name);
+    return hbhip_host_is_biplanar(fmt) ? fmt : AV_PIX_FMT_NONE;
+}
+
+/* work.c appends `format=nv12` / `format=p010le` when the encoder wants one of them (work.c:1525-1552, match_pix_fmt).
+ * Where such an entry stands behind a drop-in (transparent filters aside) of a planar YUV 4:2:0 / 4:2:2 / 4:4:4 job whose
+ * depth is at least the target's, the frames need not leave the device a filter early: the entry is marked, its drop-in
+ * makes the planar step, and bracket_runs() gives the download adapter behind it the biplanar format.  The entry keeps
+ * `format=nv12`, so that the fallback hands the CPU filter its own settings (hb_hip_filter_init_failed strips the mark).
+ * Not marked: an 8-bit stream under p010le (a higher depth: init() declines it as before), and an entry with no drop-in
+ * in front of it - on a yuv420p job its planar step would be the identity, and an interleave on the CPU is cheaper than a
+ * round trip over the bus. */
+static void mark_planar_steps(hb_job_t *job, int from)
+{
+    hb_list_t *list = job->list_filter;
+    const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(job->input_pix_fmt);
+    if (!hbhip_host_planar_yuv(desc)) return;
+    for (int i = from > 1 ? from : 1; i < hb_list_count(list); i++)
+    {
+        hb_filter_object_t *f = hb_list_item(list, i);
+        if (f->id != HB_FILTER_FORMAT || !hb_hip_filter_is_hip(f) || f->settings == NULL) continue;
+        char *name = NULL;
+        if (!hb_dict_extract_string(&name, f->settings, "format") || name == NULL) { free(name); continue; }
+        const int fmt = av_get_pix_fmt(name);
+        free(name);
+        if (!hbhip_host_is_biplanar(fmt) || desc->comp[0].depth < (fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10)) continue;
+        int j = i - 1;
+        while (j >= from && hb_hip_filter_is_hw_transparent(hb_list_item(list, j))) j--;
+        if (j < from || is_adapter(hb_list_item(list, j)) || !hb_hip_filter_is_hip(hb_list_item(list, j))) continue;
+        hb_dict_set_string(f->settings, HBHIP_FORMAT_PLANAR_STEP, "1");
+    }
+}
+
 /* vt_common.c:486-502, by position instead of by id */
 static void replace_at(hb_list_t *list, int pos, hb_filter_object_t *proto)
 {
@@ -119,7 +163,9 @@ static void bracket_runs(hb_list_t *list, int from, int host_fmt)
         }
         if (n >= least)
         {
-            hb_list_insert(list, last + 1, new_adapter(HB_FILTER_HIP_DOWNLOAD, host_fmt));
+            /* a run that ends in a marked `format=nv12 | p010le` entry leaves the device in that format */
+            const int step_fmt = planar_step_target(hb_list_item(list, last));
+            hb_list_insert(list, last + 1, new_adapter(HB_FILTER_HIP_DOWNLOAD, step_fmt != AV_PIX_FMT_NONE ? step_fmt : host_fmt));
             hb_list_insert(list, i, new_adapter(HB_FILTER_HIP_UPLOAD, host_fmt));
             last += 2;
         }
@@ -145,6 +191,7 @@ void hb_hip_setup_hw_filters(hb_job_t *job)
         hb_filter_object_t *proto = hbhip_filter_get(f->id);
         if (proto != NULL) replace_at(list, i, proto);
     }
+    mark_planar_steps(job, 0);
     bracket_runs(list, 0, job_host_fmt(job));
 }
 
@@ -156,8 +203,19 @@ int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
     if (f == NULL || is_adapter(f) || !hb_hip_filter_is_hip(f)) return 0;
     hb_filter_object_t *cpu = hb_filter_init(f->id);
     if (cpu == NULL) return 0;                                /* no CPU filter of that id: work.c drops it */
+    if (cpu->init == f->init)                                 /* the id's own filter IS the drop-in: it would decline again */
+    {
+        hb_filter_close(&cpu);
+        /* work.c drops the entry; a planar step that is not made leaves nothing for its download adapter to repack */
+        hb_filter_object_t *next = hb_list_item(list, index + 1);
+        if (planar_step_target(f) != AV_PIX_FMT_NONE && next != NULL && next->id == HB_FILTER_HIP_DOWNLOAD &&
+            next->settings != NULL)
+            hb_dict_remove(next->settings, "format");
+        return 0;
+    }
     hb_dict_free(&cpu->settings);
     cpu->settings = f->settings ? hb_value_dup(f->settings) : hb_dict_init();
+    hb_dict_remove(cpu->settings, HBHIP_FORMAT_PLANAR_STEP);  /* mark_planar_steps' key is nothing the CPU filter knows */
     if (cpu->sub_filter != NULL)                              /* mt_frame wrapper: hb_add_filter_dict copies them down */
     {
         hb_dict_free(&cpu->sub_filter->settings);
@@ -197,6 +255,13 @@ int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
             hb_list_insert(list, pos++, new_adapter(HB_FILTER_HIP_DOWNLOAD, job_host_fmt(job)));
     }
     hb_list_insert(list, pos, cpu);
+    /* what follows may have lost the drop-in it stood behind: mark afresh, then bracket */
+    for (int i = pos + 1; i < hb_list_count(list); i++)
+    {
+        hb_filter_object_t *g = hb_list_item(list, i);
+        if (g->id == HB_FILTER_FORMAT && g->settings != NULL) hb_dict_remove(g->settings, HBHIP_FORMAT_PLANAR_STEP);
+    }
+    mark_planar_steps(job, pos + 1);
     bracket_runs(list, pos + 1, job_host_fmt(job));
     return ret;
 }

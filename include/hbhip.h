@@ -484,6 +484,17 @@ int hbhip_format_create(hbhip_ctx *ctx, int width, int height, int src_depth, in
  * Arithmetic pinned to tests/format_resample_model.py only (parity unpinned). */
 int hbhip_format_resample_create(hbhip_ctx *ctx, int width, int height, int depth, int src_log2_cw, int src_log2_ch,
                                  int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out);
+/* The same scaler pass when the target also, or only, has a LOWER depth: 10 -> 8, 12 -> 8, 12 -> 10 bits, with the three
+ * pairs above or with the subsampling unchanged (4:2:0 -> 4:2:0, 4:2:2 -> 4:2:2, 4:4:4 -> 4:4:4: what libswscale does in
+ * front of a semi-planar target, where it leaves the unscaled planar copy of hbhip_format_create).  Every plane, luma
+ * included, runs through the horizontal pass or its identity (15-bit intermediates) and the output stage of the target's
+ * depth: to 8 bits with the 8 x 8 ordered dither ff_dither_8x8_128 by the OUTPUT sample's row and column (Cr three columns
+ * on), to 10 bits with a flat half.  No range conversion.  At src_depth == dst_depth this is
+ * hbhip_format_resample_create.  HBHIP_ERR_UNSUPPORTED: a higher target depth, a depth outside 8 / 10 / 12, more chroma
+ * samples in either direction, nothing to do at all, a chroma plane under 11 samples in a direction that is resampled.
+ * Arithmetic pinned to tests/format_scaled_model.py only (parity unpinned). */
+int hbhip_format_scaled_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
+                               int src_log2_ch, int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out);
 /* The zscale [-> format=gbrpf32le -> tonemap] -> zscale -> format graph colorspace_init builds
  * (colorspace.c:126-193): matrix / range / transfer / primaries conversion, with tone mapping
  * when the source transfer is SMPTE 2084 or ARIB STD-B67 and the transfer changes.  Colour ids

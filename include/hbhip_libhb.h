@@ -176,6 +176,7 @@ void         hbhip_set_cpu_count(int n);
 hb_dict_t *hb_dict_init(void);
 void       hb_dict_free(hb_dict_t **);
 void       hbhip_dict_set(hb_dict_t *, const char *key, const char *value);
+int        hb_dict_remove(hb_dict_t *, const char *key);                    /* hb_dict.h:51; 1: the key was there */
 /* "key=value:key=value" (the CLI / settings_template form). */
 hb_dict_t *hbhip_dict_from_string(const char *settings);
 int hb_dict_extract_int(int *dst, const hb_dict_t *dict, const char *key);

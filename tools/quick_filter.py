@@ -2,6 +2,7 @@
 """Times one stateless filter's batch path (16 device-resident 1080p frames per call) with the context's kernel timer.
 usage: quick_filter.py unsharp|chroma_smooth|lapsharp|colorspace_sdr|colorspace_matrix|grayscale|rotate|scale<W>x<H>|
                       format8to10|format10to8|format_422_420[_10]|format_444_422[_10]|format_444_420[_10]|
+                      format_<444|422|420>_<422|420>_<10to8|12to8|12to10> (a lower depth; 420_420: the depth alone)|
                       deblock_<preset>_<tune>[_10]|deband[_<range>][_10][_tile|_gather]|bm3d[_<sigma>][_10] [reps]
 Prints one line per kernel: name, launches, average us.  For knob experiments with tools/dev_run.sh."""
 import ctypes as C, json, os, sys
@@ -83,12 +84,16 @@ def main():
         sd, dd = (8, 10) if what == "format8to10" else (10, 8)
         make = lambda: hip._create("hbhip_format_create", ctx, [C.c_void_p] + [C.c_int] * 7 + [C.POINTER(C.c_void_p)], ctx.h, W, H, sd, dd, 1, 1, 0)
         depth_in, depth_out = sd, dd
-    elif what.startswith("format_"):                   # format_422_420, format_444_420_10 ...: chroma down-sampling at equal depth
+    elif what.startswith("format_"):                   # format_422_420, format_444_420_10 ...: chroma down-sampling
         parts = what.split("_")
         subs = {"420": (1, 1), "422": (1, 0), "444": (0, 0)}
         sub_in, sub_out = subs[parts[1]], subs[parts[2]]
-        depth_in = depth_out = 10 if parts[-1] == "10" else 8
-        make = lambda: hip.format_resample_device_filter(ctx, W, H, sub_in, sub_out, depth_in)
+        if "to" in parts[-1]:                          # format_422_420_10to8, format_420_420_12to10 ...: the scaled form
+            depth_in, depth_out = (int(v) for v in parts[-1].split("to"))
+            make = lambda: hip.format_scaled_device_filter(ctx, W, H, sub_in, sub_out, depth_in, depth_out)
+        else:
+            depth_in = depth_out = 10 if parts[-1] == "10" else 8
+            make = lambda: hip.format_resample_device_filter(ctx, W, H, sub_in, sub_out, depth_in)
     elif what.startswith("scale"):                     # scale960x540, scale1280x720, scale3840x2160 ...
         ow, oh = (int(v) for v in what[5:].split("x"))
         make = lambda: hip.cropscale_device_filter(ctx, W, H, ow, oh)
