@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "blend_body.h"
+#include "ass_compose.h"
 
 namespace {
 
@@ -58,9 +59,16 @@ struct hbhip_blend
     hbhip_frame *staging = nullptr;      // device frame of the host-frame entry point
     bool biplanar = false;               // made by hbhip_blend_create_biplanar
     uint8_t *bi_stage = nullptr;         // its staging buffer: the host picture as it is (BiLayout)
+    // hbhip_blend_set_ass_images: box table, image table and glyph bitmaps, packed in pinned memory and uploaded in one copy
+    uint8_t *h_ass = nullptr, *d_ass = nullptr;
+    size_t   h_ass_bytes = 0, d_ass_bytes = 0;
+    hipEvent_t ass_uploaded = nullptr;   // behind the last copy out of h_ass: the next call packs into it after this
 
     ~hbhip_blend()
     {
+        if (ass_uploaded) (void)hipEventDestroy(ass_uploaded);
+        if (h_ass) (void)hipHostFree(h_ass);
+        if (d_ass) (void)hipFree(d_ass);
         if (d_store) (void)hipFree(d_store);
         if (bi_stage) (void)hipFree(bi_stage);
         if (staging) hbhip_frame_release(staging);
@@ -205,6 +213,182 @@ extern "C" int hbhip_blend_set_overlays(hbhip_blend *b, const hbhip_overlay *ov,
     }
     build_launches(b);
     // the caller may free its bitmaps as soon as this returns
+    HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    return HBHIP_OK;
+}
+
+// ---- text subtitles: libass's glyph images composed on the device (ass_compose.hip) ----
+namespace {
+struct AssBox { int x1, y1, x2, y2; };
+
+// hb_box_intersect / hb_box_vec_merge / _compact (rendersub.c:144-199) as they are: a box cleared by the merge stays in the
+// vector until the compaction and takes part in the rest of the pass as (0, 0, 0, 0)
+bool ass_box_intersect(const AssBox &a, const AssBox &b, int offset)
+{
+    return std::min(a.x2, b.x2) + offset - std::max(a.x1, b.x1) >= 0 && std::min(a.y2, b.y2) + offset - std::max(a.y1, b.y1) >= 0;
+}
+
+void ass_box_append(std::vector<AssBox> &v, int x1, int y1, int x2, int y2)          // hb_box_vec_append :201-226
+{
+    if (x1 == x2 || y1 == y2) return;
+    v.push_back({ x1, y1, x2, y2 });
+    for (size_t i = 0; i + 1 < v.size(); i++)
+        for (size_t j = i + 1; j < v.size(); j++)
+            if (ass_box_intersect(v[i], v[j], 8))
+            {
+                v[i].x1 = std::min(v[i].x1, v[j].x1); v[i].y1 = std::min(v[i].y1, v[j].y1);
+                v[i].x2 = std::max(v[i].x2, v[j].x2); v[i].y2 = std::max(v[i].y2, v[j].y2);
+                v[j] = { 0, 0, 0, 0 };
+            }
+    size_t k = 0;
+    for (size_t i = 0; i < v.size(); i++)
+        if (v[i].x2 != 0 || v[i].y2 != 0) v[k++] = v[i];
+    v.resize(k);
+}
+} // namespace
+
+// render_ssa_subs (rendersub.c:623-665) behind ass_render_frame: boxes on the host, compose_subsample_ass on the device
+extern "C" int hbhip_blend_set_ass_images(hbhip_blend *b, const hbhip_ass_image *img, int n, int crop_left, int crop_top)
+{
+    if (!b || n < 0 || (n > 0 && !img)) return HBHIP_ERR_ARG;
+    if (b->subsample) return HBHIP_ERR_UNSUPPORTED;          // compose_subsample_ass makes overlays in the frame's subsampling
+    const int ws = b->ov_wshift, hs = b->ov_hshift;
+    std::vector<AssBox> boxes;
+    size_t bits = 0;
+    for (int i = 0; i < n; i++)
+    {
+        const hbhip_ass_image &m = img[i];
+        if (m.w < 0 || m.h < 0 || m.dst_x < 0 || m.dst_y < 0 || m.dst_x > (1 << 20) || m.dst_y > (1 << 20) ||
+            m.w > (1 << 20) || m.h > (1 << 20))
+            return HBHIP_ERR_ARG;
+        if (m.w && m.h && (!m.bitmap || m.stride < m.w)) return HBHIP_ERR_ARG;
+        if (m.w && m.h) bits += (size_t)m.w * m.h;
+        ass_box_append(boxes, m.dst_x, m.dst_y, m.dst_x + m.w, m.dst_y + m.h);
+    }
+    hbhip_ctx *ctx = b->ctx;
+    (void)hipSetDevice(ctx->device);
+    b->overlays.clear();
+    b->launches.clear();
+    if (boxes.empty()) return HBHIP_OK;                      // clear_ssa_rendered_sub_cache :614-621
+
+    const size_t box_bytes = boxes.size() * sizeof(AssBoxDev), img_bytes = (size_t)n * sizeof(AssImageDev);
+    const size_t bits_at = (box_bytes + img_bytes + 15) & ~(size_t)15;
+    const size_t up_bytes = bits_at + ASS_BITS_PAD + ((bits + 15) & ~(size_t)15) + ASS_BITS_PAD;
+    if (up_bytes > 0x7fffffff) return HBHIP_ERR_UNSUPPORTED;
+    size_t total = 0;
+    std::vector<OverlayDev> ovs(boxes.size());
+    for (size_t k = 0; k < boxes.size(); k++)
+    {
+        // the overlay is aligned to the chroma plane of the cropped picture, padded left and up as needed (:648-653)
+        OverlayDev &d = ovs[k];
+        d.x = boxes[k].x1 - ((boxes[k].x1 + crop_left) & ((1 << ws) - 1));
+        d.y = boxes[k].y1 - ((boxes[k].y1 + crop_top) & ((1 << hs) - 1));
+        d.width = boxes[k].x2 - d.x; d.height = boxes[k].y2 - d.y;
+        if (d.width < 1 || d.height < 1) return HBHIP_ERR_ARG;
+        const int cw = -((-d.width) >> ws), ch = -((-d.height) >> hs);
+        d.stride[0] = d.stride[3] = hbhip_align_up(d.width, 16);
+        d.stride[1] = d.stride[2] = hbhip_align_up(cw, 16);
+        total += 2 * (size_t)d.stride[0] * d.height + 2 * (size_t)d.stride[1] * ch;
+    }
+    if (total > b->store_bytes || up_bytes > b->d_ass_bytes)
+        HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));                  // launches of the previous set may still be reading them
+    if (total > b->store_bytes)
+    {
+        if (b->d_store) (void)hipFree(b->d_store);
+        b->d_store = nullptr;
+        b->store_bytes = 0;
+        HBHIP_CHECK(ctx, hipMalloc((void **)&b->d_store, total));
+        b->store_bytes = total;
+    }
+    if (up_bytes > b->d_ass_bytes)
+    {
+        if (b->d_ass) (void)hipFree(b->d_ass);
+        b->d_ass = nullptr;
+        b->d_ass_bytes = 0;
+        HBHIP_CHECK(ctx, hipMalloc((void **)&b->d_ass, up_bytes));
+        b->d_ass_bytes = up_bytes;
+    }
+    if (!b->ass_uploaded) HBHIP_CHECK(ctx, hipEventCreateWithFlags(&b->ass_uploaded, hipEventDisableTiming));
+    else HBHIP_CHECK(ctx, hipEventSynchronize(b->ass_uploaded));          // the previous call's copy has left the staging buffer
+    if (up_bytes > b->h_ass_bytes)
+    {
+        if (b->h_ass) (void)hipHostFree(b->h_ass);
+        b->h_ass = nullptr;
+        b->h_ass_bytes = 0;
+        HBHIP_CHECK(ctx, hipHostMalloc((void **)&b->h_ass, up_bytes, hipHostMallocDefault));
+        b->h_ass_bytes = up_bytes;
+    }
+
+    AssBoxDev *hb = reinterpret_cast<AssBoxDev *>(b->h_ass);
+    AssImageDev *hi = reinterpret_cast<AssImageDev *>(b->h_ass + box_bytes);
+    uint8_t *at = b->d_store;
+    dim3 grid(1, 1, (unsigned)boxes.size());
+    for (size_t k = 0; k < boxes.size(); k++)
+    {
+        OverlayDev &d = ovs[k];
+        const int ch = -((-d.height) >> hs);
+        for (int p = 0; p < 4; p++)
+        {
+            d.plane[p] = at;
+            hb[k].plane[p] = at;
+            hb[k].stride[p] = d.stride[p];
+            at += (size_t)d.stride[p] * (p == 1 || p == 2 ? ch : d.height);
+        }
+        hb[k].x = d.x; hb[k].y = d.y; hb[k].w = d.width; hb[k].h = d.height;
+        grid.x = std::max<unsigned>(grid.x, (d.width + ASS_TILE_W - 1) / ASS_TILE_W);
+        grid.y = std::max<unsigned>(grid.y, (ch + ASS_TILE_WAVES - 1) / ASS_TILE_WAVES);
+        d.x += crop_left; d.y += crop_top;                                  // :658-659
+    }
+    memset(b->h_ass + box_bytes + img_bytes, 0, bits_at + ASS_BITS_PAD - (box_bytes + img_bytes));
+    size_t off = ASS_BITS_PAD;
+    for (int i = 0; i < n; i++)
+    {
+        const hbhip_ass_image &m = img[i];
+        const bool empty = !m.w || !m.h;
+        hi[i].off = (int)off; hi[i].w = empty ? 0 : m.w; hi[i].h = empty ? 0 : m.h; hi[i].x = m.dst_x; hi[i].y = m.dst_y;
+        hi[i].yuva = (unsigned)m.y | (unsigned)m.cb << 8 | (unsigned)m.cr << 16 | (unsigned)m.a << 24;
+        hi[i].pad[0] = hi[i].pad[1] = 0;
+        if (empty) continue;
+        for (int r = 0; r < m.h; r++) memcpy(b->h_ass + bits_at + off + (size_t)r * m.w, m.bitmap + (size_t)r * m.stride, m.w);
+        off += (size_t)m.w * m.h;
+    }
+    memset(b->h_ass + bits_at + off, 0, up_bytes - bits_at - off);
+    // the caller may free its bitmaps from here on: they are in the staging buffer
+    HBHIP_CHECK(ctx, hipMemcpyAsync(b->d_ass, b->h_ass, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HBHIP_CHECK(ctx, hipEventRecord(b->ass_uploaded, ctx->stream));
+
+    AssArgs a;
+    a.box = reinterpret_cast<const AssBoxDev *>(b->d_ass);
+    a.img = reinterpret_cast<const AssImageDev *>(b->d_ass + box_bytes);
+    a.bits = b->d_ass + bits_at;
+    a.n_img = n;
+    for (int i = 0; i < 2; i++) { a.cx[i] = b->coeff[0][i]; a.cy[i] = b->coeff[1][i]; }
+    const int rc = hbhip_ass_compose_launch(ctx, ws, hs, grid, a);
+    if (rc != HBHIP_OK) return rc;
+    b->overlays = std::move(ovs);
+    build_launches(b);
+    return HBHIP_OK;
+}
+
+extern "C" int hbhip_blend_debug_overlay_count(hbhip_blend *b) { return b ? (int)b->overlays.size() : HBHIP_ERR_ARG; }
+
+extern "C" int hbhip_blend_debug_get_overlay(hbhip_blend *b, int index, uint8_t *const plane[4], const int stride[4], int xywh[4])
+{
+    if (!b || !xywh || index < 0 || index >= (int)b->overlays.size()) return HBHIP_ERR_ARG;
+    hbhip_ctx *ctx = b->ctx;
+    (void)hipSetDevice(ctx->device);
+    const OverlayDev &d = b->overlays[index];
+    xywh[0] = d.x; xywh[1] = d.y; xywh[2] = d.width; xywh[3] = d.height;
+    if (!plane) return HBHIP_OK;
+    if (!stride) return HBHIP_ERR_ARG;
+    const int cw = -((-d.width) >> b->ov_wshift), ch = -((-d.height) >> b->ov_hshift);
+    for (int p = 0; p < 4; p++)
+    {
+        const bool chroma = p == 1 || p == 2;
+        const int w = chroma ? cw : d.width, h = chroma ? ch : d.height;
+        if (!plane[p] || stride[p] < w) return HBHIP_ERR_ARG;
+        HBHIP_CHECK(ctx, hipMemcpy2DAsync(plane[p], stride[p], d.plane[p], d.stride[p], w, h, hipMemcpyDeviceToHost, ctx->stream));
+    }
     HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     return HBHIP_OK;
 }

@@ -402,6 +402,66 @@ def blend_run(lib, symbol, frame, overlays, pix_fmt=AV_PIX_FMT_YUV420P, overlay_
     return tuple(out)
 
 
+class AssImage(C.Structure):
+    """hbhip_ass_image: one glyph image of libass's list - coverage bitmap, position, colour and transparency."""
+    _fields_ = [("bitmap", C.c_void_p), ("stride", C.c_int), ("w", C.c_int), ("h", C.c_int), ("dst_x", C.c_int),
+                ("dst_y", C.c_int), ("y", C.c_uint8), ("cb", C.c_uint8), ("cr", C.c_uint8), ("a", C.c_uint8)]
+
+
+def ass_image_array(images):
+    """images: list of (bitmap, w, dst_x, dst_y, (y, cb, cr, a)) - bitmap a 2-D uint8 array whose row pitch is the stride
+    and whose first w columns are the image (w = 0: an empty one).  Returns (ctypes array, keep-alive list)."""
+    arr = (AssImage * max(len(images), 1))()
+    keep = []
+    for i, (bitmap, w, x, y, (cy, cb, cr, a)) in enumerate(images):
+        bitmap = np.ascontiguousarray(bitmap, dtype=np.uint8)
+        keep.append(bitmap)
+        arr[i].bitmap = bitmap.ctypes.data
+        arr[i].stride = bitmap.strides[0]
+        arr[i].w, arr[i].h, arr[i].dst_x, arr[i].dst_y = w, bitmap.shape[0], x, y
+        arr[i].y, arr[i].cb, arr[i].cr, arr[i].a = cy, cb, cr, a
+    return arr, keep
+
+
+def blend_run_ass(lib, symbol, frame, lists, crop=(0, 0, 0, 0), pix_fmt=AV_PIX_FMT_YUV420P, overlay_fmt=AV_PIX_FMT_YUVA420P,
+                  chroma_location=1, dev_ctx=None, depth=8):
+    """A text subtitle through the compositor object `symbol` of `lib` ("hb_blend_hip"): every list of `lists` (see
+    ass_image_array) is handed to hb_blend_hip_set_ass_images in order, then work() composites the last one on a copy of
+    `frame`.  crop = (top, bottom, left, right).  dev_ctx: a hip.Ctx - the frame is then a device-resident one of it."""
+    rt = runtime()
+    rt.hbh_blend_run_ass.restype = C.c_int
+    rt.hbh_blend_run_ass.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                     C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p),
+                                     C.POINTER(C.c_int)]
+    out = [np.ascontiguousarray(p).copy() for p in frame]
+    h, w = out[0].shape
+    ptrs = (C.c_void_p * 3)(*[p.ctypes.data for p in out])
+    strides = (C.c_int * 3)(*[p.strides[0] for p in out])
+    arrs = [ass_image_array(images) for images in lists]
+    counts = (C.c_int * max(len(lists), 1))(*[len(images) for images in lists])
+    tables = (C.c_void_p * max(len(lists), 1))(*[C.cast(a, C.c_void_p) for a, _ in arrs])
+    proto = C.addressof(C.c_char.in_dll(lib, symbol))
+    setter = C.cast(lib.hb_blend_hip_set_ass_images, C.c_void_p)
+    fr_in, fr_out = None, C.c_void_p()
+    if dev_ctx is not None:
+        from . import hip
+        lch, lcw = (out[0].shape[0] // out[1].shape[0]) >> 1, (out[0].shape[1] // out[1].shape[1]) >> 1
+        fr = hip.Frame(dev_ctx, w, h, depth, lcw, lch)
+        fr.upload(out)
+        fr_in, fr.h = fr.h, None                           # the call takes the reference over
+    rc = rt.hbh_blend_run_ass(proto, setter, pix_fmt, w, h, chroma_location, overlay_fmt, ptrs, strides, fr_in,
+                              C.byref(fr_out), len(lists), counts, tables, (C.c_int * 4)(*crop))
+    if rc != 0:
+        raise RuntimeError(f"hbh_blend_run_ass({symbol}) failed ({rc})")
+    if dev_ctx is not None:
+        fr.h = fr_out
+        try:
+            out = fr.download()
+        finally:
+            fr.close()
+    return tuple(out)
+
+
 def motion_metric_run(lib, symbol, luma_a, luma_b, pix_fmt=AV_PIX_FMT_YUV420P) -> float:
     """Run the metric object `symbol` of `lib` (e.g. "hb_motion_metric_hip") on two luma planes."""
     rt = runtime()

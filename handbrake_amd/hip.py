@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "hbhip_rotate_create", "hbhip_grayscale_create", "hbhip_cropscale_create", "hbhip_colorspace_create", "hbhip_pad_create", "hbhip_yadif_create", "hbhip_bwdif_create", "hbhip_format_create", "hbhip_format_resample_create", "hbhip_format_scaled_create",
     "hbhip_blend_create", "hbhip_blend_set_overlays", "hbhip_blend_apply", "hbhip_blend_apply_dev", "hbhip_blend_destroy",
     "hbhip_blend_create_biplanar", "hbhip_blend_apply_biplanar",
+    "hbhip_blend_set_ass_images", "hbhip_blend_debug_overlay_count", "hbhip_blend_debug_get_overlay",
     "hbhip_motion_metric_create", "hbhip_motion_metric_run", "hbhip_motion_metric_run_dev", "hbhip_motion_metric_destroy",
     "hbhip_detelecine_create", "hbhip_detelecine_push", "hbhip_detelecine_push_frame",
     "hbhip_deblock_create", "hbhip_deblock_set_warmup",
@@ -615,6 +616,35 @@ class BlendDevice:
 
     def apply_dev(self, frame: DevFrame):
         check(lib().hbhip_blend_apply_dev(self.h, C.byref(frame)), self.ctx.h, "blend_apply_dev")
+
+    def set_ass_images(self, images, crop_left=0, crop_top=0):
+        """images: libass's glyph images as hbrt.ass_image_array takes them; composed into overlays on the device"""
+        from . import hbrt
+        L = lib()
+        L.hbhip_blend_set_ass_images.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+        arr, keep = hbrt.ass_image_array(images)
+        check(L.hbhip_blend_set_ass_images(self.h, C.cast(arr, C.c_void_p), len(images), crop_left, crop_top), self.ctx.h,
+              "set_ass_images")
+
+    def overlays(self, log2_cw=1, log2_ch=1):
+        """the object's overlay list read back from its device store (test hook): [(x, y, (Y, Cb, Cr, A))], the chroma
+        planes in the overlay subsampling given"""
+        import numpy as np
+        L = lib()
+        L.hbhip_blend_debug_overlay_count.argtypes = [C.c_void_p]
+        L.hbhip_blend_debug_get_overlay.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        out = []
+        for i in range(check(L.hbhip_blend_debug_overlay_count(self.h), self.ctx.h, "overlay_count")):
+            g = (C.c_int * 4)()
+            check(L.hbhip_blend_debug_get_overlay(self.h, i, None, None, g), self.ctx.h, "get_overlay")
+            x, y, w, h = g
+            cw, ch = -(-w >> log2_cw), -(-h >> log2_ch)
+            planes = [np.zeros(s, np.uint8) for s in ((h, w), (ch, cw), (ch, cw), (h, w))]
+            ptrs = (C.c_void_p * 4)(*[p.ctypes.data for p in planes])
+            strides = (C.c_int * 4)(*[p.strides[0] for p in planes])
+            check(L.hbhip_blend_debug_get_overlay(self.h, i, ptrs, strides, g), self.ctx.h, "get_overlay")
+            out.append((x, y, tuple(planes)))
+        return out
 
     def close(self):
         if self.h:

@@ -11,6 +11,9 @@
  * (storage_type HBHIP_DEVICE) are composited in place without leaving the device.
  * Host frames in NV12 / P010LE (two planes, 4:2:0, 8 or 10 bits) take the biplanar forms (blend8onbi*, csrc/biplanar.hip)
  * through hbhip_blend_create_biplanar / _apply_biplanar; every other two-plane format is refused in init().
+ * Text subtitles: hb_blend_hip_set_ass_images hands libass's glyph images to the device, which composes the overlays in
+ * its own store (csrc/ass_compose.hip, in place of compose_subsample_ass, rendersub.c:474-612); work() with an empty list
+ * then composites those.  INTEGRATION.md has the lines for render_ssa_subs.
  */
 #include "hbhip_host.h"
 
@@ -18,6 +21,7 @@ struct hb_blend_private_s
 {
     hbhip_blend *dev;                /* made on the first frame: on the GPU that frame lives on */
     int          have_overlays;      /* the device holds the current list */
+    int          have_ass;           /* ... and it came from hb_blend_hip_set_ass_images: work() has nothing to upload */
     int          width, height, depth, lcw, lch, chroma_location, ov_lcw, ov_lch;
     int          biplanar;           /* NV12 / P010LE host frames */
 };
@@ -96,11 +100,11 @@ static hb_buffer_t *blend_hip_work(hb_blend_object_t *object, hb_buffer_t *in, h
     hb_blend_private_t *pv = object->private_data;
     hb_buffer_t *out = in;
     const int n = hb_buffer_list_count(overlays);
-    if (n == 0)
+    if (n == 0 && !pv->have_ass)
         return out;                                                                /* blend.c:856-859 */
 
     int rc = blend_hip_device(pv, in);
-    if (rc == HBHIP_OK && (changed || !pv->have_overlays))
+    if (rc == HBHIP_OK && n > 0 && (changed || !pv->have_overlays))
     {
         hbhip_overlay *ov = calloc((size_t)n, sizeof(*ov));
         if (ov == NULL) return NULL;
@@ -120,6 +124,7 @@ static hb_buffer_t *blend_hip_work(hb_blend_object_t *object, hb_buffer_t *in, h
         rc = hbhip_blend_set_overlays(pv->dev, ov, i);
         free(ov);
         pv->have_overlays = rc == HBHIP_OK;
+        pv->have_ass = 0;
     }
     if (rc == HBHIP_OK)
     {
@@ -190,6 +195,22 @@ static hb_buffer_t *blend_hip_work(hb_blend_object_t *object, hb_buffer_t *in, h
         return NULL;
     }
     return out;
+}
+
+/* render_ssa_subs' part behind ass_render_frame (rendersub.c:632-663) for a `blend` that is hb_blend_hip: the glyph images
+ * of the frame's subtitle become the device's overlay list (n == 0: none, as clear_ssa_rendered_sub_cache leaves it).  The
+ * caller's `changed` decides when, as it does for the compose loop this stands in for.  crop = top, bottom, left, right. */
+int hb_blend_hip_set_ass_images(hb_blend_object_t *blend, const hb_buffer_t *frame, const hbhip_ass_image *img, int n,
+                                const int crop[4])
+{
+    hb_blend_private_t *pv = blend != NULL ? blend->private_data : NULL;
+    if (pv == NULL || frame == NULL || crop == NULL) return HBHIP_ERR_ARG;
+    int rc = blend_hip_device(pv, frame);
+    if (rc == HBHIP_OK) rc = hbhip_blend_set_ass_images(pv->dev, img, n, crop[2], crop[0]);
+    pv->have_overlays = 0;
+    pv->have_ass = rc == HBHIP_OK && n > 0;
+    if (rc != HBHIP_OK) hb_error("blend(hip): %s", hbhip_strerror(rc));
+    return rc;
 }
 
 static void blend_hip_close(hb_blend_object_t *object)

@@ -758,6 +758,68 @@ int hbh_blend_run(const void *proto, int pix_fmt, int width, int height, int chr
     return rc;
 }
 
+int hbh_blend_run_ass(const void *proto, const void *set_images, int pix_fmt, int width, int height, int chroma_location,
+                      int overlay_fmt, uint8_t *const plane[3], const int stride[3], void *dev_frame, void **dev_frame_out,
+                      int n_lists, const int *n_images, const void *const *lists, const int crop[4])
+{
+    typedef int (*set_images_f)(hb_blend_object_t *, const hb_buffer_t *, const void *, int, const int *);
+    const set_images_f set = (set_images_f)set_images;
+    hb_blend_object_t blend = *(const hb_blend_object_t *)proto;
+    hb_buffer_list_t none;
+    memset(&none, 0, sizeof(none));
+    int rc = 0;
+    hb_buffer_t *b = dev_frame != NULL ? hb_buffer_init(0) : hb_frame_buffer_init(pix_fmt, width, height);
+    if (b == NULL) return -1;
+    if (dev_frame != NULL)
+    {
+        /* the shell a device-resident run puts around a picture in HBM: no host planes */
+        b->s.type = FRAME_BUF;
+        b->f.fmt = pix_fmt;
+        b->f.width = width;
+        b->f.height = height;
+        b->f.max_plane = 2;
+        for (int p = 0; p < 3; p++)
+        {
+            b->plane[p].width = hb_image_width(pix_fmt, width, p);
+            b->plane[p].height = hb_image_height(pix_fmt, height, p);
+        }
+        b->storage = dev_frame;
+        b->storage_type = HBHIP_DEVICE;
+    }
+    else
+        for (int p = 0; p <= b->f.max_plane; p++)
+            for (int y = 0; y < b->plane[p].height; y++)
+                memcpy(b->plane[p].data + (size_t)y * b->plane[p].stride, plane[p] + (size_t)y * stride[p],
+                       MIN(stride[p], b->plane[p].stride));
+    if (blend.init(&blend, width, height, pix_fmt, chroma_location, 1, overlay_fmt) != 0)
+    {
+        hb_buffer_close(&b);
+        return -1;
+    }
+    for (int k = 0; k < n_lists && rc == 0; k++)
+        if (set(&blend, b, lists[k], n_images[k], crop) != 0) rc = -3;
+    if (rc == 0)
+    {
+        hb_buffer_t *out = blend.work(&blend, b, &none, 0);
+        b = NULL;
+        if (out == NULL) rc = -2;
+        else if (dev_frame != NULL)
+        {
+            *dev_frame_out = out->storage;                 /* the buffer's reference goes to the caller */
+            out->storage = NULL;
+        }
+        else
+            for (int p = 0; p <= out->f.max_plane; p++)
+                for (int y = 0; y < out->plane[p].height; y++)
+                    memcpy(plane[p] + (size_t)y * stride[p], out->plane[p].data + (size_t)y * out->plane[p].stride,
+                           MIN(stride[p], out->plane[p].stride));
+        hb_buffer_close(&out);
+    }
+    if (b != NULL) hb_buffer_close(&b);
+    blend.close(&blend);
+    return rc;
+}
+
 /* ---- frame-difference metric objects (hb_motion_metric_object_t) ---------------------------
  * vfr.c's part (:76-108, :380): copy the prototype, init with the stream's hb_filter_init_t, then
  * work(previous frame, current frame).  Only luma is looked at. */

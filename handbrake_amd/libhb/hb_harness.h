@@ -85,6 +85,15 @@ typedef struct
 int hbh_blend_run(const void *proto, int pix_fmt, int width, int height, int chroma_location, int overlay_fmt,
                   uint8_t *const plane[3], const int stride[3], int n_overlays, const hbh_overlay_t *ov, int passes);
 
+/* The same for a text subtitle, playing render_ssa_subs (rendersub.c:623-665) with a compositor that takes libass's glyph
+ * images itself: set_images(blend, frame, lists[k], n_images[k], crop) for every list in order - the address of
+ * hb_blend_hip_set_ass_images, each list an array of hbhip_ass_image (include/hbhip.h) - then work() once with an empty overlay
+ * list.  dev_frame != NULL: the frame is that device-resident one (an hbhip_frame, whose reference the call takes over) in
+ * place of plane / stride; the frame work() returned comes back in *dev_frame_out, with a reference that is the caller's. */
+int hbh_blend_run_ass(const void *proto, const void *set_images, int pix_fmt, int width, int height, int chroma_location,
+                      int overlay_fmt, uint8_t *const plane[3], const int stride[3], void *dev_frame, void **dev_frame_out,
+                      int n_lists, const int *n_images, const void *const *lists, const int crop[4]);
+
 /* a decoded bitmap subtitle for the job's burn-in track (see hbh_set_job_subtitle): shown from start to stop (90 kHz, stop < 0:
  * until the next one) on a window_w x window_h canvas */
 int hbh_chain_push_subtitle(hbh_chain_t *c, const hbh_overlay_t *ov, int64_t start, int64_t stop, int window_w, int window_h);

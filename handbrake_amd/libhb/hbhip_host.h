@@ -144,6 +144,10 @@ extern hb_filter_object_t hb_filter_bwdif_hip;
 extern hb_filter_object_t hb_filter_format_hip;
 /* the subtitle compositor object rendersub.c can use in place of hb_blend (blend.c:40-46) */
 extern hb_blend_object_t  hb_blend_hip;
+/* text subtitles: libass's glyph images of the frame's subtitle as the overlay list of a `blend` that is hb_blend_hip, composed
+ * on the GPU `frame` lives on (render_ssa_subs, rendersub.c:623-665; INTEGRATION.md has the hook).  HBHIP_OK or HBHIP_ERR_*. */
+int hb_blend_hip_set_ass_images(hb_blend_object_t *blend, const hb_buffer_t *frame, const hbhip_ass_image *img, int n,
+                                const int crop[4]);
 /* the frame-difference metric object vfr.c can use in place of hb_motion_metric (motion_metric.c:306-312) */
 extern hb_motion_metric_object_t hb_motion_metric_hip;
 extern hb_filter_object_t hb_filter_decomb_hip;

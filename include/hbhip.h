@@ -559,6 +559,25 @@ void hbhip_blend_destroy(hbhip_blend *b);                                    /* 
 int  hbhip_blend_create_biplanar(hbhip_ctx *ctx, int width, int height, int depth, int chroma_location,
                                  int overlay_log2_chroma_w, int overlay_log2_chroma_h, hbhip_blend **out);
 int  hbhip_blend_apply_biplanar(hbhip_blend *b, const hbhip_host_biplanar *frame);   /* H2D, blend, D2H; synchronous */
+/* Text subtitles (SSA / ASS, SRT, TX3G, CC608: everything libass renders).  What render_ssa_subs does behind ass_render_frame
+ * (rendersub.c:623-665) when the list has changed: the boxes of hb_box_vec_append / _merge / _compact (:144-226), each pulled
+ * back to a chroma sample of the cropped picture (:648-653) and placed at its position plus the crop (:658-659), and
+ * compose_subsample_ass (:474-612) into one overlay per box - that part on the GPU (csrc/ass_compose.hip), straight into the
+ * object's overlay store.  `img` is the ASS_Image list in list order: the 8-bit coverage bitmap, its position, the colour as
+ * rgb2yuv_fn(color >> 8) gives it (Y = bits 16-23, Cr = 8-15, Cb = 0-7) and a = color & 0xff, libass's transparency (0 =
+ * opaque).  Replaces the object's overlay list (n == 0 or no image with an area: clears it, clear_ssa_rendered_sub_cache
+ * :614-621); the bitmaps are consumed when this returns.  Bit-exact with the reference, except that a chroma sample no
+ * covered pixel contributes to (accu_c == 0, :593 - the reference leaves what its buffer pool held) is 0; it lies under
+ * alpha 0.  For objects of hbhip_blend_create and of hbhip_blend_create_biplanar.  HBHIP_ERR_UNSUPPORTED where the object's
+ * overlay subsampling is not the frame's (ssa_post_init never asks for that, :679-712); HBHIP_ERR_ARG for a negative
+ * position or size, a stride below the width or a missing bitmap. */
+typedef struct hbhip_ass_image { const uint8_t *bitmap; int stride, w, h, dst_x, dst_y;
+                                 uint8_t y, cb, cr, a; } hbhip_ass_image;
+int  hbhip_blend_set_ass_images(hbhip_blend *b, const hbhip_ass_image *img, int n, int crop_left, int crop_top);
+/* test hooks: how many overlays the object holds, and overlay `index` of its device store read back - xywh = its position and
+ * size, plane / stride = where the Y, Cb, Cr and alpha planes go (plane == NULL: the geometry only) */
+int  hbhip_blend_debug_overlay_count(hbhip_blend *b);
+int  hbhip_blend_debug_get_overlay(hbhip_blend *b, int index, uint8_t *const plane[4], const int stride[4], int xywh[4]);
 
 /* ---- test hook ------------------------------------------------------------------------------
  * The EEDI2 mask passes of a batch run as ONE launch whose tiles wait for the previous field's tiles (csrc/eedi2_engine.h:
