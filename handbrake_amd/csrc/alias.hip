@@ -168,10 +168,10 @@ __global__ __launch_bounds__(256) void rotate8_batch_kernel(RotBatch B)
     }
 }
 
-class RotateFilter : public SimpleFilter
+class RotateFilter : public BurstFilter
 {
 public:
-    RotateFilter(hbhip_ctx *c, int angle, int flip) : SimpleFilter(c)
+    RotateFilter(hbhip_ctx *c, int angle, int flip) : BurstFilter(c)
     {
         switch (angle)                                     // rotate.c:190-215
         {
@@ -192,16 +192,9 @@ public:
     }
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
-        bool ok = n > 0;
-        for (int f = 0; ok && f < n; f++)
-        {
-            ok = batch_ok(ins[f], outs[f]);
-            for (int c = 0; ok && c < 3; c++) ok = ins[f]->pitch[c] == ins[0]->pitch[c] && outs[f]->pitch[c] == outs[0]->pitch[c];
-        }
-        if (!ok) return SimpleFilter::process_many(ins, outs, n);          // frame by frame (process() does not come back here then)
-        for (int at = 0; at < n; at += RB_FRAMES)
-        {
-            const int nf = std::min(RB_FRAMES, n - at);
+        return hbhip_for_each_run(ctx, ins, outs, n, RB_FRAMES, [&](int at, int nf) {
+            if (!hbhip_run_all(ins, outs, at, nf, [&](DevPicture *in, DevPicture *out) { return batch_ok(in, out); }))
+                return hbhip_each_frame(ins, outs, at, nf, [&](DevPicture *in, DevPicture *out) { return one_frame(in, out); });
             RotBatch B;
             int max_w = 0, max_h = 0;
             for (int c = 0; c < 3; c++)
@@ -217,17 +210,12 @@ public:
             }
             B.trans = trans; B.hflip = hflip; B.vflip = vflip; B.n = nf;
             HBHIP_LAUNCH(ctx, "rotate", rotate8_batch_kernel, dim3(hbhip_grid_x((max_w + 63) / 64), (max_h + 63) / 64, 3 * nf), dim3(64, 4), 0, B);
-            HBHIP_CHECK(ctx, hipGetLastError());
-        }
-        return HBHIP_OK;
+            return HBHIP_OK;
+        });
     }
-    int process(DevPicture *in, DevPicture *out) override
+    // the generic kernel: any depth, any alignment, a plane per launch
+    int one_frame(DevPicture *in, DevPicture *out)
     {
-        if (batch_ok(in, out))
-        {
-            DevPicture *i1[1] = { in }, *o1[1] = { out };
-            return process_many(i1, o1, 1);
-        }
         for (int c = 0; c < 3; c++)
         {
             RotArgs a;
@@ -238,7 +226,6 @@ public:
             if (in_geo.bps == 1) HBHIP_LAUNCH(ctx, "rotate", rotate_kernel<uint8_t>, dim3((a.dw + 63) / 64, (a.dh + 63) / 64), dim3(64, 4), 0, a);
             else                 HBHIP_LAUNCH(ctx, "rotate", rotate_kernel<uint16_t>, dim3((a.dw + 63) / 64, (a.dh + 63) / 64), dim3(64, 4), 0, a);
         }
-        HBHIP_CHECK(ctx, hipGetLastError());
         return HBHIP_OK;
     }
     int trans = T_NONE, hflip = 0, vflip = 0;
@@ -377,11 +364,11 @@ __global__ __launch_bounds__(256) void monochrome8_batch_kernel(MonoBatch B)
     }
 }
 
-class MonochromeFilter : public SimpleFilter
+class MonochromeFilter : public BurstFilter
 {
 public:
     MonochromeFilter(hbhip_ctx *c, double cb_, double cr_, double size_, double high_)
-        : SimpleFilter(c), cb(cb_), cr(cr_), size(size_), high(high_) {}
+        : BurstFilter(c), cb(cb_), cr(cr_), size(size_), high(high_) {}
     ~MonochromeFilter() override { if (d_lut) (void)hipFree(d_lut); }
     int setup()
     {
@@ -413,16 +400,9 @@ public:
     }
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
-        bool ok = n > 0;
-        for (int i = 0; ok && i < n; i++)
-        {
-            ok = batch_ok(ins[i], outs[i]);
-            for (int c = 0; ok && c < 3; c++) ok = ins[i]->pitch[c] == ins[0]->pitch[c] && outs[i]->pitch[c] == outs[0]->pitch[c];
-        }
-        if (!ok) return SimpleFilter::process_many(ins, outs, n);          // frame by frame (process() does not come back here then)
-        for (int at = 0; at < n; at += MB_FRAMES)
-        {
-            const int nf = std::min(MB_FRAMES, n - at);
+        return hbhip_for_each_run(ctx, ins, outs, n, MB_FRAMES, [&](int at, int nf) {
+            if (!hbhip_run_all(ins, outs, at, nf, [&](DevPicture *in, DevPicture *out) { return batch_ok(in, out); }))
+                return hbhip_each_frame(ins, outs, at, nf, [&](DevPicture *in, DevPicture *out) { return one_frame(in, out); });
             MonoBatch B;
             for (int f = 0; f < nf; f++)
             {
@@ -436,17 +416,12 @@ public:
             const int gx = std::max(((B.w + 15) / 16 + 63) / 64, ((B.cw + 15) / 16 + 63) / 64);
             const int gy = std::max(((B.h + 1) / 2 + 3) / 4, (2 * B.ch + 3) / 4);
             HBHIP_LAUNCH(ctx, "monochrome", monochrome8_batch_kernel, dim3(gx, gy, 2 * nf), dim3(64, 4), 0, B);
-            HBHIP_CHECK(ctx, hipGetLastError());
-        }
-        return HBHIP_OK;
+            return HBHIP_OK;
+        });
     }
-    int process(DevPicture *in, DevPicture *out) override
+    // the generic kernels: any depth, subsampling and alignment
+    int one_frame(DevPicture *in, DevPicture *out)
     {
-        if (batch_ok(in, out))
-        {
-            DevPicture *i1[1] = { in }, *o1[1] = { out };
-            return process_many(i1, o1, 1);
-        }
         const int w = in->width[0], h = in->height[0];
         const int max = (1 << in_geo.depth) - 1, mid = 1 << (in_geo.depth - 1);
         if (in_geo.bps == 1)
@@ -467,7 +442,6 @@ public:
             else                 HBHIP_LAUNCH(ctx, "monochrome_fill", fill_plane_kernel<uint16_t>, grid, dim3(256), 0,
                                               out->plane[c], out->pitch[c], out->width[c], out->height[c], mid);
         }
-        HBHIP_CHECK(ctx, hipGetLastError());
         return HBHIP_OK;
     }
     double cb, cr, size, high;
@@ -1176,10 +1150,10 @@ void quantize_taps(const double *coef, int taps, short *q)
     q[big] = (short)(q[big] + (16384 - sum));
 }
 
-class CropScaleFilter : public SimpleFilter
+class CropScaleFilter : public BurstFilter
 {
 public:
-    CropScaleFilter(hbhip_ctx *c, const hbhip_cropscale_params &p) : SimpleFilter(c), par(p) {}
+    CropScaleFilter(hbhip_ctx *c, const hbhip_cropscale_params &p) : BurstFilter(c), par(p) {}
     ~CropScaleFilter() override
     {
         for (int c = 0; c < 3; c++)
@@ -1198,6 +1172,11 @@ public:
         const int cw = in_geo.width - par.crop_left - par.crop_right;
         const int ch = in_geo.height - par.crop_top - par.crop_bottom;
         if (cw < 1 || ch < 1) return HBHIP_ERR_ARG;
+        auto upload = [&](auto *&dptr, const auto &v) -> int {
+            HBHIP_CHECK(ctx, hipMalloc((void **)&dptr, sizeof(v[0]) * v.size()));
+            HBHIP_CHECK(ctx, hipMemcpy(dptr, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice));
+            return HBHIP_OK;
+        };
         for (int c = 0; c < 3; c++)
         {
             const int lw = c ? in_geo.log2_cw : 0, lh = c ? in_geo.log2_ch : 0;
@@ -1219,15 +1198,10 @@ public:
                 const int hpos = (c && lw) ? 64 : 128;
                 tx[c] = sws_filter(crop_w[c], dw, 1 << 14, hpos, hpos, px, qx);
                 ty[c] = sws_filter(crop_h[c], dh, 1 << 12, 128, 128, py, qy);
-                auto up = [&](auto *&dptr, const auto &v) -> int {
-                    HBHIP_CHECK(ctx, hipMalloc((void **)&dptr, sizeof(v[0]) * v.size()));
-                    HBHIP_CHECK(ctx, hipMemcpy(dptr, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice));
-                    return HBHIP_OK;
-                };
-                int rc = up(d_bx[c], px);
-                if (rc == HBHIP_OK) rc = up(d_by[c], py);
-                if (rc == HBHIP_OK) rc = up(d_qx[c], qx);
-                if (rc == HBHIP_OK) rc = up(d_qy[c], qy);
+                int rc = upload(d_bx[c], px);
+                if (rc == HBHIP_OK) rc = upload(d_by[c], py);
+                if (rc == HBHIP_OK) rc = upload(d_qx[c], qx);
+                if (rc == HBHIP_OK) rc = upload(d_qy[c], qy);
                 if (rc != HBHIP_OK) return rc;
                 up6 = false;
                 continue;
@@ -1236,11 +1210,6 @@ public:
             std::vector<double> cx, cy;
             tx[c] = lanczos_table(crop_w[c], dw, sx, ix, cx, &bx);
             ty[c] = lanczos_table(crop_h[c], dh, 0.0, iy, cy, &by);
-            auto upload = [&](auto *&dptr, const auto &v) -> int {
-                HBHIP_CHECK(ctx, hipMalloc((void **)&dptr, sizeof(v[0]) * v.size()));
-                HBHIP_CHECK(ctx, hipMemcpy(dptr, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice));
-                return HBHIP_OK;
-            };
             int rc = upload(d_iy[c], iy);
             if (rc != HBHIP_OK) return rc;
             {
@@ -1307,9 +1276,7 @@ public:
         for (int i = 0; i < n; i++) (void)copy_identity_planes(ins[i], outs[i]);
         if (identity[0] && identity[1] && identity[2]) { HBHIP_CHECK(ctx, hipGetLastError()); return HBHIP_OK; }
         if (up6)
-            for (int i0 = 0; i0 < n; i0 += SU_FRAMES)
-            {
-                const int m = std::min(SU_FRAMES, n - i0);
+            return hbhip_for_each_run(ctx, ins, outs, n, SU_FRAMES, [&](int i0, int m) {
                 ScaleBatch8 B;
                 memset(&B, 0, sizeof(B));
                 for (int c = 0; c < 3; c++)
@@ -1320,11 +1287,7 @@ public:
                     P.dw = out_geo.pw[c]; P.dh = out_geo.ph[c]; P.sw = crop_w[c]; P.sh = crop_h[c];
                     P.active = !identity[c];
                     B.spitch[c] = ins[i0]->pitch[c]; B.dpitch[c] = outs[i0]->pitch[c];
-                    for (int k = 0; k < m; k++)
-                    {
-                        if (ins[i0 + k]->pitch[c] != B.spitch[c] || outs[i0 + k]->pitch[c] != B.dpitch[c]) return HBHIP_ERR_ARG;
-                        B.src[k][c] = window(ins[i0 + k], c); B.dst[k][c] = outs[i0 + k]->plane[c];
-                    }
+                    for (int k = 0; k < m; k++) { B.src[k][c] = window(ins[i0 + k], c); B.dst[k][c] = outs[i0 + k]->plane[c]; }
                 }
                 const dim3 grid((out_geo.pw[0] + SU_TW - 1) / SU_TW, (out_geo.ph[0] + SU_TH - 1) / SU_TH, 3 * m);
                 const dim3 grid_tall(grid.x, (out_geo.ph[0] + 2 * SU_TH - 1) / (2 * SU_TH), grid.z);
@@ -1332,11 +1295,10 @@ public:
                 else if (in_geo.bps == 1) HBHIP_LAUNCH(ctx, "cropscale_lanczos_fused", scale8_up_kernel<SU_TH>, grid, dim3(256), 0, B);
                 else if (tall)       HBHIP_LAUNCH(ctx, "cropscale_lanczos_fused", scale16_up_kernel<2 * SU_TH>, grid_tall, dim3(256), 0, B, vmax);
                 else                 HBHIP_LAUNCH(ctx, "cropscale_lanczos_fused", scale16_up_kernel<SU_TH>, grid, dim3(256), 0, B, vmax);
-            }
-        else if (!sws)
-            for (int i0 = 0; i0 < n; i0 += SD_FRAMES)
-            {
-                const int m = std::min(SD_FRAMES, n - i0);
+                return HBHIP_OK;
+            });
+        if (!sws)
+            return hbhip_for_each_run(ctx, ins, outs, n, SD_FRAMES, [&](int i0, int m) {
                 ScaleBatchHV B;
                 memset(&B, 0, sizeof(B));
                 int gw = 0, ghr = 0, gvr = 0;
@@ -1349,11 +1311,7 @@ public:
                     B.src_bytes[c] = crop_w[c] * in_geo.bps;
                     B.tqx[c] = d_tqx[c]; B.iy[c] = d_iy[c]; B.qy[c] = d_qy[c];
                     B.hoff[c] = hoff[c];
-                    for (int k = 0; k < m; k++)
-                    {
-                        if (ins[i0 + k]->pitch[c] != B.spitch[c] || outs[i0 + k]->pitch[c] != B.dpitch[c]) return HBHIP_ERR_ARG;
-                        B.src[k][c] = window(ins[i0 + k], c); B.dst[k][c] = outs[i0 + k]->plane[c];
-                    }
+                    for (int k = 0; k < m; k++) { B.src[k][c] = window(ins[i0 + k], c); B.dst[k][c] = outs[i0 + k]->plane[c]; }
                     gw = std::max(gw, B.dw[c]); ghr = std::max(ghr, B.src_rows[c]); gvr = std::max(gvr, B.dh[c]);
                 }
                 B.hframe = hframe;
@@ -1377,37 +1335,34 @@ public:
                 }
 #undef SD_PICK
 #undef SD_GO
-            }
-        else
-            for (int i = 0; i < n; i++)
-                for (int c = 0; c < 3; c++)
+                return HBHIP_OK;
+            });
+        for (int i = 0; i < n; i++)
+            for (int c = 0; c < 3; c++)
+            {
+                if (identity[c]) continue;
+                ScaleSwsArgs w;                                     // (swscale's arithmetic: odd sizes, a plane and a pass per launch)
+                w.src = window(ins[i], c); w.dst = outs[i]->plane[c];
+                w.spitch = ins[i]->pitch[c]; w.dpitch = outs[i]->pitch[c];
+                w.dw = out_geo.pw[c]; w.dh = out_geo.ph[c]; w.tx = tx[c]; w.ty = ty[c]; w.src_rows = crop_h[c];
+                w.px = d_bx[c]; w.py = d_by[c]; w.qx = d_qx[c]; w.qy = d_qy[c];
+                const dim3 gh((w.dw + 63) / 64, (crop_h[c] + 3) / 4), gv((w.dw + 63) / 64, (w.dh + 3) / 4);
+                if (in_geo.bps == 1)
                 {
-                    if (identity[c]) continue;
-                    {
-                        ScaleSwsArgs w;                                     // (swscale's arithmetic: odd sizes, a plane and a pass per launch)
-                        w.src = window(ins[i], c); w.dst = outs[i]->plane[c];
-                        w.spitch = ins[i]->pitch[c]; w.dpitch = outs[i]->pitch[c];
-                        w.dw = out_geo.pw[c]; w.dh = out_geo.ph[c]; w.tx = tx[c]; w.ty = ty[c]; w.src_rows = crop_h[c];
-                        w.px = d_bx[c]; w.py = d_by[c]; w.qx = d_qx[c]; w.qy = d_qy[c];
-                        const dim3 gh((w.dw + 63) / 64, (crop_h[c] + 3) / 4), gv((w.dw + 63) / 64, (w.dh + 3) / 4);
-                        if (in_geo.bps == 1)
-                        {
-                            HBHIP_LAUNCH(ctx, "cropscale_sws_h", scale_sws_h_kernel<uint8_t>, gh, dim3(64, 4), 0, w, (int16_t *)hbuf16, 7);
-                            HBHIP_LAUNCH(ctx, "cropscale_sws_v", scale_sws_v_kernel<uint8_t>, gv, dim3(64, 4), 0, w, (const int16_t *)hbuf16, 64 << 12, 19, 255);
-                        }
-                        else
-                        {
-                            const int d = in_geo.depth, shift = 11 + 16 - d;
-                            HBHIP_LAUNCH(ctx, "cropscale_sws_h", scale_sws_h_kernel<uint16_t>, gh, dim3(64, 4), 0, w, (int16_t *)hbuf16, d - 1);
-                            HBHIP_LAUNCH(ctx, "cropscale_sws_v", scale_sws_v_kernel<uint16_t>, gv, dim3(64, 4), 0, w, (const int16_t *)hbuf16, 1 << (shift - 1), shift, (1 << d) - 1);
-                        }
-                    }
+                    HBHIP_LAUNCH(ctx, "cropscale_sws_h", scale_sws_h_kernel<uint8_t>, gh, dim3(64, 4), 0, w, (int16_t *)hbuf16, 7);
+                    HBHIP_LAUNCH(ctx, "cropscale_sws_v", scale_sws_v_kernel<uint8_t>, gv, dim3(64, 4), 0, w, (const int16_t *)hbuf16, 64 << 12, 19, 255);
                 }
+                else
+                {
+                    const int d = in_geo.depth, shift = 11 + 16 - d;
+                    HBHIP_LAUNCH(ctx, "cropscale_sws_h", scale_sws_h_kernel<uint16_t>, gh, dim3(64, 4), 0, w, (int16_t *)hbuf16, d - 1);
+                    HBHIP_LAUNCH(ctx, "cropscale_sws_v", scale_sws_v_kernel<uint16_t>, gv, dim3(64, 4), 0, w, (const int16_t *)hbuf16, 1 << (shift - 1), shift, (1 << d) - 1);
+                }
+            }
         HBHIP_CHECK(ctx, hipGetLastError());
         return HBHIP_OK;
     }
 
-    int process(DevPicture *in, DevPicture *out) override { return process_many(&in, &out, 1); }
     bool sws = false;           // libswscale's arithmetic (the reference's path for odd sizes) instead of zimg's
     bool up6 = true;            // six taps either way and every tile fits the fused kernel's LDS frame
     bool tall = true;           // ... also at 32 rows per tile

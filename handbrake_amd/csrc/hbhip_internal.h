@@ -494,8 +494,10 @@ struct SimpleFilter : hbhip_filter
 };
 
 // ---- bursts: the frames of a process_many() that go out in one launch ----
-// The rule, here and nowhere else: a launch takes up to MAXF consecutive frames whose three input and three output pitches
-// equal those of the first of them (the kernels take one pitch per plane for the whole launch).
+// The rule, here and nowhere else: a launch takes up to maxf consecutive frames whose three input and three output pitches
+// equal those of the first of them (the kernels take one pitch per plane for the whole launch).  Every one-in / one-out
+// filter cuts its process_many() with hbhip_for_each_run, directly or through hbhip_for_each_burst; whether a filter's
+// batched kernel can take a run (sample size, alignment, ...) is that filter's question, asked per run behind the cut.
 static inline bool hbhip_same_pitches(DevPicture *const *ins, DevPicture *const *outs, int i, int k)
 {
     for (int c = 0; c < 3; c++)
@@ -503,15 +505,29 @@ static inline bool hbhip_same_pitches(DevPicture *const *ins, DevPicture *const 
     return true;
 }
 
-// Cuts ins / outs [0, n) into such runs.  For the run [at, at + nf) a zeroed Args gets src[f][c], dst[f][c], spitch[c] and
-// dpitch[c], `bits` is every one of those addresses and pitches ORed together (the caller's alignment test), and
-// launch(a, nf, at, bits) fills in the rest and launches: anything but HBHIP_OK from it ends the walk with that code.
-template <int MAXF, class Args, class Fn>
-static int hbhip_for_each_burst(hbhip_ctx *ctx, DevPicture *const *ins, DevPicture *const *outs, int n, Fn &&launch)
+// The cut alone: fn(at, nf) for each maximal run [at, at + nf) of ins / outs [0, n), in order.  Anything but HBHIP_OK from
+// it ends the walk with that code, and so does a launch error behind a run.  For the filters whose argument structs lay
+// out planes and pitches their own way (or whose sources are not plane starts: crop/scale's windows).
+template <class Fn>
+static int hbhip_for_each_run(hbhip_ctx *ctx, DevPicture *const *ins, DevPicture *const *outs, int n, int maxf, Fn &&fn)
 {
     for (int at = 0, nf; at < n; at += nf)
     {
-        for (nf = 1; at + nf < n && nf < MAXF && hbhip_same_pitches(ins, outs, at, at + nf); ) nf++;
+        for (nf = 1; at + nf < n && nf < maxf && hbhip_same_pitches(ins, outs, at, at + nf); ) nf++;
+        const int rc = fn(at, nf);
+        if (rc != HBHIP_OK) return rc;
+        HBHIP_CHECK(ctx, hipGetLastError());
+    }
+    return HBHIP_OK;
+}
+
+// The cut and the fill, for argument structs of this shape: for the run [at, at + nf) a zeroed Args gets src[f][c],
+// dst[f][c], spitch[c] and dpitch[c], `bits` is every one of those addresses and pitches ORed together (the caller's
+// alignment test), and launch(a, nf, at, bits) fills in the rest and launches.
+template <int MAXF, class Args, class Fn>
+static int hbhip_for_each_burst(hbhip_ctx *ctx, DevPicture *const *ins, DevPicture *const *outs, int n, Fn &&launch)
+{
+    return hbhip_for_each_run(ctx, ins, outs, n, MAXF, [&](int at, int nf) {
         Args a;
         memset(&a, 0, sizeof(a));
         uintptr_t bits = 0;
@@ -525,9 +541,27 @@ static int hbhip_for_each_burst(hbhip_ctx *ctx, DevPicture *const *ins, DevPictu
                 bits |= (uintptr_t)a.src[f][c] | (uintptr_t)a.dst[f][c];
             }
         }
-        const int rc = launch(a, nf, at, bits);
+        return launch(a, nf, at, bits);
+    });
+}
+
+// Behind the cut: does every frame of the run pass the filter's test for its batched kernel ...
+template <class Fn>
+static bool hbhip_run_all(DevPicture *const *ins, DevPicture *const *outs, int at, int nf, Fn &&ok)
+{
+    for (int f = at; f < at + nf; f++)
+        if (!ok(ins[f], outs[f])) return false;
+    return true;
+}
+
+// ... and a run that does not: frame by frame through one(in, out), the filter's generic kernels.
+template <class Fn>
+static int hbhip_each_frame(DevPicture *const *ins, DevPicture *const *outs, int at, int nf, Fn &&one)
+{
+    for (int f = at; f < at + nf; f++)
+    {
+        const int rc = one(ins[f], outs[f]);
         if (rc != HBHIP_OK) return rc;
-        HBHIP_CHECK(ctx, hipGetLastError());
     }
     return HBHIP_OK;
 }

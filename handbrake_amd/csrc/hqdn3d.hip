@@ -465,10 +465,10 @@ __global__ __launch_bounds__(256) void hqdn3d_t_kernel(HqArgs a)
     reinterpret_cast<PIX *>(P.dst + (size_t)y * P.dpitch)[x] = (PIX)(t >> SH);
 }
 
-class Hqdn3dFilter : public SimpleFilter
+class Hqdn3dFilter : public BurstFilter
 {
 public:
-    Hqdn3dFilter(hbhip_ctx *c, const hbhip_hqdn3d_params &p) : SimpleFilter(c), par(p) {}
+    Hqdn3dFilter(hbhip_ctx *c, const hbhip_hqdn3d_params &p) : BurstFilter(c), par(p) {}
     ~Hqdn3dFilter() override
     {
         if (d_coef) (void)hipFree(d_coef);
@@ -496,7 +496,8 @@ public:
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         return HBHIP_OK;
     }
-    int process(DevPicture *in, DevPicture *out) override
+    // a frame on its own: the frame-at-a-time kernels
+    int one_frame(DevPicture *in, DevPicture *out)
     {
         HqArgs a;
         bool any_spatial = false, any_temporal = false;
@@ -538,28 +539,26 @@ public:
         else if (in_geo.depth == 10) HQ_GO(uint16_t, 6);
         else                         HQ_GO(uint16_t, 4);
 #undef HQ_GO
-        HBHIP_CHECK(ctx, hipGetLastError());
         return HBHIP_OK;
     }
     // Several frames: the spatial passes of all of them in one launch each, then the temporal step frame after frame
     // per sample (see HqBatch).  The same numbers as frame-by-frame calls: the spatial passes never looked at another
-    // frame, and the temporal chain is walked in the same order.
+    // frame, and the temporal chain is walked in the same order: the runs are taken in frame order, a run of one frame
+    // by the frame-at-a-time kernels.
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
-        if (n < 2) return SimpleFilter::process_many(ins, outs, n);
-        for (int c = 0; c < 3 && !hbuf_n[c]; c++)
-        {
-            const size_t bytes = sizeof(uint16_t) * (size_t)in_geo.pw[c] * in_geo.ph[c] * HQ_BATCH;
-            HBHIP_CHECK(ctx, hipMalloc((void **)&hbuf_n[c], bytes));
-            HBHIP_CHECK(ctx, hipMalloc((void **)&vsp_n[c], bytes));
-        }
-        for (int at = 0; at < n; at += HQ_BATCH)
-        {
-            const int k = std::min(HQ_BATCH, n - at);
+        return hbhip_for_each_run(ctx, ins, outs, n, HQ_BATCH, [&](int at, int k) {
+            if (k < 2) return one_frame(ins[at], outs[at]);
+            for (int c = 0; c < 3 && !hbuf_n[c]; c++)
+            {
+                const size_t bytes = sizeof(uint16_t) * (size_t)in_geo.pw[c] * in_geo.ph[c] * HQ_BATCH;
+                HBHIP_CHECK(ctx, hipMalloc((void **)&hbuf_n[c], bytes));
+                HBHIP_CHECK(ctx, hipMalloc((void **)&vsp_n[c], bytes));
+            }
             HqBatch B;
             memset(&B, 0, sizeof(B));
             B.n = k;
-            bool any_spatial = false, same = true;
+            bool any_spatial = false;
             int max_w = 0, max_h = 0;
             for (int c = 0; c < 3; c++)
             {
@@ -572,17 +571,7 @@ public:
                 B.spatial_on[c] = par.coef[2 * c][0] != 0;                  // spatial strength != 0 (denoise.c:191)
                 any_spatial |= B.spatial_on[c] != 0;
                 max_w = std::max(max_w, B.w[c]); max_h = std::max(max_h, B.h[c]);
-                for (int f = 0; f < k; f++)
-                {
-                    B.src[f][c] = ins[at + f]->plane[c]; B.dst[f][c] = outs[at + f]->plane[c];
-                    same &= ins[at + f]->pitch[c] == B.spitch[c] && outs[at + f]->pitch[c] == B.dpitch[c];
-                }
-            }
-            if (!same)
-            {
-                int rc = SimpleFilter::process_many(ins + at, outs + at, k);
-                if (rc != HBHIP_OK) return rc;
-                continue;
+                for (int f = 0; f < k; f++) { B.src[f][c] = ins[at + f]->plane[c]; B.dst[f][c] = outs[at + f]->plane[c]; }
             }
             auto cut = [&](int len, int target, int align, int most) {
                 HqSeg g;
@@ -604,10 +593,9 @@ public:
             else if (in_geo.depth == 10) HQ_GO_N(uint16_t, 6);
             else                         HQ_GO_N(uint16_t, 4);
 #undef HQ_GO_N
-            HBHIP_CHECK(ctx, hipGetLastError());
             for (int c = 0; c < 3; c++) seeded[c] = 1;
-        }
-        return HBHIP_OK;
+            return HBHIP_OK;
+        });
     }
     hbhip_hqdn3d_params par;
     uint16_t *hbuf_n[3] = {nullptr, nullptr, nullptr};   // batches: the h-filtered rows of HQ_BATCH frames per plane

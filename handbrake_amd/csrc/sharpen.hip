@@ -868,45 +868,51 @@ static bool lap_float_mix_cached(int kernel, double strength, int &kinv, float &
     return it->second.ok;
 }
 
-class LapsharpFilter : public SimpleFilter
+class LapsharpFilter : public BurstFilter
 {
 public:
-    LapsharpFilter(hbhip_ctx *c, const hbhip_lapsharp_params &p) : SimpleFilter(c), par(p)
+    LapsharpFilter(hbhip_ctx *c, const hbhip_lapsharp_params &p) : BurstFilter(c), par(p)
     {
         // the search behind lap_float_mix (tens of milliseconds) runs here, at create time - init() of the plugin -, once
         // per (kernel, strength) of the process, not inside the first frame's work()
         for (int pl = 0; pl < 3; pl++)
+        {
             mix_fast[pl] = LAP_TABLE[par.kernel[pl]].size == 3 && lap_float_mix_cached(par.kernel[pl], par.strength[pl], mix_k[pl], mix_f[pl]);
+            rows3 &= LAP_TABLE[par.kernel[pl]].size == 3;
+        }
+    }
+    // what LapPlane3 and LapArgs share, for plane c
+    template <class P>
+    void fill_plane(P &p, const DevPicture *in, const DevPicture *out, int c) const
+    {
+        p.width = in->width[c]; p.height = in->height[c];
+        p.src_pitch = in->pitch[c]; p.dst_pitch = out->pitch[c];
+        // host buffers: the caller's stride decides (lapsharp.c:145); device-resident frames have no
+        // hb_buffer stride, so use what hb_image_stride would be and read the padding as zeros
+        // (in samples: the reference divides the strides by bps first, lapsharp.c:137-138)
+        const int hb_stride = in_is_dev ? hbhip_align_up(in->width[c] * in->bps, 64) / in->bps : in_stride[c] / in->bps;
+        p.stride_border = (hb_stride - in->width[c]) / 2;
+        p.valid_w = in_is_dev ? in->width[c] : (1 << 30);
+        p.coef = LAP_TABLE[par.kernel[c]].coef; p.strength = par.strength[c];
     }
     // up to LS_FRAMES frames per launch when every plane uses a 3x3 kernel
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
-        bool rows3 = true;
-        for (int c = 0; c < 3; c++) rows3 &= LAP_TABLE[par.kernel[c]].size == 3;
-        if (!rows3) return SimpleFilter::process_many(ins, outs, n);
-        for (int at = 0; at < n; at += LS_FRAMES)
-        {
-            const int nf = std::min(LS_FRAMES, n - at);
+        return hbhip_for_each_run(ctx, ins, outs, n, LS_FRAMES, [&](int at, int nf) {
+            if (!rows3) return hbhip_each_frame(ins, outs, at, nf, [&](DevPicture *in, DevPicture *out) { return one_frame(in, out); });
             LapBatch3 B;
             int max_w = 0, max_h = 0;
             for (int c = 0; c < 3; c++)
             {
                 const LapKernel &k = LAP_TABLE[par.kernel[c]];
-                const DevPicture *in = ins[at];
                 LapPlane3 &P = B.pl[c];
-                P.width = in->width[c]; P.height = in->height[c];
-                P.src_pitch = in->pitch[c]; P.dst_pitch = outs[at]->pitch[c];
-                const int hb_stride = in_is_dev ? hbhip_align_up(in->width[c] * in->bps, 64) / in->bps : in_stride[c] / in->bps;
-                P.stride_border = (hb_stride - in->width[c]) / 2;
-                P.valid_w = in_is_dev ? in->width[c] : (1 << 30);
+                fill_plane(P, ins[at], outs[at], c);
                 P.a = k.tap[0]; P.b = k.tap[1]; P.c = k.tap[4];
-                P.coef = k.coef; P.strength = par.strength[c];
                 P.active = 1;
                 P.fast = in_geo.bps == 1 && mix_fast[c]; P.kinv = mix_k[c]; P.mixf = mix_f[c];
                 max_w = std::max(max_w, P.width); max_h = std::max(max_h, P.height);
                 for (int f = 0; f < nf; f++)
                 {
-                    if (ins[at + f]->pitch[c] != P.src_pitch || outs[at + f]->pitch[c] != P.dst_pitch) return SimpleFilter::process_many(ins, outs, n);
                     B.src[f][c] = ins[at + f]->plane[c];
                     B.dst[f][c] = outs[at + f]->plane[c];
                 }
@@ -916,18 +922,12 @@ public:
             const dim3 grid(hbhip_grid_x(((max_w + 3) / 4 + LS_BX - 1) / LS_BX), (max_h + rows - 1) / rows, 3 * nf);
             if (in_geo.bps == 1) HBHIP_LAUNCH(ctx, "lapsharp_3x3", lapsharp3_rows_kernel, grid, dim3(LS_BX, LS_BY), 0, B);
             else                 HBHIP_LAUNCH(ctx, "lapsharp_3x3", lapsharp3_rows16_kernel, grid, dim3(LS_BX, LS_BY), 0, B, (1 << in_geo.depth) - 1);
-            HBHIP_CHECK(ctx, hipGetLastError());
-        }
-        return HBHIP_OK;
+            return HBHIP_OK;
+        });
     }
-    int process(DevPicture *in, DevPicture *out) override
+    // the generic kernels: one launch per kernel size present (3x3: lap / isolap, 5x5: log / isolog), covering the planes that use it
+    int one_frame(DevPicture *in, DevPicture *out)
     {
-        if (LAP_TABLE[par.kernel[0]].size == 3 && LAP_TABLE[par.kernel[1]].size == 3 && LAP_TABLE[par.kernel[2]].size == 3)
-        {
-            DevPicture *i1[1] = { in }, *o1[1] = { out };
-            return process_many(i1, o1, 1);
-        }
-        // one launch per kernel size present (3x3: lap / isolap, 5x5: log / isolog), covering the planes that use it
         for (int size : {3, 5})
         {
             LapArgs3 all;
@@ -938,16 +938,8 @@ public:
                 if (k.size != size) continue;
                 LapArgs &a = all.p[n++];
                 a.src = in->plane[c]; a.dst = out->plane[c];
-                a.width = in->width[c]; a.height = in->height[c];
-                a.src_pitch = in->pitch[c]; a.dst_pitch = out->pitch[c];
-                // host buffers: the caller's stride decides (lapsharp.c:145); device-resident frames have no
-                // hb_buffer stride, so use what hb_image_stride would be and read the padding as zeros
-                // (in samples: the reference divides the strides by bps first, lapsharp.c:137-138)
-                const int hb_stride = in_is_dev ? hbhip_align_up(in->width[c] * in->bps, 64) / in->bps : in_stride[c] / in->bps;
-                a.stride_border = (hb_stride - in->width[c]) / 2;
-                a.valid_w = in_is_dev ? in->width[c] : (1 << 30);
+                fill_plane(a, in, out, c);
                 for (int i = 0; i < 25; i++) a.tap[i] = k.tap[i];
-                a.coef = k.coef; a.strength = par.strength[c];
                 max_w = std::max(max_w, a.width); max_h = std::max(max_h, a.height);
             }
             if (n == 0) continue;
@@ -965,21 +957,33 @@ public:
                 if (size == 3) HBHIP_LAUNCH(ctx, name, lapsharp_kernel<3>, grid, dim3(256), 0, all);
                 else           HBHIP_LAUNCH(ctx, name, lapsharp_kernel<5>, grid, dim3(256), 0, all);
             }
-            HBHIP_CHECK(ctx, hipGetLastError());
         }
         return HBHIP_OK;
     }
     hbhip_lapsharp_params par;
+    bool  rows3 = true;                            // every plane uses a 3x3 kernel: the rows kernels take the frames
     bool  mix_fast[3] = {};                        // lap_float_mix per plane (the constructor)
     int   mix_k[3] = {};
     float mix_f[3] = {};
 };
 
-class BlurMixFilter : public SimpleFilter
+// the binomial row of order 2 * steps in coef[0 .. len), zeros behind it
+static void binomial_row(int steps, uint32_t *coef, int len)
+{
+    for (int i = 0; i < len; i++) coef[i] = 0;
+    coef[0] = 1;
+    for (int k = 1; k <= 2 * steps; k++)
+    {
+        coef[k] = 1;
+        for (int i = k - 1; i >= 1; i--) coef[i] += coef[i - 1];
+    }
+}
+
+class BlurMixFilter : public BurstFilter
 {
 public:
     BlurMixFilter(hbhip_ctx *c, const hbhip_blur_params &p, int sign_, int vmin_, int vmax_, const char *nm)
-        : SimpleFilter(c), par(p), sign(sign_), vmin(vmin_), vmax(vmax_), name(nm) {}
+        : BurstFilter(c), par(p), sign(sign_), vmin(vmin_), vmax(vmax_), name(nm) {}
     // the rows kernel takes 8-bit planes with sizes up to 9 whose rows are dword aligned
     bool rows_ok(const DevPicture *in, const DevPicture *out) const
     {
@@ -990,6 +994,15 @@ public:
             if ((in->pitch[c] & 3) || (out->pitch[c] & 3) || ((uintptr_t)in->plane[c] & 3) || ((uintptr_t)out->plane[c] & 3)) return false;
         }
         return true;
+    }
+    // up to BR_FRAMES frames per launch (hbhip_filter_process_dev / a chain batch)
+    int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
+    {
+        return hbhip_for_each_run(ctx, ins, outs, n, BR_FRAMES, [&](int at, int nf) {
+            if (!hbhip_run_all(ins, outs, at, nf, [&](DevPicture *in, DevPicture *out) { return rows_ok(in, out); }))
+                return hbhip_each_frame(ins, outs, at, nf, [&](DevPicture *in, DevPicture *out) { return one_frame(in, out); });
+            return run_rows(ins + at, outs + at, nf);
+        });
     }
     int run_rows(DevPicture *const *ins, DevPicture *const *outs, int nf)
     {
@@ -1008,13 +1021,7 @@ public:
             P.steps = P.amount ? par.size[c] / 2 : 0;
             P.scalebits = P.steps * 4;
             P.halfscale = P.steps ? 1 << (P.scalebits - 1) : 0;
-            uint32_t row[2 * BR_MAX_STEPS + 1] = {1};                       // binomial row of order 2*steps
-            for (int k = 1; k <= 2 * P.steps; k++)
-            {
-                row[k] = 1;
-                for (int i = k - 1; i >= 1; i--) row[i] += row[i - 1];
-            }
-            for (int i = 0; i <= 2 * BR_MAX_STEPS; i++) P.coef[i] = i <= 2 * P.steps ? row[i] : 0;
+            binomial_row(P.steps, P.coef, 2 * BR_MAX_STEPS + 1);
             if (P.amount) want[P.steps] = true;
             max_w = std::max(max_w, P.width); max_h = std::max(max_h, P.height);
             for (int f = 0; f < nf; f++) { B.src[f][c] = ins[f]->plane[c]; B.dst[f][c] = outs[f]->plane[c]; }
@@ -1037,29 +1044,11 @@ public:
         }
         if (!copies_done)                                                    // nothing filtered: every plane is a copy
             HBHIP_LAUNCH(ctx, name, blur_rows8_kernel<1>, grid, block, 0, B);
-        HBHIP_CHECK(ctx, hipGetLastError());
         return HBHIP_OK;
     }
-    // up to BR_FRAMES frames per launch (hbhip_filter_process_dev / a chain batch)
-    int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
+    // the generic kernel: any depth, size and alignment
+    int one_frame(DevPicture *in, DevPicture *out)
     {
-        bool ok = n > 0;
-        for (int f = 0; f < n && ok; f++)
-        {
-            ok = rows_ok(ins[f], outs[f]);
-            for (int c = 0; c < 3 && ok; c++) ok = ins[f]->pitch[c] == ins[0]->pitch[c] && outs[f]->pitch[c] == outs[0]->pitch[c];
-        }
-        if (!ok) return SimpleFilter::process_many(ins, outs, n);
-        for (int at = 0; at < n; at += BR_FRAMES)
-        {
-            const int rc = run_rows(ins + at, outs + at, std::min(BR_FRAMES, n - at));
-            if (rc != HBHIP_OK) return rc;
-        }
-        return HBHIP_OK;
-    }
-    int process(DevPicture *in, DevPicture *out) override
-    {
-        if (rows_ok(in, out)) return run_rows(&in, &out, 1);
         BlurArgs3 all;
         int n = 0, max_w = 0, max_h = 0;
         for (int c = 0; c < 3; c++)
@@ -1080,14 +1069,7 @@ public:
             a.halfscale = 1 << (a.scalebits - 1);
             a.amount = amount;
             a.sign = sign; a.vmin = vmin; a.vmax = vmax;
-            // binomial row of order 2*steps
-            uint32_t row[2 * MAX_STEPS + 1] = {1};
-            for (int k = 1; k <= 2 * a.steps; k++)
-            {
-                row[k] = 1;
-                for (int i = k - 1; i >= 1; i--) row[i] += row[i - 1];
-            }
-            for (int i = 0; i <= 2 * MAX_STEPS; i++) a.coef[i] = i <= 2 * a.steps ? row[i] : 0;
+            binomial_row(a.steps, a.coef, 2 * MAX_STEPS + 1);
             max_w = std::max(max_w, a.width); max_h = std::max(max_h, a.height);
         }
         if (n > 0)
@@ -1096,7 +1078,6 @@ public:
             dim3 grid((max_w + BT_W - 1) / BT_W, (max_h + BT_H - 1) / BT_H, n), block(256);
             if (in->bps == 2) HBHIP_LAUNCH(ctx, name, blur_mix_kernel<uint16_t>, grid, block, 0, all);
             else              HBHIP_LAUNCH(ctx, name, blur_mix_kernel<uint8_t>, grid, block, 0, all);
-            HBHIP_CHECK(ctx, hipGetLastError());
         }
         return HBHIP_OK;
     }

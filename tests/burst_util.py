@@ -5,12 +5,14 @@ import numpy as np
 from handbrake_amd import hip
 
 
-def bursts(make_filter, frames, sizes, pads=(0,), depth=8, out_shape=None, setup=None, out_depth=None, ctx=None):
+def bursts(make_filter, frames, sizes, pads=(0,), depth=8, out_shape=None, setup=None, out_depth=None, ctx=None,
+           out_row_bytes=1):
     """`frames` (tuples of three numpy planes) through make_filter(ctx) in bursts of the given sizes; input i's rows are
     padded by pads[i % len(pads)] samples, so that pitches mix inside a burst.  Returns the output frames as lists of
     numpy planes, or None when setup(flt) - a knob of the filter's, applied once - returns a non-zero code.
     out_shape: the (height, width) of the output luma where it differs from the input's (pad); out_depth: the output's
-    depth where it differs (format); ctx: a context of the caller's, left open (its profile, say), else one of its own."""
+    depth where it differs (format); ctx: a context of the caller's, left open (its profile, say), else one of its own;
+    out_row_bytes: the output rows' pitch is rounded up to a multiple of this (a 40-byte chroma row on a 16-byte pitch)."""
     import torch
     tdt = lambda d: torch.int16 if d > 8 else torch.uint8
     conv = lambda t: t.cpu().numpy().view(np.uint16) if t.dtype == torch.int16 else t.cpu().numpy()
@@ -41,7 +43,9 @@ def bursts(make_filter, frames, sizes, pads=(0,), depth=8, out_shape=None, setup
             shapes = [p.shape for p in part[0]]
             if out_shape is not None:                                    # the chroma planes grow by the luma's ratio
                 shapes = [(s[0] * out_shape[0] // shapes[0][0], s[1] * out_shape[1] // shapes[0][1]) for s in shapes]
-            outs = [[torch.full(s, 7, dtype=tdt(out_depth), device="cuda") for s in shapes] for _ in part]
+            unit = max(1, out_row_bytes // (2 if out_depth > 8 else 1))                     # in samples
+            outs = [[torch.full((s[0], -(-s[1] // unit) * unit), 7, dtype=tdt(out_depth), device="cuda")[:, :s[1]] for s in shapes]
+                    for _ in part]
             torch.cuda.synchronize()
             arr_in = (hip.DevFrame * n)(*[hip.dev_frame(f) for f in dev_in])
             arr_out = (hip.DevFrame * n)(*[hip.dev_frame(o) for o in outs])
