@@ -103,19 +103,15 @@ __device__ __forceinline__ W12<PIX> ldw12(const uint8_t *row, int x, int pitch)
     return W12<PIX>{ x >= 4 ? p[-1] : Px4<PIX>::zero(), p[0], x + 4 < pitch ? p[1] : Px4<PIX>::zero() };
 }
 
+// samples x .. x + 3 of row y of plane pl of frame F (x < w, y < h): every mode
 template <typename PIX>
-__global__ __launch_bounds__(256) void decomb_plane4_kernel(DecombBatch B, int maxv)
+__device__ __forceinline__ void decomb_row4(const DecombBatch &B, const DecombFrame &F, int pl, int x, int y, int maxv)
 {
     typedef Px4<PIX> X4;
     typedef typename X4::T T;
     typedef W12<PIX> WIN;
-    const int pl = blockIdx.z % 3;
-    const DecombFrame &F = B.f[blockIdx.z / 3];
     const int w = B.w[pl], h = B.h[pl], st = B.pitch[pl];             // st: bytes between rows
     const int pitch_s = st / (int)sizeof(PIX);
-    const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
-    const int y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x >= w || y >= h) return;
     const uint8_t *cb = F.cur[pl];
     const uint8_t *crow = cb + (size_t)y * st;
     uint8_t *orow = F.dst[pl] + (size_t)y * B.dst_pitch[pl];
@@ -278,6 +274,106 @@ __global__ __launch_bounds__(256) void decomb_plane4_kernel(DecombBatch B, int m
         o4[k] = pred;
     }
     store(X4::pack(o4));
+}
+
+template <typename PIX>
+__global__ __launch_bounds__(256) void decomb_plane4_kernel(DecombBatch B, int maxv)
+{
+    const int pl = blockIdx.z % 3;
+    const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
+    const int y = blockIdx.y * blockDim.y + threadIdx.y;
+    if (x >= B.w[pl] || y >= B.h[pl]) return;
+    decomb_row4<PIX>(B, B.f[blockIdx.z / 3], pl, x, y, maxv);
+}
+
+// ---- the EEDI2-guided yadif (mode & M_EEDI2, 8-bit), walked down the rows --------------------------------------------------
+// decomb_row4 loads thirteen dwords for a rebuilt row and unpacks all of them, and rows y + 1 of one rebuilt row are rows
+// y - 1 of the next.  Here a thread owns four columns of a strip of 2 DW_R rows: it walks the strip's DW_R rebuilt rows
+// downwards and carries, per sample, what the next row needs again - cur[y + 1] (the next row's cur[y - 1]), |prev[y + 1] -
+// cur[y + 1]| and |next[y + 1] - cur[y + 1]| (the first terms of the next td1 / td2), and the averages of the rows y and
+// y + 2 of the two same-parity fields (f becomes d becomes b; |p2 - n2| of row y + 2 is the next td0): six new dwords a
+// rebuilt row.  The kept row beside each rebuilt one is stored from the cur dword the thread holds anyway.  All of a strip's
+// loads are issued before its first store (lapsharp3_rows_kernel has the reason).  The arithmetic is decomb_row4's, per
+// sample in 32 bits.  Strips that touch the rows next to the plane's top or bottom (vertical_edge, the mirrored sp / sn), and
+// frames in any other mode, go row by row through decomb_row4.
+#ifndef DW_R_N
+#define DW_R_N 8
+#endif
+constexpr int DW_R = DW_R_N;
+
+__global__ __launch_bounds__(256) void decomb_rowwalk8_kernel(DecombBatch B, int maxv)
+{
+    typedef Px4<uint8_t> X4;
+    const int pl = blockIdx.z % 3;
+    const DecombFrame &F = B.f[blockIdx.z / 3];
+    const int w = B.w[pl], h = B.h[pl], st = B.pitch[pl], dst_st = B.dst_pitch[pl];
+    const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
+    const int ys = (blockIdx.y * blockDim.y + threadIdx.y) * (2 * DW_R);
+    if (x >= w || ys >= h) return;
+    const int y0 = ys + (F.parity ? 0 : 1);                                      // the strip's first rebuilt row (:795-807)
+    const bool walk = (F.mode & M_EEDI2) && (F.mode & M_YADIF) && !B.ff && y0 >= 3 && y0 + 2 * (DW_R - 1) <= h - 4;
+    if (!walk)                                                                   // uniform for the thread row
+    {
+        for (int r = 0; r < 2 * DW_R && ys + r < h; r++) decomb_row4<uint8_t>(B, F, pl, x, ys + r, maxv);
+        return;
+    }
+    auto dw = [&](const uint8_t *base, int y, int pitch) { return *reinterpret_cast<const uint32_t *>(base + (size_t)y * pitch + x); };
+    auto store = [&](int y, uint32_t v) {
+        uint8_t *o = F.dst[pl] + (size_t)y * dst_st + x;
+        if (x + 3 < w) *reinterpret_cast<uint32_t *>(o) = v;
+        else for (int k = 0; k < 4 && x + k < w; k++) o[k] = (uint8_t)X4::get(v, k);
+    };
+    const uint8_t *p2base = F.field_parity ? F.prev[pl] : F.cur[pl], *n2base = F.field_parity ? F.cur[pl] : F.next[pl];
+    // rows y0 - 1 + 2 i of cur / prev / next, rows y0 - 2 + 2 i of the same-parity fields, rows y0 + 2 i of the guess
+    uint32_t cu[DW_R + 1], pv[DW_R + 1], nx[DW_R + 1], p2[DW_R + 2], n2[DW_R + 2], gs[DW_R];
+#pragma unroll
+    for (int i = 0; i < DW_R + 1; i++)
+    {
+        cu[i] = dw(F.cur[pl], y0 - 1 + 2 * i, st); pv[i] = dw(F.prev[pl], y0 - 1 + 2 * i, st); nx[i] = dw(F.next[pl], y0 - 1 + 2 * i, st);
+    }
+#pragma unroll
+    for (int i = 0; i < DW_R + 2; i++) { p2[i] = dw(p2base, y0 - 2 + 2 * i, st); n2[i] = dw(n2base, y0 - 2 + 2 * i, st); }
+#pragma unroll
+    for (int i = 0; i < DW_R; i++) gs[i] = dw(F.guess[pl], y0 + 2 * i, B.guess_pitch[pl]);
+
+    int cc[4], a_pu[4], a_nu[4], b[4], d[4], td0[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+    {
+        cc[k] = X4::get(cu[0], k);
+        a_pu[k] = abs(X4::get(pv[0], k) - cc[k]);
+        a_nu[k] = abs(X4::get(nx[0], k) - cc[k]);
+        b[k] = (X4::get(p2[0], k) + X4::get(n2[0], k)) >> 1;
+        d[k] = (X4::get(p2[1], k) + X4::get(n2[1], k)) >> 1;
+        td0[k] = abs(X4::get(p2[1], k) - X4::get(n2[1], k));
+    }
+#pragma unroll
+    for (int i = 0; i < DW_R; i++)
+    {
+        const int y = y0 + 2 * i;
+        int o4[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+        {
+            const int e = X4::get(cu[i + 1], k);
+            const int a_pd = abs(X4::get(pv[i + 1], k) - e), a_nd = abs(X4::get(nx[i + 1], k) - e);
+            const int P2 = X4::get(p2[i + 2], k), N2 = X4::get(n2[i + 2], k);
+            const int f = (P2 + N2) >> 1;
+            const int td1 = (a_pu[k] + a_pd) >> 1, td2 = (a_nu[k] + a_nd) >> 1;
+            int diff = max3i(td0[k] >> 1, td1, td2);
+            int pred = X4::get(gs[i], k);
+            const int mx = max3i(d[k] - e, d[k] - cc[k], min(b[k] - cc[k], f - e));
+            const int mn = min3i(d[k] - e, d[k] - cc[k], max(b[k] - cc[k], f - e));
+            diff = max3i(diff, mn, -mx);
+            if (pred > d[k] + diff)      pred = d[k] + diff;
+            else if (pred < d[k] - diff) pred = d[k] - diff;
+            o4[k] = pred;
+            cc[k] = e; a_pu[k] = a_pd; a_nu[k] = a_nd; b[k] = d[k]; d[k] = f; td0[k] = abs(P2 - N2);
+        }
+        store(y, X4::pack(o4));
+        if (F.parity) store(y + 1, cu[i + 1]);                                    // the kept row of the pair (:795-807)
+        else          store(y - 1, cu[i]);
+    }
 }
 
 // ------------------------------------------------------------------- host side
@@ -606,7 +702,15 @@ private:
             for (int k = 0; k < B.n; k++) B.f[k] = gathered[i0 + k];
             const dim3 block(64, 4), grid(hbhip_grid_x((B.w[0] + 255) / 256), (B.h[0] + 3) / 4, 3 * B.n);
             const int maxv = (1 << in_geo.depth) - 1;
-            if (ff_yadif)
+            // every frame of the launch EEDI2-guided yadif on 8-bit samples: the row walk
+            bool walk = !ff_yadif && in_geo.bps == 1;
+            for (int k = 0; k < B.n; k++) walk &= (B.f[k].mode & M_EEDI2) && (B.f[k].mode & M_YADIF) && B.f[k].guess[0];
+            if (walk)
+            {
+                const dim3 wgrid(grid.x, (B.h[0] + 8 * DW_R - 1) / (8 * DW_R), grid.z);
+                HBHIP_LAUNCH(lc, "decomb_plane", decomb_rowwalk8_kernel, wgrid, block, 0, B, maxv);
+            }
+            else if (ff_yadif)
             {
                 if (in_geo.bps == 2) HBHIP_LAUNCH(lc, "yadif", decomb_plane4_kernel<uint16_t>, grid, block, 0, B, maxv);
                 else                 HBHIP_LAUNCH(lc, "yadif", decomb_plane4_kernel<uint8_t>, grid, block, 0, B, maxv);

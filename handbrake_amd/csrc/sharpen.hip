@@ -14,6 +14,7 @@
 #include <mutex>
 #include <utility>
 #include "hbhip_internal.h"
+#include "lapsharp_rowdot.h"
 
 namespace {
 
@@ -590,7 +591,7 @@ int launch_copy(hbhip_ctx *ctx, const char *name, DevPicture *in, DevPicture *ou
 // (16-bit samples: four rows per thread - 2160p x 16 frames 197 us per launch against 211 at eight; at 8 bits eight rows are
 // 7 % ahead of four, profiles/r6g_lapsharp_block_shapes.log)
 constexpr int LS_ROWS = LS_ROWS_N, LS_ROWS16 = LS_ROWS16_N, LS_FRAMES = 16, LS_BX = LS_BX_N, LS_BY = 256 / LS_BX_N;
-struct LapPlane3 { int width, height, src_pitch, dst_pitch, stride_border, valid_w, a, b, c, active; double coef, strength; int fast, kinv; float mixf; };
+struct LapPlane3 { int width, height, src_pitch, dst_pitch, stride_border, valid_w, a, b, c, active; double coef, strength; int fast, kinv; float mixf; LrdTaps taps; float ckf; };
 struct LapBatch3
 {
     LapPlane3      pl[3];
@@ -720,6 +721,183 @@ __global__ __launch_bounds__(256) void lapsharp3_rows_kernel(LapBatch3 B)
         else for (int k = 0; x0 + k < P.width; k++) d[k] = (uint8_t)(packed >> (8 * k));
 #pragma unroll
         for (int k = 0; k < 4; k++) { u_prev[k] = u_cur[k]; u_cur[k] = u_next[k]; v_cur[k] = v_next[k]; m_cur[k] = m_next[k]; }
+    }
+}
+
+// ---- the same walk, wider: what runs where every plane and pitch is aligned to a lane's 4 LW_DW bytes and luma fills a
+// wave's span (the shape is measured: profiles/r11_lapsharp_block_shapes.log) ------------------------------
+// lapsharp3_rows_kernel reads every sample three times (each lane its own dword and both neighbours'), a workgroup row is
+// two 128-byte lines of payload between two more that only its edge lanes touch - the neighbouring workgroup runs on
+// another XCD with its own L2 -, and a pixel costs ~22 vector instructions.  Here a lane loads LW_DW dwords of a row ONCE,
+// takes the dword to its left and to its right from the neighbouring lanes (DPP wave shifts; only lane 0 and lane 63 of a
+// wave load one dword beyond the wave's span, and within a workgroup that is L1), LW_WX waves stand side by side so that a
+// workgroup row is LW_SPAN bytes, and the row sums are byte dot products (lapsharp_rowdot.h): per pixel one v_alignbyte
+// for its window, two v_dot4_u32_u8 and one v_add3_u32 for the nine taps.  The one-float-multiply mix stays in float up
+// to a saturating v_cvt_pk_u8_f32; the double form is lapsharp3_rows_kernel's, operation for operation.  Every lane of a
+// wave that has a column inside the plane stays active to the end (the exchanges need all 64): lanes beyond the plane's
+// width load clamped addresses and skip their store.
+#ifndef LW_DW_N
+#define LW_DW_N 2
+#endif
+#ifndef LW_WX_N
+#define LW_WX_N 2
+#endif
+#ifndef LW_BY_N
+#define LW_BY_N 2
+#endif
+#ifndef LW_ROWS_N
+#define LW_ROWS_N 8
+#endif
+constexpr int LW_DW = LW_DW_N, LW_WX = LW_WX_N, LW_BY = LW_BY_N, LW_ROWS = LW_ROWS_N;
+constexpr int LW_PX = 4 * LW_DW, LW_WAVE_SPAN = 64 * LW_PX, LW_SPAN = LW_WX * LW_WAVE_SPAN;
+struct alignas(4 * LW_DW) LwVec { uint32_t v[LW_DW]; };
+
+__device__ __forceinline__ uint32_t lw_from_lane_below(uint32_t x)   // lane l <- lane l-1 (all 64 lanes active)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+}
+__device__ __forceinline__ uint32_t lw_from_lane_above(uint32_t x)   // lane l <- lane l+1
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x130 /* wave_shl:1 */, 0xf, 0xf, false);
+}
+// the low `keep` bytes of a dword (keep <= 0: none, keep >= 4: all)
+__device__ __forceinline__ uint32_t lw_keep_mask(int keep) { return keep <= 0 ? 0u : keep >= 4 ? 0xffffffffu : (1u << (8 * keep)) - 1u; }
+
+__global__ __launch_bounds__(64 * LW_WX * LW_BY) void lapsharp3_wide_kernel(LapBatch3 B)
+{
+    constexpr int NDW = LW_DW, PX = LW_PX, R = LW_ROWS;
+    const int job = blockIdx.z, f = job / 3, c = job - 3 * f;
+    const LapPlane3 &P = B.pl[c];
+    if (!P.active) return;
+    const int lane = threadIdx.x & 63;
+    const int x0 = (blockIdx.x * (64 * LW_WX) + threadIdx.x) * PX;
+    const int ys = (blockIdx.y * LW_BY + threadIdx.y) * R;
+    const int wave_x0 = x0 - lane * PX;
+    if (wave_x0 >= P.width || ys >= P.height) return;                        // wave-uniform: a wave stays whole
+    const uint8_t *src = B.src[f][c];
+    uint8_t *dst = B.dst[f][c];
+    // What lapsharp3_rows_kernel reads, sample for sample: the dword left of column 0 is the row's first dword, the dword
+    // right of the pitch's last one is that last one (both only reach pixels that end up copied), and bytes at
+    // x >= valid_w read as 0 by the position they stand for.  Lanes that start beyond the pitch load its last dwords.
+    const uint32_t ow = (uint32_t)min(x0, P.src_pitch - PX);
+    const bool rclamp = x0 + PX >= P.src_pitch;                              // no dword to the right of this lane's
+    const bool lload = lane == 0, rload = lane == 63 && !rclamp;
+    const uint32_t oe = (uint32_t)min(lload ? max(x0 - 4, 0) : x0 + PX, P.src_pitch - 4);
+    const bool tail = wave_x0 + LW_WAVE_SPAN + 4 > P.valid_w;               // wave-uniform
+    uint32_t keep[NDW + 2];
+#pragma unroll
+    for (int j = 0; j < NDW + 2; j++) keep[j] = lw_keep_mask(P.valid_w - (x0 - 4 + 4 * j));
+
+    LwVec raw[R + 2];
+    uint32_t edge[R + 2];
+#pragma unroll
+    for (int i = 0; i < R + 2; i++)
+    {
+        const int yy = min(max(ys - 1 + i, 0), P.height - 1);                // (outside the plane: only read for pixels that end up copied)
+        raw[i] = *reinterpret_cast<const LwVec *>(src + ((uint32_t)__mul24(yy, P.src_pitch) + ow));
+        edge[i] = 0;
+    }
+    if (lload || rload)
+    {
+#pragma unroll
+        for (int i = 0; i < R + 2; i++)
+        {
+            const int yy = min(max(ys - 1 + i, 0), P.height - 1);
+            edge[i] = *reinterpret_cast<const uint32_t *>(src + ((uint32_t)__mul24(yy, P.src_pitch) + oe));
+        }
+    }
+    const LrdTaps taps = P.taps;
+    // a row's U for the thread's PX pixels, and its H where the row is an output row
+    auto prep = [&](int i, uint32_t (&u)[PX], uint32_t (&h)[PX]) __attribute__((always_inline)) {
+        const uint32_t below = lw_from_lane_below(raw[i].v[NDW - 1]), above = lw_from_lane_above(raw[i].v[0]);
+        uint32_t ext[NDW + 2];
+        ext[0] = lload ? edge[i] : below;
+#pragma unroll
+        for (int k = 0; k < NDW; k++) ext[1 + k] = raw[i].v[k];
+        ext[NDW + 1] = rclamp ? raw[i].v[NDW - 1] : rload ? edge[i] : above;
+        if (tail)
+        {
+#pragma unroll
+            for (int j = 0; j < NDW + 2; j++) ext[j] &= keep[j];
+#pragma unroll
+            for (int k = 0; k < NDW; k++) raw[i].v[k] = ext[1 + k];
+        }
+#pragma unroll
+        for (int p = 0; p < PX; p++)
+        {
+            const uint32_t win = lrd_window<NDW>(ext, p);
+            u[p] = lrd_row_u(win, taps);
+            h[p] = lrd_row_h(win, taps);
+        }
+    };
+    uint32_t u_prev[PX], u_cur[PX], h_cur[PX];
+    {
+        uint32_t h_tmp[PX];
+        prep(0, u_prev, h_tmp);
+        prep(1, u_cur, h_cur);
+    }
+    // the bytes of the thread's dwords that are copied whatever the row (lapsharp.c:167-171)
+    uint32_t copy_cols[NDW];
+    bool has_copy = false;
+#pragma unroll
+    for (int k = 0; k < NDW; k++)
+    {
+        copy_cols[k] = 0;
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            if (x0 + 4 * k + j < P.stride_border + 2 || x0 + 4 * k + j > P.width + P.stride_border - 2) copy_cols[k] |= 0xffu << (8 * j);
+        has_copy |= copy_cols[k] != 0;
+    }
+    const int y_end = min(ys + R, P.height);
+    const float ckf = P.ckf, mixf = P.mixf;
+#pragma unroll
+    for (int r = 0; r < R; r++)
+    {
+        const int y = ys + r;
+        if (y >= y_end) break;                                               // wave-uniform
+        uint32_t u_next[PX], h_next[PX];
+        prep(r + 2, u_next, h_next);
+        const LwVec own = raw[r + 1];
+        LwVec out = own;
+        if (!((y < 2) || (y > P.height - 2)))                                // wave-uniform (a wave works on one row)
+        {
+#pragma unroll
+            for (int k = 0; k < NDW; k++)
+            {
+                uint32_t packed = 0;
+                if (P.fast)                                                  // one float multiply stands for the mix (lap_float_mix)
+                {
+#define LW_PIX(J) packed = __builtin_amdgcn_cvt_pk_u8_f32(lrd_mix_fast<J>(own.v[k], lrd_neg_sum(h_cur[4 * k + J], u_prev[4 * k + J], u_next[4 * k + J]), ckf, mixf), J, packed)
+                    LW_PIX(0); LW_PIX(1); LW_PIX(2); LW_PIX(3);
+#undef LW_PIX
+                }
+                else
+                {
+#pragma unroll
+                    for (int j = 0; j < 4; j++)
+                    {
+                        const int centre = (int)((own.v[k] >> (8 * j)) & 0xffu);
+                        const int acc = lrd_acc(centre, lrd_neg_sum(h_cur[4 * k + j], u_prev[4 * k + j], u_next[4 * k + j]), taps);
+                        const double mixed = (((double)acc * P.coef) - (double)centre) * P.strength;   // lapsharp.c:174-175
+                        int o = (int)(short)(int)mixed + centre;
+                        o = min(max(o, 0), 255);
+                        packed |= (uint32_t)o << (8 * j);
+                    }
+                }
+                if (has_copy) packed = (packed & ~copy_cols[k]) | (own.v[k] & copy_cols[k]);   // border columns keep the source sample
+                out.v[k] = packed;
+            }
+        }
+        uint8_t *d = dst + ((uint32_t)__mul24(y, P.dst_pitch) + (uint32_t)x0);
+        if (x0 + PX <= P.width) *reinterpret_cast<LwVec *>(d) = out;
+        else
+        {
+#pragma unroll
+            for (int k = 0; k < PX; k++)
+                if (x0 + k < P.width) d[k] = (uint8_t)(out.v[k >> 2] >> (8 * (k & 3)));
+        }
+#pragma unroll
+        for (int p = 0; p < PX; p++) { u_prev[p] = u_cur[p]; u_cur[p] = u_next[p]; h_cur[p] = h_next[p]; }
     }
 }
 
@@ -902,6 +1080,10 @@ public:
             if (!rows3) return hbhip_each_frame(ins, outs, at, nf, [&](DevPicture *in, DevPicture *out) { return one_frame(in, out); });
             LapBatch3 B;
             int max_w = 0, max_h = 0;
+            // lapsharp3_wide_kernel: 8-bit samples, tables of lapsharp_rowdot.h's shape, every plane and pitch aligned for
+            // its vector loads and stores, and a luma row that fills a wave's span; lapsharp3_rows_kernel otherwise
+            bool wide = in_geo.bps == 1;
+            uintptr_t bits = 0;
             for (int c = 0; c < 3; c++)
             {
                 const LapKernel &k = LAP_TABLE[par.kernel[c]];
@@ -910,12 +1092,23 @@ public:
                 P.a = k.tap[0]; P.b = k.tap[1]; P.c = k.tap[4];
                 P.active = 1;
                 P.fast = in_geo.bps == 1 && mix_fast[c]; P.kinv = mix_k[c]; P.mixf = mix_f[c];
+                wide &= lrd_taps(P.a, P.b, P.c, P.taps) && P.src_pitch >= LW_PX;
+                P.ckf = (float)(P.c - P.kinv);
+                bits |= (uintptr_t)(P.src_pitch | P.dst_pitch);
                 max_w = std::max(max_w, P.width); max_h = std::max(max_h, P.height);
                 for (int f = 0; f < nf; f++)
                 {
                     B.src[f][c] = ins[at + f]->plane[c];
                     B.dst[f][c] = outs[at + f]->plane[c];
+                    bits |= (uintptr_t)B.src[f][c] | (uintptr_t)B.dst[f][c];
                 }
+            }
+            wide &= (bits & (4 * LW_DW - 1)) == 0 && max_w >= LW_WAVE_SPAN;
+            if (wide)
+            {
+                const dim3 grid(hbhip_grid_x((max_w + LW_SPAN - 1) / LW_SPAN), (max_h + LW_BY * LW_ROWS - 1) / (LW_BY * LW_ROWS), 3 * nf);
+                HBHIP_LAUNCH(ctx, "lapsharp_3x3", lapsharp3_wide_kernel, grid, dim3(64 * LW_WX, LW_BY), 0, B);
+                return HBHIP_OK;
             }
             // (hbhip_grid_x: never a multiple of 8 workgroups per row of strips - see hbhip_internal.h)
             const int rows = LS_BY * (in_geo.bps == 1 ? LS_ROWS : LS_ROWS16);
