@@ -429,7 +429,10 @@ __global__ __launch_bounds__(256) void bwdif_kernel(DecombArgs a, int field_end,
     if (field_end)
     {
         const int prefs = (y + df) < h ? st : -st, mrefs = y > (df - 1) ? -st : st;
-        const int prefs3 = (y + 3 * df) < h ? 3 * st : -st, mrefs3 = y > (3 * df - 1) ? -3 * st : st;
+        // on a plane of six rows or fewer at 16 bits (df = 2) these tests send the first row's tap to row -1 and the last
+        // row's to row h: vf_bwdif.c reads its frame padding there, nothing defined.  Row y + 3 / y - 3 is inside then.
+        const int prefs3 = (y + 3 * df) < h ? 3 * st : (y ? -st : 3 * st);
+        const int mrefs3 = y > (3 * df - 1) ? -3 * st : (y + 1 < h ? st : -3 * st);
         const T c1 = dw(cur + mrefs), e1 = dw(cur + prefs), c3 = dw(cur + mrefs3), e3 = dw(cur + prefs3);
 #pragma unroll
         for (int k = 0; k < 4; k++)

@@ -181,7 +181,12 @@ void orc_bwdif_plane(const void *prev, const void *cur, const void *next, int st
             else if (field_end)
             {
                 const int prefs = (y + df) < h ? st : -st, mrefs = y > (df - 1) ? -st : st;
-                const int prefs3 = (y + 3 * df) < h ? 3 * st : -st, mrefs3 = y > (3 * df - 1) ? -3 * st : st;
+                /* With df = 2 and h <= 6 (the chroma planes of a 16-bit frame of 12 rows or fewer) the two tests below send
+                 * the tap of row 0 to row -1 and the tap of row h - 1 to row h: vf_bwdif.c reads its frame padding there,
+                 * so nothing is defined.  Here such a tap takes the test's other branch, row y + 3 / y - 3, which is
+                 * inside the plane (h >= 4); every tap that vf_bwdif.c keeps inside the plane is unchanged. */
+                const int prefs3 = (y + 3 * df) < h ? 3 * st : (y ? -st : 3 * st);
+                const int mrefs3 = y > (3 * df - 1) ? -3 * st : (y + 1 < h ? st : -3 * st);
                 int interpol = (coef_sp[0] * (yd_px(cur, at + mrefs, bps) + yd_px(cur, at + prefs, bps)) -
                                 coef_sp[1] * (yd_px(cur, at + mrefs3, bps) + yd_px(cur, at + prefs3, bps))) >> 13;
                 out = interpol < 0 ? 0 : interpol > clip_max ? clip_max : interpol;
