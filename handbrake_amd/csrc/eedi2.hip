@@ -15,13 +15,14 @@
 //                      five passes, one LDS-tiled launch
 //   k_calc_dir_rows    eedi2_calc_directions                 :358-525   (the time sink; k_calc_dir_mark / work
 //                      is the fallback for search distances beyond the LDS halo)
-//   k_dir_map4 / k_dir_map_c   eedi2_filter_dir_map / expand_dir_map :649-773 and the _2x forms :872-1011
+//   k_dir_map_fe       eedi2_filter_dir_map + expand_dir_map :649-773 and the _2x pair :872-1011, a pair per launch;
+//                      <2, true> carries eedi2_post_process :1349-1378 as well (the eedi2_bit_blit before it, :46-68,
+//                      is saved by where the schedule keeps the map)
+//   k_dir_map4 / k_dir_map_c   the half-height pair as two launches (search distances beyond the LDS halo)
 //   k_filter_map       eedi2_filter_map                      :538-635
 //   k_mark_2x4         eedi2_upscale_by_2 (x3) :98-108 + eedi2_mark_directions_2x :787-858
 //   k_fill_gaps_b      eedi2_fill_gaps_2x                    :1025-1132
 //   k_lattice_cand_q / k_lattice_resolve   eedi2_interpolate_lattice   :1148-1335
-//   k_post             eedi2_post_process :1349-1378 (normally folded into the last expand_dir_map_2x; the
-//                      eedi2_bit_blit before it, :46-68, into the dir-map filter that follows it)
 //   eedi_blur1 / eedi_derivatives / eedi_blur_sqrt2 / eedi_post_corner (eedi2_corner.h, shared with the 16-bit engine)
 //                      post-processing 2/3: eedi2_gaussian_blur1 :1391-1527, eedi2_calc_derivatives :1760-1848,
 //                      eedi2_gaussian_blur_sqrt2 :1539-1748, eedi2_post_process_corner :1864-1904
@@ -67,8 +68,8 @@ struct P3
     uint8_t *a[3];       // pass specific roles, see each kernel
     uint8_t *b[3];
     uint8_t *c[3];
-    uint8_t *d[3];
-    uint8_t *e[3];
+    uint8_t *d[3];       // d - g: k_mark_2x4's line doublings; d and f: where k_dir_map_fe<2, true> leaves the filtered map
+    uint8_t *e[3];       // and corrects the picture
     uint8_t *f[3];
     uint8_t *g[3];
     int pitch[3], width[3], height[3];   // height = rows of the buffers this pass walks
@@ -89,9 +90,11 @@ struct P3
 struct PL { uint8_t *a, *b, *c, *d, *e, *f, *g; };
 __device__ __forceinline__ PL plane_ptrs(const P3 &P, int pl, size_t off)
 {
-    // only d is ever tested for "not bound" (the optional copy of the dir-map passes); the others are either bound or not
-    // looked at by the pass, so they move without the test (a compare and two selects on the scalar unit per pointer and
-    // wave - these passes run near the scalar issue rate, tools/salu_rate.hip)
+    // No kernel tests a pointer for "not bound": each is either bound or not looked at by the pass, so they move without
+    // such a test (a compare and two selects on the scalar unit per pointer and wave - these passes run near the scalar
+    // issue rate, tools/salu_rate.hip).  d still moves only where it is bound, from the time when the dir-map passes had an
+    // optional copy there: the kernels that use it (k_mark_2x4, k_dir_map_fe<2, true>) are compiled with that test, and
+    // taking it out changes their code - which wants a measurement of its own.
     PL q = { P.a[pl] + off, P.b[pl] + off, P.c[pl] + off, P.d[pl], P.e[pl] + off, P.f[pl] + off, P.g[pl] + off };
     if (q.d) q.d += off;
     return q;
@@ -199,13 +202,6 @@ __device__ __forceinline__ void st4(uint8_t *dst_at_x, const int (&out)[4], int 
     else
         for (int k = 0; k < 4 && x + k < limit; k++) dst_at_x[k] = (uint8_t)out[k];
 }
-
-#define XY4_PLANE(P)                                                        \
-    FIELD_PLANE(P);                                                         \
-    const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x);              \
-    const int y = blockIdx.y * blockDim.y + threadIdx.y;                    \
-    const int pitch = (P).pitch[pl], width = (P).width[pl], height = (P).height[pl]; \
-    (void)width; (void)height; (void)pitch
 
 // ------------------------------------------------------------------------------------------
 // The five mask passes in one launch: build_edge_mask -> erode -> dilate -> erode ->
@@ -1082,16 +1078,15 @@ __global__ __launch_bounds__(CD_W) CD_WAVES_ATTR void k_calc_dir_rows(P3 P, int 
     }
 }
 
-// filter_dir_map / expand_dir_map and their _2x forms.
-// a = edge mask, b = direction map in, c = out.  step = 1 (half height) or 2.
-// step 1: rows 1..height-2, neighbours y+-1, mask row y.
-// step 2: rows y0, y0+2, ... < height-1, neighbours y+-2 (guarded by y>1 / y<height-2), mask rows y-1 and y+1.
+// filter_dir_map / expand_dir_map as two launches (k_dir_map4, k_dir_map_c): the half-height pair for search distances
+// beyond what the tiled calc_directions takes.  Every other dir-map pair - the half-height one below that distance and the
+// _2x forms - is one launch of k_dir_map_fe, which shares the votes below.
+// a = edge mask, b = direction map in, c = out: rows 1..height-2, neighbours y+-1, mask row y.
 
 // Four pixels per thread.  One byte per thread makes these passes latency bound: a wave lives for two dependent memory
 // round trips whatever it computes, so the time is (#waves / resident waves) x that.  Here a thread owns one aligned dword of
-// its row: three 12-byte windows (rows y-step, y, y+step of the direction map) + one or two mask dwords, a quarter of
-// the waves and of the load instructions, one dword store.  In the _2x forms (step 2) every other row is only copied:
-// that is decided per row (a wave = one row), before anything but the row's own dword is loaded.
+// its row: three 12-byte windows (rows y-1, y, y+1 of the direction map) + one mask dword, a quarter of the waves and of
+// the load instructions, one dword store.
 __device__ __forceinline__ int dir_map_px(int u0, int u1, int u2, int c0, int c1, int c2, int n0, int n1, int n2,
                                           bool up_ok, bool dn_ok, int expand, const uint8_t *limlut)
 {
@@ -1153,88 +1148,45 @@ __device__ __forceinline__ uint32_t dir_map_quad(const Win12 &wu, const Win12 &w
     return ::dir_map_quad<PAIRS>(wu.w0, wu.w1, wu.w2, wc.w0, wc.w1, wc.w2, wd.w0, wd.w1, wd.w2);
 }
 
-// In the _2x forms a thread takes the rows 2r and 2r + 1 of its dword column: the one with the parity of the rebuilt rows
-// is worked on, the other only copied (a wave per copied row spent more on finding its plane and field - scalar
-// instructions - than on its dword).
-__global__ __launch_bounds__(256) void k_dir_map4(P3 P, int step)
+// k_dir_map4 is eedi2_filter_dir_map in that form.
+__global__ __launch_bounds__(256) void k_dir_map4(P3 P)
 {
     FIELD_PLANE(P);
     const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
-    const int r = blockIdx.y * blockDim.y + threadIdx.y;
+    const int y = blockIdx.y * blockDim.y + threadIdx.y;
     const int pitch = P.pitch[pl], width = P.width[pl], height = P.height[pl];
-    const int y0 = step == 1 ? 1 : 2 - tff;
-    const int y = step == 1 ? r : 2 * r + (y0 & 1);
-    if (x >= width) return;
+    if (x >= width || y >= height) return;
+    uint8_t *o = Q.c + (size_t)y * pitch + x;
     if (maskless)
     {
         // No mask pixel in the plane: the pass is its bit_blit (:656 / :729) - of a map that calc_directions filled with
         // peaks for want of a mask pixel (:371) and that every pass since has only copied: the output is peaks too, and a
-        // thread stores its dwords without loading anything (as copies the chroma planes of 16 fields were 66 MB and 14 us
-        // per full-height launch).
-        const int ya = step == 1 ? r : 2 * r, nrows = step == 1 ? 1 : 2;
+        // thread stores its dword without loading anything.
         const int out[4] = { PEAK, PEAK, PEAK, PEAK };
-        for (int i = 0; i < nrows && ya + i < height; i++)
-        {
-            const size_t at = (size_t)(ya + i) * pitch + x;
-            st4(Q.c + at, out, x, width);
-            if (Q.d) st4(Q.d + at, out, x, width);
-        }
-        return;
-    }
-    // the row of the pair that is never rebuilt (bit_blit only): fetched now, stored after the other row's work, so that
-    // its load is one of the thread's loads in flight and not a round trip of its own
-    const int yc = 2 * r + 1 - (y0 & 1);
-    const bool copy = step != 1 && yc < height;
-    uint32_t vcopy = 0;
-    if (copy) vcopy = *reinterpret_cast<const uint32_t *>(Q.b + (size_t)yc * pitch + x);
-    auto put_copy = [&]() {
-        if (!copy) return;
-        int out[4] = { (int)(vcopy & 0xff), (int)((vcopy >> 8) & 0xff), (int)((vcopy >> 16) & 0xff), (int)(vcopy >> 24) };
-        st4(Q.c + (size_t)yc * pitch + x, out, x, width);
-        if (Q.d) st4(Q.d + (size_t)yc * pitch + x, out, x, width);
-    };
-    if (y >= height) { put_copy(); return; }
-    const uint8_t *dc = Q.b + (size_t)y * pitch + x;
-    uint8_t *o = Q.c + (size_t)y * pitch + x;
-    const bool row_ok = step == 1 ? (y >= 1 && y < height - 1) : (y >= y0 && y < height - 1);
-    if (!row_ok)
-    {
-        // bit_blit only (and the optional copy of the input, the eedi2_bit_blit before post-processing)
-        const uint32_t v = *reinterpret_cast<const uint32_t *>(dc);
-        int out[4] = { (int)(v & 0xff), (int)((v >> 8) & 0xff), (int)((v >> 16) & 0xff), (int)(v >> 24) };
         st4(o, out, x, width);
-        if (Q.d) st4(Q.d + (size_t)y * pitch + x, out, x, width);
-        put_copy();
         return;
     }
+    const uint8_t *dc = Q.b + (size_t)y * pitch + x;
     // The row's own dword and the mask first: a thread without a pixel to work on (off the mask - whole planes of them
     // where the chroma has no edges: a third of a field's pixels) copies its dword and never fetches the 32 bytes around it.
     const uint32_t own = *reinterpret_cast<const uint32_t *>(dc);
-    const uint8_t *mk = Q.a + (size_t)y * pitch + x;
-    const uint32_t m0 = *reinterpret_cast<const uint32_t *>(step == 1 ? mk : mk - (ptrdiff_t)pitch);
-    const uint32_t m1 = step == 1 ? 0u : *reinterpret_cast<const uint32_t *>(mk + pitch);
-    const bool up_ok = step == 1 || y > 1, dn_ok = step == 1 || y < height - 2;
-    // the pixels the pass works on, one flag byte each (:658): inside the row, on the mask
-    const uint32_t work = ((ff_bytes(m0) | ff_bytes(m1)) >> 7) & bytes_in(x, 1, width - 1);
     uint32_t res = own;
-    if (work)
+    if (y >= 1 && y < height - 1)                                  // the first and the last row are the bit_blit only
     {
-        asm volatile("" ::: "memory");                         // a real branch: waves without such a pixel skip the loads and the votes
-        const Win12 wc = ldwin(dc), wu = ldwin(dc - (ptrdiff_t)step * pitch), wd = ldwin(dc + (ptrdiff_t)step * pitch);
-        const Win12 none = { 0xffffffffu, 0xffffffffu, 0xffffffffu };
-        const Win12 eu = up_ok ? wu : none, ed = dn_ok ? wd : none;
-        const uint32_t votes = dir_map_quad<3>(eu, wc, ed);
-        const uint32_t sel = (work << 8) - work;                     // 255 per flag byte
-        res = (res & ~sel) | (votes & sel);
+        const uint32_t m0 = *reinterpret_cast<const uint32_t *>(Q.a + (size_t)y * pitch + x);
+        // the pixels the pass works on, one flag byte each (:658): inside the row, on the mask
+        const uint32_t work = (ff_bytes(m0) >> 7) & bytes_in(x, 1, width - 1);
+        if (work)
+        {
+            asm volatile("" ::: "memory");                         // a real branch: waves without such a pixel skip the loads and the votes
+            const Win12 wc = ldwin(dc), wu = ldwin(dc - (ptrdiff_t)pitch), wd = ldwin(dc + (ptrdiff_t)pitch);
+            const uint32_t votes = dir_map_quad<3>(wu, wc, wd);
+            const uint32_t sel = (work << 8) - work;                     // 255 per flag byte
+            res = (res & ~sel) | (votes & sel);
+        }
     }
     int out[4] = { (int)(res & 0xff), (int)((res >> 8) & 0xff), (int)((res >> 16) & 0xff), (int)(res >> 24) };
     st4(o, out, x, width);
-    if (Q.d)
-    {
-        int in[4] = { (int)(own & 0xff), (int)((own >> 8) & 0xff), (int)((own >> 16) & 0xff), (int)(own >> 24) };
-        st4(Q.d + (size_t)y * pitch + x, in, x, width);
-    }
-    put_copy();
 }
 
 // k_dir_map4 in two phases.  Which pixels reach the sort is decided by byte arithmetic on whole dwords
@@ -1250,47 +1202,38 @@ __device__ __forceinline__ uint32_t live3(const Win12 &w, uint32_t &centre)   //
     return __builtin_amdgcn_alignbyte(n1, n0, 3) + n1 + __builtin_amdgcn_alignbyte(n2, n1, 1);
 }
 
-// post != 0 (the last expand_dir_map_2x of a field): eedi2_post_process (:1349-1378, k_post) rides along - it is
-// pointwise in the map this pass has just made (e = the map before the post filters, f = dst2p, rebuilt rows only).
+// k_dir_map_c is eedi2_expand_dir_map in that form: the pass only fills peak pixels and leaves the centre out of its count
+// of usable neighbours (:671), which needs five of them.
 // DC_R thread rows per thread: the pass is two phases around a queue with little arithmetic in the first, and a wave that
 // takes one dword row of it spends more scalar instructions on finding its plane, field and rows than vector ones on the
-// row (91 scalar instructions per wave with one row each; expand_dir_map_2x 73 -> 66 us per launch at two rows, 63 at four).
+// row (91 scalar instructions per wave with one row each; measured on the full-height form this kernel once had, per
+// launch: 73 us, 66 at two rows, 63 at four).
 #ifndef DC_THREAD_ROWS
 #define DC_THREAD_ROWS 4
 #endif
 constexpr int DC_R = DC_THREAD_ROWS, DC_ROWS = 4 * DC_R;
-__global__ __launch_bounds__(256) void k_dir_map_c(P3 P, int step, int expand, int post)
+__global__ __launch_bounds__(256) void k_dir_map_c(P3 P)
 {
     __shared__ __attribute__((aligned(16))) uint8_t s_out[DC_ROWS][256];
     __shared__ uint16_t s_list[DC_ROWS * 256];
     __shared__ int s_count;
     __shared__ uint8_t s_lim[LIM_PAD];
     FIELD_PLANE(P);
-    const int y0 = step == 1 ? 1 : 2 - tff;
-    // step 2: a thread row takes the PAIR of rows 2r, 2r + 1 - the one with the rebuilt rows' parity goes through the
-    // pass, the other is only copied (k_dir_map4)
-    const int rb = blockIdx.y * DC_ROWS;
+    const int rb = blockIdx.y * DC_ROWS;                                             // row of thread row 0
     const int bx0 = 4 * (blockIdx.x * 64), x = bx0 + 4 * threadIdx.x;
-    const int yb = step == 1 ? rb : 2 * rb + (y0 & 1);                              // row of thread row 0
     const int pitch = P.pitch[pl], width = P.width[pl], height = P.height[pl];
-    if (bx0 >= width || (step == 1 ? rb : 2 * rb) >= height) return;                 // whole workgroup outside
+    if (bx0 >= width || rb >= height) return;                                        // whole workgroup outside
     if (maskless)
     {
-        // no mask pixel in the plane: the pass is its bit_blit of a map of peaks (k_dir_map4), and the post-processing that
-        // may ride along finds every direction a peak and leaves the picture alone (:1364)
+        // no mask pixel in the plane: the pass is its bit_blit of a map of peaks (k_dir_map4)
         if (x < width)
         {
             const int out[4] = { PEAK, PEAK, PEAK, PEAK };
 #pragma unroll
             for (int h = 0; h < DC_R; h++)
             {
-                const int r = rb + (int)threadIdx.y + 4 * h, ya = step == 1 ? r : 2 * r, nrows = step == 1 ? 1 : 2;
-                for (int i = 0; i < nrows && ya + i < height; i++)
-                {
-                    const size_t at = (size_t)(ya + i) * pitch + x;
-                    st4(Q.c + at, out, x, width);
-                    if (Q.d) st4(Q.d + at, out, x, width);
-                }
+                const int y = rb + (int)threadIdx.y + 4 * h;
+                if (y < height) st4(Q.c + (size_t)y * pitch + x, out, x, width);
             }
         }
         return;
@@ -1300,87 +1243,59 @@ __global__ __launch_bounds__(256) void k_dir_map_c(P3 P, int step, int expand, i
     lim_fill(s_lim, tid);
     __syncthreads();
     // Three sweeps over the thread's DC_R rows, so that the loads of all of them are in flight together: as one loop (load the
-    // row's dword and masks, wait, load its windows, wait, count) a thread went through 2 DC_R memory round trips one after
+    // row's dword and mask, wait, load its windows, wait, count) a thread went through 2 DC_R memory round trips one after
     // the other, and the pass - mostly a copy - ran at half of what its bytes allow.
-    uint32_t vcopy[DC_R], own[DC_R], m0[DC_R], m1[DC_R], cand[DC_R];
+    uint32_t own[DC_R], m0[DC_R], cand[DC_R];
 #pragma unroll
     for (int h = 0; h < DC_R; h++)
     {
-        const int lr = (int)threadIdx.y + 4 * h, r = rb + lr, y = step == 1 ? r : 2 * r + (y0 & 1);
-        // the copied row of the pair: fetched now, stored when the workgroup is done (see k_dir_map4)
-        const int yc = 2 * r + 1 - (y0 & 1);
-        vcopy[h] = 0; own[h] = 0; m0[h] = 0; m1[h] = 0;
-        if (step != 1 && x < width && yc < height) vcopy[h] = *reinterpret_cast<const uint32_t *>(Q.b + (size_t)yc * pitch + x);
-        const bool inside = x < width && y < height;
-        const bool row_ok = step == 1 ? (y >= 1 && y < height - 1) : (y >= y0 && y < height - 1);
-        if (inside)
+        const int y = rb + (int)threadIdx.y + 4 * h;
+        own[h] = 0; m0[h] = 0;
+        if (x < width && y < height)
         {
             own[h] = *reinterpret_cast<const uint32_t *>(Q.b + (size_t)y * pitch + x);
-            if (row_ok)
-            {
-                const uint8_t *mk = Q.a + (size_t)y * pitch + x;
-                m0[h] = *reinterpret_cast<const uint32_t *>(step == 1 ? mk : mk - (ptrdiff_t)pitch);
-                if (step != 1) m1[h] = *reinterpret_cast<const uint32_t *>(mk + pitch);
-            }
+            if (y >= 1 && y < height - 1)                                               // the first and the last row are the bit_blit only
+                m0[h] = *reinterpret_cast<const uint32_t *>(Q.a + (size_t)y * pitch + x);
         }
     }
     Win12 wc[DC_R], wu[DC_R], wd[DC_R];
 #pragma unroll
     for (int h = 0; h < DC_R; h++)
     {
-        const int lr = (int)threadIdx.y + 4 * h, r = rb + lr, y = step == 1 ? r : 2 * r + (y0 & 1);
-        const bool inside = x < width && y < height;
-        const bool row_ok = step == 1 ? (y >= 1 && y < height - 1) : (y >= y0 && y < height - 1);
-        // the row's own dword and the mask first: without a candidate among its four pixels a thread copies its dword and
-        // fetches nothing else (k_dir_map4)
-        cand[h] = 0;
+        const int y = rb + (int)threadIdx.y + 4 * h;
+        // the row's own dword and the mask first: without a candidate among its four pixels - on the mask (m0 is 0 where the
+        // pass does not work), inside the row, a peak - a thread copies its dword and fetches nothing else (k_dir_map4)
+        cand[h] = (ff_bytes(m0[h]) >> 7) & bytes_in(x, 1, width - 1) & (ff_bytes(own[h]) >> 7);
         wc[h] = wu[h] = wd[h] = Win12{ 0u, 0u, 0u };
-        if (inside && row_ok)
+        if (cand[h])
         {
-            cand[h] = ((ff_bytes(m0[h]) | ff_bytes(m1[h])) >> 7) & bytes_in(x, 1, width - 1);
-            if (expand) cand[h] &= ff_bytes(own[h]) >> 7;                                  // expand only fills peak pixels
-            if (cand[h])
-            {
-                const uint8_t *dc = Q.b + (size_t)y * pitch + x;
-                wc[h] = ldwin(dc); wu[h] = ldwin(dc - (ptrdiff_t)step * pitch); wd[h] = ldwin(dc + (ptrdiff_t)step * pitch);
-            }
+            const uint8_t *dc = Q.b + (size_t)y * pitch + x;
+            wc[h] = ldwin(dc); wu[h] = ldwin(dc - (ptrdiff_t)pitch); wd[h] = ldwin(dc + (ptrdiff_t)pitch);
         }
     }
 #pragma unroll
     for (int h = 0; h < DC_R; h++)
     {
-        const int lr = (int)threadIdx.y + 4 * h, r = rb + lr, y = step == 1 ? r : 2 * r + (y0 & 1);
-        const bool inside = x < width && y < height;
-        if (inside)
+        const int lr = (int)threadIdx.y + 4 * h, y = rb + lr;
+        if (x < width && y < height)
         {
-            uint32_t out = own[h];
             if (cand[h])
             {
-                const bool up_ok = step == 1 || y > 1, dn_ok = step == 1 || y < height - 2;
                 uint32_t nc, nu, nd;
                 const uint32_t s3c = live3(wc[h], nc), s3u = live3(wu[h], nu), s3d = live3(wd[h], nd);
-                uint32_t u = expand ? s3c - nc : s3c;                                  // expand leaves the centre out (:671)
-                if (up_ok) u += s3u;
-                if (dn_ok) u += s3d;
-                const uint32_t enough = ((u + (uint32_t)(0x80 - (expand ? 5 : 4)) * 0x01010101u) >> 7) & 0x01010101u;
-                if (!expand) out |= (cand[h] & ~enough) * 255u;                        // too few neighbours: peak
+                const uint32_t u = s3c - nc + s3u + s3d;
+                const uint32_t enough = ((u + (uint32_t)(0x80 - 5) * 0x01010101u) >> 7) & 0x01010101u;
                 const uint32_t sortpx = cand[h] & enough;
                 if (sortpx)
                 {
-                    const int n = __popc(sortpx);
-                    int at = atomicAdd(&s_count, n);
+                    int at = atomicAdd(&s_count, __popc(sortpx));
 #pragma unroll
                     for (int k = 0; k < 4; k++)
                         if ((sortpx >> (8 * k)) & 1u) s_list[at++] = (uint16_t)((lr << 8) | (4 * threadIdx.x + k));
                 }
                 (void)nu; (void)nd;
             }
-            *reinterpret_cast<uint32_t *>(&s_out[lr][4 * threadIdx.x]) = out;
-            if (Q.d)                                                                    // optional copy of the input (the eedi2_bit_blit before post-processing)
-            {
-                int in[4] = { (int)(own[h] & 0xff), (int)((own[h] >> 8) & 0xff), (int)((own[h] >> 16) & 0xff), (int)(own[h] >> 24) };
-                st4(Q.d + (size_t)y * pitch + x, in, x, width);
-            }
+            *reinterpret_cast<uint32_t *>(&s_out[lr][4 * threadIdx.x]) = own[h];
         }
     }
     __syncthreads();
@@ -1388,51 +1303,21 @@ __global__ __launch_bounds__(256) void k_dir_map_c(P3 P, int step, int expand, i
     for (int i = tid; i < count; i += 256)
     {
         const int e = s_list[i], ly = e >> 8, lx = e & 255;
-        const int yy = yb + step * ly;
-        const uint8_t *c = Q.b + (size_t)yy * pitch + bx0 + lx;
-        const uint8_t *up = c - (ptrdiff_t)step * pitch, *dn = c + (ptrdiff_t)step * pitch;
-        const bool up_ok = step == 1 || yy > 1, dn_ok = step == 1 || yy < height - 2;
-        s_out[ly][lx] = (uint8_t)dir_map_px(up[-1], up[0], up[1], c[-1], c[0], c[1], dn[-1], dn[0], dn[1], up_ok, dn_ok, expand, s_lim);
+        const uint8_t *c = Q.b + (size_t)(rb + ly) * pitch + bx0 + lx;
+        const uint8_t *up = c - (ptrdiff_t)pitch, *dn = c + (ptrdiff_t)pitch;
+        s_out[ly][lx] = (uint8_t)dir_map_px(up[-1], up[0], up[1], c[-1], c[0], c[1], dn[-1], dn[0], dn[1], true, true, 1, s_lim);
     }
     __syncthreads();
 #pragma unroll
     for (int h = 0; h < DC_R; h++)
     {
-        const int lr = (int)threadIdx.y + 4 * h, r = rb + lr, y = step == 1 ? r : 2 * r + (y0 & 1);
-        const int yc = 2 * r + 1 - (y0 & 1);
-        const bool row_ok = step == 1 ? (y >= 1 && y < height - 1) : (y >= y0 && y < height - 1);
+        const int lr = (int)threadIdx.y + 4 * h, y = rb + lr;
         if (x < width && y < height)
         {
             const uint32_t v = *reinterpret_cast<const uint32_t *>(&s_out[lr][4 * threadIdx.x]);
             uint8_t *o = Q.c + (size_t)y * pitch + x;
             if (x + 3 < width) *reinterpret_cast<uint32_t *>(o) = v;
             else for (int k = 0; k < 4 && x + k < width; k++) o[k] = (uint8_t)(v >> (8 * k));
-            if (post && row_ok)
-            {
-                const size_t at = (size_t)y * pitch + x;
-                const uint32_t om4 = *reinterpret_cast<const uint32_t *>(Q.e + at);
-                uint8_t *d = Q.f + at;
-                const uint32_t up4 = *reinterpret_cast<const uint32_t *>(d - pitch), dn4 = *reinterpret_cast<const uint32_t *>(d + pitch);
-                const uint32_t cur4 = *reinterpret_cast<const uint32_t *>(d);
-                int out[4];
-                bool any = false;
-#pragma unroll
-                for (int k = 0; k < 4; k++)
-                {
-                    const int nm = (v >> (8 * k)) & 0xffu, om = (om4 >> (8 * k)) & 0xffu;
-                    const int lim = s_lim[iabs(nm - NEUTRAL) >> 2];
-                    const bool fix = iabs(nm - om) > lim && om != PEAK && om != NEUTRAL;
-                    out[k] = fix ? (int)((((up4 >> (8 * k)) & 0xffu) + ((dn4 >> (8 * k)) & 0xffu) + 1) >> 1) : (int)((cur4 >> (8 * k)) & 0xffu);
-                    any |= fix;
-                }
-                if (any) st4(d, out, x, width);
-            }
-        }
-        if (step != 1 && x < width && yc < height)
-        {
-            int in[4] = { (int)(vcopy[h] & 0xff), (int)((vcopy[h] >> 8) & 0xff), (int)((vcopy[h] >> 16) & 0xff), (int)(vcopy[h] >> 24) };
-            st4(Q.c + (size_t)yc * pitch + x, in, x, width);
-            if (Q.d) st4(Q.d + (size_t)yc * pitch + x, in, x, width);
         }
     }
 }
@@ -1481,7 +1366,7 @@ __device__ __forceinline__ void fe_expand_row(const uint32_t (*s_f)[FE_LW], int 
     *reinterpret_cast<uint32_t *>(&s_out[lr][4 * tx]) = own;
 }
 
-// POST (the pair in front of eedi2_post_process, :1349-1378, which rides along as in k_dir_map_c): d = where the filtered
+// POST (the pair in front of eedi2_post_process, :1349-1378, which rides along: it is pointwise in the map the pass has just made): d = where the filtered
 // map goes as well (the reference leaves it in dst2mp), f = the picture; the old map is the pass's own input, so the
 // eedi2_bit_blit that keeps a copy of it is not needed - the caller has the input in the plane the copy would go to.
 template <int STEP, bool POST>
@@ -2762,31 +2647,6 @@ __global__ __launch_bounds__(LR_T) void k_lattice_resolve(P3 P, const uint32_t *
     }
 }
 
-// a = nmsk, b = omsk, c = dst (in place, row y from rows y+-1), 4 pixels per thread
-__global__ void k_post(P3 P)
-{
-    XY4_PLANE(P);
-    const int y0 = 2 - tff;
-    if (x >= width || y >= height - 1 || y < y0 || ((y - y0) & 1)) return;
-    const size_t at = (size_t)y * pitch + x;
-    const uint32_t nm4 = *reinterpret_cast<const uint32_t *>(Q.a + at), om4 = *reinterpret_cast<const uint32_t *>(Q.b + at);
-    uint8_t *d = Q.c + at;
-    const uint32_t up4 = *reinterpret_cast<const uint32_t *>(d - pitch), dn4 = *reinterpret_cast<const uint32_t *>(d + pitch);
-    const uint32_t cur4 = *reinterpret_cast<const uint32_t *>(d);
-    int out[4];
-    bool any = false;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-    {
-        const int nm = (nm4 >> (8 * k)) & 0xffu, om = (om4 >> (8 * k)) & 0xffu;
-        const int lim = c_limlut[iabs(nm - NEUTRAL) >> 2];
-        const bool fix = iabs(nm - om) > lim && om != PEAK && om != NEUTRAL;
-        out[k] = fix ? (int)((((up4 >> (8 * k)) & 0xffu) + ((dn4 >> (8 * k)) & 0xffu) + 1) >> 1) : (int)((cur4 >> (8 * k)) & 0xffu);
-        any |= fix;
-    }
-    if (any) st4(d, out, x, width);
-}
-
 } // namespace
 
 // ---- MaskChainGuard (eedi2_engine.h): what happens when a wait of the mask chain runs out ------------------------
@@ -3220,22 +3080,8 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
     uint32_t *cand = reinterpret_cast<uint32_t *>(cand_raw_) + (size_t)s0 * (slot_bytes_ / sizeof(uint32_t));
     const dim3 blk(64, 4);
     const unsigned gz = 3u * (unsigned)n;
-    auto grid4_for = [&](const EediFrame &f, bool whole_pitch) {        // kernels with 4 pixels per thread
-        const int w = whole_pitch ? f.stride[0] : f.width[0];
-        return dim3(hbhip_grid_x((w + 255) / 256), (f.height[0] + 3) / 4, gz);
-    };
-    bool post_folded = false;
-    auto dir_map = [&](const char *name, const EediFrame &f, const P3 &Pv, int step, int expand, int post = 0) {
-        // the queueing form pays where few pixels reach the sort (expand: only peak pixels with >= 5 usable neighbours);
-        // filter_dir_map sorts at most masked pixels, there the in-place form is ahead
-        // step 2: a thread row per PAIR of rows (the rebuilt one and the copied one)
-        const int trows = step == 1 ? f.height[0] : (f.height[0] + 1) / 2;             // thread rows
-        if (!expand) HBHIP_LAUNCH_ON(lc, st, name, k_dir_map4, dim3(hbhip_grid_x((f.width[0] + 255) / 256), (trows + 3) / 4, gz), blk, 0, Pv, step);
-        else
-        {
-            HBHIP_LAUNCH_ON(lc, st, name, k_dir_map_c, dim3(hbhip_grid_x((f.width[0] + 255) / 256), (trows + DC_ROWS - 1) / DC_ROWS, gz), blk, 0, Pv, step, expand, post);
-            post_folded = post != 0;
-        }
+    auto grid4_for = [&](const EediFrame &f, int rows) {               // kernels with 4 pixels per thread, `rows` rows per block
+        return dim3(hbhip_grid_x((f.width[0] + 255) / 256), (f.height[0] + rows - 1) / rows, gz);
     };
     auto geom = [&](P3 &P, const EediFrame &f) {
         for (int c = 0; c < 3; c++) { P.pitch[c] = f.stride[c]; P.width[c] = f.width[c]; P.height[c] = f.height[c]; }
@@ -3255,11 +3101,11 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
     // pass leaves the expanded map in tmpp, where the reference has it
     // (the padding of the rows with it: calc_directions' memset leaves 255 there, which the fused pass writes into tmpp,
     // while dstp keeps the zeros the passes of the reference never touch)
-    const bool fused = par_.maximum_search_distance <= CD_HALO - 2 && hbhip_dev_int("HBHIP_EEDI2_FUSE_DIRMAP", 1) != 0;
+    const bool fused = par_.maximum_search_distance <= CD_HALO - 2;
     const uint32_t padv = fused ? 0u : 0xffffffffu;
     bind(P.a, mskp); bind(P.b, srcp); bind(P.c, fused ? dstp : tmpp);
     const int nt13 = (par_.noise_threshold * 13) & 0xff, nt19 = (par_.noise_threshold * 19) & 0xff;      // typed `pixel` in the reference
-    if (par_.maximum_search_distance <= CD_HALO - 2)
+    if (fused)
     {
         // 256 columns x 4 rows per block: blocks with at least half of their pixels listed search in the dense form
         // (calc_dir_dense), the others walk their list.  Measured on the decomb bob workload, us per 16 fields: the list form
@@ -3321,46 +3167,35 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
     }
     else
     {
+        // the queueing form pays where few pixels reach the sort (expand: only peak pixels with >= 5 usable neighbours);
+        // filter_dir_map sorts at most masked pixels, there the in-place form is ahead
         bind(P.a, mskp); bind(P.b, tmpp); bind(P.c, dstp);
-        dir_map("eedi2_filter_dir_map", srcp, P, 1, 0);
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_filter_dir_map", k_dir_map4, grid4_for(srcp, 4), blk, 0, P);
         bind(P.a, mskp); bind(P.b, dstp); bind(P.c, tmpp);
-        dir_map("eedi2_expand_dir_map", srcp, P, 1, 1);
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_expand_dir_map", k_dir_map_c, grid4_for(srcp, DC_ROWS), blk, 0, P);
     }
     bind(P.a, mskp); bind(P.b, tmpp); bind(P.c, dstp);
-    HBHIP_LAUNCH_ON(lc, st, "eedi2_filter_map", k_filter_map, grid4_for(srcp, false), blk, 0, P);
+    HBHIP_LAUNCH_ON(lc, st, "eedi2_filter_map", k_filter_map, grid4_for(srcp, 4), blk, 0, P);
     // line doubling of srcp / dstp / mskp + mark_directions_2x in one launch (full-height geometry)
     geom(P, dst2p);
     bind(P.g, srcp); bind(P.b, dstp); bind(P.a, mskp);
-    // the pair of _2x dir-map passes behind it as one launch too (k_dir_map_fe<2>): the marked map then goes to dst2mp
-    const bool fused2 = hbhip_dev_int("HBHIP_EEDI2_FUSE_DIRMAP_2X", 1) != 0;
-    // ... and the pair in front of post_process (k_dir_map_fe<2, true>).  That pass reads the map the lattice leaves and the
+    // the pair of _2x dir-map passes behind it is one launch too (k_dir_map_fe<2>): the marked map goes to dst2mp
+    // ... and so is the pair in front of post_process (k_dir_map_fe<2, true>).  That pass reads the map the lattice leaves and the
     // reference has it write the new map over it, with the eedi2_bit_blit in front keeping a copy in tmp2p2
-    // (decomb_template.c:426-429); one launch cannot read a plane's neighbourhoods and write that plane.  So the two planes
-    // change places from mark_directions_2x on: the direction map lives in tmp2p2 - where the copy would go: no blit - and the
-    // doubled half-height map (the lattice's omsk, dead behind it) in tmp2p, which the fused pass then overwrites with the new
-    // map.  Every plane ends as the reference leaves it, the padding of its rows included.
+    // (decomb_template.c:426-429); one launch cannot read a plane's neighbourhoods and write that plane.  So with that pair
+    // to come the two planes change places from mark_directions_2x on: the direction map lives in tmp2p2 - where the copy
+    // would go: no blit - and the doubled half-height map (the lattice's omsk, dead behind it) in tmp2p, which the fused pass
+    // then overwrites with the new map.  Every plane ends as the reference leaves it, the padding of its rows included.
     const bool post1 = par_.post_processing == 1 || par_.post_processing == 3;
-    const bool swapped = fused2 && post1 && hbhip_dev_int("HBHIP_EEDI2_FUSE_DIRMAP_POST", 1) != 0;
-    const EediFrame &map2 = swapped ? tmp2p2 : tmp2p, &omsk2 = swapped ? tmp2p : tmp2p2;
-    bind(P.d, dst2p); bind(P.e, omsk2); bind(P.f, msk2p); bind(P.c, fused2 ? dst2mp : map2);
+    const EediFrame &map2 = post1 ? tmp2p2 : tmp2p, &omsk2 = post1 ? tmp2p : tmp2p2;
+    bind(P.d, dst2p); bind(P.e, omsk2); bind(P.f, msk2p); bind(P.c, dst2mp);
     HBHIP_LAUNCH_ON(lc, st, "eedi2_mark_directions_2x", k_mark_2x4,                                      // a thread row per PAIR of full-height rows
-                 dim3(hbhip_grid_x((dst2p.stride[0] + 255) / 256), ((dst2p.height[0] + 1) / 2 + 3) / 4, gz), blk, 0, P, fused2 ? 0u : 0xffffffffu);
-    for (int c = 0; c < 3; c++) P.d[c] = P.e[c] = P.f[c] = P.g[c] = nullptr;    // slot d doubles as the dir-map kernels' optional copy target
+                 dim3(hbhip_grid_x((dst2p.stride[0] + 255) / 256), ((dst2p.height[0] + 1) / 2 + 3) / 4, gz), blk, 0, P, 0u);
     const dim3 fe2_grid(hbhip_grid_x((dst2p.stride[0] + 255) / 256), ((dst2p.height[0] + 1) / 2 + FE_R - 1) / FE_R, gz);
-    if (fused2)
-    {
-        bind(P.a, msk2p); bind(P.b, dst2mp); bind(P.c, map2);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_filter_expand_dir_map_2x", (k_dir_map_fe<2, false>), fe2_grid, blk, 0, P, swapped ? 0u : 0xffffffffu);
-    }
-    else
-    {
-        bind(P.a, msk2p); bind(P.b, tmp2p); bind(P.c, dst2mp);
-        dir_map("eedi2_filter_dir_map_2x", dst2p, P, 2, 0);
-        bind(P.a, msk2p); bind(P.b, dst2mp); bind(P.c, tmp2p);
-        dir_map("eedi2_expand_dir_map_2x", dst2p, P, 2, 1);
-    }
-    // (a workgroup per row here: with the copied row of a pair folded into the workgroup of the rebuilt one, as in the dir-map
-    // passes, this kernel went from 131 to 163-165 us per launch)
+    bind(P.a, msk2p); bind(P.b, dst2mp); bind(P.c, map2);
+    HBHIP_LAUNCH_ON(lc, st, "eedi2_filter_expand_dir_map_2x", (k_dir_map_fe<2, false>), fe2_grid, blk, 0, P, post1 ? 0u : 0xffffffffu);
+    // (a workgroup per row here: with the copied row of a pair folded into the workgroup of the rebuilt one, this kernel went
+    // from 131 to 163-165 us per launch)
     const dim3 fg_grid(hbhip_grid_x((dst2p.width[0] + FG_W - 1) / FG_W), (dst2p.height[0] + 2 * FG_R - 1) / (2 * FG_R), gz);
     bind(P.a, msk2p); bind(P.b, map2); bind(P.c, dst2mp);
     HBHIP_LAUNCH_ON(lc, st, "eedi2_fill_gaps_2x", k_fill_gaps_b, fg_grid, dim3(FG_T), 0, P);
@@ -3376,27 +3211,12 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
         HBHIP_LAUNCH_ON(lc, st, "eedi2_lattice_resolve", k_lattice_resolve, dim3(1, (nrows + 1 + LR_ROWS - 1) / LR_ROWS, gz), dim3(LR_T), 0, P,
                      (const uint32_t *)cand, cand_pitch_, cand_plane_stride_);
     }
-    if (swapped)
+    if (post1)
     {
         // filter_dir_map_2x, expand_dir_map_2x and post_process in one launch: tmp2p2 (the map, and what the reference's copy of
         // it would hold) -> tmp2p, the filtered map to dst2mp, the corrections to dst2p
         bind(P.a, msk2p); bind(P.b, tmp2p2); bind(P.c, tmp2p); bind(P.d, dst2mp); bind(P.f, dst2p);
         HBHIP_LAUNCH_ON(lc, st, "eedi2_filter_expand_dir_map_2x_post", (k_dir_map_fe<2, true>), fe2_grid, blk, 0, P, 0xffffffffu);
-        for (int c = 0; c < 3; c++) P.d[c] = P.f[c] = nullptr;
-    }
-    else if (post1)
-    {
-        // eedi2_bit_blit(tmp2p -> tmp2p2) keeps the pre-filter direction map for post_process
-        // (decomb_template.c:426); the filter that follows reads every byte of tmp2p the blit copies,
-        // so it writes that copy itself (slot d) and the separate launch is saved
-        bind(P.a, msk2p); bind(P.b, tmp2p); bind(P.c, dst2mp); bind(P.d, tmp2p2);
-        dir_map("eedi2_filter_dir_map_2x", dst2p, P, 2, 0);
-        for (int c = 0; c < 3; c++) P.d[c] = nullptr;
-        bind(P.a, msk2p); bind(P.b, dst2mp); bind(P.c, tmp2p); bind(P.e, tmp2p2); bind(P.f, dst2p);
-        dir_map("eedi2_expand_dir_map_2x", dst2p, P, 2, 1, 1);                          // + post_process where the kernel can carry it
-        for (int c = 0; c < 3; c++) P.e[c] = P.f[c] = nullptr;
-        bind(P.a, tmp2p); bind(P.b, tmp2p2); bind(P.c, dst2p);
-        if (!post_folded) HBHIP_LAUNCH_ON(lc, st, "eedi2_post_process", k_post, grid4_for(dst2p, false), blk, 0, P);
     }
     if (par_.post_processing == 2 || par_.post_processing == 3)
     {

@@ -29,7 +29,8 @@ struct K16
 struct Q3
 {
     uint16_t *a[3], *b[3], *c[3];          // pass specific roles, see each kernel
-    uint16_t *d[3], *e[3], *f[3], *g[3];   // q_mark_2x's line doublings (picked by that kernel itself)
+    uint16_t *d[3], *e[3], *f[3], *g[3];   // q_mark_2x's line doublings; d and f: where q_dir_map_fe<2, true> leaves the filtered
+                                           // map and corrects the picture (picked by those kernels themselves)
     int pitch[3], width[3], height[3];
     size_t   fstride;                      // field batching (see eedi2.hip): samples between the slots of consecutive fields
     uint32_t tffbits;                      // bit f: pv->tff of field f of the launch
@@ -752,9 +753,8 @@ __global__ __launch_bounds__(QW) void q_calc_dir_rows(Q3 P, K16 k, int maxd, int
     }
 }
 
-// filter_dir_map (:649-709) / expand_dir_map (:722-773) and, with step 2, the _2x forms (:872-1011).
-// a = mask, b = direction map in, c = out.  step 1: rows 1..height-2 looking at rows y+-1 and mask row y;
-// step 2: rows y0, y0+2, ... looking at rows y+-2 and mask rows y-1 / y+1.
+// filter_dir_map (:649-709) / expand_dir_map (:722-773) and the _2x forms (:872-1011): what their kernels share
+// (q_dir_map_fe, a pair per launch at half and at full height; q_dir_map4 / q_dir_map, the half-height pair as two).
 // (the candidates sit in nine fixed slots - an absent one holds ABSENT16, larger than any sample and farther from any
 // midpoint than any vote limit - and a sorting network orders them: no data-dependent loop, no indexed array; the
 // midpoint and the vote are sorted_mid's / vote16's, as in the 8-bit k_dir_map)
@@ -902,21 +902,24 @@ __device__ __forceinline__ uint32_t dir_map_pair16(const Win16 &wu, const Win16 
     return out;
 }
 
-// a = mask, b = direction map in, c = out.  Four samples per thread; in the _2x form a thread takes the rows 2r and 2r + 1 -
-// the one with the rebuilt rows' parity is worked on, the other copied (eedi2.hip: k_dir_map4)
-__global__ __launch_bounds__(256) void q_dir_map4(Q3 P, K16 k, int step, int expand)
+// filter_dir_map and expand_dir_map as two launches: the half-height pair for search distances beyond what the tiled
+// calc_directions takes (every other dir-map pair is one launch of q_dir_map_fe).  a = mask, b = direction map in, c = out:
+// rows 1 .. height - 2, neighbours y -+ 1, mask row y.
+// `expand` (0 = filter_dir_map, 1 = expand_dir_map) stays an argument of both kernels although q_dir_map4 is only launched
+// for the one and q_dir_map for the other: as a constant at every call of dir_map_pair16 / dir_map_px16 it is folded into
+// those helpers before they are inlined, and the code of q_dir_map_fe, which shares them, comes out in another order.
+// q_dir_map4: four samples per thread, the vote in registers (eedi2.hip: k_dir_map4)
+__global__ __launch_bounds__(256) void q_dir_map4(Q3 P, K16 k, int expand)
 {
     FIELD16(P);
     const int x = 4 * (blockIdx.x * blockDim.x + threadIdx.x);
-    const int r = blockIdx.y * blockDim.y + threadIdx.y;
+    const int y = blockIdx.y * blockDim.y + threadIdx.y;
     const int pitch = P.pitch[pl], width = P.width[pl], height = P.height[pl];
-    const int y0 = step == 1 ? 1 : 2 - tff;
-    const int y = step == 1 ? r : 2 * r + (y0 & 1);
-    if (x >= width) return;
+    if (x >= width || y >= height) return;
     const int peak = k.peak;
     const uint32_t peak2 = (uint32_t)peak * 0x00010001u;
-    auto put = [&](int yy, uint2 v) {
-        uint16_t *o = Q.c + (size_t)yy * pitch + x;
+    auto put = [&](uint2 v) {
+        uint16_t *o = Q.c + (size_t)y * pitch + x;
         if (x + 3 < width) *reinterpret_cast<uint2 *>(o) = v;
         else
         {
@@ -924,41 +927,21 @@ __global__ __launch_bounds__(256) void q_dir_map4(Q3 P, K16 k, int step, int exp
             for (int j = 0; j < 4 && x + j < width; j++) o[j] = o4[j];
         }
     };
-    if (maskless)
-    {
-        const int ya = step == 1 ? r : 2 * r, nrows = step == 1 ? 1 : 2;
-        for (int i = 0; i < nrows && ya + i < height; i++) put(ya + i, make_uint2(peak2, peak2));
-        return;
-    }
-    const int yc = 2 * r + 1 - (y0 & 1);
-    const bool copy = step != 1 && yc < height;
-    uint2 vcopy = make_uint2(0u, 0u);
-    if (copy) vcopy = *reinterpret_cast<const uint2 *>(Q.b + (size_t)yc * pitch + x);
-    if (y >= height) { if (copy) put(yc, vcopy); return; }
+    // no mask sample in the plane: the pass is its bit_blit of a map of peaks (eedi2.hip: k_dir_map4)
+    if (maskless) { put(make_uint2(peak2, peak2)); return; }
     const uint16_t *dc = Q.b + (size_t)y * pitch + x;
-    const bool row_ok = step == 1 ? (y >= 1 && y < height - 1) : (y >= y0 && y < height - 1);
     const uint2 own = *reinterpret_cast<const uint2 *>(dc);
-    if (!row_ok)
-    {
-        put(y, own);
-        if (copy) put(yc, vcopy);
-        return;
-    }
-    const uint16_t *mk = Q.a + (size_t)y * pitch + x;
-    const uint2 m0 = *reinterpret_cast<const uint2 *>(step == 1 ? mk : mk - (ptrdiff_t)pitch);
-    const uint2 m1 = step == 1 ? make_uint2(0u, 0u) : *reinterpret_cast<const uint2 *>(mk + pitch);
-    const bool up_ok = step == 1 || y > 1, dn_ok = step == 1 || y < height - 2;
+    if (y < 1 || y >= height - 1) { put(own); return; }          // the first and the last row are the bit_blit only
+    const uint2 m0 = *reinterpret_cast<const uint2 *>(Q.a + (size_t)y * pitch + x);
     // the samples the pass works on (:658 / :738): inside the row, on the mask, and for expand a peak
     const int mm0[4] = { (int)(m0.x & 0xffffu), (int)(m0.x >> 16), (int)(m0.y & 0xffffu), (int)(m0.y >> 16) };
-    const int mm1[4] = { (int)(m1.x & 0xffffu), (int)(m1.x >> 16), (int)(m1.y & 0xffffu), (int)(m1.y >> 16) };
     const int oo[4] = { (int)(own.x & 0xffffu), (int)(own.x >> 16), (int)(own.y & 0xffffu), (int)(own.y >> 16) };
     uint32_t work = 0;
 #pragma unroll
     for (int j = 0; j < 4; j++)
     {
         const int xx = x + j;
-        const bool masked = mm0[j] == peak || (step != 1 && mm1[j] == peak);
-        if (xx >= 1 && xx < width - 1 && masked && !(expand && oo[j] != peak)) work |= 1u << j;
+        if (xx >= 1 && xx < width - 1 && mm0[j] == peak && !(expand && oo[j] != peak)) work |= 1u << j;
     }
     uint2 res = own;
     if (work)
@@ -970,9 +953,7 @@ __global__ __launch_bounds__(256) void q_dir_map4(Q3 P, K16 k, int step, int exp
             const uint32_t rr = x + 4 < pitch ? *reinterpret_cast<const uint32_t *>(row + 4) : 0u;
             return Win16{ l, c4.x, c4.y, rr };
         };
-        const Win16 none = { peak2, peak2, peak2, peak2 };
-        const Win16 wc = ldwin(dc);
-        const Win16 wu = up_ok ? ldwin(dc - (ptrdiff_t)step * pitch) : none, wd = dn_ok ? ldwin(dc + (ptrdiff_t)step * pitch) : none;
+        const Win16 wc = ldwin(dc), wu = ldwin(dc - (ptrdiff_t)pitch), wd = ldwin(dc + (ptrdiff_t)pitch);
         const uint32_t p01 = dir_map_pair16<0>(wu, wc, wd, expand, peak, k.neutral, k.shift);
         const uint32_t p23 = dir_map_pair16<2>(wu, wc, wd, expand, peak, k.neutral, k.shift);
         const uint32_t s01 = ((work & 1u) ? 0x0000ffffu : 0u) | ((work & 2u) ? 0xffff0000u : 0u);
@@ -980,42 +961,30 @@ __global__ __launch_bounds__(256) void q_dir_map4(Q3 P, K16 k, int step, int exp
         res.x = (res.x & ~s01) | (p01 & s01);
         res.y = (res.y & ~s23) | (p23 & s23);
     }
-    put(y, res);
-    if (copy) put(yc, vcopy);
+    put(res);
 }
 
-// Two phases, as for 8-bit samples (eedi2.hip: k_dir_map_c).  Phase 1, four samples per thread: which samples reach the
+// q_dir_map: two phases, as for 8-bit samples (eedi2.hip: k_dir_map_c).  Phase 1, four samples per thread: which samples reach the
 // sort at all (inside the mask, enough usable directions around them) - on real pictures a small minority, spread so
 // that nearly every wave holds a few, and a wave pays for the sort if one lane needs it.  They are queued (an LDS list
-// per workgroup of 4 rows x 256 samples) and phase 2 gives each queued sample a lane of its own.  a = edge mask,
-// b = direction map in, c = out; step 1 (half height) or 2.
-// post != 0 (the last expand_dir_map_2x of a field): eedi2_post_process (:1349-1378, q_post) rides along, as in the
-// 8-bit engine - it is pointwise in the map this pass has just made (e = the map before the post filters, f = dst2p,
-// rebuilt rows only; the rows it averages are of the other parity, which no thread of the pass writes).
-__global__ __launch_bounds__(256) void q_dir_map(Q3 P, K16 k, int step, int expand, int post)
+// per workgroup of 4 rows x 256 samples) and phase 2 gives each queued sample a lane of its own.
+__global__ __launch_bounds__(256) void q_dir_map(Q3 P, K16 k, int expand)
 {
     __shared__ __attribute__((aligned(16))) uint16_t s_out[4][256];
     __shared__ uint16_t s_list[4 * 256];
     __shared__ int s_count;
     __shared__ int s_lim[33];
     FIELD16(P);
-    const int y0 = step == 1 ? 1 : 2 - tff;
-    // step 2: a thread row takes the PAIR of rows 2r, 2r + 1 - the one with the rebuilt rows' parity goes through the pass,
-    // the other is only copied: fetched now, stored when the workgroup is done (eedi2.hip: k_dir_map_c)
-    const int rb = blockIdx.y * 4, r = rb + threadIdx.y;
-    const int bx0 = 4 * (blockIdx.x * 64), x = bx0 + 4 * threadIdx.x, y = step == 1 ? r : 2 * r + (y0 & 1);
-    const int yb = step == 1 ? rb : 2 * rb + (y0 & 1);                              // row of thread row 0
+    const int rb = blockIdx.y * 4, y = rb + threadIdx.y;                             // rb: row of thread row 0
+    const int bx0 = 4 * (blockIdx.x * 64), x = bx0 + 4 * threadIdx.x;
     const int pitch = P.pitch[pl], width = P.width[pl], height = P.height[pl];
-    if (bx0 >= width || (step == 1 ? rb : 2 * rb) >= height) return;                 // whole workgroup outside
+    if (bx0 >= width || rb >= height) return;                                        // whole workgroup outside
+    const bool inside = x < width && y < height;
     if (maskless)
     {
         // no mask sample in the plane: the pass is its bit_blit of a map of peaks (eedi2.hip: k_dir_map4)
-        if (x < width)
-        {
-            const int ya = step == 1 ? r : 2 * r, nrows = step == 1 ? 1 : 2;
-            for (int i = 0; i < nrows && ya + i < height; i++)
-                for (int j = 0; j < 4 && x + j < width; j++) Q.c[(size_t)(ya + i) * pitch + x + j] = (uint16_t)k.peak;
-        }
+        if (inside)
+            for (int j = 0; j < 4 && x + j < width; j++) Q.c[(size_t)y * pitch + x + j] = (uint16_t)k.peak;
         return;
     }
     const int tid = threadIdx.y * 64 + threadIdx.x;
@@ -1023,19 +992,12 @@ __global__ __launch_bounds__(256) void q_dir_map(Q3 P, K16 k, int step, int expa
     if (tid < 33) s_lim[tid] = k.limlut[tid];
     __syncthreads();
     const int peak = k.peak;
-    const int yc = 2 * r + 1 - (y0 & 1);
-    const bool copy = step != 1 && x < width && yc < height;
-    uint2 vcopy = make_uint2(0u, 0u);
-    if (copy) vcopy = *reinterpret_cast<const uint2 *>(Q.b + (size_t)yc * pitch + x);
-    const bool inside = x < width && y < height;
-    const bool row_ok = step == 1 ? (y >= 1 && y < height - 1) : (y >= y0 && y < height - 1);
     const uint16_t *dc = Q.b + (size_t)y * pitch + x;
     if (inside)
     {
         uint2 out = *reinterpret_cast<const uint2 *>(dc);
-        if (row_ok)
+        if (y >= 1 && y < height - 1)                                                   // the first and the last row are the bit_blit only
         {
-            const bool up_ok = step == 1 || y > 1, dn_ok = step == 1 || y < height - 2;
             // six samples x-1 .. x+4 of the three rows: usable (non-peak) flags, bit j = sample x-1+j
             auto usable6 = [&](const uint16_t *row) -> uint32_t {
                 const uint2 v = *reinterpret_cast<const uint2 *>(row);
@@ -1043,23 +1005,17 @@ __global__ __launch_bounds__(256) void q_dir_map(Q3 P, K16 k, int step, int expa
                 return (l != peak ? 1u : 0u) | ((int)(v.x & 0xffffu) != peak ? 2u : 0u) | ((int)(v.x >> 16) != peak ? 4u : 0u) |
                        ((int)(v.y & 0xffffu) != peak ? 8u : 0u) | ((int)(v.y >> 16) != peak ? 16u : 0u) | (r != peak ? 32u : 0u);
             };
-            const uint32_t fc = usable6(dc);
-            const uint32_t fu = up_ok ? usable6(dc - (ptrdiff_t)step * pitch) : 0u;
-            const uint32_t fd = dn_ok ? usable6(dc + (ptrdiff_t)step * pitch) : 0u;
-            const uint16_t *mk = Q.a + (size_t)y * pitch + x;
-            const uint2 m0 = *reinterpret_cast<const uint2 *>(step == 1 ? mk : mk - (ptrdiff_t)pitch);
-            const uint2 m1 = step == 1 ? make_uint2(0u, 0u) : *reinterpret_cast<const uint2 *>(mk + pitch);
+            const uint32_t fc = usable6(dc), fu = usable6(dc - (ptrdiff_t)pitch), fd = usable6(dc + (ptrdiff_t)pitch);
+            const uint2 m0 = *reinterpret_cast<const uint2 *>(Q.a + (size_t)y * pitch + x);
             const int mm0[4] = { (int)(m0.x & 0xffffu), (int)(m0.x >> 16), (int)(m0.y & 0xffffu), (int)(m0.y >> 16) };
-            const int mm1[4] = { (int)(m1.x & 0xffffu), (int)(m1.x >> 16), (int)(m1.y & 0xffffu), (int)(m1.y >> 16) };
             uint32_t o4[4] = { out.x & 0xffffu, out.x >> 16, out.y & 0xffffu, out.y >> 16 };
             uint32_t sortpx = 0;
 #pragma unroll
             for (int j = 0; j < 4; j++)
             {
                 const int xx = x + j;
-                const bool masked = mm0[j] == peak || (step != 1 && mm1[j] == peak);
                 const bool centre_usable = (fc >> (j + 1)) & 1u;
-                const bool cand = xx >= 1 && xx < width - 1 && masked && !(expand && centre_usable);
+                const bool cand = xx >= 1 && xx < width - 1 && mm0[j] == peak && !(expand && centre_usable);
                 // usable values among the 3 x 3 (expand leaves the centre out, :671)
                 const int u = __popc((fu >> j) & 7u) + __popc((fd >> j) & 7u) + __popc((fc >> j) & (expand ? 5u : 7u));
                 const bool enough = u >= (expand ? 5 : 4);
@@ -1082,11 +1038,9 @@ __global__ __launch_bounds__(256) void q_dir_map(Q3 P, K16 k, int step, int expa
     for (int i = tid; i < count; i += 256)
     {
         const int e = s_list[i], ly = e >> 8, lx = e & 255;
-        const int yy = yb + step * ly;
-        const uint16_t *c = Q.b + (size_t)yy * pitch + bx0 + lx;
-        const bool up_ok = step == 1 || yy > 1, dn_ok = step == 1 || yy < height - 2;
-        const uint16_t *up = up_ok ? c - (ptrdiff_t)step * pitch : c, *dn = dn_ok ? c + (ptrdiff_t)step * pitch : c;
-        s_out[ly][lx] = (uint16_t)dir_map_px16(up[-1], up[0], up[1], c[-1], c[0], c[1], dn[-1], dn[0], dn[1], up_ok, dn_ok, expand,
+        const uint16_t *c = Q.b + (size_t)(rb + ly) * pitch + bx0 + lx;
+        const uint16_t *up = c - (ptrdiff_t)pitch, *dn = c + (ptrdiff_t)pitch;
+        s_out[ly][lx] = (uint16_t)dir_map_px16(up[-1], up[0], up[1], c[-1], c[0], c[1], dn[-1], dn[0], dn[1], true, true, expand,
                                                peak, k.neutral, 2 + k.shift, s_lim);
     }
     __syncthreads();
@@ -1098,41 +1052,6 @@ __global__ __launch_bounds__(256) void q_dir_map(Q3 P, K16 k, int step, int expa
         else
         {
             const uint16_t o4[4] = { (uint16_t)(v.x & 0xffffu), (uint16_t)(v.x >> 16), (uint16_t)(v.y & 0xffffu), (uint16_t)(v.y >> 16) };
-            for (int j = 0; j < 4 && x + j < width; j++) o[j] = o4[j];
-        }
-        if (post && row_ok)
-        {
-            const size_t at = (size_t)fld * P.fstride + (size_t)y * pitch + x;
-            const uint2 om4 = *reinterpret_cast<const uint2 *>(P.e[pl] + at);
-            uint16_t *d = P.f[pl] + at;
-            const uint2 up4 = *reinterpret_cast<const uint2 *>(d - pitch), dn4 = *reinterpret_cast<const uint2 *>(d + pitch);
-            const uint2 cur4 = *reinterpret_cast<const uint2 *>(d);
-            auto s4 = [](const uint2 &w, int j) -> int { return (int)(((j < 2 ? w.x : w.y) >> (16 * (j & 1))) & 0xffffu); };
-            uint32_t out[4];
-            bool any = false;
-#pragma unroll
-            for (int j = 0; j < 4; j++)
-            {
-                const int nm = s4(v, j), om = s4(om4, j);
-                const int lim = s_lim[iabs(nm - k.neutral) >> (2 + k.shift)];
-                const bool fix = iabs(nm - om) > lim && om != k.peak && om != k.neutral;
-                out[j] = fix ? (uint32_t)((s4(up4, j) + s4(dn4, j) + 1) >> 1) : (uint32_t)s4(cur4, j);
-                any |= fix;
-            }
-            if (any)
-            {
-                if (x + 3 < width) *reinterpret_cast<uint2 *>(d) = make_uint2(out[0] | (out[1] << 16), out[2] | (out[3] << 16));
-                else for (int j = 0; j < 4 && x + j < width; j++) d[j] = (uint16_t)out[j];
-            }
-        }
-    }
-    if (copy)
-    {
-        uint16_t *o = Q.c + (size_t)yc * pitch + x;
-        if (x + 3 < width) *reinterpret_cast<uint2 *>(o) = vcopy;
-        else
-        {
-            const uint16_t o4[4] = { (uint16_t)(vcopy.x & 0xffffu), (uint16_t)(vcopy.x >> 16), (uint16_t)(vcopy.y & 0xffffu), (uint16_t)(vcopy.y >> 16) };
             for (int j = 0; j < 4 && x + j < width; j++) o[j] = o4[j];
         }
     }
@@ -1147,7 +1066,7 @@ __global__ __launch_bounds__(256) void q_dir_map(Q3 P, K16 k, int step, int expa
 #define FE16_ROWS 14
 #endif
 constexpr int QFE_R = FE16_ROWS, QFE_LW = 272;                      // LDS row: the group of 4 left of the tile, 256 samples, the group right of it
-// POST (the pair in front of eedi2_post_process, which rides along as in q_dir_map): d = where the filtered map goes as
+// POST (the pair in front of eedi2_post_process, which rides along: it is pointwise in the map the pass has just made): d = where the filtered map goes as
 // well, f = the picture, the old map = the pass's own input (eedi2.hip: k_dir_map_fe<2, true>); padv = what the padding of
 // the output's rows gets.
 template <int STEP, bool POST>
@@ -1797,19 +1716,6 @@ __global__ __launch_bounds__(256) void q_fill_gaps_b(Q3 P, K16 k)
     }
 }
 
-// plain copy of the visible width (eedi2_bit_blit :46-68): a = in, c = out; eight samples per thread
-__global__ void q_blit(Q3 P)
-{
-    FIELD16(P);
-    const int x = 8 * (blockIdx.x * blockDim.x + threadIdx.x), y = blockIdx.y * blockDim.y + threadIdx.y;
-    const int pitch = P.pitch[pl], width = P.width[pl], height = P.height[pl];
-    if (x >= width || y >= height) return;
-    const uint16_t *in = Q.a + (size_t)y * pitch + x;
-    uint16_t *out = Q.c + (size_t)y * pitch + x;
-    if (x + 7 < width) *reinterpret_cast<uint4 *>(out) = *reinterpret_cast<const uint4 *>(in);
-    else for (int i = 0; x + i < width; i++) out[i] = in[i];
-}
-
 // interpolate_lattice in two launches, as for 8-bit samples (eedi2.hip: k_lattice_cand / k_lattice_resolve).  Of all a
 // pixel's tests only one looks at the direction value just written at x-1 (the left-hand half of :1194); everything else
 // - including the whole "outcome B" the pixel takes when that test fails - reads values no pixel of the pass changes.
@@ -2422,9 +2328,6 @@ int Eedi2Engine16::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, 
     auto grid4 = [&](const EediFrame &f, unsigned z) {                          // four samples per thread, blocks of 64 x 4 threads
         return dim3(hbhip_grid_x((f.width[0] + 255) / 256), (f.height[0] + 3) / 4, z);
     };
-    auto grid4p = [&](const EediFrame &f, unsigned z) {                         // the same with a thread row per PAIR of rows (step 2)
-        return dim3(hbhip_grid_x((f.width[0] + 255) / 256), ((f.height[0] + 1) / 2 + 3) / 4, z);
-    };
     Q3 P;
     memset(&P, 0, sizeof(P));
     P.fstride = slot_bytes_ / 2;
@@ -2437,9 +2340,9 @@ int Eedi2Engine16::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, 
     // filter_dir_map and expand_dir_map as one launch (q_dir_map_fe; eedi2.hip: Eedi2Engine::enqueue_passes): calc_directions
     // then writes dstp, and leaves the padding of its rows alone, so that the fused pass leaves the expanded map - and the
     // padding calc_directions' fill gives it - in tmpp, where the reference has them
-    const bool fused = par_.maximum_search_distance <= QHALO - 2 && hbhip_dev_int("HBHIP_EEDI2_FUSE_DIRMAP", 1) != 0;
+    const bool fused = par_.maximum_search_distance <= QHALO - 2;
     bind(P.a, mskp); bind(P.b, srcp); bind(P.c, fused ? dstp : tmpp);
-    if (par_.maximum_search_distance <= QHALO - 2)
+    if (fused)
         // 256 columns x 4 rows per block, the mostly listed blocks in the dense form (eedi2.hip: Eedi2Engine::enqueue_passes);
         // its keys hold sums of 12-bit samples at most
         HBHIP_LAUNCH_ON(lc, st, "eedi2_16_calc_directions", q_calc_dir_rows<4>, dim3(hbhip_grid_x((srcp.stride[0] / 2 + QW - 1) / QW), (srcp.height[0] + 3) / 4, gz),
@@ -2456,38 +2359,26 @@ int Eedi2Engine16::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, 
     else
     {
         bind(P.a, mskp); bind(P.b, tmpp); bind(P.c, dstp);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_filter_dir_map", q_dir_map4, grid4(srcp, gz), blk, 0, P, k, 1, 0);
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_filter_dir_map", q_dir_map4, grid4(srcp, gz), blk, 0, P, k, 0);
         bind(P.a, mskp); bind(P.b, dstp); bind(P.c, tmpp);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_expand_dir_map", q_dir_map, grid4(srcp, gz), blk, 0, P, k, 1, 1, 0);
+        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_expand_dir_map", q_dir_map, grid4(srcp, gz), blk, 0, P, k, 1);
     }
     bind(P.a, mskp); bind(P.b, tmpp); bind(P.c, dstp);
     HBHIP_LAUNCH_ON(lc, st, "eedi2_16_filter_map", q_filter_map, grid4(srcp, gz), blk, 0, P, k);
     // the three line doublings + mark_directions_2x in one launch (full-height geometry)
     geom(P, dst2p);
-    // the pair of _2x dir-map passes behind it as one launch too (q_dir_map_fe<2>): the marked map then goes to dst2mp; and the
-    // pair in front of post_process with tmp2p and tmp2p2 in each other's places from here on, so that it reads the map where
+    // the pair of _2x dir-map passes behind it is one launch too (q_dir_map_fe<2>): the marked map goes to dst2mp; and so is the
+    // pair in front of post_process, with tmp2p and tmp2p2 in each other's places from here on, so that it reads the map where
     // the reference's copy of it would go (no blit) and writes the new one where the reference has it (eedi2.hip:
     // Eedi2Engine::enqueue_passes has the whole argument)
-    const bool fused2 = hbhip_dev_int("HBHIP_EEDI2_FUSE_DIRMAP_2X", 1) != 0;
     const bool post1 = par_.post_processing == 1 || par_.post_processing == 3;
-    const bool swapped = fused2 && post1 && hbhip_dev_int("HBHIP_EEDI2_FUSE_DIRMAP_POST", 1) != 0;
-    const EediFrame &map2 = swapped ? tmp2p2 : tmp2p, &omsk2 = swapped ? tmp2p : tmp2p2;
-    bind(P.a, mskp); bind(P.b, dstp); bind(P.g, srcp); bind(P.c, fused2 ? dst2mp : map2); bind(P.d, dst2p); bind(P.e, omsk2); bind(P.f, msk2p);
+    const EediFrame &map2 = post1 ? tmp2p2 : tmp2p, &omsk2 = post1 ? tmp2p : tmp2p2;
+    bind(P.a, mskp); bind(P.b, dstp); bind(P.g, srcp); bind(P.c, dst2mp); bind(P.d, dst2p); bind(P.e, omsk2); bind(P.f, msk2p);
     HBHIP_LAUNCH_ON(lc, st, "eedi2_16_mark_directions_2x", q_mark_2x,                                    // a thread row per pair of rows, four samples per thread
-                 dim3(hbhip_grid_x((dst2p.stride[0] / 2 + 255) / 256), ((dst2p.height[0] + 1) / 2 + 3) / 4, gz), blk, 0, P, k, fused2 ? 0 : k.peak);
+                 dim3(hbhip_grid_x((dst2p.stride[0] / 2 + 255) / 256), ((dst2p.height[0] + 1) / 2 + 3) / 4, gz), blk, 0, P, k, 0);
     const dim3 fe2_grid(hbhip_grid_x((dst2p.stride[0] / 2 + 255) / 256), ((dst2p.height[0] + 1) / 2 + QFE_R - 1) / QFE_R, gz);
-    if (fused2)
-    {
-        bind(P.a, msk2p); bind(P.b, dst2mp); bind(P.c, map2);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_filter_expand_dir_map_2x", (q_dir_map_fe<2, false>), fe2_grid, blk, 0, P, k, swapped ? 0 : k.peak);
-    }
-    else
-    {
-        bind(P.a, msk2p); bind(P.b, tmp2p); bind(P.c, dst2mp);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_filter_dir_map_2x", q_dir_map4, grid4p(dst2p, gz), blk, 0, P, k, 2, 0);
-        bind(P.a, msk2p); bind(P.b, dst2mp); bind(P.c, tmp2p);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_expand_dir_map_2x", q_dir_map, grid4p(dst2p, gz), blk, 0, P, k, 2, 1, 0);
-    }
+    bind(P.a, msk2p); bind(P.b, dst2mp); bind(P.c, map2);
+    HBHIP_LAUNCH_ON(lc, st, "eedi2_16_filter_expand_dir_map_2x", (q_dir_map_fe<2, false>), fe2_grid, blk, 0, P, k, post1 ? 0 : k.peak);
     for (int pass = 0; pass < 2; pass++)
     {
         const EediFrame &in = pass ? dst2mp : map2, &out = pass ? map2 : dst2mp;
@@ -2502,23 +2393,12 @@ int Eedi2Engine16::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, 
         HBHIP_LAUNCH_ON(lc, st, "eedi2_16_lattice_resolve", q_lattice_resolve16, dim3(1, nrows + 1, gz), dim3(LR16_T), 0, P, k,
                      (const unsigned long long *)cand, cand_pitch_, cand_plane_stride_);
     }
-    if (swapped)
+    if (post1)
     {
         // filter_dir_map_2x, expand_dir_map_2x and post_process in one launch: tmp2p2 -> tmp2p, the filtered map to dst2mp,
         // the corrections to dst2p
         bind(P.a, msk2p); bind(P.b, tmp2p2); bind(P.c, tmp2p); bind(P.d, dst2mp); bind(P.f, dst2p);
         HBHIP_LAUNCH_ON(lc, st, "eedi2_16_filter_expand_dir_map_2x_post", (q_dir_map_fe<2, true>), fe2_grid, blk, 0, P, k, k.peak);
-    }
-    else if (post1)
-    {
-        // (the copy as a store of the filter behind it, as the 8-bit engine has it, cost that launch what the blit costs: 44 us)
-        bind(P.a, tmp2p); bind(P.c, tmp2p2);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_blit", q_blit, dim3(hbhip_grid_x((dst2p.width[0] + 511) / 512), (dst2p.height[0] + 3) / 4, gz), blk, 0, P);   // eedi2_bit_blit(tmp2p -> tmp2p2)
-        bind(P.a, msk2p); bind(P.b, tmp2p); bind(P.c, dst2mp);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_filter_dir_map_2x", q_dir_map4, grid4p(dst2p, gz), blk, 0, P, k, 2, 0);
-        // + eedi2_post_process (new map = what the pass writes, old map tmp2p2, picture dst2p): folded into the pass
-        bind(P.a, msk2p); bind(P.b, dst2mp); bind(P.c, tmp2p); bind(P.e, tmp2p2); bind(P.f, dst2p);
-        HBHIP_LAUNCH_ON(lc, st, "eedi2_16_expand_dir_map_2x", q_dir_map, grid4p(dst2p, gz), blk, 0, P, k, 2, 1, 1);
     }
     if (par_.post_processing == 2 || par_.post_processing == 3)
     {

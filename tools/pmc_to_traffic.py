@@ -14,9 +14,9 @@ NAMES = {
     "k_calc_dir_rows": ("eedi2_calc_directions", 16), "k_fill_gaps_b": ("eedi2_fill_gaps_2x", 16),
     "k_lattice_cand_q": ("eedi2_lattice_candidates", 16), "k_lattice_resolve": ("eedi2_lattice_resolve", 16),
     "k_mark_2x4": ("eedi2_mark_directions_2x", 16),
-    "k_filter_map": ("eedi2_filter_map", 16), "k_post": ("eedi2_post_process", 16),
-    "k_dir_map4": ("eedi2_filter_dir_map_2x", 16),          # half-height and _2x forms, mean
-    "k_dir_map_c": ("eedi2_expand_dir_map_2x", 16),         # half-height and _2x forms, mean
+    "k_filter_map": ("eedi2_filter_map", 16),
+    "k_dir_map4": ("eedi2_filter_dir_map", 16),             # the half-height pair as two launches: search distances
+    "k_dir_map_c": ("eedi2_expand_dir_map", 16),            # above 30 only
     "decomb_plane4_kernel": ("decomb_plane", 16), "scale8_up_kernel": ("cropscale_lanczos_fused", 16),
     "lapsharp3_rows_kernel": ("lapsharp_3x3", 16), "copy3_batch_kernel": ("copy_planes", 32),
     "k_mask_chain": ("eedi2_mask_passes", 16), "k_mask_fused4": ("eedi2_mask_passes", 1),
