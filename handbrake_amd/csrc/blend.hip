@@ -21,10 +21,13 @@
 #include "hbhip_internal.h"
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "blend_body.h"
 #include "ass_compose.h"
+#include "bitmap_scale.h"
+#include "sws_filter.h"
 
 namespace {
 
@@ -63,9 +66,15 @@ struct hbhip_blend
     uint8_t *h_ass = nullptr, *d_ass = nullptr;
     size_t   h_ass_bytes = 0, d_ass_bytes = 0;
     hipEvent_t ass_uploaded = nullptr;   // behind the last copy out of h_ass: the next call packs into it after this
+    // hbhip_blend_set_bitmaps: the bitmap subtitles the object holds, scaled, each in an allocation of its own (they come
+    // and go one by one); it packs its tables and source planes into h_ass / d_ass as well
+    struct Bitmap { uint64_t key; int sw, sh, dw, dh; uint8_t *d; size_t cap; };   // d: Y, Cb, Cr, A back to back, stride align16(dw)
+    std::vector<Bitmap> bitmaps;
+    int64_t bmp_scaled = 0, bmp_uploaded = 0, bmp_hits = 0;
 
     ~hbhip_blend()
     {
+        for (Bitmap &m : bitmaps) (void)hipFree(m.d);
         if (ass_uploaded) (void)hipEventDestroy(ass_uploaded);
         if (h_ass) (void)hipHostFree(h_ass);
         if (d_ass) (void)hipFree(d_ass);
@@ -217,6 +226,33 @@ extern "C" int hbhip_blend_set_overlays(hbhip_blend *b, const hbhip_overlay *ov,
     return HBHIP_OK;
 }
 
+// The pinned staging buffer h_ass and its device twin d_ass, both at least `bytes`.  On return the previous call's copy has
+// left the staging buffer; a twin that has to grow waits for the kernels that may still be reading the old one.
+static int reserve_upload(hbhip_blend *b, size_t bytes)
+{
+    hbhip_ctx *ctx = b->ctx;
+    if (bytes > b->d_ass_bytes)
+    {
+        HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (b->d_ass) (void)hipFree(b->d_ass);
+        b->d_ass = nullptr;
+        b->d_ass_bytes = 0;
+        HBHIP_CHECK(ctx, hipMalloc((void **)&b->d_ass, bytes));
+        b->d_ass_bytes = bytes;
+    }
+    if (!b->ass_uploaded) HBHIP_CHECK(ctx, hipEventCreateWithFlags(&b->ass_uploaded, hipEventDisableTiming));
+    else HBHIP_CHECK(ctx, hipEventSynchronize(b->ass_uploaded));
+    if (bytes > b->h_ass_bytes)
+    {
+        if (b->h_ass) (void)hipHostFree(b->h_ass);
+        b->h_ass = nullptr;
+        b->h_ass_bytes = 0;
+        HBHIP_CHECK(ctx, hipHostMalloc((void **)&b->h_ass, bytes, hipHostMallocDefault));
+        b->h_ass_bytes = bytes;
+    }
+    return HBHIP_OK;
+}
+
 // ---- text subtitles: libass's glyph images composed on the device (ass_compose.hip) ----
 namespace {
 struct AssBox { int x1, y1, x2, y2; };
@@ -300,24 +336,8 @@ extern "C" int hbhip_blend_set_ass_images(hbhip_blend *b, const hbhip_ass_image 
         HBHIP_CHECK(ctx, hipMalloc((void **)&b->d_store, total));
         b->store_bytes = total;
     }
-    if (up_bytes > b->d_ass_bytes)
-    {
-        if (b->d_ass) (void)hipFree(b->d_ass);
-        b->d_ass = nullptr;
-        b->d_ass_bytes = 0;
-        HBHIP_CHECK(ctx, hipMalloc((void **)&b->d_ass, up_bytes));
-        b->d_ass_bytes = up_bytes;
-    }
-    if (!b->ass_uploaded) HBHIP_CHECK(ctx, hipEventCreateWithFlags(&b->ass_uploaded, hipEventDisableTiming));
-    else HBHIP_CHECK(ctx, hipEventSynchronize(b->ass_uploaded));          // the previous call's copy has left the staging buffer
-    if (up_bytes > b->h_ass_bytes)
-    {
-        if (b->h_ass) (void)hipHostFree(b->h_ass);
-        b->h_ass = nullptr;
-        b->h_ass_bytes = 0;
-        HBHIP_CHECK(ctx, hipHostMalloc((void **)&b->h_ass, up_bytes, hipHostMallocDefault));
-        b->h_ass_bytes = up_bytes;
-    }
+    const int rs = reserve_upload(b, up_bytes);
+    if (rs != HBHIP_OK) return rs;
 
     AssBoxDev *hb = reinterpret_cast<AssBoxDev *>(b->h_ass);
     AssImageDev *hi = reinterpret_cast<AssImageDev *>(b->h_ass + box_bytes);
@@ -367,6 +387,283 @@ extern "C" int hbhip_blend_set_ass_images(hbhip_blend *b, const hbhip_ass_image 
     if (rc != HBHIP_OK) return rc;
     b->overlays = std::move(ovs);
     build_launches(b);
+    return HBHIP_OK;
+}
+
+// ---- bitmap subtitles: scale_subtitle (rendersub.c:242-377) with the scaling on the device (bitmap_scale.hip) ----
+namespace {
+struct BitmapPlan
+{
+    const hbhip_bitmap_sub *sub;
+    int dw, dh, x, y;                    // scaled size, placed position
+    bool scale, fresh;                   // fresh: this call made the entry and fills it
+    size_t entry;                        // in hbhip_blend::bitmaps
+    size_t at, planes_at;                // a fresh one's bytes in the staging buffer: tables (scaled ones), packed source planes
+    std::vector<int> px, py;
+    std::vector<short> qx, qy;
+    int tx, ty, rows;
+};
+
+// everything the object holds goes, once what may still be reading it has run
+void drop_bitmaps(hbhip_blend *b)
+{
+    if (b->bitmaps.empty()) return;
+    (void)hipSetDevice(b->ctx->device);
+    (void)hipStreamSynchronize(b->ctx->stream);
+    for (hbhip_blend::Bitmap &m : b->bitmaps) (void)hipFree(m.d);
+    b->bitmaps.clear();
+}
+
+// :311-375: out of the cropped zones, 2 % of the height (20 rows at most) clear of top and bottom and 20 columns of the
+// sides, centred where it does not fit.  crop = top, bottom, left, right.
+void place_bitmap(int W, int H, const int crop[4], int w, int h, int &x, int &y)
+{
+    int margin_top = ((H - crop[0] - crop[1]) * 2) / 100;
+    if (margin_top > 20) margin_top = 20;
+    if (h > H - crop[0] - crop[1] - margin_top * 2) y = crop[0] + (H - crop[0] - crop[1] - h) / 2;
+    else if (y < crop[0] + margin_top)              y = crop[0] + margin_top;
+    else if (y > H - crop[1] - margin_top - h)      y = H - crop[1] - margin_top - h;
+    if (w > W - crop[2] - crop[3] - 40)             x = crop[2] + (W - crop[2] - crop[3] - w) / 2;
+    else if (x < crop[2] + 20)                      x = crop[2] + 20;
+    else if (x > W - crop[3] - 20 - w)              x = W - crop[3] - 20 - w;
+}
+
+// the tables of a bitmap that has to be scaled, and the most source rows a tile of bitmap_scale_kernel taps (its own walk)
+int plan_tables(BitmapPlan &pl)
+{
+    const int sw = pl.sub->width, sh = pl.sub->height;
+    pl.tx = sws_filter(sw, pl.dw, 1 << 14, 128, 128, pl.px, pl.qx);
+    pl.ty = sws_filter(sh, pl.dh, 1 << 12, 128, 128, pl.py, pl.qy);
+    for (int v : pl.px) if (v < 0 || v + pl.tx > sw) return HBHIP_ERR_UNSUPPORTED;
+    for (int v : pl.py) if (v < 0 || v + pl.ty > sh) return HBHIP_ERR_UNSUPPORTED;
+    pl.rows = 0;
+    for (int y0 = 0; y0 < pl.dh; y0 += BMS_TILE_H)
+    {
+        int r0 = pl.py[y0], r1 = r0 + pl.ty;
+        for (int y = y0 + 1; y < std::min(y0 + BMS_TILE_H, pl.dh); y++)
+        {
+            r0 = std::min(r0, pl.py[y]);
+            r1 = std::max(r1, pl.py[y] + pl.ty);
+        }
+        pl.rows = std::max(pl.rows, r1 - r0);
+    }
+    return pl.rows <= BMS_MAX_ROWS ? HBHIP_OK : HBHIP_ERR_UNSUPPORTED;
+}
+
+int set_bitmaps(hbhip_blend *b, const hbhip_bitmap_sub *sub, int n, const int crop[4])
+{
+    if (n < 0 || (n > 0 && !sub) || !crop) return HBHIP_ERR_ARG;
+    if (b->ov_wshift || b->ov_hshift) return HBHIP_ERR_UNSUPPORTED;       // bitmap subtitles are YUVA444P (:418, :1073)
+    hbhip_ctx *ctx = b->ctx;
+    (void)hipSetDevice(ctx->device);
+    const int W = b->geo.width, H = b->geo.height;
+
+    // sizes and positions, in the reference's double arithmetic (:246-283)
+    std::vector<BitmapPlan> plans;
+    for (int i = 0; i < n; i++)
+    {
+        const hbhip_bitmap_sub &s = sub[i];
+        if (s.width < 0 || s.height < 0) return HBHIP_ERR_ARG;
+        if (!s.width || !s.height) continue;                                // a PGS "clear" packet (:1043-1055)
+        for (int p = 0; p < 4; p++)
+            if (!s.plane[p] || s.stride[p] < s.width) return HBHIP_ERR_ARG;
+        double factor = 1.;
+        if (s.window_width > 0 && s.window_height > 0)
+        {
+            const double xfactor = (double)W / s.window_width, yfactor = (double)H / s.window_height;
+            factor = xfactor > yfactor ? xfactor : yfactor;
+        }
+        BitmapPlan pl;
+        pl.sub = &s;
+        pl.scale = std::fabs(factor - 1) > 0.01;
+        pl.fresh = false;
+        pl.dw = s.width; pl.dh = s.height; pl.x = s.x; pl.y = s.y;
+        if (pl.scale)
+        {
+            // below 8 samples libswscale clamps its tap count to the plane (initFilter: size <= src - 2)
+            if (factor < 0.25 || factor > 4. || s.width < 8 || s.height < 8) return HBHIP_ERR_UNSUPPORTED;
+            pl.dw = (int)(s.width * factor); pl.dh = (int)(s.height * factor);
+            pl.x = (int)(s.x * factor); pl.y = (int)(s.y * factor);
+            if (pl.dw < 1 || pl.dh < 1) return HBHIP_ERR_UNSUPPORTED;
+        }
+        place_bitmap(W, H, crop, pl.dw, pl.dh, pl.x, pl.y);
+        pl.entry = pl.at = pl.planes_at = 0;
+        pl.tx = pl.ty = pl.rows = 0;
+        plans.push_back(std::move(pl));
+    }
+
+    // A key the object holds at this geometry is a hit.  Any other gets an entry, once every hit is known: in the allocation
+    // of an entry this call does not name where one is large enough - whoever still reads that is queued on the stream ahead
+    // of what fills it again, so a subtitle that replaces another waits for nothing and allocates nothing - or a new one.
+    std::vector<signed char> used(b->bitmaps.size(), 0);
+    auto find = [&](const BitmapPlan &pl) {
+        const hbhip_bitmap_sub &s = *pl.sub;
+        size_t e = 0;
+        while (e < b->bitmaps.size() && !(used[e] >= 0 && b->bitmaps[e].key == s.key && b->bitmaps[e].sw == s.width &&
+                                          b->bitmaps[e].sh == s.height && b->bitmaps[e].dw == pl.dw && b->bitmaps[e].dh == pl.dh))
+            e++;
+        return e;
+    };
+    const size_t held = b->bitmaps.size();
+    for (BitmapPlan &pl : plans)
+        if ((pl.entry = find(pl)) < held) used[pl.entry] = 1;
+    for (size_t e = 0; e < held; e++)
+        if (!used[e]) used[e] = -1;                                         // not named: its key means nothing from here on
+    for (BitmapPlan &pl : plans)
+    {
+        if (pl.entry == held) pl.entry = find(pl);                          // (a key named twice in a list: made once)
+        if (pl.entry < b->bitmaps.size())
+        {
+            b->bmp_hits++;
+            continue;
+        }
+        const hbhip_bitmap_sub &s = *pl.sub;
+        if (pl.scale)
+        {
+            const int rt = plan_tables(pl);
+            if (rt != HBHIP_OK) return rt;
+        }
+        const size_t need = 4 * (size_t)hbhip_align_up(pl.dw, 16) * pl.dh;
+        size_t e = b->bitmaps.size();
+        for (size_t k = 0; k < held; k++)
+            if (used[k] < 0 && b->bitmaps[k].cap >= need && (e == b->bitmaps.size() || b->bitmaps[k].cap < b->bitmaps[e].cap)) e = k;
+        if (e == b->bitmaps.size())
+        {
+            hbhip_blend::Bitmap m = { 0, 0, 0, 0, 0, nullptr, need };
+            HBHIP_CHECK(ctx, hipMalloc((void **)&m.d, need));
+            b->bitmaps.push_back(m);
+            used.push_back(1);
+        }
+        hbhip_blend::Bitmap &m = b->bitmaps[e];
+        m.key = s.key; m.sw = s.width; m.sh = s.height; m.dw = pl.dw; m.dh = pl.dh;
+        used[e] = 1;
+        pl.entry = e;
+        pl.fresh = true;
+    }
+
+    // the fresh ones through the staging buffer: [tables][source planes] of every one to scale, in one copy to its twin,
+    // then the planes of the others, each copied to where it stays
+    std::vector<BitmapPlan *> fresh;
+    for (int scale = 1; scale >= 0; scale--)
+        for (BitmapPlan &pl : plans)
+            if (pl.fresh && pl.scale == (scale != 0)) fresh.push_back(&pl);
+    size_t up_bytes = 0, scaled_bytes = 0;
+    for (BitmapPlan *pl : fresh)
+    {
+        pl->at = up_bytes;
+        if (pl->scale)
+            up_bytes += ((pl->px.size() + pl->py.size()) * sizeof(int) + (pl->qx.size() + pl->qy.size()) * sizeof(short) + 15) & ~(size_t)15;
+        pl->planes_at = up_bytes;
+        up_bytes += 4 * (size_t)hbhip_align_up(pl->sub->width, 16) * pl->sub->height;
+        if (pl->scale) scaled_bytes = up_bytes;
+    }
+    if (up_bytes > 0x7fffffff) return HBHIP_ERR_UNSUPPORTED;
+    if (!fresh.empty())
+    {
+        const int rs = reserve_upload(b, up_bytes);
+        if (rs != HBHIP_OK) return rs;
+        for (BitmapPlan *pl : fresh)
+        {
+            const hbhip_bitmap_sub &s = *pl->sub;
+            uint8_t *at = b->h_ass + pl->at;
+            if (pl->scale)
+            {
+                memset(b->h_ass + pl->planes_at - 16, 0, 16);                   // (the tables end inside these)
+                memcpy(at, pl->px.data(), pl->px.size() * sizeof(int));   at += pl->px.size() * sizeof(int);
+                memcpy(at, pl->py.data(), pl->py.size() * sizeof(int));   at += pl->py.size() * sizeof(int);
+                memcpy(at, pl->qx.data(), pl->qx.size() * sizeof(short)); at += pl->qx.size() * sizeof(short);
+                memcpy(at, pl->qy.data(), pl->qy.size() * sizeof(short));
+            }
+            const int sp = hbhip_align_up(s.width, 16);
+            at = b->h_ass + pl->planes_at;
+            for (int p = 0; p < 4; p++)
+                for (int r = 0; r < s.height; r++, at += sp)
+                {
+                    memcpy(at, s.plane[p] + (size_t)r * s.stride[p], s.width);
+                    memset(at + s.width, 0, sp - s.width);
+                }
+        }
+        // the caller may free its bitmaps from here on: they are in the staging buffer
+        if (scaled_bytes) HBHIP_CHECK(ctx, hipMemcpyAsync(b->d_ass, b->h_ass, scaled_bytes, hipMemcpyHostToDevice, ctx->stream));
+        for (BitmapPlan *pl : fresh)
+        {
+            const hbhip_bitmap_sub &s = *pl->sub;
+            const size_t src_plane = (size_t)hbhip_align_up(s.width, 16) * s.height;
+            uint8_t *dst = b->bitmaps[pl->entry].d;
+            b->bmp_uploaded++;
+            if (!pl->scale)
+            {
+                HBHIP_CHECK(ctx, hipMemcpyAsync(dst, b->h_ass + pl->planes_at, 4 * src_plane, hipMemcpyHostToDevice, ctx->stream));
+                continue;
+            }
+            BitmapScaleArgs a;
+            a.spitch = hbhip_align_up(s.width, 16); a.dpitch = hbhip_align_up(pl->dw, 16);
+            a.dw = pl->dw; a.dh = pl->dh; a.tx = pl->tx; a.ty = pl->ty;
+            for (int p = 0; p < 4; p++)
+            {
+                a.src[p] = b->d_ass + pl->planes_at + p * src_plane;
+                a.dst[p] = dst + p * (size_t)a.dpitch * pl->dh;
+            }
+            a.px = reinterpret_cast<const int *>(b->d_ass + pl->at);
+            a.py = a.px + pl->px.size();
+            a.qx = reinterpret_cast<const short *>(a.py + pl->py.size());
+            a.qy = a.qx + pl->qx.size();
+            const int rl = hbhip_bitmap_scale_launch(ctx, a, pl->rows);
+            if (rl != HBHIP_OK) return rl;
+            b->bmp_scaled++;
+        }
+        HBHIP_CHECK(ctx, hipEventRecord(b->ass_uploaded, ctx->stream));
+    }
+
+    // the list, in list order; then the keys this call did not name go
+    for (const BitmapPlan &pl : plans)
+    {
+        const hbhip_blend::Bitmap &m = b->bitmaps[pl.entry];
+        OverlayDev d;
+        d.x = pl.x; d.y = pl.y; d.width = m.dw; d.height = m.dh;
+        for (int p = 0; p < 4; p++)
+        {
+            d.stride[p] = hbhip_align_up(m.dw, 16);
+            d.plane[p] = m.d + p * (size_t)d.stride[p] * m.dh;
+        }
+        b->overlays.push_back(d);
+    }
+    if (std::find(used.begin(), used.end(), -1) != used.end())
+    {
+        HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));                // launches of the previous list may still be reading them
+        size_t keep = 0;
+        for (size_t e = 0; e < b->bitmaps.size(); e++)
+            if (used[e] > 0) b->bitmaps[keep++] = b->bitmaps[e];
+            else (void)hipFree(b->bitmaps[e].d);
+        b->bitmaps.resize(keep);
+    }
+    build_launches(b);
+    return HBHIP_OK;
+}
+} // namespace
+
+extern "C" int hbhip_blend_set_bitmaps(hbhip_blend *b, const hbhip_bitmap_sub *sub, int n, const int crop[4])
+{
+    if (!b) return HBHIP_ERR_ARG;
+    b->overlays.clear();
+    b->launches.clear();
+    const int rc = set_bitmaps(b, sub, n, crop);
+    if (rc != HBHIP_OK)
+    {
+        // an empty list, and nothing half-made behind it: the caller takes this frame's subtitles down its other path
+        b->overlays.clear();
+        b->launches.clear();
+        drop_bitmaps(b);
+    }
+    return rc;
+}
+
+extern "C" int hbhip_blend_debug_bitmap_stats(hbhip_blend *b, int64_t *scaled, int64_t *uploaded, int64_t *hits)
+{
+    if (!b) return HBHIP_ERR_ARG;
+    if (scaled) *scaled = b->bmp_scaled;
+    if (uploaded) *uploaded = b->bmp_uploaded;
+    if (hits) *hits = b->bmp_hits;
     return HBHIP_OK;
 }
 

@@ -462,6 +462,57 @@ def blend_run_ass(lib, symbol, frame, lists, crop=(0, 0, 0, 0), pix_fmt=AV_PIX_F
     return tuple(out)
 
 
+class Bitmap(C.Structure):
+    """hbh_bitmap_t: a decoded bitmap subtitle - the bitmap at (x, y) of its canvas, the canvas, its start time"""
+    _fields_ = [("ov", Overlay), ("window_width", C.c_int), ("window_height", C.c_int), ("start", C.c_int64)]
+
+
+def blend_run_bitmaps(lib, symbol, frame, subs, calls, crop=(0, 0, 0, 0), pix_fmt=AV_PIX_FMT_YUV420P,
+                      overlay_fmt=AV_PIX_FMT_YUVA444P, chroma_location=1, dev_ctx=None, depth=8):
+    """Bitmap subtitles through the compositor object `symbol` of `lib` ("hb_blend_hip").  subs: the track's decoded
+    subtitles, (x, y, (Y, Cb, Cr, A), (window_width, window_height), start); calls: for each call of
+    hb_blend_hip_set_bitmaps, in order, the indices into `subs` it lists.  Then work() composites the last list on a copy of
+    `frame`.  crop = (top, bottom, left, right).  dev_ctx: a hip.Ctx - the frame is then a device-resident one of it."""
+    rt = runtime()
+    rt.hbh_blend_run_bitmaps.restype = C.c_int
+    rt.hbh_blend_run_bitmaps.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_void_p), C.POINTER(C.c_int),
+                                         C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(Bitmap), C.c_int,
+                                         C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_int)), C.POINTER(C.c_int)]
+    out = [np.ascontiguousarray(p).copy() for p in frame]
+    h, w = out[0].shape
+    ptrs = (C.c_void_p * 3)(*[p.ctypes.data for p in out])
+    strides = (C.c_int * 3)(*[p.strides[0] for p in out])
+    ovs, keep = overlay_array([(x, y, planes) for x, y, planes, _, _ in subs])
+    arr = (Bitmap * max(len(subs), 1))()
+    for i, (_, _, _, window, start) in enumerate(subs):
+        arr[i].ov = ovs[i]
+        arr[i].window_width, arr[i].window_height = window
+        arr[i].start = start
+    idx = [(C.c_int * max(len(c), 1))(*c) for c in calls]
+    counts = (C.c_int * max(len(calls), 1))(*[len(c) for c in calls])
+    tables = (C.POINTER(C.c_int) * max(len(calls), 1))(*[C.cast(a, C.POINTER(C.c_int)) for a in idx])
+    proto = C.addressof(C.c_char.in_dll(lib, symbol))
+    setter = C.cast(lib.hb_blend_hip_set_bitmaps, C.c_void_p)
+    fr_in, fr_out = None, C.c_void_p()
+    if dev_ctx is not None:
+        from . import hip
+        lch, lcw = (out[0].shape[0] // out[1].shape[0]) >> 1, (out[0].shape[1] // out[1].shape[1]) >> 1
+        fr = hip.Frame(dev_ctx, w, h, depth, lcw, lch)
+        fr.upload(out)
+        fr_in, fr.h = fr.h, None                           # the call takes the reference over
+    rc = rt.hbh_blend_run_bitmaps(proto, setter, pix_fmt, w, h, chroma_location, overlay_fmt, ptrs, strides, fr_in,
+                                  C.byref(fr_out), len(subs), arr, len(calls), counts, tables, (C.c_int * 4)(*crop))
+    if rc != 0:
+        raise RuntimeError(f"hbh_blend_run_bitmaps({symbol}) failed ({rc})")
+    if dev_ctx is not None:
+        fr.h = fr_out
+        try:
+            out = fr.download()
+        finally:
+            fr.close()
+    return tuple(out)
+
+
 def motion_metric_run(lib, symbol, luma_a, luma_b, pix_fmt=AV_PIX_FMT_YUV420P) -> float:
     """Run the metric object `symbol` of `lib` (e.g. "hb_motion_metric_hip") on two luma planes."""
     rt = runtime()

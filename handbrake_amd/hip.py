@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "hbhip_blend_create", "hbhip_blend_set_overlays", "hbhip_blend_apply", "hbhip_blend_apply_dev", "hbhip_blend_destroy",
     "hbhip_blend_create_biplanar", "hbhip_blend_apply_biplanar",
     "hbhip_blend_set_ass_images", "hbhip_blend_debug_overlay_count", "hbhip_blend_debug_get_overlay",
+    "hbhip_blend_set_bitmaps", "hbhip_blend_debug_bitmap_stats",
     "hbhip_motion_metric_create", "hbhip_motion_metric_run", "hbhip_motion_metric_run_dev", "hbhip_motion_metric_destroy",
     "hbhip_detelecine_create", "hbhip_detelecine_push", "hbhip_detelecine_push_frame",
     "hbhip_deblock_create", "hbhip_deblock_set_warmup",
@@ -57,6 +58,12 @@ class HostBiplanar(C.Structure):
 
 class DevFrame(C.Structure):
     _fields_ = [("plane", C.c_void_p * 3), ("stride", C.c_int * 3)]
+
+
+class BitmapSub(C.Structure):
+    """hbhip_bitmap_sub: a decoded bitmap subtitle - the 4:4:4 YUVA bitmap, its place on its canvas, the canvas, a key"""
+    _fields_ = [("plane", C.c_void_p * 4), ("stride", C.c_int * 4), ("x", C.c_int), ("y", C.c_int), ("width", C.c_int),
+                ("height", C.c_int), ("window_width", C.c_int), ("window_height", C.c_int), ("key", C.c_uint64)]
 
 
 class NLMeansParams(C.Structure):
@@ -625,6 +632,37 @@ class BlendDevice:
         arr, keep = hbrt.ass_image_array(images)
         check(L.hbhip_blend_set_ass_images(self.h, C.cast(arr, C.c_void_p), len(images), crop_left, crop_top), self.ctx.h,
               "set_ass_images")
+
+    def set_bitmaps(self, subs, crop=(0, 0, 0, 0), strides=None, raise_on_error=True):
+        """subs: decoded bitmap subtitles, a list of (x, y, (Y, Cb, Cr, A) uint8 arrays, (window_width, window_height), key);
+        scaled and placed on the device as scale_subtitle would, once per key.  crop = (top, bottom, left, right).
+        strides: row pitches to declare in place of the arrays' own (per sub, four each).  Returns the HBHIP_* code where
+        raise_on_error is off."""
+        import numpy as np
+        L = lib()
+        L.hbhip_blend_set_bitmaps.argtypes = [C.c_void_p, C.POINTER(BitmapSub), C.c_int, C.POINTER(C.c_int)]
+        arr = (BitmapSub * max(len(subs), 1))()
+        keep = []
+        for i, (x, y, planes, window, key) in enumerate(subs):
+            planes = [np.ascontiguousarray(p, dtype=np.uint8) for p in planes]
+            keep.append(planes)
+            for k, p in enumerate(planes):
+                arr[i].plane[k] = p.ctypes.data
+                arr[i].stride[k] = p.strides[0] if strides is None else strides[i][k]
+            arr[i].x, arr[i].y = x, y
+            arr[i].height, arr[i].width = planes[0].shape
+            arr[i].window_width, arr[i].window_height = window
+            arr[i].key = key
+        rc = L.hbhip_blend_set_bitmaps(self.h, arr, len(subs), (C.c_int * 4)(*crop))
+        return check(rc, self.ctx.h, "set_bitmaps") if raise_on_error else rc
+
+    def bitmap_stats(self):
+        """(scale launches, bitmaps uploaded, cache hits) of set_bitmaps since the object was made (test hook)"""
+        L = lib()
+        L.hbhip_blend_debug_bitmap_stats.argtypes = [C.c_void_p] + [C.POINTER(C.c_int64)] * 3
+        v = [C.c_int64() for _ in range(3)]
+        check(L.hbhip_blend_debug_bitmap_stats(self.h, *[C.byref(x) for x in v]), self.ctx.h, "bitmap_stats")
+        return tuple(x.value for x in v)
 
     def overlays(self, log2_cw=1, log2_ch=1):
         """the object's overlay list read back from its device store (test hook): [(x, y, (Y, Cb, Cr, A))], the chroma

@@ -14,6 +14,8 @@
  * Text subtitles: hb_blend_hip_set_ass_images hands libass's glyph images to the device, which composes the overlays in
  * its own store (csrc/ass_compose.hip, in place of compose_subsample_ass, rendersub.c:474-612); work() with an empty list
  * then composites those.  INTEGRATION.md has the lines for render_ssa_subs.
+ * Bitmap subtitles: hb_blend_hip_set_bitmaps hands the decoded bitmaps over the same way; the device scales and places them
+ * (csrc/bitmap_scale.hip, in place of scale_subtitle, rendersub.c:242-377) once per subtitle, not per frame.
  */
 #include "hbhip_host.h"
 
@@ -21,7 +23,7 @@ struct hb_blend_private_s
 {
     hbhip_blend *dev;                /* made on the first frame: on the GPU that frame lives on */
     int          have_overlays;      /* the device holds the current list */
-    int          have_ass;           /* ... and it came from hb_blend_hip_set_ass_images: work() has nothing to upload */
+    int          have_ass;           /* ... and it came from hb_blend_hip_set_ass_images / _set_bitmaps: work() has nothing to upload */
     int          width, height, depth, lcw, lch, chroma_location, ov_lcw, ov_lch;
     int          biplanar;           /* NV12 / P010LE host frames */
 };
@@ -207,6 +209,40 @@ int hb_blend_hip_set_ass_images(hb_blend_object_t *blend, const hb_buffer_t *fra
     if (pv == NULL || frame == NULL || crop == NULL) return HBHIP_ERR_ARG;
     int rc = blend_hip_device(pv, frame);
     if (rc == HBHIP_OK) rc = hbhip_blend_set_ass_images(pv->dev, img, n, crop[2], crop[0]);
+    pv->have_overlays = 0;
+    pv->have_ass = rc == HBHIP_OK && n > 0;
+    if (rc != HBHIP_OK) hb_error("blend(hip): %s", hbhip_strerror(rc));
+    return rc;
+}
+
+/* render_vobsubs' / render_pgs_subs' calls of scale_subtitle (rendersub.c:402, :1061) for a `blend` that is hb_blend_hip: the
+ * active subtitles of the frame, in list order, become the device's overlay list (n == 0: none).  Called for every frame:
+ * a subtitle the device already holds costs nothing.  crop = top, bottom, left, right. */
+int hb_blend_hip_set_bitmaps(hb_blend_object_t *blend, const hb_buffer_t *frame, hb_buffer_t *const *subs, int n,
+                             const int crop[4])
+{
+    hb_blend_private_t *pv = blend != NULL ? blend->private_data : NULL;
+    if (pv == NULL || frame == NULL || crop == NULL || n < 0 || (n > 0 && subs == NULL)) return HBHIP_ERR_ARG;
+    hbhip_bitmap_sub *bs = calloc((size_t)(n > 0 ? n : 1), sizeof(*bs));
+    if (bs == NULL) return HBHIP_ERR_NOMEM;
+    int rc = blend_hip_device(pv, frame);
+    for (int i = 0; i < n && rc == HBHIP_OK; i++)
+    {
+        const hb_buffer_t *s = subs[i];
+        if (s == NULL) { rc = HBHIP_ERR_ARG; break; }
+        for (int p = 0; p < 4; p++)
+        {
+            bs[i].plane[p] = s->plane[p].data;
+            bs[i].stride[p] = s->plane[p].stride;
+        }
+        bs[i].x = s->f.x; bs[i].y = s->f.y; bs[i].width = s->f.width; bs[i].height = s->f.height;
+        bs[i].window_width = s->f.window_width; bs[i].window_height = s->f.window_height;
+        /* an address is reused once rendersub has closed the buffer: the start time tells the next subtitle from it */
+        bs[i].key = (uint64_t)(uintptr_t)s ^ ((uint64_t)s->s.start * 0x9E3779B97F4A7C15ull);
+    }
+    if (rc == HBHIP_OK) rc = hbhip_blend_set_bitmaps(pv->dev, bs, n, crop);
+    else if (pv->dev != NULL) hbhip_blend_set_bitmaps(pv->dev, NULL, 0, crop);
+    free(bs);
     pv->have_overlays = 0;
     pv->have_ass = rc == HBHIP_OK && n > 0;
     if (rc != HBHIP_OK) hb_error("blend(hip): %s", hbhip_strerror(rc));

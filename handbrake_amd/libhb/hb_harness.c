@@ -758,21 +758,14 @@ int hbh_blend_run(const void *proto, int pix_fmt, int width, int height, int chr
     return rc;
 }
 
-int hbh_blend_run_ass(const void *proto, const void *set_images, int pix_fmt, int width, int height, int chroma_location,
-                      int overlay_fmt, uint8_t *const plane[3], const int stride[3], void *dev_frame, void **dev_frame_out,
-                      int n_lists, const int *n_images, const void *const *lists, const int crop[4])
+/* The frame of hbh_blend_run_ass / _bitmaps: a copy of the caller's planes, or the shell a device-resident run puts around a
+ * picture in HBM (no host planes) ... */
+static hb_buffer_t *blend_frame_in(int pix_fmt, int width, int height, uint8_t *const plane[3], const int stride[3], void *dev_frame)
 {
-    typedef int (*set_images_f)(hb_blend_object_t *, const hb_buffer_t *, const void *, int, const int *);
-    const set_images_f set = (set_images_f)set_images;
-    hb_blend_object_t blend = *(const hb_blend_object_t *)proto;
-    hb_buffer_list_t none;
-    memset(&none, 0, sizeof(none));
-    int rc = 0;
     hb_buffer_t *b = dev_frame != NULL ? hb_buffer_init(0) : hb_frame_buffer_init(pix_fmt, width, height);
-    if (b == NULL) return -1;
+    if (b == NULL) return NULL;
     if (dev_frame != NULL)
     {
-        /* the shell a device-resident run puts around a picture in HBM: no host planes */
         b->s.type = FRAME_BUF;
         b->f.fmt = pix_fmt;
         b->f.width = width;
@@ -791,6 +784,42 @@ int hbh_blend_run_ass(const void *proto, const void *set_images, int pix_fmt, in
             for (int y = 0; y < b->plane[p].height; y++)
                 memcpy(b->plane[p].data + (size_t)y * b->plane[p].stride, plane[p] + (size_t)y * stride[p],
                        MIN(stride[p], b->plane[p].stride));
+    return b;
+}
+
+/* ... and work() on it with an empty overlay list: the frame it returns goes back into the caller's planes or, a
+ * device-resident one, into *dev_frame_out.  Takes `b`. */
+static int blend_frame_work(hb_blend_object_t *blend, hb_buffer_t *b, uint8_t *const plane[3], const int stride[3],
+                            void *dev_frame, void **dev_frame_out)
+{
+    hb_buffer_list_t none;
+    memset(&none, 0, sizeof(none));
+    hb_buffer_t *out = blend->work(blend, b, &none, 0);
+    if (out == NULL) return -2;
+    if (dev_frame != NULL)
+    {
+        *dev_frame_out = out->storage;                 /* the buffer's reference goes to the caller */
+        out->storage = NULL;
+    }
+    else
+        for (int p = 0; p <= out->f.max_plane; p++)
+            for (int y = 0; y < out->plane[p].height; y++)
+                memcpy(plane[p] + (size_t)y * stride[p], out->plane[p].data + (size_t)y * out->plane[p].stride,
+                       MIN(stride[p], out->plane[p].stride));
+    hb_buffer_close(&out);
+    return 0;
+}
+
+int hbh_blend_run_ass(const void *proto, const void *set_images, int pix_fmt, int width, int height, int chroma_location,
+                      int overlay_fmt, uint8_t *const plane[3], const int stride[3], void *dev_frame, void **dev_frame_out,
+                      int n_lists, const int *n_images, const void *const *lists, const int crop[4])
+{
+    typedef int (*set_images_f)(hb_blend_object_t *, const hb_buffer_t *, const void *, int, const int *);
+    const set_images_f set = (set_images_f)set_images;
+    hb_blend_object_t blend = *(const hb_blend_object_t *)proto;
+    int rc = 0;
+    hb_buffer_t *b = blend_frame_in(pix_fmt, width, height, plane, stride, dev_frame);
+    if (b == NULL) return -1;
     if (blend.init(&blend, width, height, pix_fmt, chroma_location, 1, overlay_fmt) != 0)
     {
         hb_buffer_close(&b);
@@ -798,25 +827,64 @@ int hbh_blend_run_ass(const void *proto, const void *set_images, int pix_fmt, in
     }
     for (int k = 0; k < n_lists && rc == 0; k++)
         if (set(&blend, b, lists[k], n_images[k], crop) != 0) rc = -3;
-    if (rc == 0)
-    {
-        hb_buffer_t *out = blend.work(&blend, b, &none, 0);
-        b = NULL;
-        if (out == NULL) rc = -2;
-        else if (dev_frame != NULL)
-        {
-            *dev_frame_out = out->storage;                 /* the buffer's reference goes to the caller */
-            out->storage = NULL;
-        }
-        else
-            for (int p = 0; p <= out->f.max_plane; p++)
-                for (int y = 0; y < out->plane[p].height; y++)
-                    memcpy(plane[p] + (size_t)y * stride[p], out->plane[p].data + (size_t)y * out->plane[p].stride,
-                           MIN(stride[p], out->plane[p].stride));
-        hb_buffer_close(&out);
-    }
-    if (b != NULL) hb_buffer_close(&b);
+    if (rc == 0) rc = blend_frame_work(&blend, b, plane, stride, dev_frame, dev_frame_out);
+    else hb_buffer_close(&b);
     blend.close(&blend);
+    return rc;
+}
+
+int hbh_blend_run_bitmaps(const void *proto, const void *set_bitmaps, int pix_fmt, int width, int height, int chroma_location,
+                          int overlay_fmt, uint8_t *const plane[3], const int stride[3], void *dev_frame, void **dev_frame_out,
+                          int n_subs, const hbh_bitmap_t *subs, int n_calls, const int *n_listed, const int *const *lists,
+                          const int crop[4])
+{
+    typedef int (*set_bitmaps_f)(hb_blend_object_t *, const hb_buffer_t *, hb_buffer_t *const *, int, const int *);
+    const set_bitmaps_f set = (set_bitmaps_f)set_bitmaps;
+    hb_blend_object_t blend = *(const hb_blend_object_t *)proto;
+    int rc = 0, most = 1;
+    for (int k = 0; k < n_calls; k++) most = MAX(most, n_listed[k]);
+    hb_buffer_t **pool = calloc((size_t)MAX(n_subs, 1), sizeof(*pool)), **list = calloc((size_t)most, sizeof(*list));
+    hb_buffer_t *b = blend_frame_in(pix_fmt, width, height, plane, stride, dev_frame);
+    if (pool == NULL || list == NULL || b == NULL) rc = -1;
+    /* the decoded subtitles as decpgssub / decvobsub hand them on (hbh_chain_push_subtitle): sub_list's buffers */
+    for (int i = 0; i < n_subs && rc == 0; i++)
+    {
+        const hbh_overlay_t *ov = &subs[i].ov;
+        hb_buffer_t *o = pool[i] = hb_frame_buffer_init(AV_PIX_FMT_YUVA444P, ov->width, ov->height);
+        if (o == NULL) { rc = -1; break; }
+        for (int p = 0; p <= o->f.max_plane; p++)
+            for (int y = 0; y < o->plane[p].height; y++)
+                memcpy(o->plane[p].data + (size_t)y * o->plane[p].stride, ov->plane[p] + (size_t)y * ov->stride[p], o->plane[p].width);
+        o->f.x = ov->x;
+        o->f.y = ov->y;
+        o->f.window_width = subs[i].window_width;
+        o->f.window_height = subs[i].window_height;
+        o->s.start = subs[i].start;
+    }
+    if (rc == 0 && blend.init(&blend, width, height, pix_fmt, chroma_location, 1, overlay_fmt) != 0) rc = -1;
+    if (rc == -1)
+    {
+        for (int i = 0; pool != NULL && i < n_subs; i++) hb_buffer_close(&pool[i]);
+        if (b != NULL) hb_buffer_close(&b);
+        free(pool);
+        free(list);
+        return rc;
+    }
+    for (int k = 0; k < n_calls && rc == 0; k++)
+    {
+        for (int i = 0; i < n_listed[k] && rc == 0; i++)
+        {
+            if (lists[k][i] < 0 || lists[k][i] >= n_subs) rc = -1;
+            else list[i] = pool[lists[k][i]];
+        }
+        if (rc == 0 && set(&blend, b, list, n_listed[k], crop) != 0) rc = -3;
+    }
+    if (rc == 0) rc = blend_frame_work(&blend, b, plane, stride, dev_frame, dev_frame_out);
+    else hb_buffer_close(&b);
+    blend.close(&blend);
+    for (int i = 0; i < n_subs; i++) hb_buffer_close(&pool[i]);
+    free(pool);
+    free(list);
     return rc;
 }
 

@@ -94,6 +94,23 @@ int hbh_blend_run_ass(const void *proto, const void *set_images, int pix_fmt, in
                       int overlay_fmt, uint8_t *const plane[3], const int stride[3], void *dev_frame, void **dev_frame_out,
                       int n_lists, const int *n_images, const void *const *lists, const int crop[4]);
 
+/* The same for bitmap subtitles, playing render_vobsubs / render_pgs_subs (rendersub.c:381-414, :1016-1067) with a compositor
+ * that scales and places the decoded bitmaps itself.  `subs` are the n_subs decoded subtitles of the track - each becomes one
+ * buffer, as in rendersub's sub_list, so that a subtitle listed by several calls is the same buffer in all of them.  Call k
+ * hands set_bitmaps(blend, frame, buffers, n_listed[k], crop) the buffers lists[k][0 .. n_listed[k]) index into `subs` - the
+ * address of hb_blend_hip_set_bitmaps - in order; then work() runs once with an empty overlay list.  dev_frame / dev_frame_out
+ * as above. */
+typedef struct
+{
+    hbh_overlay_t ov;                     /* the bitmap, 4:4:4, at (x, y) of its canvas */
+    int           window_width, window_height;
+    int64_t       start;
+} hbh_bitmap_t;
+int hbh_blend_run_bitmaps(const void *proto, const void *set_bitmaps, int pix_fmt, int width, int height, int chroma_location,
+                          int overlay_fmt, uint8_t *const plane[3], const int stride[3], void *dev_frame, void **dev_frame_out,
+                          int n_subs, const hbh_bitmap_t *subs, int n_calls, const int *n_listed, const int *const *lists,
+                          const int crop[4]);
+
 /* a decoded bitmap subtitle for the job's burn-in track (see hbh_set_job_subtitle): shown from start to stop (90 kHz, stop < 0:
  * until the next one) on a window_w x window_h canvas */
 int hbh_chain_push_subtitle(hbh_chain_t *c, const hbh_overlay_t *ov, int64_t start, int64_t stop, int window_w, int window_h);

@@ -148,6 +148,13 @@ extern hb_blend_object_t  hb_blend_hip;
  * on the GPU `frame` lives on (render_ssa_subs, rendersub.c:623-665; INTEGRATION.md has the hook).  HBHIP_OK or HBHIP_ERR_*. */
 int hb_blend_hip_set_ass_images(hb_blend_object_t *blend, const hb_buffer_t *frame, const hbhip_ass_image *img, int n,
                                 const int crop[4]);
+/* bitmap subtitles: the active decoded bitmaps of the frame (render_vobsubs / render_pgs_subs, rendersub.c:381-414, :1016-1067)
+ * as the overlay list of a `blend` that is hb_blend_hip - scaled and placed as scale_subtitle (:242-377) would, on the GPU
+ * `frame` lives on, once per subtitle (INTEGRATION.md has the hook).  A buffer is known by its address and s.start:
+ * rendersub owns the buffers of its sub_list for as long as it lists them.  HBHIP_OK or HBHIP_ERR_*; after a failure the
+ * device's list is empty and the caller takes scale_subtitle. */
+int hb_blend_hip_set_bitmaps(hb_blend_object_t *blend, const hb_buffer_t *frame, hb_buffer_t *const *subs, int n,
+                             const int crop[4]);
 /* the frame-difference metric object vfr.c can use in place of hb_motion_metric (motion_metric.c:306-312) */
 extern hb_motion_metric_object_t hb_motion_metric_hip;
 extern hb_filter_object_t hb_filter_decomb_hip;

@@ -574,8 +574,32 @@ int  hbhip_blend_apply_biplanar(hbhip_blend *b, const hbhip_host_biplanar *frame
 typedef struct hbhip_ass_image { const uint8_t *bitmap; int stride, w, h, dst_x, dst_y;
                                  uint8_t y, cb, cr, a; } hbhip_ass_image;
 int  hbhip_blend_set_ass_images(hbhip_blend *b, const hbhip_ass_image *img, int n, int crop_left, int crop_top);
-/* test hooks: how many overlays the object holds, and overlay `index` of its device store read back - xywh = its position and
- * size, plane / stride = where the Y, Cb, Cr and alpha planes go (plane == NULL: the geometry only) */
+/* Bitmap subtitles (PGS, DVB, VOBSUB).  What scale_subtitle (rendersub.c:242-377) makes of each decoded bitmap for a frame of
+ * the object's size, for the whole list at once: factor = max(width / window_width, height / window_height) in double
+ * (:249-266), used when it is more than 1 % off 1 (:267); size and position (int)(value * factor) (:273-283); the placement
+ * rule of :311-375 with crop = job->crop (top, bottom, left, right).  The scaling itself - the reference's
+ * SWS_LANCZOS | SWS_ACCURATE_RND context, run per frame - is one kernel per bitmap (csrc/bitmap_scale.hip), and it runs once
+ * per subtitle: the object keeps what it has made under the caller's `key`.  A key seen before with the same source and
+ * scaled size costs no copy and no launch; keys a call does not name are dropped.  Replaces the object's overlay list, in list
+ * order; entries without an area (PGS "clear" packets, :1043-1055) are skipped, n == 0 empties the list.  The bitmaps are
+ * consumed when this returns.  PARITY UNPINNED: libswscale's arithmetic as oracle/alias_oracle.c:orc_cropscale_plane_sws
+ * restates it.  For objects of hbhip_blend_create and of hbhip_blend_create_biplanar.  HBHIP_ERR_UNSUPPORTED: an object whose
+ * overlays are not 4:4:4 (:418, :1073), a factor outside [0.25, 4], a bitmap narrower or lower than 8 samples that has to
+ * be scaled (libswscale clamps its tap count there); HBHIP_ERR_ARG: a negative size, a stride below the width, a missing
+ * plane.  After any failure the list is empty. */
+typedef struct hbhip_bitmap_sub
+{
+    const uint8_t *plane[4];          /* Y, Cb, Cr, alpha: 8-bit 4:4:4 (host memory) */
+    int            stride[4];
+    int            x, y, width, height;               /* hb_buffer_t.f.x / .y / .width / .height */
+    int            window_width, window_height;       /* f.window_*: the canvas; <= 0: none */
+    uint64_t       key;                               /* the caller's identity of this subtitle */
+} hbhip_bitmap_sub;
+int  hbhip_blend_set_bitmaps(hbhip_blend *b, const hbhip_bitmap_sub *sub, int n, const int crop[4]);
+/* test hooks: scale launches, bitmaps uploaded and cache hits of hbhip_blend_set_bitmaps since the object was made; how many
+ * overlays the object holds, and overlay `index` of its device store read back - xywh = its position and size, plane / stride
+ * = where the Y, Cb, Cr and alpha planes go (plane == NULL: the geometry only) */
+int  hbhip_blend_debug_bitmap_stats(hbhip_blend *b, int64_t *scaled, int64_t *uploaded, int64_t *hits);
 int  hbhip_blend_debug_overlay_count(hbhip_blend *b);
 int  hbhip_blend_debug_get_overlay(hbhip_blend *b, int index, uint8_t *const plane[4], const int stride[4], int xywh[4]);
 
