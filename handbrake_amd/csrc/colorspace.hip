@@ -5,7 +5,9 @@
 //     -> zscale=primaries:transfer:matrix:range -> format=<pix_fmt>  (:170-193)
 // which hb_avfilter_combine merges into HB_FILTER_AVFILTER; the arithmetic is zimg's and
 // vf_tonemap.c's (not in the reference tree: "parity unpinned", pinned to oracle/colorspace_oracle.c,
-// whose header lists what is restated and what is simplified).
+// whose header lists what is restated and what is simplified).  The matrices that are no plain Kr / Kb matrix -
+// bt2020c, chroma-derived-nc / -c, ictcp, which colorspace.c:108-112, 180-182 hands to zscale like any other - have no
+// oracle: they are held to tests/colour_model_wide.py, whose table lists the choices made from memory of zimg.
 //
 // MI355X shape: the CPU graph makes five passes over float planes (to float, chroma to 4:4:4,
 // colour conversion, chroma back to 4:2:0, to integer).  Here one launch does all of it for up to 16 frames: a
@@ -18,6 +20,7 @@
 
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 namespace {
@@ -33,6 +36,18 @@ struct CsPlan
     float tm_param, tm_peak, tm_a, tm_b, tm_c;
     int   tc_in, tc_out;                 // transfer classes
     float lin_scale, gam_scale;          // PQ / HLG: display-light scale after the EOTF / before its inverse
+};
+
+// The constant-luminance (bt2020c, chroma-derived-c) and ICtCp forms: what their instantiations take besides the plan.
+// Both keep three transfer functions in and three out; what enters them is (R', Y', B') or L'M'S', what leaves them
+// (R, Yl, B) or LMS.  m_pre takes that to linear RGB where tone mapping sits between it and the gamut matrix; everywhere
+// else, and on the output side always, the 3 x 3 is folded into m_gamut on the host.
+struct CsPlanWide : CsPlan
+{
+    int   cl_in, cl_out, pre;            // CL chroma scale on the way in / out; m_pre is a stage of its own
+    float m_pre[3][3];
+    float cl_mul[4];                     // 2 Nb, 2 Pb, 2 Nr, 2 Pr: Cb, Cr -> B' - Y', R' - Y'
+    float cl_rcp[4];                     // their reciprocals (rounded once, on the host)
 };
 
 struct CsBatch
@@ -254,6 +269,72 @@ __device__ __forceinline__ void convert_px(const CsPlan &p, float y, float u, fl
         out[i] = row3(p.m_out[i], g[0], g[1], g[2]);
 }
 
+// The constant-luminance and ICtCp instantiation (always through linear light).  CL in: B' = Y' + Cb 2 (Cb < 0 ? Nb : Pb),
+// R' likewise, and (R', Y', B') enter the transfer functions; CL out: Cb = (B' - Y') / (2 (B' - Y' < 0 ? Nb : Pb)) as a
+// multiplication by the host's reciprocal.  ICtCp: m_in / m_out hold BT.2100's matrix and its inverse.  Every branch
+// below is on a plan field: uniform over the launch.
+__device__ __forceinline__ void convert_px_wide(const CsPlanWide &p, float y, float u, float v, float out[3])
+{
+    float c[3], g[3];
+    if (p.cl_in)
+    {
+        c[0] = __fmaf_rn(v, v < 0.0f ? p.cl_mul[2] : p.cl_mul[3], y);
+        c[1] = y;
+        c[2] = __fmaf_rn(u, u < 0.0f ? p.cl_mul[0] : p.cl_mul[1], y);
+    }
+    else
+    {
+#pragma unroll
+        for (int i = 0; i < 3; i++) c[i] = row3(p.m_in[i], y, u, v);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+        c[i] = to_linear_dev(p.tc_in, c[i]) * p.lin_scale;
+    if (p.pre)
+    {
+#pragma unroll
+        for (int i = 0; i < 3; i++) g[i] = row3(p.m_pre[i], c[0], c[1], c[2]);
+#pragma unroll
+        for (int i = 0; i < 3; i++) c[i] = g[i];
+    }
+    if (p.tonemap >= 0)
+    {
+        float sig = c[0] > c[1] ? c[0] : c[1];
+        sig = sig > c[2] ? sig : c[2];
+        sig = sig > 1e-6f ? sig : 1e-6f;
+        const float k = __fdiv_rn(tonemap_sig(p, sig), sig);
+#pragma unroll
+        for (int i = 0; i < 3; i++) c[i] *= k;
+    }
+    if (p.gamut)
+    {
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+            g[i] = row3(p.m_gamut[i], c[0], c[1], c[2]);
+    }
+    else
+    {
+#pragma unroll
+        for (int i = 0; i < 3; i++) g[i] = c[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 3; i++)
+        g[i] = to_gamma_dev(p.tc_out, g[i] * p.gam_scale);
+    if (p.cl_out)
+    {
+        const float db = g[2] - g[1], dr = g[0] - g[1];
+        out[0] = g[1];
+        out[1] = db * (db < 0.0f ? p.cl_rcp[0] : p.cl_rcp[1]);
+        out[2] = dr * (dr < 0.0f ? p.cl_rcp[2] : p.cl_rcp[3]);
+    }
+    else
+    {
+#pragma unroll
+        for (int i = 0; i < 3; i++)
+            out[i] = row3(p.m_out[i], g[0], g[1], g[2]);
+    }
+}
+
 __device__ __forceinline__ int quant(float v, float mul, float off, int vmax)
 {
     float t = __fmaf_rn(v, mul, off);        // +-inf / NaN (out-of-gamut input beyond a transfer function's pole): to the clip limits
@@ -271,8 +352,12 @@ __device__ __forceinline__ float samp(const uint8_t *row, int x) { return (float
 // SUBW / SUBH: log2 of the chroma subsampling.  Region = CS_RW x CS_RH luma positions starting HX columns left of and HY
 // rows above the tile; thread (gx, gr) converts the four positions 4 gx .. 4 gx + 3 of region rows gr and gr + 16.  The
 // samples of both rows are fetched before the first is converted (one memory latency per workgroup, not two).
-template <typename PIX, int SUBW, int SUBH, bool LINEAR>
-__global__ __launch_bounds__(256) void colorspace_kernel(CsBatch a, CsPlan p)
+// PLAN = CsPlanWide: the constant-luminance / ICtCp instantiation (LINEAR always).  Left alone it takes 87 VGPRs where
+// chroma is subsampled horizontally, five waves a SIMD against its LINEAR sibling's six; held to six it spills four to
+// six VGPRs and is 4 % faster (profiles/colorspace_wide.json).  The other instantiations compile as without the hint.
+template <typename PIX, int SUBW, int SUBH, bool LINEAR, typename PLAN = CsPlan>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(std::is_same<PLAN, CsPlanWide>::value ? 6 : 1)))
+void colorspace_kernel(CsBatch a, PLAN p)
 {
     constexpr int HX = SUBW ? 4 : 0, HY = SUBH ? 1 : 0, TW = CS_RW - HX, TH = CS_RH - 2 * HY;
     constexpr bool LDS = SUBW || SUBH;
@@ -417,7 +502,8 @@ __global__ __launch_bounds__(256) void colorspace_kernel(CsBatch a, CsPlan p)
         for (int j = 0; j < 4; j++)
         {
             float o[3];
-            convert_px<LINEAR>(p, yf[j], uf[j], vf[j], o);
+            if constexpr (std::is_same<PLAN, CsPlanWide>::value) convert_px_wide(p, yf[j], uf[j], vf[j], o);
+            else convert_px<LINEAR>(p, yf[j], uf[j], vf[j], o);
             oy[j] = o[0]; ou[j] = o[1]; ov[j] = o[2];
         }
         if (LDS)
@@ -536,6 +622,21 @@ bool luma_coefficients(int id, double &kr, double &kb)
     return false;
 }
 
+// the matrices that are no plain Kr / Kb matrix: bt2020c (10) and chroma-derived-c (13) are constant luminance, 14 is ICtCp
+enum { CS_PLAIN = 0, CS_CL, CS_ICTCP };
+int matrix_form(int id) { return id == 10 || id == 13 ? CS_CL : id == 14 ? CS_ICTCP : CS_PLAIN; }
+
+// BT.2020 table 4's chroma scales Pb, Nb, Pr, Nr: 1 - OETF(Kb), OETF(1 - Kb), 1 - OETF(Kr), OETF(1 - Kr) with the
+// exact-alpha OETF; fixed, whatever transfer the stream signals
+constexpr double CL_PB = 0.7909854, CL_NB = 0.9701716, CL_PR = 0.4969147, CL_NR = 0.8591209;
+// BT.2100 tables 7 and 8: linear RGB -> LMS, and L'M'S' -> I Ct Cp in its PQ and HLG form
+const double ICTCP_LMS[3][3] = { { 1688 / 4096.0, 2146 / 4096.0, 262 / 4096.0 }, { 683 / 4096.0, 2951 / 4096.0, 462 / 4096.0 },
+                                 { 99 / 4096.0, 309 / 4096.0, 3688 / 4096.0 } };
+const double ICTCP_PQ[3][3] = { { 2048 / 4096.0, 2048 / 4096.0, 0.0 }, { 6610 / 4096.0, -13613 / 4096.0, 7003 / 4096.0 },
+                                { 17933 / 4096.0, -17390 / 4096.0, -543 / 4096.0 } };
+const double ICTCP_HLG[3][3] = { { 2048 / 4096.0, 2048 / 4096.0, 0.0 }, { 3625 / 4096.0, -7465 / 4096.0, 3840 / 4096.0 },
+                                 { 9500 / 4096.0, -9212 / 4096.0, -288 / 4096.0 } };
+
 // chromaticities (xr yr xg yg xb yb xw yw) of an AVCOL_PRI_* / HB_COLR_PRI_* id
 bool chromaticities(int id, double xy[8])
 {
@@ -576,6 +677,27 @@ void rgb_to_xyz(double m[3][3], const double xy[8])
         for (int r = 0; r < 3; r++)
             m[r][i] = p[r][i] * s;
     }
+}
+
+// (Kr, Kb) of one side of the conversion, or false where that side's matrix has no defined result with its primaries
+// and transfer (zimg has no path): chroma-derived-nc (12) takes them from the primaries - the standard's rounded pair
+// for BT.709 / BT.2020, otherwise the Y row of RGB -> XYZ; the constant-luminance pair (10, 13) needs BT.2020 primaries,
+// ICtCp (14) BT.2020 primaries and PQ or HLG
+bool side_coefficients(int matrix, int prim, int transfer, double &kr, double &kb)
+{
+    if (matrix == 12)
+    {
+        double xy[8], m[3][3];
+        if (prim == 1 || prim == 9) return luma_coefficients(prim, kr, kb);
+        if (!chromaticities(primaries_class(prim), xy)) return false;
+        rgb_to_xyz(m, xy);
+        kr = m[1][0]; kb = m[1][2];
+        return true;
+    }
+    if (matrix_form(matrix) == CS_PLAIN) return luma_coefficients(matrix, kr, kb);
+    if (prim != 9) return false;
+    if (matrix == 14 && transfer != 16 && transfer != 18) return false;
+    return luma_coefficients(9, kr, kb);
 }
 
 void gamut_matrix(double g[3][3], const double in_xy[8], const double out_xy[8])
@@ -627,7 +749,10 @@ public:
         const int s = depth - 8;
         plan.vmax = (1 << depth) - 1;
         double kr_i, kb_i, kr_o, kb_o;
-        if (!luma_coefficients(par.in_matrix, kr_i, kb_i) || !luma_coefficients(par.out_matrix, kr_o, kb_o)) return HBHIP_ERR_UNSUPPORTED;
+        if (!side_coefficients(par.in_matrix, par.in_prim, par.in_transfer, kr_i, kb_i) ||
+            !side_coefficients(par.out_matrix, par.out_prim, par.out_transfer, kr_o, kb_o)) return HBHIP_ERR_UNSUPPORTED;
+        const int form_i = matrix_form(par.in_matrix), form_o = matrix_form(par.out_matrix);
+        wide = form_i != CS_PLAIN || form_o != CS_PLAIN;
         if (par.in_range < 1 || par.in_range > 2 || par.out_range < 1 || par.out_range > 2) return HBHIP_ERR_UNSUPPORTED;
         const bool lim_i = par.in_range == 1, lim_o = par.out_range == 1;
         plan.yoff_in = lim_i ? (float)(16 << s) : 0.f;
@@ -651,9 +776,13 @@ public:
         static const double ycgco_o[3][3] = { { 0.25, 0.5, 0.25 }, { -0.25, 0.5, -0.25 }, { 0.5, 0.0, -0.5 } };
         if (par.in_matrix == 8) memcpy(mi, ycgco_i, sizeof(mi));
         if (par.out_matrix == 8) memcpy(mo, ycgco_o, sizeof(mo));
+        // ICtCp: I Ct Cp in the Y, Cb, Cr slots; what m_in yields and m_out takes is L'M'S' (CL uses neither matrix)
+        if (form_i == CS_ICTCP) inv3(mi, par.in_transfer == 16 ? ICTCP_PQ : ICTCP_HLG);
+        if (form_o == CS_ICTCP) memcpy(mo, par.out_transfer == 16 ? ICTCP_PQ : ICTCP_HLG, sizeof(mo));
         const int tc_i = transfer_class(par.in_transfer), tc_o = transfer_class(par.out_transfer);
         const int pc_i = primaries_class(par.in_prim), pc_o = primaries_class(par.out_prim);
-        plan.need_linear = tc_i != tc_o || pc_i != pc_o;
+        // CL and ICtCp meet the other matrices only in linear light
+        plan.need_linear = tc_i != tc_o || pc_i != pc_o || wide;
         plan.tonemap = -1;
         double md[3][3];
         mul3(md, mo, mi);
@@ -667,9 +796,10 @@ public:
         if (!plan.need_linear) return HBHIP_OK;
 
         plan.gamut = pc_i != pc_o;
+        double g[3][3] = { { 1.0, 0.0, 0.0 }, { 0.0, 1.0, 0.0 }, { 0.0, 0.0, 1.0 } };
         if (plan.gamut)
         {
-            double xi[8], xo[8], g[3][3];
+            double xi[8], xo[8];
             if (!chromaticities(pc_i, xi) || !chromaticities(pc_o, xo)) return HBHIP_ERR_UNSUPPORTED;
             gamut_matrix(g, xi, xo);
             for (int i = 0; i < 3; i++)
@@ -715,7 +845,38 @@ public:
             plan.tm_param = param;
             plan.tm_peak = (float)peak;
         }
+        if (wide) fold_wide(form_i, form_o, kr_i, kb_i, kr_o, kb_o, g);
         return HBHIP_OK;
+    }
+    // The 3 x 3 either side of linear RGB, multiplied in double: (R, Yl, B) <-> (R, G, B) for CL, BT.2100's LMS matrix
+    // for ICtCp.  The output side's always joins the gamut matrix g; the input side's too, unless the tone mapping's
+    // max(R, G, B) sits between them.
+    void fold_wide(int form_i, int form_o, double kr_i, double kb_i, double kr_o, double kb_o, double g[3][3])
+    {
+        const double cl[4] = { 2.0 * CL_NB, 2.0 * CL_PB, 2.0 * CL_NR, 2.0 * CL_PR };
+        for (int i = 0; i < 4; i++) { plan.cl_mul[i] = (float)cl[i]; plan.cl_rcp[i] = (float)(1.0 / cl[i]); }
+        plan.cl_in = form_i == CS_CL;
+        plan.cl_out = form_o == CS_CL;
+        if (form_o != CS_PLAIN)
+        {
+            const double yl[3][3] = { { 1.0, 0.0, 0.0 }, { kr_o, 1.0 - kr_o - kb_o, kb_o }, { 0.0, 0.0, 1.0 } };
+            mul3(g, form_o == CS_CL ? yl : ICTCP_LMS, g);
+        }
+        if (form_i != CS_PLAIN)
+        {
+            const double yl[3][3] = { { 1.0, 0.0, 0.0 }, { kr_i, 1.0 - kr_i - kb_i, kb_i }, { 0.0, 0.0, 1.0 } };
+            double pre[3][3];
+            inv3(pre, form_i == CS_CL ? yl : ICTCP_LMS);
+            plan.pre = plan.tonemap >= 0;
+            if (!plan.pre) mul3(g, g, pre);
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++)
+                    plan.m_pre[i][j] = (float)pre[i][j];
+        }
+        plan.gamut = plan.gamut || form_o != CS_PLAIN || !plan.pre;
+        for (int i = 0; i < 3; i++)
+            for (int j = 0; j < 3; j++)
+                plan.m_gamut[i][j] = (float)g[i][j];
     }
     template <typename PIX>
     void launch(const CsBatch &B, int nf)
@@ -723,19 +884,27 @@ public:
         const int sw = in_geo.log2_cw, sh = in_geo.log2_ch;
         const int tw = CS_RW - (sw ? 4 : 0), th = CS_RH - (sh ? 2 : 0);
         const dim3 grid(hbhip_grid_x((B.w + tw - 1) / tw), (B.h + th - 1) / th, nf);
-        if (plan.need_linear)
+        const CsPlan &base = plan;
+        if (wide)
         {
-            if (sw && sh)       HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 1, true>), grid, dim3(256), 0, B, plan);
-            else if (sw)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 0, true>), grid, dim3(256), 0, B, plan);
-            else if (sh)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 1, true>), grid, dim3(256), 0, B, plan);
-            else                HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 0, true>), grid, dim3(256), 0, B, plan);
+            if (sw && sh)       HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 1, true, CsPlanWide>), grid, dim3(256), 0, B, plan);
+            else if (sw)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 0, true, CsPlanWide>), grid, dim3(256), 0, B, plan);
+            else if (sh)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 1, true, CsPlanWide>), grid, dim3(256), 0, B, plan);
+            else                HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 0, true, CsPlanWide>), grid, dim3(256), 0, B, plan);
+        }
+        else if (plan.need_linear)
+        {
+            if (sw && sh)       HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 1, true>), grid, dim3(256), 0, B, base);
+            else if (sw)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 0, true>), grid, dim3(256), 0, B, base);
+            else if (sh)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 1, true>), grid, dim3(256), 0, B, base);
+            else                HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 0, true>), grid, dim3(256), 0, B, base);
         }
         else
         {
-            if (sw && sh)       HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 1, false>), grid, dim3(256), 0, B, plan);
-            else if (sw)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 0, false>), grid, dim3(256), 0, B, plan);
-            else if (sh)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 1, false>), grid, dim3(256), 0, B, plan);
-            else                HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 0, false>), grid, dim3(256), 0, B, plan);
+            if (sw && sh)       HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 1, false>), grid, dim3(256), 0, B, base);
+            else if (sw)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 0, false>), grid, dim3(256), 0, B, base);
+            else if (sh)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 1, false>), grid, dim3(256), 0, B, base);
+            else                HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 0, false>), grid, dim3(256), 0, B, base);
         }
     }
     // the frames of a batch (a chain batch, a device-resident batch) in one launch where their pitches agree
@@ -749,7 +918,8 @@ public:
         });
     }
     hbhip_colorspace_params par;
-    CsPlan plan;
+    CsPlanWide plan;                     // the wide fields only where wide is set
+    bool wide = false;
 };
 
 } // namespace

@@ -573,7 +573,9 @@ TONEMAPS = {"none": 0, "linear": 1, "gamma": 2, "clip": 3, "reinhard": 4, "hable
 
 def colorspace_device_filter(ctx, width, height, src, dst, tonemap="hable", param=float("nan"), desat=0.0,
                              npl=100.0, peak=10.0, depth=8, log2_cw=1, log2_ch=1):
-    """src / dst = (primaries, transfer, matrix, range) in AVCOL_* numbers, range 1 = tv, 2 = pc."""
+    """src / dst = (primaries, transfer, matrix, range) in AVCOL_* numbers, range 1 = tv, 2 = pc.  Matrix 12
+    (chroma-derived-nc) on primaries with known chromaticities, 10 / 13 (bt2020c, chroma-derived-c) on BT.2020
+    primaries and 14 (ICtCp) on BT.2020 primaries with PQ or HLG are accepted on either side."""
     p = ColorspaceParams(*src, *dst, TONEMAPS[tonemap], param, desat, npl, peak)
     return _create("hbhip_colorspace_create", ctx,
                    [C.c_void_p, C.POINTER(ColorspaceParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],

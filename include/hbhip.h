@@ -500,7 +500,11 @@ int hbhip_format_scaled_create(hbhip_ctx *ctx, int width, int height, int src_de
  * when the source transfer is SMPTE 2084 or ARIB STD-B67 and the transfer changes.  Colour ids
  * are the AVCOL_* = HB_COLR_* numbers (common.h), range 1 = tv, 2 = pc; tonemap ids are
  * vf_tonemap's.  Arithmetic pinned to oracle/colorspace_oracle.c only (parity unpinned).
- * 8/10/12-bit, 4:2:0 / 4:2:2 / 4:4:4.  HBHIP_ERR_UNSUPPORTED for conversions outside its tables. */
+ * 8/10/12-bit, 4:2:0 / 4:2:2 / 4:4:4.  HBHIP_ERR_UNSUPPORTED for conversions outside its tables.
+ * Matrix ids beyond the plain Kr / Kb ones, on either side: 12 (chroma-derived-nc: Kr / Kb of that side's primaries),
+ * 10 and 13 (bt2020c, chroma-derived-c: constant luminance, BT.2020 primaries only) and 14 (ICtCp: BT.2020 primaries
+ * with SMPTE 2084 or ARIB STD-B67 only); 10, 13 and 14 always convert through linear light.  These have no oracle:
+ * arithmetic pinned to tests/colour_model_wide.py within a code. */
 enum { HBHIP_TONEMAP_NONE = 0, HBHIP_TONEMAP_LINEAR = 1, HBHIP_TONEMAP_GAMMA = 2, HBHIP_TONEMAP_CLIP = 3,
        HBHIP_TONEMAP_REINHARD = 4, HBHIP_TONEMAP_HABLE = 5, HBHIP_TONEMAP_MOBIUS = 6 };
 typedef struct hbhip_colorspace_params
