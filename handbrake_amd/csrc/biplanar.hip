@@ -4,6 +4,9 @@
 //   bi_split_kernel           staging -> the three planes of a planar frame (NV12: luma copied, chroma de-interleaved;
 //                             P010LE: every sample >> 6 into a 10-bit planar frame)
 //   bi_merge_kernel           the inverse (P010LE: every sample << 6, low six bits zero)
+//   bi_surface_split_kernel / bi_surface_merge_kernel
+//                             the same pair between a device surface - a pitch of its own per plane, the planes where their
+//                             maker put them - and the frame, without a staging buffer (below)
 //   blend_bi_same_kernel      blend8onbi8 :606-691 / blend8onbi1x :693-786
 //   blend_bi_subsample_kernel blend_subsample_8onbi8 :330-423 / blend_subsample_8onbi1x :142-234   (blend_body.h)
 //
@@ -109,6 +112,82 @@ __global__ __launch_bounds__(256) void bi_merge_kernel(BiRepack a)
     *reinterpret_cast<uint4 *>(a.stage + (size_t)a.luma_units * 16 + (size_t)row * a.spitch1 + (size_t)col * 16) = v;
 }
 
+// The same repack between a planar frame and a device surface (hbhip_surface): a picture whose two planes have a pitch of
+// their own each (any multiple of 16 that holds the row), padded rows behind them, and need not lie back to back.  Rows on
+// blockIdx.y - the luma rows, then the chroma rows - and one 16-byte unit of the interleaved side per lane along x: no
+// division, and both sides are addressed by row and pitch.
+//   split   writes EVERY unit of the frame's row, up to the frame's pitch: from the surface's row as far as the surface's
+//           pitch reaches (its padding travels, as a host picture's does), zero beyond - the rule of bi_split_kernel.
+//           Reads stay inside pitch * rows of either surface plane.
+//   merge   writes [0, align16(row bytes)) of the surface's row and nothing else of the surface: the rest of the pitch, the
+//           padded rows and whatever lies between the planes are not this library's.
+struct BiSurface
+{
+    uint8_t *splane[2];              // the surface
+    uint8_t *plane[3];               // the planar frame
+    int spitch[2];
+    int fpitch[2];                   // of the frame's luma plane / of its chroma planes
+    unsigned rows0;                  // luma rows; the grid's y runs over them and the chroma rows behind them
+    unsigned units[2];               // lanes with work in a luma / chroma row (split: the frame's row, merge: the samples')
+    unsigned sunits[2];              // split: units the surface's row holds, spitch / 16
+};
+
+template <typename PIX>
+__global__ __launch_bounds__(256) void bi_surface_split_kernel(BiSurface a)
+{
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (blockIdx.y < a.rows0)
+    {
+        if (u >= a.units[0]) return;
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (u < a.sunits[0])
+        {
+            v = *reinterpret_cast<const uint4 *>(a.splane[0] + (size_t)blockIdx.y * a.spitch[0] + (size_t)u * 16);
+            v.x = to_planar<PIX>(v.x); v.y = to_planar<PIX>(v.y); v.z = to_planar<PIX>(v.z); v.w = to_planar<PIX>(v.w);
+        }
+        *reinterpret_cast<uint4 *>(a.plane[0] + (size_t)blockIdx.y * a.fpitch[0] + (size_t)u * 16) = v;
+        return;
+    }
+    if (u >= a.units[1]) return;
+    const unsigned row = blockIdx.y - a.rows0;
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (u < a.sunits[1])
+        v = *reinterpret_cast<const uint4 *>(a.splane[1] + (size_t)row * a.spitch[1] + (size_t)u * 16);
+    uint2 cb, cr;
+    cb.x = to_planar<PIX>(__builtin_amdgcn_perm(v.y, v.x, Sel<PIX>::even));
+    cb.y = to_planar<PIX>(__builtin_amdgcn_perm(v.w, v.z, Sel<PIX>::even));
+    cr.x = to_planar<PIX>(__builtin_amdgcn_perm(v.y, v.x, Sel<PIX>::odd));
+    cr.y = to_planar<PIX>(__builtin_amdgcn_perm(v.w, v.z, Sel<PIX>::odd));
+    const size_t at = (size_t)row * a.fpitch[1] + (size_t)u * 8;
+    *reinterpret_cast<uint2 *>(a.plane[1] + at) = cb;
+    *reinterpret_cast<uint2 *>(a.plane[2] + at) = cr;
+}
+
+template <typename PIX>
+__global__ __launch_bounds__(256) void bi_surface_merge_kernel(BiSurface a)
+{
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    if (blockIdx.y < a.rows0)
+    {
+        if (u >= a.units[0]) return;
+        uint4 v = *reinterpret_cast<const uint4 *>(a.plane[0] + (size_t)blockIdx.y * a.fpitch[0] + (size_t)u * 16);
+        v.x = to_biplanar<PIX>(v.x); v.y = to_biplanar<PIX>(v.y); v.z = to_biplanar<PIX>(v.z); v.w = to_biplanar<PIX>(v.w);
+        *reinterpret_cast<uint4 *>(a.splane[0] + (size_t)blockIdx.y * a.spitch[0] + (size_t)u * 16) = v;
+        return;
+    }
+    if (u >= a.units[1]) return;
+    const unsigned row = blockIdx.y - a.rows0;
+    const size_t at = (size_t)row * a.fpitch[1] + (size_t)u * 8;
+    const uint2 cb = *reinterpret_cast<const uint2 *>(a.plane[1] + at);
+    const uint2 cr = *reinterpret_cast<const uint2 *>(a.plane[2] + at);
+    uint4 v;
+    v.x = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.x, cb.x, Sel<PIX>::zip_lo));
+    v.y = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.x, cb.x, Sel<PIX>::zip_hi));
+    v.z = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.y, cb.y, Sel<PIX>::zip_lo));
+    v.w = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.y, cb.y, Sel<PIX>::zip_hi));
+    *reinterpret_cast<uint4 *>(a.splane[1] + (size_t)row * a.spitch[1] + (size_t)u * 16) = v;
+}
+
 template <typename PIX>
 __global__ __launch_bounds__(256) void blend_bi_same_kernel(BlendArgs a, OverlayGroup G)
 {
@@ -163,6 +242,51 @@ int hbhip_bi_repack_launch(hbhip_ctx *ctx, hipStream_t stream, bool merge, uint8
     {
         if (p.bps == 1) HBHIP_LAUNCH_ON(ctx, stream, "bi_split", bi_split_kernel<uint8_t>, grid, blk, 0, a);
         else            HBHIP_LAUNCH_ON(ctx, stream, "bi_split", bi_split_kernel<uint16_t>, grid, blk, 0, a);
+    }
+    HBHIP_CHECK(ctx, hipGetLastError());
+    return HBHIP_OK;
+}
+
+int hbhip_bi_surface_launch(hbhip_ctx *ctx, hipStream_t stream, bool merge, const hbhip_surface *s, const hbhip_frame *fr)
+{
+    BiLayout l;
+    hbhip_bi_layout(fr->width, fr->height, fr->depth, &l);
+    const DevPicture &p = fr->pic;
+    // what the kernels' addressing rests on: a frame as hbhip_frame_alloc lays it out, a surface as hbhip_surface_wrap admits it
+    if (s->width != fr->width || s->height != fr->height || s->depth != fr->depth || p.pitch[1] != p.pitch[2] ||
+        (p.pitch[0] & 15) || (p.pitch[1] & 7) || p.pitch[0] < hbhip_align_up(l.row_bytes[0], 16) ||
+        p.pitch[1] * 2 < hbhip_align_up(l.row_bytes[1], 16) ||
+        p.height[0] != l.rows[0] || p.height[1] != l.rows[1] || p.height[2] != l.rows[1] || l.rows[0] + l.rows[1] > 65535)
+        return HBHIP_ERR_ARG;
+    BiSurface a;
+    for (int c = 0; c < 3; c++)
+    {
+        if (!p.plane[c] || ((uintptr_t)p.plane[c] & 15)) return HBHIP_ERR_ARG;
+        a.plane[c] = p.plane[c];
+    }
+    for (int c = 0; c < 2; c++)
+    {
+        a.splane[c] = s->plane[c];
+        a.spitch[c] = s->pitch[c];
+        if (!s->plane[c] || ((uintptr_t)s->plane[c] & 15) || (s->pitch[c] & 15) || s->pitch[c] < l.row_bytes[c]) return HBHIP_ERR_ARG;
+        a.sunits[c] = (unsigned)s->pitch[c] / 16;
+        // merge: the samples' units (inside both pitches, see above); split: the frame's whole row, in units of the interleaved side
+        a.units[c] = merge ? (unsigned)hbhip_align_up(l.row_bytes[c], 16) / 16 : c == 0 ? (unsigned)p.pitch[0] / 16 : (unsigned)p.pitch[1] / 8;
+    }
+    a.fpitch[0] = p.pitch[0];
+    a.fpitch[1] = p.pitch[1];
+    a.rows0 = (unsigned)l.rows[0];
+    const unsigned most = a.units[0] > a.units[1] ? a.units[0] : a.units[1];
+    const dim3 grid(hbhip_grid_x((most + 255) / 256), (unsigned)(l.rows[0] + l.rows[1])), blk(256);
+    if (merge)
+    {
+        if (p.bps == 1) HBHIP_LAUNCH_ON(ctx, stream, "bi_surface_merge", bi_surface_merge_kernel<uint8_t>, grid, blk, 0, a);
+        else            HBHIP_LAUNCH_ON(ctx, stream, "bi_surface_merge", bi_surface_merge_kernel<uint16_t>, grid, blk, 0, a);
+    }
+    else
+    {
+        if (p.bps == 1) HBHIP_LAUNCH_ON(ctx, stream, "bi_surface_split", bi_surface_split_kernel<uint8_t>, grid, blk, 0, a);
+        else            HBHIP_LAUNCH_ON(ctx, stream, "bi_surface_split", bi_surface_split_kernel<uint16_t>, grid, blk, 0, a);
     }
     HBHIP_CHECK(ctx, hipGetLastError());
     return HBHIP_OK;

@@ -287,6 +287,16 @@ static size_t layout_bytes(const DevPicture *p)
 {
     return (size_t)(p->plane[2] - p->plane[0]) + (size_t)p->pitch[2] * p->height[2];
 }
+// what the copy of a frame between `p` and host planes moves over the bus (hbhip_ctx_bus_bytes): the one block, else the
+// rows of the 2-D copies - up with the host's row padding as far as our pitch reaches, down the samples only
+static size_t copy_bytes(const DevPicture *p, uint8_t *const plane[3], const int stride[3], bool up)
+{
+    if (same_layout(p, plane, stride)) return layout_bytes(p);
+    size_t n = 0;
+    for (int c = 0; c < 3; c++)
+        n += (size_t)(up ? std::min(stride[c], p->pitch[c]) : p->width[c] * p->bps) * p->height[c];
+    return n;
+}
 
 // the H2D copy of a frame queued on the context's upload stream, and an event behind it (from the context's pool: the
 // caller gives it back with sync_ev_put once it has fired)
@@ -467,6 +477,8 @@ __global__ __launch_bounds__(1024) void copy_f4_kernel(const f32x4 *__restrict__
 
 extern "C" {
 
+static void surface_reap(hbhip_ctx *ctx, bool wait);     // device surfaces, below
+
 int hbhip_abi_version(void) { return HBHIP_ABI_VERSION; }
 
 int hbhip_host_alloc(size_t bytes, void **out)
@@ -584,6 +596,12 @@ void hbhip_ctx_destroy(hbhip_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->up_stream) { (void)hipStreamSynchronize(ctx->up_stream); (void)hipStreamDestroy(ctx->up_stream); }
     if (ctx->down_stream) { (void)hipStreamSynchronize(ctx->down_stream); (void)hipStreamDestroy(ctx->down_stream); }
+    surface_reap(ctx, true);
+    for (hbhip_surface *s : ctx->surface_pool)
+    {
+        (void)hipFree(s->base);
+        delete s;
+    }
     for (hipEvent_t e : ctx->sync_ev_pool) (void)hipEventDestroy(e);
     for (auto &p : ctx->prof_pending)
     {
@@ -608,6 +626,7 @@ int hbhip_ctx_sync(hbhip_ctx *ctx)
 {
     if (!ctx) return HBHIP_ERR_ARG;
     HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    surface_reap(ctx, true);                    // (surface kernels still queued on the copy streams: waited for, their references dropped)
     return HBHIP_OK;
 }
 
@@ -960,6 +979,7 @@ int hbhip_frame_upload(hbhip_frame *fr, const hbhip_host_frame *src)
     (void)hipSetDevice(fr->ctx->device);
     const int rc = hbhip_copy_h2d(fr->ctx, &fr->pic, src);      // returns when the copy has finished
     if (rc != HBHIP_OK) return rc;
+    fr->ctx->bus_h2d += copy_bytes(&fr->pic, src->plane, src->stride, true);
     std::lock_guard<std::mutex> lk(fr->ctx->frame_lock);
     set_contents(fr, nullptr);
     return HBHIP_OK;
@@ -983,6 +1003,7 @@ int hbhip_frame_upload_async(hbhip_frame *fr, const hbhip_host_frame *src, void 
     hipEvent_t done = nullptr;
     const int rc = hbhip_copy_h2d_queue(ctx, &fr->pic, src, &done);
     if (rc != HBHIP_OK) return rc;
+    ctx->bus_h2d += copy_bytes(&fr->pic, src->plane, src->stride, true);
     m->stream = ctx->up();
     const hipError_t e = hipEventRecord(m->ev, ctx->up());
     if (e != hipSuccess)
@@ -1008,6 +1029,7 @@ int hbhip_ctx_upload_done(hbhip_ctx *ctx, void *token, int block)
     hipError_t e = block ? hipEventSynchronize(ev) : hipEventQuery(ev);
     if (e == hipErrorNotReady) { (void)hipGetLastError(); return HBHIP_AGAIN; }
     ctx->sync_ev_put(ev);
+    surface_reap(ctx, false);
     return e == hipSuccess ? HBHIP_OK : ctx->fail(e, "upload: wait for the copy");
 }
 
@@ -1065,6 +1087,7 @@ int hbhip_frame_download_async(hbhip_frame *fr, const hbhip_host_frame *dst, voi
         }
     e = hipEventRecord(ev, ctx->down());
     if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->down()); return fail(e, "hipEventRecord(download)"); }
+    ctx->bus_d2h += copy_bytes(src, dst->plane, dst->stride, false);
     *token = ev;
     return HBHIP_OK;
 }
@@ -1077,6 +1100,7 @@ int hbhip_frame_download_wait(hbhip_frame *fr, void *token)
     hipEvent_t ev = (hipEvent_t)token;
     const hipError_t e = hipEventSynchronize(ev);
     ctx->sync_ev_put(ev);
+    surface_reap(ctx, false);
     return e == hipSuccess ? HBHIP_OK : ctx->fail(e, "hipEventSynchronize(download)");
 }
 
@@ -1139,6 +1163,16 @@ static hipError_t bi_copy(uint8_t *stage, const BiLayout &l, const hbhip_host_bi
     return e;
 }
 
+// what bi_copy moves over the bus (hbhip_ctx_bus_bytes)
+static size_t bi_copy_bytes(const BiLayout &l, const hbhip_host_biplanar *hb, bool to_device)
+{
+    if (hb->stride[0] == l.pitch[0] && hb->stride[1] == l.pitch[1] && hb->plane[1] == hb->plane[0] + (size_t)l.pitch[0] * l.rows[0])
+        return l.bytes;
+    size_t n = 0;
+    for (int p = 0; p < 2; p++) n += (size_t)(to_device ? std::min(hb->stride[p], l.pitch[p]) : l.row_bytes[p]) * l.rows[p];
+    return n;
+}
+
 // `src` must stay valid until hbhip_ctx_upload_done(token) says so, as with hbhip_frame_upload_async
 int hbhip_frame_upload_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *src, void **token)
 {
@@ -1177,6 +1211,7 @@ int hbhip_frame_upload_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar
     m->recorded = true;
     m->closed.store(true, std::memory_order_release);
     { std::lock_guard<std::mutex> lk(ctx->frame_lock); set_contents(fr, std::move(m)); }
+    ctx->bus_h2d += bi_copy_bytes(l, src, true);
     *token = done;
     return HBHIP_OK;
 }
@@ -1217,6 +1252,7 @@ int hbhip_frame_download_biplanar_async(hbhip_frame *fr, const hbhip_host_biplan
             return e != hipSuccess ? ctx->fail(e, "download (biplanar)") : rc;
         }
     }
+    ctx->bus_d2h += bi_copy_bytes(l, dst, false);
     *token = ev;
     return HBHIP_OK;
 }
@@ -1226,6 +1262,308 @@ int hbhip_frame_download_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *ds
     void *token = nullptr;
     const int rc = hbhip_frame_download_biplanar_async(fr, dst, &token);
     return rc != HBHIP_OK ? rc : hbhip_frame_download_wait(fr, token);
+}
+
+// ---- device surfaces (NV12 / P010LE pictures in HBM) at the two ends of a run -----------------------------------------
+// No staging buffer and no bi_lock: the repack kernel reads or writes the surface where it lies.  The same ordering rule:
+// the split runs on the upload stream behind the surface's contents and is the frame's ready mark, the merge on the
+// download stream behind the frame's contents (and the surface's earlier readers) and is the surface's ready mark.
+static int surface_geometry_ok(int width, int height, int depth)
+{
+    return (depth == 8 || depth == 10) && width >= 2 && height >= 2;
+}
+
+// the last reference has gone: a pooled surface goes back to its pool, a wrapped one to its owner (outside the lock)
+static void surface_unref(hbhip_surface *s)
+{
+    {
+        std::lock_guard<std::mutex> lk(s->ctx->surface_lock);
+        if (--s->refs > 0) return;
+        if (s->base) { s->ctx->surface_pool.push_back(s); return; }
+    }
+    if (s->release) s->release(s->opaque);
+    delete s;
+}
+
+// drop the references of the kernels queued on `ctx` that have finished (all of them when `wait`: they are waited for)
+static void surface_reap(hbhip_ctx *ctx, bool wait)
+{
+    std::vector<hbhip_ctx::SurfaceOp> gone;
+    {
+        std::lock_guard<std::mutex> lk(ctx->surface_lock);
+        if (ctx->surface_ops.empty()) return;
+        if (wait) gone.swap(ctx->surface_ops);
+        else
+        {
+            size_t keep = 0;
+            for (hbhip_ctx::SurfaceOp &op : ctx->surface_ops)
+                if (mark_passed(op.done)) gone.push_back(std::move(op));
+                else { if (&ctx->surface_ops[keep] != &op) ctx->surface_ops[keep] = std::move(op); keep++; }
+            ctx->surface_ops.resize(keep);
+            (void)hipGetLastError();                              // hipErrorNotReady of the queries
+        }
+    }
+    for (hbhip_ctx::SurfaceOp &op : gone)
+    {
+        if (wait && op.done) (void)hipEventSynchronize(op.done->ev);
+        surface_unref(op.s);
+    }
+}
+
+// a mark recorded on `stream` right now
+static std::shared_ptr<IdleMark> record_mark(hipStream_t stream)
+{
+    std::shared_ptr<IdleMark> m = std::make_shared<IdleMark>();
+    if (hipEventCreateWithFlags(&m->ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(m->ev, stream) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    m->stream = stream;
+    m->recorded = true;
+    m->closed.store(true, std::memory_order_release);
+    return m;
+}
+
+int hbhip_surface_alloc(hbhip_ctx *ctx, int width, int height, int depth, int pitch_align, int rows_align, hbhip_surface **out)
+{
+    if (!ctx || !out) return HBHIP_ERR_ARG;
+    *out = nullptr;
+    if (pitch_align < 16 || (pitch_align & (pitch_align - 1)) || pitch_align > 4096 || rows_align < 1 || rows_align > 256)
+        return HBHIP_ERR_ARG;
+    if (!surface_geometry_ok(width, height, depth)) return HBHIP_ERR_UNSUPPORTED;
+    (void)hipSetDevice(ctx->device);
+    surface_reap(ctx, false);
+    {
+        std::lock_guard<std::mutex> lk(ctx->surface_lock);
+        // the longest-released one first: the likeliest to have no reader left that an export into it would wait for
+        for (size_t i = 0; i < ctx->surface_pool.size(); i++)
+        {
+            hbhip_surface *s = ctx->surface_pool[i];
+            if (s->width != width || s->height != height || s->depth != depth || s->pitch_align != pitch_align ||
+                s->rows_align != rows_align)
+                continue;
+            ctx->surface_pool.erase(ctx->surface_pool.begin() + (ptrdiff_t)i);
+            s->refs = 1;
+            *out = s;
+            return HBHIP_OK;
+        }
+    }
+    BiLayout l;
+    hbhip_bi_layout(width, height, depth, &l);
+    hbhip_surface *s = new (std::nothrow) hbhip_surface();
+    if (!s) return HBHIP_ERR_NOMEM;
+    s->ctx = ctx; s->width = width; s->height = height; s->depth = depth;
+    s->pitch_align = pitch_align; s->rows_align = rows_align;
+    const int rows0 = hbhip_align_up(height, rows_align);
+    for (int p = 0; p < 2; p++) s->pitch[p] = hbhip_align_up(l.row_bytes[p], pitch_align);
+    const size_t bytes = (size_t)s->pitch[0] * rows0 + (size_t)s->pitch[1] * ((rows0 + 1) / 2);
+    if (hipMalloc((void **)&s->base, bytes) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        delete s;
+        return HBHIP_ERR_NOMEM;
+    }
+    s->plane[0] = s->base;
+    s->plane[1] = s->base + (size_t)s->pitch[0] * rows0;
+    // padding and padded rows are never written by an export: cleared once, and the first export waits for that
+    (void)hipMemsetAsync(s->base, 0, bytes, ctx->stream);
+    s->ready = stream_now(ctx);
+    *out = s;
+    return HBHIP_OK;
+}
+
+int hbhip_surface_wrap(hbhip_ctx *ctx, const hbhip_dev_surface *mem, int width, int height, int depth,
+                       void (*release)(void *), void *opaque, hbhip_surface **out)
+{
+    if (!ctx || !mem || !out) return HBHIP_ERR_ARG;
+    *out = nullptr;
+    if (!mem->plane[0] || !mem->plane[1]) return HBHIP_ERR_ARG;
+    if (!surface_geometry_ok(width, height, depth)) return HBHIP_ERR_UNSUPPORTED;
+    BiLayout l;
+    hbhip_bi_layout(width, height, depth, &l);
+    for (int p = 0; p < 2; p++)
+        if (((uintptr_t)mem->plane[p] & 15) || mem->pitch[p] < 0 || (mem->pitch[p] & 15)) return HBHIP_ERR_UNSUPPORTED;
+    for (int p = 0; p < 2; p++)
+        if (mem->pitch[p] < l.row_bytes[p]) return HBHIP_ERR_ARG;
+    const uintptr_t b0 = (uintptr_t)mem->plane[0], e0 = b0 + (size_t)mem->pitch[0] * l.rows[0];
+    const uintptr_t b1 = (uintptr_t)mem->plane[1], e1 = b1 + (size_t)mem->pitch[1] * l.rows[1];
+    if (b0 < e1 && b1 < e0) return HBHIP_ERR_ARG;                 // the planes overlap
+    hbhip_surface *s = new (std::nothrow) hbhip_surface();
+    if (!s) return HBHIP_ERR_NOMEM;
+    s->ctx = ctx; s->width = width; s->height = height; s->depth = depth;
+    for (int p = 0; p < 2; p++) { s->plane[p] = (uint8_t *)mem->plane[p]; s->pitch[p] = mem->pitch[p]; }
+    s->release = release;
+    s->opaque = opaque;
+    *out = s;
+    return HBHIP_OK;
+}
+
+void hbhip_surface_retain(hbhip_surface *s)
+{
+    if (!s) return;
+    std::lock_guard<std::mutex> lk(s->ctx->surface_lock);
+    s->refs++;
+}
+
+void hbhip_surface_release(hbhip_surface *s)
+{
+    if (!s) return;
+    hbhip_ctx *ctx = s->ctx;
+    (void)hipSetDevice(ctx->device);
+    surface_unref(s);
+    surface_reap(ctx, false);
+}
+
+int hbhip_surface_describe(hbhip_surface *s, hbhip_dev_surface *out, int *width, int *height, int *depth)
+{
+    if (!s || !out) return HBHIP_ERR_ARG;
+    for (int p = 0; p < 2; p++) { out->plane[p] = s->plane[p]; out->pitch[p] = s->pitch[p]; }
+    if (width) *width = s->width;
+    if (height) *height = s->height;
+    if (depth) *depth = s->depth;
+    return HBHIP_OK;
+}
+
+int hbhip_surface_set_ready_event(hbhip_surface *s, void *hip_event)
+{
+    if (!s) return HBHIP_ERR_ARG;
+    std::lock_guard<std::mutex> lk(s->ctx->surface_lock);
+    s->ready_event = (hipEvent_t)hip_event;
+    return HBHIP_OK;
+}
+
+static int surface_check(const hbhip_frame *fr, const hbhip_surface *s)
+{
+    if ((fr->depth != 8 && fr->depth != 10) || fr->lcw != 1 || fr->lch != 1 || fr->width < 2 || fr->height < 2)
+        return HBHIP_ERR_UNSUPPORTED;
+    if (s->depth != fr->depth || s->width != fr->width || s->height != fr->height) return HBHIP_ERR_UNSUPPORTED;
+    if (s->ctx->device != fr->ctx->device) return HBHIP_ERR_ARG;
+    return HBHIP_OK;
+}
+
+// the kernel is queued: the library's own reference on the surface until `done` has fired
+static void surface_hold(hbhip_ctx *ctx, hbhip_surface *s, const std::shared_ptr<IdleMark> &done)
+{
+    hbhip_surface_retain(s);
+    std::lock_guard<std::mutex> lk(ctx->surface_lock);
+    ctx->surface_ops.push_back({s, done});
+}
+
+int hbhip_frame_import_surface_async(hbhip_frame *fr, hbhip_surface *src, void **token)
+{
+    if (!fr || !src || !token) return HBHIP_ERR_ARG;
+    *token = nullptr;
+    hbhip_ctx *ctx = fr->ctx;
+    int rc = surface_check(fr, src);
+    if (rc != HBHIP_OK) return rc;
+    (void)hipSetDevice(ctx->device);
+    surface_reap(ctx, false);
+    hipEvent_t done = ctx->sync_ev_get();
+    if (!done) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(import)");
+    hipStream_t up = ctx->up();
+    std::shared_ptr<IdleMark> ready, earlier;
+    hipEvent_t producer;
+    {
+        std::lock_guard<std::mutex> lk(src->ctx->surface_lock);
+        ready = src->ready; producer = src->ready_event; earlier = src->read_idle;
+    }
+    hipError_t e = hbhip_pic_wait_idle(up, &fr->pic);
+    if (e == hipSuccess) e = wait_mark(up, ready);
+    if (e == hipSuccess && producer) e = hipStreamWaitEvent(up, producer, 0);
+    if (e == hipSuccess) e = wait_mark(up, earlier);            // (another stream's import: an export then waits for ours alone)
+    if (e != hipSuccess) { ctx->sync_ev_put(done); return ctx->fail(e, "import: order behind the surface's contents"); }
+    rc = hbhip_bi_surface_launch(ctx, up, false, src, fr);
+    // the token's event ahead of the mark: once the library lets go of the surface (the mark has fired) the token is done
+    if (rc == HBHIP_OK) e = hipEventRecord(done, up);
+    std::shared_ptr<IdleMark> m = rc == HBHIP_OK && e == hipSuccess ? record_mark(up) : nullptr;
+    if (rc == HBHIP_OK && e == hipSuccess && !m) e = hipErrorOutOfMemory;
+    if (rc != HBHIP_OK || e != hipSuccess)
+    {
+        (void)hipStreamSynchronize(up);                          // what is queued must not outlive the call
+        ctx->sync_ev_put(done);
+        return rc != HBHIP_OK ? rc : ctx->fail(e, "import (surface)");
+    }
+    {
+        std::lock_guard<std::mutex> lk(src->ctx->surface_lock);
+        src->read_idle = m;
+        if (producer && src->ready_event == producer)           // the first reader has waited for it: later ones wait for this one
+        {
+            src->ready_event = nullptr;
+            src->ready = m;
+        }
+    }
+    surface_hold(ctx, src, m);
+    { std::lock_guard<std::mutex> lk(ctx->frame_lock); set_contents(fr, std::move(m)); }
+    *token = done;
+    return HBHIP_OK;
+}
+
+int hbhip_frame_import_surface(hbhip_frame *fr, hbhip_surface *src)
+{
+    void *token = nullptr;
+    const int rc = hbhip_frame_import_surface_async(fr, src, &token);
+    return rc != HBHIP_OK ? rc : hbhip_ctx_upload_done(fr->ctx, token, 1);
+}
+
+int hbhip_frame_export_surface_async(hbhip_frame *fr, hbhip_surface *dst, void **token)
+{
+    if (!fr || !dst || !token) return HBHIP_ERR_ARG;
+    *token = nullptr;
+    hbhip_ctx *ctx = fr->ctx;
+    int rc = surface_check(fr, dst);
+    if (rc != HBHIP_OK) return rc;
+    (void)hipSetDevice(ctx->device);
+    surface_reap(ctx, false);
+    hipEvent_t ev = ctx->sync_ev_get();
+    if (!ev) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(export)");
+    hipStream_t down = ctx->down();
+    hipError_t e;
+    { std::lock_guard<std::mutex> lk(ctx->frame_lock); e = order_after_contents(fr, down); }
+    std::shared_ptr<IdleMark> ready, readers;
+    hipEvent_t producer;
+    {
+        std::lock_guard<std::mutex> lk(dst->ctx->surface_lock);
+        ready = dst->ready; producer = dst->ready_event; readers = dst->read_idle;
+    }
+    if (e == hipSuccess) e = wait_mark(down, ready);            // an earlier writer (another context's download stream; the clearing)
+    if (e == hipSuccess && producer) e = hipStreamWaitEvent(down, producer, 0);
+    if (e == hipSuccess) e = wait_mark(down, readers);
+    if (e != hipSuccess) { ctx->sync_ev_put(ev); return ctx->fail(e, "export: order behind the frame's contents and the surface's users"); }
+    rc = hbhip_bi_surface_launch(ctx, down, true, dst, fr);
+    if (rc == HBHIP_OK) e = hipEventRecord(ev, down);
+    std::shared_ptr<IdleMark> m = rc == HBHIP_OK && e == hipSuccess ? record_mark(down) : nullptr;
+    if (rc == HBHIP_OK && e == hipSuccess && !m) e = hipErrorOutOfMemory;
+    if (rc != HBHIP_OK || e != hipSuccess)
+    {
+        (void)hipStreamSynchronize(down);
+        ctx->sync_ev_put(ev);
+        return rc != HBHIP_OK ? rc : ctx->fail(e, "export (surface)");
+    }
+    {
+        std::lock_guard<std::mutex> lk(dst->ctx->surface_lock);
+        dst->ready = m;
+        dst->ready_event = nullptr;
+        dst->read_idle.reset();
+    }
+    surface_hold(ctx, dst, m);
+    *token = ev;
+    return HBHIP_OK;
+}
+
+int hbhip_frame_export_surface(hbhip_frame *fr, hbhip_surface *dst)
+{
+    void *token = nullptr;
+    const int rc = hbhip_frame_export_surface_async(fr, dst, &token);
+    return rc != HBHIP_OK ? rc : hbhip_frame_download_wait(fr, token);
+}
+
+int hbhip_ctx_bus_bytes(hbhip_ctx *ctx, uint64_t *h2d, uint64_t *d2h)
+{
+    if (!ctx) return HBHIP_ERR_ARG;
+    if (h2d) *h2d = ctx->bus_h2d.load(std::memory_order_relaxed);
+    if (d2h) *d2h = ctx->bus_d2h.load(std::memory_order_relaxed);
+    return HBHIP_OK;
 }
 
 // ---- generic filter surface -------------------------------------------------

@@ -92,6 +92,15 @@ struct hbhip_ctx
     std::mutex bi_lock[2];
     uint8_t   *bi_stage[2] = {nullptr, nullptr};
     size_t     bi_stage_bytes[2] = {0, 0};
+    // device surfaces (hbhip_surface_*): the pool of library-owned ones, and the repack kernels queued on this context's
+    // copy streams that have not been seen to finish yet - each holds a reference on its surface (surface_reap drops it).
+    // One lock for both and for every surface's reference count and marks, whichever context the surface belongs to:
+    // surface_lock of the surface's OWN context for the surface, of the context that queued the kernel for `surface_ops`.
+    struct SurfaceOp { struct hbhip_surface *s; std::shared_ptr<IdleMark> done; };
+    std::vector<struct hbhip_surface *> surface_pool;
+    std::vector<SurfaceOp> surface_ops;
+    std::mutex surface_lock;
+    std::atomic<uint64_t> bus_h2d{0}, bus_d2h{0};   // hbhip_ctx_bus_bytes
     // last_error and the profiler's bookkeeping are written from whichever filter thread fails / launches:
     // libhb runs every filter of a job on its own thread (work.c:2527-2600) and they share this context
     std::recursive_mutex state_lock;
@@ -229,6 +238,27 @@ struct BiLayout
 void hbhip_bi_layout(int width, int height, int depth, BiLayout *l);
 // the repack kernel between a staging buffer of that layout and the planar 4:2:0 frame `fr` (depth 8 or 10), on `stream`
 int hbhip_bi_repack_launch(hbhip_ctx *ctx, hipStream_t stream, bool merge, uint8_t *stage, const hbhip_frame *fr);
+
+// An NV12 / P010LE picture in device memory with a layout of its maker's choosing: the library's own (base != nullptr: from
+// the owner's surface_pool, back to it with the last reference) or a caller's (release(opaque) with the last reference).
+struct hbhip_surface
+{
+    hbhip_ctx *ctx = nullptr;
+    uint8_t   *plane[2] = {nullptr, nullptr};
+    int        pitch[2] = {0, 0};
+    int        width = 0, height = 0, depth = 8;
+    uint8_t   *base = nullptr;
+    int        pitch_align = 0, rows_align = 0;      // of a pooled one: what hbhip_surface_alloc matches on
+    void     (*release)(void *) = nullptr;
+    void      *opaque = nullptr;
+    // under ctx->surface_lock
+    int        refs = 1;
+    std::shared_ptr<IdleMark> ready;        // the contents are complete behind this point: the last export into it
+    hipEvent_t ready_event = nullptr;       // ... or behind a producer of the caller's (hbhip_surface_set_ready_event)
+    std::shared_ptr<IdleMark> read_idle;    // the last import has read it behind this point: an export waits for it
+};
+// the repack kernel between a surface and the planar 4:2:0 frame `fr` (same size and depth: the caller has checked), on `stream`
+int hbhip_bi_surface_launch(hbhip_ctx *ctx, hipStream_t stream, bool merge, const hbhip_surface *s, const hbhip_frame *fr);
 
 // Geometry of a planar YUV picture.
 struct PicGeometry

@@ -143,6 +143,47 @@ class Chain:
         if rc != 0:
             raise RuntimeError(f"hbh_chain_feed failed ({rc})")
 
+    def push_surface(self, surface, flags: int = 0x10, pts: int = 0):
+        """A frame that lies in device memory already: `surface` is a hip.Surface (NV12 / P010LE, the chain's pix_fmt); the
+        buffer gets a reference of its own."""
+        self._rt.hbh_chain_push_surface.restype = C.c_int
+        self._rt.hbh_chain_push_surface.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64]
+        surface.retain()                                   # the call takes a reference over
+        rc = self._rt.hbh_chain_push_surface(self._h, surface.h, flags, pts)
+        if rc != 0:
+            raise RuntimeError(f"hbh_chain_push_surface failed ({rc})")
+
+    def feed_surfaces(self, surfaces, first: int, count: int, duration: int = 3003, flags: int = 0x10):
+        """the surface form of feed(): `count` buffers cycling through the hip.Surface objects of `surfaces`, nothing copied"""
+        from . import hip
+        n = len(surfaces)
+        ptrs = (C.c_void_p * n)(*[s.h.value for s in surfaces])
+        self._rt.hbh_chain_feed_surfaces.restype = C.c_int
+        self._rt.hbh_chain_feed_surfaces.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_int64,
+                                                     C.c_int, C.c_void_p]
+        retain = C.cast(hip.lib().hbhip_surface_retain, C.c_void_p)
+        rc = self._rt.hbh_chain_feed_surfaces(self._h, ptrs, n, first, count, duration, flags, retain)
+        if rc != 0:
+            raise RuntimeError(f"hbh_chain_feed_surfaces failed ({rc})")
+
+    def pop_surface(self):
+        """Next output as (hip.Surface, FrameInfo) when it is a surface buffer - the buffer's reference is the object's, close()
+        gives the surface back; None for the EOF marker, an empty queue or a host frame (which stays queued for pop())."""
+        from . import hip
+        info = FrameInfo()
+        if self._rt.hbh_chain_peek(self._h, C.byref(info)) != 0:
+            return None
+        if info.is_eof:
+            self._rt.hbh_chain_pop(self._h, None, None)
+            self.eof = True
+            return None
+        self._rt.hbh_chain_pop_surface.restype = C.c_int
+        self._rt.hbh_chain_pop_surface.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        h = C.c_void_p()
+        if self._rt.hbh_chain_pop_surface(self._h, C.byref(h)) != 0:
+            return None
+        return hip.Surface.adopt(h), info
+
     def push_eof(self):
         rc = self._rt.hbh_chain_push_eof(self._h)
         if rc != 0:

@@ -24,6 +24,8 @@ ABI_SYMBOLS = [
     "hbhip_frame_alloc", "hbhip_frame_retain", "hbhip_frame_release", "hbhip_frame_refs", "hbhip_frame_use_on", "hbhip_frame_describe", "hbhip_frame_copy",
     "hbhip_frame_upload", "hbhip_frame_upload_async", "hbhip_ctx_upload_done", "hbhip_frame_download", "hbhip_frame_mark_ready", "hbhip_frame_download_async", "hbhip_frame_download_wait",
     "hbhip_frame_upload_biplanar", "hbhip_frame_download_biplanar", "hbhip_frame_upload_biplanar_async", "hbhip_frame_download_biplanar_async",
+    "hbhip_surface_alloc", "hbhip_surface_wrap", "hbhip_surface_retain", "hbhip_surface_release", "hbhip_surface_describe", "hbhip_surface_set_ready_event",
+    "hbhip_frame_import_surface", "hbhip_frame_import_surface_async", "hbhip_frame_export_surface", "hbhip_frame_export_surface_async", "hbhip_ctx_bus_bytes",
     "hbhip_filter_use_frames", "hbhip_filter_push_frame", "hbhip_filter_pull_frame", "hbhip_filter_push", "hbhip_filter_push_dev", "hbhip_filter_pull", "hbhip_filter_pull_dev",
     "hbhip_filter_process_dev", "hbhip_filter_submit_async", "hbhip_filter_wait", "hbhip_filter_inflight", "hbhip_filter_flush", "hbhip_filter_pending", "hbhip_filter_defer", "hbhip_filter_kick", "hbhip_filter_destroy",
     "hbhip_filter_out_geometry",
@@ -58,6 +60,14 @@ class HostBiplanar(C.Structure):
 
 class DevFrame(C.Structure):
     _fields_ = [("plane", C.c_void_p * 3), ("stride", C.c_int * 3)]
+
+
+class DevSurface(C.Structure):
+    """hbhip_dev_surface: an NV12 / P010LE picture in device memory (luma, interleaved Cb Cr), a pitch per plane"""
+    _fields_ = [("plane", C.c_void_p * 2), ("pitch", C.c_int * 2)]
+
+
+SURFACE_RELEASE = C.CFUNCTYPE(None, C.c_void_p)
 
 
 class BitmapSub(C.Structure):
@@ -160,6 +170,19 @@ def lib() -> C.CDLL:
             getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(HostBiplanar), C.POINTER(C.c_void_p)]
         L.hbhip_frame_download_wait.argtypes = [C.c_void_p, C.c_void_p]
         L.hbhip_ctx_upload_done.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.hbhip_surface_alloc.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)]
+        L.hbhip_surface_wrap.argtypes = [C.c_void_p, C.POINTER(DevSurface), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_void_p)]
+        for fn in ("hbhip_surface_retain", "hbhip_surface_release"):
+            getattr(L, fn).argtypes = [C.c_void_p]
+            getattr(L, fn).restype = None
+        L.hbhip_surface_describe.argtypes = [C.c_void_p, C.POINTER(DevSurface)] + [C.POINTER(C.c_int)] * 3
+        L.hbhip_surface_set_ready_event.argtypes = [C.c_void_p, C.c_void_p]
+        for fn in ("hbhip_frame_import_surface", "hbhip_frame_export_surface"):
+            getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p]
+        for fn in ("hbhip_frame_import_surface_async", "hbhip_frame_export_surface_async"):
+            getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.hbhip_ctx_bus_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.hbhip_filter_use_frames.argtypes = [C.c_void_p]
         L.hbhip_decomb_push_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
         L.hbhip_bm3d_params_from_settings.argtypes = [C.c_char_p, C.c_int, C.POINTER(Bm3dParams)]
@@ -245,6 +268,12 @@ class Ctx:
         check(lib().hbhip_ctx_elapsed_ms(self.h, a, b, C.byref(ms)), self.h, "elapsed")
         return ms.value
 
+    def bus_bytes(self):
+        """(H2D, D2H) bytes the frame upload / download entry points have queued over the bus on this context"""
+        up, down = C.c_uint64(), C.c_uint64()
+        check(lib().hbhip_ctx_bus_bytes(self.h, C.byref(up), C.byref(down)), self.h, "bus_bytes")
+        return up.value, down.value
+
     def close(self):
         if self.h:
             lib().hbhip_ctx_destroy(self.h)
@@ -292,6 +321,12 @@ class Frame:
         check(lib().hbhip_frame_download(self.h, C.byref(host_frame(out))), self.ctx.h, "frame_download")
         return out
 
+    def import_surface(self, surface: "Surface"):
+        check(lib().hbhip_frame_import_surface(self.h, surface.h), self.ctx.h, "frame_import_surface")
+
+    def export_surface(self, surface: "Surface"):
+        check(lib().hbhip_frame_export_surface(self.h, surface.h), self.ctx.h, "frame_export_surface")
+
     def copy_from(self, src: "Frame"):
         check(lib().hbhip_frame_copy(self.h, src.h), self.ctx.h, "frame_copy")
 
@@ -307,6 +342,46 @@ class Frame:
     def close(self):
         if self.h:
             self.release()
+            self.h = None
+
+
+class Surface:
+    """An NV12 / P010LE picture in device memory (hbhip_surface_*), holding one reference until close()."""
+
+    def __init__(self, ctx: Ctx, width, height, depth=8, pitch_align=256, rows_align=16):
+        h = C.c_void_p()
+        check(lib().hbhip_surface_alloc(ctx.h, width, height, depth, pitch_align, rows_align, C.byref(h)), ctx.h, "surface_alloc")
+        self.h = h
+
+    @classmethod
+    def adopt(cls, handle):
+        """around an hbhip_surface* whose reference becomes the object's"""
+        s = cls.__new__(cls)
+        s.h = handle
+        return s
+
+    @classmethod
+    def wrap(cls, ctx: Ctx, planes, pitches, width, height, depth=8, release=None, opaque=None):
+        """caller-owned device memory: planes = two device addresses; release: a SURFACE_RELEASE the caller keeps alive"""
+        mem = DevSurface((C.c_void_p * 2)(*planes), (C.c_int * 2)(*pitches))
+        h = C.c_void_p()
+        fn = C.cast(release, C.c_void_p) if release is not None else None
+        check(lib().hbhip_surface_wrap(ctx.h, C.byref(mem), width, height, depth, fn, opaque, C.byref(h)), ctx.h, "surface_wrap")
+        return cls.adopt(h)
+
+    def describe(self):
+        """((plane addresses), (pitches), width, height, depth)"""
+        d = DevSurface()
+        w, h, depth = C.c_int(), C.c_int(), C.c_int()
+        check(lib().hbhip_surface_describe(self.h, C.byref(d), C.byref(w), C.byref(h), C.byref(depth)), what="surface_describe")
+        return tuple(d.plane), tuple(d.pitch), w.value, h.value, depth.value
+
+    def retain(self):
+        lib().hbhip_surface_retain(self.h)
+
+    def close(self):
+        if self.h:
+            lib().hbhip_surface_release(self.h)
             self.h = None
 
 

@@ -10,6 +10,7 @@ Prints one JSON object: output frames/s, the bus traffic that goes with it, and 
 from __future__ import annotations
 
 import argparse
+import ctypes
 import json
 import os
 import sys
@@ -23,7 +24,7 @@ def frame_bytes(w, h):
     return w * h * 3 // 2
 
 
-def chain_for(workload, scale, vfr=True):
+def chain_for(workload, scale, vfr=True, surfaces=False):
     """The filter list a front-end builds for this job, as hb_hip_setup_hw_filters leaves it: every preset-built job has
     a frame-rate shaper between decomb and NLMeans (preset.c:2026-2048) - "same as source" here, after a bob that
     doubles 29.97 - and it is a member of the device-resident run (libhb/hip_common.c).  Outside libhb the shaper is
@@ -37,23 +38,53 @@ def chain_for(workload, scale, vfr=True):
         if scale:
             chain.append(("hb_filter_crop_scale_hip", "width=%d:height=%d" % tuple(scale)))
         chain.append(("hb_filter_lapsharp_hip", LAPSHARP))
-    chain.append(("hb_filter_hip_download", ""))
+    # --surfaces: the run ends on NV12 pictures that stay in HBM (for a hardware encoder) instead of host frames
+    chain.append(("hb_filter_hip_download", "format=nv12:surface=1" if surfaces else ""))
     return chain
 
 
-def run(workload, w, h, scale, cfg=3, n_warm=32, n_in=2048, chain=None, content="interlaced", feeders=4):
+def resident_surfaces(ctx, frames):
+    """the stream as NV12 pictures in HBM, made once: each frame is uploaded and exported into a surface laid out as a video
+    engine's allocator would (what a hardware decoder hands over)"""
+    from handbrake_amd import hip
+    h, w = frames[0][0].shape
+    out = []
+    fr = hip.Frame(ctx, w, h, 8)
+    for planes in frames:
+        s = hip.Surface(ctx, w, h, 8)
+        fr.upload(planes)
+        fr.export_surface(s)
+        out.append(s)
+    fr.close()
+    return out
+
+
+def run(workload, w, h, scale, cfg=3, n_warm=32, n_in=2048, chain=None, content="interlaced", feeders=4, surfaces=False):
     """Timed from a warmed-up, quiet pipeline (n_warm frames in, their outputs out as far as the batching stages let
     them: allocations, pinned pool, slabs all made) to the end of the stream n_in frames later, EOF drain included.
     The frames the last stage makes are counted and dropped as they come, as an encoder that keeps up would."""
     from handbrake_amd import hbrt, hip, synth
-    chain = chain or chain_for(workload, scale)
+    chain = chain or chain_for(workload, scale, surfaces=surfaces)
     frames = synth.stream(content, w, h, 48, cfg=cfg)          # a 48-frame stream walked round and round
+    ctx = resident = None
+    if surfaces:
+        ctx = hip.Ctx.__new__(hip.Ctx)                         # the drop-ins' shared context: lives as long as the process
+        ctx.h = ctypes.c_void_p(hip.filters().hbhip_host_ctx_ptr())
+        resident = resident_surfaces(ctx, frames)
+
+    def feed(ch, first, count):
+        # the source: `feeders` C threads fill hb_buffer_t's (the decoder's part in libhb) and the frames go in in order;
+        # --surfaces: the pictures lie in HBM already and the buffers only name them
+        if surfaces:
+            ch.feed_surfaces(resident, first, count, flags=8)
+        else:
+            ch.feed(frames, first, count, flags=8, threads=feeders)
+
     hbrt.set_threaded(True)
     hbrt.set_discard_output(True)
     try:
-        with hbrt.Chain(hip.filters(), chain, w, h) as ch:
-            # the source: `feeders` C threads fill hb_buffer_t's (the decoder's part in libhb) and the frames go in in order
-            ch.feed(frames, 0, n_warm, flags=8, threads=feeders)
+        with hbrt.Chain(hip.filters(), chain, w, h, hbrt.AV_PIX_FMT_NV12 if surfaces else hbrt.AV_PIX_FMT_YUV420P) as ch:
+            feed(ch, 0, n_warm)
             t_wait, last, t_last = time.perf_counter(), -1, time.perf_counter()
             while time.perf_counter() - t_wait < 60:
                 n = ch.produced()
@@ -65,10 +96,12 @@ def run(workload, w, h, scale, cfg=3, n_warm=32, n_in=2048, chain=None, content=
             n0 = ch.produced()
             t0 = time.perf_counter()
             busy0 = [ch.stage_busy_ms(s) for s in range(len(chain))]
-            ch.feed(frames, n_warm, n_in, flags=8, threads=feeders)
+            bus0 = ctx.bus_bytes() if surfaces else None
+            feed(ch, n_warm, n_in)
             ch.push_eof()                         # returns when every stage has finished
             dt = time.perf_counter() - t0
             total_out = ch.produced()
+            bus1 = ctx.bus_bytes() if surfaces else None
             # frames of the warm-up that were still inside the pipe at t0 come out in the timed interval too; what the
             # interval is credited with is the output of ITS inputs: (outputs per input of the whole run) x n_in
             n_out = int(round(total_out / (n_warm + n_in) * n_in))
@@ -78,7 +111,18 @@ def run(workload, w, h, scale, cfg=3, n_warm=32, n_in=2048, chain=None, content=
     finally:
         hbrt.set_discard_output(False)
         hbrt.set_threaded(False)
+        for s in resident or []:
+            s.close()
     ow, oh = scale if scale else (w, h)
+    if surfaces:
+        return {"value": round(n_out / dt, 2), "unit": "output frames/s", "input_fps": round(n_in / dt, 2), "ends": "device surfaces",
+                "path": "hb_filter_object_t chain (" + " -> ".join(c[0].replace("hb_filter_", "") for c in chain) + ") in the libhb "
+                        "stand-in harness, one thread per filter with libhb's bounded fifos between them; the source: 48 NV12 "
+                        "surfaces resident in HBM, walked round and round; the run ends on NV12 surfaces of the pool, dropped as they arrive",
+                "pcie_GBps": round((bus1[0] - bus0[0] + bus1[1] - bus0[1]) / dt / 1e9, 2),       # hbhip_ctx_bus_bytes: expected 0
+                "stage_thread_busy_fraction": busy, "n_out": n_out, "seconds": round(dt, 4),
+                "sample": f"{n_in} input frames after {n_warm} of warm-up -> {n_out} output frames credited ({n_late} more were "
+                          f"warm-up frames still in the pipe), {dt:.3f}s wall"}
     return {"value": round(n_out / dt, 2), "unit": "output frames/s", "input_fps": round(n_in / dt, 2),
             "path": "hb_filter_object_t chain (" + " -> ".join(c[0].replace("hb_filter_", "") for c in chain) + ") in the libhb "
                     "stand-in harness, one thread per filter with libhb's bounded fifos between them, pinned host "
@@ -102,13 +146,16 @@ def main():
     ap.add_argument("--content", default="interlaced", help="picture model of handbrake_amd/synth.py")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--feeders", type=int, default=4, help="threads of the source (copy pictures into pinned hb_buffer_t's)")
+    ap.add_argument("--surfaces", action="store_true",
+                    help="start and end the run on NV12 pictures resident in HBM (device surfaces) instead of host frames")
     a = ap.parse_args()
     os.environ["HBHIP_DEVICE"] = str(a.device)          # the drop-ins' shared context (libhb/hbhip_registry.c)
     sys.path.insert(0, ROOT)
     scale = None if a.scale == "none" else tuple(int(v) for v in a.scale.split("x"))
     try:
         res = run(a.workload, a.width, a.height, scale, cfg=a.cfg, n_in=a.frames,
-                  chain=chain_for(a.workload, scale, vfr=not a.no_vfr), content=a.content, feeders=a.feeders)
+                  chain=chain_for(a.workload, scale, vfr=not a.no_vfr, surfaces=a.surfaces), content=a.content,
+                  feeders=a.feeders, surfaces=a.surfaces)
     except Exception as e:                               # the caller never loses its own line over this pass
         res = {"error": repr(e), "n_out": 0, "seconds": 0.0}
     print(json.dumps(res), flush=True)

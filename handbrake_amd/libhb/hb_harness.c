@@ -552,6 +552,75 @@ int hbh_chain_feed(hbh_chain_t *c, const uint8_t *const *plane, const int stride
     return (started == 0 || f.pushed < count || c->failed) ? -2 : 0;
 }
 
+/* A frame that lies in device memory already (a hardware decoder's picture): a buffer without host planes whose storage is
+ * `surface`, an hbhip_surface whose reference the call takes over - the buffer's, dropped by whoever closes it (on failure:
+ * here, through the closing of the buffer). */
+static hb_buffer_t *surface_buffer(hbh_chain_t *c, void *surface, int flags, int64_t start, int64_t stop)
+{
+    hb_buffer_t *b = hb_buffer_init(0);
+    if (b == NULL) return NULL;
+    b->s.type = FRAME_BUF;
+    b->s.start = start;
+    b->s.stop = stop;
+    b->s.duration = (double)(stop - start);
+    b->s.flags = (uint16_t)flags;
+    b->f.fmt = c->init_in.pix_fmt;
+    b->f.width = c->init_in.geometry.width;
+    b->f.height = c->init_in.geometry.height;
+    b->f.max_plane = 1;
+    b->f.color_prim = c->init_in.color_prim;
+    b->f.color_transfer = c->init_in.color_transfer;
+    b->f.color_matrix = c->init_in.color_matrix;
+    b->f.color_range = c->init_in.color_range;
+    b->f.chroma_location = c->init_in.chroma_location;
+    b->storage = surface;
+    b->storage_type = HBHIP_SURFACE;
+    return b;
+}
+
+int hbh_chain_push_surface(hbh_chain_t *c, void *surface, int flags, int64_t pts)
+{
+    if (c == NULL || c->eof_seen || surface == NULL) return -1;
+    hb_buffer_t *b = surface_buffer(c, surface, flags, pts, pts + 3003);
+    if (b == NULL) return -1;
+    if (c->threaded) fifo_put(&c->fifo[0], b);
+    else             run_from(c, 0, b);
+    return c->failed ? -2 : 0;
+}
+
+/* the surface form of hbh_chain_feed: `count` buffers cycling through `n_unique` surfaces, each with a reference of its own
+ * that `retain` takes (the address of hbhip_surface_retain); nothing is copied, so one thread keeps up */
+int hbh_chain_feed_surfaces(hbh_chain_t *c, void *const *surfaces, int n_unique, int first, int count, int64_t duration,
+                            int flags, void (*retain)(void *))
+{
+    if (c == NULL || c->eof_seen || surfaces == NULL || retain == NULL || n_unique < 1 || count < 0) return -1;
+    for (int i = 0; i < count && !c->failed; i++)
+    {
+        const int64_t n = first + i;
+        void *s = surfaces[n % n_unique];
+        retain(s);
+        hb_buffer_t *b = surface_buffer(c, s, flags, n * duration, (n + 1) * duration);
+        if (b == NULL) return -1;
+        if (c->threaded) fifo_put(&c->fifo[0], b);
+        else             run_from(c, 0, b);
+    }
+    return c->failed ? -2 : 0;
+}
+
+/* The next output when it is a surface buffer: 0, *surface = its hbhip_surface (the buffer's reference goes to the caller)
+ * and the buffer is gone; 1: the next output is something else (a host frame, EOF) and stays; -1: nothing queued. */
+int hbh_chain_pop_surface(hbh_chain_t *c, void **surface)
+{
+    hb_buffer_t *b = c ? hb_buffer_list_head(&c->out) : NULL;
+    if (b == NULL || surface == NULL) return -1;
+    if (b->storage_type != HBHIP_SURFACE) return 1;
+    b = hb_buffer_list_rem_head(&c->out);
+    *surface = b->storage;
+    b->storage = NULL;
+    hb_buffer_close(&b);
+    return 0;
+}
+
 int hbh_chain_push_eof(hbh_chain_t *c)
 {
     if (c == NULL || c->eof_seen) return -1;

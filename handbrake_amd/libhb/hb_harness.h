@@ -61,6 +61,15 @@ int  hbh_chain_push(hbh_chain_t *c, const uint8_t *const plane[3], const int str
  * filled by `nthreads` threads (the decoder's part in libhb), pushed in order; returns when the last one is in */
 int  hbh_chain_feed(hbh_chain_t *c, const uint8_t *const *plane, const int stride[3], int n_unique, int first, int count,
                     int64_t duration, int flags, int nthreads);
+/* Device surfaces at the ends of a chain (an hbhip_surface, include/hbhip.h; pix_fmt NV12 / P010LE): push takes over the
+ * caller's reference, shown from pts for 3003 ticks; the feeder takes a reference per buffer through `retain` (the address of
+ * hbhip_surface_retain) and numbers the buffers like hbh_chain_feed; pop hands the next output's surface and its reference
+ * to the caller - 1 when the next output is not a surface buffer (it stays), -1 when there is none.  hbh_chain_peek
+ * describes a surface buffer with nplanes = 0 (no host planes). */
+int  hbh_chain_push_surface(hbh_chain_t *c, void *surface, int flags, int64_t pts);
+int  hbh_chain_feed_surfaces(hbh_chain_t *c, void *const *surfaces, int n_unique, int first, int count, int64_t duration,
+                             int flags, void (*retain)(void *));
+int  hbh_chain_pop_surface(hbh_chain_t *c, void **surface);
 int  hbh_chain_push_eof(hbh_chain_t *c);
 int  hbh_chain_pending(hbh_chain_t *c);
 int  hbh_chain_peek(hbh_chain_t *c, hbh_frame_info_t *info);

@@ -595,6 +595,17 @@ void hbhip_rt_set_storage_hooks(void (*retain)(void *), void (*release)(void *))
     g_storage_release = release;
 }
 
+/* The second device storage type, HBHIP_SURFACE: an NV12 / P010LE picture in device memory (an hbhip_surface) at the two
+ * ends of a run - what a hardware decoder hands over and a hardware encoder takes.  Shared by reference like the first. */
+static void (*g_surface_release)(void *) = NULL;
+static void (*g_surface_retain)(void *) = NULL;
+
+void hbhip_rt_set_surface_hooks(void (*retain)(void *), void (*release)(void *))
+{
+    g_surface_retain = retain;
+    g_surface_release = release;
+}
+
 void hb_buffer_close(hb_buffer_t **pb)
 {
     if (pb == NULL) return;
@@ -604,6 +615,8 @@ void hb_buffer_close(hb_buffer_t **pb)
         hb_buffer_t *next = b->next;
         if (b->storage_type == HBHIP_DEVICE && b->storage && g_storage_release)
             g_storage_release(b->storage);
+        if (b->storage_type == HBHIP_SURFACE && b->storage && g_surface_release)
+            g_surface_release(b->storage);
         if (b->data && b->storage_type == STANDARD)
         {
             if (b->hooked_alloc && g_big_free) g_big_free(b->data, b->alloc);
@@ -634,7 +647,7 @@ int hb_buffer_copy(hb_buffer_t *dst, const hb_buffer_t *src)
 hb_buffer_t *hb_buffer_dup(const hb_buffer_t *src)
 {
     if (src == NULL) return NULL;
-    if (src->storage_type == HBHIP_DEVICE)
+    if (src->storage_type == HBHIP_DEVICE || src->storage_type == HBHIP_SURFACE)
     {
         /* share the device picture, like av_frame_ref in the reference's AVFRAME case (fifo.c:668-714) */
         hb_buffer_t *b = hb_buffer_init(0);
@@ -643,8 +656,9 @@ hb_buffer_t *hb_buffer_dup(const hb_buffer_t *src)
         b->f = src->f;
         memcpy(b->plane, src->plane, sizeof(b->plane));
         b->storage = src->storage;
-        b->storage_type = HBHIP_DEVICE;
-        if (g_storage_retain) g_storage_retain(b->storage);
+        b->storage_type = src->storage_type;
+        void (*retain)(void *) = src->storage_type == HBHIP_DEVICE ? g_storage_retain : g_surface_retain;
+        if (retain) retain(b->storage);
         return b;
     }
     hb_buffer_t *b = hb_buffer_init(src->size);

@@ -80,6 +80,19 @@ static inline hbhip_frame *hbhip_host_frame_of(const hb_buffer_t *b)
 {
     return b->storage_type == HBHIP_DEVICE ? (hbhip_frame *)b->storage : NULL;
 }
+/* The second storage type, at the two ends of a run only: an NV12 / P010LE picture that lies in device memory already (a
+ * hardware decoder's) or stays there (for a hardware encoder).  `storage` is an hbhip_surface*; the buffer has no host
+ * planes, f.fmt says NV12 or P010LE.  The reference's COREMEDIA buffers are the precedent again (vt_common.c:413-416).
+ * The upload adapter imports such a buffer, the download adapter emits them under surface=1; nothing in between sees one. */
+#if defined(HBHIP_IN_LIBHB) && defined(HBHIP_DEVICE) && !defined(HBHIP_SURFACE)
+#define HBHIP_SURFACE (HBHIP_DEVICE + 1)      /* a build that spells INTEGRATION.md's enumerators as -D: the second follows the first */
+#endif
+static inline hbhip_surface *hbhip_host_surface_of(const hb_buffer_t *b)
+{
+    return b->storage_type == HBHIP_SURFACE ? (hbhip_surface *)b->storage : NULL;
+}
+/* hb_buffer_t shell around a surface (takes over the caller's reference): f.fmt = o->pix_fmt, NV12 / P010LE */
+hb_buffer_t *hbhip_host_wrap_surface(hbhip_surface *s, const hb_filter_init_t *o, int width, int height);
 /* HBHIP_ZERO_COPY=0: the drop-ins of a device-resident run copy frames into and out of pictures of their own again
  * (hbhip_filter_push_dev / pull_dev) instead of adopting them (hbhip_filter_use_frames) - for A/B measurements */
 static inline int hbhip_host_zero_copy(void) { const char *e = getenv("HBHIP_ZERO_COPY"); return e == NULL || atoi(e) != 0; }

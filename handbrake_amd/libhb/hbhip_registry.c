@@ -267,10 +267,14 @@ static void pinned_release(void *p, size_t size)
     if (p != NULL) hbhip_host_free(p);
 }
 
+static void surface_retain(void *s)  { hbhip_surface_retain((hbhip_surface *)s); }
+static void surface_release(void *s) { hbhip_surface_release((hbhip_surface *)s); }
+
 __attribute__((constructor)) static void hbhip_host_register_hooks(void)
 {
 #ifndef HBHIP_IN_LIBHB
     hbhip_rt_set_storage_hooks(storage_retain, storage_release);
+    hbhip_rt_set_surface_hooks(surface_retain, surface_release);
     hbhip_rt_set_job_hooks(hb_hip_setup_hw_filters, hb_hip_filter_init_failed, hb_hip_job_close);   /* inside libhb work.c calls them itself */
     /* inside libhb: `case AV_PIX_FMT_HBHIP:` in vfr.c:76-108 and rendersub.c:1129-1161 */
     hbhip_rt_register_hw_helper(0, AV_PIX_FMT_HBHIP, &hb_motion_metric_hip);
@@ -313,6 +317,39 @@ hb_buffer_t *hbhip_host_wrap_frame(hbhip_frame *fr, const hb_filter_init_t *o, i
     (void)desc;
     b->storage = fr;
     b->storage_type = HBHIP_DEVICE;
+    return b;
+}
+
+hb_buffer_t *hbhip_host_wrap_surface(hbhip_surface *s, const hb_filter_init_t *o, int width, int height)
+{
+    hb_buffer_t *b = hb_buffer_init(0);
+    if (b == NULL)
+    {
+        hbhip_surface_release(s);
+        return NULL;
+    }
+    b->s.type = FRAME_BUF;
+    b->f.fmt = o->pix_fmt;
+    b->f.width = width;
+    b->f.height = height;
+    b->f.max_plane = 1;
+    b->f.color_prim = o->color_prim;
+    b->f.color_transfer = o->color_transfer;
+    b->f.color_matrix = o->color_matrix;
+    b->f.color_range = o->color_range;
+    b->f.chroma_location = o->chroma_location;
+    hbhip_dev_surface d;
+    hbhip_surface_describe(s, &d, NULL, NULL, NULL);
+    for (int p = 0; p < 2; p++)
+    {
+        b->plane[p].data = NULL;                       /* not host-addressable */
+        b->plane[p].stride = d.pitch[p];
+        b->plane[p].width = hb_image_width(o->pix_fmt, width, p);
+        b->plane[p].height = hb_image_height(o->pix_fmt, height, p);
+        b->plane[p].size = 0;
+    }
+    b->storage = s;
+    b->storage_type = HBHIP_SURFACE;
     return b;
 }
 
@@ -672,6 +709,7 @@ struct hb_filter_private_s
     hb_filter_init_t output;
     int              depth, lcw, lch;
     int              biplanar;            /* the host side of this adapter is NV12 / P010LE: repacked on the GPU */
+    int              surface;             /* download, surface=1: the NV12 / P010LE pictures it emits stay in device memory */
     hbhip_ctx       *ctx;                 /* the job's GPU (hbhip_host_ctx_for) */
     dl_slot_t        dl[DL_DEPTH + 1];
     int              dl_head, dl_count;
@@ -681,7 +719,11 @@ struct hb_filter_private_s
 
 /* Biplanar host pictures exist at the two ends of a run only: device frames are planar (the one layout every kernel here
  * reads).  The upload adapter takes NV12 / P010LE as the stream's format and hands YUV420P / YUV420P10LE on; the download
- * adapter's one setting, format=nv12 | p010le, makes it emit those from a 4:2:0 run of 8 / 10 bits. */
+ * adapter's setting format=nv12 | p010le makes it emit those from a 4:2:0 run of 8 / 10 bits.
+ * Device surfaces (HBHIP_SURFACE buffers) are the same two formats without the bus: an upload adapter initialised for NV12 /
+ * P010LE imports a buffer that holds one (a hardware decoder's picture), and the download adapter under
+ * format=nv12 | p010le:surface=1 emits them (for a hardware encoder), from the context's pool, laid out as a video engine's
+ * allocator would (256-byte pitch, 16 padded rows). */
 static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int to_device)
 {
     hb_filter_private_t *pv = calloc(1, sizeof(*pv));
@@ -716,6 +758,14 @@ static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int 
         }
     }
     free(want);
+    int surface = 0;
+    if (!to_device && hb_dict_extract_bool(&surface, filter->settings, "surface") && surface && !hbhip_host_is_biplanar(host_fmt))
+    {
+        hb_error("hipdownload: surface=1 needs format=nv12 or format=p010le");
+        free(pv);
+        return 1;
+    }
+    pv->surface = surface != 0;
     if (hbhip_host_is_biplanar(host_fmt))
     {
         if (init->geometry.width < 2 || init->geometry.height < 2)
@@ -749,7 +799,7 @@ static hb_buffer_t *dl_collect(hb_filter_private_t *pv)
     dl_slot_t s = pv->dl[pv->dl_head];
     pv->dl_head = (pv->dl_head + 1) % (DL_DEPTH + 1);
     pv->dl_count--;
-    const int rc = hbhip_frame_download_wait(hbhip_host_frame_of(s.in), s.token);
+    const int rc = hbhip_frame_download_wait(hbhip_host_frame_of(s.in), s.token);      /* a D2H copy or an export: the same token */
     hb_buffer_copy_props(s.out, s.in);
     hb_buffer_close(&s.in);
     if (rc != HBHIP_OK) hb_buffer_close(&s.out);
@@ -798,6 +848,12 @@ static int upload_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buff
         *buf_in = NULL;
         return (in->s.flags & HB_BUF_FLAG_EOF) ? HB_FILTER_DONE : HB_FILTER_OK;
     }
+    hbhip_surface *sf = hbhip_host_surface_of(in);
+    if (sf != NULL && !pv->biplanar)
+    {
+        hb_error("hipupload: a device surface on an adapter that was not initialised for NV12 / P010LE");
+        return HB_FILTER_FAILED;
+    }
     if (ul_retire(pv, 0) != HBHIP_OK) return HB_FILTER_FAILED;       /* makes room: waits for the oldest copy when the ring is full */
     hbhip_frame *fr = NULL;
     hbhip_host_frame hf;
@@ -807,8 +863,10 @@ static int upload_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buff
     void *token = NULL;
     hbhip_host_biplanar hb;
     hbhip_host_biplanar_from_buf(&hb, in);
-    if ((pv->biplanar ? hbhip_frame_upload_biplanar_async(fr, &hb, &token)
-                      : hbhip_frame_upload_async(fr, &hf, &token)) != HBHIP_OK)
+    /* a surface buffer stays in the ring like a host buffer: until the split has read it */
+    if ((sf != NULL     ? hbhip_frame_import_surface_async(fr, sf, &token) :
+         pv->biplanar   ? hbhip_frame_upload_biplanar_async(fr, &hb, &token)
+                        : hbhip_frame_upload_async(fr, &hf, &token)) != HBHIP_OK)
     {
         hbhip_frame_release(fr);
         return HB_FILTER_FAILED;
@@ -850,21 +908,38 @@ static int download_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_bu
         *buf_in = NULL;
         return (in->s.flags & HB_BUF_FLAG_EOF) ? HB_FILTER_DONE : HB_FILTER_OK;
     }
-#ifndef HBHIP_IN_LIBHB
-    hbhip_rt_next_buffer_uninitialised();               /* the copy fills it (libhb's own hb_buffer_init never clears) */
-#endif
-    hb_buffer_t *out = hbhip_host_alloc_out(&pv->output, in->f.width, in->f.height);
-    if (out == NULL) return HB_FILTER_FAILED;
-    hbhip_host_frame hf;
-    hbhip_host_frame_from_buf(&hf, out);
+    hb_buffer_t *out = NULL;
     void *token = NULL;
-    hbhip_host_biplanar hb;
-    hbhip_host_biplanar_from_buf(&hb, out);
-    if ((pv->biplanar ? hbhip_frame_download_biplanar_async(fr, &hb, &token)
-                      : hbhip_frame_download_async(fr, &hf, &token)) != HBHIP_OK)
+    if (pv->surface)
     {
-        hb_buffer_close(&out);
-        return HB_FILTER_FAILED;
+        /* the merge writes a surface of the pool; it goes back there when the consumer closes the buffer */
+        hbhip_surface *sf = NULL;
+        if (hbhip_surface_alloc(pv->ctx, in->f.width, in->f.height, pv->depth, 256, 16, &sf) != HBHIP_OK) return HB_FILTER_FAILED;
+        out = hbhip_host_wrap_surface(sf, &pv->output, in->f.width, in->f.height);
+        if (out == NULL) return HB_FILTER_FAILED;
+        if (hbhip_frame_export_surface_async(fr, sf, &token) != HBHIP_OK)
+        {
+            hb_buffer_close(&out);
+            return HB_FILTER_FAILED;
+        }
+    }
+    else
+    {
+#ifndef HBHIP_IN_LIBHB
+        hbhip_rt_next_buffer_uninitialised();           /* the copy fills it (libhb's own hb_buffer_init never clears) */
+#endif
+        out = hbhip_host_alloc_out(&pv->output, in->f.width, in->f.height);
+        if (out == NULL) return HB_FILTER_FAILED;
+        hbhip_host_frame hf;
+        hbhip_host_frame_from_buf(&hf, out);
+        hbhip_host_biplanar hb;
+        hbhip_host_biplanar_from_buf(&hb, out);
+        if ((pv->biplanar ? hbhip_frame_download_biplanar_async(fr, &hb, &token)
+                          : hbhip_frame_download_async(fr, &hf, &token)) != HBHIP_OK)
+        {
+            hb_buffer_close(&out);
+            return HB_FILTER_FAILED;
+        }
     }
     dl_slot_t *s = &pv->dl[(pv->dl_head + pv->dl_count) % (DL_DEPTH + 1)];
     s->in = in; s->out = out; s->token = token;
@@ -894,7 +969,7 @@ hb_filter_object_t hb_filter_hip_download =
     .enforce_order = 0,
     .name          = "HIP download adapter",
     .short_name    = "hipdownload",
-    .settings_template = "format=^(nv12|p010le)$",
+    .settings_template = "format=^(nv12|p010le)$:surface=^([01])$",
     .init          = download_init,
     .work          = download_work,
     .close         = adapter_close,

@@ -155,6 +155,46 @@ int  hbhip_frame_download_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *d
 int  hbhip_frame_upload_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *src, void **token);
 int  hbhip_frame_download_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *dst, void **token);
 
+/* ---- device surfaces: NV12 / P010LE pictures that already are, or stay, in HBM ------------------------------------------
+ * What AMD's decoder hands out and AMF / VCE take in, without the host copy: a surface has a pitch of its own per plane
+ * (any multiple of 16 that holds the row), rows padded as its maker likes, and its two planes in one allocation or two.
+ * Import repacks a surface into a planar 4:2:0 frame (depth 8: NV12, depth 10: P010LE, samples >> 6), export the other way
+ * (<< 6, low six bits zero), one kernel each (csrc/biplanar.hip), nothing over the bus.
+ *  * Import writes every byte of the frame's rows, row padding included: what the surface's row holds as far as its pitch
+ *    reaches, zero beyond.  It reads nothing outside pitch * rows of either plane.
+ *  * Export writes the first align16(row bytes) bytes of each of the height / ceil(height / 2) sample rows (row bytes:
+ *    width * bps, and 2 * ceil(width / 2) * bps) and nothing else of the surface.
+ * Ordering is the frames' (hbhip_core.hip, "How frames are ordered"): an import runs on the frame's context's upload
+ * stream behind the surface's contents - the last export into it, or the event of hbhip_surface_set_ready_event - and is
+ * the frame's ready mark; an export runs on the download stream behind the frame's contents and every earlier import of the
+ * surface, and is the surface's ready mark.  Nothing waits on the host; the library keeps a reference of its own on the
+ * surface from the call until the queued kernel has finished.
+ * Refused before anything is queued - HBHIP_ERR_UNSUPPORTED: a depth other than 8 / 10, a frame that is not 4:2:0, a
+ * surface of another depth or size than the frame, a width or height below 2, a plane address or pitch that is no
+ * multiple of 16; HBHIP_ERR_ARG: a pitch below the row bytes, planes that overlap, a surface of another GPU than the frame. */
+typedef struct hbhip_dev_surface { void *plane[2]; int pitch[2]; } hbhip_dev_surface;   /* NV12 (depth 8) / P010LE (depth 10), device memory */
+typedef struct hbhip_surface hbhip_surface;                                             /* reference-counted */
+/* library-owned, recycled through a per-context pool like frames.  pitch_align >= 16 and a power of two; rows_align >= 1:
+ * plane 1 starts at pitch * align(height, rows_align).  (256, 16) is what a video engine's allocator gives. */
+int  hbhip_surface_alloc(hbhip_ctx *ctx, int width, int height, int depth, int pitch_align, int rows_align, hbhip_surface **out);
+/* caller-owned memory (a decoder's picture): release(opaque) is called when the last reference has gone and nothing queued
+ * reads or writes the memory any more - from whichever call of the library notices that first (the token calls,
+ * hbhip_ctx_sync, the surface calls) */
+int  hbhip_surface_wrap(hbhip_ctx *ctx, const hbhip_dev_surface *mem, int width, int height, int depth,
+                        void (*release)(void *), void *opaque, hbhip_surface **out);
+void hbhip_surface_retain(hbhip_surface *s);
+void hbhip_surface_release(hbhip_surface *s);
+int  hbhip_surface_describe(hbhip_surface *s, hbhip_dev_surface *out, int *width, int *height, int *depth);
+/* a wrapped surface whose producer is still running: the hipEvent_t (as void*) the first reader has to wait for */
+int  hbhip_surface_set_ready_event(hbhip_surface *s, void *hip_event);
+int  hbhip_frame_import_surface(hbhip_frame *fr, hbhip_surface *src);
+int  hbhip_frame_import_surface_async(hbhip_frame *fr, hbhip_surface *src, void **token);   /* finished with hbhip_ctx_upload_done */
+int  hbhip_frame_export_surface(hbhip_frame *fr, hbhip_surface *dst);
+int  hbhip_frame_export_surface_async(hbhip_frame *fr, hbhip_surface *dst, void **token);   /* finished with hbhip_frame_download_wait */
+/* bytes the frame upload / download entry points (hbhip_frame_upload*, hbhip_frame_download*) have queued over the bus on
+ * this context */
+int  hbhip_ctx_bus_bytes(hbhip_ctx *ctx, uint64_t *h2d, uint64_t *d2h);
+
 /* ---- frames in, frames out: what a drop-in inside a device-resident run uses instead of push_dev / pull_dev -----------
  * hbhip_filter_use_frames(f) (once, before the first push): the filter's pictures are frames of its context's pool.
  * hbhip_filter_push_frame: the frame becomes the filter's input picture without a copy (the filter holds a reference of its

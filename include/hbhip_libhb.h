@@ -246,7 +246,7 @@ struct hb_buffer_s
     } plane[4];
 
     void *storage;
-    enum { STANDARD, AVFRAME, COREMEDIA, HBHIP_DEVICE } storage_type;
+    enum { STANDARD, AVFRAME, COREMEDIA, HBHIP_DEVICE, HBHIP_SURFACE } storage_type;
 
     hb_buffer_t *palette;
     void       **side_data;
@@ -282,6 +282,8 @@ int          hb_buffer_is_writable(const hb_buffer_t *buf);       /* fifo.c:624-
 void         hb_compute_chroma_smoothing_coefficient(uint32_t chroma_coeffs[2][4], int pix_fmt, int chroma_location);
 /* stand-in runtime only: how to share / drop an HBHIP_DEVICE storage handle */
 void         hbhip_rt_set_storage_hooks(void (*retain)(void *), void (*release)(void *));
+/* ... and an HBHIP_SURFACE one (an hbhip_surface: an NV12 / P010LE picture in device memory) */
+void         hbhip_rt_set_surface_hooks(void (*retain)(void *), void (*release)(void *));
 /* stand-in runtime only: allocator for frame-sized buffer payloads (page-locked pool) */
 void         hbhip_rt_set_alloc_hooks(void *(*alloc)(size_t), void (*release)(void *, size_t));
 void         hbhip_rt_next_buffer_uninitialised(void);   /* the next hb_buffer_init on this thread leaves its payload as it is */

@@ -2,12 +2,20 @@
 """NV12 / P010LE at the ends of a run: what the repack kernels and the adapters cost.
 
   repack [out.json]       64 frames of 1920 x 1080 and of 3840 x 2160, at 8 and 10 bits, through hbhip_frame_upload_biplanar /
-                          hbhip_frame_download_biplanar; writes the box's copy ceiling (hbhip_ctx_copy_bandwidth) and the
+                          hbhip_frame_download_biplanar (the staging pair) and through hbhip_frame_import_surface /
+                          hbhip_frame_export_surface on a surface with a 256-byte pitch and 16 padded rows (the surface pair:
+                          the same bytes, no host copy); writes the box's copy ceiling (hbhip_ctx_copy_bandwidth) and the
                           bytes a kernel must move per frame.  Meant to run under
                           `rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o NAME -- python tools/biplanar_rates.py repack DIR/repack.json`
   summarize TRACE.csv REPACK.json
                           the kernel trace of that run, per kernel and frame size: mean time, achieved GB/s and the fraction
                           of the copy ceiling - what tools/kernel_rooflines.py reports for the other secondary kernels
+  company                 the surface pair in two kinds of company, 64 rounds each, at the two points with 3 840-byte rows (2160p
+                          8 bits, 1080p 10 bits): A, export and import back to back; B, between the bus copies the staging
+                          pair runs between (upload_biplanar, export, import, download_biplanar).  Under rocprofv3 as above
+  company-summarize TRACE.csv
+                          per kernel [mean, min, median] µs: the surface kernels' first 64 launches (A) and next 64 (B), the
+                          staging kernels of loop B
   adapters [frames]       [upload, lapsharp, download] at 1080p through the plugin surface (a thread per filter, pinned
                           hb_buffer_t in and out, as handbrake_amd/hostpath.py runs its lists): NV12 in and out against
                           planar 8 bits, three runs each, alternated
@@ -53,6 +61,11 @@ def repack(out_path):
             for _ in range(res["frames"]):
                 hip.check(L.hbhip_frame_upload_biplanar(fr, C.byref(hb)), ctx.h, "upload_biplanar")
                 hip.check(L.hbhip_frame_download_biplanar(fr, C.byref(hb)), ctx.h, "download_biplanar")
+            surface = hip.Surface(ctx, w, h, depth)
+            for _ in range(res["frames"]):
+                hip.check(L.hbhip_frame_export_surface(fr, surface.h), ctx.h, "export_surface")
+                hip.check(L.hbhip_frame_import_surface(fr, surface.h), ctx.h, "import_surface")
+            surface.close()
             L.hbhip_frame_release(fr)
             # a kernel reads one layout and writes the other: the samples of the frame twice
             res["cases"].append({"width": w, "height": h, "depth": depth, "bytes_per_frame": 2 * (w * h * 3 // 2) * bps})
@@ -68,13 +81,15 @@ def summarize(trace, repack_json):
     ceiling = info["copy_ceiling_GBps"]
     groups = {}
     for r in csv.DictReader(open(trace)):
-        m = re.search(r"(bi_split_kernel|bi_merge_kernel)<([^>]*)>", r["Kernel_Name"])
+        m = re.search(r"(bi_split_kernel|bi_merge_kernel|bi_surface_split_kernel|bi_surface_merge_kernel)<([^>]*)>", r["Kernel_Name"])
         if not m:
             continue
         depth = 8 if "char" in m.group(2) else 10
-        groups.setdefault((m.group(1), depth, int(r["Grid_Size_X"])), []).append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
+        # what tells the two frame sizes apart: the staging kernels' grids are one-dimensional, the surface kernels' rows are on y
+        size = int(r["Grid_Size_Y"] if "surface" in m.group(1) else r["Grid_Size_X"])
+        groups.setdefault((m.group(1), depth, size), []).append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
     out = {"copy_ceiling_GBps": ceiling, "kernels": []}
-    for kernel in ("bi_split_kernel", "bi_merge_kernel"):
+    for kernel in ("bi_split_kernel", "bi_merge_kernel", "bi_surface_split_kernel", "bi_surface_merge_kernel"):
         for depth in (8, 10):
             grids = sorted(g for k, d, g in groups if k == kernel and d == depth)        # the smaller grid is the smaller frame
             for (w, h), grid in zip(SIZES, grids):
@@ -86,6 +101,47 @@ def summarize(trace, repack_json):
                                        "avg_us": round(us, 2), "min_us": round(min(ns) / 1e3, 2),
                                        "bytes_per_launch": case["bytes_per_frame"], "achieved_GBps": round(gbps, 1),
                                        "frac_of_copy_ceiling": round(gbps / ceiling, 4)})
+    print(json.dumps(out, indent=1))
+
+
+def company():
+    from handbrake_amd import hip
+    L = hip.lib()
+    ctx = hip.Ctx(0)
+    rng = np.random.default_rng(1)
+    for w, h, depth, bps in ((3840, 2160, 8, 1), (1920, 1080, 10, 2)):
+        pitch = align64(w * bps)
+        host = rng.integers(0, 256, pitch * (h + h // 2), dtype=np.uint8)
+        hb = hip.HostBiplanar()
+        hb.plane[0], hb.plane[1] = host.ctypes.data, host.ctypes.data + pitch * h
+        hb.stride[0] = hb.stride[1] = pitch
+        fr = C.c_void_p()
+        hip.check(L.hbhip_frame_alloc(ctx.h, w, h, depth, 1, 1, C.byref(fr)), ctx.h, "frame_alloc")
+        surface = hip.Surface(ctx, w, h, depth)
+        hip.check(L.hbhip_frame_upload_biplanar(fr, C.byref(hb)), ctx.h, "upload_biplanar")
+        for _ in range(64):                                                   # A
+            hip.check(L.hbhip_frame_export_surface(fr, surface.h), ctx.h, "export_surface")
+            hip.check(L.hbhip_frame_import_surface(fr, surface.h), ctx.h, "import_surface")
+        for _ in range(64):                                                   # B
+            hip.check(L.hbhip_frame_upload_biplanar(fr, C.byref(hb)), ctx.h, "upload_biplanar")
+            hip.check(L.hbhip_frame_export_surface(fr, surface.h), ctx.h, "export_surface")
+            hip.check(L.hbhip_frame_import_surface(fr, surface.h), ctx.h, "import_surface")
+            hip.check(L.hbhip_frame_download_biplanar(fr, C.byref(hb)), ctx.h, "download_biplanar")
+        surface.close()
+        L.hbhip_frame_release(fr)
+    ctx.close()
+
+
+def company_summarize(trace):
+    seq = {}
+    for r in sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"])):
+        m = re.search(r"(bi_split_kernel|bi_merge_kernel|bi_surface_split_kernel|bi_surface_merge_kernel)<([^>]*)>", r["Kernel_Name"])
+        if m:
+            seq.setdefault((m.group(1), 8 if "char" in m.group(2) else 10), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    stats = lambda v: [round(float(np.mean(v)), 2), round(min(v), 2), round(float(np.median(v)), 2)]
+    out = {}
+    for (k, d), v in seq.items():
+        out[f"{k} {d}"] = {"A_back_to_back": stats(v[:64]), "B_between_copies": stats(v[64:128])} if "surface" in k else {"B": stats(v)}
     print(json.dumps(out, indent=1))
 
 
@@ -140,6 +196,10 @@ if __name__ == "__main__":
         repack(sys.argv[2] if len(sys.argv) > 2 else None)
     elif mode == "summarize":
         summarize(sys.argv[2], sys.argv[3])
+    elif mode == "company":
+        company()
+    elif mode == "company-summarize":
+        company_summarize(sys.argv[2])
     elif mode == "adapters":
         adapters(int(sys.argv[2]) if len(sys.argv) > 2 else 1024)
     else:
