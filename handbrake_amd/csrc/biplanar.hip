@@ -60,6 +60,25 @@ template <typename PIX> __device__ __forceinline__ unsigned to_biplanar(unsigned
     return sizeof(PIX) == 2 ? (v << 6) & 0xffc0ffc0u : v;
 }
 
+// The arithmetic of one 16-byte unit of the merges, shared by the staging kernel and the surface kernel (they differ in
+// addressing only): a luma unit, and 8 bytes of Cb and 8 of Cr into an interleaved unit.  The two splits keep theirs in
+// their bodies: through such functions the compiler allots bi_surface_split_kernel's registers and orders its shifts
+// another way, and the kernels are held to the instructions they had.
+template <typename PIX> __device__ __forceinline__ uint4 luma_to_biplanar(uint4 v)
+{
+    v.x = to_biplanar<PIX>(v.x); v.y = to_biplanar<PIX>(v.y); v.z = to_biplanar<PIX>(v.z); v.w = to_biplanar<PIX>(v.w);
+    return v;
+}
+template <typename PIX> __device__ __forceinline__ uint4 chroma_merge(uint2 cb, uint2 cr)
+{
+    uint4 v;
+    v.x = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.x, cb.x, Sel<PIX>::zip_lo));
+    v.y = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.x, cb.x, Sel<PIX>::zip_hi));
+    v.z = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.y, cb.y, Sel<PIX>::zip_lo));
+    v.w = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.y, cb.y, Sel<PIX>::zip_hi));
+    return v;
+}
+
 template <typename PIX>
 __global__ __launch_bounds__(256) void bi_split_kernel(BiRepack a)
 {
@@ -93,9 +112,8 @@ __global__ __launch_bounds__(256) void bi_merge_kernel(BiRepack a)
     const unsigned u = blockIdx.x * 256u + threadIdx.x;
     if (u < a.luma_units)
     {
-        uint4 v = *reinterpret_cast<const uint4 *>(a.plane[0] + (size_t)u * 16);
-        v.x = to_biplanar<PIX>(v.x); v.y = to_biplanar<PIX>(v.y); v.z = to_biplanar<PIX>(v.z); v.w = to_biplanar<PIX>(v.w);
-        *reinterpret_cast<uint4 *>(a.stage + (size_t)u * 16) = v;
+        const uint4 v = *reinterpret_cast<const uint4 *>(a.plane[0] + (size_t)u * 16);
+        *reinterpret_cast<uint4 *>(a.stage + (size_t)u * 16) = luma_to_biplanar<PIX>(v);
         return;
     }
     const unsigned c = u - a.luma_units;
@@ -104,12 +122,7 @@ __global__ __launch_bounds__(256) void bi_merge_kernel(BiRepack a)
     const size_t at = (size_t)row * a.cpitch + (size_t)col * 8;
     const uint2 cb = *reinterpret_cast<const uint2 *>(a.plane[1] + at);
     const uint2 cr = *reinterpret_cast<const uint2 *>(a.plane[2] + at);
-    uint4 v;
-    v.x = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.x, cb.x, Sel<PIX>::zip_lo));
-    v.y = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.x, cb.x, Sel<PIX>::zip_hi));
-    v.z = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.y, cb.y, Sel<PIX>::zip_lo));
-    v.w = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.y, cb.y, Sel<PIX>::zip_hi));
-    *reinterpret_cast<uint4 *>(a.stage + (size_t)a.luma_units * 16 + (size_t)row * a.spitch1 + (size_t)col * 16) = v;
+    *reinterpret_cast<uint4 *>(a.stage + (size_t)a.luma_units * 16 + (size_t)row * a.spitch1 + (size_t)col * 16) = chroma_merge<PIX>(cb, cr);
 }
 
 // The same repack between a planar frame and a device surface (hbhip_surface): a picture whose two planes have a pitch of
@@ -170,9 +183,8 @@ __global__ __launch_bounds__(256) void bi_surface_merge_kernel(BiSurface a)
     if (blockIdx.y < a.rows0)
     {
         if (u >= a.units[0]) return;
-        uint4 v = *reinterpret_cast<const uint4 *>(a.plane[0] + (size_t)blockIdx.y * a.fpitch[0] + (size_t)u * 16);
-        v.x = to_biplanar<PIX>(v.x); v.y = to_biplanar<PIX>(v.y); v.z = to_biplanar<PIX>(v.z); v.w = to_biplanar<PIX>(v.w);
-        *reinterpret_cast<uint4 *>(a.splane[0] + (size_t)blockIdx.y * a.spitch[0] + (size_t)u * 16) = v;
+        const uint4 v = *reinterpret_cast<const uint4 *>(a.plane[0] + (size_t)blockIdx.y * a.fpitch[0] + (size_t)u * 16);
+        *reinterpret_cast<uint4 *>(a.splane[0] + (size_t)blockIdx.y * a.spitch[0] + (size_t)u * 16) = luma_to_biplanar<PIX>(v);
         return;
     }
     if (u >= a.units[1]) return;
@@ -180,12 +192,7 @@ __global__ __launch_bounds__(256) void bi_surface_merge_kernel(BiSurface a)
     const size_t at = (size_t)row * a.fpitch[1] + (size_t)u * 8;
     const uint2 cb = *reinterpret_cast<const uint2 *>(a.plane[1] + at);
     const uint2 cr = *reinterpret_cast<const uint2 *>(a.plane[2] + at);
-    uint4 v;
-    v.x = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.x, cb.x, Sel<PIX>::zip_lo));
-    v.y = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.x, cb.x, Sel<PIX>::zip_hi));
-    v.z = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.y, cb.y, Sel<PIX>::zip_lo));
-    v.w = to_biplanar<PIX>(__builtin_amdgcn_perm(cr.y, cb.y, Sel<PIX>::zip_hi));
-    *reinterpret_cast<uint4 *>(a.splane[1] + (size_t)row * a.spitch[1] + (size_t)u * 16) = v;
+    *reinterpret_cast<uint4 *>(a.splane[1] + (size_t)row * a.spitch[1] + (size_t)u * 16) = chroma_merge<PIX>(cb, cr);
 }
 
 template <typename PIX>

@@ -287,82 +287,97 @@ static size_t layout_bytes(const DevPicture *p)
 {
     return (size_t)(p->plane[2] - p->plane[0]) + (size_t)p->pitch[2] * p->height[2];
 }
-// what the copy of a frame between `p` and host planes moves over the bus (hbhip_ctx_bus_bytes): the one block, else the
-// rows of the 2-D copies - up with the host's row padding as far as our pitch reaches, down the samples only
-static size_t copy_bytes(const DevPicture *p, uint8_t *const plane[3], const int stride[3], bool up)
+static bool host_planes_ok(const DevPicture *p, const hbhip_host_frame *hf)
 {
-    if (same_layout(p, plane, stride)) return layout_bytes(p);
-    size_t n = 0;
     for (int c = 0; c < 3; c++)
-        n += (size_t)(up ? std::min(stride[c], p->pitch[c]) : p->width[c] * p->bps) * p->height[c];
-    return n;
+        if (hf->plane[c] == nullptr || hf->stride[c] < p->width[c] * p->bps) return false;
+    return true;
 }
 
-// the H2D copy of a frame queued on the context's upload stream, and an event behind it (from the context's pool: the
-// caller gives it back with sync_ev_put once it has fired)
-static int hbhip_copy_h2d_queue(hbhip_ctx *ctx, DevPicture *dst, const hbhip_host_frame *src, hipEvent_t *done_out)
+// The copy of a picture from / into host planes, queued on `stream`; *moved: what it sends over the bus (hbhip_ctx_bus_bytes).
+// `one_block`: a host picture laid out like ours moves whole, row padding included.  The ends of a run and push say yes;
+// pull and the submit pipe say no, as they always have: what their callers find in their row padding must not change.
+static hipError_t queue_h2d(DevPicture *dst, const hbhip_host_frame *src, bool one_block, hipStream_t stream, size_t *moved)
 {
-    for (int c = 0; c < 3; c++)
-        if (src->plane[c] == nullptr || src->stride[c] < dst->width[c] * dst->bps) return HBHIP_ERR_ARG;
+    *moved = one_block && same_layout(dst, src->plane, src->stride) ? layout_bytes(dst) : 0;
+    if (*moved) return hipMemcpyAsync(dst->plane[0], src->plane[0], *moved, hipMemcpyHostToDevice, stream);
+    hipError_t e = hipSuccess;
+    for (int c = 0; c < 3 && e == hipSuccess; c++)
+    {
+        const size_t row = (size_t)std::min(src->stride[c], dst->pitch[c]);     // the host's row padding, as far as our pitch reaches
+        e = hipMemcpy2DAsync(dst->plane[c], dst->pitch[c], src->plane[c], src->stride[c], row, dst->height[c], hipMemcpyHostToDevice, stream);
+        *moved += row * dst->height[c];
+    }
+    return e;
+}
+
+static hipError_t queue_d2h(const hbhip_host_frame *dst, const DevPicture *src, bool one_block, hipStream_t stream, size_t *moved)
+{
+    *moved = one_block && same_layout(src, dst->plane, dst->stride) ? layout_bytes(src) : 0;
+    if (*moved) return hipMemcpyAsync(dst->plane[0], src->plane[0], *moved, hipMemcpyDeviceToHost, stream);
+    hipError_t e = hipSuccess;
+    for (int c = 0; c < 3 && e == hipSuccess; c++)
+    {
+        const size_t row = (size_t)src->width[c] * src->bps;                    // the samples only
+        e = hipMemcpy2DAsync(dst->plane[c], dst->stride[c], src->plane[c], src->pitch[c], row, src->height[c], hipMemcpyDeviceToHost, stream);
+        *moved += row * src->height[c];
+    }
+    return e;
+}
+
+static int hip_rc(hbhip_ctx *ctx, hipError_t e, const char *what) { return e == hipSuccess ? HBHIP_OK : ctx->fail(e, what); }
+
+// the one way out of a copy that failed part-way: what is queued on `stream` must not outlive the call (it reads or writes
+// the caller's planes), and the event goes back to the pool
+static int abandon(hbhip_ctx *ctx, hipStream_t stream, hipEvent_t ev, int rc)
+{
+    (void)hipStreamSynchronize(stream);
+    ctx->sync_ev_put(ev);
+    return rc;
+}
+
+// H2D on the upload stream, waited for; *moved: the bytes sent
+static int copy_h2d_wait(hbhip_ctx *ctx, DevPicture *dst, const hbhip_host_frame *src, size_t *moved)
+{
+    if (!host_planes_ok(dst, src)) return HBHIP_ERR_ARG;
     hipEvent_t done = ctx->sync_ev_get();
     if (!done) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(upload)");
-    auto fail = [&](hipError_t e, const char *what) { ctx->sync_ev_put(done); return ctx->fail(e, what); };
+    hipStream_t up = ctx->up();
     // whatever still reads the picture's previous contents was queued ahead of its idle mark when it was recycled
-    hipError_t e = hbhip_pic_wait_idle(ctx->up(), dst);
-    if (e != hipSuccess) return fail(e, "upload: wait for the picture's last reader");
-    if (same_layout(dst, src->plane, src->stride))
-        e = hipMemcpyAsync(dst->plane[0], src->plane[0], layout_bytes(dst), hipMemcpyHostToDevice, ctx->up());
-    else
-        for (int c = 0; c < 3 && e == hipSuccess; c++)
-        {
-            const size_t row = (size_t)std::min(src->stride[c], dst->pitch[c]);
-            e = hipMemcpy2DAsync(dst->plane[c], dst->pitch[c], src->plane[c], src->stride[c],
-                                 row, dst->height[c], hipMemcpyHostToDevice, ctx->up());
-        }
-    if (e == hipSuccess) e = hipEventRecord(done, ctx->up());
-    if (e != hipSuccess)
-    {
-        (void)hipStreamSynchronize(ctx->up());                // planes already queued must not outlive the call
-        return fail(e, "hipMemcpyAsync(upload)");
-    }
-    *done_out = done;
-    return HBHIP_OK;
+    hipError_t e = hbhip_pic_wait_idle(up, dst);
+    if (e == hipSuccess) e = queue_h2d(dst, src, true, up, moved);
+    if (e == hipSuccess) e = hipEventRecord(done, up);
+    if (e != hipSuccess) return abandon(ctx, up, done, ctx->fail(e, "hipMemcpyAsync(upload)"));
+    // The caller may free or reuse its planes as soon as we return (filter_loop closes buf_in, work.c:2566-2569):
+    // wait for THIS copy - not for the kernels other filters have queued.  Once it has completed, work launched
+    // on any stream afterwards sees the data.
+    e = hipEventSynchronize(done);
+    ctx->sync_ev_put(done);
+    return hip_rc(ctx, e, "hipEventSynchronize(upload)");
 }
 
 int hbhip_copy_h2d(hbhip_ctx *ctx, DevPicture *dst, const hbhip_host_frame *src)
 {
-    hipEvent_t done = nullptr;
-    const int rc = hbhip_copy_h2d_queue(ctx, dst, src, &done);
-    if (rc != HBHIP_OK) return rc;
-    // The caller may free or reuse its planes as soon as we return (filter_loop closes buf_in, work.c:2566-2569):
-    // wait for THIS copy - not for the kernels other filters have queued.  Once it has completed, work launched
-    // on any stream afterwards sees the data.
-    const hipError_t e = hipEventSynchronize(done);
-    ctx->sync_ev_put(done);
-    if (e != hipSuccess) return ctx->fail(e, "hipEventSynchronize(upload)");
-    return HBHIP_OK;
+    size_t moved;
+    return copy_h2d_wait(ctx, dst, src, &moved);
 }
 
 int hbhip_copy_d2h(hbhip_ctx *ctx, const hbhip_host_frame *dst, const DevPicture *src)
 {
-    for (int c = 0; c < 3; c++)
-        if (dst->plane[c] == nullptr || dst->stride[c] < src->width[c] * src->bps) return HBHIP_ERR_ARG;
+    if (!host_planes_ok(src, dst)) return HBHIP_ERR_ARG;
     hipEvent_t ev = ctx->sync_ev_get();
     if (!ev) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(download)");
+    hipStream_t down = ctx->down();
+    size_t n = 0;
     // the picture's producers are on ctx->stream, all queued by now
-    HBHIP_CHECK(ctx, hipEventRecord(ev, ctx->stream));
-    HBHIP_CHECK(ctx, hipStreamWaitEvent(ctx->down(), ev, 0));
-    for (int c = 0; c < 3; c++)
-    {
-        const size_t row = (size_t)src->width[c] * src->bps;
-        HBHIP_CHECK(ctx, hipMemcpy2DAsync(dst->plane[c], dst->stride[c], src->plane[c], src->pitch[c],
-                                          row, src->height[c], hipMemcpyDeviceToHost, ctx->down()));
-    }
-    HBHIP_CHECK(ctx, hipEventRecord(ev, ctx->down()));
-    const hipError_t e = hipEventSynchronize(ev);
+    hipError_t e = hipEventRecord(ev, ctx->stream);
+    if (e == hipSuccess) e = hipStreamWaitEvent(down, ev, 0);
+    if (e == hipSuccess) e = queue_d2h(dst, src, false, down, &n);
+    if (e == hipSuccess) e = hipEventRecord(ev, down);
+    if (e != hipSuccess) return abandon(ctx, down, ev, ctx->fail(e, "download: queue the copy"));
+    e = hipEventSynchronize(ev);
     ctx->sync_ev_put(ev);
-    if (e != hipSuccess) return ctx->fail(e, "hipEventSynchronize(download)");
-    return HBHIP_OK;
+    return hip_rc(ctx, e, "hipEventSynchronize(download)");
 }
 
 // Device-to-device copies of a picture's three planes as ONE kernel launch: hipMemcpy2DAsync makes a blit kernel per
@@ -827,6 +842,75 @@ static void frame_idle(hbhip_frame *fr)
     fr->reader_idle = foreign ? stream_now(foreign) : nullptr;
 }
 
+// a mark recorded on `stream` right now
+static std::shared_ptr<IdleMark> record_mark(hipStream_t stream)
+{
+    std::shared_ptr<IdleMark> m = std::make_shared<IdleMark>();
+    if (hipEventCreateWithFlags(&m->ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(m->ev, stream) != hipSuccess)
+    {
+        (void)hipGetLastError();
+        return nullptr;
+    }
+    m->stream = stream;
+    m->recorded = true;
+    m->closed.store(true, std::memory_order_release);
+    return m;
+}
+
+// The two ends of a run.  A frame is filled on its context's upload stream and drained on its download stream, from and
+// into a planar host picture, an NV12 / P010LE host picture or a device surface: the entry points below check their
+// arguments and bring the step that is theirs, the protocol around it is here.  A step returns HBHIP_OK or the code of
+// what failed (through ctx->fail where a HIP call did); then the stream is waited out (abandon) and the token stays null.
+//
+// fill: the stream behind whatever still reads the frame's previous contents (queued ahead of its idle marks when it was
+// recycled); `queue(up, done)` queues the source's work and records `done` where the SOURCE is free again; the frame's
+// ready mark behind all of it.  *token: `done`, for hbhip_ctx_upload_done.
+extern "C++" {                                         // (templates, in the middle of the C ABI)
+template <class Queue>
+static int fill_frame(hbhip_frame *fr, const char *what, Queue queue, void **token, std::shared_ptr<IdleMark> *ready_out = nullptr)
+{
+    hbhip_ctx *ctx = fr->ctx;
+    hipStream_t up = ctx->up();
+    hipEvent_t done = ctx->sync_ev_get();
+    if (!done) return ctx->fail(hipErrorOutOfMemory, what);
+    int rc = hip_rc(ctx, hbhip_pic_wait_idle(up, &fr->pic), what);
+    if (rc == HBHIP_OK) rc = queue(up, done);
+    std::shared_ptr<IdleMark> ready = rc == HBHIP_OK ? record_mark(up) : nullptr;
+    if (rc == HBHIP_OK && !ready) rc = ctx->fail(hipErrorOutOfMemory, what);
+    if (rc != HBHIP_OK) return abandon(ctx, up, done, rc);
+    if (ready_out) *ready_out = ready;
+    { std::lock_guard<std::mutex> lk(ctx->frame_lock); set_contents(fr, std::move(ready)); }
+    *token = done;
+    return HBHIP_OK;
+}
+
+// drain: the stream behind the frame's contents; `queue(down)` queues the destination's work; the token's event behind it;
+// `then(down)` what has to lie behind that event.  *token: the event, for hbhip_frame_download_wait.
+template <class Queue, class Then>
+static int drain_frame(hbhip_frame *fr, const char *what, Queue queue, Then then, void **token)
+{
+    hbhip_ctx *ctx = fr->ctx;
+    hipStream_t down = ctx->down();
+    hipEvent_t ev = ctx->sync_ev_get();
+    if (!ev) return ctx->fail(hipErrorOutOfMemory, what);
+    hipError_t e;
+    { std::lock_guard<std::mutex> lk(ctx->frame_lock); e = order_after_contents(fr, down); }
+    int rc = hip_rc(ctx, e, what);
+    if (rc == HBHIP_OK) rc = queue(down);
+    if (rc == HBHIP_OK) rc = hip_rc(ctx, hipEventRecord(ev, down), what);
+    if (rc == HBHIP_OK) rc = then(down);
+    if (rc != HBHIP_OK) return abandon(ctx, down, ev, rc);
+    *token = ev;
+    return HBHIP_OK;
+}
+
+template <class Queue>
+static int drain_frame(hbhip_frame *fr, const char *what, Queue queue, void **token)
+{
+    return drain_frame(fr, what, queue, [](hipStream_t) { return HBHIP_OK; }, token);
+}
+} // extern "C++"
+
 hbhip_ctx *hbhip_frame_context(hbhip_frame *fr)
 {
     return fr ? fr->ctx : nullptr;
@@ -977,9 +1061,10 @@ int hbhip_frame_upload(hbhip_frame *fr, const hbhip_host_frame *src)
 {
     if (!fr || !src) return HBHIP_ERR_ARG;
     (void)hipSetDevice(fr->ctx->device);
-    const int rc = hbhip_copy_h2d(fr->ctx, &fr->pic, src);      // returns when the copy has finished
+    size_t moved = 0;
+    const int rc = copy_h2d_wait(fr->ctx, &fr->pic, src, &moved);      // returns when the copy has finished
     if (rc != HBHIP_OK) return rc;
-    fr->ctx->bus_h2d += copy_bytes(&fr->pic, src->plane, src->stride, true);
+    fr->ctx->bus_h2d += moved;
     std::lock_guard<std::mutex> lk(fr->ctx->frame_lock);
     set_contents(fr, nullptr);
     return HBHIP_OK;
@@ -987,36 +1072,22 @@ int hbhip_frame_upload(hbhip_frame *fr, const hbhip_host_frame *src)
 
 // The pipelined H2D (the upload adapter keeps a few in flight, as the download adapter does with its copies): the copy is
 // queued on the upload stream and the call returns; `src` must stay valid until hbhip_ctx_upload_done(token) says so.  The
-// frame's ready mark is the copy's event.
+// frame's ready mark lies right behind the copy.
 int hbhip_frame_upload_async(hbhip_frame *fr, const hbhip_host_frame *src, void **token)
 {
     if (!fr || !src || !token) return HBHIP_ERR_ARG;
     *token = nullptr;
     hbhip_ctx *ctx = fr->ctx;
     (void)hipSetDevice(ctx->device);
-    std::shared_ptr<IdleMark> m = std::make_shared<IdleMark>();
-    if (hipEventCreateWithFlags(&m->ev, hipEventDisableTiming) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(upload ready)");
-    }
-    hipEvent_t done = nullptr;
-    const int rc = hbhip_copy_h2d_queue(ctx, &fr->pic, src, &done);
-    if (rc != HBHIP_OK) return rc;
-    ctx->bus_h2d += copy_bytes(&fr->pic, src->plane, src->stride, true);
-    m->stream = ctx->up();
-    const hipError_t e = hipEventRecord(m->ev, ctx->up());
-    if (e != hipSuccess)
-    {
-        (void)hipEventSynchronize(done);
-        ctx->sync_ev_put(done);
-        return ctx->fail(e, "hipEventRecord(upload ready)");
-    }
-    m->recorded = true;
-    m->closed.store(true, std::memory_order_release);
-    { std::lock_guard<std::mutex> lk(ctx->frame_lock); set_contents(fr, std::move(m)); }
-    *token = done;
-    return HBHIP_OK;
+    if (!host_planes_ok(&fr->pic, src)) return HBHIP_ERR_ARG;
+    size_t moved = 0;
+    const int rc = fill_frame(fr, "upload", [&](hipStream_t up, hipEvent_t done) {
+        hipError_t e = queue_h2d(&fr->pic, src, true, up, &moved);
+        if (e == hipSuccess) e = hipEventRecord(done, up);
+        return hip_rc(ctx, e, "hipMemcpyAsync(upload)");
+    }, token);
+    if (rc == HBHIP_OK) ctx->bus_h2d += moved;
+    return rc;
 }
 
 // has the copy behind `token` finished (block != 0: wait for it)?  HBHIP_OK: yes, the source planes are free again and the
@@ -1058,38 +1129,13 @@ int hbhip_frame_download_async(hbhip_frame *fr, const hbhip_host_frame *dst, voi
     *token = nullptr;
     hbhip_ctx *ctx = fr->ctx;
     (void)hipSetDevice(ctx->device);
-    const DevPicture *src = &fr->pic;
-    for (int c = 0; c < 3; c++)
-        if (dst->plane[c] == nullptr || dst->stride[c] < src->width[c] * src->bps) return HBHIP_ERR_ARG;
-    hipEvent_t ev = ctx->sync_ev_get();
-    if (!ev) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(download)");
-    auto fail = [&](hipError_t e, const char *what) { ctx->sync_ev_put(ev); return ctx->fail(e, what); };
-    std::unique_lock<std::mutex> lk(ctx->frame_lock);
-    hipError_t e = order_after_contents(fr, ctx->down());
-    lk.unlock();
-    if (e != hipSuccess) return fail(e, "download: order behind the frame's contents");
-    if (same_layout(src, dst->plane, dst->stride))
-    {
-        e = hipMemcpyAsync(dst->plane[0], src->plane[0], layout_bytes(src), hipMemcpyDeviceToHost, ctx->down());
-        if (e != hipSuccess) return fail(e, "hipMemcpyAsync(download)");
-    }
-    else
-        for (int c = 0; c < 3; c++)
-        {
-            const size_t row = (size_t)src->width[c] * src->bps;
-            e = hipMemcpy2DAsync(dst->plane[c], dst->stride[c], src->plane[c], src->pitch[c], row, src->height[c],
-                                 hipMemcpyDeviceToHost, ctx->down());
-            if (e != hipSuccess)
-            {
-                (void)hipStreamSynchronize(ctx->down());      // planes already queued must not outlive the call
-                return fail(e, "hipMemcpy2DAsync(download)");
-            }
-        }
-    e = hipEventRecord(ev, ctx->down());
-    if (e != hipSuccess) { (void)hipStreamSynchronize(ctx->down()); return fail(e, "hipEventRecord(download)"); }
-    ctx->bus_d2h += copy_bytes(src, dst->plane, dst->stride, false);
-    *token = ev;
-    return HBHIP_OK;
+    if (!host_planes_ok(&fr->pic, dst)) return HBHIP_ERR_ARG;
+    size_t moved = 0;
+    const int rc = drain_frame(fr, "download", [&](hipStream_t down) {
+        return hip_rc(ctx, queue_d2h(dst, &fr->pic, true, down, &moved), "hipMemcpyAsync(download)");
+    }, token);
+    if (rc == HBHIP_OK) ctx->bus_d2h += moved;
+    return rc;
 }
 
 int hbhip_frame_download_wait(hbhip_frame *fr, void *token)
@@ -1109,10 +1155,20 @@ int hbhip_frame_download_wait(hbhip_frame *fr, void *token)
 // (biplanar.hip).  Same ordering rule as the planar copies: the split runs behind the H2D copy on the upload stream and
 // the frame's ready mark is the split; the merge runs on the download stream behind the frame's contents and the D2H
 // copy behind the merge.
+static int surface_geometry_ok(int width, int height, int depth)
+{
+    return (depth == 8 || depth == 10) && width >= 2 && height >= 2;
+}
+
+// a frame the repack kernels take: 4:2:0, and what a surface may be
+static bool bi_frame_ok(const hbhip_frame *fr)
+{
+    return fr->lcw == 1 && fr->lch == 1 && surface_geometry_ok(fr->width, fr->height, fr->depth);
+}
+
 static int bi_check(const hbhip_frame *fr, const hbhip_host_biplanar *hb, BiLayout *l)
 {
-    if ((fr->depth != 8 && fr->depth != 10) || fr->lcw != 1 || fr->lch != 1 || fr->width < 2 || fr->height < 2)
-        return HBHIP_ERR_UNSUPPORTED;
+    if (!bi_frame_ok(fr)) return HBHIP_ERR_UNSUPPORTED;
     hbhip_bi_layout(fr->width, fr->height, fr->depth, l);
     for (int p = 0; p < 2; p++)
         if (hb->plane[p] == nullptr || hb->stride[p] < l->row_bytes[p]) return HBHIP_ERR_ARG;
@@ -1141,36 +1197,32 @@ static uint8_t *bi_stage(hbhip_ctx *ctx, int dir, size_t bytes, hipStream_t stre
     return ctx->bi_stage[dir];
 }
 
-// host picture <-> staging buffer: one 1-D copy when the host picture has the staging layout, else a 2-D copy per plane
-static hipError_t bi_copy(uint8_t *stage, const BiLayout &l, const hbhip_host_biplanar *hb, bool to_device, hipStream_t stream)
+// host picture <-> staging buffer: one 1-D copy when the host picture has the staging layout, else a 2-D copy per plane.
+// *moved: what goes over the bus (hbhip_ctx_bus_bytes)
+static hipError_t bi_copy(uint8_t *stage, const BiLayout &l, const hbhip_host_biplanar *hb, bool to_device, hipStream_t stream, size_t *moved)
 {
     const hipMemcpyKind kind = to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost;
+    *moved = 0;
     if (hb->stride[0] == l.pitch[0] && hb->stride[1] == l.pitch[1] &&
         hb->plane[1] == hb->plane[0] + (size_t)l.pitch[0] * l.rows[0])
+    {
+        *moved = l.bytes;
         return to_device ? hipMemcpyAsync(stage, hb->plane[0], l.bytes, kind, stream)
                          : hipMemcpyAsync(hb->plane[0], stage, l.bytes, kind, stream);
+    }
     hipError_t e = hipSuccess;
     uint8_t *at = stage;
     for (int p = 0; p < 2 && e == hipSuccess; p++)
     {
         // up: the caller's row padding travels too (up to our pitch), as in the planar upload - the split hands it on to
         // the frame, whose readers read it; down: the samples only, as in the planar download
-        const size_t up_row = (size_t)std::min(hb->stride[p], l.pitch[p]);
-        e = to_device ? hipMemcpy2DAsync(at, l.pitch[p], hb->plane[p], hb->stride[p], up_row, l.rows[p], kind, stream)
-                      : hipMemcpy2DAsync(hb->plane[p], hb->stride[p], at, l.pitch[p], l.row_bytes[p], l.rows[p], kind, stream);
+        const size_t row = to_device ? (size_t)std::min(hb->stride[p], l.pitch[p]) : (size_t)l.row_bytes[p];
+        e = to_device ? hipMemcpy2DAsync(at, l.pitch[p], hb->plane[p], hb->stride[p], row, l.rows[p], kind, stream)
+                      : hipMemcpy2DAsync(hb->plane[p], hb->stride[p], at, l.pitch[p], row, l.rows[p], kind, stream);
         at += (size_t)l.pitch[p] * l.rows[p];
+        *moved += row * l.rows[p];
     }
     return e;
-}
-
-// what bi_copy moves over the bus (hbhip_ctx_bus_bytes)
-static size_t bi_copy_bytes(const BiLayout &l, const hbhip_host_biplanar *hb, bool to_device)
-{
-    if (hb->stride[0] == l.pitch[0] && hb->stride[1] == l.pitch[1] && hb->plane[1] == hb->plane[0] + (size_t)l.pitch[0] * l.rows[0])
-        return l.bytes;
-    size_t n = 0;
-    for (int p = 0; p < 2; p++) n += (size_t)(to_device ? std::min(hb->stride[p], l.pitch[p]) : l.row_bytes[p]) * l.rows[p];
-    return n;
 }
 
 // `src` must stay valid until hbhip_ctx_upload_done(token) says so, as with hbhip_frame_upload_async
@@ -1183,37 +1235,16 @@ int hbhip_frame_upload_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar
     int rc = bi_check(fr, src, &l);
     if (rc != HBHIP_OK) return rc;
     (void)hipSetDevice(ctx->device);
-    std::shared_ptr<IdleMark> m = std::make_shared<IdleMark>();
-    if (hipEventCreateWithFlags(&m->ev, hipEventDisableTiming) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(upload ready)");
-    }
-    hipEvent_t done = ctx->sync_ev_get();
-    if (!done) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(upload)");
-    hipStream_t up = ctx->up();
-    {
+    size_t moved = 0;
+    rc = fill_frame(fr, "upload (biplanar)", [&](hipStream_t up, hipEvent_t done) {
         std::lock_guard<std::mutex> lk(ctx->bi_lock[0]);
         uint8_t *stage = bi_stage(ctx, 0, l.bytes, up);
-        hipError_t e = stage ? hbhip_pic_wait_idle(up, &fr->pic) : hipErrorOutOfMemory;
-        if (e == hipSuccess) e = bi_copy(stage, l, src, true, up);
+        hipError_t e = stage ? bi_copy(stage, l, src, true, up, &moved) : hipErrorOutOfMemory;
         if (e == hipSuccess) e = hipEventRecord(done, up);                    // the host picture is free behind the copy
-        if (e == hipSuccess) rc = hbhip_bi_repack_launch(ctx, up, false, stage, fr);
-        if (e == hipSuccess && rc == HBHIP_OK) e = hipEventRecord(m->ev, up);
-        if (e != hipSuccess || rc != HBHIP_OK)
-        {
-            (void)hipStreamSynchronize(up);                                   // what is queued must not outlive the call
-            ctx->sync_ev_put(done);
-            return e != hipSuccess ? ctx->fail(e, "upload (biplanar)") : rc;
-        }
-    }
-    m->stream = up;
-    m->recorded = true;
-    m->closed.store(true, std::memory_order_release);
-    { std::lock_guard<std::mutex> lk(ctx->frame_lock); set_contents(fr, std::move(m)); }
-    ctx->bus_h2d += bi_copy_bytes(l, src, true);
-    *token = done;
-    return HBHIP_OK;
+        return e != hipSuccess ? ctx->fail(e, "upload (biplanar)") : hbhip_bi_repack_launch(ctx, up, false, stage, fr);
+    }, token);
+    if (rc == HBHIP_OK) ctx->bus_h2d += moved;
+    return rc;
 }
 
 int hbhip_frame_upload_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *src)
@@ -1233,28 +1264,16 @@ int hbhip_frame_download_biplanar_async(hbhip_frame *fr, const hbhip_host_biplan
     int rc = bi_check(fr, dst, &l);
     if (rc != HBHIP_OK) return rc;
     (void)hipSetDevice(ctx->device);
-    hipEvent_t ev = ctx->sync_ev_get();
-    if (!ev) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(download)");
-    hipStream_t down = ctx->down();
-    hipError_t e;
-    { std::lock_guard<std::mutex> lk(ctx->frame_lock); e = order_after_contents(fr, down); }
-    {
+    size_t moved = 0;
+    rc = drain_frame(fr, "download (biplanar)", [&](hipStream_t down) {
         std::lock_guard<std::mutex> lk(ctx->bi_lock[1]);
-        uint8_t *stage = e == hipSuccess ? bi_stage(ctx, 1, l.bytes, down) : nullptr;
-        if (e == hipSuccess && !stage) e = hipErrorOutOfMemory;
-        if (e == hipSuccess) rc = hbhip_bi_repack_launch(ctx, down, true, stage, fr);
-        if (e == hipSuccess && rc == HBHIP_OK) e = bi_copy(stage, l, dst, false, down);
-        if (e == hipSuccess && rc == HBHIP_OK) e = hipEventRecord(ev, down);
-        if (e != hipSuccess || rc != HBHIP_OK)
-        {
-            (void)hipStreamSynchronize(down);
-            ctx->sync_ev_put(ev);
-            return e != hipSuccess ? ctx->fail(e, "download (biplanar)") : rc;
-        }
-    }
-    ctx->bus_d2h += bi_copy_bytes(l, dst, false);
-    *token = ev;
-    return HBHIP_OK;
+        uint8_t *stage = bi_stage(ctx, 1, l.bytes, down);
+        if (!stage) return ctx->fail(hipErrorOutOfMemory, "download (biplanar)");
+        const int launched = hbhip_bi_repack_launch(ctx, down, true, stage, fr);
+        return launched != HBHIP_OK ? launched : hip_rc(ctx, bi_copy(stage, l, dst, false, down, &moved), "download (biplanar)");
+    }, token);
+    if (rc == HBHIP_OK) ctx->bus_d2h += moved;
+    return rc;
 }
 
 int hbhip_frame_download_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *dst)
@@ -1268,11 +1287,6 @@ int hbhip_frame_download_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *ds
 // No staging buffer and no bi_lock: the repack kernel reads or writes the surface where it lies.  The same ordering rule:
 // the split runs on the upload stream behind the surface's contents and is the frame's ready mark, the merge on the
 // download stream behind the frame's contents (and the surface's earlier readers) and is the surface's ready mark.
-static int surface_geometry_ok(int width, int height, int depth)
-{
-    return (depth == 8 || depth == 10) && width >= 2 && height >= 2;
-}
-
 // the last reference has gone: a pooled surface goes back to its pool, a wrapped one to its owner (outside the lock)
 static void surface_unref(hbhip_surface *s)
 {
@@ -1308,21 +1322,6 @@ static void surface_reap(hbhip_ctx *ctx, bool wait)
         if (wait && op.done) (void)hipEventSynchronize(op.done->ev);
         surface_unref(op.s);
     }
-}
-
-// a mark recorded on `stream` right now
-static std::shared_ptr<IdleMark> record_mark(hipStream_t stream)
-{
-    std::shared_ptr<IdleMark> m = std::make_shared<IdleMark>();
-    if (hipEventCreateWithFlags(&m->ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(m->ev, stream) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        return nullptr;
-    }
-    m->stream = stream;
-    m->recorded = true;
-    m->closed.store(true, std::memory_order_release);
-    return m;
 }
 
 int hbhip_surface_alloc(hbhip_ctx *ctx, int width, int height, int depth, int pitch_align, int rows_align, hbhip_surface **out)
@@ -1435,8 +1434,7 @@ int hbhip_surface_set_ready_event(hbhip_surface *s, void *hip_event)
 
 static int surface_check(const hbhip_frame *fr, const hbhip_surface *s)
 {
-    if ((fr->depth != 8 && fr->depth != 10) || fr->lcw != 1 || fr->lch != 1 || fr->width < 2 || fr->height < 2)
-        return HBHIP_ERR_UNSUPPORTED;
+    if (!bi_frame_ok(fr)) return HBHIP_ERR_UNSUPPORTED;
     if (s->depth != fr->depth || s->width != fr->width || s->height != fr->height) return HBHIP_ERR_UNSUPPORTED;
     if (s->ctx->device != fr->ctx->device) return HBHIP_ERR_ARG;
     return HBHIP_OK;
@@ -1459,31 +1457,22 @@ int hbhip_frame_import_surface_async(hbhip_frame *fr, hbhip_surface *src, void *
     if (rc != HBHIP_OK) return rc;
     (void)hipSetDevice(ctx->device);
     surface_reap(ctx, false);
-    hipEvent_t done = ctx->sync_ev_get();
-    if (!done) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(import)");
-    hipStream_t up = ctx->up();
-    std::shared_ptr<IdleMark> ready, earlier;
+    std::shared_ptr<IdleMark> ready, earlier, m;
     hipEvent_t producer;
     {
         std::lock_guard<std::mutex> lk(src->ctx->surface_lock);
         ready = src->ready; producer = src->ready_event; earlier = src->read_idle;
     }
-    hipError_t e = hbhip_pic_wait_idle(up, &fr->pic);
-    if (e == hipSuccess) e = wait_mark(up, ready);
-    if (e == hipSuccess && producer) e = hipStreamWaitEvent(up, producer, 0);
-    if (e == hipSuccess) e = wait_mark(up, earlier);            // (another stream's import: an export then waits for ours alone)
-    if (e != hipSuccess) { ctx->sync_ev_put(done); return ctx->fail(e, "import: order behind the surface's contents"); }
-    rc = hbhip_bi_surface_launch(ctx, up, false, src, fr);
-    // the token's event ahead of the mark: once the library lets go of the surface (the mark has fired) the token is done
-    if (rc == HBHIP_OK) e = hipEventRecord(done, up);
-    std::shared_ptr<IdleMark> m = rc == HBHIP_OK && e == hipSuccess ? record_mark(up) : nullptr;
-    if (rc == HBHIP_OK && e == hipSuccess && !m) e = hipErrorOutOfMemory;
-    if (rc != HBHIP_OK || e != hipSuccess)
-    {
-        (void)hipStreamSynchronize(up);                          // what is queued must not outlive the call
-        ctx->sync_ev_put(done);
-        return rc != HBHIP_OK ? rc : ctx->fail(e, "import (surface)");
-    }
+    rc = fill_frame(fr, "import (surface)", [&](hipStream_t up, hipEvent_t done) {
+        hipError_t e = wait_mark(up, ready);
+        if (e == hipSuccess && producer) e = hipStreamWaitEvent(up, producer, 0);
+        if (e == hipSuccess) e = wait_mark(up, earlier);        // (another stream's import: an export then waits for ours alone)
+        if (e != hipSuccess) return ctx->fail(e, "import: order behind the surface's contents");
+        const int launched = hbhip_bi_surface_launch(ctx, up, false, src, fr);
+        // the token's event ahead of the mark: once the library lets go of the surface (the mark has fired) the token is done
+        return launched != HBHIP_OK ? launched : hip_rc(ctx, hipEventRecord(done, up), "import (surface)");
+    }, token, &m);
+    if (rc != HBHIP_OK) return rc;
     {
         std::lock_guard<std::mutex> lk(src->ctx->surface_lock);
         src->read_idle = m;
@@ -1494,8 +1483,6 @@ int hbhip_frame_import_surface_async(hbhip_frame *fr, hbhip_surface *src, void *
         }
     }
     surface_hold(ctx, src, m);
-    { std::lock_guard<std::mutex> lk(ctx->frame_lock); set_contents(fr, std::move(m)); }
-    *token = done;
     return HBHIP_OK;
 }
 
@@ -1515,31 +1502,23 @@ int hbhip_frame_export_surface_async(hbhip_frame *fr, hbhip_surface *dst, void *
     if (rc != HBHIP_OK) return rc;
     (void)hipSetDevice(ctx->device);
     surface_reap(ctx, false);
-    hipEvent_t ev = ctx->sync_ev_get();
-    if (!ev) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(export)");
-    hipStream_t down = ctx->down();
-    hipError_t e;
-    { std::lock_guard<std::mutex> lk(ctx->frame_lock); e = order_after_contents(fr, down); }
-    std::shared_ptr<IdleMark> ready, readers;
+    std::shared_ptr<IdleMark> ready, readers, m;
     hipEvent_t producer;
     {
         std::lock_guard<std::mutex> lk(dst->ctx->surface_lock);
         ready = dst->ready; producer = dst->ready_event; readers = dst->read_idle;
     }
-    if (e == hipSuccess) e = wait_mark(down, ready);            // an earlier writer (another context's download stream; the clearing)
-    if (e == hipSuccess && producer) e = hipStreamWaitEvent(down, producer, 0);
-    if (e == hipSuccess) e = wait_mark(down, readers);
-    if (e != hipSuccess) { ctx->sync_ev_put(ev); return ctx->fail(e, "export: order behind the frame's contents and the surface's users"); }
-    rc = hbhip_bi_surface_launch(ctx, down, true, dst, fr);
-    if (rc == HBHIP_OK) e = hipEventRecord(ev, down);
-    std::shared_ptr<IdleMark> m = rc == HBHIP_OK && e == hipSuccess ? record_mark(down) : nullptr;
-    if (rc == HBHIP_OK && e == hipSuccess && !m) e = hipErrorOutOfMemory;
-    if (rc != HBHIP_OK || e != hipSuccess)
-    {
-        (void)hipStreamSynchronize(down);
-        ctx->sync_ev_put(ev);
-        return rc != HBHIP_OK ? rc : ctx->fail(e, "export (surface)");
-    }
+    rc = drain_frame(fr, "export (surface)", [&](hipStream_t down) {
+        hipError_t e = wait_mark(down, ready);                  // an earlier writer (another context's download stream; the clearing)
+        if (e == hipSuccess && producer) e = hipStreamWaitEvent(down, producer, 0);
+        if (e == hipSuccess) e = wait_mark(down, readers);
+        if (e != hipSuccess) return ctx->fail(e, "export: order behind the surface's users");
+        return hbhip_bi_surface_launch(ctx, down, true, dst, fr);
+    }, [&](hipStream_t down) {                                  // the surface's mark behind the token's event, as in the import
+        m = record_mark(down);
+        return m ? HBHIP_OK : ctx->fail(hipErrorOutOfMemory, "export (surface)");
+    }, token);
+    if (rc != HBHIP_OK) return rc;
     {
         std::lock_guard<std::mutex> lk(dst->ctx->surface_lock);
         dst->ready = m;
@@ -1547,7 +1526,6 @@ int hbhip_frame_export_surface_async(hbhip_frame *fr, hbhip_surface *dst, void *
         dst->read_idle.reset();
     }
     surface_hold(ctx, dst, m);
-    *token = ev;
     return HBHIP_OK;
 }
 
@@ -1716,10 +1694,7 @@ int hbhip_filter_submit_async(hbhip_filter *f, const hbhip_host_frame *in, const
     }
     hipEvent_t ev = ctx->sync_ev_get(), done = ctx->sync_ev_get();
     int rc = (ev && done) ? HBHIP_OK : HBHIP_ERR_NOMEM;
-    for (int c = 0; rc == HBHIP_OK && c < 3; c++)
-        if (!in->plane[c] || in->stride[c] < pic->width[c] * pic->bps || !out->plane[c] ||
-            out->stride[c] < o->width[c] * o->bps)
-            rc = HBHIP_ERR_ARG;
+    if (rc == HBHIP_OK && !(host_planes_ok(pic, in) && host_planes_ok(o, out))) rc = HBHIP_ERR_ARG;
     auto fail = [&](int code) {
         // copies of the caller's `in` / `out` may be in flight: nothing of them may outlive this call
         if (ctx->up_stream) (void)hipStreamSynchronize(ctx->up_stream);
@@ -1737,10 +1712,8 @@ int hbhip_filter_submit_async(hbhip_filter *f, const hbhip_host_frame *in, const
     for (int c = 0; c < 3; c++) f->in_stride[c] = in->stride[c];
     f->in_is_dev = false;
     ASYNC_CHECK(hbhip_pic_wait_idle(ctx->up(), pic));
-    for (int c = 0; c < 3; c++)
-        ASYNC_CHECK(hipMemcpy2DAsync(pic->plane[c], pic->pitch[c], in->plane[c], in->stride[c],
-                                     (size_t)std::min(in->stride[c], pic->pitch[c]), pic->height[c],
-                                     hipMemcpyHostToDevice, ctx->up()));
+    size_t moved;
+    ASYNC_CHECK(queue_h2d(pic, in, false, ctx->up(), &moved));
     ASYNC_CHECK(hipEventRecord(ev, ctx->up()));
     ASYNC_CHECK(hipStreamWaitEvent(ctx->stream, ev, 0));
     rc = f->process_pair(pic, o);
@@ -1749,9 +1722,7 @@ int hbhip_filter_submit_async(hbhip_filter *f, const hbhip_host_frame *in, const
     pic = nullptr;
     ASYNC_CHECK(hipEventRecord(ev, ctx->stream));
     ASYNC_CHECK(hipStreamWaitEvent(ctx->down(), ev, 0));
-    for (int c = 0; c < 3; c++)
-        ASYNC_CHECK(hipMemcpy2DAsync(out->plane[c], out->stride[c], o->plane[c], o->pitch[c], (size_t)o->width[c] * o->bps,
-                                     o->height[c], hipMemcpyDeviceToHost, ctx->down()));
+    ASYNC_CHECK(queue_d2h(out, o, false, ctx->down(), &moved));
     ASYNC_CHECK(hipEventRecord(done, ctx->down()));
 #undef ASYNC_CHECK
     ctx->sync_ev_put(ev);

@@ -916,7 +916,7 @@ static int download_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_bu
         hbhip_surface *sf = NULL;
         if (hbhip_surface_alloc(pv->ctx, in->f.width, in->f.height, pv->depth, 256, 16, &sf) != HBHIP_OK) return HB_FILTER_FAILED;
         out = hbhip_host_wrap_surface(sf, &pv->output, in->f.width, in->f.height);
-        if (out == NULL) return HB_FILTER_FAILED;
+        if (out == NULL) return HB_FILTER_FAILED;       /* (the wrap takes the reference over: it has released the surface) */
         if (hbhip_frame_export_surface_async(fr, sf, &token) != HBHIP_OK)
         {
             hb_buffer_close(&out);
