@@ -42,6 +42,14 @@ constexpr int NLM_BORDER = 16;   // nlmeans.c:529 for every patch size <= 29
 #define NLM16_SYM_PAIRS 3        // 16-bit samples: how many of frame 0's four displacement pairs share their distances (3 | 4)
 #endif
 
+// measurement switches (tools/variant.sh; profiles/nlmeans_staging_ab.json): 0 takes the piece out, the results stay the same
+#ifndef NLM_JOB_ARITH
+#define NLM_JOB_ARITH 1          // the job of a tile by arithmetic (0: every launch searches its table)
+#endif
+#ifndef NLM_ORIGIN_F32
+#define NLM_ORIGIN_F32 1         // 8-bit pairs' kernel: the origin term in single precision where origin_tune == 1
+#endif
+
 struct alignas(16) NlmJob
 {
     const uint8_t *frame[HBHIP_NLMEANS_FRAMES_MAX];
@@ -98,43 +106,104 @@ __device__ __forceinline__ uint32_t byte_of(uint32_t v, int k) { return (v >> (8
 constexpr int LTXA = TXN - 2;            // lanes of a tile row that own output pixels
 constexpr int LTW = LTXA * PX;           // 120
 
-// Stage a (rows x dwords*4)-byte window of `plane` whose top-left pixel is (x0, y0) into LDS
-// (row pitch `pitch` dwords) with the reference's mirrored borders (nlmeans_template.c:29-41).
-// A thread keeps one column for the whole tile, so the column reflection and the index split
-// are computed once; the per-row work is a row reflection, one address and one load.
-__device__ __forceinline__ void load_tile_p(uint32_t *lds, int pitch, int dwords, int rows,
-                                            const uint8_t *__restrict__ plane, int src_pitch,
-                                            int w, int h, int x0, int y0)
+// Which job a workgroup's tile belongs to.  Every job of a launch comes from one filter instance, so the frames of a
+// launch have the same planes with the same tile counts: `per_frame` tiles a frame, the first plane's tiles before
+// `after0`, the second's before `after1`.  The job and the tile within it then follow from blockIdx.x by one division
+// and two compares - no load at all.  per_frame == 0 (the host found a table that does not repeat): the binary search
+// over the jobs' first tile indices, log2(njobs) dependent loads.
+struct NlmTiles { int per_frame, after0, after1, planes; };
+
+__device__ __forceinline__ int job_of_tile(const NlmJob *__restrict__ jobs, int njobs, const NlmTiles &tc, int &tile)
 {
+    const uint32_t b = blockIdx.x;
+    if (tc.per_frame > 0)
+    {
+        const uint32_t fr = b / (uint32_t)tc.per_frame;
+        const int rem = (int)(b - fr * (uint32_t)tc.per_frame);
+        const int pl = (rem >= tc.after0 ? 1 : 0) + (rem >= tc.after1 ? 1 : 0);
+        tile = rem - (pl == 2 ? tc.after1 : pl == 1 ? tc.after0 : 0);
+        return (int)fr * tc.planes + pl;
+    }
+    int j = 0;
+    for (int hi = njobs - 1; j < hi;)
+    {
+        const int mid = (j + hi + 1) >> 1;
+        if ((int)b >= jobs[mid].tile_start) j = mid; else hi = mid - 1;
+    }
+    tile = (int)b - jobs[j].tile_start;
+    return j;
+}
+
+// The most rows a tile of an instantiation can have (the kernels size their staging registers by it, the host checks
+// its cmp_rows against it): the pairs' sharing only runs with a 3 x 3 search; the narrow tile pitch (36 dwords of
+// bytes, 76 of 16-bit samples) only with a search halo of one / two dwords a side (4 / 8 pixels); and no filter gets
+// past the reference's mirrored border.
+constexpr int nlm_max_rows(int n, bool sym, int max_rh_of_pitch)
+{
+    return TH + 2 * (sym ? n / 2 + 1 : (n / 2 + max_rh_of_pitch < NLM_BORDER ? n / 2 + max_rh_of_pitch : NLM_BORDER));
+}
+
+// Staging a (rows x dwords)-dword window of `plane` whose top-left pixel is (x0, y0) into LDS (row pitch `pitch`
+// dwords) with the reference's mirrored borders (nlmeans_template.c:29-41).  BPS: bytes per sample (a dword is 4 / BPS
+// pixels).  A thread keeps one column for the whole tile, so the column reflection and the index split are computed
+// once; thread (r0, c) takes rows r0, r0 + rpp, ...
+// (planes are device allocations: read through global pointers, so that the loads count against vmcnt alone and a load
+// in flight never holds up an LDS read - a flat load counts against both)
+#define NLM_GLOBAL __attribute__((address_space(1)))
+typedef const NLM_GLOBAL uint8_t *nlm_gbytes;
+typedef const NLM_GLOBAL u32_unaligned *nlm_gdword;
+// MAXT: the compile-time bound on a thread's trips (nlm_max_rows over the rows per pass).
+template <int BPS, int MAXT>
+__device__ __forceinline__ void load_tile(uint32_t *lds, int pitch, int dwords, int rows,
+                                          const uint8_t *__restrict__ plane, int src_pitch,
+                                          int w, int h, int x0, int y0)
+{
+    constexpr int PPD = 4 / BPS;
     int tid = threadIdx.x;
     asm volatile("" : "+v"(tid));                      // keep this cold code out of LICM's reach
     const int rpp = (TXN * TYN) / dwords;              // rows per pass
     const int r0 = (int)(((float)tid + 0.5f) * (1.0f / (float)dwords));   // tid / dwords (tid < 2^10)
     const int c = tid - r0 * dwords;
     if (r0 >= rpp) return;
-    const int x = x0 + 4 * c;
-    const bool whole = x >= 0 && x + 3 < w;
-    const int o0 = reflect(x, w), o1 = reflect(x + 1, w), o2 = reflect(x + 2, w), o3 = reflect(x + 3, w);
-    uint32_t *out = lds + r0 * pitch + c;
-    if (y0 >= 0 && y0 + rows <= h && x0 >= 0 && x0 + 4 * dwords <= w)
+    const int x = x0 + PPD * c;
+    // dword c of a row; 16-bit samples: in the row's even half (c / 2) or odd half (pitch / 2 + c / 2), see nlmeans_lanes16_kernel
+    uint32_t *out = lds + r0 * pitch + (BPS == 1 ? c : (c >> 1) + (c & 1) * (pitch >> 1));
+    if (y0 >= 0 && y0 + rows <= h && x0 >= 0 && x0 + PPD * dwords <= w)
     {
-        // tile and halo wholly inside the plane (most tiles): no reflection, one pointer bump per row
-        const uint8_t *ptr = plane + (size_t)(y0 + r0) * src_pitch + x;
+        // tile and halo wholly inside the plane (most tiles): no reflection.  Every load of the thread is issued before its
+        // first LDS store, so a store waits for its own load only when all of them are in flight - the loop is unrolled to
+        // its bound, and the trips past `rows` fall away by a uniform test
+        __builtin_assume(rows >= TH);
+        const nlm_gbytes ptr = (nlm_gbytes)plane + (size_t)(y0 + r0) * src_pitch + (size_t)x * BPS;
         const size_t step = (size_t)rpp * src_pitch;
-#pragma nounroll
-        for (int r = r0; r < rows; r += rpp, out += rpp * pitch, ptr += step)
-            *out = reinterpret_cast<const u32_unaligned *>(ptr)->v;
+        uint32_t v[MAXT];
+#pragma unroll
+        for (int k = 0; k < MAXT; k++)
+            if (k * rpp < rows && r0 + k * rpp < rows) v[k] = ((nlm_gdword)(ptr + k * step))->v;
+#pragma unroll
+        for (int k = 0; k < MAXT; k++)
+            if (k * rpp < rows && r0 + k * rpp < rows) out[k * rpp * pitch] = v[k];
         return;
     }
+    // a tile on a plane's edge: row and column reflected, one load (or one gather of its pixels) and one store per trip
+    const bool whole = x >= 0 && x + PPD - 1 < w;
+    int o[PPD];
+#pragma unroll
+    for (int i = 0; i < PPD; i++) o[i] = reflect(x + i, w);
 #pragma nounroll
     for (int r = r0; r < rows; r += rpp, out += rpp * pitch)
     {
-        const uint8_t *row = plane + (size_t)reflect(y0 + r, h) * src_pitch;
+        const nlm_gbytes row = (nlm_gbytes)plane + (size_t)reflect(y0 + r, h) * src_pitch;
         uint32_t v;
         if (whole)
-            v = reinterpret_cast<const u32_unaligned *>(row + x)->v;
+            v = ((nlm_gdword)(row + (size_t)x * BPS))->v;
         else
-            v = (uint32_t)row[o0] | ((uint32_t)row[o1] << 8) | ((uint32_t)row[o2] << 16) | ((uint32_t)row[o3] << 24);
+        {
+            v = 0;
+#pragma unroll
+            for (int i = 0; i < PPD; i++)
+                v |= (BPS == 1 ? (uint32_t)row[o[i]] : (uint32_t)((const NLM_GLOBAL uint16_t *)row)[o[i]]) << (8 * BPS * i);
+        }
         *out = v;
     }
 }
@@ -173,14 +242,16 @@ static bool nlm_no_static_lds(const void *kernel)
 // later plus 26.5 KB; the last four read the index of their mirror one row down and / or one pixel across (a
 // neighbouring lane's dword of the same wave) and only look the weight up, convert the pixel and accumulate - in the
 // reference's order of displacements, with the reference's weights.
-template <int N, int FAST, int CPD, bool PRE>
+// ORG1: every job of the launch has origin_tune == 1 exactly (the origin term in single precision, see there).
+template <int N, int FAST, int CPD, bool PRE, bool ORG1 = false>
 __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes_kernel(const NlmJob *__restrict__ jobs, int njobs,
-                                                                     int cmp_rows, int rq)
+                                                                     int cmp_rows, int rq, NlmTiles tc)
 {
     constexpr int NH = N / 2;
     constexpr int ROWS = RY + N - 1;
     constexpr bool INTIDX = FAST >= 2;
     constexpr bool SYM = FAST == 3 && !PRE;
+    constexpr int MAXT = (nlm_max_rows(N, SYM, CPD == 36 ? 4 : NLM_BORDER) + (TXN * TYN) / CPD - 1) / ((TXN * TYN) / CPD);   // staging trips of a thread
     static_assert(FAST != 3 || N <= 7, "the pairs' sharing reads a neighbouring lane's edge pixel: patch sizes up to 7");
     constexpr int ST_ROWS = RY + 1, ST_SLOT = ST_ROWS * TXN * TYN;        // the stash: [slot 0..3][row 0..RY][thread] dwords
     static_assert(NH <= PX, "patch must not reach past the adjacent lane");
@@ -204,15 +275,9 @@ __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes_kernel(const NlmJo
     uint32_t *s_rc = PRE ? s_r0 + tile_dwords : s_tc;
     uint32_t *s_stash = s_tc;                                     // SYM: over the next frame's tile (free while f == 0) and beyond
 
-    // which (frame, plane) job owns this tile: binary search over the jobs' first tile indices
-    int j = 0;
-    for (int hi = njobs - 1; j < hi;)
-    {
-        const int mid = (j + hi + 1) >> 1;
-        if ((int)blockIdx.x >= jobs[mid].tile_start) j = mid; else hi = mid - 1;
-    }
-    const NlmJob &job = jobs[j];
-    const int tile = blockIdx.x - job.tile_start;
+    // which (frame, plane) job owns this tile
+    int tile;
+    const NlmJob &job = jobs[job_of_tile(jobs, njobs, tc, tile)];
     const int tile_y = tile / job.tiles_x;
     int tile_x = tile - tile_y * job.tiles_x;
     // an even number of tiles per row (1920 / 120 = 16) would keep every column of tiles on one XCD, or on a few (workgroups
@@ -231,21 +296,24 @@ __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes_kernel(const NlmJo
     typedef __attribute__((address_space(3))) const float lds_cfloat;
     // (checked on the host before the first launch of every such instantiation: nlm_no_static_lds)
     __builtin_assume(!INTIDX || reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint32_t *)smem) == 0);
-    if (threadIdx.x < 128) s_exp[threadIdx.x] = job.exptable[threadIdx.x];
+    // the table entry travels with the first tile's loads: read here, stored behind them
+    float exp_entry = 0.f;
+    if (threadIdx.x < 128) exp_entry = ((const NLM_GLOBAL float *)job.exptable)[threadIdx.x];
     // lane tx holds the source pixels tx0 + 4*(tx-1) .. +3: the tiles start one lane (and rq
     // dwords of search halo) left of tx0
+    const int wx0 = tx0 - PX - 4 * rq, wy0 = ty0 - NH - RH;
+    auto stage = [&](uint32_t *lds, const uint8_t *plane, int pitch) __attribute__((always_inline))
+    {
+        load_tile<1, MAXT>(lds, CPD, CPD, cmp_rows, plane, pitch, w, h, wx0, wy0);
+    };
     if (PRE)
     {
-        load_tile_p(s_t0, CPD, CPD, cmp_rows, job.src_pre, job.src_pre_pitch, w, h,
-                    tx0 - PX - 4 * rq, ty0 - NH - RH);
-        load_tile_p(s_r0, CPD, CPD, cmp_rows, job.frame[0], job.fpitch[0], w, h,
-                    tx0 - PX - 4 * rq, ty0 - NH - RH);
+        stage(s_t0, job.src_pre, job.src_pre_pitch);
+        stage(s_r0, job.frame[0], job.fpitch[0]);
     }
     else
-    {
-        load_tile_p(s_t0, CPD, CPD, cmp_rows, job.frame[0], job.fpitch[0], w, h,
-                    tx0 - PX - 4 * rq, ty0 - NH - RH);
-    }
+        stage(s_t0, job.frame[0], job.fpitch[0]);
+    if (threadIdx.x < 128) s_exp[threadIdx.x] = exp_entry;
     const int own_off = (ty * RY + RH) * CPD + tx + rq;
     const uint32_t *own = s_t0 + own_off;       // this lane's source-patch dwords, row 0 of its walk
     const uint32_t *own_raw = s_r0 + own_off;   // the same pixels of the raw frame being filtered
@@ -267,35 +335,41 @@ __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes_kernel(const NlmJo
     // a wave (two tile rows of lanes) whose 16 output rows all lie below the plane has nothing to do
     const bool wave_live = ty0 + (ty & ~1) * RY < h;
 
-    for (int f = 0; f < job.nframes; f++)
+    // The displacement walks of frame f over the tiles staged for it.  F0 (f0c): frame 0 of a launch that shares the
+    // pairs' distances (a compile-time flag, so that the row walk of every other frame carries none of the stash code).
+    auto walks = [&](auto f0c, int f) __attribute__((always_inline))
     {
-        if (PRE || f > 0)
-        {
-            __syncthreads();   // everyone is done with the previous compare tile
-            if (PRE)
-            {
-                load_tile_p(s_tc, CPD, CPD, cmp_rows, job.frame_pre[f], job.ppitch[f], w, h,
-                            tx0 - PX - 4 * rq, ty0 - NH - RH);
-                if (f > 0)
-                    load_tile_p(s_rc, CPD, CPD, cmp_rows, job.frame[f], job.fpitch[f], w, h,
-                                tx0 - PX - 4 * rq, ty0 - NH - RH);
-            }
-            else
-            {
-                load_tile_p(s_tc, CPD, CPD, cmp_rows, job.frame[f], job.fpitch[f], w, h,
-                            tx0 - PX - 4 * rq, ty0 - NH - RH);
-            }
-        }
-        __syncthreads();
-        if (!wave_live) continue;
         const uint32_t *cmp_tile = (PRE || f > 0) ? s_tc : s_t0;     // what the patch distances are taken against
         const uint32_t *pix_tile = f > 0 ? s_rc : s_r0;              // what is averaged (== cmp_tile without a prefilter)
 
-        // one displacement; F0: frame 0 of a launch that shares the pairs' distances (a compile-time flag, so that the
-        // row walk of every other frame carries none of the stash code)
-        auto displacement = [&](auto f0c, int dy, int dx) __attribute__((always_inline))
+        // the second of a pair (SYM, frame 0): the index its mirror (-dy, -dx) left for the pixel at (row + dy, x + dx)
+        auto second = [&](int dy, int dx) __attribute__((always_inline))
         {
-            constexpr bool F0 = decltype(f0c)::value;
+            const int s = dx + 4 * rq;
+            const int sh = s & 3;
+            const uint32_t *st = s_stash + ((-dy + 1) * 3 + (-dx + 1)) * ST_SLOT + dy * (TXN * TYN) + (int)threadIdx.x;
+            const uint32_t *prow = pix_tile + (ty * RY + dy + RH + NH) * CPD + tx + (s >> 2);
+#pragma unroll
+            for (int o = 0; o < RY; o++)
+            {
+                const uint32_t w0 = st[o * (TXN * TYN)];
+                uint32_t id4 = w0;
+                if (dx > 0) id4 = __builtin_amdgcn_alignbyte(st[o * (TXN * TYN) + 1], w0, 1);
+                else if (dx < 0) id4 = __builtin_amdgcn_alignbyte(w0, st[o * (TXN * TYN) - 1], 3);
+                const uint32_t pix = __builtin_amdgcn_alignbyte(prow[o * CPD + 1], prow[o * CPD], sh);
+                const uint32_t o0 = (id4 << 2) & 0x1fcu, o1 = (id4 >> 6) & 0x1fcu, o2 = (id4 >> 14) & 0x1fcu, o3 = (id4 >> 22) & 0x1fcu;
+                const f2 wa = {*reinterpret_cast<lds_cfloat *>(o0), *reinterpret_cast<lds_cfloat *>(o1)};
+                const f2 wb = {*reinterpret_cast<lds_cfloat *>(o2), *reinterpret_cast<lds_cfloat *>(o3)};
+                const f2 pa = {(float)(int)byte_of(pix, 0), (float)(int)byte_of(pix, 1)};
+                const f2 pb = {(float)(int)byte_of(pix, 2), (float)(int)byte_of(pix, 3)};
+                aw[o][0] += wa; ap[o][0] += wa * pa;
+                aw[o][1] += wb; ap[o][1] += wb * pb;
+            }
+        };
+        // one displacement, but the second of a pair
+        auto displacement = [&](auto f0c_, int dy, int dx) __attribute__((always_inline))
+        {
+            constexpr bool F0 = decltype(f0c_)::value;
             {
                 if (f == 0 && dx == 0 && dy == 0)
                 {
@@ -306,6 +380,20 @@ __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes_kernel(const NlmJo
 #pragma unroll
                         for (int p = 0; p < PX; p++)
                         {
+                            if (ORG1)
+                            {
+                                // origin_tune == 1: the same numbers in single precision.  The reference rounds the double
+                                // sum a + t to float, a >= 0 a float below 2^13 (at most 18 weights <= 1, times 255) and
+                                // t an integer in 0 .. 255 (1, or the pixel).  t == 0: both forms give a.  Else take t in
+                                // [2^j, 2^(j+1)).  If a's last bit is worth 2^(j-52) or more, the double sum is exact (it
+                                // spans at most 53 bits), and rounding the exact sum to float IS the float addition.  If
+                                // not, a < 2^(j-28): a sixteenth of t's float half-ulp 2^(j-24).  The exact sum and the
+                                // double sum (off by 2^(j-53) at most) then both lie between t and the midpoint above it,
+                                // and both forms give t.  (tests/test_nlmeans_origin_cpu.py walks the exponents and ties.)
+                                aw[o][p / 2][p & 1] = aw[o][p / 2][p & 1] + 1.0f;
+                                ap[o][p / 2][p & 1] = ap[o][p / 2][p & 1] + (float)(int)byte_of(cpx, p);
+                                continue;
+                            }
                             aw[o][p / 2][p & 1] = (float)((double)aw[o][p / 2][p & 1] + origin_tune);
                             ap[o][p / 2][p & 1] = (float)((double)ap[o][p / 2][p & 1] + origin_tune * (double)(int)byte_of(cpx, p));
                             __builtin_amdgcn_sched_barrier(0);   // cold block: keep its f64 temporaries few
@@ -316,29 +404,6 @@ __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes_kernel(const NlmJo
 
                 const int s = dx + 4 * rq;                   // >= 0, wave-uniform
                 const int sh = s & 3;
-                if (SYM && F0 && (dy > 0 || (dy == 0 && dx > 0)))
-                {
-                    // the second of a pair: the index its mirror (-dy, -dx) left for the pixel at (row + dy, x + dx)
-                    const uint32_t *st = s_stash + ((-dy + 1) * 3 + (-dx + 1)) * ST_SLOT + dy * (TXN * TYN) + (int)threadIdx.x;
-                    const uint32_t *prow = pix_tile + (ty * RY + dy + RH + NH) * CPD + tx + (s >> 2);
-#pragma unroll
-                    for (int o = 0; o < RY; o++)
-                    {
-                        const uint32_t w0 = st[o * (TXN * TYN)];
-                        uint32_t id4 = w0;
-                        if (dx > 0) id4 = __builtin_amdgcn_alignbyte(st[o * (TXN * TYN) + 1], w0, 1);
-                        else if (dx < 0) id4 = __builtin_amdgcn_alignbyte(w0, st[o * (TXN * TYN) - 1], 3);
-                        const uint32_t pix = __builtin_amdgcn_alignbyte(prow[o * CPD + 1], prow[o * CPD], sh);
-                        const uint32_t o0 = (id4 << 2) & 0x1fcu, o1 = (id4 >> 6) & 0x1fcu, o2 = (id4 >> 14) & 0x1fcu, o3 = (id4 >> 22) & 0x1fcu;
-                        const f2 wa = {*reinterpret_cast<lds_cfloat *>(o0), *reinterpret_cast<lds_cfloat *>(o1)};
-                        const f2 wb = {*reinterpret_cast<lds_cfloat *>(o2), *reinterpret_cast<lds_cfloat *>(o3)};
-                        const f2 pa = {(float)(int)byte_of(pix, 0), (float)(int)byte_of(pix, 1)};
-                        const f2 pb = {(float)(int)byte_of(pix, 2), (float)(int)byte_of(pix, 3)};
-                        aw[o][0] += wa; ap[o][0] += wa * pa;
-                        aw[o][1] += wb; ap[o][1] += wb * pb;
-                    }
-                    return;
-                }
                 // the first of a pair leaves its indices behind; with dy < 0 its mirror reads them one row down
                 constexpr bool stash_on = SYM && F0;        // (here: dy < 0 or dy == 0 && dx < 0)
                 const bool extra_row = stash_on && dy < 0;
@@ -495,12 +560,41 @@ __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes_kernel(const NlmJo
                 }
             }
         };
-        for (int dy = -RH; dy <= RH; dy++)
-            for (int dx = -RH; dx <= RH; dx++)
+        if constexpr (SYM && decltype(f0c)::value)
+        {
+            // the 3 x 3 search in the reference's order: the firsts of the pairs and the origin, then the seconds
+            for (int i = 0; i < 5; i++) displacement(f0c, i < 3 ? -1 : 0, i < 3 ? i - 1 : i - 4);
+            for (int i = 5; i < 9; i++) second(i < 6 ? 0 : 1, i < 6 ? 1 : i - 7);
+        }
+        else
+        {
+            for (int dy = -RH; dy <= RH; dy++)
+                for (int dx = -RH; dx <= RH; dx++) displacement(f0c, dy, dx);
+        }
+    };
+
+    // (frame 0 of the pairs' form stands outside the loop of the frames: with its walks and the plain ones as two
+    // branches of one loop body the register allocator spills - 168 VGPRs and 184 bytes of scratch against 149 and none)
+    if constexpr (SYM)
+    {
+        __syncthreads();
+        if (wave_live) walks(std::true_type{}, 0);
+    }
+    for (int f = SYM ? 1 : 0; f < job.nframes; f++)
+    {
+        if (PRE || f > 0)
+        {
+            __syncthreads();   // everyone is done with the previous compare tile (SYM, f == 1: with the stash)
+            if (PRE)
             {
-                if (SYM && f == 0) displacement(std::true_type{}, dy, dx);
-                else displacement(std::false_type{}, dy, dx);
+                stage(s_tc, job.frame_pre[f], job.ppitch[f]);
+                if (f > 0) stage(s_rc, job.frame[f], job.fpitch[f]);
             }
+            else
+                stage(s_tc, job.frame[f], job.fpitch[f]);
+        }
+        __syncthreads();
+        if (wave_live) walks(std::false_type{}, f);
     }
 
     // normalise + store (the outer lanes own no pixels)
@@ -539,34 +633,6 @@ __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes_kernel(const NlmJo
 // in 16-bit containers; prefilter = 0).  A lane still owns 4 pixels x 8 rows, now 2 dwords per
 // row; tiles hold 2 pixels per dword.  Squared differences stay below 2^24 and the patch sums
 // below 2^31 for depths <= 12, so the integer path is unchanged.
-__device__ __forceinline__ void load_tile16(uint32_t *lds, int pitch, int dwords, int rows,
-                                            const uint8_t *__restrict__ plane, int src_pitch_bytes,
-                                            int w, int h, int x0, int y0)
-{
-    int tid = threadIdx.x;
-    asm volatile("" : "+v"(tid));
-    const int rpp = (TXN * TYN) / dwords;
-    const int r0 = (int)(((float)tid + 0.5f) * (1.0f / (float)dwords));
-    const int c = tid - r0 * dwords;
-    if (r0 >= rpp) return;
-    const int x = x0 + 2 * c;                                  // first of the dword's two pixels
-    const bool whole = x >= 0 && x + 1 < w;
-    const int o0 = reflect(x, w), o1 = reflect(x + 1, w);
-    // dword c of a row goes to the row's even half (c / 2) or odd half (pitch / 2 + c / 2): see nlmeans_lanes16_kernel
-    uint32_t *out = lds + r0 * pitch + (c >> 1) + (c & 1) * (pitch >> 1);
-#pragma nounroll
-    for (int r = r0; r < rows; r += rpp, out += rpp * pitch)
-    {
-        const uint16_t *row = reinterpret_cast<const uint16_t *>(plane + (size_t)reflect(y0 + r, h) * src_pitch_bytes);
-        uint32_t v;
-        if (whole)
-            v = reinterpret_cast<const u32_unaligned *>(row + x)->v;
-        else
-            v = (uint32_t)row[o0] | ((uint32_t)row[o1] << 16);
-        *out = v;
-    }
-}
-
 __device__ __forceinline__ uint32_t half_of(uint32_t v, int k) { return (v >> (16 * k)) & 0xffffu; }
 
 // (a.lo - b.lo, a.hi - b.hi) as two int16, and c + d.lo^2 / c + d.hi^2 (the compiler extracts the halves with a v_bfe and
@@ -594,11 +660,12 @@ __device__ __forceinline__ uint32_t sq_acc_hi(uint32_t d, uint32_t c)
 // pairs: all four need 59 KB of LDS per workgroup (two workgroups per CU), the three with dy != 0 fit three)
 template <int N, int FAST, int CPD, bool PRE, int SYM_PAIRS = 4>
 __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes16_kernel(const NlmJob *__restrict__ jobs, int njobs,
-                                                                       int cmp_rows, int rq)
+                                                                       int cmp_rows, int rq, NlmTiles tc)
 {
     constexpr int NH = N / 2;
     constexpr int ROWS = RY + N - 1;
     constexpr bool SYM = FAST == 3 && !PRE;
+    constexpr int MAXT = (nlm_max_rows(N, SYM, CPD == 76 ? 8 : NLM_BORDER) + (TXN * TYN) / CPD - 1) / ((TXN * TYN) / CPD);   // staging trips of a thread
     static_assert(FAST != 3 || N <= 7, "the pairs' sharing reads a neighbouring lane's edge pixel: patch sizes up to 7");
     constexpr int ST_ROWS = RY + 1, ST_SLOT = ST_ROWS * TXN * TYN;        // the stash: [slot][row 0..RY][thread] dwords
     static_assert(NH <= PX, "patch must not reach past the adjacent lane");
@@ -626,14 +693,8 @@ __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes16_kernel(const Nlm
     typedef __attribute__((address_space(3))) const float lds_cfloat;
     __builtin_assume(FAST < 2 || reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) uint32_t *)smem) == 0);   // nlm_no_static_lds
 
-    int j = 0;
-    for (int hi = njobs - 1; j < hi;)
-    {
-        const int mid = (j + hi + 1) >> 1;
-        if ((int)blockIdx.x >= jobs[mid].tile_start) j = mid; else hi = mid - 1;
-    }
-    const NlmJob &job = jobs[j];
-    const int tile = blockIdx.x - job.tile_start;
+    int tile;
+    const NlmJob &job = jobs[job_of_tile(jobs, njobs, tc, tile)];
     const int tile_y = tile / job.tiles_x;
     int tile_x = tile - tile_y * job.tiles_x;
     // an even number of tiles per row (1920 / 120 = 16) would keep every column of tiles on one XCD, or on a few (workgroups
@@ -647,14 +708,20 @@ __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes16_kernel(const Nlm
     const int tx = threadIdx.x & (TXN - 1);
     const int ty = threadIdx.x / TXN;
 
-    if (threadIdx.x < 128) s_exp[threadIdx.x] = job.exptable[threadIdx.x];
+    float exp_entry = 0.f;                                       // (travels with the first tile's loads)
+    if (threadIdx.x < 128) exp_entry = ((const NLM_GLOBAL float *)job.exptable)[threadIdx.x];
+    auto stage = [&](uint32_t *lds, const uint8_t *plane, int pitch) __attribute__((always_inline))
+    {
+        load_tile<2, MAXT>(lds, CPD, CPD, cmp_rows, plane, pitch, w, h, tx0 - PX - 4 * rq, ty0 - NH - RH);
+    };
     if (PRE)
     {
-        load_tile16(s_t0, CPD, CPD, cmp_rows, job.src_pre, job.src_pre_pitch, w, h, tx0 - PX - 4 * rq, ty0 - NH - RH);
-        load_tile16(s_r0, CPD, CPD, cmp_rows, job.frame[0], job.fpitch[0], w, h, tx0 - PX - 4 * rq, ty0 - NH - RH);
+        stage(s_t0, job.src_pre, job.src_pre_pitch);
+        stage(s_r0, job.frame[0], job.fpitch[0]);
     }
     else
-        load_tile16(s_t0, CPD, CPD, cmp_rows, job.frame[0], job.fpitch[0], w, h, tx0 - PX - 4 * rq, ty0 - NH - RH);
+        stage(s_t0, job.frame[0], job.fpitch[0]);
+    if (threadIdx.x < 128) s_exp[threadIdx.x] = exp_entry;
     // lane tx's own 4 pixels = dwords 2*tx + 2*rq, +1 of a tile row = entry tx + rq of the row's even and of its odd half
     const int own_off = (ty * RY + RH) * CPD + tx + rq;
     const uint32_t *own = s_t0 + own_off;
@@ -681,15 +748,11 @@ __global__ __launch_bounds__(TXN * TYN, 3) void nlmeans_lanes16_kernel(const Nlm
             __syncthreads();
             if (PRE)
             {
-                load_tile16(s_tc, CPD, CPD, cmp_rows, job.frame_pre[f], job.ppitch[f], w, h,
-                            tx0 - PX - 4 * rq, ty0 - NH - RH);
-                if (f > 0)
-                    load_tile16(s_rc, CPD, CPD, cmp_rows, job.frame[f], job.fpitch[f], w, h,
-                                tx0 - PX - 4 * rq, ty0 - NH - RH);
+                stage(s_tc, job.frame_pre[f], job.ppitch[f]);
+                if (f > 0) stage(s_rc, job.frame[f], job.fpitch[f]);
             }
             else
-                load_tile16(s_tc, CPD, CPD, cmp_rows, job.frame[f], job.fpitch[f], w, h,
-                            tx0 - PX - 4 * rq, ty0 - NH - RH);
+                stage(s_tc, job.frame[f], job.fpitch[f]);
         }
         __syncthreads();
         if (!wave_live) continue;
@@ -1545,7 +1608,10 @@ private:
             NlmJob *hj = h_jobs + (size_t)table * jobs_cap;
             NlmJob *dj = d_jobs + (size_t)table * jobs_cap;
             int nj = 0, tiles = 0, max_rh = 0;
-            bool all_rh1 = true;
+            bool all_rh1 = true, all_org1 = true;
+            // the tile counts of a frame's planes (NlmTiles), taken from the first frame's jobs and held against the rest
+            int plane_tiles[3] = {0, 0, 0}, planes = 0;
+            bool repeats = true;
             bool fast = true, fast_int = true;
             for (int t = 0; t < ready; t++)
                 for (int c = 0; c < 3; c++)
@@ -1584,11 +1650,24 @@ private:
                     jb.r_half = (par.range[c] - 1) / 2;
                     jb.tiles_x = generic ? (jb.w + GW - 1) / GW : (jb.w + LTW - 1) / LTW;
                     jb.tile_start = tiles;
-                    tiles += jb.tiles_x * (generic ? (jb.h + GH - 1) / GH : (jb.h + TH - 1) / TH);
+                    const int job_tiles = jb.tiles_x * (generic ? (jb.h + GH - 1) / GH : (jb.h + TH - 1) / TH);
+                    tiles += job_tiles;
+                    if (t == 0) plane_tiles[planes++] = job_tiles;
+                    else repeats &= plane_tiles[(nj - 1) % planes] == job_tiles;
                     max_rh = std::max(max_rh, jb.r_half);
                     all_rh1 &= jb.r_half == 1;
+                    all_org1 &= par.origin_tune[c] == 1.0;
                 }
             if (nj == 0) continue;
+            repeats &= nj == planes * ready;
+            NlmTiles tc = {0, 0, 0, 0};              // (all zero: the kernels search the table)
+            if (repeats && NLM_JOB_ARITH)
+            {
+                tc.per_frame = plane_tiles[0] + plane_tiles[1] + plane_tiles[2];
+                tc.after0 = plane_tiles[0];
+                tc.after1 = plane_tiles[0] + plane_tiles[1];
+                tc.planes = planes;
+            }
             // the table travels by a copy kernel reading the pinned host buffer: hipMemcpyAsync of this size holds the
             // calling thread until the stream gets to it (measured 1.4 ms per call in a busy chain)
             {
@@ -1622,6 +1701,9 @@ private:
             // (patch sizes up to 7: the mirrored index of a lane's edge pixel comes from the neighbouring lane's edge pixel,
             // whose own window must not reach past ITS neighbour - the outer lanes of a tile row have none)
             const bool sym = fast && fast_int && !pre && all_rh1 && n <= 7;
+            // (what the kernels size their staging registers by)
+            if (cmp_rows > nlm_max_rows(n, sym, cpd == (wide ? 76 : 36) ? (wide ? 8 : 4) : NLM_BORDER))
+                return ctx->fail(hipErrorInvalidValue, "nlmeans: tile taller than its kernel stages");
             size_t shmem = sizeof(uint32_t) * (pre ? 4 : 2) * (cpd * cmp_rows + 4) + 512;
             // (16-bit samples: NLM16_SYM_PAIRS of the four pairs share - the stash of three fits three workgroups on a CU)
             const int sym_slots = wide ? NLM16_SYM_PAIRS : 4;
@@ -1635,9 +1717,11 @@ private:
                 if ((fast && fast_int) && !lds_free) return ctx->fail(hipErrorInvalidValue, "nlmeans: kernel has static LDS in front of its table"); \
                 if (shmem > 65536) \
                     HBHIP_CHECK(ctx, hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-                HBHIP_LAUNCH(ctx, kname, (KERNEL), grid, block, shmem, dj, nj, cmp_rows, rq); \
+                HBHIP_LAUNCH(ctx, kname, (KERNEL), grid, block, shmem, dj, nj, cmp_rows, rq, tc); \
             } while (0)
 #define NLM_GO(NN, FF, CC, PP) NLM_LAUNCH((nlmeans_lanes_kernel<NN, FF, CC, PP>))
+#define NLM_SYM(NN, CC) do { if (all_org1 && NLM_ORIGIN_F32) NLM_LAUNCH((nlmeans_lanes_kernel<NN, (NN <= 7 ? 3 : 2), CC, false, true>)); \
+                             else NLM_GO(NN, (NN <= 7 ? 3 : 2), CC, false); } while (0)
 #define NLM_PRE(NN, FF, CC) do { if (pre) NLM_GO(NN, FF, CC, true); else NLM_GO(NN, FF, CC, false); } while (0)
 #define NLM_16P(NN, FF, PP) do { if (cpd == 76) NLM_LAUNCH((nlmeans_lanes16_kernel<NN, FF, 76, PP>)); \
                                 else NLM_LAUNCH((nlmeans_lanes16_kernel<NN, FF, 84, PP>)); } while (0)
@@ -1645,8 +1729,8 @@ private:
 #define NLM_16S(NN) NLM_LAUNCH((nlmeans_lanes16_kernel<NN, (NN <= 7 ? 3 : 2), 76, false, NLM16_SYM_PAIRS>))
 #define NLM_VAR(NN) do { const char *kname = "nlmeans_plane_n" #NN; \
                      if (wide) { if (sym && NN <= 7 && cpd == 76) NLM_16S(NN); else if (fast && fast_int) NLM_16(NN, 2); else if (fast) NLM_16(NN, 1); else NLM_16(NN, 0); } \
-                     else if (cpd == 36) { if (sym && NN <= 7) NLM_GO(NN, (NN <= 7 ? 3 : 2), 36, false); else if (fast && fast_int) NLM_PRE(NN, 2, 36); else if (fast) NLM_PRE(NN, 1, 36); else NLM_PRE(NN, 0, 36); } \
-                     else { if (sym && NN <= 7) NLM_GO(NN, (NN <= 7 ? 3 : 2), 44, false); else if (fast && fast_int) NLM_PRE(NN, 2, 44); else if (fast) NLM_PRE(NN, 1, 44); else NLM_PRE(NN, 0, 44); } } while (0)
+                     else if (cpd == 36) { if (sym && NN <= 7) NLM_SYM(NN, 36); else if (fast && fast_int) NLM_PRE(NN, 2, 36); else if (fast) NLM_PRE(NN, 1, 36); else NLM_PRE(NN, 0, 36); } \
+                     else { if (sym && NN <= 7) NLM_SYM(NN, 44); else if (fast && fast_int) NLM_PRE(NN, 2, 44); else if (fast) NLM_PRE(NN, 1, 44); else NLM_PRE(NN, 0, 44); } } while (0)
             switch (n)
             {
                 case 3: NLM_VAR(3); break;
@@ -1659,6 +1743,7 @@ private:
 #undef NLM_16P
 #undef NLM_16S
 #undef NLM_PRE
+#undef NLM_SYM
 #undef NLM_GO
 #undef NLM_LAUNCH
             HBHIP_CHECK(ctx, hipGetLastError());
