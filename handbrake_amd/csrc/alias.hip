@@ -1856,6 +1856,269 @@ public:
     short *d_hq = nullptr, *d_vq = nullptr;
 };
 
+// ------------------------------------------------------------------ format (chroma up-sampling at equal or higher depth)
+// `format=pix_fmts=...` when the target has MORE chroma samples than the stream (4:2:0 -> 4:2:2, 4:2:2 -> 4:4:4,
+// 4:2:0 -> 4:4:4; 8 -> 8, 10 -> 10, 12 -> 12, 8 -> 10, 8 -> 12, 10 -> 12 bits): what an encoder that only takes 4:2:2 or
+// 4:4:4 input gets behind a 4:2:0 title (work.c:1525-1552, the third match_pix_fmt call).  libswscale's general scaler as
+// above, on the tables of the 1:2 ratio - sws_filter(bicubic)'s x_inc <= 1 << 16 arm, four taps - with hScale8To15 /
+// hScale16To15's intermediates by the SOURCE depth and yuv2planeX_8 / _10 / _12 by the TARGET's (the flat round term: the
+// depth does not fall, nothing is dithered).  Luma runs through the identity filters: v << (ddepth - sdepth), a copy at
+// equal depth (no top-bit replication in either range, unlike format_kernel's full-range luma).  PARITY UNPINNED; the
+// model is tests/format_upsample_model.py.
+// Siting: target row j a quarter above (j even) / below (j odd) source row j / 2 (srcPos = dstPos = 128); target column i
+// on source column i / 2 for an even i, midway to the next for an odd one (left-sited chroma: srcPos 64, dstPos 128).
+//
+// The tables in a NOMINAL form again: output row / column i taps the UP_TAPS = 6 source samples from 2 * (i >> 2) - 2 on.
+// The four taps of output i lie in (i >> 1) - 1 .. (i >> 1) + 2 horizontally and (i >> 1) - 2 .. (i >> 1) + 2 vertically
+// (an odd target size, 2 s - 1 for s, moves the positions by up to half a sample along the plane), both inside that
+// window for all four outputs of a group; create() checks every row and declines a table that does not fit.  The window
+// starts on an even sample and is the same for a thread's four adjacent output columns, so a thread loads three sample
+// pairs a source row and every output is three v_dot2_i32_i16; vertically the window is the same for four adjacent
+// output rows, a thread owns UP_ROWS = 8 of them over UP_ROWS / 2 + 4 source rows, which are loaded ONCE, taken through
+// the horizontal pass (or the identity's shift) and kept in registers as 15-bit intermediates, a pair of rows to a dword.
+// No LDS.  The vertical coefficients of a row are the same for a whole wave (one threadIdx.y) and come through scalar
+// loads.  Without a vertical pass a thread makes UP_ROWS_H rows, each from its own source row.
+constexpr int UP_TAPS = 6, UP_ROWS = 8, UP_ROWS_H = 4, UP_LROWS = 4;
+struct FormatUpsampleArgs
+{
+    const uint8_t *src[FMT_FRAMES][3];
+    uint8_t       *dst[FMT_FRAMES][3];
+    int spitch[3], dpitch[3];
+    int w, h, scw, sch, dcw, dch, sdepth, ddepth;     // luma size; chroma size of the source and of the target; depths
+    int ly, cy;                               // grid.y: ly workgroup rows of luma, then cy of Cb, then cy of Cr
+    const short *hq, *vq;                     // [column][UP_TAPS] (columns padded to 4), [row][UP_TAPS]
+};
+
+// samples s0 .. s0 + 5 of a row (s0 even, possibly negative) as three dwords of 16-bit pairs; those outside [0, w) read as
+// 0 and are never loaded (their coefficients are 0)
+template <typename PIX>
+__device__ __forceinline__ void up_load6(const PIX *row, int s0, int w, uint32_t *p)
+{
+    if (s0 >= 0 && s0 + 5 < w)
+    {
+#pragma unroll
+        for (int g = 0; g < 3; g++)
+        {
+            if (sizeof(PIX) == 1) p[g] = __builtin_amdgcn_perm(0u, (uint32_t)*reinterpret_cast<const uint16_t *>(row + s0 + 2 * g), 0x0c010c00u);
+            else                  p[g] = *reinterpret_cast<const uint32_t *>(row + s0 + 2 * g);
+        }
+    }
+    else
+    {
+        uint32_t v[6];
+#pragma unroll
+        for (int i = 0; i < 6; i++) v[i] = (s0 + i >= 0 && s0 + i < w) ? (uint32_t)row[s0 + i] : 0u;
+#pragma unroll
+        for (int g = 0; g < 3; g++) p[g] = v[2 * g] | (v[2 * g + 1] << 16);
+    }
+}
+
+// HP / VP: the chroma planes take a horizontal / a vertical pass.  The grid is format_resample_kernel's: grid.z = frame,
+// grid.y = the workgroup rows of luma (four samples of UP_LROWS rows a thread), then those of Cb, then those of Cr (a
+// chroma thread row is UP_ROWS / UP_ROWS_H output rows); grid.x is sized for luma.
+template <typename PIX, typename DPIX, bool HP, bool VP>
+__global__ __launch_bounds__(256, 4) void format_upsample_kernel(FormatUpsampleArgs a)
+{
+    static_assert((HP || VP) && sizeof(DPIX) >= sizeof(PIX), "one pass at least; the depth does not fall");
+    const int f = blockIdx.z;
+    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if ((int)blockIdx.y < a.ly)
+    {
+        // the identity filters and the output stage: (v << (15 - sdepth) << 12 + round) >> shift = v << (ddepth - sdepth)
+        const int y0 = (blockIdx.y * blockDim.y + threadIdx.y) * UP_LROWS;
+        if (x0 >= a.w) return;
+        const int up = a.ddepth - a.sdepth;
+        uint32_t p[UP_LROWS][2];
+#pragma unroll
+        for (int r = 0; r < UP_LROWS; r++)
+            if (y0 + r < a.h) fr_load_pairs(reinterpret_cast<const PIX *>(a.src[f][0] + (size_t)(y0 + r) * a.spitch[0]), x0, a.w, p[r]);
+#pragma unroll
+        for (int r = 0; r < UP_LROWS; r++)
+        {
+            if (y0 + r >= a.h) break;
+            int o[4];
+#pragma unroll
+            for (int i = 0; i < 4; i++) o[i] = (int)((p[r][i >> 1] >> (16 * (i & 1))) & 0xffffu) << up;
+            fr_store4(reinterpret_cast<DPIX *>(a.dst[f][0] + (size_t)(y0 + r) * a.dpitch[0]), x0, a.w, o);
+        }
+        return;
+    }
+    const int cby = (int)blockIdx.y - a.ly, c = 1 + cby / a.cy;
+    constexpr int ROWS = VP ? UP_ROWS : UP_ROWS_H;                           // output rows a thread
+    const int j0 = __builtin_amdgcn_readfirstlane((cby % a.cy) * blockDim.y + threadIdx.y) * ROWS;      // the first one: one value a wave
+    if (x0 >= a.dcw || j0 >= a.dch) return;
+    const int sh = sizeof(PIX) == 1 ? 7 : a.sdepth - 1;                      // hScale8To15_c / hScale16To15_c
+    // yuv2planeX_8_c: the flat dither of 64 (round = 64 << 12, shift 19); yuv2planeX_10 / _12: half of the shift 27 - depth
+    const int shift = sizeof(DPIX) == 1 ? 19 : 27 - a.ddepth, round = sizeof(DPIX) == 1 ? 64 << 12 : 1 << (shift - 1);
+    const int vmax = (1 << a.ddepth) - 1;
+    const uint8_t *sp = a.src[f][c];
+    const int spitch = a.spitch[c];
+    uint32_t hc[HP ? 2 * UP_TAPS : 1];                                       // the four columns' coefficients, in pairs
+    if (HP)
+    {
+        const uint4 *q = reinterpret_cast<const uint4 *>(a.hq + (size_t)x0 * UP_TAPS);      // 48 bytes a thread, 16-byte aligned
+#pragma unroll
+        for (int k = 0; k < UP_TAPS / 2; k++)
+        {
+            const uint4 t = q[k];
+            hc[4 * k] = t.x; hc[4 * k + 1] = t.y; hc[4 * k + 2] = t.z; hc[4 * k + 3] = t.w;
+        }
+    }
+    // source row sr (clamped into the plane: the rows outside of it have coefficient 0) -> the four columns' intermediates
+    auto hrow = [&](int sr, int *e) {
+        const PIX *row = reinterpret_cast<const PIX *>(sp + (size_t)min(max(sr, 0), a.sch - 1) * spitch);
+        if (HP)
+        {
+            uint32_t p[UP_TAPS / 2];                                         // the six samples under the four columns, in pairs
+            up_load6(row, (x0 >> 1) - 2, a.scw, p);
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+            {
+                int v = 0;
+#pragma unroll
+                for (int u = 0; u < UP_TAPS / 2; u++) v = dot2(p[u], hc[i * (UP_TAPS / 2) + u], v);
+                e[i] = min(v >> sh, (1 << 15) - 1);
+            }
+        }
+        else
+        {
+            // the identity filter, one tap of 1 << 14: (s << 14) >> sh
+            uint32_t p[2];
+            fr_load_pairs(row, x0, a.scw, p);
+#pragma unroll
+            for (int i = 0; i < 4; i++) e[i] = (int)((p[i >> 1] >> (16 * (i & 1))) & 0xffffu) << (14 - sh);
+        }
+    };
+    auto put = [&](int j, const int *acc) {
+        int o[4];
+#pragma unroll
+        for (int i = 0; i < 4; i++) o[i] = min(max(acc[i] >> shift, 0), vmax);
+        fr_store4(reinterpret_cast<DPIX *>(a.dst[f][c] + (size_t)j * a.dpitch[c]), x0, a.dcw, o);
+    };
+    if (!VP)
+    {
+        int e[ROWS][4];
+#pragma unroll
+        for (int r = 0; r < ROWS; r++) hrow(j0 + r, e[r]);
+#pragma unroll
+        for (int r = 0; r < ROWS; r++)
+        {
+            if (j0 + r >= a.dch) break;
+            int acc[4];                                                      // the identity filter: one tap of 1 << 12
+#pragma unroll
+            for (int i = 0; i < 4; i++) acc[i] = round + e[r][i] * (1 << 12);
+            put(j0 + r, acc);
+        }
+    }
+    else
+    {
+        // source rows (j0 >> 1) - 2 + 2k and the one below it, row pair k: output rows j0 + 4g .. j0 + 4g + 3 read pairs g .. g + 2
+        constexpr int NP = ROWS / 4 + UP_TAPS / 2 - 1;
+        uint32_t hp[NP][4];
+#pragma unroll
+        for (int k = 0; k < NP; k++)
+        {
+            int ea[4], eb[4];
+            hrow((j0 >> 1) - 2 + 2 * k, ea);
+            hrow((j0 >> 1) - 1 + 2 * k, eb);
+#pragma unroll
+            for (int i = 0; i < 4; i++) hp[k][i] = ((uint32_t)ea[i] & 0xffffu) | ((uint32_t)eb[i] << 16);
+        }
+#pragma unroll
+        for (int r = 0; r < ROWS; r++)
+        {
+            if (j0 + r >= a.dch) break;
+            const uint32_t *vq = reinterpret_cast<const uint32_t *>(a.vq + (size_t)(j0 + r) * UP_TAPS);
+            int acc[4] = { round, round, round, round };
+#pragma unroll
+            for (int u = 0; u < UP_TAPS / 2; u++)
+            {
+                const uint32_t q = vq[u];
+#pragma unroll
+                for (int i = 0; i < 4; i++) acc[i] = dot2(hp[(r >> 2) + u][i], q, acc[i]);
+            }
+            put(j0 + r, acc);
+        }
+    }
+}
+
+class FormatUpsampleFilter : public BurstFilter
+{
+public:
+    using BurstFilter::BurstFilter;
+    ~FormatUpsampleFilter() override
+    {
+        if (d_hq) (void)hipFree(d_hq);
+        if (d_vq) (void)hipFree(d_vq);
+    }
+    // sws_filter's rows in the kernel's nominal frame; false: a row has a tap outside of it
+    static bool nominal(int src, int dst, int one, int src_pos, int dst_pos, int pad, std::vector<short> &out)
+    {
+        std::vector<int> pos;
+        std::vector<short> coef;
+        const int taps = sws_filter(src, dst, one, src_pos, dst_pos, pos, coef, true);
+        out.assign((size_t)((dst + pad - 1) / pad * pad) * UP_TAPS, 0);
+        for (int i = 0; i < dst; i++)
+            for (int t = 0; t < taps; t++)
+            {
+                const short q = coef[(size_t)i * taps + t];
+                if (q == 0) continue;
+                const int k = pos[i] + t - (2 * (i >> 2) - 2);
+                if (k < 0 || k >= UP_TAPS || pos[i] + t < 0 || pos[i] + t >= src) return false;
+                out[(size_t)i * UP_TAPS + k] = q;
+            }
+        return true;
+    }
+    int setup()
+    {
+        hpass = out_geo.log2_cw < in_geo.log2_cw;
+        vpass = out_geo.log2_ch < in_geo.log2_ch;
+        auto up = [&](short *&dptr, const std::vector<short> &v) -> int {
+            HBHIP_CHECK(ctx, hipMalloc((void **)&dptr, sizeof(short) * v.size()));
+            HBHIP_CHECK(ctx, hipMemcpy(dptr, v.data(), sizeof(short) * v.size(), hipMemcpyHostToDevice));
+            return HBHIP_OK;
+        };
+        std::vector<short> q;
+        // left-sited chroma, the down-sampling's positions swapped: source 128 >> 1, target 128; rows: centred, 128 both
+        if (hpass)
+        {
+            if (!nominal(in_geo.pw[1], out_geo.pw[1], 1 << 14, 64, 128, 4, q)) return HBHIP_ERR_UNSUPPORTED;
+            const int rc = up(d_hq, q);
+            if (rc != HBHIP_OK) return rc;
+        }
+        if (vpass)
+        {
+            if (!nominal(in_geo.ph[1], out_geo.ph[1], 1 << 12, 128, 128, 1, q)) return HBHIP_ERR_UNSUPPORTED;
+            const int rc = up(d_vq, q);
+            if (rc != HBHIP_OK) return rc;
+        }
+        return HBHIP_OK;
+    }
+    int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
+    {
+        return hbhip_for_each_burst<FMT_FRAMES, FormatUpsampleArgs>(ctx, ins, outs, n, [&](FormatUpsampleArgs &a, int nf, int, uintptr_t bits) {
+            if ((bits & 7) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
+            a.w = in_geo.width; a.h = in_geo.height; a.sdepth = in_geo.depth; a.ddepth = out_geo.depth;
+            a.scw = in_geo.pw[1]; a.sch = in_geo.ph[1]; a.dcw = out_geo.pw[1]; a.dch = out_geo.ph[1];
+            a.hq = d_hq; a.vq = d_vq;
+            a.ly = (a.h + 4 * UP_LROWS - 1) / (4 * UP_LROWS);
+            const int rows = 4 * (vpass ? UP_ROWS : UP_ROWS_H);               // output rows a workgroup
+            a.cy = (a.dch + rows - 1) / rows;
+            const dim3 grid(hbhip_grid_x((a.w + 255) / 256), a.ly + 2 * a.cy, nf);
+#define FU_GO(PIX, DPIX, HP, VP) HBHIP_LAUNCH(ctx, "format_upsample", (format_upsample_kernel<PIX, DPIX, HP, VP>), grid, dim3(64, 4), 0, a)
+#define FU_PICK(PIX, DPIX) do { if (hpass && vpass) FU_GO(PIX, DPIX, true, true); else if (hpass) FU_GO(PIX, DPIX, true, false); else FU_GO(PIX, DPIX, false, true); } while (0)
+            if (out_geo.bps == 1)     FU_PICK(uint8_t, uint8_t);
+            else if (in_geo.bps == 1) FU_PICK(uint8_t, uint16_t);
+            else                      FU_PICK(uint16_t, uint16_t);
+#undef FU_PICK
+#undef FU_GO
+            return HBHIP_OK;
+        });
+    }
+    bool hpass = false, vpass = false;
+    short *d_hq = nullptr, *d_vq = nullptr;
+};
+
 } // namespace
 
 extern "C" int hbhip_format_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth,
@@ -1914,6 +2177,34 @@ extern "C" int hbhip_format_scaled_create(hbhip_ctx *ctx, int width, int height,
 {
     (void)chroma_location;
     return format_resample_make(ctx, width, height, src_depth, dst_depth, src_log2_cw, src_log2_ch, dst_log2_cw, dst_log2_ch, out);
+}
+
+// (chroma_location: every value is taken as left-sited, as above)
+extern "C" int hbhip_format_upsample_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
+                                            int src_log2_ch, int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out)
+{
+    (void)chroma_location;
+    if (!ctx || !out) return HBHIP_ERR_ARG;
+    *out = nullptr;
+    for (int d : {src_depth, dst_depth})
+        if (d != 8 && d != 10 && d != 12) return HBHIP_ERR_UNSUPPORTED;
+    if (width < 1 || height < 1) return HBHIP_ERR_ARG;
+    if (!hbhip_yuv_layout_ok(src_log2_cw, src_log2_ch) || !hbhip_yuv_layout_ok(dst_log2_cw, dst_log2_ch)) return HBHIP_ERR_UNSUPPORTED;
+    // up only: no dimension loses chroma samples, the depth does not fall, and one dimension gains
+    if (dst_log2_cw > src_log2_cw || dst_log2_ch > src_log2_ch || dst_depth < src_depth ||
+        (dst_log2_cw == src_log2_cw && dst_log2_ch == src_log2_ch)) return HBHIP_ERR_UNSUPPORTED;
+    PicGeometry gi, go;
+    gi.set(width, height, src_depth, src_log2_cw, src_log2_ch);
+    go.set(width, height, dst_depth, dst_log2_cw, dst_log2_ch);
+    // a chroma plane so small that initFilter's clamp (size = min(size, src - 2)) cuts the five taps short
+    if ((dst_log2_cw < src_log2_cw && gi.pw[1] - 2 < 5) || (dst_log2_ch < src_log2_ch && gi.ph[1] - 2 < 5))
+        return HBHIP_ERR_UNSUPPORTED;
+    FormatUpsampleFilter *f = hbhip_make_filter<FormatUpsampleFilter>(ctx, gi, go);
+    if (!f) return HBHIP_ERR_NOMEM;
+    const int rc = f->setup();
+    if (rc != HBHIP_OK) { delete f; return rc; }
+    *out = f;
+    return HBHIP_OK;
 }
 
 extern "C" int hbhip_pad_create(hbhip_ctx *ctx, const hbhip_pad_params *p, int width, int height, int depth,

@@ -224,10 +224,17 @@ static int rotate_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
  *     libswscale takes every semi-planar target but the two exact repacks through its scaler, so a depth change alone is
  *     the scaled form too (yuv420p10le -> nv12 is NOT format_kernel's 10 -> 8); a stream that already is the planar
  *     step passes through.
+ *   - planar YUV chroma UP-sampling, 4:2:0 -> 4:2:2, 4:2:2 -> 4:4:4, 4:2:0 -> 4:4:4, at equal or HIGHER depth
+ *     (format_upsample_kernel), when hip_common.c has marked the entry with HBHIP_FORMAT_UP_STEP, i.e. behind another
+ *     drop-in of a device-resident run.  The reference does ask for it: hb_get_best_pix_fmt chooses the pipeline's format
+ *     from the title alone, never above its chroma (common.c:7516-7604), and for an encoder whose list holds only 4:2:2 or
+ *     4:4:4 formats (x264 high422 / high444, x265 main422-10 / -12 / main444-8, common.c:2252-2384; ProRes, DNxHR) the
+ *     two chroma-keeping match_pix_fmt calls of work.c:1525-1552 find nothing and the third, match_pix_fmt(..., 0, 0),
+ *     returns the list's first entry: `format=yuv422p10le` behind a yuv420p chain.
  * Any other target makes init() fail, which keeps the CPU filter (work.c:1861-1868): more chroma samples than the
- * stream has (the rule above never asks for it), fewer chroma samples together with a HIGHER depth, semi-planar targets
- * that nobody marked (a lone `format=nv12` has no adapter to repack for it), RGB, a chroma plane too small for
- * swscale's nine taps. */
+ * stream has where nobody marked the entry (a lone `format` on host frames would pay a round trip over the bus for a
+ * cheap filter), fewer chroma samples together with a HIGHER depth, semi-planar targets that nobody marked (a lone
+ * `format=nv12` has no adapter to repack for it), RGB, a chroma plane too small for swscale's taps (nine down, five up). */
 static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
 static int format_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
 
@@ -274,8 +281,14 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
             return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
     const int resample = dd->log2_chroma_w != desc->log2_chroma_w || dd->log2_chroma_h != desc->log2_chroma_h;
     const int sdepth = desc->comp[0].depth, ddepth = dd->comp[0].depth;
+    /* hip_common.c's mark on an entry inside a run whose target has more chroma samples: no dimension loses any, one gains,
+     * and the depth does not fall.  Without the mark (a lone drop-in on host frames) such a target is declined below. */
+    int upsample = 0;
+    hb_dict_extract_bool(&upsample, filter->settings, HBHIP_FORMAT_UP_STEP);
+    upsample = upsample && pv->s.dev_io && !planar_step && resample && ddepth >= sdepth &&
+               dd->log2_chroma_w <= desc->log2_chroma_w && dd->log2_chroma_h <= desc->log2_chroma_h;
     /* fewer chroma samples AND a higher depth: nothing asks for it; a biplanar target above the stream's depth neither */
-    if ((resample || planar_step) && ddepth > sdepth)
+    if (!upsample && (resample || planar_step) && ddepth > sdepth)
         return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
     if (planar_step && !resample && ddepth == sdepth)
     {
@@ -286,8 +299,11 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     if (ctx == NULL) return hbhip_host_simple_fail(filter, HBHIP_ERR_NODEVICE);
     /* the scaler's path at a lower depth: with fewer chroma samples, or (semi-planar target) on its own */
     const int scaled = ddepth < sdepth && (resample || planar_step);
-    /* (the create functions decline what is left: upsampling, other depths, planes too small) */
-    int rc = scaled   ? hbhip_format_scaled_create(ctx, init->geometry.width, init->geometry.height, sdepth, ddepth,
+    /* (the create functions decline what is left: upsampling that nobody marked, other depths, planes too small) */
+    int rc = upsample ? hbhip_format_upsample_create(ctx, init->geometry.width, init->geometry.height, sdepth, ddepth,
+                                                     desc->log2_chroma_w, desc->log2_chroma_h, dd->log2_chroma_w,
+                                                     dd->log2_chroma_h, init->chroma_location, &pv->s.dev)
+           : scaled   ? hbhip_format_scaled_create(ctx, init->geometry.width, init->geometry.height, sdepth, ddepth,
                                                    desc->log2_chroma_w, desc->log2_chroma_h, dd->log2_chroma_w,
                                                    dd->log2_chroma_h, init->chroma_location, &pv->s.dev)
            : resample ? hbhip_format_resample_create(ctx, init->geometry.width, init->geometry.height, sdepth,

@@ -36,6 +36,10 @@ static inline int hbhip_host_is_biplanar(int pix_fmt) { return pix_fmt == HBHIP_
  * the public `format=`): the Format drop-in then makes the planar step only, yuv420p / yuv420p10le, and the run's download
  * adapter repacks it.  hb_hip_filter_init_failed() strips it before the CPU filter sees the settings. */
 #define HBHIP_FORMAT_PLANAR_STEP "hip-planar-step"
+/* Its sibling on a `format=yuv422p... | yuv444p...` entry inside a run whose target has MORE chroma samples than the job's
+ * frames (at equal or higher depth): the Format drop-in takes such a target only where this key stands, i.e. where the
+ * frames already are in HBM.  Stripped wherever the key above is. */
+#define HBHIP_FORMAT_UP_STEP "hip-up-step"
 static inline void hbhip_host_biplanar_from_buf(hbhip_host_biplanar *f, const hb_buffer_t *b)
 {
     for (int p = 0; p < 2; p++)

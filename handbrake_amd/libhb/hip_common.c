@@ -11,7 +11,9 @@
  *      so frames stay in HBM inside the run (a lone drop-in moves its own frames; adapters would only add two threads).
  *   3. a `format=nv12 | p010le` entry behind a drop-in of a planar YUV job is split: the Format drop-in is told (through
  *      HBHIP_FORMAT_PLANAR_STEP in its settings, never through the public `format=` value) to make yuv420p / yuv420p10le,
- *      and the run's download adapter gets format=nv12 | p010le and repacks on the GPU (mark_planar_steps).
+ *      and the run's download adapter gets format=nv12 | p010le and repacks on the GPU (mark_planar_steps).  The same walk
+ *      marks a `format=yuv422p... | yuv444p...` entry behind a drop-in whose target has MORE chroma samples than the job's
+ *      frames (HBHIP_FORMAT_UP_STEP): the Format drop-in takes such a target only there.
  * And one thing the VideoToolbox path does not need: a drop-in's init() may refuse settings it has no kernels for.
  * work.c drops a filter whose init fails (:1861-1868) - for a drop-in that would silently lose the filter, so the init
  * loop calls hb_hip_filter_init_failed() first, which puts the CPU filter back (and re-brackets the run around it).
@@ -93,7 +95,16 @@ static int planar_step_target(const hb_filter_object_t *f)
  * `format=nv12`, so that the fallback hands the CPU filter its own settings (hb_hip_filter_init_failed strips the mark).
  * Not marked: an 8-bit stream under p010le (a higher depth: init() declines it as before), and an entry with no drop-in
  * in front of it - on a yuv420p job its planar step would be the identity, and an interleave on the CPU is cheaper than a
- * round trip over the bus. */
+ * round trip over the bus.
+ *
+ * The same walk marks the UP step (HBHIP_FORMAT_UP_STEP).  work.c appends `format=yuv422p...` / `format=yuv444p...` to a
+ * 4:2:0 chain when the encoder's list holds only such formats: hb_get_best_pix_fmt chooses the pipeline's format from the
+ * title alone (common.c:7516-7604), the two chroma-keeping match_pix_fmt calls find nothing in the list and the third,
+ * match_pix_fmt(..., 0, 0), returns its first entry (x264 high422 / high444, x265 main422-10 / -12 / main444-8,
+ * common.c:2252-2384; ProRes, DNxHR).  Such an entry - a planar YUV 4:2:0 / 4:2:2 / 4:4:4 target at 8 / 10 / 12 bits that
+ * loses chroma samples in no dimension, gains them in one at least and is no shallower than the job - is marked under the
+ * same condition, a drop-in in front of it, and for the same reason; the Format drop-in takes such a target only where
+ * the mark stands, so a lone `format=yuv422p` keeps its CPU filter as before. */
 static void mark_planar_steps(hb_job_t *job, int from)
 {
     hb_list_t *list = job->list_filter;
@@ -107,11 +118,26 @@ static void mark_planar_steps(hb_job_t *job, int from)
         if (!hb_dict_extract_string(&name, f->settings, "format") || name == NULL) { free(name); continue; }
         const int fmt = av_get_pix_fmt(name);
         free(name);
-        if (!hbhip_host_is_biplanar(fmt) || desc->comp[0].depth < (fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10)) continue;
+        const char *key = NULL;
+        if (hbhip_host_is_biplanar(fmt))
+        {
+            if (desc->comp[0].depth >= (fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10)) key = HBHIP_FORMAT_PLANAR_STEP;
+        }
+        else
+        {
+            /* the up step: a planar YUV target that loses chroma samples in no dimension, gains them in one at least, and
+             * is no shallower than the job's frames */
+            const AVPixFmtDescriptor *dd = av_pix_fmt_desc_get(fmt);
+            if (hbhip_host_planar_yuv(dd) && dd->log2_chroma_w <= desc->log2_chroma_w && dd->log2_chroma_h <= desc->log2_chroma_h &&
+                (dd->log2_chroma_w < desc->log2_chroma_w || dd->log2_chroma_h < desc->log2_chroma_h) &&
+                dd->comp[0].depth >= desc->comp[0].depth)
+                key = HBHIP_FORMAT_UP_STEP;
+        }
+        if (key == NULL) continue;
         int j = i - 1;
         while (j >= from && hb_hip_filter_is_hw_transparent(hb_list_item(list, j))) j--;
         if (j < from || is_adapter(hb_list_item(list, j)) || !hb_hip_filter_is_hip(hb_list_item(list, j))) continue;
-        hb_dict_set_string(f->settings, HBHIP_FORMAT_PLANAR_STEP, "1");
+        hb_dict_set_string(f->settings, key, "1");
     }
 }
 
@@ -215,7 +241,8 @@ int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
     }
     hb_dict_free(&cpu->settings);
     cpu->settings = f->settings ? hb_value_dup(f->settings) : hb_dict_init();
-    hb_dict_remove(cpu->settings, HBHIP_FORMAT_PLANAR_STEP);  /* mark_planar_steps' key is nothing the CPU filter knows */
+    hb_dict_remove(cpu->settings, HBHIP_FORMAT_PLANAR_STEP);  /* mark_planar_steps' keys are nothing the CPU filter knows */
+    hb_dict_remove(cpu->settings, HBHIP_FORMAT_UP_STEP);
     if (cpu->sub_filter != NULL)                              /* mt_frame wrapper: hb_add_filter_dict copies them down */
     {
         hb_dict_free(&cpu->sub_filter->settings);
@@ -259,7 +286,9 @@ int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
     for (int i = pos + 1; i < hb_list_count(list); i++)
     {
         hb_filter_object_t *g = hb_list_item(list, i);
-        if (g->id == HB_FILTER_FORMAT && g->settings != NULL) hb_dict_remove(g->settings, HBHIP_FORMAT_PLANAR_STEP);
+        if (g->id != HB_FILTER_FORMAT || g->settings == NULL) continue;
+        hb_dict_remove(g->settings, HBHIP_FORMAT_PLANAR_STEP);
+        hb_dict_remove(g->settings, HBHIP_FORMAT_UP_STEP);
     }
     mark_planar_steps(job, pos + 1);
     bracket_runs(list, pos + 1, job_host_fmt(job));

@@ -535,6 +535,20 @@ int hbhip_format_resample_create(hbhip_ctx *ctx, int width, int height, int dept
  * Arithmetic pinned to tests/format_scaled_model.py only (parity unpinned). */
 int hbhip_format_scaled_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
                                int src_log2_ch, int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out);
+/* The other direction: a target with MORE chroma samples than the stream, at equal or HIGHER depth - 4:2:0 -> 4:2:2 (a
+ * vertical pass), 4:2:2 -> 4:4:4 (a horizontal pass), 4:2:0 -> 4:4:4 (both); 8 -> 8, 10 -> 10, 12 -> 12, 8 -> 10, 8 -> 12,
+ * 10 -> 12 bits.  What an encoder that only takes 4:2:2 / 4:4:4 input gets behind a 4:2:0 title (work.c:1525-1552: the
+ * third match_pix_fmt call takes the first entry of the encoder's list).  libswscale's general scaler again: Cb and Cr
+ * through the bicubic tables of the 1:2 ratio (four taps: target column 2i on source column i, target rows 2j and 2j + 1 a
+ * quarter above and below source row j), 15-bit intermediates, the output stage of the target's depth with its flat round
+ * term (the depth does not fall: no dither).  Luma runs through the identity filters: a copy at equal depth, v << (dst_depth -
+ * src_depth) above it in BOTH ranges - the scaler replicates no top bits, unlike hbhip_format_create's full-range 8 -> 10.
+ * The target's chroma planes are -((-width) >> dst_log2_cw) by -((-height) >> dst_log2_ch).  `chroma_location`: every
+ * value is taken as left-sited.  HBHIP_ERR_UNSUPPORTED: a depth outside 8 / 10 / 12, a lower target depth, fewer chroma
+ * samples in either direction, equal subsampling, a chroma plane under 7 samples in a direction that is up-sampled
+ * (libswscale shortens its filter there).  Arithmetic pinned to tests/format_upsample_model.py only (parity unpinned). */
+int hbhip_format_upsample_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
+                                 int src_log2_ch, int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out);
 /* The zscale [-> format=gbrpf32le -> tonemap] -> zscale -> format graph colorspace_init builds
  * (colorspace.c:126-193): matrix / range / transfer / primaries conversion, with tone mapping
  * when the source transfer is SMPTE 2084 or ARIB STD-B67 and the transfer changes.  Colour ids
