@@ -18,10 +18,14 @@ HIP_HDR := $(wildcard $(PKG)/csrc/*.h) $(wildcard include/*.h)
 FLT_SRC := $(wildcard $(PKG)/libhb/*_hip.c) $(PKG)/libhb/hbhip_registry.c $(PKG)/libhb/hip_common.c $(PKG)/libhb/vfr_standin.c
 
 all: product oracle
-product: $(PKG)/libhbrt.so $(PKG)/libhbhip.so $(PKG)/libhbhip_filters.so tools/vote_avg_check tools/dirmap_vote_check tools/lapsharp_rowdot_check
+product: $(PKG)/libhbrt.so $(PKG)/libhbhip.so $(PKG)/libhbhip_filters.so tools/vote_avg_check tools/dirmap_vote_check tools/lapsharp_rowdot_check tools/format_nominal_check
 
 # lapsharp's byte dot products run on the HOST (tests/test_lapsharp_rowdot_cpu.py)
 tools/lapsharp_rowdot_check: tools/lapsharp_rowdot_check.hip $(PKG)/csrc/lapsharp_rowdot.h
+	$(HIPCC) --offload-arch=$(ARCH) -O2 -ffp-contract=off -fno-fast-math -I$(PKG)/csrc $< -o $@
+
+# the format scaler's table builder run on the HOST (tests/test_format_nominal_cpu.py)
+tools/format_nominal_check: tools/format_nominal_check.hip $(PKG)/csrc/sws_filter.h
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -ffp-contract=off -fno-fast-math -I$(PKG)/csrc $< -o $@
 
 # GPU-side exhaustive check of a device function shared with the kernels (tests/test_eedi2_gpu.py runs it)

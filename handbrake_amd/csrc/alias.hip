@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "dot2.h"
 #include "sws_filter.h"
 
 namespace {
@@ -457,13 +458,8 @@ public:
 // horizontal pass first, then back to 8 bits with round half up of v / 256 (oracle/alias_oracle.c:
 // orc_cropscale_plane_fx has the derivation and the caveats - parity unpinned).  Integer throughout, so the result
 // does not depend on evaluation order and the kernels below are free to use packed dot products: two taps per
-// v_dot2_i32_i16, the 16-bit value between the passes kept biased by -32768 as zimg keeps it (a filter row sums to
+// v_dot2_i32_i16 (dot2.h), the 16-bit value between the passes kept biased by -32768 as zimg keeps it (a filter row sums to
 // exactly 1 << 14, so the bias comes out as a constant).
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ int dot2(uint32_t a, uint32_t b, int acc)
-{
-    return __builtin_amdgcn_sdot2(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b), acc, false);
-}
 __device__ __forceinline__ int reflect_idx(int j, int n)          // taps outside the plane fold back in (edge sample repeated)
 {
     if (j < 0) j = -j - 1;
@@ -1320,892 +1316,7 @@ public:
     hbhip_pad_params par;
 };
 
-// ------------------------------------------------------------------ format (depth conversion)
-// `format=pix_fmts=...` (libhb/format.c:13-111): libavfilter inserts a same-size `scale`, i.e. libswscale's
-// unscaled planar copy (swscale_unscaled.c:planarCopyWrapper; parity unpinned, restated in
-// oracle/alias_oracle.c:orc_format_plane).  Up: shift (limited range, chroma) or top-bit replication
-// (full-range luma); down: ordered dither then the overflow clamp tmp - (tmp >> depth).  One launch for the
-// three planes, four samples per thread, HBM-bound (read in + write out).
-constexpr int FMT_FRAMES = 16;
-struct FormatArgs
-{
-    const uint8_t *src[FMT_FRAMES][3];
-    uint8_t       *dst[FMT_FRAMES][3];
-    int spitch[3], dpitch[3], w[3], h[3];
-    int sdepth, ddepth, full_range;
-};
-
-// four samples per thread, moved as one dword (bytes) or two (16-bit samples) where the row has them; grid.z =
-// 3 * frame + plane: the frames of a batch in one launch
-template <typename SRC, typename DST>
-__global__ __launch_bounds__(256) void format_kernel(FormatArgs a)
-{
-    const int c = blockIdx.z % 3, f = blockIdx.z / 3;
-    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4, y = blockIdx.y * blockDim.y + threadIdx.y;
-    if (x0 >= a.w[c] || y >= a.h[c]) return;
-    const SRC *s = reinterpret_cast<const SRC *>(a.src[f][c] + (size_t)y * a.spitch[c]);
-    DST *d = reinterpret_cast<DST *>(a.dst[f][c] + (size_t)y * a.dpitch[c]);
-    const bool shiftonly = c != 0 || !a.full_range;
-    const int up = a.ddepth - a.sdepth;
-    const bool whole = x0 + 3 < a.w[c];
-    unsigned v4[4] = { 0, 0, 0, 0 };
-    if (whole)
-    {
-        if (sizeof(SRC) == 1)
-        {
-            const uint32_t w = *reinterpret_cast<const uint32_t *>(s + x0);
-#pragma unroll
-            for (int i = 0; i < 4; i++) v4[i] = (w >> (8 * i)) & 0xffu;
-        }
-        else
-        {
-            const uint2 w = *reinterpret_cast<const uint2 *>(s + x0);
-            v4[0] = w.x & 0xffffu; v4[1] = w.x >> 16; v4[2] = w.y & 0xffffu; v4[3] = w.y >> 16;
-        }
-    }
-    else
-        for (int i = 0; x0 + i < a.w[c]; i++) v4[i] = s[x0 + i];
-    unsigned o4[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-    {
-        const int x = x0 + i;
-        const unsigned v = v4[i];
-        unsigned o;
-        if (up == 0) o = v;
-        else if (up > 0) o = shiftonly ? v << up : (v << up) | (v >> (2 * a.sdepth - a.ddepth));
-        else
-        {
-            const int shift = -up;
-            // dithers[shift - 1][y & 7][x & 7] of swscale_unscaled.c for shift 2 / 4 (2x2 / 4x4 ordered matrices)
-            // one nibble per cell: {1,2;3,0} and {4,8,7,11; 12,0,15,3; 6,10,5,9; 14,2,13,1}
-            constexpr uint64_t D4 = 0xB784ull | (0x3F0Cull << 16) | (0x95A6ull << 32) | (0x1D2Eull << 48);
-            const unsigned dm = shift == 2 ? ((0x0321u >> (4 * ((y & 1) * 2 + (x & 1)))) & 15u)
-                                           : (unsigned)((D4 >> (16 * (y & 3) + 4 * (x & 3))) & 15u);
-            if (shiftonly)
-            {
-                const unsigned tmp = (v + dm) >> shift;
-                o = tmp - (tmp >> a.ddepth);
-            }
-            else
-                o = (v - (v >> a.ddepth) + dm) >> shift;                // full-range luma: DITHER_COPY's other arm
-        }
-        o4[i] = o;
-    }
-    if (whole)
-    {
-        if (sizeof(DST) == 1) *reinterpret_cast<uint32_t *>(d + x0) = o4[0] | (o4[1] << 8) | (o4[2] << 16) | (o4[3] << 24);
-        else                  *reinterpret_cast<uint2 *>(d + x0) = make_uint2(o4[0] | (o4[1] << 16), o4[2] | (o4[3] << 16));
-    }
-    else
-        for (int i = 0; x0 + i < a.w[c]; i++) d[x0 + i] = (DST)o4[i];
-}
-
-class FormatFilter : public BurstFilter
-{
-public:
-    FormatFilter(hbhip_ctx *c, int full) : BurstFilter(c), full_range(full) {}
-    int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
-    {
-        return hbhip_for_each_burst<FMT_FRAMES, FormatArgs>(ctx, ins, outs, n, [&](FormatArgs &a, int nf, int, uintptr_t bits) {
-            if ((bits & 7) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
-            for (int c = 0; c < 3; c++) { a.w[c] = in_geo.pw[c]; a.h[c] = in_geo.ph[c]; }
-            a.sdepth = in_geo.depth; a.ddepth = out_geo.depth; a.full_range = full_range;
-            const dim3 grid(hbhip_grid_x((a.w[0] + 255) / 256), (a.h[0] + 3) / 4, 3 * nf);
-            if (in_geo.bps == 1 && out_geo.bps == 1)      HBHIP_LAUNCH(ctx, "format", (format_kernel<uint8_t, uint8_t>), grid, dim3(64, 4), 0, a);
-            else if (in_geo.bps == 1)                     HBHIP_LAUNCH(ctx, "format", (format_kernel<uint8_t, uint16_t>), grid, dim3(64, 4), 0, a);
-            else if (out_geo.bps == 1)                    HBHIP_LAUNCH(ctx, "format", (format_kernel<uint16_t, uint8_t>), grid, dim3(64, 4), 0, a);
-            else                                          HBHIP_LAUNCH(ctx, "format", (format_kernel<uint16_t, uint16_t>), grid, dim3(64, 4), 0, a);
-            return HBHIP_OK;
-        });
-    }
-    int full_range;
-};
-
-// ------------------------------------------------------------------ format (chroma down-sampling at equal depth)
-// `format=pix_fmts=...` when the target has fewer chroma samples than the stream (4:2:2 -> 4:2:0, 4:4:4 -> 4:2:2 / 4:2:0):
-// libavfilter's auto-inserted `scale` is then libswscale's general scaler at its default flags, bicubic.  Luma runs through
-// its identity filters and is a copy; Cb and Cr are filtered with the tables of sws_filter(bicubic) - 14-bit horizontal,
-// 12-bit vertical coefficients - and the intermediates of scale_sws_h_kernel / scale_sws_v_kernel (hScale8To15 /
-// hScale16To15, yuv2planeX_8 / _10 / _12).  PARITY UNPINNED like the rest of the family: libswscale is outside the
-// reference tree; the model is tests/format_resample_model.py.
-// Siting: vertically target row j lies midway between source rows 2j and 2j + 1 (srcPos = dstPos = 128); horizontally
-// target column i is co-sited with source column 2i (left-sited chroma: srcPos 128, dstPos 64), whatever the stream's
-// chroma_location says - the rule of the crop/scale drop-in's swscale branch.
-//
-// The kernel reads the tables in a NOMINAL form: output row / column j taps the FR_TAPS source rows / columns from
-// 2j + FR_BASE on, sws_filter's (position, coefficients) rows moved into that frame with zeros around them (a 2:1 bicubic
-// filter is 7 - 9 taps at 2j - 3 or, for an odd source size, one sample further left; create() checks that every row
-// fits).  That makes every window a compile-time offset that starts on an even sample, so both passes take their taps
-// two at a time (v_dot2_i32_i16): a thread owns four adjacent output columns (a dword of bytes, a qword of 16-bit
-// samples) and FR_ROWS (both passes: FR_ROWS_HV) output rows; the source rows under them are loaded ONCE, taken through
-// the horizontal pass (or the identity's shift) and kept in registers as 15-bit intermediates, a PAIR OF ROWS to a
-// dword; the vertical pass reads registers only.  No LDS.  The vertical coefficients of a row are the same for a whole wave (a wave is one
-// threadIdx.y) and come through scalar loads.
-//   4:2:2 -> 4:2:0   all FR_ROWS + FR_TAPS / 2 - 1 row pairs are loaded ahead of the arithmetic;
-//   4:4:4 -> 4:2:0   the window of FR_TAPS / 2 row pairs rolls down one pair an output row (the horizontal pass needs
-//                    the registers the whole window would take);
-//   4:4:4 -> 4:2:2   two rows a turn, the vertical identity applied to each half.
-constexpr int FR_TAPS = 10, FR_BASE = -4, FR_ROWS = 8, FR_ROWS_HV = 16, FR_LROWS = 4;
-struct FormatResampleArgs
-{
-    const uint8_t *src[FMT_FRAMES][3];
-    uint8_t       *dst[FMT_FRAMES][3];
-    int spitch[3], dpitch[3];
-    int w, h, scw, sch, dcw, dch, depth;      // luma size; chroma size of the source and of the target
-    int ly, cy;                               // grid.y: ly workgroup rows of luma, then cy of Cb, then cy of Cr
-    const short *hq, *vq;                     // [column][FR_TAPS] (columns padded to 4), [row][FR_TAPS]
-};
-
-// The scaled form's extra arguments.  dither: libswscale's ff_dither_8x8_128, row r in dwords 2r (columns 0 .. 3, a byte
-// each) and 2r + 1 (columns 4 .. 7).
-struct FormatScaledArgs : FormatResampleArgs
-{
-    int ddepth;                               // the target's depth (`depth` is the source's)
-    uint32_t dither[16];
-};
-__device__ __forceinline__ int fr_ddepth(const FormatResampleArgs &a) { return a.depth; }
-__device__ __forceinline__ int fr_ddepth(const FormatScaledArgs &a) { return a.ddepth; }
-
-// the dither bytes of output row y, columns x0 .. x0 + 3 (x0 a multiple of 4): Y and Cb read the table at column x, Cr at
-// x + 3 (yuv2planeX_8_c's offset argument, yuv2nv12cX_c's two halves) - bytes 3 .. 6, or 7, 0, 1, 2, of the row's eight
-__device__ __forceinline__ uint32_t fr_dither4(const FormatScaledArgs &a, int y, int x0, bool cr)
-{
-    const uint32_t lo = a.dither[2 * (y & 7)], hi = a.dither[2 * (y & 7) + 1];
-    const uint32_t p = (x0 & 4) ? hi : lo, q = (x0 & 4) ? lo : hi;
-    return cr ? __builtin_amdgcn_alignbyte(q, p, 3u) : p;
-}
-
-// samples x0 .. x0 + 3 of a row (x0 a multiple of 4, possibly negative) as two dwords of 16-bit pairs; those outside
-// [0, w) read as 0 and are never loaded
-template <typename PIX>
-__device__ __forceinline__ void fr_load_pairs(const PIX *row, int x0, int w, uint32_t *p)
-{
-    if (x0 >= 0 && x0 + 3 < w)
-    {
-        if (sizeof(PIX) == 1)
-        {
-            const uint32_t d = *reinterpret_cast<const uint32_t *>(row + x0);
-            p[0] = __builtin_amdgcn_perm(0u, d, 0x0c010c00u);
-            p[1] = __builtin_amdgcn_perm(0u, d, 0x0c030c02u);
-        }
-        else
-        {
-            const uint2 d = *reinterpret_cast<const uint2 *>(row + x0);
-            p[0] = d.x; p[1] = d.y;
-        }
-    }
-    else
-    {
-        uint32_t v[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) v[i] = (x0 + i >= 0 && x0 + i < w) ? (uint32_t)row[x0 + i] : 0u;
-        p[0] = v[0] | (v[1] << 16); p[1] = v[2] | (v[3] << 16);
-    }
-}
-
-template <typename PIX>
-__device__ __forceinline__ void fr_store4(PIX *row, int x0, int w, const int *o)
-{
-    if (x0 + 3 < w)
-    {
-        if (sizeof(PIX) == 1) *reinterpret_cast<uint32_t *>(row + x0) = (uint32_t)o[0] | ((uint32_t)o[1] << 8) | ((uint32_t)o[2] << 16) | ((uint32_t)o[3] << 24);
-        else                  *reinterpret_cast<uint2 *>(row + x0) = make_uint2((uint32_t)o[0] | ((uint32_t)o[1] << 16), (uint32_t)o[2] | ((uint32_t)o[3] << 16));
-    }
-    else
-        for (int i = 0; x0 + i < w; i++) row[x0 + i] = (PIX)o[i];
-}
-
-// The scaler on identity filters, rows y0 .. y0 + FR_LROWS - 1 of plane c (w x h), columns x0 .. x0 + 3 < w + 3:
-// hScale16To15's one tap, v << (15 - depth), then yuv2plane1_8 - (t + dither) >> 7 - or yuv2plane1_10, (t + 16) >> 5,
-// clipped at the top (nothing is negative here).  The loads go ahead of the arithmetic; a qword in, a dword or a qword out.
-template <typename DPIX>
-__device__ __forceinline__ void fr_identity_rows(const FormatScaledArgs &a, int f, int c, int x0, int y0, int w, int h)
-{
-    const uint8_t *s = a.src[f][c];
-    uint8_t *d = a.dst[f][c];
-    const int up = 15 - a.depth, vmax = (1 << a.ddepth) - 1;
-    uint32_t p[FR_LROWS][2];
-#pragma unroll
-    for (int r = 0; r < FR_LROWS; r++)
-        if (y0 + r < h) fr_load_pairs(reinterpret_cast<const uint16_t *>(s + (size_t)(y0 + r) * a.spitch[c]), x0, w, p[r]);
-#pragma unroll
-    for (int r = 0; r < FR_LROWS; r++)
-    {
-        if (y0 + r >= h) break;
-        const uint32_t dm = sizeof(DPIX) == 1 ? fr_dither4(a, y0 + r, x0, c == 2) : 0u;
-        int o[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-        {
-            const int t = (int)((p[r][i >> 1] >> (16 * (i & 1))) & 0xffffu) << up;
-            o[i] = sizeof(DPIX) == 1 ? min((t + (int)((dm >> (8 * i)) & 0xffu)) >> 7, vmax) : min((t + 16) >> 5, vmax);
-        }
-        fr_store4(reinterpret_cast<DPIX *>(d + (size_t)(y0 + r) * a.dpitch[c]), x0, w, o);
-    }
-}
-
-// HP / VP: the chroma planes take a horizontal / a vertical pass.  grid.z = frame: the frames of a burst in one launch;
-// grid.y = the workgroup rows of luma (a thread moves four samples of FR_LROWS rows as dwords / qwords, the accesses of
-// format_kernel), then those of Cb, then those of Cr (a chroma thread row is FR_ROWS / FR_ROWS_HV output rows); grid.x
-// is sized for luma and the workgroups beyond a chroma plane return at once.
-//
-// SC: the scaled form, a LOWER target depth - 10 -> 8, 12 -> 8, 12 -> 10 bits (DPIX: the target's sample type; Args:
-// FormatScaledArgs).  The chroma passes are the same; what changes is the intermediate's shift (the source depth), the output
-// stage (the target depth: to 8 bits its round term is the 8 x 8 ordered dither, a byte a column) and the store type.
-// Luma is no copy then but the identity filter and the output stage, and so are Cb and Cr where neither pass is taken
-// (4:2:0 -> 4:2:0, the planar step in front of the NV12 / P010LE repack).  The model is tests/format_scaled_model.py.
-// The equal-depth instantiations take the defaults and compile to the instructions they had before the form existed.
-template <typename PIX, bool HP, bool VP, typename DPIX = PIX, bool SC = false, class Args = FormatResampleArgs>
-__global__ __launch_bounds__(256, 4) void format_resample_kernel(Args a)
-{
-    static_assert(SC || ((HP || VP) && std::is_same<PIX, DPIX>::value), "equal depth: one pass at least, one sample type");
-    const int f = blockIdx.z;
-    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if constexpr (SC)
-    {
-        // the planes that take no pass: a thread row is FR_LROWS rows (one value a wave, as the dither's row has to be)
-        const bool luma = (int)blockIdx.y < a.ly;
-        if (luma || (!HP && !VP))
-        {
-            const int cby = (int)blockIdx.y - a.ly, c = luma ? 0 : 1 + cby / a.cy;
-            const int wy = luma ? (int)blockIdx.y : cby % a.cy;
-            const int y0 = __builtin_amdgcn_readfirstlane(wy * blockDim.y + threadIdx.y) * FR_LROWS;
-            const int w = luma ? a.w : a.dcw, h = luma ? a.h : a.dch;
-            if (x0 >= w || y0 >= h) return;
-            fr_identity_rows<DPIX>(a, f, c, x0, y0, w, h);
-            return;
-        }
-    }
-    else if ((int)blockIdx.y < a.ly)
-    {
-        const int y0 = (blockIdx.y * blockDim.y + threadIdx.y) * FR_LROWS;
-        if (x0 >= a.w) return;
-        const uint8_t *s = a.src[f][0];
-        uint8_t *d = a.dst[f][0];
-        if (x0 + 3 < a.w)
-        {
-            typedef typename std::conditional<sizeof(PIX) == 1, uint32_t, uint2>::type V;
-            V v[FR_LROWS];
-#pragma unroll
-            for (int r = 0; r < FR_LROWS; r++)
-                if (y0 + r < a.h) v[r] = *reinterpret_cast<const V *>(s + (size_t)(y0 + r) * a.spitch[0] + (size_t)x0 * sizeof(PIX));
-#pragma unroll
-            for (int r = 0; r < FR_LROWS; r++)
-                if (y0 + r < a.h) *reinterpret_cast<V *>(d + (size_t)(y0 + r) * a.dpitch[0] + (size_t)x0 * sizeof(PIX)) = v[r];
-        }
-        else
-            for (int r = 0; r < FR_LROWS && y0 + r < a.h; r++)
-                for (int i = 0; x0 + i < a.w; i++)
-                    reinterpret_cast<PIX *>(d + (size_t)(y0 + r) * a.dpitch[0])[x0 + i] = reinterpret_cast<const PIX *>(s + (size_t)(y0 + r) * a.spitch[0])[x0 + i];
-        return;
-    }
-    const int cby = (int)blockIdx.y - a.ly, c = 1 + cby / a.cy;
-    constexpr int ROWS = HP && VP ? FR_ROWS_HV : FR_ROWS;                    // output rows a thread
-    const int j0 = __builtin_amdgcn_readfirstlane((cby % a.cy) * blockDim.y + threadIdx.y) * ROWS;      // the first one: one value a wave
-    if (x0 >= a.dcw || j0 >= a.dch) return;
-    const int sh = sizeof(PIX) == 1 ? 7 : a.depth - 1;                       // hScale8To15_c / hScale16To15_c
-    // yuv2planeX_8_c: the flat dither of 64 (round = 64 << 12, shift 19); yuv2planeX_10 / _12: half of the shift 27 - depth
-    // (the scaled form: yuv2planeX_8_c's round term is the dither, seed() below; to 10 bits it is the flat half as well)
-    const int ddepth = fr_ddepth(a);
-    const int shift = sizeof(DPIX) == 1 ? 19 : 27 - ddepth, round = sizeof(DPIX) == 1 ? 64 << 12 : 1 << (shift - 1);
-    const int vmax = (1 << ddepth) - 1;
-    const uint8_t *sp = a.src[f][c];
-    const int spitch = a.spitch[c];
-    uint32_t hc[HP ? 2 * FR_TAPS : 1];                                       // the four columns' coefficients, in pairs
-    if (HP)
-    {
-        const uint4 *q = reinterpret_cast<const uint4 *>(a.hq + (size_t)x0 * FR_TAPS);      // 80 bytes a thread, 16-byte aligned
-#pragma unroll
-        for (int k = 0; k < FR_TAPS / 2; k++)
-        {
-            const uint4 t = q[k];
-            hc[4 * k] = t.x; hc[4 * k + 1] = t.y; hc[4 * k + 2] = t.z; hc[4 * k + 3] = t.w;
-        }
-    }
-    // source rows sr, sr + 1 (clamped into the plane: the rows outside of it have coefficient 0) -> the four columns'
-    // intermediates, row sr in the low and row sr + 1 in the high half of e[column]
-    auto hpair = [&](int sr, uint32_t *e) {
-        const PIX *ra = reinterpret_cast<const PIX *>(sp + (size_t)min(max(sr, 0), a.sch - 1) * spitch);
-        const PIX *rb = reinterpret_cast<const PIX *>(sp + (size_t)min(max(sr + 1, 0), a.sch - 1) * spitch);
-        if (HP)
-        {
-            uint32_t pa[8], pb[8];                                           // the sixteen samples under the four columns, in pairs
-#pragma unroll
-            for (int g = 0; g < 4; g++)
-            {
-                fr_load_pairs(ra, 2 * x0 + FR_BASE + 4 * g, a.scw, pa + 2 * g);
-                fr_load_pairs(rb, 2 * x0 + FR_BASE + 4 * g, a.scw, pb + 2 * g);
-            }
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-            {
-                int va = 0, vb = 0;
-#pragma unroll
-                for (int u = 0; u < FR_TAPS / 2; u++)
-                {
-                    va = dot2(pa[i + u], hc[i * (FR_TAPS / 2) + u], va);
-                    vb = dot2(pb[i + u], hc[i * (FR_TAPS / 2) + u], vb);
-                }
-                va = min(va >> sh, (1 << 15) - 1);
-                vb = min(vb >> sh, (1 << 15) - 1);
-                e[i] = ((uint32_t)va & 0xffffu) | ((uint32_t)vb << 16);
-            }
-        }
-        else
-        {
-            // the identity filter, one tap of 1 << 14: (s << 14) >> sh, below 1 << 15 for every sample - both halves in one shift
-            uint32_t pa[2], pb[2];
-            fr_load_pairs(ra, x0, a.scw, pa);
-            fr_load_pairs(rb, x0, a.scw, pb);
-#pragma unroll
-            for (int g = 0; g < 2; g++)
-            {
-                e[2 * g]     = __builtin_amdgcn_perm(pb[g], pa[g], 0x05040100u) << (14 - sh);
-                e[2 * g + 1] = __builtin_amdgcn_perm(pb[g], pa[g], 0x07060302u) << (14 - sh);
-            }
-        }
-    };
-    auto put = [&](int j, const int *acc) {
-        int o[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) o[i] = min(max(acc[i] >> shift, 0), vmax);
-        fr_store4(reinterpret_cast<DPIX *>(a.dst[f][c] + (size_t)j * a.dpitch[c]), x0, a.dcw, o);
-    };
-    // the round term of output row j's four columns
-    auto seed = [&](int j, int *acc) {
-        if constexpr (SC && sizeof(DPIX) == 1)
-        {
-            const uint32_t dm = fr_dither4(a, j, x0, c == 2);
-#pragma unroll
-            for (int i = 0; i < 4; i++) acc[i] = (int)((dm >> (8 * i)) & 0xffu) << 12;
-        }
-        else
-        {
-#pragma unroll
-            for (int i = 0; i < 4; i++) acc[i] = round;
-        }
-    };
-    // output row j from the FR_TAPS / 2 row pairs at win
-    auto vrow = [&](int j, const uint32_t (*win)[4]) {
-        const uint32_t *vq = reinterpret_cast<const uint32_t *>(a.vq + (size_t)j * FR_TAPS);
-        int acc[4] = { round, round, round, round };
-        if constexpr (SC) seed(j, acc);
-#pragma unroll
-        for (int u = 0; u < FR_TAPS / 2; u++)
-        {
-            const uint32_t q = vq[u];
-#pragma unroll
-            for (int i = 0; i < 4; i++) acc[i] = dot2(win[u][i], q, acc[i]);
-        }
-        put(j, acc);
-    };
-    if (!HP)
-    {
-        constexpr int NP = FR_ROWS + FR_TAPS / 2 - 1;
-        uint32_t hp[NP][4];
-#pragma unroll
-        for (int k = 0; k < NP; k++) hpair(2 * (j0 + k) + FR_BASE, hp[k]);
-#pragma unroll
-        for (int r = 0; r < FR_ROWS; r++)
-            if (j0 + r < a.dch) vrow(j0 + r, hp + r);
-    }
-    else if (!VP)
-    {
-#pragma unroll
-        for (int r = 0; r < ROWS; r += 2)
-        {
-            if (j0 + r >= a.dch) break;
-            uint32_t e[4];
-            hpair(j0 + r, e);
-            int lo[4], hi[4];                                                // the identity filter: one tap of 1 << 12
-#pragma unroll
-            for (int i = 0; i < 4; i++) { lo[i] = round + ((int)(short)(e[i] & 0xffffu) << 12); hi[i] = round + (((int)e[i] >> 16) << 12); }
-            if constexpr (SC)
-            {
-                int da[4], db[4];
-                seed(j0 + r, da);
-                seed(j0 + r + 1, db);
-#pragma unroll
-                for (int i = 0; i < 4; i++) { lo[i] += da[i] - round; hi[i] += db[i] - round; }
-            }
-            put(j0 + r, lo);
-            if (j0 + r + 1 < a.dch) put(j0 + r + 1, hi);
-        }
-    }
-    else
-    {
-        uint32_t win[FR_TAPS / 2][4] = {};
-#pragma unroll 2
-        for (int r = 1 - FR_TAPS / 2; r < ROWS && j0 + r < a.dch; r++)        // (the first FR_TAPS / 2 - 1 turns only fill the window)
-        {
-#pragma unroll
-            for (int u = 0; u < FR_TAPS / 2 - 1; u++)
-#pragma unroll
-                for (int i = 0; i < 4; i++) win[u][i] = win[u + 1][i];
-            hpair(2 * (j0 + r) + FR_BASE + FR_TAPS - 2, win[FR_TAPS / 2 - 1]);
-            if (r >= 0) vrow(j0 + r, win);
-        }
-    }
-}
-
-class FormatResampleFilter : public BurstFilter
-{
-public:
-    using BurstFilter::BurstFilter;
-    ~FormatResampleFilter() override
-    {
-        if (d_hq) (void)hipFree(d_hq);
-        if (d_vq) (void)hipFree(d_vq);
-    }
-    // sws_filter's rows in the kernel's nominal frame; false: a row has a tap outside of it
-    static bool nominal(int src, int dst, int one, int src_pos, int dst_pos, int pad, std::vector<short> &out)
-    {
-        std::vector<int> pos;
-        std::vector<short> coef;
-        const int taps = sws_filter(src, dst, one, src_pos, dst_pos, pos, coef, true);
-        out.assign((size_t)((dst + pad - 1) / pad * pad) * FR_TAPS, 0);
-        for (int i = 0; i < dst; i++)
-            for (int t = 0; t < taps; t++)
-            {
-                const short q = coef[(size_t)i * taps + t];
-                if (q == 0) continue;
-                const int k = pos[i] + t - (2 * i + FR_BASE);
-                if (k < 0 || k >= FR_TAPS || pos[i] + t >= src) return false;
-                out[(size_t)i * FR_TAPS + k] = q;
-            }
-        return true;
-    }
-    int setup()
-    {
-        hpass = out_geo.log2_cw > in_geo.log2_cw;
-        vpass = out_geo.log2_ch > in_geo.log2_ch;
-        auto up = [&](short *&dptr, const std::vector<short> &v) -> int {
-            HBHIP_CHECK(ctx, hipMalloc((void **)&dptr, sizeof(short) * v.size()));
-            HBHIP_CHECK(ctx, hipMemcpy(dptr, v.data(), sizeof(short) * v.size(), hipMemcpyHostToDevice));
-            return HBHIP_OK;
-        };
-        std::vector<short> q;
-        // left-sited chroma: source position 128 (4:4:4 has no siting), target position 128 >> 1; rows: centred, 128 both
-        if (hpass)
-        {
-            if (!nominal(in_geo.pw[1], out_geo.pw[1], 1 << 14, 128, 64, 4, q)) return HBHIP_ERR_UNSUPPORTED;
-            const int rc = up(d_hq, q);
-            if (rc != HBHIP_OK) return rc;
-        }
-        if (vpass)
-        {
-            if (!nominal(in_geo.ph[1], out_geo.ph[1], 1 << 12, 128, 128, 1, q)) return HBHIP_ERR_UNSUPPORTED;
-            const int rc = up(d_vq, q);
-            if (rc != HBHIP_OK) return rc;
-        }
-        return HBHIP_OK;
-    }
-    // the scaled form: a lower target depth, with or without a pass
-    int process_scaled(DevPicture *const *ins, DevPicture *const *outs, int n)
-    {
-        // libswscale's ff_dither_8x8_128
-        static const uint8_t dither[8][8] = {
-            {  36,  68,  60,  92,  34,  66,  58,  90 }, { 100,   4, 124,  28,  98,   2, 122,  26 },
-            {  52,  84,  44,  76,  50,  82,  42,  74 }, { 116,  20, 108,  12, 114,  18, 106,  10 },
-            {  32,  64,  56,  88,  38,  70,  62,  94 }, {  96,   0, 120,  24, 102,   6, 126,  30 },
-            {  48,  80,  40,  72,  54,  86,  46,  78 }, { 112,  16, 104,   8, 118,  22, 110,  14 } };
-        return hbhip_for_each_burst<FMT_FRAMES, FormatScaledArgs>(ctx, ins, outs, n, [&](FormatScaledArgs &a, int nf, int, uintptr_t bits) {
-            if ((bits & 7) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
-            a.w = in_geo.width; a.h = in_geo.height; a.depth = in_geo.depth; a.ddepth = out_geo.depth;
-            a.scw = in_geo.pw[1]; a.sch = in_geo.ph[1]; a.dcw = out_geo.pw[1]; a.dch = out_geo.ph[1];
-            a.hq = d_hq; a.vq = d_vq;
-            for (int r = 0; r < 8; r++)
-                for (int k = 0; k < 8; k++) a.dither[2 * r + k / 4] |= (uint32_t)dither[r][k] << (8 * (k & 3));
-            a.ly = (a.h + 4 * FR_LROWS - 1) / (4 * FR_LROWS);
-            const int rows = 4 * (hpass && vpass ? FR_ROWS_HV : hpass || vpass ? FR_ROWS : FR_LROWS);     // output rows a workgroup
-            a.cy = (a.dch + rows - 1) / rows;
-            const dim3 grid(hbhip_grid_x((a.w + 255) / 256), a.ly + 2 * a.cy, nf);
-#define FS_GO(DPIX, HP, VP) HBHIP_LAUNCH(ctx, "format_scaled", (format_resample_kernel<uint16_t, HP, VP, DPIX, true, FormatScaledArgs>), grid, dim3(64, 4), 0, a)
-#define FS_PICK(DPIX) do { if (hpass && vpass) FS_GO(DPIX, true, true); else if (hpass) FS_GO(DPIX, true, false); \
-                           else if (vpass) FS_GO(DPIX, false, true); else FS_GO(DPIX, false, false); } while (0)
-            if (out_geo.bps == 1) FS_PICK(uint8_t);
-            else                  FS_PICK(uint16_t);
-#undef FS_PICK
-#undef FS_GO
-            return HBHIP_OK;
-        });
-    }
-    int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
-    {
-        if (out_geo.depth != in_geo.depth) return process_scaled(ins, outs, n);
-        return hbhip_for_each_burst<FMT_FRAMES, FormatResampleArgs>(ctx, ins, outs, n, [&](FormatResampleArgs &a, int nf, int, uintptr_t bits) {
-            if ((bits & 7) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
-            a.w = in_geo.width; a.h = in_geo.height; a.depth = in_geo.depth;
-            a.scw = in_geo.pw[1]; a.sch = in_geo.ph[1]; a.dcw = out_geo.pw[1]; a.dch = out_geo.ph[1];
-            a.hq = d_hq; a.vq = d_vq;
-            a.ly = (a.h + 4 * FR_LROWS - 1) / (4 * FR_LROWS);
-            const int rows = 4 * (hpass && vpass ? FR_ROWS_HV : FR_ROWS);     // output rows a workgroup
-            a.cy = (a.dch + rows - 1) / rows;
-            const dim3 grid(hbhip_grid_x((a.w + 255) / 256), a.ly + 2 * a.cy, nf);
-#define FR_GO(PIX, HP, VP) HBHIP_LAUNCH(ctx, "format_resample", (format_resample_kernel<PIX, HP, VP>), grid, dim3(64, 4), 0, a)
-#define FR_PICK(PIX) do { if (hpass && vpass) FR_GO(PIX, true, true); else if (hpass) FR_GO(PIX, true, false); else FR_GO(PIX, false, true); } while (0)
-            if (in_geo.bps == 1) FR_PICK(uint8_t);
-            else                 FR_PICK(uint16_t);
-#undef FR_PICK
-#undef FR_GO
-            return HBHIP_OK;
-        });
-    }
-    bool hpass = false, vpass = false;
-    short *d_hq = nullptr, *d_vq = nullptr;
-};
-
-// ------------------------------------------------------------------ format (chroma up-sampling at equal or higher depth)
-// `format=pix_fmts=...` when the target has MORE chroma samples than the stream (4:2:0 -> 4:2:2, 4:2:2 -> 4:4:4,
-// 4:2:0 -> 4:4:4; 8 -> 8, 10 -> 10, 12 -> 12, 8 -> 10, 8 -> 12, 10 -> 12 bits): what an encoder that only takes 4:2:2 or
-// 4:4:4 input gets behind a 4:2:0 title (work.c:1525-1552, the third match_pix_fmt call).  libswscale's general scaler as
-// above, on the tables of the 1:2 ratio - sws_filter(bicubic)'s x_inc <= 1 << 16 arm, four taps - with hScale8To15 /
-// hScale16To15's intermediates by the SOURCE depth and yuv2planeX_8 / _10 / _12 by the TARGET's (the flat round term: the
-// depth does not fall, nothing is dithered).  Luma runs through the identity filters: v << (ddepth - sdepth), a copy at
-// equal depth (no top-bit replication in either range, unlike format_kernel's full-range luma).  PARITY UNPINNED; the
-// model is tests/format_upsample_model.py.
-// Siting: target row j a quarter above (j even) / below (j odd) source row j / 2 (srcPos = dstPos = 128); target column i
-// on source column i / 2 for an even i, midway to the next for an odd one (left-sited chroma: srcPos 64, dstPos 128).
-//
-// The tables in a NOMINAL form again: output row / column i taps the UP_TAPS = 6 source samples from 2 * (i >> 2) - 2 on.
-// The four taps of output i lie in (i >> 1) - 1 .. (i >> 1) + 2 horizontally and (i >> 1) - 2 .. (i >> 1) + 2 vertically
-// (an odd target size, 2 s - 1 for s, moves the positions by up to half a sample along the plane), both inside that
-// window for all four outputs of a group; create() checks every row and declines a table that does not fit.  The window
-// starts on an even sample and is the same for a thread's four adjacent output columns, so a thread loads three sample
-// pairs a source row and every output is three v_dot2_i32_i16; vertically the window is the same for four adjacent
-// output rows, a thread owns UP_ROWS = 8 of them over UP_ROWS / 2 + 4 source rows, which are loaded ONCE, taken through
-// the horizontal pass (or the identity's shift) and kept in registers as 15-bit intermediates, a pair of rows to a dword.
-// No LDS.  The vertical coefficients of a row are the same for a whole wave (one threadIdx.y) and come through scalar
-// loads.  Without a vertical pass a thread makes UP_ROWS_H rows, each from its own source row.
-constexpr int UP_TAPS = 6, UP_ROWS = 8, UP_ROWS_H = 4, UP_LROWS = 4;
-struct FormatUpsampleArgs
-{
-    const uint8_t *src[FMT_FRAMES][3];
-    uint8_t       *dst[FMT_FRAMES][3];
-    int spitch[3], dpitch[3];
-    int w, h, scw, sch, dcw, dch, sdepth, ddepth;     // luma size; chroma size of the source and of the target; depths
-    int ly, cy;                               // grid.y: ly workgroup rows of luma, then cy of Cb, then cy of Cr
-    const short *hq, *vq;                     // [column][UP_TAPS] (columns padded to 4), [row][UP_TAPS]
-};
-
-// samples s0 .. s0 + 5 of a row (s0 even, possibly negative) as three dwords of 16-bit pairs; those outside [0, w) read as
-// 0 and are never loaded (their coefficients are 0)
-template <typename PIX>
-__device__ __forceinline__ void up_load6(const PIX *row, int s0, int w, uint32_t *p)
-{
-    if (s0 >= 0 && s0 + 5 < w)
-    {
-#pragma unroll
-        for (int g = 0; g < 3; g++)
-        {
-            if (sizeof(PIX) == 1) p[g] = __builtin_amdgcn_perm(0u, (uint32_t)*reinterpret_cast<const uint16_t *>(row + s0 + 2 * g), 0x0c010c00u);
-            else                  p[g] = *reinterpret_cast<const uint32_t *>(row + s0 + 2 * g);
-        }
-    }
-    else
-    {
-        uint32_t v[6];
-#pragma unroll
-        for (int i = 0; i < 6; i++) v[i] = (s0 + i >= 0 && s0 + i < w) ? (uint32_t)row[s0 + i] : 0u;
-#pragma unroll
-        for (int g = 0; g < 3; g++) p[g] = v[2 * g] | (v[2 * g + 1] << 16);
-    }
-}
-
-// HP / VP: the chroma planes take a horizontal / a vertical pass.  The grid is format_resample_kernel's: grid.z = frame,
-// grid.y = the workgroup rows of luma (four samples of UP_LROWS rows a thread), then those of Cb, then those of Cr (a
-// chroma thread row is UP_ROWS / UP_ROWS_H output rows); grid.x is sized for luma.
-template <typename PIX, typename DPIX, bool HP, bool VP>
-__global__ __launch_bounds__(256, 4) void format_upsample_kernel(FormatUpsampleArgs a)
-{
-    static_assert((HP || VP) && sizeof(DPIX) >= sizeof(PIX), "one pass at least; the depth does not fall");
-    const int f = blockIdx.z;
-    const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-    if ((int)blockIdx.y < a.ly)
-    {
-        // the identity filters and the output stage: (v << (15 - sdepth) << 12 + round) >> shift = v << (ddepth - sdepth)
-        const int y0 = (blockIdx.y * blockDim.y + threadIdx.y) * UP_LROWS;
-        if (x0 >= a.w) return;
-        const int up = a.ddepth - a.sdepth;
-        uint32_t p[UP_LROWS][2];
-#pragma unroll
-        for (int r = 0; r < UP_LROWS; r++)
-            if (y0 + r < a.h) fr_load_pairs(reinterpret_cast<const PIX *>(a.src[f][0] + (size_t)(y0 + r) * a.spitch[0]), x0, a.w, p[r]);
-#pragma unroll
-        for (int r = 0; r < UP_LROWS; r++)
-        {
-            if (y0 + r >= a.h) break;
-            int o[4];
-#pragma unroll
-            for (int i = 0; i < 4; i++) o[i] = (int)((p[r][i >> 1] >> (16 * (i & 1))) & 0xffffu) << up;
-            fr_store4(reinterpret_cast<DPIX *>(a.dst[f][0] + (size_t)(y0 + r) * a.dpitch[0]), x0, a.w, o);
-        }
-        return;
-    }
-    const int cby = (int)blockIdx.y - a.ly, c = 1 + cby / a.cy;
-    constexpr int ROWS = VP ? UP_ROWS : UP_ROWS_H;                           // output rows a thread
-    const int j0 = __builtin_amdgcn_readfirstlane((cby % a.cy) * blockDim.y + threadIdx.y) * ROWS;      // the first one: one value a wave
-    if (x0 >= a.dcw || j0 >= a.dch) return;
-    const int sh = sizeof(PIX) == 1 ? 7 : a.sdepth - 1;                      // hScale8To15_c / hScale16To15_c
-    // yuv2planeX_8_c: the flat dither of 64 (round = 64 << 12, shift 19); yuv2planeX_10 / _12: half of the shift 27 - depth
-    const int shift = sizeof(DPIX) == 1 ? 19 : 27 - a.ddepth, round = sizeof(DPIX) == 1 ? 64 << 12 : 1 << (shift - 1);
-    const int vmax = (1 << a.ddepth) - 1;
-    const uint8_t *sp = a.src[f][c];
-    const int spitch = a.spitch[c];
-    uint32_t hc[HP ? 2 * UP_TAPS : 1];                                       // the four columns' coefficients, in pairs
-    if (HP)
-    {
-        const uint4 *q = reinterpret_cast<const uint4 *>(a.hq + (size_t)x0 * UP_TAPS);      // 48 bytes a thread, 16-byte aligned
-#pragma unroll
-        for (int k = 0; k < UP_TAPS / 2; k++)
-        {
-            const uint4 t = q[k];
-            hc[4 * k] = t.x; hc[4 * k + 1] = t.y; hc[4 * k + 2] = t.z; hc[4 * k + 3] = t.w;
-        }
-    }
-    // source row sr (clamped into the plane: the rows outside of it have coefficient 0) -> the four columns' intermediates
-    auto hrow = [&](int sr, int *e) {
-        const PIX *row = reinterpret_cast<const PIX *>(sp + (size_t)min(max(sr, 0), a.sch - 1) * spitch);
-        if (HP)
-        {
-            uint32_t p[UP_TAPS / 2];                                         // the six samples under the four columns, in pairs
-            up_load6(row, (x0 >> 1) - 2, a.scw, p);
-#pragma unroll
-            for (int i = 0; i < 4; i++)
-            {
-                int v = 0;
-#pragma unroll
-                for (int u = 0; u < UP_TAPS / 2; u++) v = dot2(p[u], hc[i * (UP_TAPS / 2) + u], v);
-                e[i] = min(v >> sh, (1 << 15) - 1);
-            }
-        }
-        else
-        {
-            // the identity filter, one tap of 1 << 14: (s << 14) >> sh
-            uint32_t p[2];
-            fr_load_pairs(row, x0, a.scw, p);
-#pragma unroll
-            for (int i = 0; i < 4; i++) e[i] = (int)((p[i >> 1] >> (16 * (i & 1))) & 0xffffu) << (14 - sh);
-        }
-    };
-    auto put = [&](int j, const int *acc) {
-        int o[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) o[i] = min(max(acc[i] >> shift, 0), vmax);
-        fr_store4(reinterpret_cast<DPIX *>(a.dst[f][c] + (size_t)j * a.dpitch[c]), x0, a.dcw, o);
-    };
-    if (!VP)
-    {
-        int e[ROWS][4];
-#pragma unroll
-        for (int r = 0; r < ROWS; r++) hrow(j0 + r, e[r]);
-#pragma unroll
-        for (int r = 0; r < ROWS; r++)
-        {
-            if (j0 + r >= a.dch) break;
-            int acc[4];                                                      // the identity filter: one tap of 1 << 12
-#pragma unroll
-            for (int i = 0; i < 4; i++) acc[i] = round + e[r][i] * (1 << 12);
-            put(j0 + r, acc);
-        }
-    }
-    else
-    {
-        // source rows (j0 >> 1) - 2 + 2k and the one below it, row pair k: output rows j0 + 4g .. j0 + 4g + 3 read pairs g .. g + 2
-        constexpr int NP = ROWS / 4 + UP_TAPS / 2 - 1;
-        uint32_t hp[NP][4];
-#pragma unroll
-        for (int k = 0; k < NP; k++)
-        {
-            int ea[4], eb[4];
-            hrow((j0 >> 1) - 2 + 2 * k, ea);
-            hrow((j0 >> 1) - 1 + 2 * k, eb);
-#pragma unroll
-            for (int i = 0; i < 4; i++) hp[k][i] = ((uint32_t)ea[i] & 0xffffu) | ((uint32_t)eb[i] << 16);
-        }
-#pragma unroll
-        for (int r = 0; r < ROWS; r++)
-        {
-            if (j0 + r >= a.dch) break;
-            const uint32_t *vq = reinterpret_cast<const uint32_t *>(a.vq + (size_t)(j0 + r) * UP_TAPS);
-            int acc[4] = { round, round, round, round };
-#pragma unroll
-            for (int u = 0; u < UP_TAPS / 2; u++)
-            {
-                const uint32_t q = vq[u];
-#pragma unroll
-                for (int i = 0; i < 4; i++) acc[i] = dot2(hp[(r >> 2) + u][i], q, acc[i]);
-            }
-            put(j0 + r, acc);
-        }
-    }
-}
-
-class FormatUpsampleFilter : public BurstFilter
-{
-public:
-    using BurstFilter::BurstFilter;
-    ~FormatUpsampleFilter() override
-    {
-        if (d_hq) (void)hipFree(d_hq);
-        if (d_vq) (void)hipFree(d_vq);
-    }
-    // sws_filter's rows in the kernel's nominal frame; false: a row has a tap outside of it
-    static bool nominal(int src, int dst, int one, int src_pos, int dst_pos, int pad, std::vector<short> &out)
-    {
-        std::vector<int> pos;
-        std::vector<short> coef;
-        const int taps = sws_filter(src, dst, one, src_pos, dst_pos, pos, coef, true);
-        out.assign((size_t)((dst + pad - 1) / pad * pad) * UP_TAPS, 0);
-        for (int i = 0; i < dst; i++)
-            for (int t = 0; t < taps; t++)
-            {
-                const short q = coef[(size_t)i * taps + t];
-                if (q == 0) continue;
-                const int k = pos[i] + t - (2 * (i >> 2) - 2);
-                if (k < 0 || k >= UP_TAPS || pos[i] + t < 0 || pos[i] + t >= src) return false;
-                out[(size_t)i * UP_TAPS + k] = q;
-            }
-        return true;
-    }
-    int setup()
-    {
-        hpass = out_geo.log2_cw < in_geo.log2_cw;
-        vpass = out_geo.log2_ch < in_geo.log2_ch;
-        auto up = [&](short *&dptr, const std::vector<short> &v) -> int {
-            HBHIP_CHECK(ctx, hipMalloc((void **)&dptr, sizeof(short) * v.size()));
-            HBHIP_CHECK(ctx, hipMemcpy(dptr, v.data(), sizeof(short) * v.size(), hipMemcpyHostToDevice));
-            return HBHIP_OK;
-        };
-        std::vector<short> q;
-        // left-sited chroma, the down-sampling's positions swapped: source 128 >> 1, target 128; rows: centred, 128 both
-        if (hpass)
-        {
-            if (!nominal(in_geo.pw[1], out_geo.pw[1], 1 << 14, 64, 128, 4, q)) return HBHIP_ERR_UNSUPPORTED;
-            const int rc = up(d_hq, q);
-            if (rc != HBHIP_OK) return rc;
-        }
-        if (vpass)
-        {
-            if (!nominal(in_geo.ph[1], out_geo.ph[1], 1 << 12, 128, 128, 1, q)) return HBHIP_ERR_UNSUPPORTED;
-            const int rc = up(d_vq, q);
-            if (rc != HBHIP_OK) return rc;
-        }
-        return HBHIP_OK;
-    }
-    int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
-    {
-        return hbhip_for_each_burst<FMT_FRAMES, FormatUpsampleArgs>(ctx, ins, outs, n, [&](FormatUpsampleArgs &a, int nf, int, uintptr_t bits) {
-            if ((bits & 7) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
-            a.w = in_geo.width; a.h = in_geo.height; a.sdepth = in_geo.depth; a.ddepth = out_geo.depth;
-            a.scw = in_geo.pw[1]; a.sch = in_geo.ph[1]; a.dcw = out_geo.pw[1]; a.dch = out_geo.ph[1];
-            a.hq = d_hq; a.vq = d_vq;
-            a.ly = (a.h + 4 * UP_LROWS - 1) / (4 * UP_LROWS);
-            const int rows = 4 * (vpass ? UP_ROWS : UP_ROWS_H);               // output rows a workgroup
-            a.cy = (a.dch + rows - 1) / rows;
-            const dim3 grid(hbhip_grid_x((a.w + 255) / 256), a.ly + 2 * a.cy, nf);
-#define FU_GO(PIX, DPIX, HP, VP) HBHIP_LAUNCH(ctx, "format_upsample", (format_upsample_kernel<PIX, DPIX, HP, VP>), grid, dim3(64, 4), 0, a)
-#define FU_PICK(PIX, DPIX) do { if (hpass && vpass) FU_GO(PIX, DPIX, true, true); else if (hpass) FU_GO(PIX, DPIX, true, false); else FU_GO(PIX, DPIX, false, true); } while (0)
-            if (out_geo.bps == 1)     FU_PICK(uint8_t, uint8_t);
-            else if (in_geo.bps == 1) FU_PICK(uint8_t, uint16_t);
-            else                      FU_PICK(uint16_t, uint16_t);
-#undef FU_PICK
-#undef FU_GO
-            return HBHIP_OK;
-        });
-    }
-    bool hpass = false, vpass = false;
-    short *d_hq = nullptr, *d_vq = nullptr;
-};
-
 } // namespace
-
-extern "C" int hbhip_format_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth,
-                                   int log2_chroma_w, int log2_chroma_h, int full_range, hbhip_filter **out)
-{
-    if (!ctx || !out) return HBHIP_ERR_ARG;
-    *out = nullptr;
-    for (int d : {src_depth, dst_depth})
-        if (d != 8 && d != 10 && d != 12) return HBHIP_ERR_UNSUPPORTED;
-    if (width < 1 || height < 1) return HBHIP_ERR_ARG;
-    PicGeometry gi, go;
-    gi.set(width, height, src_depth, log2_chroma_w, log2_chroma_h);
-    go.set(width, height, dst_depth, log2_chroma_w, log2_chroma_h);
-    *out = hbhip_make_filter<FormatFilter>(ctx, gi, go, full_range);
-    return *out ? HBHIP_OK : HBHIP_ERR_NOMEM;
-}
-
-// the chroma down-sampling and the scaled form behind both create functions: src_depth == dst_depth is the former
-static int format_resample_make(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
-                                int src_log2_ch, int dst_log2_cw, int dst_log2_ch, hbhip_filter **out)
-{
-    if (!ctx || !out) return HBHIP_ERR_ARG;
-    *out = nullptr;
-    for (int d : {src_depth, dst_depth})
-        if (d != 8 && d != 10 && d != 12) return HBHIP_ERR_UNSUPPORTED;
-    if (width < 1 || height < 1) return HBHIP_ERR_ARG;
-    if (!hbhip_yuv_layout_ok(src_log2_cw, src_log2_ch) || !hbhip_yuv_layout_ok(dst_log2_cw, dst_log2_ch)) return HBHIP_ERR_UNSUPPORTED;
-    // down only: no dimension gains chroma samples, the depth does not grow, and one of the three shrinks
-    if (dst_log2_cw < src_log2_cw || dst_log2_ch < src_log2_ch || dst_depth > src_depth ||
-        (dst_log2_cw == src_log2_cw && dst_log2_ch == src_log2_ch && dst_depth == src_depth)) return HBHIP_ERR_UNSUPPORTED;
-    PicGeometry gi, go;
-    gi.set(width, height, src_depth, src_log2_cw, src_log2_ch);
-    go.set(width, height, dst_depth, dst_log2_cw, dst_log2_ch);
-    // a chroma plane so small that initFilter's clamp (size = min(size, src - 2)) cuts the nine taps short: swscale's
-    // filter is then something else than a bicubic, and nobody's to restate
-    if ((dst_log2_cw > src_log2_cw && gi.pw[1] - 2 < 9) || (dst_log2_ch > src_log2_ch && gi.ph[1] - 2 < 9))
-        return HBHIP_ERR_UNSUPPORTED;
-    FormatResampleFilter *f = hbhip_make_filter<FormatResampleFilter>(ctx, gi, go);
-    if (!f) return HBHIP_ERR_NOMEM;
-    const int rc = f->setup();
-    if (rc != HBHIP_OK) { delete f; return rc; }
-    *out = f;
-    return HBHIP_OK;
-}
-
-// (chroma_location: every value is taken as left-sited, the crop/scale drop-in's rule)
-extern "C" int hbhip_format_resample_create(hbhip_ctx *ctx, int width, int height, int depth, int src_log2_cw, int src_log2_ch,
-                                            int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out)
-{
-    (void)chroma_location;
-    return format_resample_make(ctx, width, height, depth, depth, src_log2_cw, src_log2_ch, dst_log2_cw, dst_log2_ch, out);
-}
-
-extern "C" int hbhip_format_scaled_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
-                                          int src_log2_ch, int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out)
-{
-    (void)chroma_location;
-    return format_resample_make(ctx, width, height, src_depth, dst_depth, src_log2_cw, src_log2_ch, dst_log2_cw, dst_log2_ch, out);
-}
-
-// (chroma_location: every value is taken as left-sited, as above)
-extern "C" int hbhip_format_upsample_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
-                                            int src_log2_ch, int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out)
-{
-    (void)chroma_location;
-    if (!ctx || !out) return HBHIP_ERR_ARG;
-    *out = nullptr;
-    for (int d : {src_depth, dst_depth})
-        if (d != 8 && d != 10 && d != 12) return HBHIP_ERR_UNSUPPORTED;
-    if (width < 1 || height < 1) return HBHIP_ERR_ARG;
-    if (!hbhip_yuv_layout_ok(src_log2_cw, src_log2_ch) || !hbhip_yuv_layout_ok(dst_log2_cw, dst_log2_ch)) return HBHIP_ERR_UNSUPPORTED;
-    // up only: no dimension loses chroma samples, the depth does not fall, and one dimension gains
-    if (dst_log2_cw > src_log2_cw || dst_log2_ch > src_log2_ch || dst_depth < src_depth ||
-        (dst_log2_cw == src_log2_cw && dst_log2_ch == src_log2_ch)) return HBHIP_ERR_UNSUPPORTED;
-    PicGeometry gi, go;
-    gi.set(width, height, src_depth, src_log2_cw, src_log2_ch);
-    go.set(width, height, dst_depth, dst_log2_cw, dst_log2_ch);
-    // a chroma plane so small that initFilter's clamp (size = min(size, src - 2)) cuts the five taps short
-    if ((dst_log2_cw < src_log2_cw && gi.pw[1] - 2 < 5) || (dst_log2_ch < src_log2_ch && gi.ph[1] - 2 < 5))
-        return HBHIP_ERR_UNSUPPORTED;
-    FormatUpsampleFilter *f = hbhip_make_filter<FormatUpsampleFilter>(ctx, gi, go);
-    if (!f) return HBHIP_ERR_NOMEM;
-    const int rc = f->setup();
-    if (rc != HBHIP_OK) { delete f; return rc; }
-    *out = f;
-    return HBHIP_OK;
-}
 
 extern "C" int hbhip_pad_create(hbhip_ctx *ctx, const hbhip_pad_params *p, int width, int height, int depth,
                                 int log2_chroma_w, int log2_chroma_h, hbhip_filter **out)

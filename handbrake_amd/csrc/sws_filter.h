@@ -1,5 +1,6 @@
 // sws_filter.h — libswscale's filter table of one dimension, built on the host: the one copy behind the crop/scale and format
-// drop-ins' swscale branches (alias.hip) and the bitmap subtitle scaler (blend.hip, bitmap_scale.hip).
+// drop-in's swscale branch (alias.hip), the format drop-in's scaler (format.hip) and the bitmap subtitle scaler (blend.hip,
+// bitmap_scale.hip).  Host code only: tools/format_nominal_check runs it without a GPU.
 #pragma once
 
 #include <algorithm>
@@ -136,4 +137,31 @@ inline int sws_filter(int src, int dst, int one, int src_pos, int dst_pos, std::
         }
     }
     return fsize;
+}
+
+// The frame the format scaler's kernels read a bicubic table in (format.hip): row i taps the `taps` source samples from
+// 2 * (i >> group) + base on - a window that starts on an even sample whatever the row.  Down, 2:1: each row its own
+// window of ten; up, 1:2: four adjacent rows share one of six.
+struct SwsNominalFrame { int taps, group, base; };
+constexpr SwsNominalFrame SWS_NOMINAL_DOWN = { 10, 0, -4 }, SWS_NOMINAL_UP = { 6, 2, -2 };
+
+// sws_filter(bicubic)'s rows moved into that frame, zeros around them, `dst` padded to a multiple of `pad` rows.
+// false: a row has a tap outside of its window or of the plane - the kernels cannot take that table.
+inline bool sws_nominal(int src, int dst, int one, int src_pos, int dst_pos, int pad, const SwsNominalFrame &fr,
+                        std::vector<short> &out)
+{
+    std::vector<int> pos;
+    std::vector<short> coef;
+    const int taps = sws_filter(src, dst, one, src_pos, dst_pos, pos, coef, true);
+    out.assign((size_t)((dst + pad - 1) / pad * pad) * fr.taps, 0);
+    for (int i = 0; i < dst; i++)
+        for (int t = 0; t < taps; t++)
+        {
+            const short q = coef[(size_t)i * taps + t];
+            if (q == 0) continue;
+            const int k = pos[i] + t - (2 * (i >> fr.group) + fr.base);
+            if (k < 0 || k >= fr.taps || pos[i] + t < 0 || pos[i] + t >= src) return false;
+            out[(size_t)i * fr.taps + k] = q;
+        }
+    return true;
 }

@@ -214,7 +214,7 @@ static int rotate_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
  * libavfilter auto-inserts, i.e. libswscale.  work.c adds it when the encoder wants another pixel format
  * than the pipeline's (work.c:1530-1549), typically 8 <-> 10 bits.  Here it is a real filter for what that
  * use needs (parity unpinned):
- *   - planar YUV depth changes with the subsampling unchanged (csrc/alias.hip:format_kernel);
+ *   - planar YUV depth changes with the subsampling unchanged (csrc/format.hip:format_kernel);
  *   - planar YUV chroma DOWN-sampling, 4:2:2 -> 4:2:0, 4:4:4 -> 4:2:2, 4:4:4 -> 4:2:0, at equal depth or together with a
  *     LOWER depth (format_resample_kernel, its scaled form): hb_get_best_pix_fmt never goes below the title's chroma or
  *     depth (common.c:7516-7604), so a 10-bit 4:2:2 source in front of an 8-bit 4:2:0 encoder gets `format=yuv420p` behind

@@ -151,7 +151,7 @@ def test_device_resident_job_422_10_bit_to_420(built):
 
 
 @pytest.mark.parametrize("stream,target,w,h", [
-    ("420", "yuv422p", 128, 72),              # upsampling: hb_get_best_pix_fmt never asks for it
+    ("420", "yuv422p", 128, 72),              # upsampling: taken only as a marked step behind another drop-in
     ("420", "yuv444p", 128, 72),
     ("422", "yuv444p", 128, 72),
     ("422", "yuv420p10le", 128, 72),          # fewer chroma samples AND another depth: one swscale pass with its own dither
