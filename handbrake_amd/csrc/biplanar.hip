@@ -7,6 +7,8 @@
 //   bi_surface_split_kernel / bi_surface_merge_kernel
 //                             the same pair between a device surface - a pitch of its own per plane, the planes where their
 //                             maker put them - and the frame, without a staging buffer (below)
+//   bi_widen_merge_kernel     an 8-bit planar frame as P010LE, every sample t as t | t << 8, into the staging buffer or a
+//                             surface (below)
 //   blend_bi_same_kernel      blend8onbi8 :606-691 / blend8onbi1x :693-786
 //   blend_bi_subsample_kernel blend_subsample_8onbi8 :330-423 / blend_subsample_8onbi1x :142-234   (blend_body.h)
 //
@@ -195,6 +197,51 @@ __global__ __launch_bounds__(256) void bi_surface_merge_kernel(BiSurface a)
     *reinterpret_cast<uint4 *>(a.splane[1] + (size_t)row * a.spitch[1] + (size_t)u * 16) = chroma_merge<PIX>(cb, cr);
 }
 
+// The widening merge: an 8-bit planar 4:2:0 frame into a P010LE picture, every sample t as the 16-bit word t | t << 8 - the
+// byte twice, what libswscale's unscaled yuv420p -> p010le path writes (NOT t << 8: the low byte is t).  One
+// kernel for both destinations, which differ in addressing only once the staging buffer's luma pitch, align64(2 w), is no
+// longer the frame's, align64(w): rows on blockIdx.y as in the surface kernels, both sides by row and pitch.  A lane writes
+// one 16-byte unit and reads 8 bytes of luma or 4 of Cb and 4 of Cr; one v_perm_b32 per dword written, nothing else.
+//   staging   units = the destination's whole row (pitch / 16): the frame's row padding is read (8 * units <= align64(w),
+//             4 * units <= align64(cw)) and the destination row's written, as in bi_merge_kernel
+//   surface   units = align16(row bytes) / 16: [0, align16(row bytes)) of each sample row and nothing else of the surface
+struct BiWiden
+{
+    uint8_t *dplane[2];              // the P010LE picture: a staging buffer's two planes, or a surface's
+    const uint8_t *plane[3];         // the 8-bit planar frame
+    int dpitch[2];
+    int fpitch[2];                   // of the frame's luma plane / of its chroma planes
+    unsigned rows0;                  // luma rows; the grid's y runs over them and the chroma rows behind them
+    unsigned units[2];               // lanes with work in a luma / chroma row
+};
+
+__global__ __launch_bounds__(256) void bi_widen_merge_kernel(BiWiden a)
+{
+    const unsigned u = blockIdx.x * 256u + threadIdx.x;
+    uint4 v;
+    if (blockIdx.y < a.rows0)
+    {
+        if (u >= a.units[0]) return;
+        const uint2 y = *reinterpret_cast<const uint2 *>(a.plane[0] + (size_t)blockIdx.y * a.fpitch[0] + (size_t)u * 8);
+        v.x = __builtin_amdgcn_perm(y.x, y.x, 0x01010000u);
+        v.y = __builtin_amdgcn_perm(y.x, y.x, 0x03030202u);
+        v.z = __builtin_amdgcn_perm(y.y, y.y, 0x01010000u);
+        v.w = __builtin_amdgcn_perm(y.y, y.y, 0x03030202u);
+        *reinterpret_cast<uint4 *>(a.dplane[0] + (size_t)blockIdx.y * a.dpitch[0] + (size_t)u * 16) = v;
+        return;
+    }
+    if (u >= a.units[1]) return;
+    const unsigned row = blockIdx.y - a.rows0;
+    const size_t at = (size_t)row * a.fpitch[1] + (size_t)u * 4;
+    const unsigned cb = *reinterpret_cast<const unsigned *>(a.plane[1] + at);
+    const unsigned cr = *reinterpret_cast<const unsigned *>(a.plane[2] + at);
+    v.x = __builtin_amdgcn_perm(cr, cb, 0x04040000u);                  // cb0 cb0 cr0 cr0
+    v.y = __builtin_amdgcn_perm(cr, cb, 0x05050101u);
+    v.z = __builtin_amdgcn_perm(cr, cb, 0x06060202u);
+    v.w = __builtin_amdgcn_perm(cr, cb, 0x07070303u);
+    *reinterpret_cast<uint4 *>(a.dplane[1] + (size_t)row * a.dpitch[1] + (size_t)u * 16) = v;
+}
+
 template <typename PIX>
 __global__ __launch_bounds__(256) void blend_bi_same_kernel(BlendArgs a, OverlayGroup G)
 {
@@ -297,6 +344,56 @@ int hbhip_bi_surface_launch(hbhip_ctx *ctx, hipStream_t stream, bool merge, cons
     }
     HBHIP_CHECK(ctx, hipGetLastError());
     return HBHIP_OK;
+}
+
+// bi_widen_merge_kernel from the 8-bit frame `fr` into the P010LE picture at dplane / dpitch; `whole_rows`: the staging rule
+static int bi_widen_launch(hbhip_ctx *ctx, hipStream_t stream, uint8_t *const dplane[2], const int dpitch[2], bool whole_rows,
+                           const hbhip_frame *fr)
+{
+    BiLayout l;
+    hbhip_bi_layout(fr->width, fr->height, 10, &l);
+    const DevPicture &p = fr->pic;
+    if (fr->depth != 8 || p.bps != 1 || fr->lcw != 1 || fr->lch != 1 || p.pitch[1] != p.pitch[2] || (p.pitch[0] & 7) || (p.pitch[1] & 3) ||
+        p.height[0] != l.rows[0] || p.height[1] != l.rows[1] || p.height[2] != l.rows[1] || l.rows[0] + l.rows[1] > 65535)
+        return HBHIP_ERR_ARG;
+    BiWiden a;
+    for (int c = 0; c < 3; c++)
+    {
+        if (!p.plane[c] || ((uintptr_t)p.plane[c] & 15)) return HBHIP_ERR_ARG;
+        a.plane[c] = p.plane[c];
+    }
+    a.fpitch[0] = p.pitch[0];
+    a.fpitch[1] = p.pitch[1];
+    for (int c = 0; c < 2; c++)
+    {
+        if (!dplane[c] || ((uintptr_t)dplane[c] & 15) || (dpitch[c] & 15) || dpitch[c] < l.row_bytes[c]) return HBHIP_ERR_ARG;
+        a.dplane[c] = dplane[c];
+        a.dpitch[c] = dpitch[c];
+        a.units[c] = (unsigned)(whole_rows ? dpitch[c] : hbhip_align_up(l.row_bytes[c], 16)) / 16;
+        // what a lane reads, 8 bytes of luma or 4 of either chroma plane a unit, stays inside the frame's row
+        if ((size_t)a.units[c] * (c == 0 ? 8 : 4) > (size_t)a.fpitch[c]) return HBHIP_ERR_ARG;
+    }
+    a.rows0 = (unsigned)l.rows[0];
+    const unsigned most = a.units[0] > a.units[1] ? a.units[0] : a.units[1];
+    const dim3 grid(hbhip_grid_x((most + 255) / 256), (unsigned)(l.rows[0] + l.rows[1])), blk(256);
+    if (whole_rows) HBHIP_LAUNCH_ON(ctx, stream, "bi_merge_widen", bi_widen_merge_kernel, grid, blk, 0, a);
+    else            HBHIP_LAUNCH_ON(ctx, stream, "bi_surface_merge_widen", bi_widen_merge_kernel, grid, blk, 0, a);
+    HBHIP_CHECK(ctx, hipGetLastError());
+    return HBHIP_OK;
+}
+
+int hbhip_bi_widen_repack_launch(hbhip_ctx *ctx, hipStream_t stream, uint8_t *stage, const hbhip_frame *fr)
+{
+    BiLayout l;
+    hbhip_bi_layout(fr->width, fr->height, 10, &l);
+    uint8_t *const dplane[2] = {stage, stage + (size_t)l.pitch[0] * l.rows[0]};
+    return bi_widen_launch(ctx, stream, dplane, l.pitch, true, fr);
+}
+
+int hbhip_bi_widen_surface_launch(hbhip_ctx *ctx, hipStream_t stream, const hbhip_surface *s, const hbhip_frame *fr)
+{
+    if (s->width != fr->width || s->height != fr->height || s->depth != 10) return HBHIP_ERR_ARG;
+    return bi_widen_launch(ctx, stream, s->plane, s->pitch, false, fr);
 }
 
 int hbhip_bi_blend_launch(hbhip_ctx *ctx, bool subsample, int bps, dim3 grid, const BlendArgs &a, const OverlayGroup &g)

@@ -1166,10 +1166,11 @@ static bool bi_frame_ok(const hbhip_frame *fr)
     return fr->lcw == 1 && fr->lch == 1 && surface_geometry_ok(fr->width, fr->height, fr->depth);
 }
 
-static int bi_check(const hbhip_frame *fr, const hbhip_host_biplanar *hb, BiLayout *l)
+// `widen`: the host picture is P010LE and the frame has 8 bits (hbhip_frame_download_widen)
+static int bi_check(const hbhip_frame *fr, const hbhip_host_biplanar *hb, BiLayout *l, bool widen = false)
 {
-    if (!bi_frame_ok(fr)) return HBHIP_ERR_UNSUPPORTED;
-    hbhip_bi_layout(fr->width, fr->height, fr->depth, l);
+    if (!bi_frame_ok(fr) || (widen && fr->depth != 8)) return HBHIP_ERR_UNSUPPORTED;
+    hbhip_bi_layout(fr->width, fr->height, widen ? 10 : fr->depth, l);
     for (int p = 0; p < 2; p++)
         if (hb->plane[p] == nullptr || hb->stride[p] < l->row_bytes[p]) return HBHIP_ERR_ARG;
     return HBHIP_OK;
@@ -1254,14 +1255,14 @@ int hbhip_frame_upload_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *src)
     return rc != HBHIP_OK ? rc : hbhip_ctx_upload_done(fr->ctx, token, 1);
 }
 
-// `dst` and the frame must stay valid until hbhip_frame_download_wait(fr, token) has returned
-int hbhip_frame_download_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *dst, void **token)
+// the merge into the staging buffer and the D2H copy behind it; `widen`: an 8-bit frame as P010LE (bi_widen_merge_kernel)
+static int download_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *dst, void **token, bool widen)
 {
     if (!fr || !dst || !token) return HBHIP_ERR_ARG;
     *token = nullptr;
     hbhip_ctx *ctx = fr->ctx;
     BiLayout l;
-    int rc = bi_check(fr, dst, &l);
+    int rc = bi_check(fr, dst, &l, widen);
     if (rc != HBHIP_OK) return rc;
     (void)hipSetDevice(ctx->device);
     size_t moved = 0;
@@ -1269,17 +1270,35 @@ int hbhip_frame_download_biplanar_async(hbhip_frame *fr, const hbhip_host_biplan
         std::lock_guard<std::mutex> lk(ctx->bi_lock[1]);
         uint8_t *stage = bi_stage(ctx, 1, l.bytes, down);
         if (!stage) return ctx->fail(hipErrorOutOfMemory, "download (biplanar)");
-        const int launched = hbhip_bi_repack_launch(ctx, down, true, stage, fr);
+        const int launched = widen ? hbhip_bi_widen_repack_launch(ctx, down, stage, fr) : hbhip_bi_repack_launch(ctx, down, true, stage, fr);
         return launched != HBHIP_OK ? launched : hip_rc(ctx, bi_copy(stage, l, dst, false, down, &moved), "download (biplanar)");
     }, token);
     if (rc == HBHIP_OK) ctx->bus_d2h += moved;
     return rc;
 }
 
+// `dst` and the frame must stay valid until hbhip_frame_download_wait(fr, token) has returned
+int hbhip_frame_download_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *dst, void **token)
+{
+    return download_biplanar(fr, dst, token, false);
+}
+
 int hbhip_frame_download_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *dst)
 {
     void *token = nullptr;
     const int rc = hbhip_frame_download_biplanar_async(fr, dst, &token);
+    return rc != HBHIP_OK ? rc : hbhip_frame_download_wait(fr, token);
+}
+
+int hbhip_frame_download_widen_async(hbhip_frame *fr, const hbhip_host_biplanar *dst, void **token)
+{
+    return download_biplanar(fr, dst, token, true);
+}
+
+int hbhip_frame_download_widen(hbhip_frame *fr, const hbhip_host_biplanar *dst)
+{
+    void *token = nullptr;
+    const int rc = hbhip_frame_download_widen_async(fr, dst, &token);
     return rc != HBHIP_OK ? rc : hbhip_frame_download_wait(fr, token);
 }
 
@@ -1432,10 +1451,11 @@ int hbhip_surface_set_ready_event(hbhip_surface *s, void *hip_event)
     return HBHIP_OK;
 }
 
-static int surface_check(const hbhip_frame *fr, const hbhip_surface *s)
+// `widen`: a depth-10 surface for an 8-bit frame (hbhip_frame_export_surface_widen)
+static int surface_check(const hbhip_frame *fr, const hbhip_surface *s, bool widen = false)
 {
-    if (!bi_frame_ok(fr)) return HBHIP_ERR_UNSUPPORTED;
-    if (s->depth != fr->depth || s->width != fr->width || s->height != fr->height) return HBHIP_ERR_UNSUPPORTED;
+    if (!bi_frame_ok(fr) || (widen && fr->depth != 8)) return HBHIP_ERR_UNSUPPORTED;
+    if (s->depth != (widen ? 10 : fr->depth) || s->width != fr->width || s->height != fr->height) return HBHIP_ERR_UNSUPPORTED;
     if (s->ctx->device != fr->ctx->device) return HBHIP_ERR_ARG;
     return HBHIP_OK;
 }
@@ -1493,12 +1513,13 @@ int hbhip_frame_import_surface(hbhip_frame *fr, hbhip_surface *src)
     return rc != HBHIP_OK ? rc : hbhip_ctx_upload_done(fr->ctx, token, 1);
 }
 
-int hbhip_frame_export_surface_async(hbhip_frame *fr, hbhip_surface *dst, void **token)
+// the merge into the surface; `widen`: an 8-bit frame into a depth-10 surface (bi_widen_merge_kernel)
+static int export_surface(hbhip_frame *fr, hbhip_surface *dst, void **token, bool widen)
 {
     if (!fr || !dst || !token) return HBHIP_ERR_ARG;
     *token = nullptr;
     hbhip_ctx *ctx = fr->ctx;
-    int rc = surface_check(fr, dst);
+    int rc = surface_check(fr, dst, widen);
     if (rc != HBHIP_OK) return rc;
     (void)hipSetDevice(ctx->device);
     surface_reap(ctx, false);
@@ -1513,8 +1534,8 @@ int hbhip_frame_export_surface_async(hbhip_frame *fr, hbhip_surface *dst, void *
         if (e == hipSuccess && producer) e = hipStreamWaitEvent(down, producer, 0);
         if (e == hipSuccess) e = wait_mark(down, readers);
         if (e != hipSuccess) return ctx->fail(e, "export: order behind the surface's users");
-        return hbhip_bi_surface_launch(ctx, down, true, dst, fr);
-    }, [&](hipStream_t down) {                                  // the surface's mark behind the token's event, as in the import
+        return widen ? hbhip_bi_widen_surface_launch(ctx, down, dst, fr) : hbhip_bi_surface_launch(ctx, down, true, dst, fr);
+    }, [&](hipStream_t down) {                                // the surface's mark behind the token's event, as in the import
         m = record_mark(down);
         return m ? HBHIP_OK : ctx->fail(hipErrorOutOfMemory, "export (surface)");
     }, token);
@@ -1529,10 +1550,27 @@ int hbhip_frame_export_surface_async(hbhip_frame *fr, hbhip_surface *dst, void *
     return HBHIP_OK;
 }
 
+int hbhip_frame_export_surface_async(hbhip_frame *fr, hbhip_surface *dst, void **token)
+{
+    return export_surface(fr, dst, token, false);
+}
+
 int hbhip_frame_export_surface(hbhip_frame *fr, hbhip_surface *dst)
 {
     void *token = nullptr;
     const int rc = hbhip_frame_export_surface_async(fr, dst, &token);
+    return rc != HBHIP_OK ? rc : hbhip_frame_download_wait(fr, token);
+}
+
+int hbhip_frame_export_surface_widen_async(hbhip_frame *fr, hbhip_surface *dst, void **token)
+{
+    return export_surface(fr, dst, token, true);
+}
+
+int hbhip_frame_export_surface_widen(hbhip_frame *fr, hbhip_surface *dst)
+{
+    void *token = nullptr;
+    const int rc = hbhip_frame_export_surface_widen_async(fr, dst, &token);
     return rc != HBHIP_OK ? rc : hbhip_frame_download_wait(fr, token);
 }
 

@@ -259,6 +259,10 @@ struct hbhip_surface
 };
 // the repack kernel between a surface and the planar 4:2:0 frame `fr` (same size and depth: the caller has checked), on `stream`
 int hbhip_bi_surface_launch(hbhip_ctx *ctx, hipStream_t stream, bool merge, const hbhip_surface *s, const hbhip_frame *fr);
+// the widening merges: the 8-bit planar 4:2:0 frame `fr` as P010LE (every sample t as t | t << 8) into a staging buffer laid
+// out for depth 10, or into a depth-10 surface of the frame's size (the caller has checked both), on `stream`
+int hbhip_bi_widen_repack_launch(hbhip_ctx *ctx, hipStream_t stream, uint8_t *stage, const hbhip_frame *fr);
+int hbhip_bi_widen_surface_launch(hbhip_ctx *ctx, hipStream_t stream, const hbhip_surface *s, const hbhip_frame *fr);
 
 // Geometry of a planar YUV picture.
 struct PicGeometry

@@ -339,6 +339,137 @@ def run_job(filters, frames, flags: int = 0x10, pix_fmt: int = AV_PIX_FMT_YUV420
     return names, out
 
 
+class _FilterObject(C.Structure):
+    """hb_filter_object_t (include/hbhip_libhb.h; tests/golden/filter_object_layout.txt pins the offsets)"""
+    _fields_ = [("id", C.c_int), ("enforce_order", C.c_int), ("skip", C.c_int), ("aliased", C.c_int),
+                ("name", C.c_char_p), ("short_name", C.c_char_p), ("settings", C.c_void_p),
+                ("init", C.c_void_p), ("init_thread", C.c_void_p), ("post_init", C.c_void_p), ("work", C.c_void_p),
+                ("work_thread", C.c_void_p), ("close", C.c_void_p), ("info", C.c_void_p),
+                ("settings_template", C.c_char_p), ("fifo_in", C.c_void_p), ("fifo_out", C.c_void_p),
+                ("subtitle", C.c_void_p), ("private_data", C.c_void_p), ("thread", C.c_void_p), ("done", C.c_void_p),
+                ("status", C.c_int), ("chapter_val", C.c_int), ("chapter_time", C.c_int64), ("sub_filter", C.c_void_p)]
+
+
+class _Job(C.Structure):
+    """hb_job_t, the stand-in's fields (include/hbhip_libhb.h)"""
+    _fields_ = [("list_filter", C.c_void_p), ("hw_pix_fmt", C.c_int), ("input_pix_fmt", C.c_int),
+                ("hw_device_index", C.c_int), ("h", C.c_void_p), ("done", C.c_int), ("crop", C.c_int * 4),
+                ("title", C.c_void_p), ("list_subtitle", C.c_void_p), ("list_attachment", C.c_void_p),
+                ("vcodec", C.c_int), ("hw_decode", C.c_int)]
+
+
+class _Init(C.Structure):
+    """hb_filter_init_t as far as a source fills it in (hb_harness.c:source_init); the tail is room for the rest"""
+    _fields_ = [("job", C.c_void_p), ("pix_fmt", C.c_int), ("hw_pix_fmt", C.c_int), ("hw_frames_ctx", C.c_void_p),
+                ("color", C.c_int * 4), ("chroma_location", C.c_int), ("geometry", C.c_int * 4), ("crop", C.c_int * 4),
+                ("grayscale", C.c_int), ("vrate", C.c_int * 2), ("cfr", C.c_int), ("time_base", C.c_int * 2),
+                ("tail", C.c_int * 32)]
+
+
+_INIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p)
+_CLOSE_FN = C.CFUNCTYPE(None, C.c_void_p)
+
+
+def filter_stub(filter_id: int, name: str, init_result: int = 0):
+    """A registered (CPU) filter of the given id that does nothing: its init() answers init_result.  For list tests that
+    never push a frame.  Returns (address for register_filters' table, what must stay alive)."""
+    fn = _INIT_FN(lambda f, init: init_result)
+    obj = _FilterObject()
+    obj.id, obj.enforce_order = filter_id, 1
+    obj.name = obj.short_name = name.encode()
+    obj.init = C.cast(fn, C.c_void_p)
+    return C.addressof(obj), (obj, fn)
+
+
+class JobList:
+    """A job's filter list WITHOUT a chain around it - what do_job() has before it starts its threads: built from the
+    registered objects by id (hb_filter_init + hb_add_filter_dict), handed to hb_hip_setup_hw_filters (setup()), and
+    initialised the way work.c:1820-1870 / hbh_job_open do it, with hb_hip_filter_init_failed as the fallback
+    (init_all()).  entries() says what the list holds at any point: [(name, {settings})]."""
+
+    def __init__(self, filters, width: int, height: int, pix_fmt: int = AV_PIX_FMT_YUV420P):
+        from . import hip
+        rt = self._rt = runtime()
+        self._flt = hip.filters()
+        for fn, res, args in (("hb_list_init", C.c_void_p, []), ("hb_list_count", C.c_int, [C.c_void_p]),
+                              ("hb_list_item", C.c_void_p, [C.c_void_p, C.c_int]), ("hb_list_rem", None, [C.c_void_p, C.c_void_p]),
+                              ("hb_list_close", None, [C.POINTER(C.c_void_p)]), ("hb_filter_init", C.c_void_p, [C.c_int]),
+                              ("hb_filter_close", None, [C.POINTER(C.c_void_p)]),
+                              ("hb_add_filter_dict", None, [C.c_void_p, C.c_void_p, C.c_void_p]),
+                              ("hbhip_dict_from_string", C.c_void_p, [C.c_char_p]), ("hb_dict_free", None, [C.POINTER(C.c_void_p)])):
+            getattr(rt, fn).restype, getattr(rt, fn).argtypes = res, args
+        self._flt.hb_hip_setup_hw_filters.restype, self._flt.hb_hip_setup_hw_filters.argtypes = None, [C.c_void_p]
+        self._flt.hb_hip_filter_init_failed.restype = C.c_int
+        self._flt.hb_hip_filter_init_failed.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        self.job = _Job()
+        self.job.hw_pix_fmt, self.job.input_pix_fmt, self.job.hw_device_index = -1, pix_fmt, -1
+        self.job.list_filter = rt.hb_list_init()
+        for fid, settings in filters:
+            f = rt.hb_filter_init(fid)
+            if not f:
+                raise RuntimeError(f"no filter registered for id {fid}")
+            d = C.c_void_p(rt.hbhip_dict_from_string((settings or "").encode()))
+            rt.hb_add_filter_dict(self.job.list_filter, f, d)
+            rt.hb_dict_free(C.byref(d))
+        self.init = _Init()
+        self.init.job = C.addressof(self.job)
+        self.init.pix_fmt, self.init.hw_pix_fmt, self.init.chroma_location = pix_fmt, -1, 1
+        self.init.color[:] = [1, 1, 1, 1]
+        self.init.geometry[:] = [width, height, 1, 1]
+        self.init.vrate[:] = [30000, 1001]
+        self.init.time_base[:] = [1, 90000]
+
+    def _items(self):
+        n = self._rt.hb_list_count(self.job.list_filter)
+        return [self._rt.hb_list_item(self.job.list_filter, i) for i in range(n)]
+
+    def entries(self):
+        out = []
+        for p in self._items():
+            f = _FilterObject.from_address(p)
+            settings, d = {}, f.settings
+            e = C.cast(d, C.POINTER(C.c_void_p))[0] if d else None            # hbhip_dict_s { kv *head, *tail }
+            while e:
+                k, v, e = C.cast(e, C.POINTER(C.c_void_p))[0:3]                # kv_s { char *k, *v; kv *next }
+                settings[C.cast(k, C.c_char_p).value.decode()] = C.cast(v, C.c_char_p).value.decode()
+            out.append((f.name.decode(), settings))
+        return out
+
+    def setup(self):
+        self._flt.hb_hip_setup_hw_filters(C.byref(self.job))
+        return self.entries()
+
+    def init_all(self):
+        rt, i = self._rt, 0
+        while i < rt.hb_list_count(self.job.list_filter):
+            p = rt.hb_list_item(self.job.list_filter, i)
+            f = _FilterObject.from_address(p)
+            f.private_data = None
+            if f.init and _INIT_FN(f.init)(p, C.addressof(self.init)):
+                back = self._flt.hb_hip_filter_init_failed(C.byref(self.job), i, C.byref(self.init))
+                if back > 0:
+                    i -= back - 1
+                    continue
+                rt.hb_list_rem(self.job.list_filter, p)
+                rt.hb_filter_close(C.byref(C.c_void_p(p)))
+                continue
+            i += 1
+        return self.entries()
+
+    def close(self):
+        if not self.job.list_filter:
+            return
+        for p in self._items():
+            f = _FilterObject.from_address(p)
+            if f.private_data and f.close:
+                _CLOSE_FN(f.close)(p)
+            self._rt.hb_list_rem(self.job.list_filter, p)
+            self._rt.hb_filter_close(C.byref(C.c_void_p(p)))
+        lst = C.c_void_p(self.job.list_filter)
+        self._rt.hb_list_close(C.byref(lst))
+        self.job.list_filter = None
+
+
 def set_job_device(index: int = -1):
     """job->hw_device_index (common.h:991) of jobs opened from now on: the GPU their drop-ins run on; -1 = not set."""
     rt = runtime()

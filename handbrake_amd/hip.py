@@ -26,6 +26,7 @@ ABI_SYMBOLS = [
     "hbhip_frame_upload_biplanar", "hbhip_frame_download_biplanar", "hbhip_frame_upload_biplanar_async", "hbhip_frame_download_biplanar_async",
     "hbhip_surface_alloc", "hbhip_surface_wrap", "hbhip_surface_retain", "hbhip_surface_release", "hbhip_surface_describe", "hbhip_surface_set_ready_event",
     "hbhip_frame_import_surface", "hbhip_frame_import_surface_async", "hbhip_frame_export_surface", "hbhip_frame_export_surface_async", "hbhip_ctx_bus_bytes",
+    "hbhip_frame_download_widen", "hbhip_frame_download_widen_async", "hbhip_frame_export_surface_widen", "hbhip_frame_export_surface_widen_async",
     "hbhip_filter_use_frames", "hbhip_filter_push_frame", "hbhip_filter_pull_frame", "hbhip_filter_push", "hbhip_filter_push_dev", "hbhip_filter_pull", "hbhip_filter_pull_dev",
     "hbhip_filter_process_dev", "hbhip_filter_submit_async", "hbhip_filter_wait", "hbhip_filter_inflight", "hbhip_filter_flush", "hbhip_filter_pending", "hbhip_filter_defer", "hbhip_filter_kick", "hbhip_filter_destroy",
     "hbhip_filter_out_geometry",
@@ -164,9 +165,9 @@ def lib() -> C.CDLL:
         for fn in ("hbhip_frame_upload", "hbhip_frame_download"):
             getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(HostFrame)]
         L.hbhip_frame_upload_async.argtypes = [C.c_void_p, C.POINTER(HostFrame), C.POINTER(C.c_void_p)]
-        for fn in ("hbhip_frame_upload_biplanar", "hbhip_frame_download_biplanar"):
+        for fn in ("hbhip_frame_upload_biplanar", "hbhip_frame_download_biplanar", "hbhip_frame_download_widen"):
             getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(HostBiplanar)]
-        for fn in ("hbhip_frame_upload_biplanar_async", "hbhip_frame_download_biplanar_async"):
+        for fn in ("hbhip_frame_upload_biplanar_async", "hbhip_frame_download_biplanar_async", "hbhip_frame_download_widen_async"):
             getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(HostBiplanar), C.POINTER(C.c_void_p)]
         L.hbhip_frame_download_wait.argtypes = [C.c_void_p, C.c_void_p]
         L.hbhip_ctx_upload_done.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
@@ -178,9 +179,9 @@ def lib() -> C.CDLL:
             getattr(L, fn).restype = None
         L.hbhip_surface_describe.argtypes = [C.c_void_p, C.POINTER(DevSurface)] + [C.POINTER(C.c_int)] * 3
         L.hbhip_surface_set_ready_event.argtypes = [C.c_void_p, C.c_void_p]
-        for fn in ("hbhip_frame_import_surface", "hbhip_frame_export_surface"):
+        for fn in ("hbhip_frame_import_surface", "hbhip_frame_export_surface", "hbhip_frame_export_surface_widen"):
             getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p]
-        for fn in ("hbhip_frame_import_surface_async", "hbhip_frame_export_surface_async"):
+        for fn in ("hbhip_frame_import_surface_async", "hbhip_frame_export_surface_async", "hbhip_frame_export_surface_widen_async"):
             getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.hbhip_ctx_bus_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.hbhip_filter_use_frames.argtypes = [C.c_void_p]
@@ -326,6 +327,10 @@ class Frame:
 
     def export_surface(self, surface: "Surface"):
         check(lib().hbhip_frame_export_surface(self.h, surface.h), self.ctx.h, "frame_export_surface")
+
+    def export_surface_widen(self, surface: "Surface"):
+        """an 8-bit 4:2:0 frame into a depth-10 surface, every sample t as t | t << 8"""
+        check(lib().hbhip_frame_export_surface_widen(self.h, surface.h), self.ctx.h, "frame_export_surface_widen")
 
     def copy_from(self, src: "Frame"):
         check(lib().hbhip_frame_copy(self.h, src.h), self.ctx.h, "frame_copy")

@@ -224,6 +224,8 @@ static int rotate_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
  *     libswscale takes every semi-planar target but the two exact repacks through its scaler, so a depth change alone is
  *     the scaled form too (yuv420p10le -> nv12 is NOT format_kernel's 10 -> 8); a stream that already is the planar
  *     step passes through.
+ *   - `format=p010le` on 8-bit 4:2:0 frames, when hip_common.c has marked the entry with HBHIP_FORMAT_WIDEN_STEP: the frames
+ *     pass through as they are, yuv420p, and the run's download adapter widens them inside its repack.
  *   - planar YUV chroma UP-sampling, 4:2:0 -> 4:2:2, 4:2:2 -> 4:4:4, 4:2:0 -> 4:4:4, at equal or HIGHER depth
  *     (format_upsample_kernel), when hip_common.c has marked the entry with HBHIP_FORMAT_UP_STEP, i.e. behind another
  *     drop-in of a device-resident run.  The reference does ask for it: hb_get_best_pix_fmt chooses the pipeline's format
@@ -267,6 +269,16 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     }
     int dst_fmt = av_get_pix_fmt(format);                                     /* :107 */
     free(format);
+    /* hip_common.c's mark on a `format=p010le` entry inside a run of 8-bit 4:2:0 frames: nothing to do here, the run's download
+     * adapter widens inside its repack and says p010le downstream.  (A frame under 2 x 2 it would refuse: declined here.) */
+    int widen_step = 0;
+    hb_dict_extract_bool(&widen_step, filter->settings, HBHIP_FORMAT_WIDEN_STEP);
+    if (widen_step && pv->s.dev_io && dst_fmt == HBHIP_PIX_FMT_P010LE && init->pix_fmt == AV_PIX_FMT_YUV420P &&
+        init->geometry.width >= 2 && init->geometry.height >= 2)
+    {
+        pv->s.output = *init;
+        return 0;
+    }
     /* hip_common.c's mark on a `format=nv12 | p010le` entry inside a run: make the planar frame the download adapter repacks */
     int planar_step = 0;
     hb_dict_extract_bool(&planar_step, filter->settings, HBHIP_FORMAT_PLANAR_STEP);

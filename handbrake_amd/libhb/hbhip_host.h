@@ -40,6 +40,12 @@ static inline int hbhip_host_is_biplanar(int pix_fmt) { return pix_fmt == HBHIP_
  * frames (at equal or higher depth): the Format drop-in takes such a target only where this key stands, i.e. where the
  * frames already are in HBM.  Stripped wherever the key above is. */
 #define HBHIP_FORMAT_UP_STEP "hip-up-step"
+/* The third: on a `format=p010le` entry inside a run of 8-bit 4:2:0 frames (a yuv420p or nv12 job in front of a 10-bit
+ * hardware encoder).  The Format drop-in passes such frames through, and the run's download adapter, which hip_common.c
+ * gives format=p010le and this same key, widens them inside its repack (every sample t as t | t << 8).  Only under the key
+ * does the adapter take format=p010le on an 8-bit run; it is no part of its settings template.  Stripped wherever the
+ * other two are. */
+#define HBHIP_FORMAT_WIDEN_STEP "hip-widen-step"
 static inline void hbhip_host_biplanar_from_buf(hbhip_host_biplanar *f, const hb_buffer_t *b)
 {
     for (int p = 0; p < 2; p++)

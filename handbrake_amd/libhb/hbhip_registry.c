@@ -710,6 +710,7 @@ struct hb_filter_private_s
     int              depth, lcw, lch;
     int              biplanar;            /* the host side of this adapter is NV12 / P010LE: repacked on the GPU */
     int              surface;             /* download, surface=1: the NV12 / P010LE pictures it emits stay in device memory */
+    int              widen;               /* download, HBHIP_FORMAT_WIDEN_STEP: P010LE from a run of 8-bit frames */
     hbhip_ctx       *ctx;                 /* the job's GPU (hbhip_host_ctx_for) */
     dl_slot_t        dl[DL_DEPTH + 1];
     int              dl_head, dl_count;
@@ -723,7 +724,10 @@ struct hb_filter_private_s
  * Device surfaces (HBHIP_SURFACE buffers) are the same two formats without the bus: an upload adapter initialised for NV12 /
  * P010LE imports a buffer that holds one (a hardware decoder's picture), and the download adapter under
  * format=nv12 | p010le:surface=1 emits them (for a hardware encoder), from the context's pool, laid out as a video engine's
- * allocator would (256-byte pitch, 16 padded rows). */
+ * allocator would (256-byte pitch, 16 padded rows).
+ * format=p010le fits a run of 10 bits only - except under HBHIP_FORMAT_WIDEN_STEP, the key hip_common.c sets beside it behind
+ * a marked `format=p010le` entry of an 8-bit 4:2:0 run: the adapter then emits P010LE, host pictures or depth-10 surfaces,
+ * widened inside the repack (hbhip_frame_download_widen / hbhip_frame_export_surface_widen). */
 static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int to_device)
 {
     hb_filter_private_t *pv = calloc(1, sizeof(*pv));
@@ -747,8 +751,12 @@ static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int 
     if (!to_device && hb_dict_extract_string(&want, filter->settings, "format") && want != NULL && want[0] != 0)
     {
         host_fmt = av_get_pix_fmt(want);
+        /* hip_common.c's key beside format=p010le on a run of 8-bit frames: the repack widens (never a public setting) */
+        int widen = 0;
+        hb_dict_extract_bool(&widen, filter->settings, HBHIP_FORMAT_WIDEN_STEP);
+        pv->widen = widen && host_fmt == HBHIP_PIX_FMT_P010LE && pv->depth == 8;
         const int ok = hbhip_host_is_biplanar(host_fmt) && hbhip_host_planar_yuv(desc) && pv->lcw == 1 && pv->lch == 1 &&
-                       pv->depth == (host_fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10);
+                       (pv->depth == (host_fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10) || pv->widen);
         if (!ok)
         {
             hb_error("hipdownload: format=%s does not fit a run of %s", want, desc->name);
@@ -914,10 +922,11 @@ static int download_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_bu
     {
         /* the merge writes a surface of the pool; it goes back there when the consumer closes the buffer */
         hbhip_surface *sf = NULL;
-        if (hbhip_surface_alloc(pv->ctx, in->f.width, in->f.height, pv->depth, 256, 16, &sf) != HBHIP_OK) return HB_FILTER_FAILED;
+        if (hbhip_surface_alloc(pv->ctx, in->f.width, in->f.height, pv->widen ? 10 : pv->depth, 256, 16, &sf) != HBHIP_OK) return HB_FILTER_FAILED;
         out = hbhip_host_wrap_surface(sf, &pv->output, in->f.width, in->f.height);
         if (out == NULL) return HB_FILTER_FAILED;       /* (the wrap takes the reference over: it has released the surface) */
-        if (hbhip_frame_export_surface_async(fr, sf, &token) != HBHIP_OK)
+        if ((pv->widen ? hbhip_frame_export_surface_widen_async(fr, sf, &token)
+                       : hbhip_frame_export_surface_async(fr, sf, &token)) != HBHIP_OK)
         {
             hb_buffer_close(&out);
             return HB_FILTER_FAILED;
@@ -934,7 +943,8 @@ static int download_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_bu
         hbhip_host_frame_from_buf(&hf, out);
         hbhip_host_biplanar hb;
         hbhip_host_biplanar_from_buf(&hb, out);
-        if ((pv->biplanar ? hbhip_frame_download_biplanar_async(fr, &hb, &token)
+        if ((pv->widen    ? hbhip_frame_download_widen_async(fr, &hb, &token) :
+             pv->biplanar ? hbhip_frame_download_biplanar_async(fr, &hb, &token)
                           : hbhip_frame_download_async(fr, &hf, &token)) != HBHIP_OK)
         {
             hb_buffer_close(&out);

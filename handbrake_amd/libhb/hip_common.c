@@ -13,7 +13,9 @@
  *      HBHIP_FORMAT_PLANAR_STEP in its settings, never through the public `format=` value) to make yuv420p / yuv420p10le,
  *      and the run's download adapter gets format=nv12 | p010le and repacks on the GPU (mark_planar_steps).  The same walk
  *      marks a `format=yuv422p... | yuv444p...` entry behind a drop-in whose target has MORE chroma samples than the job's
- *      frames (HBHIP_FORMAT_UP_STEP): the Format drop-in takes such a target only there.
+ *      frames (HBHIP_FORMAT_UP_STEP): the Format drop-in takes such a target only there.  And `format=p010le` behind a
+ *      drop-in of a yuv420p or nv12 job (HBHIP_FORMAT_WIDEN_STEP): the Format drop-in passes the 8-bit frames through and
+ *      the download adapter, given format=p010le and the same key, widens them inside its repack.
  * And one thing the VideoToolbox path does not need: a drop-in's init() may refuse settings it has no kernels for.
  * work.c drops a filter whose init fails (:1861-1868) - for a drop-in that would silently lose the filter, so the init
  * loop calls hb_hip_filter_init_failed() first, which puts the CPU filter back (and re-brackets the run around it).
@@ -67,25 +69,40 @@ static int job_host_fmt(const hb_job_t *job)
 
 /* `host_fmt`: the job's own format when that is NV12 / P010LE.  The upload adapter sees it as the stream's format; the
  * download adapter is told to give it back (format=), so that what leaves the run is what the job's encoder expects. */
-static hb_filter_object_t *new_adapter(int id, int host_fmt)
+static hb_filter_object_t *new_adapter(int id, int host_fmt, int widen)
 {
     hb_filter_object_t *a = hb_filter_copy(hbhip_filter_get(id));
     if (a != NULL && a->settings == NULL) a->settings = hb_dict_init();
     if (a != NULL && id == HB_FILTER_HIP_DOWNLOAD && hbhip_host_is_biplanar(host_fmt))
+    {
         hb_dict_set_string(a->settings, "format", host_fmt == HBHIP_PIX_FMT_NV12 ? "nv12" : "p010le");
+        if (widen) hb_dict_set_string(a->settings, HBHIP_FORMAT_WIDEN_STEP, "1");
+    }
     return a;
 }
 
-/* the NV12 / P010LE target of a Format drop-in entry that mark_planar_steps() has marked, else AV_PIX_FMT_NONE */
-static int planar_step_target(const hb_filter_object_t *f)
+/* the NV12 / P010LE target of a Format drop-in entry that mark_planar_steps() has marked, else AV_PIX_FMT_NONE.
+ * *widen: the mark is HBHIP_FORMAT_WIDEN_STEP (the target is P010LE and the frames have 8 bits) */
+static int planar_step_target(const hb_filter_object_t *f, int *widen)
 {
     int marked = 0, fmt = AV_PIX_FMT_NONE;
     char *name = NULL;
+    *widen = 0;
     if (f == NULL || f->id != HB_FILTER_FORMAT || !hb_hip_filter_is_hip(f) || f->settings == NULL) return AV_PIX_FMT_NONE;
-    if (!hb_dict_extract_bool(&marked, f->settings, HBHIP_FORMAT_PLANAR_STEP) || !marked) return AV_PIX_FMT_NONE;
+    if (hb_dict_extract_bool(&marked, f->settings, HBHIP_FORMAT_WIDEN_STEP) && marked) *widen = 1;
+    else if (!hb_dict_extract_bool(&marked, f->settings, HBHIP_FORMAT_PLANAR_STEP) || !marked) return AV_PIX_FMT_NONE;
     if (hb_dict_extract_string(&name, f->settings, "format") && name != NULL) fmt = av_get_pix_fmt(name);
     free(name);
+    if (*widen && fmt != HBHIP_PIX_FMT_P010LE) { *widen = 0; return AV_PIX_FMT_NONE; }
     return hbhip_host_is_biplanar(fmt) ? fmt : AV_PIX_FMT_NONE;
+}
+
+/* the three keys of mark_planar_steps(): nothing a CPU filter knows, and stale once the list in front has changed */
+static void remove_marks(hb_dict_t *settings)
+{
+    hb_dict_remove(settings, HBHIP_FORMAT_PLANAR_STEP);
+    hb_dict_remove(settings, HBHIP_FORMAT_UP_STEP);
+    hb_dict_remove(settings, HBHIP_FORMAT_WIDEN_STEP);
 }
 
 /* work.c appends `format=nv12` / `format=p010le` when the encoder wants one of them (work.c:1525-1552, match_pix_fmt).
@@ -93,9 +110,9 @@ static int planar_step_target(const hb_filter_object_t *f)
  * depth is at least the target's, the frames need not leave the device a filter early: the entry is marked, its drop-in
  * makes the planar step, and bracket_runs() gives the download adapter behind it the biplanar format.  The entry keeps
  * `format=nv12`, so that the fallback hands the CPU filter its own settings (hb_hip_filter_init_failed strips the mark).
- * Not marked: an 8-bit stream under p010le (a higher depth: init() declines it as before), and an entry with no drop-in
- * in front of it - on a yuv420p job its planar step would be the identity, and an interleave on the CPU is cheaper than a
- * round trip over the bus.
+ * Not marked: an 8-bit 4:2:2 / 4:4:4 stream under p010le (a higher depth: init() declines it as before; 8-bit 4:2:0 gets
+ * the widen step, below), and an entry with no drop-in in front of it - on a yuv420p job its planar step would be the
+ * identity, and an interleave on the CPU is cheaper than a round trip over the bus.
  *
  * The same walk marks the UP step (HBHIP_FORMAT_UP_STEP).  work.c appends `format=yuv422p...` / `format=yuv444p...` to a
  * 4:2:0 chain when the encoder's list holds only such formats: hb_get_best_pix_fmt chooses the pipeline's format from the
@@ -104,12 +121,21 @@ static int planar_step_target(const hb_filter_object_t *f)
  * common.c:2252-2384; ProRes, DNxHR).  Such an entry - a planar YUV 4:2:0 / 4:2:2 / 4:4:4 target at 8 / 10 / 12 bits that
  * loses chroma samples in no dimension, gains them in one at least and is no shallower than the job - is marked under the
  * same condition, a drop-in in front of it, and for the same reason; the Format drop-in takes such a target only where
- * the mark stands, so a lone `format=yuv422p` keeps its CPU filter as before. */
+ * the mark stands, so a lone `format=yuv422p` keeps its CPU filter as before.
+ *
+ * And the WIDEN step (HBHIP_FORMAT_WIDEN_STEP): `format=p010le` on a job of 8-bit 4:2:0 frames, what work.c appends for
+ * every 8-bit title in front of AMD's 10-bit encoders (encavcodec.c:321-324, hb_get_best_pix_fmt never lifts the pipeline
+ * above the title's depth, common.c:7516-7524).  On a yuv420p job and on an nv12 job alike - the upload adapter of an nv12
+ * job's run makes yuv420p frames, and this is the one mark such a job gets - under the same condition, a drop-in in front.
+ * The Format drop-in passes the frames through and the run's download adapter widens them inside its repack.  8-bit
+ * 4:2:2 / 4:4:4 under p010le stay unmarked: the scaler from an 8-bit source is not built. */
 static void mark_planar_steps(hb_job_t *job, int from)
 {
     hb_list_t *list = job->list_filter;
     const AVPixFmtDescriptor *desc = av_pix_fmt_desc_get(job->input_pix_fmt);
-    if (!hbhip_host_planar_yuv(desc)) return;
+    const int planar = hbhip_host_planar_yuv(desc);
+    const int widens = job->input_pix_fmt == AV_PIX_FMT_YUV420P || job->input_pix_fmt == HBHIP_PIX_FMT_NV12;
+    if (!planar && !widens) return;
     for (int i = from > 1 ? from : 1; i < hb_list_count(list); i++)
     {
         hb_filter_object_t *f = hb_list_item(list, i);
@@ -121,9 +147,10 @@ static void mark_planar_steps(hb_job_t *job, int from)
         const char *key = NULL;
         if (hbhip_host_is_biplanar(fmt))
         {
-            if (desc->comp[0].depth >= (fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10)) key = HBHIP_FORMAT_PLANAR_STEP;
+            if (widens && fmt == HBHIP_PIX_FMT_P010LE) key = HBHIP_FORMAT_WIDEN_STEP;
+            else if (planar && desc->comp[0].depth >= (fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10)) key = HBHIP_FORMAT_PLANAR_STEP;
         }
-        else
+        else if (planar)
         {
             /* the up step: a planar YUV target that loses chroma samples in no dimension, gains them in one at least, and
              * is no shallower than the job's frames */
@@ -190,9 +217,10 @@ static void bracket_runs(hb_list_t *list, int from, int host_fmt)
         if (n >= least)
         {
             /* a run that ends in a marked `format=nv12 | p010le` entry leaves the device in that format */
-            const int step_fmt = planar_step_target(hb_list_item(list, last));
-            hb_list_insert(list, last + 1, new_adapter(HB_FILTER_HIP_DOWNLOAD, step_fmt != AV_PIX_FMT_NONE ? step_fmt : host_fmt));
-            hb_list_insert(list, i, new_adapter(HB_FILTER_HIP_UPLOAD, host_fmt));
+            int widen;
+            const int step_fmt = planar_step_target(hb_list_item(list, last), &widen);
+            hb_list_insert(list, last + 1, new_adapter(HB_FILTER_HIP_DOWNLOAD, step_fmt != AV_PIX_FMT_NONE ? step_fmt : host_fmt, widen));
+            hb_list_insert(list, i, new_adapter(HB_FILTER_HIP_UPLOAD, host_fmt, 0));
             last += 2;
         }
         i = last + 1;
@@ -234,15 +262,18 @@ int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
         hb_filter_close(&cpu);
         /* work.c drops the entry; a planar step that is not made leaves nothing for its download adapter to repack */
         hb_filter_object_t *next = hb_list_item(list, index + 1);
-        if (planar_step_target(f) != AV_PIX_FMT_NONE && next != NULL && next->id == HB_FILTER_HIP_DOWNLOAD &&
+        int widen;
+        if (planar_step_target(f, &widen) != AV_PIX_FMT_NONE && next != NULL && next->id == HB_FILTER_HIP_DOWNLOAD &&
             next->settings != NULL)
+        {
             hb_dict_remove(next->settings, "format");
+            hb_dict_remove(next->settings, HBHIP_FORMAT_WIDEN_STEP);       /* (they came together) */
+        }
         return 0;
     }
     hb_dict_free(&cpu->settings);
     cpu->settings = f->settings ? hb_value_dup(f->settings) : hb_dict_init();
-    hb_dict_remove(cpu->settings, HBHIP_FORMAT_PLANAR_STEP);  /* mark_planar_steps' keys are nothing the CPU filter knows */
-    hb_dict_remove(cpu->settings, HBHIP_FORMAT_UP_STEP);
+    remove_marks(cpu->settings);                              /* mark_planar_steps' keys are nothing the CPU filter knows */
     if (cpu->sub_filter != NULL)                              /* mt_frame wrapper: hb_add_filter_dict copies them down */
     {
         hb_dict_free(&cpu->sub_filter->settings);
@@ -279,16 +310,14 @@ int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
             ret = 2;                                          /* the CPU filter now sits one slot earlier */
         }
         else
-            hb_list_insert(list, pos++, new_adapter(HB_FILTER_HIP_DOWNLOAD, job_host_fmt(job)));
+            hb_list_insert(list, pos++, new_adapter(HB_FILTER_HIP_DOWNLOAD, job_host_fmt(job), 0));
     }
     hb_list_insert(list, pos, cpu);
     /* what follows may have lost the drop-in it stood behind: mark afresh, then bracket */
     for (int i = pos + 1; i < hb_list_count(list); i++)
     {
         hb_filter_object_t *g = hb_list_item(list, i);
-        if (g->id != HB_FILTER_FORMAT || g->settings == NULL) continue;
-        hb_dict_remove(g->settings, HBHIP_FORMAT_PLANAR_STEP);
-        hb_dict_remove(g->settings, HBHIP_FORMAT_UP_STEP);
+        if (g->id == HB_FILTER_FORMAT && g->settings != NULL) remove_marks(g->settings);
     }
     mark_planar_steps(job, pos + 1);
     bracket_runs(list, pos + 1, job_host_fmt(job));

@@ -154,6 +154,15 @@ int  hbhip_frame_upload_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *src
 int  hbhip_frame_download_biplanar(hbhip_frame *fr, const hbhip_host_biplanar *dst);
 int  hbhip_frame_upload_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *src, void **token);
 int  hbhip_frame_download_biplanar_async(hbhip_frame *fr, const hbhip_host_biplanar *dst, void **token);
+/* P010LE from an 8-bit frame - what a 10-bit hardware encoder is fed from an 8-bit title: `fr` is a planar 4:2:0 frame of
+ * depth 8, `dst` a P010LE host picture of its size, and every sample t of the three planes becomes the 16-bit word
+ * t | t << 8 (the byte twice: libswscale's unscaled yuv420p -> p010le), widened inside the merge kernel.
+ * Ordering, the token and what is written of `dst` are hbhip_frame_download_biplanar's, with P010LE's row bytes
+ * (2 * width, 4 * ceil(width / 2)).  HBHIP_ERR_UNSUPPORTED: a frame that is not 4:2:0 at depth 8, a width or height below
+ * 2; HBHIP_ERR_ARG: a plane that is missing or a stride below the row bytes.  The entry points above keep refusing a
+ * frame whose depth is not the picture's. */
+int  hbhip_frame_download_widen(hbhip_frame *fr, const hbhip_host_biplanar *dst);
+int  hbhip_frame_download_widen_async(hbhip_frame *fr, const hbhip_host_biplanar *dst, void **token);   /* finished with hbhip_frame_download_wait */
 
 /* ---- device surfaces: NV12 / P010LE pictures that already are, or stay, in HBM ------------------------------------------
  * What AMD's decoder hands out and AMF / VCE take in, without the host copy: a surface has a pitch of its own per plane
@@ -191,6 +200,15 @@ int  hbhip_frame_import_surface(hbhip_frame *fr, hbhip_surface *src);
 int  hbhip_frame_import_surface_async(hbhip_frame *fr, hbhip_surface *src, void **token);   /* finished with hbhip_ctx_upload_done */
 int  hbhip_frame_export_surface(hbhip_frame *fr, hbhip_surface *dst);
 int  hbhip_frame_export_surface_async(hbhip_frame *fr, hbhip_surface *dst, void **token);   /* finished with hbhip_frame_download_wait */
+/* The export of a planar 4:2:0 frame of depth 8 into a DEPTH-10 surface of its size, every sample t as t | t << 8
+ * (hbhip_frame_download_widen's arithmetic, one kernel, nothing over the bus).  What it writes of the surface and how it is
+ * ordered are hbhip_frame_export_surface's: [0, align16(row bytes)) of the sample rows, behind the frame's contents and every
+ * earlier import of the surface, and it is the surface's ready mark.  Refused before anything is queued -
+ * HBHIP_ERR_UNSUPPORTED: a frame that is not 4:2:0 at depth 8, a surface that is not depth 10 or is of another size, a width
+ * or height below 2; HBHIP_ERR_ARG: a surface of another GPU than the frame (pitches, addresses and overlap: what
+ * hbhip_surface_wrap admits). */
+int  hbhip_frame_export_surface_widen(hbhip_frame *fr, hbhip_surface *dst);
+int  hbhip_frame_export_surface_widen_async(hbhip_frame *fr, hbhip_surface *dst, void **token);   /* finished with hbhip_frame_download_wait */
 /* bytes the frame upload / download entry points (hbhip_frame_upload*, hbhip_frame_download*) have queued over the bus on
  * this context */
 int  hbhip_ctx_bus_bytes(hbhip_ctx *ctx, uint64_t *h2d, uint64_t *d2h);

@@ -16,6 +16,11 @@
   company-summarize TRACE.csv
                           per kernel [mean, min, median] µs: the surface kernels' first 64 launches (A) and next 64 (B), the
                           staging kernels of loop B
+  widen                   P010LE out of 16 resident 1080p frames a form, the forms alternated, two rounds: the 10-bit merges
+                          (bi_merge_kernel, bi_surface_merge_kernel on ten-bit frames) and the widening merge of 8-bit frames
+                          into the staging buffer and into a surface.  Under rocprofv3 as above
+  widen-summarize TRACE.csv
+                          per form [mean, min, median] µs and the widening forms over their siblings
   adapters [frames]       [upload, lapsharp, download] at 1080p through the plugin surface (a thread per filter, pinned
                           hb_buffer_t in and out, as handbrake_amd/hostpath.py runs its lists): NV12 in and out against
                           planar 8 bits, three runs each, alternated
@@ -145,6 +150,69 @@ def company_summarize(trace):
     print(json.dumps(out, indent=1))
 
 
+WIDEN_FRAMES, WIDEN_ROUNDS = 16, 2
+WIDEN_FORMS = ["bi_merge_kernel<uint16_t>", "widen, staging", "bi_surface_merge_kernel<uint16_t>", "widen, surface"]
+
+
+def widen():
+    """P010LE out of 1080p frames four ways, 16 resident frames a form, the forms alternated, two rounds behind one
+    warm-up launch a form: the 10-bit merges (ten-bit frames) and the widening merges (8-bit frames), into a host picture
+    of the staging layout and into a (256, 16) surface"""
+    from handbrake_amd import hip
+    L = hip.lib()
+    ctx = hip.Ctx(0)
+    w, h, n = 1920, 1080, WIDEN_FRAMES
+    rng = np.random.default_rng(1)
+    ch, cw = h // 2, w // 2
+    f8, f10 = [hip.Frame(ctx, w, h, 8) for _ in range(n)], [hip.Frame(ctx, w, h, 10) for _ in range(n)]
+    for k in range(n):
+        f8[k].upload([rng.integers(0, 256, s, dtype=np.uint8) for s in ((h, w), (ch, cw), (ch, cw))])
+        f10[k].upload([rng.integers(0, 1024, s).astype(np.uint16) for s in ((h, w), (ch, cw), (ch, cw))])
+    pitch = align64(2 * w)
+    host = np.zeros(pitch * (h + ch), dtype=np.uint8)
+    hb = hip.HostBiplanar()
+    hb.plane[0], hb.plane[1] = host.ctypes.data, host.ctypes.data + pitch * h
+    hb.stride[0] = hb.stride[1] = pitch
+    surface = hip.Surface(ctx, w, h, 10)
+    forms = [lambda k: L.hbhip_frame_download_biplanar(f10[k].h, C.byref(hb)),
+             lambda k: L.hbhip_frame_download_widen(f8[k].h, C.byref(hb)),
+             lambda k: L.hbhip_frame_export_surface(f10[k].h, surface.h),
+             lambda k: L.hbhip_frame_export_surface_widen(f8[k].h, surface.h)]
+    for form in forms:                                                      # code objects, the staging buffer
+        hip.check(form(0), ctx.h, "warm-up")
+    for _ in range(WIDEN_ROUNDS):
+        for form in forms:
+            for k in range(n):
+                hip.check(form(k), ctx.h, "widen")
+    surface.close()
+    for fr in f8 + f10:
+        fr.close()
+    ctx.close()
+
+
+def widen_summarize(trace):
+    """per form [mean, min, median] µs of its 2 x 16 timed launches, and the widening forms' means over their siblings'.
+    The two widening forms are one kernel on one grid: told apart by their place in widen()'s order."""
+    seq = {}
+    for r in sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"])):
+        m = re.search(r"bi_merge_kernel<|bi_surface_merge_kernel<|bi_widen_merge_kernel", r["Kernel_Name"])
+        if m:
+            seq.setdefault(m.group(0), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    n = WIDEN_FRAMES
+    wide = seq["bi_widen_merge_kernel"]
+    assert len(wide) == 2 + 2 * n * WIDEN_ROUNDS and all(len(seq[k]) == 1 + n * WIDEN_ROUNDS for k in ("bi_merge_kernel<", "bi_surface_merge_kernel<"))
+    timed = wide[2:]
+    per = {WIDEN_FORMS[0]: seq["bi_merge_kernel<"][1:], WIDEN_FORMS[2]: seq["bi_surface_merge_kernel<"][1:],
+           WIDEN_FORMS[1]: [t for r in range(WIDEN_ROUNDS) for t in timed[2 * n * r:2 * n * r + n]],
+           WIDEN_FORMS[3]: [t for r in range(WIDEN_ROUNDS) for t in timed[2 * n * r + n:2 * n * (r + 1)]]}
+    out = {k: {"mean_us": round(float(np.mean(per[k])), 2), "min_us": round(min(per[k]), 2),
+               "median_us": round(float(np.median(per[k])), 2),
+               "round_means_us": [round(float(np.mean(per[k][n * r:n * (r + 1)])), 2) for r in range(WIDEN_ROUNDS)]} for k in WIDEN_FORMS}
+    out["widen_over_sibling"] = {"staging": round(out[WIDEN_FORMS[1]]["mean_us"] / out[WIDEN_FORMS[0]]["mean_us"], 3),
+                                 "surface": round(out[WIDEN_FORMS[3]]["mean_us"] / out[WIDEN_FORMS[2]]["mean_us"], 3)}
+    print(json.dumps(out, indent=1))
+
+
 def adapters(n_in):
     from handbrake_amd import hbrt, hip, synth
     w, h, n_warm = 1920, 1080, 64
@@ -200,6 +268,10 @@ if __name__ == "__main__":
         company()
     elif mode == "company-summarize":
         company_summarize(sys.argv[2])
+    elif mode == "widen":
+        widen()
+    elif mode == "widen-summarize":
+        widen_summarize(sys.argv[2])
     elif mode == "adapters":
         adapters(int(sys.argv[2]) if len(sys.argv) > 2 else 1024)
     else:
