@@ -20,8 +20,10 @@
 //                      is saved by where the schedule keeps the map)
 //   k_dir_map4 / k_dir_map_c   the half-height pair as two launches (search distances beyond the LDS halo)
 //   k_filter_map       eedi2_filter_map                      :538-635
-//   k_mark_2x4         eedi2_upscale_by_2 (x3) :98-108 + eedi2_mark_directions_2x :787-858
-//   k_fill_gaps_b      eedi2_fill_gaps_2x                    :1025-1132
+//   k_mark_2x4         eedi2_upscale_by_2 :98-108 (srcp and mskp; dstp only where its doubled form is left to be seen:
+//                      without post-processing 1 / 3) + eedi2_mark_directions_2x :787-858
+//   k_fill_gaps_b      eedi2_fill_gaps_2x                    :1025-1132 (the rows it rebuilds; the rows every full-height map
+//                      pass only copies are written once per run: Eedi2Engine::enqueue_passes)
 //   k_lattice_cand_q / k_lattice_resolve   eedi2_interpolate_lattice   :1148-1335
 //   eedi_blur1 / eedi_derivatives / eedi_blur_sqrt2 / eedi_post_corner (eedi2_corner.h, shared with the 16-bit engine)
 //                      post-processing 2/3: eedi2_gaussian_blur1 :1391-1527, eedi2_calc_derivatives :1760-1848,
@@ -1367,7 +1369,8 @@ __device__ __forceinline__ void fe_expand_row(const uint32_t (*s_f)[FE_LW], int 
 }
 
 // POST (the pair in front of eedi2_post_process, :1349-1378, which rides along: it is pointwise in the map the pass has just made): d = where the filtered
-// map goes as well (the reference leaves it in dst2mp), f = the picture; the old map is the pass's own input, so the
+// map goes as well (the reference leaves it in dst2mp; only the rows of the lattice's parity of a plane with a mask - the
+// rest of d holds its peaks since k_mark_2x4, enqueue_passes), f = the picture; the old map is the pass's own input, so the
 // eedi2_bit_blit that keeps a copy of it is not needed - the caller has the input in the plane the copy would go to.
 template <int STEP, bool POST>
 __global__ __launch_bounds__(256) void k_dir_map_fe(P3 P, uint32_t padv)
@@ -1395,23 +1398,13 @@ __global__ __launch_bounds__(256) void k_dir_map_fe(P3 P, uint32_t padv)
                     {
                         const size_t at = (size_t)(STEP * (rb + lr) + i) * pitch + x;
                         *reinterpret_cast<uint32_t *>(Q.c + at) = pad_bytes(0xffffffffu, x, width, padv);
-                        if (POST && x < width) { const int out[4] = { PEAK, PEAK, PEAK, PEAK }; st4(Q.d + at, out, x, width); }
-                    }
+                    }                                                // (POST: d, dst2mp, is all peaks since k_mark_2x4 - enqueue_passes)
         return;
     }
     const int tid = threadIdx.y * 64 + threadIdx.x;
     if (tid == 0) s_count = 0;
     lim_fill(s_lim, tid);
-    // the rows between the lattice's: fetched now, stored at the end
-    constexpr int NCOPY = STEP == 1 ? 1 : (FE_R + 3) / 4;
-    uint32_t vcopy[NCOPY];
-    if (STEP != 1)
-#pragma unroll
-        for (int h = 0; h < NCOPY; h++)
-        {
-            const int lr = threadIdx.y + 4 * h, yc = 2 * (rb + lr) + 1 - par;
-            vcopy[h] = (lr < FE_R && yc < height && x < width) ? *reinterpret_cast<const uint32_t *>(Q.b + (size_t)yc * pitch + x) : 0u;
-        }
+    // (the rows between the lattice's, STEP 2: the pass's bit_blit of them - not fetched, see where they are stored)
     // SIDE 0: the whole dword; -1 / +1: the ring's dword left / right of the tile, of which only the pixel next to the tile
     // is ever read (half the vote)
     auto filtered = [&](int r, int xx, auto side) -> uint32_t {
@@ -1513,11 +1506,10 @@ __global__ __launch_bounds__(256) void k_dir_map_fe(P3 P, uint32_t padv)
         if (STEP != 1)
         {
             const int yc = 2 * (rb + lr) + 1 - par;
-            if (yc < height)
-            {
-                *reinterpret_cast<uint32_t *>(Q.c + (size_t)yc * pitch + x) = pad_bytes(vcopy[h < NCOPY ? h : 0], x, width, padv);
-                if (POST) put_d(yc, vcopy[h < NCOPY ? h : 0]);
-            }
+            // the row between two of the lattice's, which the pass only copies: in both _2x launches its pixels are the
+            // peaks of mark_directions_2x's memset in the input (enqueue_passes) - nothing to fetch; the constant goes to c,
+            // which no launch of the run has written before this one, and d (POST) has it already
+            if (yc < height) *reinterpret_cast<uint32_t *>(Q.c + (size_t)yc * pitch + x) = pad_bytes(0xffffffffu, x, width, padv);
         }
     }
 }
@@ -1727,18 +1719,22 @@ __device__ __forceinline__ uint32_t mark_pair(const Win12 &wa, const Win12 &wb)
     return out;
 }
 
-// a = msk2p, b = dmsk (tmp2p2), c = out (tmp2p)
-// Also performs the three eedi2_upscale_by_2 line doublings (:98-108, decomb_template.c:408-410):
-// g (srcp) -> d (dst2p), b (dstp, the half-height direction map) -> e (tmp2p2), a (mskp) -> f (msk2p).
+// mark_directions_2x and the eedi2_upscale_by_2 line doublings in front of it (:98-108, decomb_template.c:408-410).
+// a = mskp, b = dstp (the half-height direction map), g = srcp; c = out (the marked map: dst2mp, see enqueue_passes);
+// d = dst2p, e = the doubled direction map (OMSK only), f = msk2p; `height` = full height.
+// The doublings: a (mskp) -> f (msk2p) and g (srcp) -> d (dst2p), every row; b (dstp) -> e with OMSK - without
+// post-processing 1 / 3 the doubled map is what tmp2p2 ends as, with it
+// the plane it would go to (tmp2p) is overwritten whole by k_dir_map_fe<2, true> and its one reader in between,
+// k_lattice_cand_q, takes dstp's rows itself: no store.
 // The rows y-1 / y+1 of the doubled maps that mark_directions reads are rows (y-1)>>1 / (y+1)>>1 of
 // the half-height ones, so it reads those directly and no separate upscale launch is needed.
-// a = mskp, b = dstp, c = out (tmp2p), g = srcp; `height` = full height.
 
 // Four pixels per thread (see k_dir_map4): the three line doublings are dword copies, and only the
 // rows mark_directions_2x rebuilds (every other one) load the two neighbouring half-height rows.
-// A thread takes the rows 2r and 2r + 1 of its dword column: both are doubled from half-height row r (three loads for six
-// stores), one of them at most is a row mark_directions_2x rebuilds, the other is the memset's 255 - a wave of its own
-// per row spent more scalar instructions on finding its plane and field than vector ones on its dword.
+// A thread takes the rows 2r and 2r + 1 of its dword column: both are doubled from half-height row r (three loads for
+// four or six stores), one of them at most is a row mark_directions_2x rebuilds, the other is the memset's 255 - a wave
+// of its own per row spent more scalar instructions on finding its plane and field than vector ones on its dword.
+template <bool OMSK>
 __global__ __launch_bounds__(256) void k_mark_2x4(P3 P, uint32_t padv)
 {
     FIELD_PLANE(P);
@@ -1774,14 +1770,19 @@ __global__ __launch_bounds__(256) void k_mark_2x4(P3 P, uint32_t padv)
         wbn = ldwin(Q.b + (ptrdiff_t)((y + 1) >> 1) * pitch + x);
     }
     {
+        // (Both rows of dst2p, although interpolate_lattice assigns every pixel of a rebuilt row afterwards: its short search
+        // reads flat, dstpnn[x - u -+ 1] with |u| <= 4 unclamped on that side (:1297-1310) - the last dword of this row's
+        // pitch and the first of the next rebuilt row, still doubled when the reference gets there - so the ends of such a
+        // row and its padding have to be stored anyway, and storing only those measured no faster than storing the row:
+        // DESIGN.md 4.2.5.)
         *reinterpret_cast<uint32_t *>(Q.d + fs) = vg;
-        *reinterpret_cast<uint32_t *>(Q.e + fs) = vb;
         *reinterpret_cast<uint32_t *>(Q.f + fs) = va;
+        if (OMSK) *reinterpret_cast<uint32_t *>(Q.e + fs) = vb;
         if (two)
         {
             *reinterpret_cast<uint32_t *>(Q.d + fs + pitch) = vg;
-            *reinterpret_cast<uint32_t *>(Q.e + fs + pitch) = vb;
             *reinterpret_cast<uint32_t *>(Q.f + fs + pitch) = va;
+            if (OMSK) *reinterpret_cast<uint32_t *>(Q.e + fs + pitch) = vb;
         }
     }
     // memset(dstp, 255, pitch*height); padv: what the rows' padding gets (0 when the map goes to the plane the fused dir-map
@@ -1819,7 +1820,8 @@ __global__ __launch_bounds__(256) void k_mark_2x4(P3 P, uint32_t padv)
 //   3. the list is worked off one gap pixel per thread; a walk reads LDS while it stays inside the staged span and
 //      falls back to memory beyond it (rare);
 //   4. the output row leaves as dwords.
-// Rows the pass does not rebuild are only copied (the reference's bit_blit), decided per workgroup.
+// Rows the pass does not rebuild are only copied by the reference (its bit_blit): peaks onto the peaks c holds already,
+// so they are neither read nor written here, and a plane without a mask pixel is left alone altogether.
 // (Tried and dropped: four pixels per thread without compaction - nearly every wave then pays four serial walks, 45 us
 // against 29; the walk on LDS without compaction, 38 us.)
 #ifndef FG_WIDTH
@@ -1857,33 +1859,10 @@ __global__ __launch_bounds__(FG_T) void k_fill_gaps_b(P3 P)
     if (ya >= height || x0 >= width) return;
     const int yb = ya + (y0 & 1);                                  // its rows of the rebuilt parity: yb, yb + 2, ..
     const int x = x0 + 4 * tid;
-    if (maskless)
-    {
-        // no mask pixel in the plane, no gap to fill (:1048-1050): the pass is its bit_blit of a map of peaks (k_dir_map4)
-        if (x + 3 < width)
-        {
-#pragma unroll
-            for (int i = 0; i < 2 * FG_R && ya + i < height; i++)
-                *reinterpret_cast<uint32_t *>(Q.c + (size_t)(ya + i) * pitch + x) = 0xffffffffu;
-        }
-        else if (x < width)
-            for (int i = 0; i < 2 * FG_R && ya + i < height; i++)
-                for (int k = 0; k < 4 && x + k < width; k++) Q.c[(size_t)(ya + i) * pitch + x + k] = (uint8_t)PEAK;
-        return;
-    }
+    // c holds the peaks of the rows this pass only copies, and of every row of a plane without a mask pixel, before the
+    // launch (enqueue_passes): those rows are neither read nor written, and a workgroup with no other row has nothing to do
+    if (maskless || yb >= height - 1) return;
     auto rebuilt = [&](int y) { return y >= y0 && y < height - 1; };
-    // the rows that are only copied (the reference's bit_blit): the other parity, and what lies outside y0 .. height - 2
-    uint32_t vcopy[2 * FG_R] = {};
-    if (x < width)                                                 // (the lane's test once, the rows' tests are uniform)
-    {
-#pragma unroll
-        for (int i = 0; i < 2 * FG_R; i++)
-        {
-            const int y = ya + i;
-            if (y < height && !((((y - y0) & 1) == 0) && rebuilt(y)))
-                vcopy[i] = *reinterpret_cast<const uint32_t *>(Q.b + (size_t)y * pitch + x);
-        }
-    }
     if (tid == 0) s_count = 0;
     const int lo = x0 - FG_HALO;                                   // column of staged byte 0 (a multiple of 4)
     const int ndw = (min(FG_W, hbhip_align_up_dev(width - x0, 4)) + 2 * FG_HALO) / 4;
@@ -1930,7 +1909,7 @@ __global__ __launch_bounds__(FG_T) void k_fill_gaps_b(P3 P)
     for (int r = 0; r < FG_R; r++)
     {
         const int y = yb + 2 * r;
-        if (y < height && rebuilt(y))                                           // (rows that are copied have their dword in vcopy)
+        if (rebuilt(y))                                                         // (nothing is done for a row that is only copied)
         {
             uint32_t gap = 0u;
             if (x < width)
@@ -2097,23 +2076,21 @@ __global__ __launch_bounds__(FG_T) void k_fill_gaps_b(P3 P)
     __syncthreads();
     // (the row loop inside the lane's one test of the row's end, not that test inside the loop: a divergent branch per
     // row cost the scalar unit as much as the rows' stores cost the vector unit)
-    auto out_word = [&](int i) -> uint32_t {
-        const int y = ya + i;
-        const bool work = (((y - y0) & 1) == 0) && rebuilt(y);
-        return work ? *reinterpret_cast<const uint32_t *>(&s_out[(i - (y0 & 1)) >> 1][4 * tid]) : vcopy[i];
-    };
+    // only the rows the pass rebuilds: the others hold their peaks in c already (above)
     if (x + 3 < width)
     {
 #pragma unroll
-        for (int i = 0; i < 2 * FG_R && ya + i < height; i++)
-            *reinterpret_cast<uint32_t *>(Q.c + (size_t)(ya + i) * pitch + x) = out_word(i);
+        for (int r = 0; r < FG_R; r++)
+            if (rebuilt(yb + 2 * r))
+                *reinterpret_cast<uint32_t *>(Q.c + (size_t)(yb + 2 * r) * pitch + x) = *reinterpret_cast<const uint32_t *>(&s_out[r][4 * tid]);
     }
     else if (x < width)
     {
-        for (int i = 0; i < 2 * FG_R && ya + i < height; i++)
+        for (int r = 0; r < FG_R; r++)
         {
-            const uint32_t v = out_word(i);
-            uint8_t *o = Q.c + (size_t)(ya + i) * pitch + x;
+            if (!rebuilt(yb + 2 * r)) continue;
+            const uint32_t v = *reinterpret_cast<const uint32_t *>(&s_out[r][4 * tid]);
+            uint8_t *o = Q.c + (size_t)(yb + 2 * r) * pitch + x;
             for (int k = 0; k < 4 && x + k < width; k++) o[k] = (uint8_t)(v >> (8 * k));
         }
     }
@@ -2354,7 +2331,8 @@ __device__ __forceinline__ uint32_t lattice_stage_c(const uint8_t *top, const ui
 // k_lattice_resolve (one wavefront per row): resolves which outcome each pixel takes —
 // that depends on the value just written at x-1 (:1194) — with a 64-lane prefix composition
 // of 2-state maps, carrying the last written value from chunk to chunk, then writes the row.
-// a = dmsk (tmp2p, in/out), b = dst (dst2p, in/out), c = omsk (tmp2p2).
+// a = dmsk (the direction map, in/out), b = dst (dst2p, in/out), c = dstp: the half-height direction map, whose row
+// Y >> 1 is row Y of the reference's omsk (k_lattice_cand_q only; k_lattice_resolve does not look at c).
 constexpr int LC_HALO = 40;   // |u| <= 34, +-1 for the triples, rounded to dwords
 
 
@@ -2386,8 +2364,14 @@ __global__ __launch_bounds__(256) void k_lattice_cand_q(P3 P, uint32_t *__restri
     if (t < 3) s_count[t] = 0;
     lim_fill(s_lim, t);
     {
+        // omsk's rows y - 1 / y + 1 (:1233-1335) are the doubled half-height direction map's: rows (y - 1) >> 1 and
+        // (y + 1) >> 1 of dstp, read where they are (as k_mark_2x4 reads them).  The staged halo runs past both ends of a
+        // row, and flat addressing finds another neighbouring row there in dstp than in the doubled plane - bytes no
+        // result sees: every omsk index of the searches is x -+ 1 -+ u, x -+ (u >> 1) or x -+ ((u + 1) >> 1) with u clamped
+        // to -x + 1 .. x - 1 and x - width + 2 .. width - 2 - x (:1244-1247), so it stays inside 0 .. width - 1, and the
+        // sixth step the window form evaluates beside the loop's five is discarded whole (lattice_stage_b_win).
         const uint8_t *g[5] = { Q.b + (size_t)(y - 1) * pitch, Q.b + (size_t)(y + 1) * pitch,
-                                Q.c + (size_t)(y - 1) * pitch, Q.c + (size_t)(y + 1) * pitch,
+                                Q.c + (size_t)((y - 1) >> 1) * pitch, Q.c + (size_t)((y + 1) >> 1) * pitch,
                                 Q.a + (size_t)y * pitch };
         // only as far right as the row's pixels (+ halo) reach
         const int need4 = (min(LQ_W, hbhip_align_up_dev(width - x0, 4)) + 2 * LC_HALO) / 4;
@@ -3184,13 +3168,33 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
     // reference has it write the new map over it, with the eedi2_bit_blit in front keeping a copy in tmp2p2
     // (decomb_template.c:426-429); one launch cannot read a plane's neighbourhoods and write that plane.  So with that pair
     // to come the two planes change places from mark_directions_2x on: the direction map lives in tmp2p2 - where the copy
-    // would go: no blit - and the doubled half-height map (the lattice's omsk, dead behind it) in tmp2p, which the fused pass
-    // then overwrites with the new map.  Every plane ends as the reference leaves it, the padding of its rows included.
+    // would go: no blit - and the doubled half-height map (the lattice's omsk, dead behind it) would go to tmp2p, which the
+    // fused pass then overwrites with the new map: it is not stored at all (3. below).  Every plane ends as the reference
+    // leaves it, the padding of its rows included.
     const bool post1 = par_.post_processing == 1 || par_.post_processing == 3;
     const EediFrame &map2 = post1 ? tmp2p2 : tmp2p, &omsk2 = post1 ? tmp2p : tmp2p2;
+    //
+    // WHO FILLS WHICH ROWS (DESIGN.md 4.2.5 has the table).  Of a full-height plane, the rows y0, y0 + 2, .. <= height - 2
+    // (y0 = 2 - tff) are the REBUILT rows; the others - the other parity, and row 0 or height - 1 of the rebuilt one -
+    // are COPY rows: every _2x map pass only carries them along (its bit_blit).  The launches below rely on:
+    //   1. dst2mp: k_mark_2x4 writes every byte of the plane, 255 into the pixels (x < width) of its copy rows - and into
+    //      every row of a plane without a mask pixel (`maskless`).  No later launch stores anything else there: the first
+    //      k_fill_gaps_b and k_dir_map_fe<2, true> leave those rows (those planes) alone instead of storing 255 again.
+    //   2. map2: k_dir_map_fe<2, false> writes every byte of the plane, 255 into the pixels of its copy rows (a constant,
+    //      not a load from dst2mp) and of every row of a maskless plane.  The second k_fill_gaps_b, k_lattice_resolve and
+    //      k_dir_map_fe<2, true> count on it: the first stores rebuilt rows only, the last takes its input's copy rows as 255.
+    //   3. tmp2p with post-processing 1 / 3: written by nobody before k_dir_map_fe<2, true>, which writes every byte of
+    //      it.  (It would hold the doubled dstp for k_lattice_cand_q, which reads dstp's rows itself.)  Without that
+    //      post-processing the doubled map is what tmp2p2 ends as, and k_mark_2x4<true> stores it.
+    // (dst2p and msk2p are doubled whole: the lattice assigns every pixel of dst2p's rebuilt rows, but reads their ends flat
+    // before it does - k_mark_2x4.)
+    // All of this happens anew in every run, before the first launch that relies on it, so what a slot holds from an
+    // earlier run - another parity, a plane that had a mask then - never shows.  Whoever moves a launch, or lets one skip
+    // a plane, has to keep 1 - 3 or store those rows again.
     bind(P.d, dst2p); bind(P.e, omsk2); bind(P.f, msk2p); bind(P.c, dst2mp);
-    HBHIP_LAUNCH_ON(lc, st, "eedi2_mark_directions_2x", k_mark_2x4,                                      // a thread row per PAIR of full-height rows
-                 dim3(hbhip_grid_x((dst2p.stride[0] + 255) / 256), ((dst2p.height[0] + 1) / 2 + 3) / 4, gz), blk, 0, P, 0u);
+    const dim3 mk_grid(hbhip_grid_x((dst2p.stride[0] + 255) / 256), ((dst2p.height[0] + 1) / 2 + 3) / 4, gz);   // a thread row per PAIR of full-height rows
+    if (post1) HBHIP_LAUNCH_ON(lc, st, "eedi2_mark_directions_2x", k_mark_2x4<false>, mk_grid, blk, 0, P, 0u);
+    else HBHIP_LAUNCH_ON(lc, st, "eedi2_mark_directions_2x", k_mark_2x4<true>, mk_grid, blk, 0, P, 0u);
     const dim3 fe2_grid(hbhip_grid_x((dst2p.stride[0] + 255) / 256), ((dst2p.height[0] + 1) / 2 + FE_R - 1) / FE_R, gz);
     bind(P.a, msk2p); bind(P.b, dst2mp); bind(P.c, map2);
     HBHIP_LAUNCH_ON(lc, st, "eedi2_filter_expand_dir_map_2x", (k_dir_map_fe<2, false>), fe2_grid, blk, 0, P, post1 ? 0u : 0xffffffffu);
@@ -3201,8 +3205,9 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
     HBHIP_LAUNCH_ON(lc, st, "eedi2_fill_gaps_2x", k_fill_gaps_b, fg_grid, dim3(FG_T), 0, P);
     bind(P.a, msk2p); bind(P.b, dst2mp); bind(P.c, map2);
     HBHIP_LAUNCH_ON(lc, st, "eedi2_fill_gaps_2x", k_fill_gaps_b, fg_grid, dim3(FG_T), 0, P);
-    // lattice
-    bind(P.a, map2); bind(P.b, dst2p); bind(P.c, omsk2);
+    // lattice (its omsk rows out of dstp, the half-height map, which is as filter_map left it: a half-height plane has the
+    // pitch of its full-height twin)
+    bind(P.a, map2); bind(P.b, dst2p); bind(P.c, dstp);
     {
         const int nrows = (dst2p.height[0] - 1) / 2;      // rows y0, y0 + 2, ... < height - 1 for either parity (the heights are even)
         const int nt = par_.noise_threshold;
