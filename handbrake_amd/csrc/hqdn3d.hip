@@ -1,9 +1,17 @@
-// hqdn3d.hip — hqdn3d spatial/temporal IIR denoiser for gfx950 (8-bit).
+// hqdn3d.hip — hqdn3d spatial/temporal IIR denoiser for gfx950: bytes (8-bit) and 16-bit containers (10 / 12-bit),
+// every kernel a template on the sample type and the LOAD / STORE shift.
 //
-//   hqdn3d_h_kernel    horizontal recurrence of hqdn3d_denoise_spatial   libhb/denoise.c:126-165
-//   hqdn3d_vt_kernel   its vertical recurrence + the temporal step, and the
-//                      first-frame seeding of hqdn3d_denoise_depth       :167-201
-//   hqdn3d_t_kernel    hqdn3d_denoise_temporal (spatial strength 0)      :102-124
+//   frame-at-a-time (Hqdn3dFilter::one_frame)
+//   hqdn3d_h_kernel        horizontal recurrence of hqdn3d_denoise_spatial   libhb/denoise.c:126-165
+//   hqdn3d_vt_kernel       its vertical recurrence + the temporal step, and the
+//                          first-frame seeding of hqdn3d_denoise_depth       :167-201
+//   hqdn3d_t_kernel        hqdn3d_denoise_temporal (spatial strength 0)      :102-124
+//   up to HQ_BATCH frames per launch (Hqdn3dFilter::process_many)
+//   hqdn3d_h_batch_kernel  the horizontal recurrence of every frame of the batch, longer segments
+//   hqdn3d_v_batch_kernel  the vertical recurrence alone: its results to `vsp`, no temporal step
+//   hqdn3d_tn_kernel       the temporal step of the batch, frame after frame per sample, with or without
+//                          a spatial filter on the plane
+//   hq_h_rows / hq_v_cols  the bodies the two forms share
 //
 // The reference fuses three first-order recurrences in one raster scan.  They are
 // separable: x-recurrence per row (rows in parallel), then y-recurrence per column on
@@ -409,7 +417,7 @@ __global__ __launch_bounds__(256) void hqdn3d_tn_kernel(HqBatch B)
         {
             const uint16_t *v = B.vsp[c] + (size_t)f * B.stride[c] + at;
 #pragma unroll
-            for (int k = 0; k < 4; k++) cur[f][k] = x0 + 256 * k < w ? v[256 * k] : 0u;
+            for (int k = 0; k < 4; k++) cur[f][k] = x0 + 256 * k < w ? v[256 * k] : 0x8000u;   // (idle lanes: mid-range, see `far`)
         }
         else
         {
@@ -432,6 +440,42 @@ __global__ __launch_bounds__(256) void hqdn3d_tn_kernel(HqBatch B)
     }
     stage_lut(lut_t, B.temporal[c], 256);
     __syncthreads();
+    // `vsp` holds the vertical result as the NEXT ROW sees it, through the reference's uint16 line buffer; its
+    // temporal step takes the 32-bit value (denoise.c:126-165).  A step ends at most 7 past the farther of
+    // (state, sample), so a column just under the top of the range can climb past 65535 - at every depth: 12-bit
+    // samples of 4095 do it on flat content, 10-bit ones need a column a few codes under 1023 - and a wrapped
+    // state may step below 0 under a small sample.  The 32-bit value is then within 7 of 0 or 65536: only
+    // there (16, for margin) is it rebuilt, exactly: it is the h-filtered sample, which always fits 16 bits
+    // (row samples sit on one lattice mod 16, a row state never leaves the 16-block of its farther end), plus
+    // an int16 table entry, so the low 16 bits and that sample give all 32 back.
+    // One test for the whole thread first (a maximum over its samples, no branch in the chains below): ordinary 8- and
+    // 10-bit content never gets near either end (their smallest states are 127 and 31).
+    if (spatial)
+    {
+        uint32_t far = 0;
+#pragma unroll
+        for (int f = 0; f < HQ_BATCH; f++)
+        {
+            if (f >= B.n) continue;
+#pragma unroll
+            for (int k = 0; k < 4; k++) far = max(far, cur[f][k] - 16u);
+        }
+        if (far >= 65536u - 32u)
+        {
+#pragma unroll
+            for (int f = 0; f < HQ_BATCH; f++)
+            {
+                if (f >= B.n) continue;
+#pragma unroll
+                for (int k = 0; k < 4; k++)
+                    if (cur[f][k] - 16u >= 65536u - 32u && x0 + 256 * k < w)
+                    {
+                        const uint32_t hv = B.hbuf[c][(size_t)f * B.stride[c] + at + 256 * k];
+                        cur[f][k] = (uint32_t)((int)hv + (int)(int16_t)(uint16_t)(cur[f][k] - hv));
+                    }
+            }
+        }
+    }
 #pragma unroll
     for (int f = 0; f < HQ_BATCH; f++)
     {
@@ -440,8 +484,11 @@ __global__ __launch_bounds__(256) void hqdn3d_tn_kernel(HqBatch B)
 #pragma unroll
         for (int k = 0; k < 4; k++)
         {
-            prev[k] = (uint32_t)(uint16_t)lowpass((int)prev[k], (int)cur[f][k], lut_t);
-            if (x0 + 256 * k < w) d[256 * k] = (PIX)(prev[k] >> SH);
+            // the state is kept in 16 bits, the sample is STOREd from all 32 (:102-124; 4096 for a 12-bit sample where
+            // the step lands past 65535, as hqdn3d_vt_kernel and hqdn3d_t_kernel write it)
+            const uint32_t t = lowpass((int)prev[k], (int)cur[f][k], lut_t);
+            prev[k] = (uint32_t)(uint16_t)t;
+            if (x0 + 256 * k < w) d[256 * k] = (PIX)(t >> SH);
         }
     }
 #pragma unroll
