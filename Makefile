@@ -18,7 +18,8 @@ HIP_HDR := $(wildcard $(PKG)/csrc/*.h) $(wildcard include/*.h)
 FLT_SRC := $(wildcard $(PKG)/libhb/*_hip.c) $(PKG)/libhb/hbhip_registry.c $(PKG)/libhb/hip_common.c $(PKG)/libhb/vfr_standin.c
 
 all: product oracle
-product: $(PKG)/libhbrt.so $(PKG)/libhbhip.so $(PKG)/libhbhip_filters.so tools/vote_avg_check tools/dirmap_vote_check tools/lapsharp_rowdot_check tools/format_nominal_check
+product: $(PKG)/libhbrt.so $(PKG)/libhbhip.so $(PKG)/libhbhip_filters.so tools/vote_avg_check tools/dirmap_vote_check tools/lapsharp_rowdot_check tools/format_nominal_check \
+         tools/chroma_siting_check tools/libcolorspace_sited_check.so
 
 # lapsharp's byte dot products run on the HOST (tests/test_lapsharp_rowdot_cpu.py)
 tools/lapsharp_rowdot_check: tools/lapsharp_rowdot_check.hip $(PKG)/csrc/lapsharp_rowdot.h
@@ -27,6 +28,15 @@ tools/lapsharp_rowdot_check: tools/lapsharp_rowdot_check.hip $(PKG)/csrc/lapshar
 # the format scaler's table builder run on the HOST (tests/test_format_nominal_cpu.py)
 tools/format_nominal_check: tools/format_nominal_check.hip $(PKG)/csrc/sws_filter.h
 	$(HIPCC) --offload-arch=$(ARCH) -O2 -ffp-contract=off -fno-fast-math -I$(PKG)/csrc $< -o $@
+
+# the chroma siting rule of crop/scale and colorspace run on the HOST (tests/test_chroma_siting_cpu.py)
+tools/chroma_siting_check: tools/chroma_siting_check.hip $(PKG)/csrc/chroma_siting.h
+	$(HIPCC) --offload-arch=$(ARCH) -O2 -ffp-contract=off -fno-fast-math -I$(PKG)/csrc $< -o $@
+
+# the colour conversion's checker with the two siting axes: the oracle's file, included unchanged, and one more frame
+# loop (tests/colorspace_sited_lib.py loads it; test infrastructure, nothing of the product links it)
+tools/libcolorspace_sited_check.so: tools/colorspace_sited_check.c oracle/colorspace_oracle.c oracle/oracle.h
+	$(CC) -std=gnu99 -O2 -g -fPIC -ffp-contract=off -Wall -Wno-unused-function -Ioracle -shared -o $@ $< -lm
 
 # GPU-side exhaustive check of a device function shared with the kernels (tests/test_eedi2_gpu.py runs it)
 tools/vote_avg_check: tools/vote_avg_check.hip $(PKG)/csrc/eedi2_vote.h $(PKG)/csrc/eedi2_dirmap_vote.h

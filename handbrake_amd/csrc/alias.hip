@@ -22,6 +22,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "chroma_siting.h"
 #include "dot2.h"
 #include "sws_filter.h"
 
@@ -1055,14 +1056,18 @@ public:
             crop_w[c] = c ? -((-cw) >> lw) : cw;
             crop_h[c] = c ? -((-ch) >> lh) : ch;
             const int dw = out_geo.pw[c], dh = out_geo.ph[c];
-            // left-sited chroma: 0.25 * (1 - src/dst) of a chroma sample, horizontally only
-            const double sx = (c && lw) ? 0.25 * (1.0 - (double)cw / (double)out_geo.width) : 0.0;
-            identity[c] = (dw == crop_w[c] && dh == crop_h[c] && (sws || sx == 0.0));
+            // chroma as the stream sites it (chroma_siting.h): left-sited 0.25 * (1 - src/dst) of a chroma sample
+            // horizontally and nothing vertically, top-sited the same expression vertically, bottom its negative
+            const double sx = c ? chroma_resize_shift_x(chroma_location, lw, cw, out_geo.width) : 0.0;
+            const double sy = c ? chroma_resize_shift_y(chroma_location, lh, ch, out_geo.height) : 0.0;
+            identity[c] = (dw == crop_w[c] && dh == crop_h[c] && (sws || (sx == 0.0 && sy == 0.0)));
             if (identity[c]) continue;
             if (sws)
             {
                 // libswscale's tables: positions + 14-bit (horizontal) / 12-bit (vertical) coefficients; left-sited chroma
-                // at horizontal position 0 (srcPos = dstPos = 64), everything else centred (128)
+                // at horizontal position 0 (srcPos = dstPos = 64), everything else centred (128).  This branch stays
+                // left-sited whatever chroma_location says: how vf_scale turns a frame's location into these positions
+                // is not restated here
                 std::vector<int> px, py;
                 std::vector<short> qx, qy;
                 const int hpos = (c && lw) ? 64 : 128;
@@ -1079,7 +1084,7 @@ public:
             std::vector<int> ix, iy, bx, by;
             std::vector<double> cx, cy;
             tx[c] = lanczos_table(crop_w[c], dw, sx, ix, cx, &bx);
-            ty[c] = lanczos_table(crop_h[c], dh, 0.0, iy, cy, &by);
+            ty[c] = lanczos_table(crop_h[c], dh, sy, iy, cy, &by);
             int rc = upload(d_iy[c], iy);
             if (rc != HBHIP_OK) return rc;
             {
@@ -1236,6 +1241,7 @@ public:
     bool sws = false;           // libswscale's arithmetic (the reference's path for odd sizes) instead of zimg's
     bool up6 = true;            // six taps either way and every tile fits the fused kernel's LDS frame
     bool tall = true;           // ... also at 32 rows per tile
+    int chroma_location = CHROMA_LOC_LEFT;      // AVCHROMA_LOC_*: where the chroma samples sit (zimg form only)
     hbhip_cropscale_params par;
     int crop_x[3], crop_y[3], crop_w[3], crop_h[3], tx[3] = {0, 0, 0}, ty[3] = {0, 0, 0};
     bool identity[3] = {false, false, false};
@@ -1376,22 +1382,31 @@ extern "C" int hbhip_grayscale_create(hbhip_ctx *ctx, double cb, double cr, doub
 }
 
 static int cropscale_create(hbhip_ctx *ctx, const hbhip_cropscale_params *p, int width, int height,
-                            int depth, int log2_chroma_w, int log2_chroma_h, bool sws, hbhip_filter **out);
+                            int depth, int log2_chroma_w, int log2_chroma_h, bool sws, int chroma_location, hbhip_filter **out);
 
 extern "C" int hbhip_cropscale_create(hbhip_ctx *ctx, const hbhip_cropscale_params *p, int width, int height,
                                       int depth, int log2_chroma_w, int log2_chroma_h, hbhip_filter **out)
 {
-    return cropscale_create(ctx, p, width, height, depth, log2_chroma_w, log2_chroma_h, false, out);
+    return cropscale_create(ctx, p, width, height, depth, log2_chroma_w, log2_chroma_h, false, CHROMA_LOC_LEFT, out);
+}
+
+extern "C" int hbhip_cropscale_create_sited(hbhip_ctx *ctx, const hbhip_cropscale_params *p, int width, int height,
+                                            int depth, int log2_chroma_w, int log2_chroma_h, int chroma_location,
+                                            hbhip_filter **out)
+{
+    if (out) *out = nullptr;
+    if (!chroma_loc_valid(chroma_location)) return HBHIP_ERR_ARG;
+    return cropscale_create(ctx, p, width, height, depth, log2_chroma_w, log2_chroma_h, false, chroma_location, out);
 }
 
 extern "C" int hbhip_cropscale_sws_create(hbhip_ctx *ctx, const hbhip_cropscale_params *p, int width, int height,
                                           int depth, int log2_chroma_w, int log2_chroma_h, hbhip_filter **out)
 {
-    return cropscale_create(ctx, p, width, height, depth, log2_chroma_w, log2_chroma_h, true, out);
+    return cropscale_create(ctx, p, width, height, depth, log2_chroma_w, log2_chroma_h, true, CHROMA_LOC_LEFT, out);
 }
 
 static int cropscale_create(hbhip_ctx *ctx, const hbhip_cropscale_params *p, int width, int height,
-                            int depth, int log2_chroma_w, int log2_chroma_h, bool sws, hbhip_filter **out)
+                            int depth, int log2_chroma_w, int log2_chroma_h, bool sws, int chroma_location, hbhip_filter **out)
 {
     if (!ctx || !p || !out) return HBHIP_ERR_ARG;
     *out = nullptr;
@@ -1401,6 +1416,7 @@ static int cropscale_create(hbhip_ctx *ctx, const hbhip_cropscale_params *p, int
     CropScaleFilter *f = new (std::nothrow) CropScaleFilter(ctx, *p);
     if (!f) return HBHIP_ERR_NOMEM;
     f->sws = sws;
+    f->chroma_location = chroma_location;
     PicGeometry gi, go;
     gi.set(width, height, depth, log2_chroma_w, log2_chroma_h);
     go.set(p->width, p->height, depth, log2_chroma_w, log2_chroma_h);

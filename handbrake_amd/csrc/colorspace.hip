@@ -17,6 +17,7 @@
 // the converted Cb'/Cr' of the region in LDS (16 KB), writes luma straight out and then decimates chroma from LDS.
 // HBM traffic is the input frame once and the output frame once.
 #include "hbhip_internal.h"
+#include "chroma_siting.h"
 
 #include <cmath>
 #include <cstring>
@@ -355,13 +356,22 @@ __device__ __forceinline__ float samp(const uint8_t *row, int x) { return (float
 // PLAN = CsPlanWide: the constant-luminance / ICtCp instantiation (LINEAR always).  Left alone it takes 87 VGPRs where
 // chroma is subsampled horizontally, five waves a SIMD against its LINEAR sibling's six; held to six it spills four to
 // six VGPRs and is 4 % faster (profiles/colorspace_wide.json).  The other instantiations compile as without the hint.
-template <typename PIX, int SUBW, int SUBH, bool LINEAR, typename PLAN = CsPlan>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(std::is_same<PLAN, CsPlanWide>::value ? 6 : 1)))
+// HCEN / VCOS: where the chroma samples sit (chroma_siting.h).  A subsampled direction is co-sited (up 2k: c[k], 2k + 1:
+// c[k] / 2 + c[k+1] / 2; down 2k - 1 .. 2k + 1 with 1/4 1/2 1/4) or centred (up 2k: c[k-1] / 4 + 3 c[k] / 4, 2k + 1:
+// 3 c[k] / 4 + c[k+1] / 4; down 2k - 1 .. 2k + 2 with 1/8 3/8 3/8 1/8).  Without the two flags columns are co-sited and
+// rows centred (MPEG-2 siting: locations 0, 1, 5), and those instantiations compile as before there were flags.  HCEN:
+// columns centred - a fourth chroma column under four positions (k - 1 .. k + 2) and, for the decimation's tap 2k + 2,
+// HXR = 4 columns of apron on the right as well (a 56 x 30 tile).  VCOS: rows co-sited - other weights, and a tap less
+// going down; the rows above and below the tile are the same ones.  The LINEAR forms with HCEN take 102 VGPRs left alone
+// (four waves a SIMD); held to six waves like the wide ones they spill 15 to 18 dwords and are 8 % faster.
+template <typename PIX, int SUBW, int SUBH, bool LINEAR, typename PLAN = CsPlan, bool HCEN = false, bool VCOS = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(std::is_same<PLAN, CsPlanWide>::value || (HCEN && LINEAR) ? 6 : 1)))
 void colorspace_kernel(CsBatch a, PLAN p)
 {
-    constexpr int HX = SUBW ? 4 : 0, HY = SUBH ? 1 : 0, TW = CS_RW - HX, TH = CS_RH - 2 * HY;
+    static_assert((!HCEN || SUBW) && (!VCOS || SUBH), "a siting only where the direction is subsampled");
+    constexpr int HX = SUBW ? 4 : 0, HXR = HCEN ? 4 : 0, HY = SUBH ? 1 : 0, TW = CS_RW - HX - HXR, TH = CS_RH - 2 * HY;
     constexpr bool LDS = SUBW || SUBH;
-    constexpr int NC = SUBW ? 3 : 4;                               // chroma columns under four positions
+    constexpr int NC = SUBW && !HCEN ? 3 : 4;                      // chroma columns under four positions
     __shared__ __attribute__((aligned(16))) float s_u[LDS ? CS_RH : 1][CS_RW], s_v[LDS ? CS_RH : 1][CS_RW];
     const int f = blockIdx.z;
     const uint8_t *sy = a.src[f][0], *su = a.src[f][1], *sv = a.src[f][2];
@@ -375,7 +385,8 @@ void colorspace_kernel(CsBatch a, PLAN p)
     // they share once
     const bool inner = wide && ux >= 0 && ux + 3 <= a.w - 1;
     int cc[NC];
-    if (SUBW) { cc[0] = ux >> 1; cc[1] = cc[0] + 1; cc[NC - 1] = min(cc[0] + 2, a.cw - 1); }
+    if constexpr (HCEN) { cc[1] = ux >> 1; cc[0] = max(cc[1] - 1, 0); cc[2] = cc[1] + 1; cc[NC - 1] = min(cc[1] + 2, a.cw - 1); }
+    else if (SUBW) { cc[0] = ux >> 1; cc[1] = cc[0] + 1; cc[NC - 1] = min(cc[0] + 2, a.cw - 1); }
     else
     {
 #pragma unroll
@@ -386,7 +397,14 @@ void colorspace_kernel(CsBatch a, PLAN p)
         Rows r;
         r.y = clampi(uy, 0, a.h - 1);
         r.r0 = r.r1 = r.y; r.wy0 = 1.f; r.wy1 = 0.f;
-        if (SUBH)
+        if constexpr (VCOS)
+        {
+            // (an even row takes c[k] as it is: 1 * c[k] + 0 * c[k] in the sum below is c[k])
+            const int k = r.y >> 1;
+            r.r0 = r.r1 = k;
+            if (r.y & 1) { r.r1 = min(k + 1, a.ch - 1); r.wy0 = 0.5f; r.wy1 = 0.5f; }
+        }
+        else if (SUBH)
         {
             const int k = r.y >> 1;
             if (r.y & 1) { r.r0 = k; r.r1 = min(k + 1, a.ch - 1); r.wy0 = 0.75f; r.wy1 = 0.25f; }
@@ -422,7 +440,7 @@ void colorspace_kernel(CsBatch a, PLAN p)
     auto pass = [&](int it) __attribute__((always_inline)) {
         const int ry = gr + 16 * it;
         const int uy = y0 - HY + ry;
-        if (ux > a.w || uy > a.h + 1) return;                      // nothing reads a position beyond column w, row h + 1
+        if (ux > a.w + (HCEN ? 1 : 0) || uy > a.h + 1) return;     // nothing reads a position beyond column w (centred columns: w + 1), row h + 1
         const Rows r = rows_of(uy);
         const float wy0 = r.wy0, wy1 = r.wy1;
         float yf[4], uf[4], vf[4];
@@ -456,7 +474,14 @@ void colorspace_kernel(CsBatch a, PLAN p)
                 }
                 else { cu[j] = u0; cv[j] = v0; }
             }
-            if (SUBW)
+            if constexpr (HCEN)
+            {
+                uf[0] = __fmaf_rn(0.75f, cu[1], 0.25f * cu[0]); uf[1] = __fmaf_rn(0.25f, cu[2], 0.75f * cu[1]);
+                uf[2] = __fmaf_rn(0.75f, cu[2], 0.25f * cu[1]); uf[3] = __fmaf_rn(0.25f, cu[3], 0.75f * cu[2]);
+                vf[0] = __fmaf_rn(0.75f, cv[1], 0.25f * cv[0]); vf[1] = __fmaf_rn(0.25f, cv[2], 0.75f * cv[1]);
+                vf[2] = __fmaf_rn(0.75f, cv[2], 0.25f * cv[1]); vf[3] = __fmaf_rn(0.25f, cv[3], 0.75f * cv[2]);
+            }
+            else if (SUBW)
             {
                 uf[0] = cu[0]; uf[1] = __fmaf_rn(0.5f, cu[1], 0.5f * cu[0]); uf[2] = cu[1]; uf[3] = __fmaf_rn(0.5f, cu[NC - 1], 0.5f * cu[1]);
                 vf[0] = cv[0]; vf[1] = __fmaf_rn(0.5f, cv[1], 0.5f * cv[0]); vf[2] = cv[1]; vf[3] = __fmaf_rn(0.5f, cv[NC - 1], 0.5f * cv[1]);
@@ -479,7 +504,15 @@ void colorspace_kernel(CsBatch a, PLAN p)
                 yf[j] = (samp<PIX>(yrow, x) - p.yoff_in) * p.ymul_in;
                 int c0 = x, c1 = x;
                 bool mix = false;
-                if (SUBW) { c0 = x >> 1; c1 = c0; if (x & 1) { c1 = min(c0 + 1, a.cw - 1); mix = true; } }
+                float wx0 = 0.5f, wx1 = 0.5f;
+                if constexpr (HCEN)
+                {
+                    const int k = x >> 1;
+                    mix = true;
+                    if (x & 1) { c0 = k; c1 = min(k + 1, a.cw - 1); wx0 = 0.75f; wx1 = 0.25f; }
+                    else       { c0 = max(k - 1, 0); c1 = k; wx0 = 0.25f; wx1 = 0.75f; }
+                }
+                else if (SUBW) { c0 = x >> 1; c1 = c0; if (x & 1) { c1 = min(c0 + 1, a.cw - 1); mix = true; } }
                 float au, bu, av, bv;
                 {
                     const float u00 = (samp<PIX>(urow0, c0) - p.coff_in) * p.cmul_in, u01 = (samp<PIX>(urow0, c1) - p.coff_in) * p.cmul_in;
@@ -493,8 +526,8 @@ void colorspace_kernel(CsBatch a, PLAN p)
                     }
                     else { au = u00; bu = u01; av = v00; bv = v01; }
                 }
-                uf[j] = mix ? __fmaf_rn(0.5f, bu, 0.5f * au) : au;
-                vf[j] = mix ? __fmaf_rn(0.5f, bv, 0.5f * av) : av;
+                uf[j] = mix ? __fmaf_rn(wx1, bu, wx0 * au) : au;
+                vf[j] = mix ? __fmaf_rn(wx1, bv, wx0 * av) : av;
             }
         }
         float oy[4], ou[4], ov[4];
@@ -512,7 +545,7 @@ void colorspace_kernel(CsBatch a, PLAN p)
             *reinterpret_cast<float4 *>(&s_v[ry][4 * gx]) = make_float4(ov[0], ov[1], ov[2], ov[3]);
         }
         // the tile's own positions: luma out (and chroma, where it is not subsampled)
-        if (ux >= x0 && ux < a.w && uy >= y0 && uy < y0 + TH && uy < a.h)
+        if (ux >= x0 && (!HCEN || ux < x0 + TW) && ux < a.w && uy >= y0 && uy < y0 + TH && uy < a.h)
         {
             uint32_t q[4];
 #pragma unroll
@@ -563,16 +596,20 @@ void colorspace_kernel(CsBatch a, PLAN p)
         for (int k = 0; k < 2; k++)
         {
             float (*s)[CS_RW] = k ? s_v : s_u;
-            float col[3];
+            float col[HCEN ? 4 : 3];
 #pragma unroll
-            for (int j = 0; j < 3; j++)
+            for (int j = 0; j < (HCEN ? 4 : 3); j++)
             {
                 if (!SUBW && j != 1) continue;
                 const int xx = SUBW ? rx - 1 + j : rx;
+                if constexpr (VCOS) col[j] = __fmaf_rn(0.25f, s[ry + 1][xx], __fmaf_rn(0.5f, s[ry][xx], 0.25f * s[ry - 1][xx]));
+                else
                 col[j] = SUBH ? __fmaf_rn(0.125f, s[ry + 2][xx], __fmaf_rn(0.375f, s[ry + 1][xx], __fmaf_rn(0.375f, s[ry][xx], 0.125f * s[ry - 1][xx])))
                               : s[ry][xx];
             }
-            const float v = SUBW ? __fmaf_rn(0.25f, col[2], __fmaf_rn(0.5f, col[1], 0.25f * col[0])) : col[1];
+            float v;
+            if constexpr (HCEN) v = __fmaf_rn(0.125f, col[3], __fmaf_rn(0.375f, col[2], __fmaf_rn(0.375f, col[1], 0.125f * col[0])));
+            else v = SUBW ? __fmaf_rn(0.25f, col[2], __fmaf_rn(0.5f, col[1], 0.25f * col[0])) : col[1];
             reinterpret_cast<PIX *>(a.dst[f][1 + k] + (size_t)cy * a.dpitch[1 + k])[cx] = (PIX)quant(v, p.cmul_out, p.coff_out, p.vmax);
         }
     }
@@ -882,30 +919,37 @@ public:
     void launch(const CsBatch &B, int nf)
     {
         const int sw = in_geo.log2_cw, sh = in_geo.log2_ch;
-        const int tw = CS_RW - (sw ? 4 : 0), th = CS_RH - (sh ? 2 : 0);
+        const bool hc = sw && chroma_convert_h_centred(chroma_location), vc = sh && chroma_convert_v_cosited(chroma_location);
+        const int tw = CS_RW - (sw ? 4 : 0) - (hc ? 4 : 0), th = CS_RH - (sh ? 2 : 0);
         const dim3 grid(hbhip_grid_x((B.w + tw - 1) / tw), (B.h + th - 1) / th, nf);
-        const CsPlan &base = plan;
-        if (wide)
+        if (wide)                   launch_sited<PIX, true, CsPlanWide>(B, plan, grid, sw, sh, hc, vc);
+        else if (plan.need_linear)  launch_sited<PIX, true, CsPlan>(B, plan, grid, sw, sh, hc, vc);
+        else                        launch_sited<PIX, false, CsPlan>(B, plan, grid, sw, sh, hc, vc);
+    }
+    // the form of the subsampling and of the siting: four of 4:2:0, two each of 4:2:2 and 4:4:0, one of 4:4:4
+    template <typename PIX, bool LINEAR, typename PLAN>
+    void launch_sited(const CsBatch &B, const PLAN &pl, const dim3 &grid, int sw, int sh, bool hc, bool vc)
+    {
+#define CS_GO(SW, SH, HC, VC) HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, SW, SH, LINEAR, PLAN, HC, VC>), grid, dim3(256), 0, B, pl)
+        if (sw && sh)
         {
-            if (sw && sh)       HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 1, true, CsPlanWide>), grid, dim3(256), 0, B, plan);
-            else if (sw)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 0, true, CsPlanWide>), grid, dim3(256), 0, B, plan);
-            else if (sh)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 1, true, CsPlanWide>), grid, dim3(256), 0, B, plan);
-            else                HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 0, true, CsPlanWide>), grid, dim3(256), 0, B, plan);
+            if (hc && vc)   CS_GO(1, 1, true, true);
+            else if (hc)    CS_GO(1, 1, true, false);
+            else if (vc)    CS_GO(1, 1, false, true);
+            else            CS_GO(1, 1, false, false);
         }
-        else if (plan.need_linear)
+        else if (sw)
         {
-            if (sw && sh)       HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 1, true>), grid, dim3(256), 0, B, base);
-            else if (sw)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 0, true>), grid, dim3(256), 0, B, base);
-            else if (sh)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 1, true>), grid, dim3(256), 0, B, base);
-            else                HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 0, true>), grid, dim3(256), 0, B, base);
+            if (hc)         CS_GO(1, 0, true, false);
+            else            CS_GO(1, 0, false, false);
         }
-        else
+        else if (sh)
         {
-            if (sw && sh)       HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 1, false>), grid, dim3(256), 0, B, base);
-            else if (sw)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 1, 0, false>), grid, dim3(256), 0, B, base);
-            else if (sh)        HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 1, false>), grid, dim3(256), 0, B, base);
-            else                HBHIP_LAUNCH(ctx, "colorspace", (colorspace_kernel<PIX, 0, 0, false>), grid, dim3(256), 0, B, base);
+            if (vc)         CS_GO(0, 1, false, true);
+            else            CS_GO(0, 1, false, false);
         }
+        else                CS_GO(0, 0, false, false);
+#undef CS_GO
     }
     // the frames of a batch (a chain batch, a device-resident batch) in one launch where their pitches agree
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
@@ -920,15 +964,18 @@ public:
     hbhip_colorspace_params par;
     CsPlanWide plan;                     // the wide fields only where wide is set
     bool wide = false;
+    int chroma_location = CHROMA_LOC_LEFT;      // AVCHROMA_LOC_*: which form of the up- and down-sampling (chroma_siting.h)
 };
 
 } // namespace
 
-extern "C" int hbhip_colorspace_create(hbhip_ctx *ctx, const hbhip_colorspace_params *p, int width, int height,
-                                       int depth, int log2_chroma_w, int log2_chroma_h, hbhip_filter **out)
+extern "C" int hbhip_colorspace_create_sited(hbhip_ctx *ctx, const hbhip_colorspace_params *p, int width, int height,
+                                             int depth, int log2_chroma_w, int log2_chroma_h, int chroma_location,
+                                             hbhip_filter **out)
 {
     if (!ctx || !p || !out) return HBHIP_ERR_ARG;
     *out = nullptr;
+    if (!chroma_loc_valid(chroma_location)) return HBHIP_ERR_ARG;
     if (depth != 8 && depth != 10 && depth != 12) return HBHIP_ERR_UNSUPPORTED;
     if (log2_chroma_w < 0 || log2_chroma_w > 1 || log2_chroma_h < 0 || log2_chroma_h > 1) return HBHIP_ERR_UNSUPPORTED;
     if (width < 2 || height < 2 || !(p->npl > 0)) return HBHIP_ERR_ARG;
@@ -936,8 +983,15 @@ extern "C" int hbhip_colorspace_create(hbhip_ctx *ctx, const hbhip_colorspace_pa
     g.set(width, height, depth, log2_chroma_w, log2_chroma_h);
     ColorspaceFilter *f = hbhip_make_filter<ColorspaceFilter>(ctx, g, g, *p);
     if (!f) return HBHIP_ERR_NOMEM;
+    f->chroma_location = chroma_location;
     int rc = f->setup(depth);
     if (rc != HBHIP_OK) { delete f; return rc; }
     *out = f;
     return HBHIP_OK;
+}
+
+extern "C" int hbhip_colorspace_create(hbhip_ctx *ctx, const hbhip_colorspace_params *p, int width, int height,
+                                       int depth, int log2_chroma_w, int log2_chroma_h, hbhip_filter **out)
+{
+    return hbhip_colorspace_create_sited(ctx, p, width, height, depth, log2_chroma_w, log2_chroma_h, CHROMA_LOC_LEFT, out);
 }

@@ -413,7 +413,7 @@ class JobList:
             rt.hb_dict_free(C.byref(d))
         self.init = _Init()
         self.init.job = C.addressof(self.job)
-        self.init.pix_fmt, self.init.hw_pix_fmt, self.init.chroma_location = pix_fmt, -1, 1
+        self.init.pix_fmt, self.init.hw_pix_fmt, self.init.chroma_location = pix_fmt, -1, _source_chroma_location
         self.init.color[:] = [1, 1, 1, 1]
         self.init.geometry[:] = [width, height, 1, 1]
         self.init.vrate[:] = [30000, 1001]
@@ -512,6 +512,20 @@ def set_source_color(prim: int = 1, transfer: int = 1, matrix: int = 1, color_ra
     rt.hbh_set_source_color.argtypes = [C.c_int] * 4
     rt.hbh_set_source_color.restype = None
     rt.hbh_set_source_color(prim, transfer, matrix, color_range)
+
+
+_source_chroma_location = 1          # AVCHROMA_LOC_LEFT
+
+
+def set_source_chroma_location(chroma_location: int = 1):
+    """Chroma sample location (init->chroma_location and every frame's; AVCHROMA_LOC_*: 0 unspecified, 1 left, 2 center,
+    3 topleft, 4 top, 5 bottomleft, 6 bottom) of the source of chains and jobs opened from now on."""
+    global _source_chroma_location
+    rt = runtime()
+    rt.hbh_set_source_chroma_location.argtypes = [C.c_int]
+    rt.hbh_set_source_chroma_location.restype = None
+    rt.hbh_set_source_chroma_location(chroma_location)
+    _source_chroma_location = chroma_location
 
 
 def run_stream(lib, stages, frames, flags: int = 0x10, pix_fmt: int = AV_PIX_FMT_YUV420P,

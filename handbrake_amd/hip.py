@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "hbhip_comb_detect_create", "hbhip_comb_detect_set_gamma_lut", "hbhip_comb_detect_store",
     "hbhip_comb_detect_store_dev",
     "hbhip_comb_detect_classify", "hbhip_comb_detect_classify_many_dev", "hbhip_comb_detect_overlay", "hbhip_comb_detect_overlay_dev",
-    "hbhip_rotate_create", "hbhip_grayscale_create", "hbhip_cropscale_create", "hbhip_colorspace_create", "hbhip_pad_create", "hbhip_yadif_create", "hbhip_bwdif_create", "hbhip_format_create", "hbhip_format_resample_create", "hbhip_format_scaled_create", "hbhip_format_upsample_create",
+    "hbhip_rotate_create", "hbhip_grayscale_create", "hbhip_cropscale_create", "hbhip_cropscale_create_sited", "hbhip_colorspace_create", "hbhip_colorspace_create_sited", "hbhip_pad_create", "hbhip_yadif_create", "hbhip_bwdif_create", "hbhip_format_create", "hbhip_format_resample_create", "hbhip_format_scaled_create", "hbhip_format_upsample_create",
     "hbhip_blend_create", "hbhip_blend_set_overlays", "hbhip_blend_apply", "hbhip_blend_apply_dev", "hbhip_blend_destroy",
     "hbhip_blend_create_biplanar", "hbhip_blend_apply_biplanar",
     "hbhip_blend_set_ass_images", "hbhip_blend_debug_overlay_count", "hbhip_blend_debug_get_overlay",
@@ -634,12 +634,20 @@ def lapsharp_device_filter(ctx, width, height, strength=0.2, kernel=1, depth=8):
                    ctx.h, C.byref(p), width, height, depth, 1, 1)
 
 
-def cropscale_device_filter(ctx, width, height, out_w, out_h, crop=(0, 0, 0, 0), depth=8, sws=False):
-    """sws: libswscale's arithmetic (the reference's branch for odd sizes) instead of zimg's"""
+def cropscale_device_filter(ctx, width, height, out_w, out_h, crop=(0, 0, 0, 0), depth=8, sws=False, log2_cw=1, log2_ch=1,
+                            chroma_location=None):
+    """sws: libswscale's arithmetic (the reference's branch for odd sizes) instead of zimg's.  chroma_location: the
+    stream's AVCHROMA_LOC_* number (zimg's arithmetic only; None = the call without one, which is left-sited)"""
     p = CropScaleParams(out_w, out_h, *crop)
+    if chroma_location is not None:
+        if sws:
+            raise ValueError("the libswscale form stays left-sited")
+        return _create("hbhip_cropscale_create_sited", ctx,
+                       [C.c_void_p, C.POINTER(CropScaleParams)] + [C.c_int] * 6 + [C.POINTER(C.c_void_p)],
+                       ctx.h, C.byref(p), width, height, depth, log2_cw, log2_ch, chroma_location)
     return _create("hbhip_cropscale_sws_create" if sws else "hbhip_cropscale_create", ctx,
                    [C.c_void_p, C.POINTER(CropScaleParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
-                   ctx.h, C.byref(p), width, height, depth, 1, 1)
+                   ctx.h, C.byref(p), width, height, depth, log2_cw, log2_ch)
 
 
 class ColorspaceParams(C.Structure):
@@ -652,11 +660,16 @@ TONEMAPS = {"none": 0, "linear": 1, "gamma": 2, "clip": 3, "reinhard": 4, "hable
 
 
 def colorspace_device_filter(ctx, width, height, src, dst, tonemap="hable", param=float("nan"), desat=0.0,
-                             npl=100.0, peak=10.0, depth=8, log2_cw=1, log2_ch=1):
+                             npl=100.0, peak=10.0, depth=8, log2_cw=1, log2_ch=1, chroma_location=None):
     """src / dst = (primaries, transfer, matrix, range) in AVCOL_* numbers, range 1 = tv, 2 = pc.  Matrix 12
     (chroma-derived-nc) on primaries with known chromaticities, 10 / 13 (bt2020c, chroma-derived-c) on BT.2020
-    primaries and 14 (ICtCp) on BT.2020 primaries with PQ or HLG are accepted on either side."""
+    primaries and 14 (ICtCp) on BT.2020 primaries with PQ or HLG are accepted on either side.  chroma_location: the
+    stream's AVCHROMA_LOC_* number (None = the call without one: left-sited horizontally, centred vertically)."""
     p = ColorspaceParams(*src, *dst, TONEMAPS[tonemap], param, desat, npl, peak)
+    if chroma_location is not None:
+        return _create("hbhip_colorspace_create_sited", ctx,
+                       [C.c_void_p, C.POINTER(ColorspaceParams)] + [C.c_int] * 6 + [C.POINTER(C.c_void_p)],
+                       ctx.h, C.byref(p), width, height, depth, log2_cw, log2_ch, chroma_location)
     return _create("hbhip_colorspace_create", ctx,
                    [C.c_void_p, C.POINTER(ColorspaceParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
                    ctx.h, C.byref(p), width, height, depth, log2_cw, log2_ch)

@@ -109,8 +109,10 @@ static int crop_scale_hip_init(hb_filter_object_t *filter, hb_filter_init_t *ini
     if (ctx == NULL) return hbhip_host_simple_fail(filter, HBHIP_ERR_NODEVICE);
     int rc = odd ? hbhip_cropscale_sws_create(ctx, &p, init->geometry.width, init->geometry.height, desc->comp[0].depth,
                                               desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev)
-                 : hbhip_cropscale_create(ctx, &p, init->geometry.width, init->geometry.height, desc->comp[0].depth,
-                                          desc->log2_chroma_w, desc->log2_chroma_h, &pv->s.dev);
+                 /* zscale shifts chroma by the frame's chroma_location (hbffmpeg.c:130; cropscale.c:150-157 sets neither
+                  * chromal nor chromal_in); the location itself goes on unchanged to the next filter */
+                 : hbhip_cropscale_create_sited(ctx, &p, init->geometry.width, init->geometry.height, desc->comp[0].depth,
+                                                desc->log2_chroma_w, desc->log2_chroma_h, init->chroma_location, &pv->s.dev);
     if (rc != HBHIP_OK) return hbhip_host_simple_fail(filter, rc);
 
     init->crop[0] = p.crop_top;                                              /* :168-178 */

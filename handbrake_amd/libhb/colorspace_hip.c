@@ -137,10 +137,12 @@ static int colorspace_hip_init(hb_filter_object_t *filter, hb_filter_init_t *ini
             p.npl = npl;
             p.peak = signal_peak(init);
             hbhip_ctx *ctx = desc != NULL && p.tonemap >= 0 ? hbhip_host_ctx_for(init) : NULL;
+            /* zscale takes the chroma siting of both of its passes from the frame's chroma_location (hbffmpeg.c:130 sets
+             * it; colorspace.c:132-186 sets neither chromal nor chromal_in); the location itself goes on unchanged */
             int err = ctx == NULL ? HBHIP_ERR_NODEVICE
-                                  : hbhip_colorspace_create(ctx, &p, init->geometry.width, init->geometry.height,
-                                                            desc->comp[0].depth, desc->log2_chroma_w,
-                                                            desc->log2_chroma_h, &pv->s.dev);
+                                  : hbhip_colorspace_create_sited(ctx, &p, init->geometry.width, init->geometry.height,
+                                                                  desc->comp[0].depth, desc->log2_chroma_w,
+                                                                  desc->log2_chroma_h, init->chroma_location, &pv->s.dev);
             if (err != HBHIP_OK)
                 rc = hbhip_host_simple_fail(filter, err);                                     /* (pv is gone) */
             else

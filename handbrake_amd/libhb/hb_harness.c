@@ -199,6 +199,9 @@ void hbh_set_source_color(int prim, int transfer, int matrix, int range)
     g_src_color[0] = prim; g_src_color[1] = transfer; g_src_color[2] = matrix; g_src_color[3] = range;
 }
 
+static int g_src_chroma_location = 1;          /* AVCHROMA_LOC_LEFT */
+void hbh_set_source_chroma_location(int chroma_location) { g_src_chroma_location = chroma_location; }
+
 static void source_init(hb_filter_init_t *init, int pix_fmt, int width, int height, int vrate_num, int vrate_den);
 
 /* A job the way do_job() prepares its video filters (work.c:1820-1870): the filter list is built from the
@@ -336,7 +339,7 @@ hbh_chain_t *hbh_chain_open(int nstages, void *const *protos, const char *const 
     init.color_transfer = g_src_color[1];
     init.color_matrix = g_src_color[2];
     init.color_range = g_src_color[3];
-    init.chroma_location = 1;
+    init.chroma_location = g_src_chroma_location;
     c->init_in = init;
 
     for (int i = 0; i < nstages; i++)
@@ -376,7 +379,7 @@ static void source_init(hb_filter_init_t *pinit, int pix_fmt, int width, int hei
     init.color_transfer = g_src_color[1];
     init.color_matrix = g_src_color[2];
     init.color_range = g_src_color[3];
-    init.chroma_location = 1;
+    init.chroma_location = g_src_chroma_location;
     *pinit = init;
 }
 

@@ -55,6 +55,9 @@ double hbh_chain_stage_busy_ms(hbh_chain_t *c, int stage);
 /* Colour description of the source for chains opened from now on (init->color_*; AVCOL_* numbers,
  * range 1 = tv, 2 = pc).  Default bt709 / tv. */
 void hbh_set_source_color(int prim, int transfer, int matrix, int range);
+/* Chroma sample location of the source for chains opened from now on (init->chroma_location and every frame's
+ * f.chroma_location; AVCHROMA_LOC_* numbers).  Default 1 (left). */
+void hbh_set_source_chroma_location(int chroma_location);
 int  hbh_chain_push(hbh_chain_t *c, const uint8_t *const plane[3], const int stride[3],
                     int64_t start, int64_t stop, int flags, int combed);
 /* `count` frames from `n_unique` prepared pictures (plane[3 * k + p], one stride per plane), numbered first, first + 1, ...:

@@ -449,6 +449,13 @@ typedef struct hbhip_cropscale_params
 } hbhip_cropscale_params;
 int hbhip_cropscale_create(hbhip_ctx *ctx, const hbhip_cropscale_params *p, int width, int height,
                            int depth, int log2_chroma_w, int log2_chroma_h, hbhip_filter **out);
+/* The same with the stream's chroma sample location (AVCHROMA_LOC_*: 0 unspecified, 1 left, 2 center, 3 topleft, 4 top,
+ * 5 bottomleft, 6 bottom), which zscale takes from the frame when its chromal / chromal_in are not set, as the reference
+ * leaves them: a subsampled chroma direction is shifted by -raw * 0.5 * (1 - src / dst) source chroma samples, raw = -0.5
+ * co-sited (left, top), 0 centred, +0.5 bottom.  hbhip_cropscale_create is this call with location 1; 0 is taken as 1.
+ * A location outside 0..6 is HBHIP_ERR_ARG.  PARITY UNPINNED: zimg's rule as recalled (csrc/chroma_siting.h). */
+int hbhip_cropscale_create_sited(hbhip_ctx *ctx, const hbhip_cropscale_params *p, int width, int height,
+                                 int depth, int log2_chroma_w, int log2_chroma_h, int chroma_location, hbhip_filter **out);
 /* The other branch of crop_scale_init (cropscale.c:159-165): `crop` + `scale=flags=lanczos+accurate_rnd`, which the
  * reference builds when hb_av_can_use_zscale() says no (an odd width or height, hbffmpeg.c:870-915) - libswscale's
  * arithmetic instead of zimg's (8-bit planes: hScale8To15 + yuv2planeX_8; 10 / 12-bit: hScale16To15 + yuv2planeX_10 / _12). */
@@ -591,6 +598,14 @@ typedef struct hbhip_colorspace_params
 } hbhip_colorspace_params;
 int hbhip_colorspace_create(hbhip_ctx *ctx, const hbhip_colorspace_params *p, int width, int height,
                             int depth, int log2_chroma_w, int log2_chroma_h, hbhip_filter **out);
+/* The same with the stream's chroma sample location (AVCHROMA_LOC_*, as hbhip_cropscale_create_sited): a subsampled
+ * direction is up- and down-sampled co-sited (up 2k: c[k], 2k + 1: (c[k] + c[k+1]) / 2; down 2k - 1 .. 2k + 1 with
+ * 1/4 1/2 1/4) or centred (up 2k: c[k-1] / 4 + 3 c[k] / 4, 2k + 1: 3 c[k] / 4 + c[k+1] / 4; down 2k - 1 .. 2k + 2 with
+ * 1/8 3/8 3/8 1/8), edges repeating.  Horizontally locations 0, 1, 3, 5 are co-sited and 2, 4, 6 centred; vertically 3
+ * and 4 are co-sited (top) and everything else centred - vertical bottom (5, 6) too, an approximation.
+ * hbhip_colorspace_create is this call with location 1.  A location outside 0..6 is HBHIP_ERR_ARG. */
+int hbhip_colorspace_create_sited(hbhip_ctx *ctx, const hbhip_colorspace_params *p, int width, int height,
+                                  int depth, int log2_chroma_w, int log2_chroma_h, int chroma_location, hbhip_filter **out);
 
 /* ---- Frame-difference metric (replaces hb_motion_metric, motion_metric.c: the object vfr.c
  *      calls on consecutive frames to choose the one to drop, vfr.c:76-108, 380) ---------------

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Times one stateless filter's batch path (16 device-resident 1080p frames per call) with the context's kernel timer.
-usage: quick_filter.py unsharp|chroma_smooth|lapsharp|colorspace_sdr|colorspace_matrix|grayscale|rotate|scale<W>x<H>|
+usage: quick_filter.py unsharp|chroma_smooth|lapsharp|colorspace_sdr|colorspace_matrix|colorspace_pq[_loc<0..6>]|grayscale|rotate|scale<W>x<H>|
                       format8to10|format10to8|format_422_420[_10]|format_444_422[_10]|format_444_420[_10]|
                       format_<444|422|420>_<422|420>_<10to8|12to8|12to10> (a lower depth; 420_420: the depth alone)|
                      format_<420|422>_<422|444>_up[_10|_8to10|_8to12|_10to12] (more chroma samples, equal or higher depth)|
@@ -75,6 +75,11 @@ def main():
         depth_in = depth_out = 10
     elif what == "colorspace_sdr": make = lambda: hip.colorspace_device_filter(ctx, W, H, (6, 6, 6, 1), (1, 1, 1, 1))
     elif what == "colorspace_matrix": make = lambda: hip.colorspace_device_filter(ctx, W, H, (1, 1, 1, 1), (1, 1, 6, 2))
+    elif what.startswith("colorspace_pq"):             # colorspace_pq, colorspace_pq_loc3: HDR10 -> BT.709 hable at 10 bits, a chroma location
+        loc = int(what.split("_loc")[1]) if "_loc" in what else None
+        make = lambda: hip.colorspace_device_filter(ctx, W, H, (9, 16, 9, 1), (1, 1, 1, 1), tonemap="hable", peak=100.0, depth=10,
+                                                    chroma_location=loc)
+        depth_in = depth_out = 10
     elif what == "grayscale":
         make = lambda: hip._create("hbhip_grayscale_create", ctx, [C.c_void_p] + [C.c_double] * 4 + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
                                    ctx.h, 0.0, 0.0, 1.0, 0.0, W, H, 8, 1, 1)
