@@ -115,11 +115,16 @@ __device__ __forceinline__ int hbhip_align_up_dev(int v, int a) { return (v + a 
 // Slots in an LDS list for the `n` (0..7) entries of each lane, in lane order, with ONE atomic per wave: the lanes' counts
 // as three ballots of their bits, the slots below a lane as mbcnt of those.  An atomicAdd of a value that differs between
 // lanes compiles to a scalar loop over the active lanes (readlane, add, writelane: nine instructions a lane, one after the
-// other) ahead of the atomic.  Call with every lane of the wave active.
+// other) ahead of the atomic.  Call with every lane of the wave active.  BITS: more of them for n up to 15 or 31.
+template <int BITS = 3>
 __device__ __forceinline__ int wave_list_slots(int *counter, unsigned n)
 {
+    static_assert(BITS >= 3 && BITS <= 5, "three to five bits of n");
     const uint64_t b0 = __ballot(n & 1u), b1 = __ballot(n & 2u), b2 = __ballot(n & 4u);
-    const int total = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
+    const uint64_t b3 = BITS > 3 ? __ballot(n & 8u) : 0ull, b4 = BITS > 4 ? __ballot(n & 16u) : 0ull;
+    int total = __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2);
+    if (BITS > 3) total += 8 * __popcll(b3);
+    if (BITS > 4) total += 16 * __popcll(b4);
     auto below = [](uint64_t m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); };
     int base = 0;
     if (total)
@@ -127,7 +132,10 @@ __device__ __forceinline__ int wave_list_slots(int *counter, unsigned n)
         if ((threadIdx.x & 63) == 0) base = atomicAdd(counter, total);
         base = __builtin_amdgcn_readfirstlane(base);
     }
-    return base + below(b0) + 2 * below(b1) + 4 * below(b2);
+    int at = base + below(b0) + 2 * below(b1) + 4 * below(b2);
+    if (BITS > 3) at += 8 * below(b3);
+    if (BITS > 4) at += 16 * below(b4);
+    return at;
 }
 
 __device__ __forceinline__ int sad3(const uint8_t *a, int ai, const uint8_t *b, int bi)
@@ -1526,7 +1534,24 @@ __global__ __launch_bounds__(256) void k_dir_map_fe(P3 P, uint32_t padv)
 // rate and the memory latency, not at its bytes.  Here a workgroup stages its 4 + 2 rows of the map (256 columns + 8 either
 // side) in LDS with dword loads, a thread owns an aligned dword of its row (mask and output as dwords), and the walks of
 // its four pixels read bytes from LDS.
-constexpr int FM_W = 256, FM_R = 4, FM_HALO = 8, FM_LW = FM_W + 2 * FM_HALO;
+//
+// That form walked the four pixels of a dword one after the other, so a wave paid, per byte position, the longest walk of
+// its 64 lanes - and a step for every position at which one lane has a candidate.  On the bench's pictures 42 % of the
+// pixels are candidates, three in four of them walk one step and the rest two: the loop ran at a quarter of its lanes'
+// worth (tools/filter_map_walks.py).  Now the threads only LIST their candidates, by walk length, and
+// after a barrier a lane takes one listed pixel, waves made of pixels of one class:
+//   list 0: direction / 16 == 0 - one step at the pixel's own column: no loop, no range, nothing to clip;
+//   list 1: the rest (2 .. 9 steps), the loop as it was.
+// The class of the four pixels of a dword is byte arithmetic on the dword (its high nibbles), the slots come from
+// wave_list_slots (one call per list for all of a thread's dwords), the lists grow from the two ends of one array.  A
+// walker writes PEAK into its pixel's byte of the output rows in LDS, which start as the map's own; the rows leave as
+// dwords.  A tile is FM_ROWS rows (a thread owns a dword of every fourth): the two halo rows, the plane / field look-up and
+// the barriers are paid once for 8 rows instead of 4.  (Measured and dropped, DESIGN.md 4.2.6: a third list for the walks
+// of three and more steps, and the dword walk for tiles of nothing but candidates.)
+constexpr int FM_W = 256, FM_HALO = 8, FM_LW = FM_W + 2 * FM_HALO;
+#ifndef FM_ROWS
+#define FM_ROWS 8
+#endif
 
 // The test of a step (:569-571 and its three siblings) without a branch per clause: every clause is the SIGN of an
 // integer - lim - |s - ref| is negative when s is off by more than lim, s - 255 is negative unless s is the peak,
@@ -1539,95 +1564,168 @@ __device__ __forceinline__ int fm_step(uint32_t s, uint32_t c, uint32_t ref, int
     return (off_s & (int)(s - 255u)) | (off_c & (int)(c - 255u)) | (509 - (int)c - (int)s);
 }
 
+// Both walks of the pixel at dc (its byte in the staged rows; xx = its column), neither with an early exit: true when the
+// walk above trips somewhere AND the walk below does (:565-627 take the second only after the first has tripped - the same
+// verdict).  With neg = min(dir, 0), pos = max(dir, 0) the four ranges of :565-620 are [max(-x, neg), min(w - x - 1, pos)]
+// above and [max(-x, -pos), min(w - x - 1, -neg)] below; the shorter walk repeats its last step.
+// ONE: the caller knows direction / 16 == 0 (list 0) - every range is [0, 0] for a pixel off the plane's border
+// (1 <= xx <= width - 2, which every candidate is), one step at the pixel's own column.
+template <bool ONE>
+__device__ __forceinline__ bool fm_walk(const uint8_t *dc, int xx, int width)
+{
+    const uint8_t *dp = dc - FM_LW, *dn = dc + FM_LW;
+    const uint32_t ref = dc[0];
+    int dir = ((int)ref - NEUTRAL) >> 2;
+    const int lim = max(iabs(dir) * 2, 12 << 2);
+    if (ONE) return ((fm_step(dp[0], ref, ref, lim) & fm_step(dn[0], ref, ref, lim)) < 0);
+    dir >>= 2;
+    const int neg = min(dir, 0), pos = max(dir, 0);
+    const int tf = max(-xx, neg), tt = min(width - xx - 1, pos), bf = max(-xx, -pos), bt = min(width - xx - 1, -neg);
+    const int n = max(tt - tf, bt - bf);
+    int any_t = 0, any_b = 0;
+    for (int i = 0; i <= n; i++)
+    {
+        const int jt = min(tf + i, tt), jb = min(bf + i, bt);
+        any_t |= fm_step(dp[jt], dc[jt], ref, lim);
+        any_b |= fm_step(dn[jb], dc[jb], ref, lim);
+    }
+    return (any_t & any_b) < 0;
+}
+
+template <int R>
 __global__ __launch_bounds__(256) void k_filter_map(P3 P)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t s_d[FM_R + 2][FM_LW];
+    static_assert(R % 4 == 0 && R >= 4 && R <= 16, "a thread owns a dword of every fourth row; a list entry has four bits for the row");
+    constexpr int NJ = R / 4, NSTAGE = (R + 2) * (FM_LW / 4), NS = (NSTAGE + 255) / 256, NLIST = R * FM_W;
+    constexpr int NBITS = NJ == 1 ? 3 : NJ == 2 ? 4 : 5;          // a lane lists up to 4 * NJ pixels
+    __shared__ __attribute__((aligned(16))) uint8_t s_d[R + 2][FM_LW];
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[R][FM_W];
+    __shared__ uint16_t s_list[NLIST];                           // entry: row << 8 | column; list 0 from the front, list 1 from the back
+    __shared__ int s_count[2];
+    __shared__ uint32_t s_some[4];
     FIELD_PLANE(P);
     const int pitch = P.pitch[pl], width = P.width[pl], height = P.height[pl];
-    const int bx0 = blockIdx.x * FM_W, by0 = blockIdx.y * FM_R;
+    const int bx0 = blockIdx.x * FM_W, by0 = blockIdx.y * R;
     if (bx0 >= width || by0 >= height) return;                   // whole workgroup outside
-    const int tid = threadIdx.y * 64 + threadIdx.x;
-    const int x = bx0 + 4 * threadIdx.x, y = by0 + threadIdx.y;
+    const int lane = threadIdx.x, ty = threadIdx.y, tid = ty * 64 + lane;
+    const int x = bx0 + 4 * lane;
+    auto store4 = [&](int y, uint32_t v4) {
+        uint8_t *o = Q.c + (size_t)y * pitch + x;
+        if (x + 3 < width) *reinterpret_cast<uint32_t *>(o) = v4;
+        else for (int k = 0; k < 4 && x + k < width; k++) o[k] = (uint8_t)(v4 >> (8 * k));
+    };
     if (maskless)
     {
         // no mask pixel in the plane: the pass is its bit_blit (:547) of a map of peaks (k_dir_map4)
+#pragma unroll
+        for (int j = 0; j < NJ; j++)
+            if (x < width && by0 + ty + 4 * j < height) store4(by0 + ty + 4 * j, 0xffffffffu);
+        return;
+    }
+    // The thread's own dwords and their masks first: a workgroup without a candidate (mask peak, map not peak, inside the frame
+    // of :557-560) - off the mask, like whole chroma planes without edges - copies its rows and stages nothing.
+    uint32_t own[NJ], cand[NJ], some = 0u;
+#pragma unroll
+    for (int j = 0; j < NJ; j++)
+    {
+        const int y = by0 + ty + 4 * j;
+        uint32_t m4 = 0u;
+        own[j] = 0u;
         if (x < width && y < height)
         {
-            uint8_t *o = Q.c + (size_t)y * pitch + x;
-            if (x + 3 < width) *reinterpret_cast<uint32_t *>(o) = 0xffffffffu;
-            else for (int k = 0; k < 4 && x + k < width; k++) o[k] = (uint8_t)PEAK;
+            own[j] = *reinterpret_cast<const uint32_t *>(Q.b + (size_t)y * pitch + x);
+            if (y >= 1 && y < height - 1) m4 = *reinterpret_cast<const uint32_t *>(Q.a + (size_t)y * pitch + x);   // (m4 stays 0 on the first / last row)
         }
-        return;
+        cand[j] = ((ff_bytes(m4) & ~ff_bytes(own[j])) >> 7) & bytes_in(x, 1, width - 1);
+        some |= cand[j];
     }
-    const bool inside = x < width && y < height;
-    // The thread's own dword and its mask first: a workgroup without a candidate (mask peak, map not peak, inside the frame
-    // of :557-560) - off the mask, like whole chroma planes without edges - copies its rows and stages nothing.
-    uint32_t m4 = 0, own = 0;
-    if (inside)
+    // "a candidate anywhere in the workgroup" behind one barrier: a word per wave
     {
-        own = *reinterpret_cast<const uint32_t *>(Q.b + (size_t)y * pitch + x);
-        if (y >= 1 && y < height - 1) m4 = *reinterpret_cast<const uint32_t *>(Q.a + (size_t)y * pitch + x);   // (m4 stays 0 on the first / last row)
+        const uint64_t bs = __ballot(some != 0u);
+        if (lane == 0) s_some[ty] = bs != 0ull;
+        if (tid < 2) s_count[tid] = 0;
     }
-    uint32_t cand = ((ff_bytes(m4) & ~ff_bytes(own)) >> 7) & bytes_in(x, 1, width - 1);
-    if (!__syncthreads_or(cand != 0u))                           // block-uniform
+    __syncthreads();
+    if (!(s_some[0] | s_some[1] | s_some[2] | s_some[3]))        // block-uniform
     {
-        if (inside)
-        {
-            uint8_t *o = Q.c + (size_t)y * pitch + x;
-            if (x + 3 < width) *reinterpret_cast<uint32_t *>(o) = own;
-            else for (int k = 0; k < 4 && x + k < width; k++) o[k] = (uint8_t)(own >> (8 * k));
-        }
-        return;
-    }
-    {
-        // 6 x 68 dwords for 256 threads: both loads of a thread in flight before the first LDS store
-        static_assert((FM_R + 2) * (FM_LW / 4) <= 2 * 256, "two staged dwords per thread");
-        uint32_t v[2] = { 0u, 0u };                              // outside the plane: never looked at (the walks are clipped to the row)
 #pragma unroll
-        for (int k = 0; k < 2; k++)
+        for (int j = 0; j < NJ; j++)
+            if (x < width && by0 + ty + 4 * j < height) store4(by0 + ty + 4 * j, own[j]);
+        return;
+    }
+    {
+        // (R + 2) x 68 dwords for 256 threads: every load of a thread in flight before the first LDS store, the lists
+        // (which need the thread's own dwords only) built behind the loads
+        uint32_t v[NS];
+#pragma unroll
+        for (int k = 0; k < NS; k++)
         {
             const int i = tid + 256 * k, r = i / (FM_LW / 4), c4 = i - r * (FM_LW / 4);
             const int yy = by0 - 1 + r, col = bx0 - FM_HALO + 4 * c4;
-            if (i < (FM_R + 2) * (FM_LW / 4) && yy >= 0 && yy < height && col >= 0 && col < pitch)
+            v[k] = 0u;                                           // outside the plane: never looked at (the walks are clipped to the row)
+            if (i < NSTAGE && yy >= 0 && yy < height && col >= 0 && col < pitch)
                 v[k] = *reinterpret_cast<const uint32_t *>(Q.b + (size_t)yy * pitch + col);
         }
+        // the length class per byte: direction / 16 = (map >> 4) - 8, so a high nibble of 8 says "one step"
+        uint32_t c0[NJ], c1[NJ];
+        unsigned k0 = 0u, k1 = 0u;
 #pragma unroll
-        for (int k = 0; k < 2; k++)
-            if (tid + 256 * k < (FM_R + 2) * (FM_LW / 4)) reinterpret_cast<uint32_t *>(&s_d[0][0])[tid + 256 * k] = v[k];
+        for (int j = 0; j < NJ; j++)
+        {
+            c0[j] = (ff_bytes(~((own[j] & 0xf0f0f0f0u) ^ 0x80808080u)) >> 7) & cand[j];
+            c1[j] = cand[j] & ~c0[j];
+            k0 += (unsigned)__popc(c0[j]);
+            k1 += (unsigned)__popc(c1[j]);
+            *reinterpret_cast<uint32_t *>(&s_out[ty + 4 * j][4 * lane]) = own[j];
+        }
+        int a0 = wave_list_slots<NBITS>(&s_count[0], k0), a1 = NLIST - 1 - wave_list_slots<NBITS>(&s_count[1], k1);
+#pragma unroll
+        for (int j = 0; j < NJ; j++)
+        {
+            const uint32_t e = (uint32_t)((ty + 4 * j) << 8 | 4 * lane);
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+            {
+                if ((c0[j] >> (8 * k)) & 1u) s_list[a0++] = (uint16_t)(e + k);
+                if ((c1[j] >> (8 * k)) & 1u) s_list[a1--] = (uint16_t)(e + k);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < NS; k++)
+            if (tid + 256 * k < NSTAGE) reinterpret_cast<uint32_t *>(&s_d[0][0])[tid + 256 * k] = v[k];
     }
     __syncthreads();
-    if (!inside) return;
-    const uint8_t *rc = &s_d[threadIdx.y + 1][FM_HALO + 4 * threadIdx.x];
-    uint32_t out4 = own;
-    // Both walks of a pixel in one loop, neither with an early exit: the pixel turns peak when the walk above trips
-    // somewhere AND the walk below does (:565-627 take the second only after the first has tripped - the same verdict).
-    // With neg = min(dir, 0), pos = max(dir, 0) the four ranges of :565-620 are [max(-x, neg), min(w - x - 1, pos)] above
-    // and [max(-x, -pos), min(w - x - 1, -neg)] below; the shorter walk repeats its last step.
-#pragma unroll 1
-    for (int k = 0; k < 4; k++)
     {
-        if (!((cand >> (8 * k)) & 1u)) continue;
-        const int xx = x + k;
-        const uint8_t *dc = rc + k, *dp = dc - FM_LW, *dn = dc + FM_LW;
-        const uint32_t ref = dc[0];
-        int dir = ((int)ref - NEUTRAL) >> 2;
-        const int lim = max(iabs(dir) * 2, 12 << 2);
-        dir >>= 2;
-        const int neg = min(dir, 0), pos = max(dir, 0);
-        const int tf = max(-xx, neg), tt = min(width - xx - 1, pos), bf = max(-xx, -pos), bt = min(width - xx - 1, -neg);
-        const int n = max(tt - tf, bt - bf);
-        int any_t = 0, any_b = 0;
-        for (int i = 0; i <= n; i++)
+        // a lane per listed pixel, list after list, in chunks of 64 entries dealt to the four waves in turn: only the last
+        // chunk of a list is a wave that is not full
+        const int n0 = __builtin_amdgcn_readfirstlane(s_count[0]), n1 = __builtin_amdgcn_readfirstlane(s_count[1]);
+        const int w0 = (n0 + 63) >> 6, w1 = (n1 + 63) >> 6;
+        for (int ch = __builtin_amdgcn_readfirstlane(ty); ch < w0 + w1; ch += 4)
         {
-            const int jt = min(tf + i, tt), jb = min(bf + i, bt);
-            any_t |= fm_step(dp[jt], dc[jt], ref, lim);
-            any_b |= fm_step(dn[jb], dc[jb], ref, lim);
+            if (ch < w0)
+            {
+                const int i = 64 * ch + lane;
+                if (i < n0)
+                {
+                    const int e = s_list[i], r = e >> 8, lx = e & 255;
+                    if (fm_walk<true>(&s_d[r + 1][FM_HALO + lx], bx0 + lx, width)) s_out[r][lx] = (uint8_t)PEAK;
+                }
+            }
+            else
+            {
+                const int i = 64 * (ch - w0) + lane;
+                if (i < n1)
+                {
+                    const int e = s_list[NLIST - 1 - i], r = e >> 8, lx = e & 255;
+                    if (fm_walk<false>(&s_d[r + 1][FM_HALO + lx], bx0 + lx, width)) s_out[r][lx] = (uint8_t)PEAK;
+                }
+            }
         }
-        if ((any_t & any_b) < 0) out4 |= 0xffu << (8 * k);
     }
-    uint8_t *o = Q.c + (size_t)y * pitch + x;
-    if (x + 3 < width) *reinterpret_cast<uint32_t *>(o) = out4;
-    else for (int k = 0; k < 4 && x + k < width; k++) o[k] = (uint8_t)(out4 >> (8 * k));
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NJ; j++)
+        if (x < width && by0 + ty + 4 * j < height) store4(by0 + ty + 4 * j, *reinterpret_cast<const uint32_t *>(&s_out[ty + 4 * j][4 * lane]));
 }
 
 // eedi2_mark_directions_2x's vote (:800-868) for the two pixels at columns K and K + 1 of a thread's dword (K = 0 or 2), the
@@ -3159,7 +3257,7 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
         HBHIP_LAUNCH_ON(lc, st, "eedi2_expand_dir_map", k_dir_map_c, grid4_for(srcp, DC_ROWS), blk, 0, P);
     }
     bind(P.a, mskp); bind(P.b, tmpp); bind(P.c, dstp);
-    HBHIP_LAUNCH_ON(lc, st, "eedi2_filter_map", k_filter_map, grid4_for(srcp, 4), blk, 0, P);
+    HBHIP_LAUNCH_ON(lc, st, "eedi2_filter_map", k_filter_map<FM_ROWS>, grid4_for(srcp, FM_ROWS), blk, 0, P);
     // line doubling of srcp / dstp / mskp + mark_directions_2x in one launch (full-height geometry)
     geom(P, dst2p);
     bind(P.g, srcp); bind(P.b, dstp); bind(P.a, mskp);

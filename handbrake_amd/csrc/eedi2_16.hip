@@ -1279,8 +1279,8 @@ __global__ __launch_bounds__(256) void q_dir_map_fe(Q3 P, K16 k, int padv)
     }
 }
 
-// eedi2_filter_map (:538-635): a = mask, b = direction map in, c = out.  The form of the 8-bit kernel (eedi2.hip:
-// k_filter_map): a workgroup stages its 4 + 2 rows of the map (256 samples + 8 either side) in LDS with 8-byte loads, a
+// eedi2_filter_map (:538-635): a = mask, b = direction map in, c = out.  The form the 8-bit kernel (eedi2.hip:
+// k_filter_map) had before it listed its candidates (the lists are open here): a workgroup stages its 4 + 2 rows of the map (256 samples + 8 either side) in LDS with 8-byte loads, a
 // thread owns four samples of its row, and both walks of a sample run in ONE loop whose step test is sign arithmetic:
 // lim - |s - ref| is negative when s is off by more than lim, s - peak unless s is the peak, 2 peak - 1 - c - s only
 // when both are the peak; the step trips on the sign of (off(s) & notpeak(s)) | (off(c) & notpeak(c)) | bothpeak.
