@@ -2,12 +2,13 @@
 // same-size `scale` computes for the pair of pixel formats, in four forms:
 //
 //   format_kernel            the depth alone: libswscale's unscaled planar copy
-//   format_resample_kernel   fewer chroma samples at equal depth, and its SCALED form, a lower depth with or without them
+//   format_resample_kernel   fewer chroma samples at equal depth, its SCALED form, a lower depth with or without them,
+//                            and its DEEPEN form, fewer chroma samples at a higher depth
 //   format_upsample_kernel   more chroma samples at equal or higher depth
 //
 // The last three are libswscale's general scaler at its default flags, bicubic.  PARITY UNPINNED: libswscale is not in
 // the reference tree; the kernels are bit-exact against OUR restatements (oracle/alias_oracle.c:orc_format_plane,
-// tests/format_resample_model.py, format_scaled_model.py, format_upsample_model.py).
+// tests/format_resample_model.py, format_scaled_model.py, format_upsample_model.py, format_deepen_model.py).
 #include "hbhip_internal.h"
 
 #include <type_traits>
@@ -206,6 +207,14 @@ __device__ __forceinline__ void fr_load_pairs(const PIX *row, int x0, int w, uin
     }
 }
 
+// four samples as they were loaded - a dword of bytes, a qword of 16-bit samples - as two dwords of 16-bit pairs
+__device__ __forceinline__ void fr_widen(uint32_t d, uint32_t *p)
+{
+    p[0] = __builtin_amdgcn_perm(0u, d, 0x0c010c00u);
+    p[1] = __builtin_amdgcn_perm(0u, d, 0x0c030c02u);
+}
+__device__ __forceinline__ void fr_widen(uint2 d, uint32_t *p) { p[0] = d.x; p[1] = d.y; }
+
 template <typename PIX>
 __device__ __forceinline__ void fr_store4(PIX *row, int x0, int w, const int *o)
 {
@@ -297,18 +306,27 @@ __device__ __forceinline__ void fs_identity_rows(const Args &a, int f, int c, in
 // Luma is no copy then but the identity filter and the output stage, and so are Cb and Cr where neither pass is taken
 // (4:2:0 -> 4:2:0, the planar step in front of the NV12 / P010LE repack).
 // The equal-depth instantiations take the defaults and compile to the instructions they had before the form existed.
+//
+// DEEP (with SC): the deepen form, fewer chroma samples at a HIGHER target depth - 8 -> 10, 8 -> 12 (PIX a byte), 10 -> 12
+// bits, DPIX 16 bits, always with a pass (Args: FormatScalerArgs, nothing is dithered).  What an encoder whose list holds
+// only 10-bit formats gets behind an 8-bit 4:2:2 / 4:4:4 title (work.c:1525-1552, the second match_pix_fmt call).  The
+// chroma passes again, hScale8To15 / hScale16To15 by the source and the flat round term of the target's yuv2planeX_10 /
+// _12; luma through the identity and yuv2plane1_10 / _12, whose shift follows the target there: v << (ddepth - sdepth).
+// Its horizontal pass loads a thread's sixteen samples ahead of one wait where all of them lie inside the plane (hpair).
 constexpr int FR_TAPS = FS_DOWN.frame.taps, FR_BASE = FS_DOWN.frame.base;
-template <typename PIX, bool HP, bool VP, typename DPIX = PIX, bool SC = false, class Args = FormatScalerArgs>
+template <typename PIX, bool HP, bool VP, typename DPIX = PIX, bool SC = false, class Args = FormatScalerArgs, bool DEEP = false>
 __global__ __launch_bounds__(256, 4) void format_resample_kernel(Args a)
 {
     static_assert(SC || ((HP || VP) && std::is_same<PIX, DPIX>::value), "equal depth: one pass at least, one sample type");
+    static_assert(!DEEP || (SC && (HP || VP) && sizeof(DPIX) == 2), "deepen: one pass at least, a 16-bit target");
     const int f = blockIdx.z;
     const int x0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
     const int ddepth = SC ? a.ddepth : a.sdepth;
     if constexpr (SC)
     {
-        // the planes that take no pass: hScale16To15's one tap, v << (15 - depth), then yuv2plane1_8 - (t + dither) >> 7 -
-        // or yuv2plane1_10, (t + 16) >> 5, clipped at the top (nothing is negative here)
+        // the planes that take no pass: hScale16To15's one tap, v << (15 - depth) (hScale8To15's v << 7 is the same at 8
+        // bits), then yuv2plane1_8 - (t + dither) >> 7 - or yuv2plane1_10, (t + 16) >> 5, clipped at the top (nothing is
+        // negative here).  The scaled form's one 16-bit target has 10 bits, a constant; the deepen form's shift is the target's.
         const bool luma = (int)blockIdx.y < a.ly;
         if (luma || (!HP && !VP))
         {
@@ -317,10 +335,11 @@ __global__ __launch_bounds__(256, 4) void format_resample_kernel(Args a)
             const int w = luma ? a.w : a.dcw, h = luma ? a.h : a.dch;
             if (x0 >= w || y0 >= h) return;
             const int up = 15 - a.sdepth, vmax = (1 << ddepth) - 1;
+            const int down = 15 - (DEEP ? ddepth : 10);
             fs_identity_rows<PIX, DPIX>(a, f, c, x0, y0, w, h, [&](int y, int i, int v) __attribute__((always_inline)) {
                 const int t = v << up;
-                if (sizeof(DPIX) == 1) return min((t + (int)((fr_dither4(a, y, x0, c == 2) >> (8 * i)) & 0xffu)) >> 7, vmax);
-                return min((t + 16) >> 5, vmax);
+                if constexpr (sizeof(DPIX) == 1) return min((t + (int)((fr_dither4(a, y, x0, c == 2) >> (8 * i)) & 0xffu)) >> 7, vmax);
+                else                             return min((t + (1 << (down - 1))) >> down, vmax);
             });
             return;
         }
@@ -367,11 +386,37 @@ __global__ __launch_bounds__(256, 4) void format_resample_kernel(Args a)
         if (HP)
         {
             uint32_t pa[8], pb[8];                                           // the sixteen samples under the four columns, in pairs
-#pragma unroll
-            for (int g = 0; g < 4; g++)
+            const int s0 = 2 * x0 + FR_BASE;
+            if (DEEP && s0 >= 0 && s0 + 15 < a.scw)
             {
-                fr_load_pairs(ra, 2 * x0 + FR_BASE + 4 * g, a.scw, pa + 2 * g);
-                fr_load_pairs(rb, 2 * x0 + FR_BASE + 4 * g, a.scw, pb + 2 * g);
+                // the deepen form, all sixteen samples inside the plane: fr_load_pairs' first arm without its test, so that
+                // the eight loads of a turn go out ahead of ONE wait (each arm of the general form below keeps its load
+                // and a wait to itself, and a turn is a chain of eight round trips to memory)
+                typedef typename std::conditional<sizeof(PIX) == 1, uint32_t, uint2>::type V;
+                V da[4], db[4];
+#pragma unroll
+                for (int g = 0; g < 4; g++)
+                {
+                    da[g] = *reinterpret_cast<const V *>(ra + s0 + 4 * g);
+                    db[g] = *reinterpret_cast<const V *>(rb + s0 + 4 * g);
+                }
+#pragma unroll
+                for (int g = 0; g < 4; g++)
+                {
+                    fr_widen(da[g], pa + 2 * g);
+                    fr_widen(db[g], pb + 2 * g);
+                }
+            }
+            else
+            {
+                // (the position spelt as it always was, not s0 + 4 * g: the other association changes the instructions
+                // of every instantiation with a horizontal pass)
+#pragma unroll
+                for (int g = 0; g < 4; g++)
+                {
+                    fr_load_pairs(ra, 2 * x0 + FR_BASE + 4 * g, a.scw, pa + 2 * g);
+                    fr_load_pairs(rb, 2 * x0 + FR_BASE + 4 * g, a.scw, pb + 2 * g);
+                }
             }
 #pragma unroll
             for (int i = 0; i < 4; i++)
@@ -696,6 +741,14 @@ public:
             HBHIP_LAUNCH(ctx, "format_scaled", (format_resample_kernel<uint16_t, hp.value, vp.value, DPIX, true, FormatScaledArgs>), grid, dim3(64, 4), 0, a);
         });
     }
+    template <typename PIX>
+    int run_deepen(DevPicture *const *ins, DevPicture *const *outs, int n)
+    {
+        return run<FormatScalerArgs>(ins, outs, n, [&](FormatScalerArgs &a, dim3 grid, auto hp, auto vp) {
+            if constexpr (hp.value || vp.value)
+                HBHIP_LAUNCH(ctx, "format_deepen", (format_resample_kernel<PIX, hp.value, vp.value, uint16_t, true, FormatScalerArgs, true>), grid, dim3(64, 4), 0, a);
+        });
+    }
     template <typename PIX, typename DPIX>
     int run_up(DevPicture *const *ins, DevPicture *const *outs, int n)
     {
@@ -709,6 +762,7 @@ public:
         const bool s8 = in_geo.bps == 1, d8 = out_geo.bps == 1;
         if (dir.up)
             return d8 ? run_up<uint8_t, uint8_t>(ins, outs, n) : s8 ? run_up<uint8_t, uint16_t>(ins, outs, n) : run_up<uint16_t, uint16_t>(ins, outs, n);
+        if (out_geo.depth > in_geo.depth) return s8 ? run_deepen<uint8_t>(ins, outs, n) : run_deepen<uint16_t>(ins, outs, n);
         if (out_geo.depth != in_geo.depth)                                   // the scaled form, with or without a pass
             return d8 ? run_scaled<uint8_t>(ins, outs, n) : run_scaled<uint16_t>(ins, outs, n);
         return s8 ? run_down<uint8_t>(ins, outs, n) : run_down<uint16_t>(ins, outs, n);
@@ -718,11 +772,12 @@ public:
     short *d_hq = nullptr, *d_vq = nullptr;
 };
 
-// Behind the three scaler create functions.  Down: no dimension gains chroma samples, the depth does not grow, and one
+// Behind the four scaler create functions.  Down: no dimension gains chroma samples, the depth does not grow, and one
 // of the three shrinks (src_depth == dst_depth is the chroma down-sampling, else the scaled form).  Up: all of it the
-// other way round, and one DIMENSION gains - the depth alone is hbhip_format_create's.
+// other way round, and one DIMENSION gains - the depth alone is hbhip_format_create's.  deepen (down only): the depth
+// GROWS and one dimension loses chroma samples.
 int format_scaler_make(hbhip_ctx *ctx, const FsDirection &dir, int width, int height, int src_depth, int dst_depth,
-                       int src_log2_cw, int src_log2_ch, int dst_log2_cw, int dst_log2_ch, hbhip_filter **out)
+                       int src_log2_cw, int src_log2_ch, int dst_log2_cw, int dst_log2_ch, hbhip_filter **out, bool deepen = false)
 {
     if (!ctx || !out) return HBHIP_ERR_ARG;
     *out = nullptr;
@@ -732,7 +787,8 @@ int format_scaler_make(hbhip_ctx *ctx, const FsDirection &dir, int width, int he
     if (!hbhip_yuv_layout_ok(src_log2_cw, src_log2_ch) || !hbhip_yuv_layout_ok(dst_log2_cw, dst_log2_ch)) return HBHIP_ERR_UNSUPPORTED;
     const int s = dir.up ? -1 : 1;
     const int pw = s * (dst_log2_cw - src_log2_cw), ph = s * (dst_log2_ch - src_log2_ch), pd = s * (src_depth - dst_depth);
-    if (pw < 0 || ph < 0 || pd < 0 || (!pw && !ph && (dir.up || !pd))) return HBHIP_ERR_UNSUPPORTED;
+    if (deepen ? pw < 0 || ph < 0 || pd >= 0 || (!pw && !ph)
+               : pw < 0 || ph < 0 || pd < 0 || (!pw && !ph && (dir.up || !pd))) return HBHIP_ERR_UNSUPPORTED;
     PicGeometry gi, go;
     gi.set(width, height, src_depth, src_log2_cw, src_log2_ch);
     go.set(width, height, dst_depth, dst_log2_cw, dst_log2_ch);
@@ -783,4 +839,11 @@ extern "C" int hbhip_format_upsample_create(hbhip_ctx *ctx, int width, int heigh
 {
     (void)chroma_location;
     return format_scaler_make(ctx, FS_UP, width, height, src_depth, dst_depth, src_log2_cw, src_log2_ch, dst_log2_cw, dst_log2_ch, out);
+}
+
+extern "C" int hbhip_format_deepen_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
+                                          int src_log2_ch, int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out)
+{
+    (void)chroma_location;
+    return format_scaler_make(ctx, FS_DOWN, width, height, src_depth, dst_depth, src_log2_cw, src_log2_ch, dst_log2_cw, dst_log2_ch, out, true);
 }

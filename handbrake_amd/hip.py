@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "hbhip_comb_detect_create", "hbhip_comb_detect_set_gamma_lut", "hbhip_comb_detect_store",
     "hbhip_comb_detect_store_dev",
     "hbhip_comb_detect_classify", "hbhip_comb_detect_classify_many_dev", "hbhip_comb_detect_overlay", "hbhip_comb_detect_overlay_dev",
-    "hbhip_rotate_create", "hbhip_grayscale_create", "hbhip_cropscale_create", "hbhip_cropscale_create_sited", "hbhip_colorspace_create", "hbhip_colorspace_create_sited", "hbhip_pad_create", "hbhip_yadif_create", "hbhip_bwdif_create", "hbhip_format_create", "hbhip_format_resample_create", "hbhip_format_scaled_create", "hbhip_format_upsample_create",
+    "hbhip_rotate_create", "hbhip_grayscale_create", "hbhip_cropscale_create", "hbhip_cropscale_create_sited", "hbhip_colorspace_create", "hbhip_colorspace_create_sited", "hbhip_pad_create", "hbhip_yadif_create", "hbhip_bwdif_create", "hbhip_format_create", "hbhip_format_resample_create", "hbhip_format_scaled_create", "hbhip_format_upsample_create", "hbhip_format_deepen_create",
     "hbhip_blend_create", "hbhip_blend_set_overlays", "hbhip_blend_apply", "hbhip_blend_apply_dev", "hbhip_blend_destroy",
     "hbhip_blend_create_biplanar", "hbhip_blend_apply_biplanar",
     "hbhip_blend_set_ass_images", "hbhip_blend_debug_overlay_count", "hbhip_blend_debug_get_overlay",
@@ -685,6 +685,13 @@ def format_scaled_device_filter(ctx, width, height, src=(1, 0), dst=(1, 1), src_
     """format's scaler pass to a lower depth, with or without fewer chroma samples: src / dst = (log2_chroma_w,
     log2_chroma_h) of the stream and of the target"""
     return _create("hbhip_format_scaled_create", ctx, [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_void_p)],
+                   ctx.h, width, height, src_depth, dst_depth, src[0], src[1], dst[0], dst[1], chroma_location)
+
+
+def format_deepen_device_filter(ctx, width, height, src=(1, 0), dst=(1, 1), src_depth=8, dst_depth=10, chroma_location=1):
+    """format's scaler pass to FEWER chroma samples at a higher depth: src / dst = (log2_chroma_w, log2_chroma_h) of the
+    stream and of the target"""
+    return _create("hbhip_format_deepen_create", ctx, [C.c_void_p] + [C.c_int] * 9 + [C.POINTER(C.c_void_p)],
                    ctx.h, width, height, src_depth, dst_depth, src[0], src[1], dst[0], dst[1], chroma_location)
 
 

@@ -235,10 +235,19 @@ static int rotate_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
  *     4:4:4 formats (x264 high422 / high444, x265 main422-10 / -12 / main444-8, common.c:2252-2384; ProRes, DNxHR) the
  *     two chroma-keeping match_pix_fmt calls of work.c:1525-1552 find nothing and the third, match_pix_fmt(..., 0, 0),
  *     returns the list's first entry: `format=yuv422p10le` behind a yuv420p chain.
+ *   - planar YUV chroma DOWN-sampling together with a HIGHER depth, 8 -> 10, 8 -> 12, 10 -> 12 bits (format_resample_kernel's
+ *     deepen form), when hip_common.c has marked the entry with HBHIP_FORMAT_DEEPEN_STEP, again behind another drop-in of
+ *     a device-resident run.  The reference asks for this too: an 8-bit 4:2:2 / 4:4:4 title runs as yuv422p / yuv444p
+ *     (common.c:7516-7604), and for an encoder whose list holds only 10-bit formats - SVT-AV1 10-bit (common.c:2267-2270,
+ *     2397-2398) and VP9 10-bit (encavcodec.c:281-284, 2357-2358): yuv420p10le; ProRes and DNxHR 10-bit
+ *     (encavcodec.c:286-289, 2384-2409): yuv422p10le - work.c's first match, which keeps chroma and depth, finds nothing
+ *     and the second, match_pix_fmt(..., 1, 0), takes any entry with no more chroma whatever its depth:
+ *     `format=yuv420p10le` behind a yuv422p or yuv444p chain, `format=yuv422p10le` behind a yuv444p one.
  * Any other target makes init() fail, which keeps the CPU filter (work.c:1861-1868): more chroma samples than the
- * stream has where nobody marked the entry (a lone `format` on host frames would pay a round trip over the bus for a
- * cheap filter), fewer chroma samples together with a HIGHER depth, semi-planar targets that nobody marked (a lone
- * `format=nv12` has no adapter to repack for it), RGB, a chroma plane too small for swscale's taps (nine down, five up). */
+ * stream has, or fewer at a higher depth, where nobody marked the entry (a lone `format` on host frames would pay a
+ * round trip over the bus for a cheap filter), semi-planar targets that nobody marked (a lone `format=nv12` has no
+ * adapter to repack for it) or above the stream's depth on 4:2:2 / 4:4:4 frames, RGB, a chroma plane too small for
+ * swscale's taps (nine down, five up). */
 static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
 static int format_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
 
@@ -301,8 +310,14 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     hb_dict_extract_bool(&upsample, filter->settings, HBHIP_FORMAT_UP_STEP);
     upsample = upsample && pv->s.dev_io && !planar_step && resample && ddepth >= sdepth &&
                dd->log2_chroma_w <= desc->log2_chroma_w && dd->log2_chroma_h <= desc->log2_chroma_h;
-    /* fewer chroma samples AND a higher depth: nothing asks for it; a biplanar target above the stream's depth neither */
-    if (!upsample && (resample || planar_step) && ddepth > sdepth)
+    /* and its mark on an entry inside a run whose target has fewer chroma samples at a HIGHER depth: no dimension gains
+     * any, one loses.  Declined below without the mark, like the up step. */
+    int deepen = 0;
+    hb_dict_extract_bool(&deepen, filter->settings, HBHIP_FORMAT_DEEPEN_STEP);
+    deepen = deepen && pv->s.dev_io && !planar_step && resample && ddepth > sdepth &&
+             dd->log2_chroma_w >= desc->log2_chroma_w && dd->log2_chroma_h >= desc->log2_chroma_h;
+    /* a higher depth with another chroma layout that nobody marked; a biplanar target above the stream's depth */
+    if (!upsample && !deepen && (resample || planar_step) && ddepth > sdepth)
         return hbhip_host_simple_fail(filter, HBHIP_ERR_UNSUPPORTED);
     if (planar_step && !resample && ddepth == sdepth)
     {
@@ -317,6 +332,9 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     int rc = upsample ? hbhip_format_upsample_create(ctx, init->geometry.width, init->geometry.height, sdepth, ddepth,
                                                      desc->log2_chroma_w, desc->log2_chroma_h, dd->log2_chroma_w,
                                                      dd->log2_chroma_h, init->chroma_location, &pv->s.dev)
+           : deepen   ? hbhip_format_deepen_create(ctx, init->geometry.width, init->geometry.height, sdepth, ddepth,
+                                                   desc->log2_chroma_w, desc->log2_chroma_h, dd->log2_chroma_w,
+                                                   dd->log2_chroma_h, init->chroma_location, &pv->s.dev)
            : scaled   ? hbhip_format_scaled_create(ctx, init->geometry.width, init->geometry.height, sdepth, ddepth,
                                                    desc->log2_chroma_w, desc->log2_chroma_h, dd->log2_chroma_w,
                                                    dd->log2_chroma_h, init->chroma_location, &pv->s.dev)

@@ -46,6 +46,11 @@ static inline int hbhip_host_is_biplanar(int pix_fmt) { return pix_fmt == HBHIP_
  * does the adapter take format=p010le on an 8-bit run; it is no part of its settings template.  Stripped wherever the
  * other two are. */
 #define HBHIP_FORMAT_WIDEN_STEP "hip-widen-step"
+/* The fourth: on a `format=yuv420p10le | yuv422p10le | ...` entry inside a run whose target has FEWER chroma samples than
+ * the job's frames and a HIGHER depth (an 8-bit 4:2:2 / 4:4:4 title in front of a 10-bit software encoder).  As with the up
+ * step, the Format drop-in takes such a target only where this key stands, i.e. where the frames already are in HBM.
+ * Stripped wherever the other three are. */
+#define HBHIP_FORMAT_DEEPEN_STEP "hip-deepen-step"
 static inline void hbhip_host_biplanar_from_buf(hbhip_host_biplanar *f, const hb_buffer_t *b)
 {
     for (int p = 0; p < 2; p++)

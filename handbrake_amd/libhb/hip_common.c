@@ -15,7 +15,9 @@
  *      marks a `format=yuv422p... | yuv444p...` entry behind a drop-in whose target has MORE chroma samples than the job's
  *      frames (HBHIP_FORMAT_UP_STEP): the Format drop-in takes such a target only there.  And `format=p010le` behind a
  *      drop-in of a yuv420p or nv12 job (HBHIP_FORMAT_WIDEN_STEP): the Format drop-in passes the 8-bit frames through and
- *      the download adapter, given format=p010le and the same key, widens them inside its repack.
+ *      the download adapter, given format=p010le and the same key, widens them inside its repack.  And a planar
+ *      `format=yuv420p10le | yuv422p10le | ...` entry behind a drop-in whose target has FEWER chroma samples than the job's
+ *      frames and a higher depth (HBHIP_FORMAT_DEEPEN_STEP), taken only there like the up step.
  * And one thing the VideoToolbox path does not need: a drop-in's init() may refuse settings it has no kernels for.
  * work.c drops a filter whose init fails (:1861-1868) - for a drop-in that would silently lose the filter, so the init
  * loop calls hb_hip_filter_init_failed() first, which puts the CPU filter back (and re-brackets the run around it).
@@ -97,12 +99,13 @@ static int planar_step_target(const hb_filter_object_t *f, int *widen)
     return hbhip_host_is_biplanar(fmt) ? fmt : AV_PIX_FMT_NONE;
 }
 
-/* the three keys of mark_planar_steps(): nothing a CPU filter knows, and stale once the list in front has changed */
+/* the four keys of mark_planar_steps(): nothing a CPU filter knows, and stale once the list in front has changed */
 static void remove_marks(hb_dict_t *settings)
 {
     hb_dict_remove(settings, HBHIP_FORMAT_PLANAR_STEP);
     hb_dict_remove(settings, HBHIP_FORMAT_UP_STEP);
     hb_dict_remove(settings, HBHIP_FORMAT_WIDEN_STEP);
+    hb_dict_remove(settings, HBHIP_FORMAT_DEEPEN_STEP);
 }
 
 /* work.c appends `format=nv12` / `format=p010le` when the encoder wants one of them (work.c:1525-1552, match_pix_fmt).
@@ -128,7 +131,15 @@ static void remove_marks(hb_dict_t *settings)
  * above the title's depth, common.c:7516-7524).  On a yuv420p job and on an nv12 job alike - the upload adapter of an nv12
  * job's run makes yuv420p frames, and this is the one mark such a job gets - under the same condition, a drop-in in front.
  * The Format drop-in passes the frames through and the run's download adapter widens them inside its repack.  8-bit
- * 4:2:2 / 4:4:4 under p010le stay unmarked: the scaler from an 8-bit source is not built. */
+ * 4:2:2 / 4:4:4 under p010le stay unmarked: the planar step from an 8-bit source in front of the repack is not built.
+ *
+ * And the DEEPEN step (HBHIP_FORMAT_DEEPEN_STEP): `format=yuv420p10le` behind a yuv422p or yuv444p chain, `format=yuv422p10le`
+ * behind a yuv444p one.  An 8-bit 4:2:2 / 4:4:4 title runs at its own depth and chroma (common.c:7516-7604); an encoder
+ * whose list holds only 10-bit formats (SVT-AV1 10-bit, common.c:2267-2270; VP9, ProRes and DNxHR 10-bit,
+ * encavcodec.c:281-289) fails work.c's first match and passes the second, match_pix_fmt(..., 1, 0): any entry with no
+ * more chroma, whatever its depth.  Such an entry - a planar YUV 4:2:0 / 4:2:2 / 4:4:4 target at 10 or 12 bits that gains
+ * chroma samples in no dimension, loses them in one at least and is deeper than the job - is marked under the same
+ * condition, a drop-in in front of it; without the mark the Format drop-in declines it as before. */
 static void mark_planar_steps(hb_job_t *job, int from)
 {
     hb_list_t *list = job->list_filter;
@@ -159,6 +170,12 @@ static void mark_planar_steps(hb_job_t *job, int from)
                 (dd->log2_chroma_w < desc->log2_chroma_w || dd->log2_chroma_h < desc->log2_chroma_h) &&
                 dd->comp[0].depth >= desc->comp[0].depth)
                 key = HBHIP_FORMAT_UP_STEP;
+            /* the deepen step: the other way round in chroma - gains in no dimension, loses in one at least - at 10 or 12
+             * bits and deeper than the job's frames */
+            else if (hbhip_host_planar_yuv(dd) && dd->log2_chroma_w >= desc->log2_chroma_w && dd->log2_chroma_h >= desc->log2_chroma_h &&
+                     (dd->log2_chroma_w > desc->log2_chroma_w || dd->log2_chroma_h > desc->log2_chroma_h) &&
+                     (dd->comp[0].depth == 10 || dd->comp[0].depth == 12) && dd->comp[0].depth > desc->comp[0].depth)
+                key = HBHIP_FORMAT_DEEPEN_STEP;
         }
         if (key == NULL) continue;
         int j = i - 1;

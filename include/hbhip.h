@@ -574,6 +574,19 @@ int hbhip_format_scaled_create(hbhip_ctx *ctx, int width, int height, int src_de
  * (libswscale shortens its filter there).  Arithmetic pinned to tests/format_upsample_model.py only (parity unpinned). */
 int hbhip_format_upsample_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
                                  int src_log2_ch, int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out);
+/* FEWER chroma samples together with a HIGHER depth: 4:2:2 -> 4:2:0, 4:4:4 -> 4:2:2, 4:4:4 -> 4:2:0 at 8 -> 10, 8 -> 12 or
+ * 10 -> 12 bits.  What an encoder whose list holds only 10-bit formats (SVT-AV1 and VP9 10-bit: yuv420p10le; ProRes and
+ * DNxHR 10-bit: yuv422p10le) gets behind an 8-bit 4:2:2 / 4:4:4 title (work.c:1525-1552: the second match_pix_fmt call
+ * takes any format with no more chroma, whatever its depth).  The general scaler of hbhip_format_resample_create, same
+ * tables and siting: the horizontal pass or its identity by the SOURCE depth (hScale8To15: >> 7; hScale16To15:
+ * >> (src_depth - 1); 15-bit intermediates, saturated at the top only), the output stage by the TARGET's
+ * (yuv2planeX_10 / _12: the flat half of the shift 27 - dst_depth, no dither), clipped to [0, 2^dst_depth - 1].  Luma is
+ * v << (dst_depth - src_depth) in both ranges, no top-bit replication: 255 -> 1020.  No range conversion.
+ * `chroma_location`: every value is taken as left-sited.  HBHIP_ERR_UNSUPPORTED: an equal or lower target depth, a depth
+ * outside 8 / 10 / 12, equal subsampling, more chroma samples in either direction, a chroma plane under 11 samples in a
+ * direction that is resampled.  Arithmetic pinned to tests/format_deepen_model.py only (parity unpinned). */
+int hbhip_format_deepen_create(hbhip_ctx *ctx, int width, int height, int src_depth, int dst_depth, int src_log2_cw,
+                               int src_log2_ch, int dst_log2_cw, int dst_log2_ch, int chroma_location, hbhip_filter **out);
 /* The zscale [-> format=gbrpf32le -> tonemap] -> zscale -> format graph colorspace_init builds
  * (colorspace.c:126-193): matrix / range / transfer / primaries conversion, with tone mapping
  * when the source transfer is SMPTE 2084 or ARIB STD-B67 and the transfer changes.  Colour ids

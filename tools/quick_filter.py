@@ -3,6 +3,7 @@
 usage: quick_filter.py unsharp|chroma_smooth|lapsharp|colorspace_sdr|colorspace_matrix|colorspace_pq[_loc<0..6>]|grayscale|rotate|scale<W>x<H>|
                       format8to10|format10to8|format_422_420[_10]|format_444_422[_10]|format_444_420[_10]|
                       format_<444|422|420>_<422|420>_<10to8|12to8|12to10> (a lower depth; 420_420: the depth alone)|
+                      format_<444|422>_<422|420>_<8to10|8to12|10to12> (fewer chroma samples at a higher depth)|
                      format_<420|422>_<422|444>_up[_10|_8to10|_8to12|_10to12] (more chroma samples, equal or higher depth)|
                       deblock_<preset>_<tune>[_10]|deband[_<range>][_10][_tile|_gather]|bm3d[_<sigma>][_10] [reps]
 Prints one line per kernel: name, launches, average us.  For knob experiments with tools/dev_run.sh."""
@@ -99,7 +100,10 @@ def main():
             make = lambda: hip.format_upsample_device_filter(ctx, W, H, sub_in, sub_out, depth_in, depth_out)
         elif "to" in parts[-1]:                         # format_422_420_10to8, format_420_420_12to10 ...: the scaled form
             depth_in, depth_out = (int(v) for v in parts[-1].split("to"))
-            make = lambda: hip.format_scaled_device_filter(ctx, W, H, sub_in, sub_out, depth_in, depth_out)
+            if depth_out > depth_in:                   # format_422_420_8to10, format_444_422_10to12 ...: the deepen form
+                make = lambda: hip.format_deepen_device_filter(ctx, W, H, sub_in, sub_out, depth_in, depth_out)
+            else:
+                make = lambda: hip.format_scaled_device_filter(ctx, W, H, sub_in, sub_out, depth_in, depth_out)
         else:
             depth_in = depth_out = 10 if parts[-1] == "10" else 8
             make = lambda: hip.format_resample_device_filter(ctx, W, H, sub_in, sub_out, depth_in)
