@@ -713,3 +713,33 @@ def motion_metric_run(lib, symbol, luma_a, luma_b, pix_fmt=AV_PIX_FMT_YUV420P) -
     if rc != 0:
         raise RuntimeError(f"hbh_motion_metric_run({symbol}) failed ({rc})")
     return out.value
+
+
+def scan_run(lib, planes, flags: int = 0, open_size=None, frame=None, surface=None, pix_fmt=None):
+    """One preview through the title scan's helper of `lib` (hb_hip_scan_open / _picture / _close, libhb/scan_hip.c), the
+    way scan.c:972-1052 would use it.  planes: the (Y, Cb, Cr) host picture; frame / surface: a hip.Frame / hip.Surface in
+    its place - the buffer takes the object's reference over - with planes giving the size only.  open_size: the (width,
+    height) the helper is opened for, the picture's by default.  Returns (rc, (combed, top, bottom, left, right, recorded)):
+    rc 0, 1 when open declined, 2 when picture did."""
+    rt = runtime()
+    rt.hbh_scan_run.restype = C.c_int
+    rt.hbh_scan_run.argtypes = [C.c_void_p] * 3 + [C.c_int] * 5 + [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p,
+                                C.c_int, C.c_int, C.POINTER(C.c_int)]
+    planes = [np.ascontiguousarray(p) for p in planes]
+    h, w = planes[0].shape
+    ow, oh = open_size if open_size is not None else (w, h)
+    ptrs = (C.c_void_p * 3)(*[p.ctypes.data for p in planes])
+    strides = (C.c_int * 3)(*[p.strides[0] for p in planes])
+    storage, kind = None, 0
+    if frame is not None:
+        storage, kind, frame.h = frame.h, 1, None
+    elif surface is not None:
+        storage, kind, surface.h = surface.h, 2, None
+    if pix_fmt is None:
+        pix_fmt = AV_PIX_FMT_NV12 if kind == 2 else AV_PIX_FMT_YUV420P
+    fns = [C.cast(getattr(lib, n), C.c_void_p) for n in ("hb_hip_scan_open", "hb_hip_scan_picture", "hb_hip_scan_close")]
+    out = (C.c_int * 6)()
+    rc = rt.hbh_scan_run(*fns, pix_fmt, ow, oh, w, h, ptrs, strides, storage, kind, flags, out)
+    if rc < 0:
+        raise RuntimeError(f"hbh_scan_run failed ({rc})")
+    return rc, tuple(out)

@@ -47,6 +47,7 @@ ABI_SYMBOLS = [
     "hbhip_deblock_create", "hbhip_deblock_set_warmup",
     "hbhip_deband_create", "hbhip_deband_offsets", "hbhip_deband_set_kernel",
     "hbhip_bm3d_params_from_settings", "hbhip_bm3d_create",
+    "hbhip_scan_create", "hbhip_scan_destroy", "hbhip_scan_push", "hbhip_scan_pull", "hbhip_scan_inflight",
 ]
 
 
@@ -97,6 +98,24 @@ class Bm3dParams(C.Structure):
     _fields_ = [("sigma", C.c_float)] + [(n, C.c_int) for n in ("block", "bstep", "group", "range", "mstep")] + \
                [("thmse", C.c_float), ("hdthr", C.c_float), ("estim", C.c_int), ("planes", C.c_int),
                 ("thr", C.c_float * 3), ("dct", C.c_float * 256)]
+
+
+class ScanParams(C.Structure):
+    """hbhip_scan_params: hb_detect_comb's six sensitivities (scan.c:973 passes 10, 30, 9, 10, 30, 9)"""
+    _fields_ = [(n, C.c_int) for n in ("color_equal", "color_diff", "threshold", "prog_equal", "prog_diff", "prog_threshold")]
+
+
+class ScanResult(C.Structure):
+    """hbhip_scan_result: a preview's crop, whether scan.c would record it, hb_detect_comb's scores and verdict"""
+    _fields_ = [(n, C.c_int) for n in ("top", "bottom", "left", "right", "recorded")] + \
+               [("cc", C.c_int * 3), ("average_cc", C.c_int), ("combed", C.c_int)]
+
+    def as_tuple(self):
+        return (self.top, self.bottom, self.left, self.right, self.recorded, tuple(self.cc), self.average_cc, self.combed)
+
+
+SCAN_INFLIGHT_MAX = 32      #: HBHIP_SCAN_INFLIGHT_MAX
+SCAN_RECORD_BYTES = 48      #: HBHIP_SCAN_RECORD_BYTES: what a scanned picture sends over the bus
 
 
 _lib = None
@@ -187,6 +206,12 @@ def lib() -> C.CDLL:
         L.hbhip_filter_use_frames.argtypes = [C.c_void_p]
         L.hbhip_decomb_push_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
         L.hbhip_bm3d_params_from_settings.argtypes = [C.c_char_p, C.c_int, C.POINTER(Bm3dParams)]
+        L.hbhip_scan_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.hbhip_scan_destroy.argtypes = [C.c_void_p]
+        L.hbhip_scan_destroy.restype = None
+        L.hbhip_scan_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ScanParams)]
+        L.hbhip_scan_pull.argtypes = [C.c_void_p, C.POINTER(ScanResult)]
+        L.hbhip_scan_inflight.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -387,6 +412,37 @@ class Surface:
     def close(self):
         if self.h:
             lib().hbhip_surface_release(self.h)
+            self.h = None
+
+
+class ScanDevice:
+    """The title scan's analysis of device pictures (hbhip_scan_*): crop and combing of 8-bit 4:2:0 previews."""
+
+    def __init__(self, ctx: Ctx, width, height):
+        h = C.c_void_p()
+        check(lib().hbhip_scan_create(ctx.h, width, height, C.byref(h)), ctx.h, "scan_create")
+        self.ctx, self.h = ctx, h
+
+    def push_rc(self, frame: Frame, flags: int = 0, params=None) -> int:
+        """the raw return code (the refusals are part of the interface)"""
+        p = C.byref(ScanParams(*params)) if params is not None else None
+        return lib().hbhip_scan_push(self.h, frame.h, flags, p)
+
+    def push(self, frame: Frame, flags: int = 0, params=None):
+        check(self.push_rc(frame, flags, params), self.ctx.h, "scan_push")
+
+    def pull(self):
+        """the oldest picture's ScanResult, or None when nothing is in flight"""
+        r = ScanResult()
+        rc = check(lib().hbhip_scan_pull(self.h, C.byref(r)), self.ctx.h, "scan_pull")
+        return None if rc == HBHIP_AGAIN else r
+
+    def inflight(self) -> int:
+        return lib().hbhip_scan_inflight(self.h)
+
+    def close(self):
+        if self.h:
+            lib().hbhip_scan_destroy(self.h)
             self.h = None
 
 

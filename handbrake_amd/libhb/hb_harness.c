@@ -987,3 +987,45 @@ int hbh_motion_metric_run(const void *proto, int pix_fmt, int width, int height,
     metric.close(&metric);
     return 0;
 }
+
+/* ---- the title scan's helper (scan_hip.c) ----------------------------------------------------
+ * scan.c's part around one preview (:972-1052 with the INTEGRATION.md hook): open for the preview size, picture() on the
+ * buffer, close.  The buffer is a copy of the caller's planes, or the shell a device-resident decoder puts around a picture
+ * in HBM: an hbhip_frame (storage 1) or an NV12 hbhip_surface (storage 2), whose reference the call takes over. */
+int hbh_scan_run(const void *open_fn, const void *picture_fn, const void *close_fn, int pix_fmt, int open_width, int open_height,
+                 int width, int height, uint8_t *const plane[3], const int stride[3], void *storage, int storage_kind,
+                 int flags, int out[6])
+{
+    typedef int  (*open_f)(void **, int, int);
+    typedef int  (*picture_f)(void *, hb_buffer_t *, int *);
+    typedef void (*close_f)(void **);
+    void *scan = NULL;
+    hb_buffer_t *b = storage_kind != 0 ? hb_buffer_init(0) : hb_frame_buffer_init(pix_fmt, width, height);
+    if (b == NULL) return -1;
+    if (storage_kind != 0)
+    {
+        b->s.type = FRAME_BUF;
+        b->f.fmt = pix_fmt;
+        b->f.width = width;
+        b->f.height = height;
+        b->f.max_plane = storage_kind == 2 ? 1 : 2;
+        for (int p = 0; p <= b->f.max_plane; p++)
+        {
+            b->plane[p].width = hb_image_width(pix_fmt, width, p);
+            b->plane[p].height = hb_image_height(pix_fmt, height, p);
+        }
+        b->storage = storage;
+        b->storage_type = storage_kind == 2 ? HBHIP_SURFACE : HBHIP_DEVICE;
+    }
+    else
+        for (int p = 0; p <= b->f.max_plane; p++)
+            for (int y = 0; y < b->plane[p].height; y++)
+                memcpy(b->plane[p].data + (size_t)y * b->plane[p].stride, plane[p] + (size_t)y * stride[p],
+                       MIN(stride[p], b->plane[p].stride));
+    b->s.flags = (uint16_t)flags;
+    int rc = ((open_f)open_fn)(&scan, open_width, open_height) != 0 ? 1 : 0;
+    if (rc == 0 && ((picture_f)picture_fn)(scan, b, out) != 0) rc = 2;
+    ((close_f)close_fn)(&scan);
+    hb_buffer_close(&b);
+    return rc;
+}

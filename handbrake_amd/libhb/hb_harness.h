@@ -86,6 +86,15 @@ void hbh_chain_close(hbh_chain_t *c);
 int hbh_motion_metric_run(const void *proto, int pix_fmt, int width, int height,
                           const uint8_t *luma_a, int stride_a, const uint8_t *luma_b, int stride_b, float *out);
 
+/* The title scan's helper (libhb/scan_hip.c) on one preview: open_fn / picture_fn / close_fn are the addresses of
+ * hb_hip_scan_open / _picture / _close; the helper is opened for open_width x open_height and handed a width x height buffer
+ * of pix_fmt - a copy of plane / stride (storage_kind 0), or the shell around a picture in device memory whose reference the
+ * call takes over: `storage` an hbhip_frame (1) or an NV12 hbhip_surface (2).  flags: the buffer's s.flags.  out: combed, top,
+ * bottom, left, right, recorded.  0, 1 when open declined, 2 when picture did, -1 on an error of the harness's own. */
+int hbh_scan_run(const void *open_fn, const void *picture_fn, const void *close_fn, int pix_fmt, int open_width, int open_height,
+                 int width, int height, uint8_t *const plane[3], const int stride[3], void *storage, int storage_kind,
+                 int flags, int out[6]);
+
 /* One rendered subtitle bitmap: 4 planes (Y, Cb, Cr, alpha; 8-bit), placed at (x, y) of the frame. */
 typedef struct
 {

@@ -19,4 +19,20 @@ int  hb_hip_filter_is_hip(const hb_filter_object_t *filter);
  * run like the ones are_filters_supported() lists (platform/macosx/vt_common.c:424-448) */
 int  hb_hip_filter_is_hw_transparent(const hb_filter_object_t *filter);
 
+/* ---- the title scan (scan_hip.c): what scan.c:972-1052 computes from a preview, on the GPU ----
+ * open once the preview size is known, picture() for every preview - a host yuv420p buffer, or one whose picture lies in
+ * HBM -, close at the end of the title.  Every call answers 0 on success and non-zero where the caller keeps its CPU loops:
+ * no GPU, HBHIP_DISABLE set, a picture that is not 8-bit 4:2:0 of even size >= 8 x 8, or of another size than open() was
+ * given.  INTEGRATION.md has the hook. */
+typedef struct hb_hip_scan_s hb_hip_scan_t;
+typedef struct hb_hip_scan_picture_s
+{
+    int combed;                       /* hb_detect_comb( vid_buf, 10, 30, 9, 10, 30, 9 ), scan.c:973 */
+    int top, bottom, left, right;     /* as scan.c:999-1044 leaves them                              */
+    int recorded;                     /* the test of scan.c:1049: hand the four to record_crop       */
+} hb_hip_scan_picture_t;
+int  hb_hip_scan_open(hb_hip_scan_t **scan, int width, int height);
+int  hb_hip_scan_picture(hb_hip_scan_t *scan, hb_buffer_t *vid_buf, hb_hip_scan_picture_t *out);
+void hb_hip_scan_close(hb_hip_scan_t **scan);
+
 #endif

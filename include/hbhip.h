@@ -633,6 +633,43 @@ int  hbhip_motion_metric_run_dev(hbhip_motion_metric *m, const void *luma_a, int
                                  const void *luma_b, int stride_b, float *out);            /* planes in HBM */
 void hbhip_motion_metric_destroy(hbhip_motion_metric *m);
 
+/* ---- Title scan (replaces what scan.c does with the pixels of every preview: hb_detect_comb, hb.c:1088-1167, called at
+ *      scan.c:973, and the black-border walk of scan.c:986-1052 over row_all_dark / column_all_dark, :456-509) -----------
+ * For pictures that are in HBM already: five launches and one small record over the bus per picture, instead of the
+ * picture itself.  Defined for what the scan decodes to (decavcodec.c:1359-1369): 8-bit planar 4:2:0 with even sizes.
+ * All integer, bit-for-bit with the reference (DESIGN.md §4.19 has the definition).  Pictures are pushed as frames - an
+ * NV12 surface through hbhip_frame_import_surface[_async] first - and their results pulled in push order; up to
+ * HBHIP_SCAN_INFLIGHT_MAX may be in flight.  The object holds a reference on a pushed frame until its result is pulled.
+ * Everything runs on the object's context's stream behind the frame's contents (hbhip_frame_use_on).
+ * hbhip_ctx_bus_bytes of the object's context counts HBHIP_SCAN_RECORD_BYTES of D2H per pushed picture and nothing else.
+ * Refused before anything is queued - HBHIP_ERR_UNSUPPORTED: a frame that is not 8-bit 4:2:0 planar, an odd width or
+ * height, a size other than the object's, a width or height below 8 (create: the same, and a size above 16384);
+ * HBHIP_ERR_ARG: a frame of another GPU than the object's; HBHIP_ERR_STATE: HBHIP_SCAN_INFLIGHT_MAX pictures in flight. */
+#define HBHIP_SCAN_INFLIGHT_MAX 32
+#define HBHIP_SCAN_RECORD_BYTES 48
+typedef struct hbhip_scan hbhip_scan;
+typedef struct hbhip_scan_params
+{
+    /* hb_detect_comb's six sensitivities; scan.c:973 passes 10, 30, 9, 10, 30, 9 */
+    int color_equal, color_diff, threshold;
+    int prog_equal, prog_diff, prog_threshold;
+} hbhip_scan_params;
+typedef struct hbhip_scan_result
+{
+    int top, bottom, left, right;        /* the picture's crop as scan.c:999-1044 leaves it                         */
+    int recorded;                        /* scan.c:1049: all four below a quarter of the picture                    */
+    int cc[3];                           /* hb_detect_comb's per-plane scores, the carried-over counts included     */
+    int average_cc;                      /* hb.c:1149                                                               */
+    int combed;                          /* hb_detect_comb's return value                                           */
+} hbhip_scan_result;
+int  hbhip_scan_create(hbhip_ctx *ctx, int width, int height, hbhip_scan **out);
+void hbhip_scan_destroy(hbhip_scan *s);                /* waits for what is in flight and drops it */
+/* pic_flags: the buffer's s.flags (bit 16 selects the prog_* triple, hb.c:1095-1101); p == NULL: scan.c's six numbers */
+int  hbhip_scan_push(hbhip_scan *s, hbhip_frame *frame, int pic_flags, const hbhip_scan_params *p);
+/* the oldest picture's result (waits for it); HBHIP_AGAIN when none is in flight */
+int  hbhip_scan_pull(hbhip_scan *s, hbhip_scan_result *out);
+int  hbhip_scan_inflight(hbhip_scan *s);
+
 /* ---- Subtitle compositor (replaces hb_blend, blend.c: the object rendersub.c hands every frame
  *      and the list of rendered overlays, rendersub.c:467, 1129-1161) -------------------------
  * Planar 8/10/12-bit frames; overlays are 8-bit Y/Cb/Cr/alpha bitmaps either in the frame's chroma
