@@ -307,7 +307,8 @@ class Ctx:
 
 
 def dev_frame(tensors) -> DevFrame:
-    """DevFrame over three 2-D uint8 torch CUDA tensors (kept alive by the caller)."""
+    """DevFrame over three 2-D torch CUDA tensors (kept alive by the caller): uint8 planes, or int16 ones for 10 / 12-bit
+    samples; the stride is taken in bytes."""
     f = DevFrame()
     for i, t in enumerate(tensors):
         f.plane[i] = t.data_ptr()

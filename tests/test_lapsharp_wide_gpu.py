@@ -4,20 +4,17 @@ and pitch is 8-byte aligned and luma is at least a wave's span wide, lapsharp3_r
 sit on the edges of a lane (8 columns), of a wave (512) and of a workgroup (1024 columns; 8 rows a thread, 16 a workgroup) and
 on either side of the width below which the narrower kernel runs; rows beyond a plane's width hold junk, which the
 kernels must read as the zero padding the reference sees."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from handbrake_amd import hip
 import oracle_lib as ol
+import sharpen_dev as sd
 
 pytestmark = pytest.mark.gpu
 
 LANE, WAVE_SPAN, WG_SPAN, ROWS, WG_ROWS = 8, 512, 1024, 8, 16     # sharpen.hip: LW_PX, LW_WAVE_SPAN, LW_SPAN, LW_ROWS, LW_BY * LW_ROWS
 KERNELS = ("lap", "isolap")
 STRENGTHS = (0.2, 0.35)                                               # the one-float-multiply mix, the double mix
-JUNK = 0x5A
 
 
 def _planes(rng, w, h, lcw, lch, content):
@@ -32,33 +29,7 @@ def _planes(rng, w, h, lcw, lch, content):
 def _run(w, h, frames, kern, strength, lcw=1, lch=1, pad=0, offset=0):
     """frames (lists of three planes) through one process_dev call; rows are padded to 64 samples + pad and filled with
     junk beyond the width; offset moves every input plane's first byte"""
-    import torch
-
-    def plane(q, off=0):
-        ph, pw = q.shape
-        pitch = (pw + 63) // 64 * 64 + pad
-        buf = torch.full((ph * pitch + 64,), JUNK, dtype=torch.uint8, device="cuda")
-        v = buf[off:off + ph * pitch].view(ph, pitch)[:, :pw]
-        v.copy_(torch.from_numpy(np.ascontiguousarray(q)))
-        return v
-    ctx = hip.Ctx(0)
-    k = ol.LAPSHARP_KERNELS[kern]
-    p = hip.LapsharpParams((C.c_double * 3)(strength, strength, strength), (C.c_int * 3)(k, k, k))
-    flt = hip._create("hbhip_lapsharp_create", ctx, [C.c_void_p, C.POINTER(hip.LapsharpParams)] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)],
-                      ctx.h, C.byref(p), w, h, 8, lcw, lch)
-    try:
-        dev_in = [[plane(q, offset) for q in f] for f in frames]
-        outs = [[plane(np.zeros_like(q)) for q in f] for f in frames]
-        torch.cuda.synchronize()
-        n = len(frames)
-        arr_in = (hip.DevFrame * n)(*[hip.dev_frame(f) for f in dev_in])
-        arr_out = (hip.DevFrame * n)(*[hip.dev_frame(o) for o in outs])
-        assert flt.process_dev(arr_in, 0, arr_out) == n
-        ctx.sync()
-        return [[q.cpu().numpy() for q in o] for o in outs]
-    finally:
-        flt.close()
-        ctx.close()
+    return sd.run_dev("lapsharp", sd.lapsharp_params([kern] * 3, [strength] * 3), w, h, 8, frames, lcw, lch, pad, offset)
 
 
 def _check(w, h, frames, kern, strength, **kw):
