@@ -373,7 +373,6 @@ class MonochromeFilter : public BurstFilter
 public:
     MonochromeFilter(hbhip_ctx *c, double cb_, double cr_, double size_, double high_)
         : BurstFilter(c), cb(cb_), cr(cr_), size(size_), high(high_) {}
-    ~MonochromeFilter() override { if (d_lut) (void)hipFree(d_lut); }
     int setup()
     {
         // one entry per (Cb, Cr) pair: 256 KB at 8 bits, 4 MB at 10, 64 MB at 12
@@ -390,8 +389,8 @@ public:
                 d = d < 0.f ? 0.f : d > 1.f ? 1.f : d;
                 lut[(size_t)u * n + v] = expf(-d);
             }
-        HBHIP_CHECK(ctx, hipMalloc((void **)&d_lut, sizeof(float) * lut.size()));
-        HBHIP_CHECK(ctx, hipMemcpyAsync(d_lut, lut.data(), sizeof(float) * lut.size(), hipMemcpyHostToDevice, ctx->stream));
+        if (const int rc = d_lut.alloc(ctx, lut.size())) return rc;
+        HBHIP_CHECK(ctx, hipMemcpyAsync(d_lut.get(), lut.data(), sizeof(float) * lut.size(), hipMemcpyHostToDevice, ctx->stream));
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         return HBHIP_OK;
     }
@@ -415,7 +414,7 @@ public:
             }
             B.ypitch = ins[at]->pitch[0]; B.cpitch = ins[at]->pitch[1]; B.dpitch = outs[at]->pitch[0]; B.dcpitch = outs[at]->pitch[1];
             B.w = ins[at]->width[0]; B.h = ins[at]->height[0]; B.cw = outs[at]->width[1]; B.ch = outs[at]->height[1];
-            B.wlut = d_lut; B.ihigh = 1.f - (float)high;
+            B.wlut = d_lut.get(); B.ihigh = 1.f - (float)high;
             // luma job: 16 x 2 pixels per thread; fill job: 16 bytes per thread over 2 * ch rows - one grid covers both
             const int gx = std::max(((B.w + 15) / 16 + 63) / 64, ((B.cw + 15) / 16 + 63) / 64);
             const int gy = std::max(((B.h + 1) / 2 + 3) / 4, (2 * B.ch + 3) / 4);
@@ -432,12 +431,12 @@ public:
             HBHIP_LAUNCH(ctx, "monochrome", monochrome_kernel<uint8_t>, dim3((w + 63) / 64, (h + 3) / 4), dim3(64, 4), 0,
                          (const uint8_t *)in->plane[0], in->pitch[0], (const uint8_t *)in->plane[1],
                          (const uint8_t *)in->plane[2], in->pitch[1], out->plane[0], out->pitch[0], w, h,
-                         in_geo.log2_cw, in_geo.log2_ch, (const float *)d_lut, 1.f - (float)high, max);
+                         in_geo.log2_cw, in_geo.log2_ch, (const float *)d_lut.get(), 1.f - (float)high, max);
         else
             HBHIP_LAUNCH(ctx, "monochrome", monochrome_kernel<uint16_t>, dim3((w + 63) / 64, (h + 3) / 4), dim3(64, 4), 0,
                          (const uint8_t *)in->plane[0], in->pitch[0], (const uint8_t *)in->plane[1],
                          (const uint8_t *)in->plane[2], in->pitch[1], out->plane[0], out->pitch[0], w, h,
-                         in_geo.log2_cw, in_geo.log2_ch, (const float *)d_lut, 1.f - (float)high, max);
+                         in_geo.log2_cw, in_geo.log2_ch, (const float *)d_lut.get(), 1.f - (float)high, max);
         for (int c = 1; c < 3; c++)
         {
             const dim3 grid((out->width[c] + 255) / 256, out->height[c]);
@@ -449,7 +448,7 @@ public:
         return HBHIP_OK;
     }
     double cb, cr, size, high;
-    float *d_lut = nullptr;
+    DevBuf<float> d_lut;
 };
 
 // ------------------------------------------------------------------ crop + lanczos scale
@@ -1025,27 +1024,14 @@ class CropScaleFilter : public BurstFilter
 {
 public:
     CropScaleFilter(hbhip_ctx *c, const hbhip_cropscale_params &p) : BurstFilter(c), par(p) {}
-    ~CropScaleFilter() override
-    {
-        for (int c = 0; c < 3; c++)
-        {
-            if (d_tqx[c]) (void)hipFree(d_tqx[c]);
-            if (d_iy[c]) (void)hipFree(d_iy[c]);
-            if (d_bx[c]) (void)hipFree(d_bx[c]);
-            if (d_by[c]) (void)hipFree(d_by[c]);
-            if (d_qx[c]) (void)hipFree(d_qx[c]);
-            if (d_qy[c]) (void)hipFree(d_qy[c]);
-        }
-        if (hbuf16) (void)hipFree(hbuf16);
-    }
     int setup()
     {
         const int cw = in_geo.width - par.crop_left - par.crop_right;
         const int ch = in_geo.height - par.crop_top - par.crop_bottom;
         if (cw < 1 || ch < 1) return HBHIP_ERR_ARG;
-        auto upload = [&](auto *&dptr, const auto &v) -> int {
-            HBHIP_CHECK(ctx, hipMalloc((void **)&dptr, sizeof(v[0]) * v.size()));
-            HBHIP_CHECK(ctx, hipMemcpy(dptr, v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice));
+        auto upload = [&](auto &buf, const auto &v) -> int {
+            if (const int rc = buf.alloc(ctx, v.size())) return rc;
+            HBHIP_CHECK(ctx, hipMemcpy(buf.get(), v.data(), sizeof(v[0]) * v.size(), hipMemcpyHostToDevice));
             return HBHIP_OK;
         };
         for (int c = 0; c < 3; c++)
@@ -1128,7 +1114,7 @@ public:
                 hframe += ((size_t)out_geo.pw[c] * crop_h[c] + 127) & ~(size_t)127;
             }
         if (!sws) need = hframe * SD_FRAMES;        // the batched two-pass form: every plane of SD_FRAMES frames between the passes
-        if (need && !up6) HBHIP_CHECK(ctx, hipMalloc((void **)&hbuf16, sizeof(uint16_t) * need));
+        if (need && !up6) return hbuf16.alloc(ctx, need);
         return HBHIP_OK;
     }
 
@@ -1157,8 +1143,8 @@ public:
                 for (int c = 0; c < 3; c++)
                 {
                     ScalePlane8 &P = B.p[c];
-                    P.bx = d_bx[c]; P.by = d_by[c];
-                    P.qx = reinterpret_cast<const uint32_t *>(d_qx[c]); P.qy = reinterpret_cast<const uint32_t *>(d_qy[c]);
+                    P.bx = d_bx[c].get(); P.by = d_by[c].get();
+                    P.qx = reinterpret_cast<const uint32_t *>(d_qx[c].get()); P.qy = reinterpret_cast<const uint32_t *>(d_qy[c].get());
                     P.dw = out_geo.pw[c]; P.dh = out_geo.ph[c]; P.sw = crop_w[c]; P.sh = crop_h[c];
                     P.active = !identity[c];
                     B.spitch[c] = ins[i0]->pitch[c]; B.dpitch[c] = outs[i0]->pitch[c];
@@ -1184,7 +1170,7 @@ public:
                     B.spitch[c] = ins[i0]->pitch[c]; B.dpitch[c] = outs[i0]->pitch[c];
                     B.dw[c] = out_geo.pw[c]; B.dh[c] = out_geo.ph[c]; B.tx[c] = tx[c]; B.ty[c] = ty[c]; B.src_rows[c] = crop_h[c];
                     B.src_bytes[c] = crop_w[c] * in_geo.bps;
-                    B.tqx[c] = d_tqx[c]; B.iy[c] = d_iy[c]; B.qy[c] = d_qy[c];
+                    B.tqx[c] = d_tqx[c].get(); B.iy[c] = d_iy[c].get(); B.qy[c] = d_qy[c].get();
                     B.hoff[c] = hoff[c];
                     for (int k = 0; k < m; k++) { B.src[k][c] = window(ins[i0 + k], c); B.dst[k][c] = outs[i0 + k]->plane[c]; }
                     gw = std::max(gw, B.dw[c]); ghr = std::max(ghr, B.src_rows[c]); gvr = std::max(gvr, B.dh[c]);
@@ -1200,13 +1186,13 @@ public:
                                        else if ((T) <= 16) SD_GO(K, PIX, 16, G, HB); else SD_GO(K, PIX, 24, G, HB); } while (0)
                 if (in_geo.bps == 1)
                 {
-                    SD_PICK(h, uint8_t, mtx, gh, hbuf16);
-                    SD_PICK(v, uint8_t, mty, gv, (const uint16_t *)hbuf16);
+                    SD_PICK(h, uint8_t, mtx, gh, hbuf16.get());
+                    SD_PICK(v, uint8_t, mty, gv, (const uint16_t *)hbuf16.get());
                 }
                 else
                 {
-                    SD_PICK(h, uint16_t, mtx, gh, hbuf16);
-                    SD_PICK(v, uint16_t, mty, gv, (const uint16_t *)hbuf16);
+                    SD_PICK(h, uint16_t, mtx, gh, hbuf16.get());
+                    SD_PICK(v, uint16_t, mty, gv, (const uint16_t *)hbuf16.get());
                 }
 #undef SD_PICK
 #undef SD_GO
@@ -1220,18 +1206,18 @@ public:
                 w.src = window(ins[i], c); w.dst = outs[i]->plane[c];
                 w.spitch = ins[i]->pitch[c]; w.dpitch = outs[i]->pitch[c];
                 w.dw = out_geo.pw[c]; w.dh = out_geo.ph[c]; w.tx = tx[c]; w.ty = ty[c]; w.src_rows = crop_h[c];
-                w.px = d_bx[c]; w.py = d_by[c]; w.qx = d_qx[c]; w.qy = d_qy[c];
+                w.px = d_bx[c].get(); w.py = d_by[c].get(); w.qx = d_qx[c].get(); w.qy = d_qy[c].get();
                 const dim3 gh((w.dw + 63) / 64, (crop_h[c] + 3) / 4), gv((w.dw + 63) / 64, (w.dh + 3) / 4);
                 if (in_geo.bps == 1)
                 {
-                    HBHIP_LAUNCH(ctx, "cropscale_sws_h", scale_sws_h_kernel<uint8_t>, gh, dim3(64, 4), 0, w, (int16_t *)hbuf16, 7);
-                    HBHIP_LAUNCH(ctx, "cropscale_sws_v", scale_sws_v_kernel<uint8_t>, gv, dim3(64, 4), 0, w, (const int16_t *)hbuf16, 64 << 12, 19, 255);
+                    HBHIP_LAUNCH(ctx, "cropscale_sws_h", scale_sws_h_kernel<uint8_t>, gh, dim3(64, 4), 0, w, (int16_t *)hbuf16.get(), 7);
+                    HBHIP_LAUNCH(ctx, "cropscale_sws_v", scale_sws_v_kernel<uint8_t>, gv, dim3(64, 4), 0, w, (const int16_t *)hbuf16.get(), 64 << 12, 19, 255);
                 }
                 else
                 {
                     const int d = in_geo.depth, shift = 11 + 16 - d;
-                    HBHIP_LAUNCH(ctx, "cropscale_sws_h", scale_sws_h_kernel<uint16_t>, gh, dim3(64, 4), 0, w, (int16_t *)hbuf16, d - 1);
-                    HBHIP_LAUNCH(ctx, "cropscale_sws_v", scale_sws_v_kernel<uint16_t>, gv, dim3(64, 4), 0, w, (const int16_t *)hbuf16, 1 << (shift - 1), shift, (1 << d) - 1);
+                    HBHIP_LAUNCH(ctx, "cropscale_sws_h", scale_sws_h_kernel<uint16_t>, gh, dim3(64, 4), 0, w, (int16_t *)hbuf16.get(), d - 1);
+                    HBHIP_LAUNCH(ctx, "cropscale_sws_v", scale_sws_v_kernel<uint16_t>, gv, dim3(64, 4), 0, w, (const int16_t *)hbuf16.get(), 1 << (shift - 1), shift, (1 << d) - 1);
                 }
             }
         HBHIP_CHECK(ctx, hipGetLastError());
@@ -1245,12 +1231,12 @@ public:
     hbhip_cropscale_params par;
     int crop_x[3], crop_y[3], crop_w[3], crop_h[3], tx[3] = {0, 0, 0}, ty[3] = {0, 0, 0};
     bool identity[3] = {false, false, false};
-    int *d_iy[3] = {nullptr, nullptr, nullptr};
-    uint32_t *d_tqx[3] = {nullptr, nullptr, nullptr};   // the two-pass form's horizontal taps (ScaleBatchHV::tqx)
-    uint16_t *hbuf16 = nullptr; // the 16-bit plane between the passes (two-launch form); zimg form: the planes of SD_FRAMES frames
+    DevBuf<int> d_iy[3];
+    DevBuf<uint32_t> d_tqx[3];   // the two-pass form's horizontal taps (ScaleBatchHV::tqx)
+    DevBuf<uint16_t> hbuf16;    // the 16-bit plane between the passes (two-launch form); zimg form: the planes of SD_FRAMES frames
     size_t hoff[3] = {0, 0, 0}, hframe = 0;
-    int *d_bx[3] = {nullptr, nullptr, nullptr}, *d_by[3] = {nullptr, nullptr, nullptr};
-    short *d_qx[3] = {nullptr, nullptr, nullptr}, *d_qy[3] = {nullptr, nullptr, nullptr};
+    DevBuf<int> d_bx[3], d_by[3];
+    DevBuf<short> d_qx[3], d_qy[3];
 };
 
 // ------------------------------------------------------------------ pad

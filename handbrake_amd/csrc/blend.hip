@@ -54,32 +54,26 @@ struct hbhip_blend
     int chroma_location = 1, ov_wshift = 0, ov_hshift = 0;
     bool subsample = false;
     unsigned coeff[2][2] = {{1, 1}, {1, 1}};
-    uint8_t *d_store = nullptr;          // the uploaded overlay bitmaps, back to back
-    size_t   store_bytes = 0;
+    DevBuf<uint8_t> d_store;             // the uploaded overlay bitmaps, back to back
     std::vector<OverlayDev> overlays;
     struct Launch { OverlayGroup g; int n; dim3 grid; };
     std::vector<Launch> launches;        // the overlays in list order, grouped (build_launches)
     hbhip_frame *staging = nullptr;      // device frame of the host-frame entry point
     bool biplanar = false;               // made by hbhip_blend_create_biplanar
-    uint8_t *bi_stage = nullptr;         // its staging buffer: the host picture as it is (BiLayout)
+    DevBuf<uint8_t> bi_stage;            // its staging buffer: the host picture as it is (BiLayout)
     // hbhip_blend_set_ass_images: box table, image table and glyph bitmaps, packed in pinned memory and uploaded in one copy
-    uint8_t *h_ass = nullptr, *d_ass = nullptr;
-    size_t   h_ass_bytes = 0, d_ass_bytes = 0;
+    PinnedBuf<uint8_t> h_ass;
+    DevBuf<uint8_t> d_ass;
     hipEvent_t ass_uploaded = nullptr;   // behind the last copy out of h_ass: the next call packs into it after this
     // hbhip_blend_set_bitmaps: the bitmap subtitles the object holds, scaled, each in an allocation of its own (they come
     // and go one by one); it packs its tables and source planes into h_ass / d_ass as well
-    struct Bitmap { uint64_t key; int sw, sh, dw, dh; uint8_t *d; size_t cap; };   // d: Y, Cb, Cr, A back to back, stride align16(dw)
+    struct Bitmap { uint64_t key; int sw, sh, dw, dh; DevBuf<uint8_t> d; };   // d: Y, Cb, Cr, A back to back, stride align16(dw)
     std::vector<Bitmap> bitmaps;
     int64_t bmp_scaled = 0, bmp_uploaded = 0, bmp_hits = 0;
 
-    ~hbhip_blend()
+    ~hbhip_blend()                       // (the buffers go with their members, behind this)
     {
-        for (Bitmap &m : bitmaps) (void)hipFree(m.d);
         if (ass_uploaded) (void)hipEventDestroy(ass_uploaded);
-        if (h_ass) (void)hipHostFree(h_ass);
-        if (d_ass) (void)hipFree(d_ass);
-        if (d_store) (void)hipFree(d_store);
-        if (bi_stage) (void)hipFree(bi_stage);
         if (staging) hbhip_frame_release(staging);
     }
 };
@@ -194,15 +188,8 @@ extern "C" int hbhip_blend_set_overlays(hbhip_blend *b, const hbhip_overlay *ov,
         const int cw = -((-ov[i].width) >> b->ov_wshift), ch = -((-ov[i].height) >> b->ov_hshift);
         total += 2 * (size_t)hbhip_align_up(ov[i].width, 16) * ov[i].height + 2 * (size_t)hbhip_align_up(cw, 16) * ch;
     }
-    if (total > b->store_bytes)
-    {
-        if (b->d_store) (void)hipFree(b->d_store);
-        b->d_store = nullptr;
-        b->store_bytes = 0;
-        HBHIP_CHECK(ctx, hipMalloc((void **)&b->d_store, total));
-        b->store_bytes = total;
-    }
-    uint8_t *at = b->d_store;
+    if (const int rc = b->d_store.reserve(ctx, total)) return rc;
+    uint8_t *at = b->d_store.get();
     for (int i = 0; i < n; i++)
     {
         OverlayDev d;
@@ -231,26 +218,14 @@ extern "C" int hbhip_blend_set_overlays(hbhip_blend *b, const hbhip_overlay *ov,
 static int reserve_upload(hbhip_blend *b, size_t bytes)
 {
     hbhip_ctx *ctx = b->ctx;
-    if (bytes > b->d_ass_bytes)
+    if (bytes > b->d_ass.count())
     {
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        if (b->d_ass) (void)hipFree(b->d_ass);
-        b->d_ass = nullptr;
-        b->d_ass_bytes = 0;
-        HBHIP_CHECK(ctx, hipMalloc((void **)&b->d_ass, bytes));
-        b->d_ass_bytes = bytes;
+        if (const int rc = b->d_ass.alloc(ctx, bytes)) return rc;
     }
     if (!b->ass_uploaded) HBHIP_CHECK(ctx, hipEventCreateWithFlags(&b->ass_uploaded, hipEventDisableTiming));
     else HBHIP_CHECK(ctx, hipEventSynchronize(b->ass_uploaded));
-    if (bytes > b->h_ass_bytes)
-    {
-        if (b->h_ass) (void)hipHostFree(b->h_ass);
-        b->h_ass = nullptr;
-        b->h_ass_bytes = 0;
-        HBHIP_CHECK(ctx, hipHostMalloc((void **)&b->h_ass, bytes, hipHostMallocDefault));
-        b->h_ass_bytes = bytes;
-    }
-    return HBHIP_OK;
+    return b->h_ass.reserve(ctx, bytes);
 }
 
 // ---- text subtitles: libass's glyph images composed on the device (ass_compose.hip) ----
@@ -326,22 +301,16 @@ extern "C" int hbhip_blend_set_ass_images(hbhip_blend *b, const hbhip_ass_image 
         d.stride[1] = d.stride[2] = hbhip_align_up(cw, 16);
         total += 2 * (size_t)d.stride[0] * d.height + 2 * (size_t)d.stride[1] * ch;
     }
-    if (total > b->store_bytes || up_bytes > b->d_ass_bytes)
+    if (total > b->d_store.count() || up_bytes > b->d_ass.count())
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));                  // launches of the previous set may still be reading them
-    if (total > b->store_bytes)
-    {
-        if (b->d_store) (void)hipFree(b->d_store);
-        b->d_store = nullptr;
-        b->store_bytes = 0;
-        HBHIP_CHECK(ctx, hipMalloc((void **)&b->d_store, total));
-        b->store_bytes = total;
-    }
+    if (const int rc = b->d_store.reserve(ctx, total)) return rc;
     const int rs = reserve_upload(b, up_bytes);
     if (rs != HBHIP_OK) return rs;
 
-    AssBoxDev *hb = reinterpret_cast<AssBoxDev *>(b->h_ass);
-    AssImageDev *hi = reinterpret_cast<AssImageDev *>(b->h_ass + box_bytes);
-    uint8_t *at = b->d_store;
+    uint8_t *const h_ass = b->h_ass.get(), *const d_ass = b->d_ass.get();
+    AssBoxDev *hb = reinterpret_cast<AssBoxDev *>(h_ass);
+    AssImageDev *hi = reinterpret_cast<AssImageDev *>(h_ass + box_bytes);
+    uint8_t *at = b->d_store.get();
     dim3 grid(1, 1, (unsigned)boxes.size());
     for (size_t k = 0; k < boxes.size(); k++)
     {
@@ -359,7 +328,7 @@ extern "C" int hbhip_blend_set_ass_images(hbhip_blend *b, const hbhip_ass_image 
         grid.y = std::max<unsigned>(grid.y, (ch + ASS_TILE_WAVES - 1) / ASS_TILE_WAVES);
         d.x += crop_left; d.y += crop_top;                                  // :658-659
     }
-    memset(b->h_ass + box_bytes + img_bytes, 0, bits_at + ASS_BITS_PAD - (box_bytes + img_bytes));
+    memset(h_ass + box_bytes + img_bytes, 0, bits_at + ASS_BITS_PAD - (box_bytes + img_bytes));
     size_t off = ASS_BITS_PAD;
     for (int i = 0; i < n; i++)
     {
@@ -369,18 +338,18 @@ extern "C" int hbhip_blend_set_ass_images(hbhip_blend *b, const hbhip_ass_image 
         hi[i].yuva = (unsigned)m.y | (unsigned)m.cb << 8 | (unsigned)m.cr << 16 | (unsigned)m.a << 24;
         hi[i].pad[0] = hi[i].pad[1] = 0;
         if (empty) continue;
-        for (int r = 0; r < m.h; r++) memcpy(b->h_ass + bits_at + off + (size_t)r * m.w, m.bitmap + (size_t)r * m.stride, m.w);
+        for (int r = 0; r < m.h; r++) memcpy(h_ass + bits_at + off + (size_t)r * m.w, m.bitmap + (size_t)r * m.stride, m.w);
         off += (size_t)m.w * m.h;
     }
-    memset(b->h_ass + bits_at + off, 0, up_bytes - bits_at - off);
+    memset(h_ass + bits_at + off, 0, up_bytes - bits_at - off);
     // the caller may free its bitmaps from here on: they are in the staging buffer
-    HBHIP_CHECK(ctx, hipMemcpyAsync(b->d_ass, b->h_ass, up_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HBHIP_CHECK(ctx, hipMemcpyAsync(d_ass, h_ass, up_bytes, hipMemcpyHostToDevice, ctx->stream));
     HBHIP_CHECK(ctx, hipEventRecord(b->ass_uploaded, ctx->stream));
 
     AssArgs a;
-    a.box = reinterpret_cast<const AssBoxDev *>(b->d_ass);
-    a.img = reinterpret_cast<const AssImageDev *>(b->d_ass + box_bytes);
-    a.bits = b->d_ass + bits_at;
+    a.box = reinterpret_cast<const AssBoxDev *>(d_ass);
+    a.img = reinterpret_cast<const AssImageDev *>(d_ass + box_bytes);
+    a.bits = d_ass + bits_at;
     a.n_img = n;
     for (int i = 0; i < 2; i++) { a.cx[i] = b->coeff[0][i]; a.cy[i] = b->coeff[1][i]; }
     const int rc = hbhip_ass_compose_launch(ctx, ws, hs, grid, a);
@@ -410,7 +379,6 @@ void drop_bitmaps(hbhip_blend *b)
     if (b->bitmaps.empty()) return;
     (void)hipSetDevice(b->ctx->device);
     (void)hipStreamSynchronize(b->ctx->stream);
-    for (hbhip_blend::Bitmap &m : b->bitmaps) (void)hipFree(m.d);
     b->bitmaps.clear();
 }
 
@@ -526,12 +494,12 @@ int set_bitmaps(hbhip_blend *b, const hbhip_bitmap_sub *sub, int n, const int cr
         const size_t need = 4 * (size_t)hbhip_align_up(pl.dw, 16) * pl.dh;
         size_t e = b->bitmaps.size();
         for (size_t k = 0; k < held; k++)
-            if (used[k] < 0 && b->bitmaps[k].cap >= need && (e == b->bitmaps.size() || b->bitmaps[k].cap < b->bitmaps[e].cap)) e = k;
+            if (used[k] < 0 && b->bitmaps[k].d.count() >= need && (e == b->bitmaps.size() || b->bitmaps[k].d.count() < b->bitmaps[e].d.count())) e = k;
         if (e == b->bitmaps.size())
         {
-            hbhip_blend::Bitmap m = { 0, 0, 0, 0, 0, nullptr, need };
-            HBHIP_CHECK(ctx, hipMalloc((void **)&m.d, need));
-            b->bitmaps.push_back(m);
+            hbhip_blend::Bitmap m = {};
+            if (const int rc = m.d.alloc(ctx, need)) return rc;
+            b->bitmaps.push_back(std::move(m));
             used.push_back(1);
         }
         hbhip_blend::Bitmap &m = b->bitmaps[e];
@@ -562,20 +530,21 @@ int set_bitmaps(hbhip_blend *b, const hbhip_bitmap_sub *sub, int n, const int cr
     {
         const int rs = reserve_upload(b, up_bytes);
         if (rs != HBHIP_OK) return rs;
+        uint8_t *const h_ass = b->h_ass.get(), *const d_ass = b->d_ass.get();
         for (BitmapPlan *pl : fresh)
         {
             const hbhip_bitmap_sub &s = *pl->sub;
-            uint8_t *at = b->h_ass + pl->at;
+            uint8_t *at = h_ass + pl->at;
             if (pl->scale)
             {
-                memset(b->h_ass + pl->planes_at - 16, 0, 16);                   // (the tables end inside these)
+                memset(h_ass + pl->planes_at - 16, 0, 16);                   // (the tables end inside these)
                 memcpy(at, pl->px.data(), pl->px.size() * sizeof(int));   at += pl->px.size() * sizeof(int);
                 memcpy(at, pl->py.data(), pl->py.size() * sizeof(int));   at += pl->py.size() * sizeof(int);
                 memcpy(at, pl->qx.data(), pl->qx.size() * sizeof(short)); at += pl->qx.size() * sizeof(short);
                 memcpy(at, pl->qy.data(), pl->qy.size() * sizeof(short));
             }
             const int sp = hbhip_align_up(s.width, 16);
-            at = b->h_ass + pl->planes_at;
+            at = h_ass + pl->planes_at;
             for (int p = 0; p < 4; p++)
                 for (int r = 0; r < s.height; r++, at += sp)
                 {
@@ -584,16 +553,16 @@ int set_bitmaps(hbhip_blend *b, const hbhip_bitmap_sub *sub, int n, const int cr
                 }
         }
         // the caller may free its bitmaps from here on: they are in the staging buffer
-        if (scaled_bytes) HBHIP_CHECK(ctx, hipMemcpyAsync(b->d_ass, b->h_ass, scaled_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (scaled_bytes) HBHIP_CHECK(ctx, hipMemcpyAsync(d_ass, h_ass, scaled_bytes, hipMemcpyHostToDevice, ctx->stream));
         for (BitmapPlan *pl : fresh)
         {
             const hbhip_bitmap_sub &s = *pl->sub;
             const size_t src_plane = (size_t)hbhip_align_up(s.width, 16) * s.height;
-            uint8_t *dst = b->bitmaps[pl->entry].d;
+            uint8_t *dst = b->bitmaps[pl->entry].d.get();
             b->bmp_uploaded++;
             if (!pl->scale)
             {
-                HBHIP_CHECK(ctx, hipMemcpyAsync(dst, b->h_ass + pl->planes_at, 4 * src_plane, hipMemcpyHostToDevice, ctx->stream));
+                HBHIP_CHECK(ctx, hipMemcpyAsync(dst, h_ass + pl->planes_at, 4 * src_plane, hipMemcpyHostToDevice, ctx->stream));
                 continue;
             }
             BitmapScaleArgs a;
@@ -601,10 +570,10 @@ int set_bitmaps(hbhip_blend *b, const hbhip_bitmap_sub *sub, int n, const int cr
             a.dw = pl->dw; a.dh = pl->dh; a.tx = pl->tx; a.ty = pl->ty;
             for (int p = 0; p < 4; p++)
             {
-                a.src[p] = b->d_ass + pl->planes_at + p * src_plane;
+                a.src[p] = d_ass + pl->planes_at + p * src_plane;
                 a.dst[p] = dst + p * (size_t)a.dpitch * pl->dh;
             }
-            a.px = reinterpret_cast<const int *>(b->d_ass + pl->at);
+            a.px = reinterpret_cast<const int *>(d_ass + pl->at);
             a.py = a.px + pl->px.size();
             a.qx = reinterpret_cast<const short *>(a.py + pl->py.size());
             a.qy = a.qx + pl->qx.size();
@@ -624,7 +593,7 @@ int set_bitmaps(hbhip_blend *b, const hbhip_bitmap_sub *sub, int n, const int cr
         for (int p = 0; p < 4; p++)
         {
             d.stride[p] = hbhip_align_up(m.dw, 16);
-            d.plane[p] = m.d + p * (size_t)d.stride[p] * m.dh;
+            d.plane[p] = m.d.get() + p * (size_t)d.stride[p] * m.dh;
         }
         b->overlays.push_back(d);
     }
@@ -633,9 +602,8 @@ int set_bitmaps(hbhip_blend *b, const hbhip_bitmap_sub *sub, int n, const int cr
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));                // launches of the previous list may still be reading them
         size_t keep = 0;
         for (size_t e = 0; e < b->bitmaps.size(); e++)
-            if (used[e] > 0) b->bitmaps[keep++] = b->bitmaps[e];
-            else (void)hipFree(b->bitmaps[e].d);
-        b->bitmaps.resize(keep);
+            if (used[e] > 0) b->bitmaps[keep++] = std::move(b->bitmaps[e]);
+        b->bitmaps.erase(b->bitmaps.begin() + (ptrdiff_t)keep, b->bitmaps.end());
     }
     build_launches(b);
     return HBHIP_OK;
@@ -761,8 +729,8 @@ extern "C" int hbhip_blend_apply_biplanar(hbhip_blend *b, const hbhip_host_bipla
     if (b->overlays.empty()) return HBHIP_OK;
     hbhip_ctx *ctx = b->ctx;
     (void)hipSetDevice(ctx->device);
-    if (!b->bi_stage) HBHIP_CHECK(ctx, hipMalloc((void **)&b->bi_stage, l.bytes));
-    uint8_t *plane[2] = { b->bi_stage, b->bi_stage + (size_t)l.pitch[0] * l.rows[0] };
+    if (const int rc = b->bi_stage.reserve(ctx, l.bytes)) return rc;
+    uint8_t *plane[2] = { b->bi_stage.get(), b->bi_stage.get() + (size_t)l.pitch[0] * l.rows[0] };
     for (int p = 0; p < 2; p++)
         HBHIP_CHECK(ctx, hipMemcpy2DAsync(plane[p], l.pitch[p], frame->plane[p], frame->stride[p], l.row_bytes[p], l.rows[p],
                                           hipMemcpyHostToDevice, ctx->stream));

@@ -255,7 +255,6 @@ class Bm3dFilter : public BurstFilter
 {
 public:
     Bm3dFilter(hbhip_ctx *c, const hbhip_bm3d_params &p) : BurstFilter(c), par(p) {}
-    ~Bm3dFilter() override { if (dct) (void)hipFree(dct); }
     int process_many(DevPicture *const *ins, DevPicture *const *outs, int n) override
     {
         return hbhip_for_each_burst<BM_FRAMES, Bm3dArgs>(ctx, ins, outs, n, [&](Bm3dArgs &a, int nf, int, uintptr_t bits) {
@@ -265,7 +264,7 @@ public:
                 a.thr[c] = par.thr[c];
                 if (((a.spitch[c] | a.dpitch[c]) & (in_geo.bps - 1)) != 0) return HBHIP_ERR_ARG;
             }
-            a.dct = dct;
+            a.dct = dct.get();
             a.maxv = (1 << in_geo.depth) - 1;
             a.aligned = (bits & 7) == 0;
             const dim3 grid(hbhip_grid_x((a.w[0] + BM_TW - 1) / BM_TW), (a.h[0] + BM_TH - 1) / BM_TH, 3 * nf);
@@ -275,7 +274,7 @@ public:
         });
     }
     hbhip_bm3d_params par;
-    float *dct = nullptr;
+    DevBuf<float> dct;
 };
 
 } // namespace
@@ -335,12 +334,12 @@ extern "C" int hbhip_bm3d_create(hbhip_ctx *ctx, const hbhip_bm3d_params *p, int
         if (g.pw[c] < BM_BLOCK || g.ph[c] < BM_BLOCK) return HBHIP_ERR_UNSUPPORTED;      // the clamped origin would be negative
     Bm3dFilter *f = hbhip_make_filter<Bm3dFilter>(ctx, g, g, *p);
     if (!f) return HBHIP_ERR_NOMEM;
-    hipError_t e = hipMalloc(&f->dct, sizeof(p->dct));
-    if (e == hipSuccess) e = hipMemcpy(f->dct, p->dct, sizeof(p->dct), hipMemcpyHostToDevice);
-    if (e != hipSuccess)
+    int rc = f->dct.alloc(ctx, sizeof(p->dct) / sizeof(float));
+    if (rc == HBHIP_OK && hipMemcpy(f->dct.get(), p->dct, sizeof(p->dct), hipMemcpyHostToDevice) != hipSuccess) rc = HBHIP_ERR_HIP;
+    if (rc != HBHIP_OK)
     {
         delete f;
-        return e == hipErrorOutOfMemory ? HBHIP_ERR_NOMEM : HBHIP_ERR_HIP;
+        return rc;
     }
     *out = f;
     return HBHIP_OK;

@@ -543,20 +543,6 @@ class CombDetectFilter : public hbhip_filter
 {
 public:
     CombDetectFilter(hbhip_ctx *c, const hbhip_comb_detect_params &p) : hbhip_filter(c), par(p) {}
-    ~CombDetectFilter() override
-    {
-        for (int i = 0; i < 3; i++) if (luma_alloc[i]) (void)hipFree(luma_alloc[i]);
-        if (masks) (void)hipFree(masks);
-        if (d_lut) (void)hipFree(d_lut);
-        if (d_tab) (void)hipFree(d_tab);
-        if (d_result) (void)hipFree(d_result);
-        if (h_result) (void)hipHostFree(h_result);
-        if (stage) (void)hipFree(stage);
-        if (bmasks) (void)hipFree(bmasks);
-        if (d_bresult) (void)hipFree(d_bresult);
-        if (h_bresult) (void)hipHostFree(h_bresult);
-    }
-
     int setup(int w, int h, int depth)
     {
         width = w; height = h;
@@ -575,23 +561,29 @@ public:
         if (h < 5 || w < 4) return HBHIP_ERR_UNSUPPORTED;
         pitch = hbhip_align_up(w * bps, 256);                      // bytes
         mstride = hbhip_align_up(w, 64);                            // hb_image_stride(GRAY8, w)
-        for (int i = 0; i < 3; i++)
-        {
-            HBHIP_CHECK(ctx, hipMalloc((void **)&luma_alloc[i], (size_t)pitch * h));
-            slot[i] = -1;
-        }
-        const size_t msz = (size_t)mstride * h + 256;               // tail guard for the column-`width` reads
-        HBHIP_CHECK(ctx, hipMalloc((void **)&masks, 3 * msz));
-        HBHIP_CHECK(ctx, hipMemsetAsync(masks, 0, 3 * msz, ctx->stream));
-        mask = masks; mask_filtered = masks + msz; mask_temp = masks + 2 * msz;
-        HBHIP_CHECK(ctx, hipMalloc((void **)&d_lut, sizeof(float) * (max_value + 1)));
+        int rc = HBHIP_OK;
+        for (int i = 0; i < 3 && rc == HBHIP_OK; i++) rc = luma_alloc[i].alloc(ctx, (size_t)pitch * h);
+        msz = (size_t)mstride * h + 256;                            // tail guard for the column-`width` reads
+        // 8 bits without overlay: classify() is a batch of one, on the batch's masks (one frame's worth here, more when
+        // classify_many() first asks for them) and, for the mask filter modes that run as a pass of their own, its
+        // intermediate mask; otherwise the three masks of the pass-by-pass path
+        batched = bps == 1 && !overlay;
+        const bool own_pass = (par.mode & 2) && par.filter_mode != 2;
+        const size_t nmasks = !batched ? 3 : own_pass ? 1 : 0;
+        if (rc == HBHIP_OK && nmasks) rc = masks.alloc(ctx, nmasks * msz);
+        if (rc == HBHIP_OK && batched) rc = batch_masks(1);
+        if (rc == HBHIP_OK) rc = d_lut.alloc(ctx, (size_t)max_value + 1);
+        if (rc == HBHIP_OK) rc = d_result.alloc(ctx, 4 * CB_FRAMES);
+        if (rc == HBHIP_OK) rc = h_result.alloc(ctx, 4 * CB_FRAMES);
+        if (rc != HBHIP_OK) return rc;
+        if (nmasks) HBHIP_CHECK(ctx, hipMemsetAsync(masks.get(), 0, nmasks * msz, ctx->stream));
+        if (!batched) { mask = masks.get(); mask_filtered = mask + msz; mask_temp = mask + 2 * msz; }
+        else if (own_pass) mask_temp = masks.get();
         if (depth == 8)
         {
-            HBHIP_CHECK(ctx, hipMemcpyAsync(d_lut, par.gamma_lut, sizeof(float) * 256, hipMemcpyHostToDevice, ctx->stream));
+            HBHIP_CHECK(ctx, hipMemcpyAsync(d_lut.get(), par.gamma_lut, sizeof(float) * 256, hipMemcpyHostToDevice, ctx->stream));
             lut_ready = true;
         }
-        HBHIP_CHECK(ctx, hipMalloc((void **)&d_result, sizeof(int) * 4));
-        HBHIP_CHECK(ctx, hipHostMalloc((void **)&h_result, sizeof(int) * 4, hipHostMallocDefault));
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         k.mode = par.mode; k.spatial_metric = par.spatial_metric;
         k.motion_threshold = par.motion_threshold; k.spatial_threshold = par.spatial_threshold;
@@ -629,8 +621,8 @@ public:
             }
         }
         if (!ok) return HBHIP_OK;                                          // not monotone: the float form stays
-        HBHIP_CHECK(ctx, hipMalloc((void **)&d_tab, sizeof(uint32_t) * 512));
-        HBHIP_CHECK(ctx, hipMemcpy(d_tab, tab.data(), sizeof(uint32_t) * 512, hipMemcpyHostToDevice));
+        if (const int rc = d_tab.alloc(ctx, 512)) return rc;
+        HBHIP_CHECK(ctx, hipMemcpy(d_tab.get(), tab.data(), sizeof(uint32_t) * 512, hipMemcpyHostToDevice));
         return HBHIP_OK;
     }
 
@@ -638,7 +630,7 @@ public:
     int set_gamma_lut(const float *lut, int entries)
     {
         if (!lut || entries != k.lut_len) return HBHIP_ERR_ARG;
-        HBHIP_CHECK(ctx, hipMemcpyAsync(d_lut, lut, sizeof(float) * entries, hipMemcpyHostToDevice, ctx->stream));
+        HBHIP_CHECK(ctx, hipMemcpyAsync(d_lut.get(), lut, sizeof(float) * entries, hipMemcpyHostToDevice, ctx->stream));
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         lut_ready = true;
         if (k.lut_len == 256 && (par.mode & 1))
@@ -646,7 +638,7 @@ public:
             // the 8-bit kernel classifies through integer thresholds derived from the table (build_threshold_tables):
             // a new table means new thresholds, or the float form when the new one is not monotone
             memcpy(par.gamma_lut, lut, sizeof(float) * 256);
-            if (d_tab) { (void)hipFree(d_tab); d_tab = nullptr; }
+            d_tab.reset();
             return build_threshold_tables();
         }
         return HBHIP_OK;
@@ -656,7 +648,6 @@ public:
     int store(const void *luma, int stride, bool device)
     {
         // rotate: the allocation that held ref[0] is reused unless ref[1]/ref[2] still point at it
-        int freed = ref[0];
         ref[0] = ref[1]; ref[1] = ref[2];
         if (luma == nullptr)
         {
@@ -666,120 +657,66 @@ public:
         int use = -1;
         for (int i = 0; i < 3 && use < 0; i++)
             if (i != ref[0] && i != ref[1]) use = i;
-        (void)freed;
         if (stride < width * bps) return HBHIP_ERR_ARG;
         if (device)
-            HBHIP_CHECK(ctx, hipMemcpy2DAsync(luma_alloc[use], pitch, luma, stride, (size_t)width * bps, height,
+            HBHIP_CHECK(ctx, hipMemcpy2DAsync(luma_alloc[use].get(), pitch, luma, stride, (size_t)width * bps, height,
                                               hipMemcpyDeviceToDevice, ctx->stream));
         else
         {
             // on the context's upload stream: wait for this copy only, not for what the job's other filters have
             // queued on the compute stream.  The slot being overwritten was last read by a classify() two frames ago,
             // and classify() waits for its kernels, so nothing can still be reading it.
-            hipEvent_t done = ctx->sync_ev_get();
-            if (!done) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(store)");
-            HBHIP_CHECK(ctx, hipMemcpy2DAsync(luma_alloc[use], pitch, luma, stride, (size_t)width * bps, height,
+            HBHIP_CHECK(ctx, hipMemcpy2DAsync(luma_alloc[use].get(), pitch, luma, stride, (size_t)width * bps, height,
                                               hipMemcpyHostToDevice, ctx->up()));
-            HBHIP_CHECK(ctx, hipEventRecord(done, ctx->up()));
-            const hipError_t e = hipEventSynchronize(done);
-            ctx->sync_ev_put(done);
-            if (e != hipSuccess) return ctx->fail(e, "hipEventSynchronize(store)");
+            if (const int rc = hbhip_wait_behind(ctx, ctx->up(), "comb detect: store")) return rc;
         }
         ref[2] = use;
         return HBHIP_OK;
     }
 
-    int classify(int force, int *combed)
+    // the block scores of n masks `fs` bytes apart, read back into h_result and waited for: an event behind the read-back
+    // rather than the whole stream, which other filter threads keep filling
+    int score(const uint8_t *m, size_t fs, int n, bool best_block, bool filt, int *blocks_x_out)
     {
-        if (ref[0] < 0 || ref[1] < 0 || ref[2] < 0) return HBHIP_ERR_STATE;
-        if ((par.mode & 1) && !lut_ready) return HBHIP_ERR_STATE;
-        dim3 b(64, 4);
-        dim3 g((mstride + 63) / 64, (height - 4 + 3) / 4);
-        const size_t lds = (par.mode & 1) ? sizeof(float) * k.lut_len : 0;
-        const bool quad = bps == 1 && !overlay;
-        if (quad)
-        {
-            CombBatch B;
-            for (int i = 0; i < 3; i++) B.luma[i] = luma_alloc[ref[i]];
-            B.force = force ? 1u : 0u; B.n = 1;
-            const dim3 g4(hbhip_grid_x((mstride / 4 + 63) / 64), (height - 4 + 3) / 4, 1);
-            if ((par.mode & 1) && d_tab) HBHIP_LAUNCH(ctx, "comb_detect", (comb_detect4_kernel<true, true>), g4, b, 0, B, pitch, mask, (size_t)0, mstride, width, height, k, (const float *)d_lut, (const uint32_t *)d_tab);
-            else if (par.mode & 1)       HBHIP_LAUNCH(ctx, "comb_detect", (comb_detect4_kernel<true, false>), g4, b, 0, B, pitch, mask, (size_t)0, mstride, width, height, k, (const float *)d_lut, (const uint32_t *)nullptr);
-            else                         HBHIP_LAUNCH(ctx, "comb_detect", (comb_detect4_kernel<false, false>), g4, b, 0, B, pitch, mask, (size_t)0, mstride, width, height, k, (const float *)d_lut, (const uint32_t *)nullptr);
-        }
-        else if (bps == 2)
-            HBHIP_LAUNCH(ctx, "comb_detect", comb_detect_kernel<uint16_t>, g, b, lds, (const uint16_t *)luma_alloc[ref[0]],
-                         (const uint16_t *)luma_alloc[ref[1]], (const uint16_t *)luma_alloc[ref[2]], pitch / 2, mask, mstride,
-                         width, height, k, (const float *)d_lut, force);
-        else
-            HBHIP_LAUNCH(ctx, "comb_detect", comb_detect_kernel<uint8_t>, g, b, lds, (const uint8_t *)luma_alloc[ref[0]],
-                         (const uint8_t *)luma_alloc[ref[1]], (const uint8_t *)luma_alloc[ref[2]], pitch, mask, mstride,
-                         width, height, k, (const float *)d_lut, force);
-        const bool filt = (par.mode & 2) != 0;
-        dim3 gm((width - 2 + 63) / 64, (height - 2 + 3) / 4);
-        if (filt)
-        {
-            // overlay modes: the box outline written into the filtered mask persists in the cells no pass rewrites
-            // and the passes read it, so they run one by one on the real buffers (the fused kernel carries its
-            // intermediate masks in LDS and assumes those cells are zero)
-            const bool fused = par.filter_mode == 2 && !overlay;
-            if (fused && quad)
-                HBHIP_LAUNCH(ctx, "comb_mask_passes", comb_mask_fused4_kernel, dim3((width + 63) / 64, (height + 15) / 16, 1), b, 0,
-                             (const uint8_t *)mask, mask_filtered, (size_t)0, mstride, width, height);
-            else if (fused)
-                HBHIP_LAUNCH(ctx, "comb_mask_passes", comb_mask_fused_kernel,
-                             dim3((width - 2 + CF_W - 1) / CF_W, (height - 2 + CF_H - 1) / CF_H), b, 0,
-                             (const uint8_t *)mask, mask_filtered, mstride, width, height);
-            else if (par.filter_mode == 1)
-                HBHIP_LAUNCH(ctx, "comb_mask_filter", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)mask, mask_filtered, mstride, width, height, 0, 1);
-            else
-                HBHIP_LAUNCH(ctx, "comb_mask_filter", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)mask, mask_temp, mstride, width, height, 0, 0);
-            if (par.filter_mode == 2 && !fused)
-            {
-                HBHIP_LAUNCH(ctx, "comb_mask_erode", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)mask_temp, mask_filtered, mstride, width, height, 1, 0);
-                HBHIP_LAUNCH(ctx, "comb_mask_dilate", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)mask_filtered, mask_temp, mstride, width, height, 2, 0);
-                HBHIP_LAUNCH(ctx, "comb_mask_erode", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)mask_temp, mask_filtered, mstride, width, height, 1, 0);
-            }
-        }
-        HBHIP_CHECK(ctx, hipMemsetAsync(d_result, 0, sizeof(int) * 4, ctx->stream));
+        HBHIP_CHECK(ctx, hipMemsetAsync(d_result.get(), 0, sizeof(int) * 4 * n, ctx->stream));
         const int bw = par.block_width, bh = par.block_height;
         const int blocks_x = (width - bw + bw - 1) / bw;             // x = 0, bw, ... while x < width - bw
         const int blocks_y = height / bh;                            // y + bh <= height
         if (blocks_x > 0 && blocks_y > 0)
-        {
-            HBHIP_LAUNCH(ctx, "comb_block_score", comb_score_kernel, dim3(blocks_y), dim3(256), 0,
-                         (const uint8_t *)(filt ? mask_filtered : mask), mstride, width, height, bw, bh,
-                         par.block_threshold, filt ? 1 : 0, blocks_x, d_result, overlay ? 1 : 0, (size_t)0);
-        }
+            HBHIP_LAUNCH(ctx, "comb_block_score", comb_score_kernel, dim3(blocks_y, n), dim3(256), 0, m, mstride, width, height, bw, bh,
+                         par.block_threshold, filt ? 1 : 0, blocks_x, d_result.get(), best_block ? 1 : 0, fs);
         HBHIP_CHECK(ctx, hipGetLastError());
-        HBHIP_CHECK(ctx, hipMemcpyAsync(h_result, d_result, sizeof(int) * 4, hipMemcpyDeviceToHost, ctx->stream));
-        {
-            // wait for the verdict - an event behind the read-back rather than the whole stream, which other filter
-            // threads keep filling
-            hipEvent_t done = ctx->sync_ev_get();
-            if (!done) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(classify)");
-            HBHIP_CHECK(ctx, hipEventRecord(done, ctx->stream));
-            const hipError_t e = hipEventSynchronize(done);
-            ctx->sync_ev_put(done);
-            if (e != hipSuccess) return ctx->fail(e, "hipEventSynchronize(classify)");
-        }
-        *combed = h_result[0];
-        if (overlay && h_result[2] > 0 && blocks_x > 0)
-        {
-            const int idx = h_result[1] > 0 ? 0x7fffffff - h_result[1] : h_result[2] - 1;
-            box_x = (idx % blocks_x) * bw;
-            box_y = (idx / blocks_x) * bh;
-        }
+        HBHIP_CHECK(ctx, hipMemcpyAsync(h_result.get(), d_result.get(), sizeof(int) * 4 * n, hipMemcpyDeviceToHost, ctx->stream));
+        *blocks_x_out = blocks_x;
+        return hbhip_wait_behind(ctx, ctx->stream, "comb detect: verdict");
+    }
+
+    // the masks of n frames of a batch, (mask, filtered mask) a frame: zeroed when made, and every launch rewrites all of a
+    // mask but the cells that stay zero, so growing them loses nothing
+    int batch_masks(int n)
+    {
+        const size_t need = 2 * msz * (size_t)n;
+        if (need <= bmasks.count()) return HBHIP_OK;
+        if (const int rc = bmasks.alloc(ctx, need)) return rc;
+        HBHIP_CHECK(ctx, hipMemsetAsync(bmasks.get(), 0, need, ctx->stream));
         return HBHIP_OK;
     }
 
-    // n frames at once: frame i is classified from lumas[i], lumas[i + 1], lumas[i + 2] (device pointers, `stride` bytes a
-    // row), in three launches and one read-back for all of them.  Independent of the ring store() / classify() work on.
+    // n frames at once (the ABI's entry): only with the mask filter the batched kernels have, or none
     int classify_many(const void *const *lumas, int stride, int n, uint32_t force_bits, int *combed)
     {
+        if ((par.mode & 2) && par.filter_mode != 2) return HBHIP_ERR_UNSUPPORTED;
+        return classify_batch(lumas, stride, n, force_bits, combed);
+    }
+
+    // Frame i is classified from lumas[i], lumas[i + 1], lumas[i + 2] (device pointers, `stride` bytes a row), in three
+    // launches and one read-back for all of them.  The one place that picks a comb_detect4_kernel.  A mask filter mode
+    // that is a pass of its own (0, 1) runs behind it for a batch of one: classify().
+    int classify_batch(const void *const *lumas, int stride, int n, uint32_t force_bits, int *combed)
+    {
         if (n < 1 || n > CB_FRAMES || bps != 1 || overlay) return HBHIP_ERR_UNSUPPORTED;
-        const bool filt = (par.mode & 2) != 0;
-        if (filt && par.filter_mode != 2) return HBHIP_ERR_UNSUPPORTED;
+        const bool filt = (par.mode & 2) != 0, own_pass = filt && par.filter_mode != 2;
+        if (own_pass && n != 1) return HBHIP_ERR_UNSUPPORTED;
         if ((par.mode & 1) && !lut_ready) return HBHIP_ERR_STATE;
         if (stride < width || (stride & 3)) return HBHIP_ERR_ARG;
         CombBatch B;
@@ -789,37 +726,83 @@ public:
             B.luma[i] = (const uint8_t *)lumas[i];
         }
         B.force = force_bits; B.n = n;
-        const size_t msz = (size_t)mstride * height + 256, fs = 2 * msz;
-        if (!bmasks)
-        {
-            HBHIP_CHECK(ctx, hipMalloc((void **)&bmasks, fs * CB_FRAMES));
-            HBHIP_CHECK(ctx, hipMemsetAsync(bmasks, 0, fs * CB_FRAMES, ctx->stream));
-            HBHIP_CHECK(ctx, hipMalloc((void **)&d_bresult, sizeof(int) * 4 * CB_FRAMES));
-            HBHIP_CHECK(ctx, hipHostMalloc((void **)&h_bresult, sizeof(int) * 4 * CB_FRAMES, hipHostMallocDefault));
-        }
+        const size_t fs = 2 * msz;
+        if (const int rc = batch_masks(n)) return rc;
+        uint8_t *const bm = bmasks.get();
+        const float *lut = d_lut.get();
+        const uint32_t *tab = d_tab.get();
         const dim3 b(64, 4), g4(hbhip_grid_x((mstride / 4 + 63) / 64), (height - 4 + 3) / 4, n);
-        if ((par.mode & 1) && d_tab) HBHIP_LAUNCH(ctx, "comb_detect", (comb_detect4_kernel<true, true>), g4, b, 0, B, stride, bmasks, fs, mstride, width, height, k, (const float *)d_lut, (const uint32_t *)d_tab);
-        else if (par.mode & 1)       HBHIP_LAUNCH(ctx, "comb_detect", (comb_detect4_kernel<true, false>), g4, b, 0, B, stride, bmasks, fs, mstride, width, height, k, (const float *)d_lut, (const uint32_t *)nullptr);
-        else                         HBHIP_LAUNCH(ctx, "comb_detect", (comb_detect4_kernel<false, false>), g4, b, 0, B, stride, bmasks, fs, mstride, width, height, k, (const float *)d_lut, (const uint32_t *)nullptr);
-        if (filt)
+        if ((par.mode & 1) && tab) HBHIP_LAUNCH(ctx, "comb_detect", (comb_detect4_kernel<true, true>), g4, b, 0, B, stride, bm, fs, mstride, width, height, k, lut, tab);
+        else if (par.mode & 1)     HBHIP_LAUNCH(ctx, "comb_detect", (comb_detect4_kernel<true, false>), g4, b, 0, B, stride, bm, fs, mstride, width, height, k, lut, tab);
+        else                       HBHIP_LAUNCH(ctx, "comb_detect", (comb_detect4_kernel<false, false>), g4, b, 0, B, stride, bm, fs, mstride, width, height, k, lut, (const uint32_t *)nullptr);
+        const dim3 gm((width - 2 + 63) / 64, (height - 2 + 3) / 4);
+        if (own_pass && par.filter_mode == 1)
+            HBHIP_LAUNCH(ctx, "comb_mask_filter", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)bm, bm + msz, mstride, width, height, 0, 1);
+        else if (own_pass)      // (into the intermediate mask: the score then reads a filtered mask nothing wrote, as ever)
+            HBHIP_LAUNCH(ctx, "comb_mask_filter", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)bm, mask_temp, mstride, width, height, 0, 0);
+        else if (filt)
             HBHIP_LAUNCH(ctx, "comb_mask_passes", comb_mask_fused4_kernel, dim3((width + 63) / 64, (height + 15) / 16, n), b, 0,
-                         (const uint8_t *)bmasks, bmasks + msz, fs, mstride, width, height);
-        HBHIP_CHECK(ctx, hipMemsetAsync(d_bresult, 0, sizeof(int) * 4 * n, ctx->stream));
-        const int bw = par.block_width, bh = par.block_height;
-        const int blocks_x = (width - bw + bw - 1) / bw, blocks_y = height / bh;
-        if (blocks_x > 0 && blocks_y > 0)
-            HBHIP_LAUNCH(ctx, "comb_block_score", comb_score_kernel, dim3(blocks_y, n), dim3(256), 0,
-                         (const uint8_t *)(filt ? bmasks + msz : bmasks), mstride, width, height, bw, bh,
-                         par.block_threshold, filt ? 1 : 0, blocks_x, d_bresult, 0, fs);
-        HBHIP_CHECK(ctx, hipGetLastError());
-        HBHIP_CHECK(ctx, hipMemcpyAsync(h_bresult, d_bresult, sizeof(int) * 4 * n, hipMemcpyDeviceToHost, ctx->stream));
-        hipEvent_t done = ctx->sync_ev_get();
-        if (!done) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(classify_many)");
-        HBHIP_CHECK(ctx, hipEventRecord(done, ctx->stream));
-        const hipError_t e = hipEventSynchronize(done);
-        ctx->sync_ev_put(done);
-        if (e != hipSuccess) return ctx->fail(e, "hipEventSynchronize(classify_many)");
-        for (int i = 0; i < n; i++) combed[i] = h_bresult[4 * i];
+                         (const uint8_t *)bm, bm + msz, fs, mstride, width, height);
+        int blocks_x;
+        if (const int rc = score(filt ? bm + msz : bm, fs, n, false, filt, &blocks_x)) return rc;
+        for (int i = 0; i < n; i++) combed[i] = h_result.get()[4 * i];
+        return HBHIP_OK;
+    }
+
+    // The frame in the ring: from ref[0], ref[1], ref[2].  8-bit pictures without overlay are a batch of one; the overlay
+    // modes and the deeper pictures have the generic kernel and the mask filters pass by pass, on masks of their own.
+    int classify(int force, int *combed)
+    {
+        if (ref[0] < 0 || ref[1] < 0 || ref[2] < 0) return HBHIP_ERR_STATE;
+        if ((par.mode & 1) && !lut_ready) return HBHIP_ERR_STATE;
+        if (batched)
+        {
+            const void *lumas[3];
+            for (int i = 0; i < 3; i++) lumas[i] = luma_alloc[ref[i]].get();
+            return classify_batch(lumas, pitch, 1, force ? 1u : 0u, combed);
+        }
+        dim3 b(64, 4);
+        dim3 g((mstride + 63) / 64, (height - 4 + 3) / 4);
+        const size_t lds = (par.mode & 1) ? sizeof(float) * k.lut_len : 0;
+        if (bps == 2)
+            HBHIP_LAUNCH(ctx, "comb_detect", comb_detect_kernel<uint16_t>, g, b, lds, (const uint16_t *)luma_alloc[ref[0]].get(),
+                         (const uint16_t *)luma_alloc[ref[1]].get(), (const uint16_t *)luma_alloc[ref[2]].get(), pitch / 2, mask, mstride,
+                         width, height, k, (const float *)d_lut.get(), force);
+        else
+            HBHIP_LAUNCH(ctx, "comb_detect", comb_detect_kernel<uint8_t>, g, b, lds, (const uint8_t *)luma_alloc[ref[0]].get(),
+                         (const uint8_t *)luma_alloc[ref[1]].get(), (const uint8_t *)luma_alloc[ref[2]].get(), pitch, mask, mstride,
+                         width, height, k, (const float *)d_lut.get(), force);
+        const bool filt = (par.mode & 2) != 0;
+        dim3 gm((width - 2 + 63) / 64, (height - 2 + 3) / 4);
+        if (filt)
+        {
+            // overlay modes: the box outline written into the filtered mask persists in the cells no pass rewrites
+            // and the passes read it, so they run one by one on the real buffers (the fused kernel carries its
+            // intermediate masks in LDS and assumes those cells are zero)
+            if (par.filter_mode == 2 && !overlay)
+                HBHIP_LAUNCH(ctx, "comb_mask_passes", comb_mask_fused_kernel,
+                             dim3((width - 2 + CF_W - 1) / CF_W, (height - 2 + CF_H - 1) / CF_H), b, 0,
+                             (const uint8_t *)mask, mask_filtered, mstride, width, height);
+            else if (par.filter_mode == 1)
+                HBHIP_LAUNCH(ctx, "comb_mask_filter", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)mask, mask_filtered, mstride, width, height, 0, 1);
+            else
+                HBHIP_LAUNCH(ctx, "comb_mask_filter", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)mask, mask_temp, mstride, width, height, 0, 0);
+            if (par.filter_mode == 2 && overlay)
+            {
+                HBHIP_LAUNCH(ctx, "comb_mask_erode", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)mask_temp, mask_filtered, mstride, width, height, 1, 0);
+                HBHIP_LAUNCH(ctx, "comb_mask_dilate", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)mask_filtered, mask_temp, mstride, width, height, 2, 0);
+                HBHIP_LAUNCH(ctx, "comb_mask_erode", comb_mask_pass_kernel, gm, b, 0, (const uint8_t *)mask_temp, mask_filtered, mstride, width, height, 1, 0);
+            }
+        }
+        int blocks_x;
+        if (const int rc = score(filt ? mask_filtered : mask, 0, 1, overlay, filt, &blocks_x)) return rc;
+        *combed = h_result.get()[0];
+        if (overlay && h_result.get()[2] > 0 && blocks_x > 0)
+        {
+            const int idx = h_result.get()[1] > 0 ? 0x7fffffff - h_result.get()[1] : h_result.get()[2] - 1;
+            box_x = (idx % blocks_x) * par.block_width;
+            box_y = (idx / blocks_x) * par.block_height;
+        }
         return HBHIP_OK;
     }
 
@@ -858,17 +841,11 @@ public:
             off[c] = total;
             total += (size_t)pitchv[c] * plane_h[c];
         }
-        if (total > stage_bytes)
-        {
-            if (stage) (void)hipFree(stage);
-            stage = nullptr; stage_bytes = 0;
-            HBHIP_CHECK(ctx, hipMalloc((void **)&stage, total));
-            stage_bytes = total;
-        }
+        if (const int rc = stage.reserve(ctx, total)) return rc;
         hbhip_dev_frame d;
         for (int c = 0; c < 3; c++)
         {
-            d.plane[c] = stage + off[c]; d.stride[c] = pitchv[c];
+            d.plane[c] = stage.get() + off[c]; d.stride[c] = pitchv[c];
             if (fr->plane[c] == nullptr || fr->stride[c] < plane_w[c] * bps) return HBHIP_ERR_ARG;
             HBHIP_CHECK(ctx, hipMemcpy2DAsync(d.plane[c], pitchv[c], fr->plane[c], fr->stride[c], (size_t)plane_w[c] * bps,
                                               plane_h[c], hipMemcpyHostToDevice, ctx->stream));
@@ -895,19 +872,20 @@ private:
     CombConst k;
     int width = 0, height = 0, pitch = 0, mstride = 0, bps = 1;
     bool lut_ready = false;
-    uint8_t *luma_alloc[3] = {nullptr, nullptr, nullptr};
-    int slot[3];
+    DevBuf<uint8_t> luma_alloc[3];
     int ref[3] = {-1, -1, -1};
-    uint8_t *masks = nullptr, *mask = nullptr, *mask_filtered = nullptr, *mask_temp = nullptr;
-    float *d_lut = nullptr;
-    uint32_t *d_tab = nullptr;          // comb_detect4_kernel<true, true>'s threshold tables (8-bit gamma metric)
-    int *d_result = nullptr, *h_result = nullptr;
+    size_t msz = 0;                                  // bytes of one mask
+    bool batched = false;                            // classify() is a batch of one frame (classify_batch)
+    DevBuf<uint8_t> masks;                           // classify() otherwise: the three below; batched: mask_temp, where a pass needs it
+    uint8_t *mask = nullptr, *mask_filtered = nullptr, *mask_temp = nullptr;
+    DevBuf<float> d_lut;
+    DevBuf<uint32_t> d_tab;             // comb_detect4_kernel<true, true>'s threshold tables (8-bit gamma metric)
+    DevBuf<int> d_result;               // 4 ints a frame, CB_FRAMES frames
+    PinnedBuf<int> h_result;
     bool overlay = false;
     int box_x = 0, box_y = 0;                        // pv->mask_box_x / _y
-    uint8_t *stage = nullptr;
-    size_t stage_bytes = 0;
-    uint8_t *bmasks = nullptr;                       // classify_many: CB_FRAMES x (mask, filtered mask)
-    int *d_bresult = nullptr, *h_bresult = nullptr;
+    DevBuf<uint8_t> stage;
+    DevBuf<uint8_t> bmasks;                          // a batch's frames x (mask, filtered mask): batch_masks()
 };
 
 } // namespace

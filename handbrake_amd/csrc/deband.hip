@@ -248,7 +248,6 @@ class DebandFilter : public BurstFilter
 {
 public:
     DebandFilter(hbhip_ctx *c, const hbhip_deband_params &p) : BurstFilter(c), par(p) {}
-    ~DebandFilter() override { if (table) (void)hipFree(table); }
     // the tile kernel's LDS bytes (0: its halo does not fit)
     int tile_bytes() const
     {
@@ -284,7 +283,7 @@ public:
             }
             a.nf = nf;
             a.aligned = (bits & 7) == 0;
-            a.table = table;
+            a.table = table.get();
             a.tw = in_geo.pw[0];
             a.R = R; a.RP = RP;
             const dim3 grid(hbhip_grid_x((a.w[0] + DB_TW - 1) / DB_TW), (a.h[0] + DB_TH - 1) / DB_TH, 3);
@@ -294,7 +293,7 @@ public:
         });
     }
     hbhip_deband_params par;
-    void *table = nullptr;
+    DevBuf<uint8_t> table;
     bool wide_table = false;
     int R = 0, RP = 0;
     int kernel = 0;                     // hbhip_deband_set_kernel
@@ -360,12 +359,13 @@ extern "C" int hbhip_deband_create(hbhip_ctx *ctx, const hbhip_deband_params *p,
     f->R = R;
     f->RP = (R + 3) & ~3;
     const size_t bytes = 2 * n * (wide ? sizeof(int16_t) : sizeof(int8_t));
-    hipError_t e = hipMalloc(&f->table, bytes);
-    if (e == hipSuccess) e = hipMemcpy(f->table, wide ? (const void *)t16.data() : (const void *)t8.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess)
+    rc = f->table.alloc(ctx, bytes);
+    if (rc == HBHIP_OK && hipMemcpy(f->table.get(), wide ? (const void *)t16.data() : (const void *)t8.data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
+        rc = HBHIP_ERR_HIP;
+    if (rc != HBHIP_OK)
     {
         delete f;
-        return e == hipErrorOutOfMemory ? HBHIP_ERR_NOMEM : HBHIP_ERR_HIP;
+        return rc;
     }
     *out = f;
     return HBHIP_OK;

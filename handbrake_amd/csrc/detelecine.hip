@@ -257,10 +257,10 @@ struct DetelecineFilter : hbhip_filter
     bool frame_busy = false;
     int passthrough_left = 1;
     int next_flags = 0;
-    int *d_slots = nullptr;      // capacity * 3 * len ints
+    DevBuf<int> d_slots;         // capacity * 3 * len ints
     int capacity = 0;
-    int *d_out = nullptr;        // 2 * DT_REQ_MAX
-    int *h_out = nullptr;        // pinned
+    DevBuf<int> d_out;           // 2 * DT_REQ_MAX
+    PinnedBuf<int> h_out;
     hipEvent_t ev_out = nullptr;
 
     explicit DetelecineFilter(hbhip_ctx *c) : hbhip_filter(c) {}
@@ -270,16 +270,13 @@ struct DetelecineFilter : hbhip_filter
         (void)hipStreamSynchronize(ctx->stream);
         for (DevPicture *p : outq) hbhip_pic_release(p, ctx);
         for (HeldPic *h : held) { hbhip_pic_release(h->pic, ctx); delete h; }
-        if (d_slots) (void)hipFree(d_slots);
-        if (d_out) (void)hipFree(d_out);
-        if (h_out) (void)hipHostFree(h_out);
         if (ev_out) (void)hipEventDestroy(ev_out);
-    }
+    }                                    // (the buffers go with their members, behind the wait above)
 
     int init()
     {
-        HBHIP_CHECK(ctx, hipMalloc((void **)&d_out, 2 * DT_REQ_MAX * sizeof(int)));
-        HBHIP_CHECK(ctx, hipHostMalloc((void **)&h_out, 2 * DT_REQ_MAX * sizeof(int), hipHostMallocDefault));
+        if (const int rc = d_out.alloc(ctx, 2 * DT_REQ_MAX)) return rc;
+        if (const int rc = h_out.alloc(ctx, 2 * DT_REQ_MAX)) return rc;
         HBHIP_CHECK(ctx, hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
         // the queue starts as nine places in a ring (pullup_make_field_queue(c, 8))
         for (int k = 0; k < 9; k++) { int rc = add_node(); if (rc != HBHIP_OK) return rc; }
@@ -299,17 +296,16 @@ struct DetelecineFilter : hbhip_filter
         if (len > 0 && k >= capacity)
         {
             const int cap = capacity ? 2 * capacity : 16;
-            int *d = nullptr;
-            const size_t per = (size_t)3 * len * sizeof(int);
-            HBHIP_CHECK(ctx, hipMalloc((void **)&d, cap * per));
-            HBHIP_CHECK(ctx, hipMemsetAsync(d, 0, cap * per, ctx->stream));
-            if (d_slots)
+            DevBuf<int> d;                                  // (a failure below frees it on the way out)
+            const size_t per = (size_t)3 * len;
+            if (const int rc = d.alloc(ctx, cap * per)) return rc;
+            HBHIP_CHECK(ctx, hipMemsetAsync(d.get(), 0, cap * per * sizeof(int), ctx->stream));
+            if (d_slots.get())
             {
-                HBHIP_CHECK(ctx, hipMemcpyAsync(d, d_slots, capacity * per, hipMemcpyDeviceToDevice, ctx->stream));
+                HBHIP_CHECK(ctx, hipMemcpyAsync(d.get(), d_slots.get(), capacity * per * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
                 HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-                (void)hipFree(d_slots);
             }
-            d_slots = d;
+            d_slots = std::move(d);
             capacity = cap;
         }
         auto n = std::make_unique<FieldSlot>();
@@ -317,7 +313,7 @@ struct DetelecineFilter : hbhip_filter
         nodes.push_back(std::move(n));
         return HBHIP_OK;
     }
-    int *slot_arrays(int k) const { return d_slots + (size_t)k * 3 * len; }
+    int *slot_arrays(int k) const { return d_slots.get() + (size_t)k * 3 * len; }
 
     // ---- pictures and locks ----
     static void lock_pic(HeldPic *h, int parity)
@@ -429,7 +425,7 @@ struct DetelecineFilter : hbhip_filter
         {
             const int n = (int)std::min<size_t>(DT_REQ_MAX, todo.size() - base);
             ReduceArgs a{};
-            a.slots = d_slots; a.len = len; a.n = n; a.out = d_out;
+            a.slots = d_slots.get(); a.len = len; a.n = n; a.out = d_out.get();
             for (int r = 0; r < n; r++)
             {
                 const Deferred &d = todo[base + r];
@@ -437,14 +433,14 @@ struct DetelecineFilter : hbhip_filter
                 if (d.kind == 0) { a.s0[r] = d.f->next->next->slot; a.s1[r] = d.f->next->next->next->slot; a.s2[r] = 0; }
                 else             { a.s0[r] = d.f->prev->slot; a.s1[r] = d.f->slot; a.s2[r] = d.f->next->slot; }
             }
-            HBHIP_CHECK(ctx, hipMemsetAsync(d_out, 0, 2 * n * sizeof(int), ctx->stream));
+            HBHIP_CHECK(ctx, hipMemsetAsync(d_out.get(), 0, 2 * n * sizeof(int), ctx->stream));
             const unsigned gx = (unsigned)std::min(64, std::max(1, (len + 2047) / 2048));
             HBHIP_LAUNCH(ctx, "dt_reduce", dt_reduce_kernel, dim3(gx, (unsigned)n), dim3(256), 0, a);
             HBHIP_CHECK(ctx, hipGetLastError());
-            HBHIP_CHECK(ctx, hipMemcpyAsync(h_out, d_out, 2 * n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+            HBHIP_CHECK(ctx, hipMemcpyAsync(h_out.get(), d_out.get(), 2 * n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
             HBHIP_CHECK(ctx, hipEventRecord(ev_out, ctx->stream));
             HBHIP_CHECK(ctx, hipEventSynchronize(ev_out));
-            for (int k = 0; k < 2 * n; k++) res[2 * base + k] = h_out[k];
+            for (int k = 0; k < 2 * n; k++) res[2 * base + k] = h_out.get()[k];
         }
         return HBHIP_OK;
     }

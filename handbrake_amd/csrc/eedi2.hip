@@ -2749,26 +2749,18 @@ extern "C" unsigned hbhip_debug_mask_chain(int spin_limit)
 
 int MaskChainGuard::init(hbhip_ctx *ctx)
 {
-    HBHIP_CHECK(ctx, hipMalloc((void **)&err, sizeof(uint32_t)));
-    HBHIP_CHECK(ctx, hipMemsetAsync(err, 0, sizeof(uint32_t), ctx->stream));
-    HBHIP_CHECK(ctx, hipHostMalloc((void **)&count_host, sizeof(uint32_t), hipHostMallocMapped));
-    *count_host = 0;
-    HBHIP_CHECK(ctx, hipHostGetDevicePointer((void **)&count_dev, count_host, 0));
+    if (const int rc = err.alloc(ctx, 1)) return rc;
+    HBHIP_CHECK(ctx, hipMemsetAsync(err.get(), 0, sizeof(uint32_t), ctx->stream));
+    if (const int rc = count_host.alloc(ctx, 1)) return rc;
+    *count_host.get() = 0;
+    HBHIP_CHECK(ctx, hipHostGetDevicePointer((void **)&count_dev, count_host.get(), 0));
     return HBHIP_OK;
-}
-
-void MaskChainGuard::destroy()
-{
-    poll("eedi2");
-    if (err) (void)hipFree(err);
-    if (count_host) (void)hipHostFree(count_host);
-    err = nullptr; count_host = nullptr; count_dev = nullptr;
 }
 
 void MaskChainGuard::poll(const char *who)
 {
-    if (!count_host) return;
-    const uint32_t now = __atomic_load_n(count_host, __ATOMIC_RELAXED);
+    if (!count_host.get()) return;
+    const uint32_t now = __atomic_load_n(count_host.get(), __ATOMIC_RELAXED);
     if (now == seen) return;
     if (seen == 0)
         fprintf(stderr, "hbhip: %s: a wait of the mask chain ran out (workgroups were not dispatched in order); the batch's "
@@ -2779,7 +2771,7 @@ void MaskChainGuard::poll(const char *who)
 
 void MaskChainGuard::bind(MaskChain &C) const
 {
-    C.err = err;
+    C.err = err.get();
     C.fallbacks = count_dev;
     C.spin_limit = eedi_chain_spin_limit();
 }
@@ -2796,13 +2788,9 @@ EediEngineBase::EediEngineBase(hbhip_ctx *ctx, const PicGeometry &geo, const Eed
     cap_ = std::min(std::max(capacity, 1), EEDI_MAX_BATCH);
 }
 
-EediEngineBase::~EediEngineBase()
+EediEngineBase::~EediEngineBase()                  // (the slab, the flags and the guard's words go with their members, behind this)
 {
-    if (slab_) (void)hipFree(slab_);
-    if (chain_flags_) (void)hipFree(chain_flags_);
-    if (chain_has_) (void)hipFree(chain_has_);
-    if (plane_flags_) (void)hipFree(plane_flags_);
-    guard_.destroy();
+    guard_.poll("eedi2");
     for (int g = 0; g < MAX_SIDE; g++)
     {
         if (side_[g]) (void)hipStreamDestroy(side_[g]);
@@ -2811,11 +2799,6 @@ EediEngineBase::~EediEngineBase()
     if (ahead_) (void)hipStreamDestroy(ahead_);
     if (ev_fork_) (void)hipEventDestroy(ev_fork_);
     if (ev_mask_) (void)hipEventDestroy(ev_mask_);
-    for (int i = 0; i < 3; i++)
-    {
-        if (deriv_[i]) (void)hipFree(deriv_[i]);
-        if (deriv_tmp_[i]) (void)hipFree(deriv_tmp_[i]);
-    }
 }
 
 // lays a frame out at `at` bytes into a slot (planes as hb_frame_buffer_init places them, strides in bytes); returns the end
@@ -2853,11 +2836,12 @@ int EediEngineBase::init_slots(const EediLayout &L)
     slot_bytes_ = up256(cand_at + L.cand_elem * (size_t)cand_plane_stride_ * 3);
     // one slot more than a batch holds, so that a batch never writes the slot whose mask its first field reads
     const size_t total = slot_bytes_ * (size_t)(cap_ + 1);
-    HBHIP_CHECK(ctx_, hipMalloc((void **)&slab_, total));
-    HBHIP_CHECK(ctx_, hipMemsetAsync(slab_, 0, total, ctx_->stream));
-    for (auto &f : half_) for (int c = 0; c < 3; c++) f.plane[c] = slab_ + (size_t)(uintptr_t)f.plane[c];
-    for (auto &f : full_) for (int c = 0; c < 3; c++) f.plane[c] = slab_ + (size_t)(uintptr_t)f.plane[c];
-    cand_raw_ = slab_ + cand_at;
+    if (const int rc = slab_.alloc(ctx_, total)) return rc;
+    uint8_t *const slab = slab_.get();
+    HBHIP_CHECK(ctx_, hipMemsetAsync(slab, 0, total, ctx_->stream));
+    for (auto &f : half_) for (int c = 0; c < 3; c++) f.plane[c] = slab + (size_t)(uintptr_t)f.plane[c];
+    for (auto &f : full_) for (int c = 0; c < 3; c++) f.plane[c] = slab + (size_t)(uintptr_t)f.plane[c];
+    cand_raw_ = slab + cand_at;
     if (cap_ >= 8)
     {
         HBHIP_CHECK(ctx_, hipEventCreateWithFlags(&ev_fork_, hipEventDisableTiming));
@@ -2872,8 +2856,8 @@ int EediEngineBase::init_slots(const EediLayout &L)
             HBHIP_CHECK(ctx_, hipEventCreateWithFlags(&ev_join_[g], hipEventDisableTiming));
         }
     }
-    HBHIP_CHECK(ctx_, hipMalloc((void **)&plane_flags_, sizeof(uint32_t) * 3 * EEDI_MAX_BATCH));
-    HBHIP_CHECK(ctx_, hipMemsetAsync(plane_flags_, 0, sizeof(uint32_t) * 3 * EEDI_MAX_BATCH, ctx_->stream));
+    if (const int rc = plane_flags_.alloc(ctx_, 3 * EEDI_MAX_BATCH)) return rc;
+    HBHIP_CHECK(ctx_, hipMemsetAsync(plane_flags_.get(), 0, sizeof(uint32_t) * 3 * EEDI_MAX_BATCH, ctx_->stream));
     last_slot_ = cap_;                                             // "the previous mask" of the first run: zeros, like the reference's
     {
         const MaskChain C = eedi_mask_chain_tiles(half_[0], L.tile_w, L.tile_h, L.tile_oy);
@@ -2884,11 +2868,11 @@ int EediEngineBase::init_slots(const EediLayout &L)
     {
         // one completion flag per lower mask tile and field of a batch (MaskChain); 0 is no launch's number
         const size_t nflags = (size_t)chain_ntiles_ * cap_;
-        HBHIP_CHECK(ctx_, hipMalloc((void **)&chain_flags_, sizeof(uint32_t) * nflags));
-        HBHIP_CHECK(ctx_, hipMemsetAsync(chain_flags_, 0, sizeof(uint32_t) * nflags, ctx_->stream));
+        if (const int rc = chain_flags_.alloc(ctx_, nflags)) return rc;
+        HBHIP_CHECK(ctx_, hipMemsetAsync(chain_flags_.get(), 0, sizeof(uint32_t) * nflags, ctx_->stream));
         // and a word per tile (upper ones too) and field: "left a mask sample set" (MaskChain::has)
-        HBHIP_CHECK(ctx_, hipMalloc((void **)&chain_has_, sizeof(uint32_t) * (size_t)chain_group_ * cap_));
-        HBHIP_CHECK(ctx_, hipMemsetAsync(chain_has_, 0, sizeof(uint32_t) * (size_t)chain_group_ * cap_, ctx_->stream));
+        if (const int rc = chain_has_.alloc(ctx_, (size_t)chain_group_ * cap_)) return rc;
+        HBHIP_CHECK(ctx_, hipMemsetAsync(chain_has_.get(), 0, sizeof(uint32_t) * (size_t)chain_group_ * cap_, ctx_->stream));
         const int grc = guard_.init(ctx_);
         if (grc != HBHIP_OK) return grc;
     }
@@ -2897,14 +2881,13 @@ int EediEngineBase::init_slots(const EediLayout &L)
         // cx2, cy2, cxy: height * stride(luma, bytes) ints each, shared by the planes (decomb.c:398-403);
         // zeroed once — the reference mallocs them, and one element per row is read before anything
         // wrote it (eedi2_template.c:1589)
-        const size_t n = sizeof(int) * (size_t)geo_.height * full_[0].stride[0];
+        const size_t n = (size_t)geo_.height * full_[0].stride[0];
         for (int i = 0; i < 3; i++)
-        {
-            HBHIP_CHECK(ctx_, hipMalloc((void **)&deriv_[i], n));
-            HBHIP_CHECK(ctx_, hipMemsetAsync(deriv_[i], 0, n, ctx_->stream));
-            HBHIP_CHECK(ctx_, hipMalloc((void **)&deriv_tmp_[i], n));
-            HBHIP_CHECK(ctx_, hipMemsetAsync(deriv_tmp_[i], 0, n, ctx_->stream));
-        }
+            for (DevBuf<int> *d : { &deriv_[i], &deriv_tmp_[i] })
+            {
+                if (const int rc = d->alloc(ctx_, n)) return rc;
+                HBHIP_CHECK(ctx_, hipMemsetAsync(d->get(), 0, sizeof(int) * n, ctx_->stream));
+            }
     }
     return HBHIP_OK;
 }
@@ -2936,9 +2919,9 @@ int EediEngineBase::next_epoch(hbhip_ctx *lc, uint32_t *epoch)
         // 2^32 mask launches later: 0 means "no launch" in the flag arrays and old numbers must not come round again -
         // drain the device, clear the flags and start over at 1 (months of continuous running apart)
         HBHIP_CHECK(lc, hipDeviceSynchronize());
-        if (chain_flags_) HBHIP_CHECK(lc, hipMemset(chain_flags_, 0, sizeof(uint32_t) * (size_t)chain_ntiles_ * cap_));
-        if (chain_has_) HBHIP_CHECK(lc, hipMemset(chain_has_, 0, sizeof(uint32_t) * (size_t)chain_group_ * cap_));
-        HBHIP_CHECK(lc, hipMemset(plane_flags_, 0, sizeof(uint32_t) * 3 * EEDI_MAX_BATCH));
+        if (chain_flags_.get()) HBHIP_CHECK(lc, hipMemset(chain_flags_.get(), 0, sizeof(uint32_t) * (size_t)chain_ntiles_ * cap_));
+        if (chain_has_.get()) HBHIP_CHECK(lc, hipMemset(chain_has_.get(), 0, sizeof(uint32_t) * (size_t)chain_group_ * cap_));
+        HBHIP_CHECK(lc, hipMemset(plane_flags_.get(), 0, sizeof(uint32_t) * 3 * EEDI_MAX_BATCH));
         chain_epoch_ = 0;
     }
     *epoch = ++chain_epoch_;
@@ -2953,11 +2936,11 @@ int EediEngineBase::begin_mask(hbhip_ctx *lc, int f0, bool has, MaskChain *C)
     uint32_t epoch = 0;
     { const int erc = next_epoch(lc, &epoch); if (erc != HBHIP_OK) return erc; }
     *C = eedi_mask_chain_tiles(half_[0], layout_.tile_w, layout_.tile_h, layout_.tile_oy);
-    C->flags = chain_flags_;
-    C->pflags = plane_flags_ + 3 * f0;
+    C->flags = chain_flags_.get();
+    C->pflags = plane_flags_.get() + 3 * f0;
     C->epoch = epoch;
     C->group = C->ntiles + C->nupper;
-    C->has = has ? chain_has_ + (size_t)f0 * C->group : nullptr;
+    C->has = has ? chain_has_.get() + (size_t)f0 * C->group : nullptr;
     guard_.bind(*C);
     return HBHIP_OK;
 }
@@ -2975,12 +2958,6 @@ Eedi2Engine::Eedi2Engine(hbhip_ctx *ctx, const PicGeometry &geo, const Eedi2Para
     static_assert(EEDI_MAX_FIELDS == EEDI_MAX_BATCH, "a batch is one launch's fields");
 }
 
-Eedi2Engine::~Eedi2Engine()
-{
-    if (work_list_) (void)hipFree(work_list_);
-    if (work_count_) (void)hipFree(work_count_);
-}
-
 int Eedi2Engine::init()
 {
     if (geo_.bps != 1) return HBHIP_ERR_UNSUPPORTED;
@@ -2992,8 +2969,8 @@ int Eedi2Engine::init()
         // work list of the calc_directions fallback (every half-height pixel could qualify)
         size_t half_px = 0;
         for (int c = 0; c < 3; c++) half_px += (size_t)half_[0].stride[c] * half_[0].height[c];
-        HBHIP_CHECK(ctx_, hipMalloc((void **)&work_list_, sizeof(uint32_t) * half_px));
-        HBHIP_CHECK(ctx_, hipMalloc((void **)&work_count_, sizeof(int)));
+        if (const int ra = work_list_.alloc(ctx_, half_px)) return ra;
+        if (const int ra = work_count_.alloc(ctx_, 1)) return ra;
     }
     HBHIP_CHECK(ctx_, hipStreamSynchronize(ctx_->stream));
     return HBHIP_OK;
@@ -3174,7 +3151,7 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
     memset(&P, 0, sizeof(P));
     P.fstride = slot_bytes_;
     P.tffbits = tffbits;
-    P.pflags = plane_flags_ + 3 * f0;                             // every kernel behind FIELD_PLANE reads it: never null here
+    P.pflags = plane_flags_.get() + 3 * f0;                          // every kernel behind FIELD_PLANE reads it: never null here
     P.pepoch = epoch;
 
     // half-height passes
@@ -3234,11 +3211,11 @@ int Eedi2Engine::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, ui
                 Q.a[c] = P.a[c] + (size_t)f * slot_bytes_; Q.b[c] = P.b[c] + (size_t)f * slot_bytes_; Q.c[c] = P.c[c] + (size_t)f * slot_bytes_;
             }
             Q.pflags = P.pflags + 3 * f;                              // (the launch's field 0 is the batch's field f)
-            HBHIP_CHECK(lc, hipMemsetAsync(work_count_, 0, sizeof(int), st));
+            HBHIP_CHECK(lc, hipMemsetAsync(work_count_.get(), 0, sizeof(int), st));
             HBHIP_LAUNCH_ON(lc, st, "eedi2_calc_directions_mark", k_calc_dir_mark, dim3((srcp.stride[0] + 63) / 64, (srcp.height[0] + 3) / 4, 3), blk, 0,
-                         Q, work_list_, work_count_);
+                         Q, work_list_.get(), work_count_.get());
             HBHIP_LAUNCH_ON(lc, st, "eedi2_calc_directions_work", k_calc_dir_work, dim3((unsigned)((half_px + 255) / 256)), dim3(256), 0, Q,
-                         (const uint32_t *)work_list_, (const int *)work_count_, par_.maximum_search_distance, nt13, nt19);
+                         (const uint32_t *)work_list_.get(), (const int *)work_count_.get(), par_.maximum_search_distance, nt13, nt19);
         }
     }
     if (fused)

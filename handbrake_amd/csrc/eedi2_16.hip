@@ -2335,7 +2335,7 @@ int Eedi2Engine16::enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, 
 
     // half-height passes (decomb_template.c:398-404), all fields per launch from here on
     geom(P, srcp);
-    P.pflags = plane_flags_ + 3 * f0;
+    P.pflags = plane_flags_.get() + 3 * f0;
     P.pepoch = epoch;
     // filter_dir_map and expand_dir_map as one launch (q_dir_map_fe; eedi2.hip: Eedi2Engine::enqueue_passes): calc_directions
     // then writes dstp, and leaves the padding of its rows alone, so that the fused pass leaves the expanded map - and the

@@ -150,7 +150,7 @@ void EediEngineBase::enqueue_corner(int f0, int n, hbhip_ctx *lc, hipStream_t st
         {
             EediCornerArgs<PIX> A;
             A.src = (PIX *)(srcp.plane[c] + foff); A.tmp = (PIX *)(tmpp.plane[c] + foff);
-            for (int i = 0; i < 3; i++) { A.c[i] = deriv_[i]; A.t[i] = deriv_tmp_[i]; }
+            for (int i = 0; i < 3; i++) { A.c[i] = deriv_[i].get(); A.t[i] = deriv_tmp_[i].get(); }
             A.pitch = srcp.stride[c] / (int)sizeof(PIX); A.width = srcp.width[c]; A.height = srcp.height[c];
             const dim3 g1((A.width + 63) / 64, (A.height + 3) / 4, 1), g3(g1.x, g1.y, 3);
             HBHIP_LAUNCH_ON(lc, st, name[0], (eedi_blur1<PIX, false>), g1, blk, 0, A);

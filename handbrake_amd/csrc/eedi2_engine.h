@@ -67,12 +67,11 @@ struct MaskChain
 // reads the host word.
 struct MaskChainGuard
 {
-    uint32_t *err = nullptr;              // device
-    uint32_t *count_host = nullptr;       // hipHostMalloc (mapped)
+    DevBuf<uint32_t> err;
+    PinnedBuf<uint32_t> count_host{hipHostMallocMapped};
     uint32_t *count_dev = nullptr;        // its device address
     uint32_t  seen = 0;
     int  init(hbhip_ctx *ctx);
-    void destroy();
     void poll(const char *who);
     void bind(MaskChain &C) const;
 };
@@ -366,7 +365,7 @@ protected:
     uint32_t    tffbits_ = 0;
     const uint8_t *src_frame_[EEDI_MAX_BATCH][3];  // the queued fields' frames
     int         src_pitch_[3] = {0, 0, 0};
-    uint8_t    *slab_ = nullptr;
+    DevBuf<uint8_t> slab_;
     size_t      slot_bytes_ = 0;
     EediLayout  layout_ = {};
     EediFrame   half_[4];    // slot 0's SRCPF, MSKPF, TMPPF, DSTPF          (decomb.c:64-68)
@@ -374,18 +373,18 @@ protected:
     uint8_t    *cand_raw_ = nullptr;    // slot 0's interpolate_lattice candidates (cand_pitch_ words a row, per plane cand_plane_stride_)
     int         cand_pitch_ = 0, cand_plane_stride_ = 0;
     int         chain_ntiles_ = 0, chain_group_ = 0;   // mask chain: lower tiles / all tiles of one field
-    uint32_t   *chain_flags_ = nullptr; //             one completion flag per lower tile and field of a batch
-    uint32_t   *chain_has_ = nullptr;   //             one word per tile and field: the tile left a mask sample set (MaskChain::has)
+    DevBuf<uint32_t> chain_flags_;  //             one completion flag per lower tile and field of a batch
+    DevBuf<uint32_t> chain_has_;    //             one word per tile and field: the tile left a mask sample set (MaskChain::has)
     uint32_t    chain_epoch_ = 0;       //             the number of the last mask launch (never 0: 0 is "no launch" in the flag arrays)
     MaskChainGuard guard_;              //             what happens when a wait of the chain runs out
-    uint32_t   *plane_flags_ = nullptr; // [field of the batch][plane]: == the mask launch's number when the plane's new mask has a sample set
+    DevBuf<uint32_t> plane_flags_;  // [field of the batch][plane]: == the mask launch's number when the plane's new mask has a sample set
     static constexpr int MAX_SIDE = 3;
     int         nside_ = 0;
     hipStream_t ahead_ = nullptr;       // mask_ahead(): the next part's mask launch runs here
     hipStream_t side_[MAX_SIDE] = {};   // the later groups of a part's fields run their passes here, beside the first group's
     hipEvent_t  ev_fork_ = nullptr, ev_mask_ = nullptr, ev_join_[MAX_SIDE] = {};
-    int        *deriv_[3] = {nullptr, nullptr, nullptr};       // post-processing 2/3: cx2, cy2, cxy (decomb.c:398-403)
-    int        *deriv_tmp_[3] = {nullptr, nullptr, nullptr};   //                      tmpc, one per array
+    DevBuf<int> deriv_[3];          // post-processing 2/3: cx2, cy2, cxy (decomb.c:398-403)
+    DevBuf<int> deriv_tmp_[3];      //                      tmpc, one per array
 };
 
 // EEDI2 on 8-bit samples (eedi2.hip).
@@ -393,15 +392,14 @@ class Eedi2Engine : public EediEngineBase
 {
 public:
     Eedi2Engine(hbhip_ctx *ctx, const PicGeometry &geo, const Eedi2Params &p, int capacity);
-    ~Eedi2Engine() override;
     int  init() override;
 
 private:
     bool may_fork() const override;
     int enqueue_mask(int f0, int n, hbhip_ctx *lc, hipStream_t st, uint32_t *epoch) override;
     int enqueue_passes(int f0, int n, hbhip_ctx *lc, hipStream_t st, uint32_t epoch) override;
-    uint32_t   *work_list_ = nullptr;   // calc_directions fallback: compacted edge pixels
-    int        *work_count_ = nullptr;
+    DevBuf<uint32_t> work_list_;    // calc_directions fallback: compacted edge pixels
+    DevBuf<int> work_count_;
 };
 
 // EEDI2 on 10 / 12-bit samples (eedi2_16.hip): the same engine on uint16 samples.  EediFrame strides are in BYTES, the

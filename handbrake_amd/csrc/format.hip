@@ -677,18 +677,13 @@ class FormatScalerFilter : public BurstFilter
 {
 public:
     FormatScalerFilter(hbhip_ctx *c, const FsDirection &d) : BurstFilter(c), dir(d) {}
-    ~FormatScalerFilter() override
-    {
-        if (d_hq) (void)hipFree(d_hq);
-        if (d_vq) (void)hipFree(d_vq);
-    }
     // sws_filter's rows in the kernel's nominal frame, to the device; HBHIP_ERR_UNSUPPORTED: a row has a tap outside of it
-    int upload(int src, int dst, int one, int src_pos, int dst_pos, int pad, short *&dptr)
+    int upload(int src, int dst, int one, int src_pos, int dst_pos, int pad, DevBuf<short> &buf)
     {
         std::vector<short> q;
         if (!sws_nominal(src, dst, one, src_pos, dst_pos, pad, dir.frame, q)) return HBHIP_ERR_UNSUPPORTED;
-        HBHIP_CHECK(ctx, hipMalloc((void **)&dptr, sizeof(short) * q.size()));
-        HBHIP_CHECK(ctx, hipMemcpy(dptr, q.data(), sizeof(short) * q.size(), hipMemcpyHostToDevice));
+        if (const int rc = buf.alloc(ctx, q.size())) return rc;
+        HBHIP_CHECK(ctx, hipMemcpy(buf.get(), q.data(), sizeof(short) * q.size(), hipMemcpyHostToDevice));
         return HBHIP_OK;
     }
     int setup()
@@ -709,7 +704,7 @@ public:
             if ((bits & 7) != 0) return HBHIP_ERR_ARG;                       // planes and pitches of this library are 64-byte aligned
             a.w = in_geo.width; a.h = in_geo.height; a.sdepth = in_geo.depth; a.ddepth = out_geo.depth;
             a.scw = in_geo.pw[1]; a.sch = in_geo.ph[1]; a.dcw = out_geo.pw[1]; a.dch = out_geo.ph[1];
-            a.hq = d_hq; a.vq = d_vq;
+            a.hq = d_hq.get(); a.vq = d_vq.get();
             a.ly = (a.h + 4 * FS_LROWS - 1) / (4 * FS_LROWS);
             const int rows = 4 * dir.rows[hpass][vpass];                     // output rows a workgroup
             a.cy = (a.dch + rows - 1) / rows;
@@ -769,7 +764,7 @@ public:
     }
     const FsDirection &dir;
     bool hpass = false, vpass = false;
-    short *d_hq = nullptr, *d_vq = nullptr;
+    DevBuf<short> d_hq, d_vq;
 };
 
 // Behind the four scaler create functions.  Down: no dimension gains chroma samples, the depth does not grow, and one

@@ -6,6 +6,8 @@
 #include <new>
 
 // ---------------------------------------------------------------- ctx helpers
+std::atomic<size_t> hbhip_live_bytes[2];
+
 int hbhip_ctx::fail(hipError_t e, const char *what)
 {
     std::lock_guard<std::recursive_mutex> lk(state_lock);
@@ -188,11 +190,7 @@ void hbhip_ctx::prof_resolve()
 // ---------------------------------------------------------------- pool
 PicturePool::~PicturePool()
 {
-    for (DevPicture *p : all_)
-    {
-        if (p->base) (void)hipFree(p->base);
-        delete p;
-    }
+    for (Owned *o : all_) delete o;
 }
 
 void PicturePool::configure(hbhip_ctx *ctx, const PicGeometry &g, int pitch_align, int pad_rows)
@@ -232,8 +230,9 @@ DevPicture *PicturePool::acquire()
             return p;
         }
     }
-    DevPicture *p = new (std::nothrow) DevPicture();
-    if (!p) return nullptr;
+    Owned *o = new (std::nothrow) Owned();
+    if (!o) return nullptr;
+    DevPicture *p = &o->pic;
     size_t off[3], total = 0;
     for (int c = 0; c < 3; c++)
     {
@@ -246,17 +245,16 @@ DevPicture *PicturePool::acquire()
     }
     p->bps = geo_.bps;
     p->bytes = total;
-    if (hipMalloc((void **)&p->base, total) != hipSuccess)
+    if (o->mem.alloc(ctx_, total) != HBHIP_OK)
     {
-        (void)hipGetLastError();
-        delete p;
+        delete o;
         return nullptr;
     }
-    (void)hipMemsetAsync(p->base, 0, total, ctx_->stream);
+    (void)hipMemsetAsync(o->mem.get(), 0, total, ctx_->stream);
     hbhip_pic_mark_idle(ctx_, p);          // an upload (on the copy stream) must not overtake the clearing
-    for (int c = 0; c < 3; c++) p->plane[c] = p->base + off[c];
+    for (int c = 0; c < 3; c++) p->plane[c] = o->mem.get() + off[c];
     p->owner = this;
-    all_.push_back(p);
+    all_.push_back(o);
     return p;
 }
 
@@ -328,32 +326,38 @@ static hipError_t queue_d2h(const hbhip_host_frame *dst, const DevPicture *src, 
 static int hip_rc(hbhip_ctx *ctx, hipError_t e, const char *what) { return e == hipSuccess ? HBHIP_OK : ctx->fail(e, what); }
 
 // the one way out of a copy that failed part-way: what is queued on `stream` must not outlive the call (it reads or writes
-// the caller's planes), and the event goes back to the pool
-static int abandon(hbhip_ctx *ctx, hipStream_t stream, hipEvent_t ev, int rc)
+// the caller's planes); the borrowed event goes back to the pool with its scope
+static int abandon(hipStream_t stream, int rc)
 {
     (void)hipStreamSynchronize(stream);
-    ctx->sync_ev_put(ev);
     return rc;
+}
+
+int hbhip_wait_behind(hbhip_ctx *ctx, hipStream_t stream, const char *what)
+{
+    SyncEvent done(ctx);
+    if (!done) return ctx->fail(hipErrorOutOfMemory, what);
+    hipError_t e = hipEventRecord(done, stream);
+    if (e == hipSuccess) e = hipEventSynchronize(done);
+    return hip_rc(ctx, e, what);
 }
 
 // H2D on the upload stream, waited for; *moved: the bytes sent
 static int copy_h2d_wait(hbhip_ctx *ctx, DevPicture *dst, const hbhip_host_frame *src, size_t *moved)
 {
     if (!host_planes_ok(dst, src)) return HBHIP_ERR_ARG;
-    hipEvent_t done = ctx->sync_ev_get();
+    SyncEvent done(ctx);
     if (!done) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(upload)");
     hipStream_t up = ctx->up();
     // whatever still reads the picture's previous contents was queued ahead of its idle mark when it was recycled
     hipError_t e = hbhip_pic_wait_idle(up, dst);
     if (e == hipSuccess) e = queue_h2d(dst, src, true, up, moved);
     if (e == hipSuccess) e = hipEventRecord(done, up);
-    if (e != hipSuccess) return abandon(ctx, up, done, ctx->fail(e, "hipMemcpyAsync(upload)"));
+    if (e != hipSuccess) return abandon(up, ctx->fail(e, "hipMemcpyAsync(upload)"));
     // The caller may free or reuse its planes as soon as we return (filter_loop closes buf_in, work.c:2566-2569):
     // wait for THIS copy - not for the kernels other filters have queued.  Once it has completed, work launched
     // on any stream afterwards sees the data.
-    e = hipEventSynchronize(done);
-    ctx->sync_ev_put(done);
-    return hip_rc(ctx, e, "hipEventSynchronize(upload)");
+    return hip_rc(ctx, hipEventSynchronize(done), "hipEventSynchronize(upload)");
 }
 
 int hbhip_copy_h2d(hbhip_ctx *ctx, DevPicture *dst, const hbhip_host_frame *src)
@@ -365,7 +369,7 @@ int hbhip_copy_h2d(hbhip_ctx *ctx, DevPicture *dst, const hbhip_host_frame *src)
 int hbhip_copy_d2h(hbhip_ctx *ctx, const hbhip_host_frame *dst, const DevPicture *src)
 {
     if (!host_planes_ok(src, dst)) return HBHIP_ERR_ARG;
-    hipEvent_t ev = ctx->sync_ev_get();
+    SyncEvent ev(ctx);
     if (!ev) return ctx->fail(hipErrorOutOfMemory, "hipEventCreate(download)");
     hipStream_t down = ctx->down();
     size_t n = 0;
@@ -374,10 +378,8 @@ int hbhip_copy_d2h(hbhip_ctx *ctx, const hbhip_host_frame *dst, const DevPicture
     if (e == hipSuccess) e = hipStreamWaitEvent(down, ev, 0);
     if (e == hipSuccess) e = queue_d2h(dst, src, false, down, &n);
     if (e == hipSuccess) e = hipEventRecord(ev, down);
-    if (e != hipSuccess) return abandon(ctx, down, ev, ctx->fail(e, "download: queue the copy"));
-    e = hipEventSynchronize(ev);
-    ctx->sync_ev_put(ev);
-    return hip_rc(ctx, e, "hipEventSynchronize(download)");
+    if (e != hipSuccess) return abandon(down, ctx->fail(e, "download: queue the copy"));
+    return hip_rc(ctx, hipEventSynchronize(ev), "hipEventSynchronize(download)");
 }
 
 // Device-to-device copies of a picture's three planes as ONE kernel launch: hipMemcpy2DAsync makes a blit kernel per
@@ -496,6 +498,14 @@ static void surface_reap(hbhip_ctx *ctx, bool wait);     // device surfaces, bel
 
 int hbhip_abi_version(void) { return HBHIP_ABI_VERSION; }
 
+int hbhip_mem_live(size_t *device_bytes, size_t *pinned_bytes)
+{
+    if (!device_bytes || !pinned_bytes) return HBHIP_ERR_ARG;
+    *device_bytes = hbhip_live_bytes[0].load(std::memory_order_relaxed);
+    *pinned_bytes = hbhip_live_bytes[1].load(std::memory_order_relaxed);
+    return HBHIP_OK;
+}
+
 int hbhip_host_alloc(size_t bytes, void **out)
 {
     if (!out) return HBHIP_ERR_ARG;
@@ -612,36 +622,30 @@ void hbhip_ctx_destroy(hbhip_ctx *ctx)
     if (ctx->up_stream) { (void)hipStreamSynchronize(ctx->up_stream); (void)hipStreamDestroy(ctx->up_stream); }
     if (ctx->down_stream) { (void)hipStreamSynchronize(ctx->down_stream); (void)hipStreamDestroy(ctx->down_stream); }
     surface_reap(ctx, true);
-    for (hbhip_surface *s : ctx->surface_pool)
-    {
-        (void)hipFree(s->base);
-        delete s;
-    }
+    for (hbhip_surface *s : ctx->surface_pool) delete s;
     for (hipEvent_t e : ctx->sync_ev_pool) (void)hipEventDestroy(e);
     for (auto &p : ctx->prof_pending)
     {
         if (p.ev0) (void)hipEventDestroy(p.ev0);
         if (p.ev1) (void)hipEventDestroy(p.ev1);
     }
-    for (hbhip_frame *fr : ctx->frame_pool)
-    {
-        if (fr->pic.base) (void)hipFree(fr->pic.base);
-        delete fr;
-    }
-    for (int i = 0; i < 2; i++)
-        if (ctx->bi_stage[i]) (void)hipFree(ctx->bi_stage[i]);
+    for (hbhip_frame *fr : ctx->frame_pool) delete fr;
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (int i = 0; i < HBHIP_MAX_MARKS; i++)
         if (ctx->marks[i]) (void)hipEventDestroy(ctx->marks[i]);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;                                 // (bi_stage with it: every stream that used it has been waited out above)
 }
 
 int hbhip_ctx_sync(hbhip_ctx *ctx)
 {
     if (!ctx) return HBHIP_ERR_ARG;
+    // the mark of the pictures released since the last launch is recorded ahead of the wait, as hbhip_ctx_destroy does: behind
+    // a sync every pooled picture IS idle, and the next hbhip_frame_alloc takes it instead of growing the pool past a mark
+    // its own query has only just recorded
+    if (ctx->has_open_mark.load(std::memory_order_acquire)) ctx->close_mark();
     HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-    surface_reap(ctx, true);                    // (surface kernels still queued on the copy streams: waited for, their references dropped)
+    surface_reap(ctx, true);                   // (surface kernels still queued on the copy streams: waited for, their references dropped)
     return HBHIP_OK;
 }
 
@@ -666,14 +670,15 @@ int hbhip_ctx_copy_bandwidth(hbhip_ctx *ctx, size_t bytes, int iters, double *gb
 {
     if (!ctx || !gbps || bytes < (1u << 20) || iters < 1) return HBHIP_ERR_ARG;
     (void)hipSetDevice(ctx->device);
-    float4 *a = nullptr, *b = nullptr;
+    DevBuf<float4> da, db;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const size_t n = bytes / sizeof(float4);
     int rc = HBHIP_OK;
     double best_ms = 0.0;
-    if (hipMalloc((void **)&a, n * sizeof(float4)) != hipSuccess || hipMalloc((void **)&b, n * sizeof(float4)) != hipSuccess ||
+    if (da.alloc(ctx, n) != HBHIP_OK || db.alloc(ctx, n) != HBHIP_OK ||
         hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess)
         rc = ctx->fail(hipErrorOutOfMemory, "hbhip_ctx_copy_bandwidth: buffers");
+    float4 *const a = da.get(), *const b = db.get();
     if (rc == HBHIP_OK && hipMemsetAsync(a, 1, n * sizeof(float4), ctx->stream) != hipSuccess) rc = HBHIP_ERR_HIP;
     // the ceiling is whatever the best of a few shapes reaches: 1 / 4 / 8 float4 in flight per lane, plain or non-temporal
     // accesses, 256 or 1024 lanes per workgroup, 8 or 32 workgroups per CU - and the runtime's own device-to-device copy
@@ -703,8 +708,6 @@ int hbhip_ctx_copy_bandwidth(hbhip_ctx *ctx, size_t bytes, int iters, double *gb
             (void)hipEventElapsedTime(&ms, e0, e1);
             if (i > 0 && (best_ms == 0.0 || ms < best_ms)) best_ms = ms;
         }
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (rc == HBHIP_OK) *gbps = best_ms > 0.0 ? 2.0 * (double)(n * sizeof(float4)) / (best_ms * 1e-3) / 1e9 : 0.0;   // read + write
@@ -871,16 +874,16 @@ static int fill_frame(hbhip_frame *fr, const char *what, Queue queue, void **tok
 {
     hbhip_ctx *ctx = fr->ctx;
     hipStream_t up = ctx->up();
-    hipEvent_t done = ctx->sync_ev_get();
+    SyncEvent done(ctx);
     if (!done) return ctx->fail(hipErrorOutOfMemory, what);
     int rc = hip_rc(ctx, hbhip_pic_wait_idle(up, &fr->pic), what);
     if (rc == HBHIP_OK) rc = queue(up, done);
     std::shared_ptr<IdleMark> ready = rc == HBHIP_OK ? record_mark(up) : nullptr;
     if (rc == HBHIP_OK && !ready) rc = ctx->fail(hipErrorOutOfMemory, what);
-    if (rc != HBHIP_OK) return abandon(ctx, up, done, rc);
+    if (rc != HBHIP_OK) return abandon(up, rc);
     if (ready_out) *ready_out = ready;
     { std::lock_guard<std::mutex> lk(ctx->frame_lock); set_contents(fr, std::move(ready)); }
-    *token = done;
+    *token = done.keep();
     return HBHIP_OK;
 }
 
@@ -891,7 +894,7 @@ static int drain_frame(hbhip_frame *fr, const char *what, Queue queue, Then then
 {
     hbhip_ctx *ctx = fr->ctx;
     hipStream_t down = ctx->down();
-    hipEvent_t ev = ctx->sync_ev_get();
+    SyncEvent ev(ctx);
     if (!ev) return ctx->fail(hipErrorOutOfMemory, what);
     hipError_t e;
     { std::lock_guard<std::mutex> lk(ctx->frame_lock); e = order_after_contents(fr, down); }
@@ -899,8 +902,8 @@ static int drain_frame(hbhip_frame *fr, const char *what, Queue queue, Then then
     if (rc == HBHIP_OK) rc = queue(down);
     if (rc == HBHIP_OK) rc = hip_rc(ctx, hipEventRecord(ev, down), what);
     if (rc == HBHIP_OK) rc = then(down);
-    if (rc != HBHIP_OK) return abandon(ctx, down, ev, rc);
-    *token = ev;
+    if (rc != HBHIP_OK) return abandon(down, rc);
+    *token = ev.keep();
     return HBHIP_OK;
 }
 
@@ -972,15 +975,14 @@ int hbhip_frame_alloc(hbhip_ctx *ctx, int width, int height, int depth, int lcw,
     total = (total + 255) & ~(size_t)255;
     fr->pic.bps = g.bps;
     fr->pic.bytes = total;
-    if (hipMalloc((void **)&fr->pic.base, total) != hipSuccess)
+    if (const int rc = fr->mem.alloc(ctx, total))
     {
-        (void)hipGetLastError();
         delete fr;
-        return HBHIP_ERR_NOMEM;
+        return rc;
     }
-    (void)hipMemsetAsync(fr->pic.base, 0, total, ctx->stream);
+    (void)hipMemsetAsync(fr->mem.get(), 0, total, ctx->stream);
     hbhip_pic_mark_idle(ctx, &fr->pic);    // an upload (on the copy stream) must not overtake the clearing
-    for (int c = 0; c < 3; c++) fr->pic.plane[c] = fr->pic.base + off[c];
+    for (int c = 0; c < 3; c++) fr->pic.plane[c] = fr->mem.get() + off[c];
     fr->pic.frame = fr;
     *out = fr;
     return HBHIP_OK;
@@ -1180,22 +1182,10 @@ static int bi_check(const hbhip_frame *fr, const hbhip_host_biplanar *hb, BiLayo
 // that uses it out first: earlier pairs may still be running.
 static uint8_t *bi_stage(hbhip_ctx *ctx, int dir, size_t bytes, hipStream_t stream)
 {
-    if (ctx->bi_stage_bytes[dir] >= bytes) return ctx->bi_stage[dir];
-    if (ctx->bi_stage[dir])
-    {
-        (void)hipStreamSynchronize(stream);
-        (void)hipFree(ctx->bi_stage[dir]);
-        ctx->bi_stage[dir] = nullptr;
-        ctx->bi_stage_bytes[dir] = 0;
-    }
-    if (hipMalloc((void **)&ctx->bi_stage[dir], bytes) != hipSuccess)
-    {
-        (void)hipGetLastError();
-        ctx->bi_stage[dir] = nullptr;
-        return nullptr;
-    }
-    ctx->bi_stage_bytes[dir] = bytes;
-    return ctx->bi_stage[dir];
+    DevBuf<uint8_t> &st = ctx->bi_stage[dir];
+    if (st.count() < bytes && st.get()) (void)hipStreamSynchronize(stream);
+    (void)st.reserve(ctx, bytes);
+    return st.get();
 }
 
 // host picture <-> staging buffer: one 1-D copy when the host picture has the staging layout, else a 2-D copy per plane.
@@ -1312,7 +1302,7 @@ static void surface_unref(hbhip_surface *s)
     {
         std::lock_guard<std::mutex> lk(s->ctx->surface_lock);
         if (--s->refs > 0) return;
-        if (s->base) { s->ctx->surface_pool.push_back(s); return; }
+        if (s->mem.get()) { s->ctx->surface_pool.push_back(s); return; }
     }
     if (s->release) s->release(s->opaque);
     delete s;
@@ -1376,16 +1366,15 @@ int hbhip_surface_alloc(hbhip_ctx *ctx, int width, int height, int depth, int pi
     const int rows0 = hbhip_align_up(height, rows_align);
     for (int p = 0; p < 2; p++) s->pitch[p] = hbhip_align_up(l.row_bytes[p], pitch_align);
     const size_t bytes = (size_t)s->pitch[0] * rows0 + (size_t)s->pitch[1] * ((rows0 + 1) / 2);
-    if (hipMalloc((void **)&s->base, bytes) != hipSuccess)
+    if (const int rc = s->mem.alloc(ctx, bytes))
     {
-        (void)hipGetLastError();
         delete s;
-        return HBHIP_ERR_NOMEM;
+        return rc;
     }
-    s->plane[0] = s->base;
-    s->plane[1] = s->base + (size_t)s->pitch[0] * rows0;
+    s->plane[0] = s->mem.get();
+    s->plane[1] = s->plane[0] + (size_t)s->pitch[0] * rows0;
     // padding and padded rows are never written by an export: cleared once, and the first export waits for that
-    (void)hipMemsetAsync(s->base, 0, bytes, ctx->stream);
+    (void)hipMemsetAsync(s->plane[0], 0, bytes, ctx->stream);
     s->ready = stream_now(ctx);
     *out = s;
     return HBHIP_OK;
@@ -1730,7 +1719,7 @@ int hbhip_filter_submit_async(hbhip_filter *f, const hbhip_host_frame *in, const
         f->abandon_input(pic);
         return HBHIP_ERR_UNSUPPORTED;              // not a one-in / one-out filter: use push / pull
     }
-    hipEvent_t ev = ctx->sync_ev_get(), done = ctx->sync_ev_get();
+    SyncEvent ev(ctx), done(ctx);
     int rc = (ev && done) ? HBHIP_OK : HBHIP_ERR_NOMEM;
     if (rc == HBHIP_OK && !(host_planes_ok(pic, in) && host_planes_ok(o, out))) rc = HBHIP_ERR_ARG;
     auto fail = [&](int code) {
@@ -1740,8 +1729,6 @@ int hbhip_filter_submit_async(hbhip_filter *f, const hbhip_host_frame *in, const
         if (ctx->down_stream) (void)hipStreamSynchronize(ctx->down_stream);
         if (pic) f->abandon_input(pic);            // (already handed back once the kernels were queued)
         f->recycle_output(o);
-        ctx->sync_ev_put(ev);
-        ctx->sync_ev_put(done);
         return code;
     };
     if (rc != HBHIP_OK) return fail(rc);
@@ -1763,8 +1750,7 @@ int hbhip_filter_submit_async(hbhip_filter *f, const hbhip_host_frame *in, const
     ASYNC_CHECK(queue_d2h(out, o, false, ctx->down(), &moved));
     ASYNC_CHECK(hipEventRecord(done, ctx->down()));
 #undef ASYNC_CHECK
-    ctx->sync_ev_put(ev);
-    f->async_q.push_back({o, done, tag});
+    f->async_q.push_back({o, done.keep(), tag});
     return HBHIP_OK;
 }
 

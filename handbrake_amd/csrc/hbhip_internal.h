@@ -33,6 +33,48 @@ struct hbhip_prof_stat
     double      total_ms = 0.0;
 };
 
+// ---- who owns device and pinned memory ----
+// Every hipMalloc / hipHostMalloc of the library is held by one of these two move-only holders and freed by its destructor
+// (hipFree synchronises implicitly, as it always has).  A destructor that must run something AHEAD of the frees - wait for
+// a stream, set the device, give pictures back - keeps that as its body: members are destroyed after the body has run.
+// The two byte counts are what hbhip_mem_live() reports: "what a filter took, it gave back" as a number a test can read.
+extern std::atomic<size_t> hbhip_live_bytes[2];     // [0] device, [1] pinned
+struct hbhip_ctx;
+
+template <class T, bool PINNED>
+class HbBuf
+{
+public:
+    HbBuf() = default;
+    explicit HbBuf(unsigned flags) : flags_(flags) {}     // hipHostMalloc's flags (pinned memory only)
+    HbBuf(HbBuf &&o) noexcept : p_(o.p_), n_(o.n_), flags_(o.flags_) { o.p_ = nullptr; o.n_ = 0; }
+    HbBuf &operator=(HbBuf &&o) noexcept
+    {
+        if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; flags_ = o.flags_; o.p_ = nullptr; o.n_ = 0; }
+        return *this;
+    }
+    ~HbBuf() { reset(); }
+    T     *get() const { return p_; }
+    size_t count() const { return n_; }
+    void reset()
+    {
+        if (!p_) return;
+        (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
+        hbhip_live_bytes[PINNED].fetch_sub(n_ * sizeof(T), std::memory_order_relaxed);
+        p_ = nullptr; n_ = 0;
+    }
+    // `count` elements, whatever was held before freed first; on failure the holder is empty and the code is ctx->fail()'s
+    int alloc(hbhip_ctx *ctx, size_t count);
+    // at least `count` elements; the contents are NOT carried over when it has to grow
+    int reserve(hbhip_ctx *ctx, size_t count) { return count <= n_ ? HBHIP_OK : alloc(ctx, count); }
+private:
+    T       *p_ = nullptr;
+    size_t   n_ = 0;
+    unsigned flags_ = hipHostMallocDefault;
+};
+template <class T> using DevBuf = HbBuf<T, false>;
+template <class T> using PinnedBuf = HbBuf<T, true>;
+
 // A point on a stream behind which some pictures' last users have all run: the pictures released between two launches
 // on a stream share ONE event, recorded right before the stream's next launch (or when somebody needs it first).  An
 // event per released picture is what this replaces: every record is a barrier packet the command processor works off
@@ -90,8 +132,7 @@ struct hbhip_ctx
     // order then keeps a frame's pair ahead of the next one's (hbhip_frame_upload_biplanar_async, hbhip_core.hip).  A lock
     // a direction: the two adapters of a run work on different threads, streams and buffers and share nothing here.
     std::mutex bi_lock[2];
-    uint8_t   *bi_stage[2] = {nullptr, nullptr};
-    size_t     bi_stage_bytes[2] = {0, 0};
+    DevBuf<uint8_t> bi_stage[2];
     // device surfaces (hbhip_surface_*): the pool of library-owned ones, and the repack kernels queued on this context's
     // copy streams that have not been seen to finish yet - each holds a reference on its surface (surface_reap drops it).
     // One lock for both and for every surface's reference count and marks, whichever context the surface belongs to:
@@ -118,6 +159,35 @@ struct hbhip_ctx
         hipError_t _e = (expr);                                                 \
         if (_e != hipSuccess) return (ctx)->fail(_e, #expr);                    \
     } while (0)
+
+template <class T, bool PINNED>
+int HbBuf<T, PINNED>::alloc(hbhip_ctx *ctx, size_t count)
+{
+    reset();
+    void *p = nullptr;
+    const hipError_t e = PINNED ? hipHostMalloc(&p, count * sizeof(T), flags_) : hipMalloc(&p, count * sizeof(T));
+    if (e != hipSuccess) return ctx->fail(e, PINNED ? "hipHostMalloc" : "hipMalloc");
+    if (!p) return HBHIP_OK;                        // (count == 0)
+    p_ = (T *)p; n_ = count;
+    hbhip_live_bytes[PINNED].fetch_add(count * sizeof(T), std::memory_order_relaxed);
+    return HBHIP_OK;
+}
+
+// A pooled sync event (hipEventDisableTiming) borrowed for a scope: it goes back to the pool on every way out.
+struct SyncEvent
+{
+    hbhip_ctx *ctx;
+    hipEvent_t ev;
+    explicit SyncEvent(hbhip_ctx *c) : ctx(c), ev(c->sync_ev_get()) {}
+    ~SyncEvent() { ctx->sync_ev_put(ev); }
+    SyncEvent(const SyncEvent &) = delete;
+    SyncEvent &operator=(const SyncEvent &) = delete;
+    operator hipEvent_t() const { return ev; }
+    hipEvent_t keep() { hipEvent_t e = ev; ev = nullptr; return e; }      // the caller's from here on (a token it hands out)
+};
+// Wait for what is queued on `stream` right now - a read-back of the caller's - and not for what others queue behind it
+// (hipStreamSynchronize would: the filters of a job share the stream).  `what` names the wait in the error text.
+int hbhip_wait_behind(hbhip_ctx *ctx, hipStream_t stream, const char *what);
 
 // Development builds only (make dev: -DHBHIP_DEV; `make product` never defines it):
 //  * hbhip_dev_int("NAME", default): a tuning knob read from the environment - in a product build the default, a constant;
@@ -191,10 +261,10 @@ static inline unsigned hbhip_grid_x(unsigned gx) { return HBHIP_GRID_ROTATE == 2
 
 static inline int hbhip_align_up(int v, int a) { return (v + a - 1) / a * a; }
 
-// One planar picture in HBM (a single allocation, planes 256-byte aligned).
+// One planar picture in HBM (a single allocation, planes 256-byte aligned).  A view: copied freely, it owns nothing - the
+// memory is held beside it by whoever made it (PicturePool::Owned, hbhip_frame::mem).
 struct DevPicture
 {
-    uint8_t *base = nullptr;
     uint8_t *plane[3] = {nullptr, nullptr, nullptr};
     int      pitch[3] = {0, 0, 0};
     int      width[3] = {0, 0, 0};   // in pixels
@@ -217,6 +287,7 @@ struct hbhip_frame
 {
     hbhip_ctx  *ctx = nullptr;
     DevPicture  pic;
+    DevBuf<uint8_t> mem;                  // what pic's planes point into
     int         width = 0, height = 0, depth = 8, lcw = 1, lch = 1;
     int         refs = 1;
     // Ordering state.  The rule, and the only code that touches these four, is in hbhip_core.hip (order_after_contents
@@ -239,7 +310,7 @@ void hbhip_bi_layout(int width, int height, int depth, BiLayout *l);
 // the repack kernel between a staging buffer of that layout and the planar 4:2:0 frame `fr` (depth 8 or 10), on `stream`
 int hbhip_bi_repack_launch(hbhip_ctx *ctx, hipStream_t stream, bool merge, uint8_t *stage, const hbhip_frame *fr);
 
-// An NV12 / P010LE picture in device memory with a layout of its maker's choosing: the library's own (base != nullptr: from
+// An NV12 / P010LE picture in device memory with a layout of its maker's choosing: the library's own (mem holds it: from
 // the owner's surface_pool, back to it with the last reference) or a caller's (release(opaque) with the last reference).
 struct hbhip_surface
 {
@@ -247,7 +318,7 @@ struct hbhip_surface
     uint8_t   *plane[2] = {nullptr, nullptr};
     int        pitch[2] = {0, 0};
     int        width = 0, height = 0, depth = 8;
-    uint8_t   *base = nullptr;
+    DevBuf<uint8_t> mem;
     int        pitch_align = 0, rows_align = 0;      // of a pooled one: what hbhip_surface_alloc matches on
     void     (*release)(void *) = nullptr;
     void      *opaque = nullptr;
@@ -304,7 +375,8 @@ private:
     int pitch_align_ = 256;
     int pad_rows_ = 0;
     bool frames_ = false;
-    std::vector<DevPicture *> all_;
+    struct Owned { DevPicture pic; DevBuf<uint8_t> mem; };
+    std::vector<Owned *> all_;
     std::vector<DevPicture *> free_;
     size_t max_pictures_ = 96;            // growth bound of the cross-stream case (acquire): three batches of 32 - a chain split over
                                           // two streams is there after its warm-up; every new picture is a hipMalloc and a memset

@@ -516,29 +516,13 @@ class Hqdn3dFilter : public BurstFilter
 {
 public:
     Hqdn3dFilter(hbhip_ctx *c, const hbhip_hqdn3d_params &p) : BurstFilter(c), par(p) {}
-    ~Hqdn3dFilter() override
-    {
-        if (d_coef) (void)hipFree(d_coef);
-        for (int c = 0; c < 3; c++) if (ant[c]) (void)hipFree(ant[c]);
-        for (int c = 0; c < 3; c++) if (hbuf[c]) (void)hipFree(hbuf[c]);
-        for (int c = 0; c < 3; c++) if (ant2[c]) (void)hipFree(ant2[c]);
-        for (int c = 0; c < 3; c++) if (vstate[c]) (void)hipFree(vstate[c]);
-        for (int c = 0; c < 3; c++) if (hbuf_n[c]) (void)hipFree(hbuf_n[c]);
-        for (int c = 0; c < 3; c++) if (vsp_n[c]) (void)hipFree(vsp_n[c]);
-    }
     int setup()
     {
-        HBHIP_CHECK(ctx, hipMalloc((void **)&d_coef, sizeof(int16_t) * 6 * LUT_N));
-        HBHIP_CHECK(ctx, hipMemcpyAsync(d_coef, par.coef, sizeof(int16_t) * 6 * LUT_N, hipMemcpyHostToDevice, ctx->stream));
+        if (const int rc = d_coef.alloc(ctx, 6 * LUT_N)) return rc;
+        HBHIP_CHECK(ctx, hipMemcpyAsync(d_coef.get(), par.coef, sizeof(int16_t) * 6 * LUT_N, hipMemcpyHostToDevice, ctx->stream));
         for (int c = 0; c < 3; c++)
-            HBHIP_CHECK(ctx, hipMalloc((void **)&ant[c], sizeof(uint16_t) * (size_t)in_geo.pw[c] * in_geo.ph[c]));
-        for (int c = 0; c < 3; c++)
-        {
-            const size_t n = sizeof(uint16_t) * (size_t)in_geo.pw[c] * in_geo.ph[c];
-            HBHIP_CHECK(ctx, hipMalloc((void **)&hbuf[c], n));
-            HBHIP_CHECK(ctx, hipMalloc((void **)&ant2[c], n));
-            HBHIP_CHECK(ctx, hipMalloc((void **)&vstate[c], n));
-        }
+            for (DevBuf<uint16_t> *b : { &ant[c], &hbuf[c], &ant2[c], &vstate[c] })
+                if (const int rc = b->alloc(ctx, (size_t)in_geo.pw[c] * in_geo.ph[c])) return rc;
         if (const char *e = getenv("HBHIP_HQDN3D_WARMUP")) warm = std::max(0, atoi(e));     // test hook: 0 forces repairs
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         return HBHIP_OK;
@@ -555,8 +539,8 @@ public:
             P.src = in->plane[c]; P.dst = out->plane[c];
             P.spitch = in->pitch[c]; P.dpitch = out->pitch[c];
             P.w = in->width[c]; P.h = in->height[c];
-            P.hbuf = hbuf[c]; P.ant = ant[c]; P.ant_out = ant2[c]; P.vstate = vstate[c];
-            P.spatial = d_coef + (size_t)(2 * c) * LUT_N; P.temporal = P.spatial + LUT_N;
+            P.hbuf = hbuf[c].get(); P.ant = ant[c].get(); P.ant_out = ant2[c].get(); P.vstate = vstate[c].get();
+            P.spatial = d_coef.get() + (size_t)(2 * c) * LUT_N; P.temporal = P.spatial + LUT_N;
             P.seeded = seeded[c];
             P.spatial_on = par.coef[2 * c][0] != 0;                  // spatial strength != 0 (denoise.c:191)
             (P.spatial_on ? any_spatial : any_temporal) = true;
@@ -596,11 +580,11 @@ public:
     {
         return hbhip_for_each_run(ctx, ins, outs, n, HQ_BATCH, [&](int at, int k) {
             if (k < 2) return one_frame(ins[at], outs[at]);
-            for (int c = 0; c < 3 && !hbuf_n[c]; c++)
+            for (int c = 0; c < 3; c++)
             {
-                const size_t bytes = sizeof(uint16_t) * (size_t)in_geo.pw[c] * in_geo.ph[c] * HQ_BATCH;
-                HBHIP_CHECK(ctx, hipMalloc((void **)&hbuf_n[c], bytes));
-                HBHIP_CHECK(ctx, hipMalloc((void **)&vsp_n[c], bytes));
+                const size_t count = (size_t)in_geo.pw[c] * in_geo.ph[c] * HQ_BATCH;
+                if (const int rc = hbuf_n[c].reserve(ctx, count)) return rc;
+                if (const int rc = vsp_n[c].reserve(ctx, count)) return rc;
             }
             HqBatch B;
             memset(&B, 0, sizeof(B));
@@ -609,9 +593,9 @@ public:
             int max_w = 0, max_h = 0;
             for (int c = 0; c < 3; c++)
             {
-                B.hbuf[c] = hbuf_n[c]; B.vsp[c] = vsp_n[c]; B.ant[c] = ant[c];
+                B.hbuf[c] = hbuf_n[c].get(); B.vsp[c] = vsp_n[c].get(); B.ant[c] = ant[c].get();
                 B.stride[c] = (size_t)in_geo.pw[c] * in_geo.ph[c];
-                B.spatial[c] = d_coef + (size_t)(2 * c) * LUT_N; B.temporal[c] = B.spatial[c] + LUT_N;
+                B.spatial[c] = d_coef.get() + (size_t)(2 * c) * LUT_N; B.temporal[c] = B.spatial[c] + LUT_N;
                 B.spitch[c] = ins[at]->pitch[c]; B.dpitch[c] = outs[at]->pitch[c];
                 B.w[c] = ins[at]->width[c]; B.h[c] = ins[at]->height[c];
                 B.seeded[c] = seeded[c];
@@ -645,13 +629,13 @@ public:
         });
     }
     hbhip_hqdn3d_params par;
-    uint16_t *hbuf_n[3] = {nullptr, nullptr, nullptr};   // batches: the h-filtered rows of HQ_BATCH frames per plane
-    uint16_t *vsp_n[3] = {nullptr, nullptr, nullptr};    //          their vertical spatial results
-    int16_t *d_coef = nullptr;
-    uint16_t *ant[3] = {nullptr, nullptr, nullptr};
-    uint16_t *hbuf[3] = {nullptr, nullptr, nullptr};   // h-filtered rows, one buffer per plane
-    uint16_t *ant2[3] = {nullptr, nullptr, nullptr};   // the other half of the temporal-state double buffer
-    uint16_t *vstate[3] = {nullptr, nullptr, nullptr}; // vertical spatial state per sample
+    DevBuf<uint16_t> hbuf_n[3];   // batches: the h-filtered rows of HQ_BATCH frames per plane
+    DevBuf<uint16_t> vsp_n[3];    //          their vertical spatial results
+    DevBuf<int16_t> d_coef;
+    DevBuf<uint16_t> ant[3];
+    DevBuf<uint16_t> hbuf[3];     // h-filtered rows, one buffer per plane
+    DevBuf<uint16_t> ant2[3];     // the other half of the temporal-state double buffer
+    DevBuf<uint16_t> vstate[3];   // vertical spatial state per sample
     int warm = 64;                                     // warm-up samples of a speculative segment
     int seeded[3] = {0, 0, 0};
 };

@@ -70,18 +70,10 @@ struct hbhip_motion_metric
 {
     hbhip_ctx *ctx = nullptr;
     int width = 0, height = 0, depth = 8, bps = 1;
-    unsigned *d_lut = nullptr;
-    unsigned long long *d_total = nullptr;
-    uint8_t *d_a = nullptr, *d_b = nullptr;      // staging of the host entry point
+    DevBuf<unsigned> d_lut;
+    DevBuf<unsigned long long> d_total;
+    DevBuf<uint8_t> d_a, d_b;                    // staging of the host entry point
     int pitch = 0;
-
-    ~hbhip_motion_metric()
-    {
-        if (d_lut) (void)hipFree(d_lut);
-        if (d_total) (void)hipFree(d_total);
-        if (d_a) (void)hipFree(d_a);
-        if (d_b) (void)hipFree(d_b);
-    }
 };
 
 extern "C" int hbhip_motion_metric_create(hbhip_ctx *ctx, int width, int height, int depth,
@@ -95,9 +87,8 @@ extern "C" int hbhip_motion_metric_create(hbhip_ctx *ctx, int width, int height,
     hbhip_motion_metric *m = new (std::nothrow) hbhip_motion_metric;
     if (!m) return HBHIP_ERR_NOMEM;
     m->ctx = ctx; m->width = width; m->height = height; m->depth = depth; m->bps = depth > 8 ? 2 : 1;
-    if (hipMalloc((void **)&m->d_lut, sizeof(unsigned) * entries) != hipSuccess ||
-        hipMalloc((void **)&m->d_total, sizeof(unsigned long long)) != hipSuccess ||
-        hipMemcpy(m->d_lut, gamma_lut, sizeof(unsigned) * entries, hipMemcpyHostToDevice) != hipSuccess)
+    if (m->d_lut.alloc(ctx, entries) != HBHIP_OK || m->d_total.alloc(ctx, 1) != HBHIP_OK ||
+        hipMemcpy(m->d_lut.get(), gamma_lut, sizeof(unsigned) * entries, hipMemcpyHostToDevice) != hipSuccess)
     {
         delete m;
         return HBHIP_ERR_NOMEM;
@@ -126,15 +117,15 @@ extern "C" int hbhip_motion_metric_run_dev(hbhip_motion_metric *m, const void *l
     unsigned long long sum = 0;
     if (bw > 0 && bh > 0)
     {
-        HBHIP_CHECK(ctx, hipMemsetAsync(m->d_total, 0, sizeof(unsigned long long), ctx->stream));
+        HBHIP_CHECK(ctx, hipMemsetAsync(m->d_total.get(), 0, sizeof(unsigned long long), ctx->stream));
         if (m->bps == 1)
             HBHIP_LAUNCH(ctx, "motion_metric", motion_metric_kernel<uint8_t>, dim3(bw, bh), dim3(256), 0,
-                         (const uint8_t *)luma_a, stride_a, (const uint8_t *)luma_b, stride_b, (const unsigned *)m->d_lut, fast, w, m->d_total);
+                         (const uint8_t *)luma_a, stride_a, (const uint8_t *)luma_b, stride_b, (const unsigned *)m->d_lut.get(), fast, w, m->d_total.get());
         else
             HBHIP_LAUNCH(ctx, "motion_metric", motion_metric_kernel<uint16_t>, dim3(bw, bh), dim3(256), 0,
-                         (const uint8_t *)luma_a, stride_a, (const uint8_t *)luma_b, stride_b, (const unsigned *)m->d_lut, fast, w, m->d_total);
+                         (const uint8_t *)luma_a, stride_a, (const uint8_t *)luma_b, stride_b, (const unsigned *)m->d_lut.get(), fast, w, m->d_total.get());
         HBHIP_CHECK(ctx, hipGetLastError());
-        HBHIP_CHECK(ctx, hipMemcpyAsync(&sum, m->d_total, sizeof(sum), hipMemcpyDeviceToHost, ctx->stream));
+        HBHIP_CHECK(ctx, hipMemcpyAsync(&sum, m->d_total.get(), sizeof(sum), hipMemcpyDeviceToHost, ctx->stream));
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
     }
     *out = (float)sum / (w * h);                                                  // :190
@@ -147,15 +138,12 @@ extern "C" int hbhip_motion_metric_run(hbhip_motion_metric *m, const uint8_t *lu
     if (!m || !luma_a || !luma_b || !out) return HBHIP_ERR_ARG;
     hbhip_ctx *ctx = m->ctx;
     (void)hipSetDevice(ctx->device);
-    if (!m->d_a)
-    {
-        m->pitch = hbhip_align_up(m->width * m->bps, 256);
-        HBHIP_CHECK(ctx, hipMalloc((void **)&m->d_a, (size_t)m->pitch * m->height));
-        HBHIP_CHECK(ctx, hipMalloc((void **)&m->d_b, (size_t)m->pitch * m->height));
-    }
-    HBHIP_CHECK(ctx, hipMemcpy2DAsync(m->d_a, m->pitch, luma_a, stride_a, (size_t)m->width * m->bps, m->height,
+    m->pitch = hbhip_align_up(m->width * m->bps, 256);
+    if (const int rc = m->d_a.reserve(ctx, (size_t)m->pitch * m->height)) return rc;
+    if (const int rc = m->d_b.reserve(ctx, (size_t)m->pitch * m->height)) return rc;
+    HBHIP_CHECK(ctx, hipMemcpy2DAsync(m->d_a.get(), m->pitch, luma_a, stride_a, (size_t)m->width * m->bps, m->height,
                                       hipMemcpyHostToDevice, ctx->stream));
-    HBHIP_CHECK(ctx, hipMemcpy2DAsync(m->d_b, m->pitch, luma_b, stride_b, (size_t)m->width * m->bps, m->height,
+    HBHIP_CHECK(ctx, hipMemcpy2DAsync(m->d_b.get(), m->pitch, luma_b, stride_b, (size_t)m->width * m->bps, m->height,
                                       hipMemcpyHostToDevice, ctx->stream));
-    return hbhip_motion_metric_run_dev(m, m->d_a, m->pitch, m->d_b, m->pitch, out);
+    return hbhip_motion_metric_run_dev(m, m->d_a.get(), m->pitch, m->d_b.get(), m->pitch, out);
 }

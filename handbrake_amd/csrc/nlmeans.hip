@@ -1350,9 +1350,6 @@ public:
     NlmFilter(hbhip_ctx *c, const hbhip_nlmeans_params &p) : hbhip_filter(c), par(p) {}
     ~NlmFilter() override
     {
-        if (d_exp) (void)hipFree(d_exp);
-        if (d_jobs) (void)hipFree(d_jobs);
-        if (h_jobs) (void)hipHostFree(h_jobs);
         for (int i = 0; i < NTABLES; i++)
             if (table_ev[i]) (void)hipEventDestroy(table_ev[i]);
     }
@@ -1419,8 +1416,8 @@ public:
                 if (!mask_pic) return HBHIP_ERR_NOMEM;
             }
         }
-        HBHIP_CHECK(ctx, hipMalloc((void **)&d_exp, sizeof(float) * 3 * 128));
-        HBHIP_CHECK(ctx, hipMemcpyAsync(d_exp, par.exptable, sizeof(float) * 3 * 128,
+        if (const int rc = d_exp.alloc(ctx, 3 * 128)) return rc;
+        HBHIP_CHECK(ctx, hipMemcpyAsync(d_exp.get(), par.exptable, sizeof(float) * 3 * 128,
                                         hipMemcpyHostToDevice, ctx->stream));
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         return HBHIP_OK;
@@ -1471,15 +1468,13 @@ private:
     int ensure_jobs(int n)
     {
         if (n <= jobs_cap) return HBHIP_OK;
-        if (d_jobs) (void)hipFree(d_jobs);
-        if (h_jobs) (void)hipHostFree(h_jobs);
-        d_jobs = nullptr; h_jobs = nullptr; jobs_cap = 0;
+        jobs_cap = 0;
         HBHIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
         // a ring of job tables; a slot is rewritten only after the upload that
         // last read it has completed (event per slot)
-        HBHIP_CHECK(ctx, hipMalloc((void **)&d_jobs, sizeof(NlmJob) * n * NTABLES));
-        HBHIP_CHECK(ctx, hipHostMalloc((void **)&h_jobs, sizeof(NlmJob) * n * NTABLES, hipHostMallocDefault));
-        HBHIP_CHECK(ctx, hipHostGetDevicePointer((void **)&h_jobs_dev, h_jobs, 0));
+        if (const int rc = d_jobs.alloc(ctx, (size_t)n * NTABLES)) return rc;
+        if (const int rc = h_jobs.alloc(ctx, (size_t)n * NTABLES)) return rc;
+        HBHIP_CHECK(ctx, hipHostGetDevicePointer((void **)&h_jobs_dev, h_jobs.get(), 0));
         for (int i = 0; i < NTABLES; i++)
         {
             if (!table_ev[i]) HBHIP_CHECK(ctx, hipEventCreateWithFlags(&table_ev[i], hipEventDisableTiming));
@@ -1605,8 +1600,8 @@ private:
             if (!any) continue;
             table = (table + 1) % NTABLES;
             if (table_used[table]) HBHIP_CHECK(ctx, hipEventSynchronize(table_ev[table]));
-            NlmJob *hj = h_jobs + (size_t)table * jobs_cap;
-            NlmJob *dj = d_jobs + (size_t)table * jobs_cap;
+            NlmJob *hj = h_jobs.get() + (size_t)table * jobs_cap;
+            NlmJob *dj = d_jobs.get() + (size_t)table * jobs_cap;
             int nj = 0, tiles = 0, max_rh = 0;
             bool all_rh1 = true, all_org1 = true;
             // the tile counts of a frame's planes (NlmTiles), taken from the first frame's jobs and held against the rest
@@ -1635,7 +1630,7 @@ private:
                     jb.src_pre = latched_raw ? ins[t].plane[c] : ins[t].pre[c];
                     jb.src_pre_pitch = latched_raw ? ins[t].pitch[c] : ins[t].ppitch[c];
                     jb.dst = outs[t].plane[c];
-                    jb.exptable = d_exp + 128 * c;
+                    jb.exptable = d_exp.get() + 128 * c;
                     jb.origin_tune = par.origin_tune[c];
                     jb.wft = par.weight_fact_table[c];
                     jb.diff_max = par.diff_max[c];
@@ -1853,8 +1848,10 @@ private:
     long frames_seen = 0;
     std::deque<DevPicture *> in, out;
     int max_frames = 1;
-    float *d_exp = nullptr;
-    NlmJob *d_jobs = nullptr, *h_jobs = nullptr, *h_jobs_dev = nullptr;   // h_jobs_dev: the device's address of h_jobs
+    DevBuf<float> d_exp;
+    DevBuf<NlmJob> d_jobs;
+    PinnedBuf<NlmJob> h_jobs;
+    NlmJob *h_jobs_dev = nullptr;                     // the device's address of h_jobs
     int jobs_cap = 0, table = 0;
     static constexpr int NTABLES = 8;
     hipEvent_t table_ev[NTABLES] = {};

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void scan_comb_kernel(CombArgs a, ScanRecord *
 
 struct Slot
 {
-    uint8_t     *d_base = nullptr;               // record, row statistics, column statistics: one allocation
+    DevBuf<uint8_t> d_base;                      // record, row statistics, column statistics: one allocation
     ScanRecord  *d_rec = nullptr, *h_rec = nullptr;
     int         *d_rows = nullptr, *d_cols = nullptr;
     hipEvent_t   done = nullptr;
@@ -272,7 +272,7 @@ struct hbhip_scan
 {
     hbhip_ctx *ctx = nullptr;
     int width = 0, height = 0;
-    ScanRecord *h_recs = nullptr;                // pinned, one per slot
+    PinnedBuf<ScanRecord> h_recs;                // one per slot
     std::vector<Slot *> slots, idle;
     std::deque<Slot *> inflight;
 
@@ -281,11 +281,9 @@ struct hbhip_scan
         for (Slot *s : slots)
         {
             if (s->frame) hbhip_frame_release(s->frame);
-            if (s->d_base) (void)hipFree(s->d_base);
             if (s->done) (void)hipEventDestroy(s->done);
             delete s;
         }
-        if (h_recs) (void)hipHostFree(h_recs);
     }
 
     Slot *take_slot()
@@ -296,18 +294,17 @@ struct hbhip_scan
         if (!s) return nullptr;
         const size_t rows_at = 64, cols_at = rows_at + sizeof(int) * 3 * 2 * (height / 4);
         const size_t bytes = cols_at + sizeof(int) * 3 * 2 * (width / 4);
-        if (hipMalloc((void **)&s->d_base, bytes) != hipSuccess ||
+        if (s->d_base.alloc(ctx, bytes) != HBHIP_OK ||
             hipEventCreateWithFlags(&s->done, hipEventDisableTiming) != hipSuccess)
         {
             (void)hipGetLastError();
-            if (s->d_base) (void)hipFree(s->d_base);
             delete s;
             return nullptr;
         }
-        s->d_rec = reinterpret_cast<ScanRecord *>(s->d_base);
-        s->d_rows = reinterpret_cast<int *>(s->d_base + rows_at);
-        s->d_cols = reinterpret_cast<int *>(s->d_base + cols_at);
-        s->h_rec = h_recs + slots.size();
+        s->d_rec = reinterpret_cast<ScanRecord *>(s->d_base.get());
+        s->d_rows = reinterpret_cast<int *>(s->d_base.get() + rows_at);
+        s->d_cols = reinterpret_cast<int *>(s->d_base.get() + cols_at);
+        s->h_rec = h_recs.get() + slots.size();
         slots.push_back(s);
         return s;
     }
@@ -331,12 +328,10 @@ extern "C" int hbhip_scan_create(hbhip_ctx *ctx, int width, int height, hbhip_sc
     hbhip_scan *s = new (std::nothrow) hbhip_scan;
     if (!s) return HBHIP_ERR_NOMEM;
     s->ctx = ctx; s->width = width; s->height = height;
-    if (hipHostMalloc((void **)&s->h_recs, sizeof(ScanRecord) * HBHIP_SCAN_INFLIGHT_MAX, hipHostMallocDefault) != hipSuccess)
+    if (const int ra = s->h_recs.alloc(ctx, HBHIP_SCAN_INFLIGHT_MAX))
     {
-        (void)hipGetLastError();
-        s->h_recs = nullptr;
         delete s;
-        return HBHIP_ERR_NOMEM;
+        return ra;
     }
     *out = s;
     return HBHIP_OK;

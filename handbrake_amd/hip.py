@@ -14,7 +14,7 @@ HBHIP_OK, HBHIP_AGAIN = 0, 1
 
 #: every entry point include/hbhip.h declares (checked by tests/test_abi.py)
 ABI_SYMBOLS = [
-    "hbhip_host_alloc", "hbhip_host_free",
+    "hbhip_host_alloc", "hbhip_host_free", "hbhip_mem_live",
     "hbhip_abi_version", "hbhip_device_count", "hbhip_strerror", "hbhip_ctx_create",
     "hbhip_ctx_create_on_stream", "hbhip_ctx_destroy", "hbhip_ctx_sync", "hbhip_ctx_last_error",
     "hbhip_debug_mask_chain", "hbhip_cropscale_sws_create", "hbhip_ctx_copy_bandwidth", "hbhip_ctx_device_name", "hbhip_ctx_device_index", "hbhip_frame_context", "hbhip_filter_context",
@@ -203,6 +203,7 @@ def lib() -> C.CDLL:
         for fn in ("hbhip_frame_import_surface_async", "hbhip_frame_export_surface_async", "hbhip_frame_export_surface_widen_async"):
             getattr(L, fn).argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]
         L.hbhip_ctx_bus_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.hbhip_mem_live.argtypes = [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.hbhip_filter_use_frames.argtypes = [C.c_void_p]
         L.hbhip_decomb_push_frame.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int]
         L.hbhip_bm3d_params_from_settings.argtypes = [C.c_char_p, C.c_int, C.POINTER(Bm3dParams)]
@@ -246,6 +247,13 @@ def check(rc: int, ctx=None, what: str = ""):
             msg += " | " + lib().hbhip_ctx_last_error(ctx).decode()
         raise HipError(f"{what}: {msg}")
     return rc
+
+
+def mem_live():
+    """(device, pinned) bytes the library holds right now, process-wide (hbhip_mem_live)"""
+    dev, pin = C.c_size_t(), C.c_size_t()
+    check(lib().hbhip_mem_live(C.byref(dev), C.byref(pin)), what="mem_live")
+    return dev.value, pin.value
 
 
 class Ctx:

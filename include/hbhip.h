@@ -102,6 +102,13 @@ int  hbhip_dev_alloc(hbhip_ctx *ctx, size_t bytes, void **out);
 int  hbhip_dev_free(hbhip_ctx *ctx, void *p);
 int  hbhip_dev_upload(hbhip_ctx *ctx, void *dst, const void *src, size_t bytes);
 int  hbhip_dev_download(hbhip_ctx *ctx, void *dst, const void *src, size_t bytes);
+/* Bytes of device and of page-locked host memory the library itself holds right now, process-wide (contexts, pools,
+ * filters; not what hbhip_host_alloc / hbhip_dev_alloc handed to the caller, nor memory a surface only wraps).  An object
+ * gives back what it holds itself when it is destroyed; what its calls grew on the context - the frame and surface pools,
+ * the staging buffers - stays with the context until hbhip_ctx_destroy, so a second create / use / destroy of the same
+ * kind ends at the counts the first ended at, and a destroyed context at those from before it was made.  A create that
+ * is refused leaves both counts as they were. */
+int  hbhip_mem_live(size_t *device_bytes, size_t *pinned_bytes);
 
 /* ---- device-resident frames (hand-off between adjacent HIP filters) -----------------
  * The reference's GPU precedent keeps frames on the device between its Metal filters
