@@ -19,7 +19,11 @@ FLT_SRC := $(wildcard $(PKG)/libhb/*_hip.c) $(PKG)/libhb/hbhip_registry.c $(PKG)
 
 all: product oracle
 product: $(PKG)/libhbrt.so $(PKG)/libhbhip.so $(PKG)/libhbhip_filters.so tools/vote_avg_check tools/dirmap_vote_check tools/lapsharp_rowdot_check tools/format_nominal_check \
-         tools/chroma_siting_check tools/libcolorspace_sited_check.so
+         tools/chroma_siting_check tools/libcolorspace_sited_check.so tools/jpeg_block_check
+
+# the preview JPEG's block arithmetic run on the HOST (tests/test_preview_jpeg_cpu.py)
+tools/jpeg_block_check: tools/jpeg_block_check.hip $(PKG)/csrc/jpeg_block.h
+	$(HIPCC) --offload-arch=$(ARCH) -O2 -ffp-contract=off -fno-fast-math -I$(PKG)/csrc $< -o $@
 
 # lapsharp's byte dot products run on the HOST (tests/test_lapsharp_rowdot_cpu.py)
 tools/lapsharp_rowdot_check: tools/lapsharp_rowdot_check.hip $(PKG)/csrc/lapsharp_rowdot.h

@@ -743,3 +743,36 @@ def scan_run(lib, planes, flags: int = 0, open_size=None, frame=None, surface=No
     if rc < 0:
         raise RuntimeError(f"hbh_scan_run failed ({rc})")
     return rc, tuple(out)
+
+
+def scan_preview_run(lib, planes, flags: int = 0, open_size=None, frame=None, surface=None, pix_fmt=None, cap=1 << 24):
+    """scan_run through hb_hip_scan_picture_preview: the analysis and the preview's JPEG of one picture, the way scan.c would
+    use the helper when store_previews is set.  Returns (rc, (combed, top, bottom, left, right, recorded), file or None,
+    whether the helper left a buffer behind)."""
+    rt = runtime()
+    rt.hbh_scan_preview_run.restype = C.c_int
+    rt.hbh_scan_preview_run.argtypes = [C.c_void_p] * 3 + [C.c_int] * 5 + [C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.c_void_p,
+                                        C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.POINTER(C.c_int)]
+    planes = [np.ascontiguousarray(p) for p in planes]
+    h, w = planes[0].shape
+    ow, oh = open_size if open_size is not None else (w, h)
+    ptrs = (C.c_void_p * 3)(*[p.ctypes.data for p in planes])
+    strides = (C.c_int * 3)(*[p.strides[0] for p in planes])
+    storage, kind = None, 0
+    if frame is not None:
+        storage, kind, frame.h = frame.h, 1, None
+    elif surface is not None:
+        storage, kind, surface.h = surface.h, 2, None
+    if pix_fmt is None:
+        pix_fmt = AV_PIX_FMT_NV12 if kind == 2 else AV_PIX_FMT_YUV420P
+    fns = [C.cast(getattr(lib, n), C.c_void_p) for n in ("hb_hip_scan_open", "hb_hip_scan_picture_preview", "hb_hip_scan_close")]
+    out = (C.c_int * 6)()
+    buf = (C.c_uint8 * cap)()
+    size, left = C.c_size_t(), C.c_int()
+    rc = rt.hbh_scan_preview_run(*fns, pix_fmt, ow, oh, w, h, ptrs, strides, storage, kind, flags, out, buf, cap, C.byref(size),
+                                 C.byref(left))
+    if rc < 0:
+        raise RuntimeError(f"hbh_scan_preview_run failed ({rc})")
+    data = bytes(memoryview(buf)[:size.value]) if rc == 0 and size.value <= cap else None
+    return rc, tuple(out), data, bool(left.value)

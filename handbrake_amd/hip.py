@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "hbhip_deband_create", "hbhip_deband_offsets", "hbhip_deband_set_kernel",
     "hbhip_bm3d_params_from_settings", "hbhip_bm3d_create",
     "hbhip_scan_create", "hbhip_scan_destroy", "hbhip_scan_push", "hbhip_scan_pull", "hbhip_scan_inflight",
+    "hbhip_jpeg_create", "hbhip_jpeg_destroy", "hbhip_jpeg_bound", "hbhip_jpeg_push", "hbhip_jpeg_pull", "hbhip_jpeg_inflight",
 ]
 
 
@@ -116,6 +117,7 @@ class ScanResult(C.Structure):
 
 SCAN_INFLIGHT_MAX = 32      #: HBHIP_SCAN_INFLIGHT_MAX
 SCAN_RECORD_BYTES = 48      #: HBHIP_SCAN_RECORD_BYTES: what a scanned picture sends over the bus
+JPEG_INFLIGHT_MAX = 4       #: HBHIP_JPEG_INFLIGHT_MAX
 
 
 _lib = None
@@ -213,6 +215,14 @@ def lib() -> C.CDLL:
         L.hbhip_scan_push.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(ScanParams)]
         L.hbhip_scan_pull.argtypes = [C.c_void_p, C.POINTER(ScanResult)]
         L.hbhip_scan_inflight.argtypes = [C.c_void_p]
+        L.hbhip_jpeg_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.hbhip_jpeg_destroy.argtypes = [C.c_void_p]
+        L.hbhip_jpeg_destroy.restype = None
+        L.hbhip_jpeg_bound.argtypes = [C.c_void_p]
+        L.hbhip_jpeg_bound.restype = C.c_size_t
+        L.hbhip_jpeg_push.argtypes = [C.c_void_p, C.c_void_p]
+        L.hbhip_jpeg_pull.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.hbhip_jpeg_inflight.argtypes = [C.c_void_p]
         _lib = L
     return _lib
 
@@ -452,6 +462,49 @@ class ScanDevice:
     def close(self):
         if self.h:
             lib().hbhip_scan_destroy(self.h)
+            self.h = None
+
+
+class JpegDevice:
+    """A preview's JPEG from a device picture (hbhip_jpeg_*): libjpeg's file for 8-bit 4:2:0 planes at one quality."""
+
+    def __init__(self, ctx: Ctx, width, height, quality=90):
+        h = C.c_void_p()
+        check(lib().hbhip_jpeg_create(ctx.h, width, height, quality, C.byref(h)), ctx.h, "jpeg_create")
+        self.ctx, self.h = ctx, h
+
+    def bound(self) -> int:
+        return lib().hbhip_jpeg_bound(self.h)
+
+    def push_rc(self, frame: Frame) -> int:
+        """the raw return code (the refusals are part of the interface)"""
+        return lib().hbhip_jpeg_push(self.h, frame.h)
+
+    def push(self, frame: Frame):
+        check(self.push_rc(frame), self.ctx.h, "jpeg_push")
+
+    def pull_rc(self, cap=None):
+        """(return code, the file's length, the file or None): the oldest picture's, into a buffer of `cap` bytes"""
+        cap = self.bound() if cap is None else cap
+        if getattr(self, "_buf", None) is None or len(self._buf) < max(cap, 1):
+            self._buf = (C.c_uint8 * max(cap, 1))()                  # kept: ctypes clears it, 80 MB at 2160p
+        buf = self._buf
+        size = C.c_size_t()
+        rc = lib().hbhip_jpeg_pull(self.h, buf, cap, C.byref(size))
+        return rc, size.value, (bytes(memoryview(buf)[:size.value]) if rc == HBHIP_OK else None)
+
+    def pull(self):
+        """the oldest picture's file, or None when nothing is in flight"""
+        rc, _, data = self.pull_rc()
+        check(rc, self.ctx.h, "jpeg_pull")
+        return None if rc == HBHIP_AGAIN else data
+
+    def inflight(self) -> int:
+        return lib().hbhip_jpeg_inflight(self.h)
+
+    def close(self):
+        if self.h:
+            lib().hbhip_jpeg_destroy(self.h)
             self.h = None
 
 

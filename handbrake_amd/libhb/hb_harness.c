@@ -992,16 +992,12 @@ int hbh_motion_metric_run(const void *proto, int pix_fmt, int width, int height,
  * scan.c's part around one preview (:972-1052 with the INTEGRATION.md hook): open for the preview size, picture() on the
  * buffer, close.  The buffer is a copy of the caller's planes, or the shell a device-resident decoder puts around a picture
  * in HBM: an hbhip_frame (storage 1) or an NV12 hbhip_surface (storage 2), whose reference the call takes over. */
-int hbh_scan_run(const void *open_fn, const void *picture_fn, const void *close_fn, int pix_fmt, int open_width, int open_height,
-                 int width, int height, uint8_t *const plane[3], const int stride[3], void *storage, int storage_kind,
-                 int flags, int out[6])
+/* the buffer of either run: a copy of the caller's planes, or the shell around a picture in device memory */
+static hb_buffer_t *scan_buffer(int pix_fmt, int width, int height, uint8_t *const plane[3], const int stride[3], void *storage,
+                                int storage_kind, int flags)
 {
-    typedef int  (*open_f)(void **, int, int);
-    typedef int  (*picture_f)(void *, hb_buffer_t *, int *);
-    typedef void (*close_f)(void **);
-    void *scan = NULL;
     hb_buffer_t *b = storage_kind != 0 ? hb_buffer_init(0) : hb_frame_buffer_init(pix_fmt, width, height);
-    if (b == NULL) return -1;
+    if (b == NULL) return NULL;
     if (storage_kind != 0)
     {
         b->s.type = FRAME_BUF;
@@ -1023,9 +1019,47 @@ int hbh_scan_run(const void *open_fn, const void *picture_fn, const void *close_
                 memcpy(b->plane[p].data + (size_t)y * b->plane[p].stride, plane[p] + (size_t)y * stride[p],
                        MIN(stride[p], b->plane[p].stride));
     b->s.flags = (uint16_t)flags;
+    return b;
+}
+
+int hbh_scan_run(const void *open_fn, const void *picture_fn, const void *close_fn, int pix_fmt, int open_width, int open_height,
+                 int width, int height, uint8_t *const plane[3], const int stride[3], void *storage, int storage_kind,
+                 int flags, int out[6])
+{
+    typedef int  (*open_f)(void **, int, int);
+    typedef int  (*picture_f)(void *, hb_buffer_t *, int *);
+    typedef void (*close_f)(void **);
+    void *scan = NULL;
+    hb_buffer_t *b = scan_buffer(pix_fmt, width, height, plane, stride, storage, storage_kind, flags);
+    if (b == NULL) return -1;
     int rc = ((open_f)open_fn)(&scan, open_width, open_height) != 0 ? 1 : 0;
     if (rc == 0 && ((picture_f)picture_fn)(scan, b, out) != 0) rc = 2;
     ((close_f)close_fn)(&scan);
     hb_buffer_close(&b);
+    return rc;
+}
+
+/* scan.c's part around one preview of a scan with store_previews set: the analysis and the preview's file in one call */
+int hbh_scan_preview_run(const void *open_fn, const void *preview_fn, const void *close_fn, int pix_fmt, int open_width,
+                         int open_height, int width, int height, uint8_t *const plane[3], const int stride[3], void *storage,
+                         int storage_kind, int flags, int out[6], uint8_t *jpeg, size_t jpeg_cap, size_t *jpeg_size,
+                         int *returned_buffer)
+{
+    typedef int  (*open_f)(void **, int, int);
+    typedef int  (*preview_f)(void *, hb_buffer_t *, int *, uint8_t **, size_t *);
+    typedef void (*close_f)(void **);
+    void *scan = NULL;
+    uint8_t *file = NULL;
+    *jpeg_size = 0;
+    *returned_buffer = 0;
+    hb_buffer_t *b = scan_buffer(pix_fmt, width, height, plane, stride, storage, storage_kind, flags);
+    if (b == NULL) return -1;
+    int rc = ((open_f)open_fn)(&scan, open_width, open_height) != 0 ? 1 : 0;
+    if (rc == 0 && ((preview_f)preview_fn)(scan, b, out, &file, jpeg_size) != 0) rc = 2;
+    ((close_f)close_fn)(&scan);
+    hb_buffer_close(&b);
+    *returned_buffer = file != NULL;
+    if (file != NULL && *jpeg_size <= jpeg_cap) memcpy(jpeg, file, *jpeg_size);
+    free(file);
     return rc;
 }

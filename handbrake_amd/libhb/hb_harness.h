@@ -94,6 +94,13 @@ int hbh_motion_metric_run(const void *proto, int pix_fmt, int width, int height,
 int hbh_scan_run(const void *open_fn, const void *picture_fn, const void *close_fn, int pix_fmt, int open_width, int open_height,
                  int width, int height, uint8_t *const plane[3], const int stride[3], void *storage, int storage_kind,
                  int flags, int out[6]);
+/* The same through hb_hip_scan_picture_preview (preview_fn): the analysis and the preview's JPEG.  The file the helper
+ * returns is copied to `jpeg` when its *jpeg_size bytes fit jpeg_cap, and freed; *returned_buffer: the helper left a buffer
+ * behind (it must not when it answers non-zero). */
+int hbh_scan_preview_run(const void *open_fn, const void *preview_fn, const void *close_fn, int pix_fmt, int open_width,
+                         int open_height, int width, int height, uint8_t *const plane[3], const int stride[3], void *storage,
+                         int storage_kind, int flags, int out[6], uint8_t *jpeg, size_t jpeg_cap, size_t *jpeg_size,
+                         int *returned_buffer);
 
 /* One rendered subtitle bitmap: 4 planes (Y, Cb, Cr, alpha; 8-bit), placed at (x, y) of the frame. */
 typedef struct

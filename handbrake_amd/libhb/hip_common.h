@@ -33,6 +33,12 @@ typedef struct hb_hip_scan_picture_s
 } hb_hip_scan_picture_t;
 int  hb_hip_scan_open(hb_hip_scan_t **scan, int width, int height);
 int  hb_hip_scan_picture(hb_hip_scan_t *scan, hb_buffer_t *vid_buf, hb_hip_scan_picture_t *out);
+/* the same and, for a scan with store_previews set, the preview's file: what hb_save_preview( .., HB_PREVIEW_FORMAT_JPG )
+ * writes (hb.c:583-629, quality 90) encoded on the GPU from the same picture, in a malloc()ed buffer that becomes the
+ * caller's - write its *jpeg_size bytes under hb_get_tempory_filename's name and free() it.  The file is libjpeg's for these
+ * planes with its default DCT (the reference asks for TJFLAG_FASTDCT: other AC rounding, same container and tables).  The
+ * encoder is made at the first call.  Non-zero: nothing was returned, *jpeg is NULL. */
+int  hb_hip_scan_picture_preview(hb_hip_scan_t *scan, hb_buffer_t *vid_buf, hb_hip_scan_picture_t *out, uint8_t **jpeg, size_t *jpeg_size);
 void hb_hip_scan_close(hb_hip_scan_t **scan);
 
 #endif

@@ -9,7 +9,10 @@
  *
  * A preview that lies in HBM (storage_type HBHIP_DEVICE: an hbhip_frame; HBHIP_SURFACE: a decoder's NV12 picture, imported
  * first) is analysed where it is and 48 bytes come back; a host buffer is uploaded through the pipelined upload.
- * INTEGRATION.md has the hook.
+ *
+ * With store_previews set scan.c:979-982 also writes every preview as a JPEG (hb_save_preview, hb.c:583-629: quality 90 on
+ * one CPU thread).  hb_hip_scan_picture_preview() queues that file's encode (hbhip_jpeg_*) behind the analysis of the same
+ * device picture and hands the finished file back: a preview in HBM is never downloaded.  INTEGRATION.md has both hooks.
  */
 #include "hbhip_host.h"
 #include "hip_common.h"
@@ -18,8 +21,11 @@ struct hb_hip_scan_s
 {
     hbhip_ctx  *ctx;
     hbhip_scan *dev;
+    hbhip_jpeg *jpeg;                  /* made at the first hb_hip_scan_picture_preview() */
     int         width, height;
 };
+
+#define SCAN_PREVIEW_QUALITY 90        /* hb.c:606 */
 
 static int scan_disabled(void)
 {
@@ -51,15 +57,19 @@ int hb_hip_scan_open(hb_hip_scan_t **scan, int width, int height)
 void hb_hip_scan_close(hb_hip_scan_t **scan)
 {
     if (scan == NULL || *scan == NULL) return;
+    hbhip_jpeg_destroy((*scan)->jpeg);
     hbhip_scan_destroy((*scan)->dev);
     free(*scan);
     *scan = NULL;
 }
 
-int hb_hip_scan_picture(hb_hip_scan_t *s, hb_buffer_t *vid_buf, hb_hip_scan_picture_t *out)
+/* the analysis of one preview and, with `jpeg` given, its file: queued together on the picture in HBM */
+static int scan_picture(hb_hip_scan_t *s, hb_buffer_t *vid_buf, hb_hip_scan_picture_t *out, uint8_t **jpeg, size_t *jpeg_size)
 {
     if (s == NULL || vid_buf == NULL || out == NULL || scan_disabled()) return 1;
     if (vid_buf->f.width != s->width || vid_buf->f.height != s->height) return 1;
+    uint8_t *file = NULL;
+    size_t file_cap = 0, file_size = 0;
     hbhip_frame   *fr = hbhip_host_frame_of(vid_buf);
     hbhip_surface *sf = hbhip_host_surface_of(vid_buf);
     void *token = NULL;
@@ -83,7 +93,24 @@ int hb_hip_scan_picture(hb_hip_scan_t *s, hb_buffer_t *vid_buf, hb_hip_scan_pict
     hbhip_scan_result r;
     memset(&r, 0, sizeof(r));
     if (rc == HBHIP_OK) rc = hbhip_scan_push(s->dev, fr, vid_buf->s.flags, NULL);
-    if (rc == HBHIP_OK) rc = hbhip_scan_pull(s->dev, &r);
+    if (rc == HBHIP_OK)
+    {
+        /* the file's launches behind the analysis's on the same stream: the one wait for the file covers both */
+        int rj = HBHIP_OK;
+        if (jpeg != NULL)
+        {
+            if (s->jpeg == NULL) rj = hbhip_jpeg_create(s->ctx, s->width, s->height, SCAN_PREVIEW_QUALITY, &s->jpeg);
+            if (rj == HBHIP_OK)
+            {
+                file_cap = hbhip_jpeg_bound(s->jpeg);        /* (pages nobody writes cost nothing; cut to size below) */
+                if ((file = malloc(file_cap)) == NULL) rj = HBHIP_ERR_NOMEM;
+            }
+            if (rj == HBHIP_OK) rj = hbhip_jpeg_push(s->jpeg, fr);
+            if (rj == HBHIP_OK) rj = hbhip_jpeg_pull(s->jpeg, file, file_cap, &file_size);
+        }
+        rc = hbhip_scan_pull(s->dev, &r);
+        if (rc == HBHIP_OK) rc = rj;
+    }
     if (token != NULL)                                  /* the copy reads vid_buf, which is the caller's again on return */
     {
         const int done = hbhip_ctx_upload_done(s->ctx, token, 1);
@@ -93,7 +120,14 @@ int hb_hip_scan_picture(hb_hip_scan_t *s, hb_buffer_t *vid_buf, hb_hip_scan_pict
     if (rc != HBHIP_OK)
     {
         if (rc != HBHIP_ERR_UNSUPPORTED) hb_error("scan(hip): %s", hbhip_strerror(rc));
+        free(file);
         return 1;
+    }
+    if (file != NULL)
+    {
+        uint8_t *fit = realloc(file, file_size);
+        *jpeg = fit != NULL ? fit : file;
+        *jpeg_size = file_size;
     }
     out->combed = r.combed;
     out->top = r.top;
@@ -102,4 +136,17 @@ int hb_hip_scan_picture(hb_hip_scan_t *s, hb_buffer_t *vid_buf, hb_hip_scan_pict
     out->right = r.right;
     out->recorded = r.recorded;
     return 0;
+}
+
+int hb_hip_scan_picture(hb_hip_scan_t *s, hb_buffer_t *vid_buf, hb_hip_scan_picture_t *out)
+{
+    return scan_picture(s, vid_buf, out, NULL, NULL);
+}
+
+int hb_hip_scan_picture_preview(hb_hip_scan_t *s, hb_buffer_t *vid_buf, hb_hip_scan_picture_t *out, uint8_t **jpeg, size_t *jpeg_size)
+{
+    if (jpeg == NULL || jpeg_size == NULL) return 1;
+    *jpeg = NULL;
+    *jpeg_size = 0;
+    return scan_picture(s, vid_buf, out, jpeg, jpeg_size);
 }

@@ -677,6 +677,33 @@ int  hbhip_scan_push(hbhip_scan *s, hbhip_frame *frame, int pic_flags, const hbh
 int  hbhip_scan_pull(hbhip_scan *s, hbhip_scan_result *out);
 int  hbhip_scan_inflight(hbhip_scan *s);
 
+/* ---- A preview's JPEG (replaces hb_save_preview's tjCompressFromYUVPlanes, hb.c:583-629, which scan.c:979-982 calls for
+ *      every preview when store_previews is set) -----------------------------------------------
+ * The picture is a device frame and stays where it is: what comes back is the finished file.  Defined for what the scan
+ * decodes to: 8-bit planar 4:2:0 with even sizes.  The file is the baseline JPEG libjpeg writes for these planes with its
+ * DEFAULT DCT (the accurate integer one, jfdctint.c), byte for byte: JFIF 1.01 header, Annex K's tables scaled by `quality`
+ * (jpeg_quality_scaling), Annex K's Huffman tables, 2x2 luma sampling, one scan, no restart markers.  hb.c:607 asks for
+ * TJFLAG_FASTDCT, whose rounding of the AC coefficients differs; container, tables and entropy code are the same.
+ * push queues a picture's launches on the context's stream behind the frame's contents, pull hands out the oldest
+ * picture's file (waiting for it); up to HBHIP_JPEG_INFLIGHT_MAX may be in flight.  The object holds a reference on a
+ * pushed frame until the pull.  Per pushed picture hbhip_ctx_bus_bytes of the object's context counts a 16-byte record and
+ * the file's scan segment (the file less its 623-byte header and the end marker) of D2H, and nothing else.
+ * Refusals, all before anything is queued - HBHIP_ERR_UNSUPPORTED: not 8-bit planar 4:2:0, an odd size, another size than
+ * the object's, below 8 x 8 (create also: above 16384); HBHIP_ERR_ARG: a quality outside 1 .. 100, a frame of another GPU
+ * than the object's; HBHIP_ERR_STATE: HBHIP_JPEG_INFLIGHT_MAX pictures in flight.
+ * pull: `cap` bytes at dst; *size is the file's length.  A file longer than `cap` answers HBHIP_ERR_ARG with *size set to
+ * the length it has, nothing written, and the picture is DROPPED (push it again): hbhip_jpeg_bound() is a capacity no file
+ * of the object's size exceeds. */
+#define HBHIP_JPEG_INFLIGHT_MAX 4
+typedef struct hbhip_jpeg hbhip_jpeg;
+int    hbhip_jpeg_create(hbhip_ctx *ctx, int width, int height, int quality, hbhip_jpeg **out);
+void   hbhip_jpeg_destroy(hbhip_jpeg *j);            /* waits for what is in flight and drops it */
+size_t hbhip_jpeg_bound(hbhip_jpeg *j);              /* a capacity no file of this size exceeds */
+int    hbhip_jpeg_push(hbhip_jpeg *j, hbhip_frame *frame);
+/* the oldest picture's file (waits for it); HBHIP_AGAIN when none is in flight */
+int    hbhip_jpeg_pull(hbhip_jpeg *j, uint8_t *dst, size_t cap, size_t *size);
+int    hbhip_jpeg_inflight(hbhip_jpeg *j);
+
 /* ---- Subtitle compositor (replaces hb_blend, blend.c: the object rendersub.c hands every frame
  *      and the list of rendered overlays, rendersub.c:467, 1129-1161) -------------------------
  * Planar 8/10/12-bit frames; overlays are 8-bit Y/Cb/Cr/alpha bitmaps either in the frame's chroma
