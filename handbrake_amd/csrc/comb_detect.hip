@@ -746,7 +746,29 @@ public:
         int blocks_x;
         if (const int rc = score(filt ? bm + msz : bm, fs, n, false, filt, &blocks_x)) return rc;
         for (int i = 0; i < n; i++) combed[i] = h_result.get()[4 * i];
+        last_n = n;
         return HBHIP_OK;
+    }
+
+    // test hook: one mask of frame `frame` of the last classify / classify_many, as it lies in HBM (height rows of
+    // mstride bytes).  which 0: the detector's mask; 1: the filtered mask (what the block score read, mask filter on);
+    // 2: the intermediate mask, where a launch writes one to HBM - filter mode 0's only pass, or the pass-by-pass
+    // chain of the overlay modes (the fused kernels carry theirs in LDS, filter mode 1 has none).  Copies only.
+    int debug_mask(int frame, int which, uint8_t *dst, size_t dst_bytes, int *stride)
+    {
+        if (stride) *stride = mstride;
+        if (frame < 0 || frame >= last_n || which < 0 || which > 2) return HBHIP_ERR_ARG;
+        const bool filt = (par.mode & 2) != 0;
+        const uint8_t *src;
+        if (which == 0) src = batched ? bmasks.get() + 2 * msz * (size_t)frame : mask;
+        else if (!filt) return HBHIP_ERR_UNSUPPORTED;
+        else if (which == 1) src = batched ? bmasks.get() + 2 * msz * (size_t)frame + msz : mask_filtered;
+        else if (par.filter_mode == 1 || (par.filter_mode == 2 && !overlay)) return HBHIP_ERR_UNSUPPORTED;
+        else src = mask_temp;
+        const size_t bytes = (size_t)mstride * height;
+        if (!dst || dst_bytes < bytes) return HBHIP_ERR_ARG;
+        HBHIP_CHECK(ctx, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return hbhip_wait_behind(ctx, ctx->stream, "comb detect: debug mask");
     }
 
     // The frame in the ring: from ref[0], ref[1], ref[2].  8-bit pictures without overlay are a batch of one; the overlay
@@ -797,7 +819,8 @@ public:
         int blocks_x;
         if (const int rc = score(filt ? mask_filtered : mask, 0, 1, overlay, filt, &blocks_x)) return rc;
         *combed = h_result.get()[0];
-        if (overlay && h_result.get()[2] > 0 && blocks_x > 0)
+        last_n = 1;
+        if (overlay &&h_result.get()[2] > 0 && blocks_x > 0)
         {
             const int idx = h_result.get()[1] > 0 ? 0x7fffffff - h_result.get()[1] : h_result.get()[2] - 1;
             box_x = (idx % blocks_x) * par.block_width;
@@ -886,6 +909,7 @@ private:
     int box_x = 0, box_y = 0;                        // pv->mask_box_x / _y
     DevBuf<uint8_t> stage;
     DevBuf<uint8_t> bmasks;                          // a batch's frames x (mask, filtered mask): batch_masks()
+    int last_n = 0;                                  // frames of the last classify / classify_many: debug_mask()
 };
 
 } // namespace
@@ -956,6 +980,14 @@ extern "C" int hbhip_comb_detect_classify_many_dev(hbhip_filter *f, const void *
     if (!c || !lumas || !combed) return HBHIP_ERR_ARG;
     (void)hipSetDevice(f->ctx->device);
     return c->classify_many(lumas, stride, n_frames, force_bits, combed);
+}
+
+extern "C" int hbhip_comb_detect_debug_mask(hbhip_filter *f, int frame, int which, uint8_t *dst, size_t dst_bytes, int *stride)
+{
+    CombDetectFilter *c = dynamic_cast<CombDetectFilter *>(f);
+    if (!c) return HBHIP_ERR_ARG;
+    (void)hipSetDevice(f->ctx->device);
+    return c->debug_mask(frame, which, dst, dst_bytes, stride);
 }
 
 extern "C" int hbhip_comb_detect_classify(hbhip_filter *f, int force_exhaustive, int *combed)

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "hbhip_comb_detect_create", "hbhip_comb_detect_set_gamma_lut", "hbhip_comb_detect_store",
     "hbhip_comb_detect_store_dev",
     "hbhip_comb_detect_classify", "hbhip_comb_detect_classify_many_dev", "hbhip_comb_detect_overlay", "hbhip_comb_detect_overlay_dev",
+    "hbhip_comb_detect_debug_mask",
     "hbhip_rotate_create", "hbhip_grayscale_create", "hbhip_cropscale_create", "hbhip_cropscale_create_sited", "hbhip_colorspace_create", "hbhip_colorspace_create_sited", "hbhip_pad_create", "hbhip_yadif_create", "hbhip_bwdif_create", "hbhip_format_create", "hbhip_format_resample_create", "hbhip_format_scaled_create", "hbhip_format_upsample_create", "hbhip_format_deepen_create",
     "hbhip_blend_create", "hbhip_blend_set_overlays", "hbhip_blend_apply", "hbhip_blend_apply_dev", "hbhip_blend_destroy",
     "hbhip_blend_create_biplanar", "hbhip_blend_apply_biplanar",
@@ -623,22 +624,48 @@ class CombDetectDevice:
     hb_filter_object_t path is hb_filter_comb_detect_hip).  Defaults = param.c:204-207."""
 
     def __init__(self, ctx: Ctx, width, height, mode=3, spatial_metric=2, motion_thresh=1, spatial_thresh=1,
-                 filter_mode=2, block_thresh=40, block_width=16, block_height=16):
+                 filter_mode=2, block_thresh=40, block_width=16, block_height=16, depth=8):
         import numpy as np
         L = lib()
         L.hbhip_comb_detect_create.argtypes = [C.c_void_p, C.POINTER(CombDetectParams)] + [C.c_int] * 3 + [C.POINTER(C.c_void_p)]
+        L.hbhip_comb_detect_store.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.hbhip_comb_detect_store_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.hbhip_comb_detect_set_gamma_lut.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.hbhip_comb_detect_classify.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+        L.hbhip_comb_detect_debug_mask.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]
         par = CombDetectParams(mode, spatial_metric, motion_thresh, spatial_thresh, filter_mode, block_thresh,
                                block_width, block_height)
         # comb_detect.c:1074-1081: pow((float)i / (float)max, 2.2f), evaluated in double, stored as float
-        lut = np.power((np.arange(256, dtype=np.float32) / np.float32(255)).astype(np.float64),
+        maxv = (1 << depth) - 1
+        lut = np.power((np.arange(maxv + 1, dtype=np.float32) / np.float32(maxv)).astype(np.float64),
                        np.float64(np.float32(2.2))).astype(np.float32)
-        for i in range(256):
-            par.gamma_lut[i] = float(lut[i])
+        if depth == 8:
+            for i in range(256):
+                par.gamma_lut[i] = float(lut[i])
         h = C.c_void_p()
-        check(L.hbhip_comb_detect_create(ctx.h, C.byref(par), width, height, 8, C.byref(h)), ctx.h, "comb_detect_create")
-        self.ctx, self.h = ctx, h
+        check(L.hbhip_comb_detect_create(ctx.h, C.byref(par), width, height, depth, C.byref(h)), ctx.h, "comb_detect_create")
+        self.ctx, self.h, self.width, self.height, self.depth = ctx, h, width, height, depth
+        if depth > 8:        # more entries than the params struct holds (comb_detect.c:1102)
+            lut = np.ascontiguousarray(lut)
+            check(L.hbhip_comb_detect_set_gamma_lut(h, lut.ctypes.data, maxv + 1), ctx.h, "comb_detect_set_gamma_lut")
+
+    def store(self, luma):
+        """A luma plane in host memory (2-D uint8, or uint16 for depth > 8) becomes the newest of the ring; None repeats it."""
+        if luma is None:
+            check(lib().hbhip_comb_detect_store(self.h, None, 0), self.ctx.h, "comb_detect_store")
+            return
+        check(lib().hbhip_comb_detect_store(self.h, luma.ctypes.data, luma.strides[0]), self.ctx.h, "comb_detect_store")
+
+    def debug_mask(self, which, frame=0):
+        """Test hook: mask `which` (0 detector, 1 filtered, 2 intermediate) of a frame of the last classify /
+        classify_many as it lies in HBM: (height, stride) uint8."""
+        import numpy as np
+        st = C.c_int()
+        lib().hbhip_comb_detect_debug_mask(self.h, frame, which, None, 0, C.byref(st))          # the stride (no buffer: refused)
+        a = np.full((self.height, st.value), 0xAA, np.uint8)
+        check(lib().hbhip_comb_detect_debug_mask(self.h, frame, which, a.ctypes.data, a.nbytes, C.byref(st)), self.ctx.h,
+              "comb_detect_debug_mask")
+        return a
 
     def store_dev(self, luma_ptr, stride):
         check(lib().hbhip_comb_detect_store_dev(self.h, C.c_void_p(luma_ptr), stride), self.ctx.h, "comb_detect_store_dev")

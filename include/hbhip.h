@@ -427,9 +427,16 @@ int hbhip_comb_detect_classify(hbhip_filter *f, int force_exhaustive, int *combe
 /* The same verdicts for n_frames (<= 16) frames at once, for callers that hold the lumas in HBM: frame i is judged
  * from lumas[i], lumas[i + 1], lumas[i + 2] (prev / cur / next as the ring would hold them - n_frames + 2 device
  * pointers, `stride` bytes a row, 4-byte aligned), bit i of force_bits = force_exhaustive for frame i.  Three
- * launches and one read-back whatever n_frames is; does not touch the ring.  8-bit, modes 0-3, filter-mode 0 or 2. */
+ * launches and one read-back whatever n_frames is; does not touch the ring.  8-bit, modes 0-3; with the mask filter on
+ * (mode & 2) only filter-mode 2, the others are HBHIP_ERR_UNSUPPORTED. */
 int hbhip_comb_detect_classify_many_dev(hbhip_filter *f, const void *const *lumas, int stride, int n_frames,
                                         unsigned force_bits, int *combed);
+/* test hook: copy one mask of frame `frame` of the last classify (frame 0) or
+ * classify_many (0 .. n-1) to `dst`: height rows of *stride bytes.
+ * which: 0 the detector's mask, 1 the mask the block score read when a mask
+ * filter is on, 2 the intermediate mask where one exists in HBM (else UNSUPPORTED). */
+int hbhip_comb_detect_debug_mask(hbhip_filter *f, int frame, int which,
+                                 uint8_t *dst, size_t dst_bytes, int *stride);
 
 /* Mask overlay, modes 4 (MODE_MASK) / 8 (MODE_COMPOSITE): draw_mask_box + apply_mask (comb_detect_template.c:21-136)
  * on `frame`, which holds a COPY of the frame the last classify judged combed (process_frame, comb_detect.c:1519-1526).
