@@ -1344,6 +1344,172 @@ __global__ void copy_plane_kernel(uint8_t *dst, int dst_pitch, const uint8_t *sr
 }
 
 // ------------------------------------------------------------------- host side
+// Every lane-sharing instantiation there is, as X(kernel, patch, wide, fast, pitch, pre, pairs, origin_f32): the kernel and
+// the fields of a launch (hbhip_nlmeans_launch) that select it.  The launch looks its kernel up in this list and
+// hbhip_nlmeans_forms() reads it out, so a kernel that is not in it cannot be launched and one that is can be counted.
+#define NLM_FORM_PRE(X, KERN, NN, WIDE, FF, CC) \
+    X((KERN<NN, FF, CC, false>), NN, WIDE, FF, CC, 0, 0, 0) X((KERN<NN, FF, CC, true>), NN, WIDE, FF, CC, 1, 0, 0)
+#define NLM_FORM_IDX(X, KERN, NN, WIDE, CC) \
+    NLM_FORM_PRE(X, KERN, NN, WIDE, 0, CC) NLM_FORM_PRE(X, KERN, NN, WIDE, 1, CC) NLM_FORM_PRE(X, KERN, NN, WIDE, 2, CC)
+#define NLM_FORM_PATCH(X, NN) \
+    NLM_FORM_IDX(X, nlmeans_lanes_kernel, NN, 0, 36) NLM_FORM_IDX(X, nlmeans_lanes_kernel, NN, 0, 44) \
+    NLM_FORM_IDX(X, nlmeans_lanes16_kernel, NN, 1, 76) NLM_FORM_IDX(X, nlmeans_lanes16_kernel, NN, 1, 84)
+// the paired displacements: patch sizes up to 7 (see the static_assert), at 8 bits with the origin term in double or in single
+#define NLM_FORM_PAIRS(X, NN) \
+    X((nlmeans_lanes_kernel<NN, 3, 36, false, false>), NN, 0, 3, 36, 0, 4, 0) X((nlmeans_lanes_kernel<NN, 3, 36, false, true>), NN, 0, 3, 36, 0, 4, 1) \
+    X((nlmeans_lanes_kernel<NN, 3, 44, false, false>), NN, 0, 3, 44, 0, 4, 0) X((nlmeans_lanes_kernel<NN, 3, 44, false, true>), NN, 0, 3, 44, 0, 4, 1) \
+    X((nlmeans_lanes16_kernel<NN, 3, 76, false, NLM16_SYM_PAIRS>), NN, 1, 3, 76, 0, NLM16_SYM_PAIRS, 0)
+// (the last three entries: what the pairs' kernels come to at patch 9, where they fall back to form 2 - built ever since
+// the pairs were dispatched by a macro over all four patch sizes, and kept so that the library holds the kernels it held;
+// no plan names them, nor the pairs at pitch 44: a 3 x 3 search never needs the wide pitch)
+#define NLM_FORMS(X) \
+    NLM_FORM_PATCH(X, 3) NLM_FORM_PATCH(X, 5) NLM_FORM_PATCH(X, 7) NLM_FORM_PATCH(X, 9) \
+    NLM_FORM_PAIRS(X, 3) NLM_FORM_PAIRS(X, 5) NLM_FORM_PAIRS(X, 7) \
+    X((nlmeans_lanes_kernel<9, 2, 36, false, true>), 9, 0, 2, 36, 0, 0, 1) X((nlmeans_lanes_kernel<9, 2, 44, false, true>), 9, 0, 2, 44, 0, 0, 1) \
+    X((nlmeans_lanes16_kernel<9, 2, 76, false, NLM16_SYM_PAIRS>), 9, 1, 2, 76, 0, NLM16_SYM_PAIRS, 0)
+
+// HBHIP_NLMEANS_GENERIC=1: every patch size through nlmeans_generic_kernel (a verification switch: the tuned kernels and
+// the generic one are two implementations of the same integers and the same float sequence)
+static bool nlm_force_generic()
+{
+    const char *e = getenv("HBHIP_NLMEANS_GENERIC");
+    return e != nullptr && atoi(e) != 0;
+}
+
+// What an instance derives from its parameters and its geometry, once: the planes it denoises, the table-index constants
+// of each, and the launches of a frame - one per distinct patch size, ascending.  This is the one place that decides
+// which kernel form runs; launch_views() dispatches from it and hbhip_nlmeans_plan() shows it.  No device is touched.
+struct NlmPlan
+{
+    int diff_cap[3] = {-1, -1, -1};
+    uint32_t imul4[3] = {0, 0, 0};
+    int ishift[3] = {0, 0, 0};
+    int pf_type[3] = {0, 0, 0};          // effective prefilter bits per plane (0 = none)
+    bool passthru[3] = {false, false, false};
+    bool any_pre = false;
+    int max_frames = 1;
+    int n = 0;
+    hbhip_nlmeans_launch launch[3];
+};
+
+static int nlm_plan(const hbhip_nlmeans_params &par, const PicGeometry &geo, bool force_generic, NlmPlan &pl)
+{
+    pl = NlmPlan();
+    for (int c = 0; c < 3; c++)
+    {
+        // a prefilter only exists if one of the base filters is selected (:438-443)
+        pl.pf_type[c] = (par.prefilter[c] & PF_BASE) ? par.prefilter[c] : 0;
+        pl.passthru[c] = (par.prefilter[c] & PF_PASSTHRU) != 0;
+        pl.any_pre |= pl.pf_type[c] != 0;
+        if (pl.passthru[c]) continue;                 // the plane is not denoised at all (nlmeans.c:485-492)
+        pl.max_frames = std::max(pl.max_frames, par.nframes[c]);
+        if (par.strength[c] == 0) continue;
+        const int n = par.patch_size[c];
+        if (n < 1 || (n & 1) == 0) return HBHIP_ERR_ARG;                        // (the drop-in sanitises as nlmeans.c:329-330)
+        if (n / 2 + par.range[c] / 2 > NLM_BORDER) return HBHIP_ERR_UNSUPPORTED;  // past the reference's own mirrored border
+        if (par.nframes[c] < 1 || par.nframes[c] > HBHIP_NLMEANS_FRAMES_MAX) return HBHIP_ERR_ARG;
+        if (geo.pw[c] < NLM_BORDER || geo.ph[c] < NLM_BORDER) return HBHIP_ERR_UNSUPPORTED;
+    }
+    for (int c = 0; c < 3; c++)
+    {
+        // smallest diff whose index reaches 127; usable only if that index is exactly 127,
+        // it does not exceed diff_max, and the table really ends in 0
+        const float wft = par.weight_fact_table[c];
+        if (par.strength[c] == 0 || par.exptable[c][127] != 0.f || !(wft > 0.f)) continue;
+        for (int d = 0; d <= par.diff_max[c]; d++)
+            if ((int)((float)d * wft) >= 127)
+            {
+                if ((int)((float)d * wft) == 127) pl.diff_cap[c] = d;
+                break;
+            }
+        // the integer form of the index (FAST 2): wft is a float, so wft * 2^(34 + s) is an integer M for some small s;
+        // usable when M fits 32 bits and (d * M) >> (34 + s) equals the float expression for every d up to the cap.
+        // The kernels take (mul_hi(d, M) >> s) & 0x1fc = 4 * index as the table's byte offset.
+        if (pl.diff_cap[c] >= 0)
+            for (int sft = 0; sft <= 12; sft++)
+            {
+                const double m = std::ldexp((double)wft, 34 + sft);
+                if (!(m > 0.0 && m < 4294967296.0)) break;
+                if (m != std::floor(m)) continue;
+                const uint64_t M = (uint64_t)m;
+                bool same = true;
+                for (int d = 0; d <= pl.diff_cap[c] && same; d++)
+                    same = (int)(((uint64_t)d * M) >> (34 + sft)) == (int)((float)d * wft);
+                if (same) { pl.imul4[c] = (uint32_t)M; pl.ishift[c] = sft; }
+                break;
+            }
+    }
+
+    // group the planes by patch size (one launch per distinct n)
+    std::vector<int> sizes;
+    for (int c = 0; c < 3; c++)
+        if (!pl.passthru[c] && par.strength[c] != 0 && std::find(sizes.begin(), sizes.end(), par.patch_size[c]) == sizes.end())
+            sizes.push_back(par.patch_size[c]);
+    std::sort(sizes.begin(), sizes.end());
+    const bool wide = geo.bps == 2;                        // 16-bit samples: 2 pixels per tile dword
+    for (int n : sizes)
+    {
+        hbhip_nlmeans_launch &L = pl.launch[pl.n++];
+        memset(&L, 0, sizeof(L));
+        L.patch_size = n;
+        L.wide = wide;
+        // a tile's job by arithmetic: the frames of a launch have the same planes with the same tile counts
+        L.job_arith = NLM_JOB_ARITH;
+        // patch sizes without a lane-sharing instantiation (1, 11, 13, 15, ...) - or all of them, when asked for the
+        // second implementation - go to nlmeans_generic_kernel
+        L.generic = force_generic || !(n == 3 || n == 5 || n == 7 || n == 9);
+        bool all_rh1 = true, all_org1 = true, fast = true, fast_int = true;
+        for (int c = 0; c < 3; c++)
+        {
+            L.diff_cap[c] = -1;
+            if (pl.passthru[c] || par.strength[c] == 0 || par.patch_size[c] != n) continue;
+            L.planes |= 1 << c;
+            L.diff_cap[c] = pl.diff_cap[c];
+            L.imul4[c] = pl.imul4[c];
+            L.ishift[c] = pl.ishift[c];
+            L.pre |= pl.pf_type[c] != 0;
+            const int r_half = (par.range[c] - 1) / 2;
+            L.max_rh = std::max(L.max_rh, r_half);
+            all_rh1 &= r_half == 1;
+            all_org1 &= par.origin_tune[c] == 1.0;
+            fast &= pl.diff_cap[c] >= 0;
+            fast_int &= pl.imul4[c] != 0 && (wide || pl.ishift[c] == 0);
+        }
+        const int nh = n / 2;
+        if (L.generic)
+        {
+            const int aw_ = GW + 2 * nh, ah_ = GH + 2 * nh, bw_ = aw_ + 2 * L.max_rh, bh_ = ah_ + 2 * L.max_rh;
+            L.tile_w = GW;
+            L.tile_h = GH;
+            L.lds_bytes = (unsigned)(sizeof(uint32_t) * ah_ * GW + (size_t)geo.bps * (((aw_ * ah_ + 1) & ~1) + bw_ * bh_ + 2));
+            continue;
+        }
+        L.tile_w = LTW;
+        L.tile_h = TH;
+        L.cmp_rows = TH + 2 * (nh + L.max_rh);
+        // tiles: 32 lanes + rq dwords of search halo either side (+1 for the alignbyte high
+        // word), pitch = 4 (mod 8) dwords
+        const int rq = (L.max_rh + 3) / 4;
+        L.pitch = wide ? (rq <= 2 ? 76 : 84) : (rq <= 1 ? 36 : 44);
+        // the pairs of frame 0 share their patch distances (FAST 3) when every plane of the launch searches 3 x 3
+        // (patch sizes up to 7: the mirrored index of a lane's edge pixel comes from the neighbouring lane's edge pixel,
+        // whose own window must not reach past ITS neighbour - the outer lanes of a tile row have none)
+        const bool sym = fast && fast_int && !L.pre && all_rh1 && n <= 7;
+        L.fast = sym ? 3 : fast && fast_int ? 2 : fast ? 1 : 0;
+        // (16-bit samples: NLM16_SYM_PAIRS of the four pairs share - the stash of three fits three workgroups on a CU)
+        L.pairs = sym ? (wide ? NLM16_SYM_PAIRS : 4) : 0;
+        L.origin_f32 = sym && !wide && all_org1 && NLM_ORIGIN_F32;
+        // (what the kernels size their staging registers by)
+        if (L.cmp_rows > nlm_max_rows(n, sym, L.pitch == (wide ? 76 : 36) ? (wide ? 8 : 4) : NLM_BORDER))
+            return HBHIP_ERR_UNSUPPORTED;
+        const size_t tile_dwords = (size_t)L.pitch * L.cmp_rows + 4;
+        size_t shmem = sizeof(uint32_t) * (L.pre ? 4 : 2) * tile_dwords + 512;
+        if (sym) shmem = 512 + sizeof(uint32_t) * (tile_dwords + std::max<size_t>(tile_dwords, (size_t)L.pairs * (RY + 1) * TXN * TYN));
+        L.lds_bytes = (unsigned)shmem;
+    }
+    return HBHIP_OK;
+}
+
 class NlmFilter : public hbhip_filter
 {
 public:
@@ -1359,53 +1525,13 @@ public:
         in_geo.set(width, height, depth, lcw, lch);
         out_geo = in_geo;
         pool.configure(ctx, in_geo);
-        max_frames = 1;
+        if (const int rc = nlm_plan(par, in_geo, force_generic, plan)) return rc;
+        max_frames = plan.max_frames;
+        any_pre = plan.any_pre;
         for (int c = 0; c < 3; c++)
         {
-            // a prefilter only exists if one of the base filters is selected (:438-443)
-            pf_type[c] = (par.prefilter[c] & PF_BASE) ? par.prefilter[c] : 0;
-            passthru[c] = (par.prefilter[c] & PF_PASSTHRU) != 0;
-            any_pre |= pf_type[c] != 0;
-            if (passthru[c]) continue;                 // the plane is not denoised at all (nlmeans.c:485-492)
-            max_frames = std::max(max_frames, par.nframes[c]);
-            if (par.strength[c] == 0) continue;
-            const int n = par.patch_size[c];
-            if (n < 1 || (n & 1) == 0) return HBHIP_ERR_ARG;                        // (the drop-in sanitises as nlmeans.c:329-330)
-            if (n / 2 + par.range[c] / 2 > NLM_BORDER) return HBHIP_ERR_UNSUPPORTED;  // past the reference's own mirrored border
-            if (par.nframes[c] < 1 || par.nframes[c] > HBHIP_NLMEANS_FRAMES_MAX) return HBHIP_ERR_ARG;
-            if (in_geo.pw[c] < NLM_BORDER || in_geo.ph[c] < NLM_BORDER) return HBHIP_ERR_UNSUPPORTED;
-        }
-        for (int c = 0; c < 3; c++)
-        {
-            // smallest diff whose index reaches 127; usable only if that index is exactly 127,
-            // it does not exceed diff_max, and the table really ends in 0
-            diff_cap[c] = -1;
-            const float wft = par.weight_fact_table[c];
-            if (par.strength[c] == 0 || par.exptable[c][127] != 0.f || !(wft > 0.f)) continue;
-            for (int d = 0; d <= par.diff_max[c]; d++)
-                if ((int)((float)d * wft) >= 127)
-                {
-                    if ((int)((float)d * wft) == 127) diff_cap[c] = d;
-                    break;
-                }
-            // the integer form of the index (FAST 2): wft is a float, so wft * 2^(34 + s) is an integer M for some small s;
-            // usable when M fits 32 bits and (d * M) >> (34 + s) equals the float expression for every d up to the cap.
-            // The kernels take (mul_hi(d, M) >> s) & 0x1fc = 4 * index as the table's byte offset.
-            imul4[c] = 0;
-            ishift[c] = 0;
-            if (diff_cap[c] >= 0)
-                for (int sft = 0; sft <= 12; sft++)
-                {
-                    const double m = std::ldexp((double)wft, 34 + sft);
-                    if (!(m > 0.0 && m < 4294967296.0)) break;
-                    if (m != std::floor(m)) continue;
-                    const uint64_t M = (uint64_t)m;
-                    bool same = true;
-                    for (int d = 0; d <= diff_cap[c] && same; d++)
-                        same = (int)(((uint64_t)d * M) >> (34 + sft)) == (int)((float)d * wft);
-                    if (same) { imul4[c] = (uint32_t)M; ishift[c] = sft; }
-                    break;
-                }
+            pf_type[c] = plan.pf_type[c];
+            passthru[c] = plan.passthru[c];
         }
         if (any_pre)
         {
@@ -1454,15 +1580,11 @@ public:
 
     int batch = 1;
     bool deferred = false;
-    int diff_cap[3] = {-1, -1, -1};
-    uint32_t imul4[3] = {0, 0, 0};
-    int ishift[3] = {0, 0, 0};
+    NlmPlan plan;                        // the launches of a frame and the table-index constants of each plane (nlm_plan)
     int pf_type[3] = {0, 0, 0};          // effective prefilter bits per plane (0 = none)
     bool passthru[3] = {false, false, false};
     bool any_pre = false;
-    // HBHIP_NLMEANS_GENERIC=1: every patch size through nlmeans_generic_kernel (a verification switch: the tuned kernels and
-    // the generic one are two implementations of the same integers and the same float sequence)
-    bool force_generic = [] { const char *e = getenv("HBHIP_NLMEANS_GENERIC"); return e != nullptr && atoi(e) != 0; }();
+    bool force_generic = nlm_force_generic();
 
 private:
     int ensure_jobs(int n)
@@ -1579,39 +1701,24 @@ private:
         if (rc != HBHIP_OK) return rc;
         const int total = (int)ins.size();
 
-        // group jobs by patch size (one launch per distinct n)
-        std::vector<int> sizes;
-        for (int c = 0; c < 3; c++)
-            if (!passthru[c] && par.strength[c] != 0 && std::find(sizes.begin(), sizes.end(), par.patch_size[c]) == sizes.end())
-                sizes.push_back(par.patch_size[c]);
-        std::sort(sizes.begin(), sizes.end());
-        for (int n : sizes)
+        // one launch per distinct patch size, in the kernel form the plan gives it
+        for (int li = 0; li < plan.n; li++)
         {
-            // patch sizes without a lane-sharing instantiation (1, 11, 13, 15, ...) - or all of them, when asked for the
-            // second implementation - go to nlmeans_generic_kernel
-            const bool generic = force_generic || !(n == 3 || n == 5 || n == 7 || n == 9);
-            bool any = false, pre = false;
-            for (int c = 0; c < 3; c++)
-                if (!passthru[c] && par.strength[c] != 0 && par.patch_size[c] == n)
-                {
-                    any = true;
-                    pre |= pf_type[c] != 0;
-                }
-            if (!any) continue;
+            const hbhip_nlmeans_launch &L = plan.launch[li];
+            const int n = L.patch_size, max_rh = L.max_rh;
+            const bool generic = L.generic != 0;
             table = (table + 1) % NTABLES;
             if (table_used[table]) HBHIP_CHECK(ctx, hipEventSynchronize(table_ev[table]));
             NlmJob *hj = h_jobs.get() + (size_t)table * jobs_cap;
             NlmJob *dj = d_jobs.get() + (size_t)table * jobs_cap;
-            int nj = 0, tiles = 0, max_rh = 0;
-            bool all_rh1 = true, all_org1 = true;
+            int nj = 0, tiles = 0;
             // the tile counts of a frame's planes (NlmTiles), taken from the first frame's jobs and held against the rest
             int plane_tiles[3] = {0, 0, 0}, planes = 0;
             bool repeats = true;
-            bool fast = true, fast_int = true;
             for (int t = 0; t < ready; t++)
                 for (int c = 0; c < 3; c++)
                 {
-                    if (passthru[c] || par.strength[c] == 0 || par.patch_size[c] != n) continue;
+                    if (!(L.planes >> c & 1)) continue;
                     NlmJob &jb = hj[nj++];
                     jb.nframes = std::min(par.nframes[c], total - t);
                     for (int f = 0; f < jb.nframes; f++)
@@ -1634,11 +1741,9 @@ private:
                     jb.origin_tune = par.origin_tune[c];
                     jb.wft = par.weight_fact_table[c];
                     jb.diff_max = par.diff_max[c];
-                    jb.diff_cap = diff_cap[c];
-                    jb.imul4 = imul4[c];
-                    jb.ishift = ishift[c];
-                    fast &= diff_cap[c] >= 0;
-                    fast_int &= imul4[c] != 0 && (in_geo.bps == 2 || ishift[c] == 0);
+                    jb.diff_cap = plan.diff_cap[c];
+                    jb.imul4 = plan.imul4[c];
+                    jb.ishift = plan.ishift[c];
                     jb.w = in_geo.pw[c];
                     jb.h = in_geo.ph[c];
                     jb.dst_pitch = outs[t].pitch[c];
@@ -1649,14 +1754,11 @@ private:
                     tiles += job_tiles;
                     if (t == 0) plane_tiles[planes++] = job_tiles;
                     else repeats &= plane_tiles[(nj - 1) % planes] == job_tiles;
-                    max_rh = std::max(max_rh, jb.r_half);
-                    all_rh1 &= jb.r_half == 1;
-                    all_org1 &= par.origin_tune[c] == 1.0;
                 }
             if (nj == 0) continue;
             repeats &= nj == planes * ready;
             NlmTiles tc = {0, 0, 0, 0};              // (all zero: the kernels search the table)
-            if (repeats && NLM_JOB_ARITH)
+            if (repeats && L.job_arith)
             {
                 tc.per_frame = plane_tiles[0] + plane_tiles[1] + plane_tiles[2];
                 tc.after0 = plane_tiles[0];
@@ -1673,74 +1775,38 @@ private:
             }
             HBHIP_CHECK(ctx, hipEventRecord(table_ev[table], ctx->stream));
             table_used[table] = true;
-            const int nh = n / 2;
+            const size_t shmem = L.lds_bytes;
             if (generic)
             {
-                const int aw_ = GW + 2 * nh, ah_ = GH + 2 * nh, bw_ = aw_ + 2 * max_rh, bh_ = ah_ + 2 * max_rh;
-                const size_t shmem = sizeof(uint32_t) * ah_ * GW + (size_t)in_geo.bps * (((aw_ * ah_ + 1) & ~1) + bw_ * bh_ + 2);
-                if (in_geo.bps == 1)
-                    HBHIP_LAUNCH(ctx, "nlmeans_plane_generic", nlmeans_generic_kernel<uint8_t>, dim3(tiles), dim3(GW * GH), shmem, dj, nj, n, max_rh, (int)pre);
+                if (!L.wide)
+                    HBHIP_LAUNCH(ctx, "nlmeans_plane_generic", nlmeans_generic_kernel<uint8_t>, dim3(tiles), dim3(GW * GH), shmem, dj, nj, n, max_rh, L.pre);
                 else
-                    HBHIP_LAUNCH(ctx, "nlmeans_plane_generic", nlmeans_generic_kernel<uint16_t>, dim3(tiles), dim3(GW * GH), shmem, dj, nj, n, max_rh, (int)pre);
+                    HBHIP_LAUNCH(ctx, "nlmeans_plane_generic", nlmeans_generic_kernel<uint16_t>, dim3(tiles), dim3(GW * GH), shmem, dj, nj, n, max_rh, L.pre);
                 HBHIP_CHECK(ctx, hipGetLastError());
                 continue;
             }
-            const int cmp_rows = TH + 2 * (nh + max_rh);
+            const int cmp_rows = L.cmp_rows;
             dim3 grid(tiles), block(TXN * TYN);
-            // tiles: 32 lanes + rq dwords of search halo either side (+1 for the alignbyte high
-            // word), pitch = 4 (mod 8) dwords
-            const int rq = (max_rh + 3) / 4;
-            const bool wide = in_geo.bps == 2;                 // 16-bit samples: 2 pixels per tile dword
-            const int cpd = wide ? (rq <= 2 ? 76 : 84) : (rq <= 1 ? 36 : 44);
-            // the pairs of frame 0 share their patch distances (FAST 3) when every plane of the launch searches 3 x 3
-            // (patch sizes up to 7: the mirrored index of a lane's edge pixel comes from the neighbouring lane's edge pixel,
-            // whose own window must not reach past ITS neighbour - the outer lanes of a tile row have none)
-            const bool sym = fast && fast_int && !pre && all_rh1 && n <= 7;
-            // (what the kernels size their staging registers by)
-            if (cmp_rows > nlm_max_rows(n, sym, cpd == (wide ? 76 : 36) ? (wide ? 8 : 4) : NLM_BORDER))
-                return ctx->fail(hipErrorInvalidValue, "nlmeans: tile taller than its kernel stages");
-            size_t shmem = sizeof(uint32_t) * (pre ? 4 : 2) * (cpd * cmp_rows + 4) + 512;
-            // (16-bit samples: NLM16_SYM_PAIRS of the four pairs share - the stash of three fits three workgroups on a CU)
-            const int sym_slots = wide ? NLM16_SYM_PAIRS : 4;
-            if (sym) shmem = 512 + sizeof(uint32_t) * ((size_t)(cpd * cmp_rows + 4) + std::max<size_t>(cpd * cmp_rows + 4, (size_t)sym_slots * (RY + 1) * TXN * TYN));
-            // the widest search ranges need more than the default 64 KB of dynamic LDS
+            const int rq = (max_rh + 3) / 4;                   // dwords of search halo either side of a tile row
+            // The launch takes the kernel whose entry of NLM_FORMS has the plan's fields.
+            // The widest search ranges need more than the default 64 KB of dynamic LDS.
             // The integer-index kernels (FAST >= 2) read the weight table at LDS address 0: true when the kernel has no static
             // LDS in front of its dynamic block.  Asked of the code object once per instantiation; a kernel that fails it is
             // refused here (the filter reports an error) rather than launched.
-#define NLM_LAUNCH(KERNEL) do { \
+            bool launched = false;
+#define NLM_TRY(KERNEL, NN, WIDE, FF, CC, PP, SP, OO) \
+            if (!launched && n == NN && L.wide == WIDE && L.fast == FF && L.pitch == CC && L.pre == PP && L.pairs == SP && L.origin_f32 == OO) \
+            { \
                 static const bool lds_free = nlm_no_static_lds((const void *)KERNEL); \
-                if ((fast && fast_int) && !lds_free) return ctx->fail(hipErrorInvalidValue, "nlmeans: kernel has static LDS in front of its table"); \
+                if (FF >= 2 && !lds_free) return ctx->fail(hipErrorInvalidValue, "nlmeans: kernel has static LDS in front of its table"); \
                 if (shmem > 65536) \
                     HBHIP_CHECK(ctx, hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem)); \
-                HBHIP_LAUNCH(ctx, kname, (KERNEL), grid, block, shmem, dj, nj, cmp_rows, rq, tc); \
-            } while (0)
-#define NLM_GO(NN, FF, CC, PP) NLM_LAUNCH((nlmeans_lanes_kernel<NN, FF, CC, PP>))
-#define NLM_SYM(NN, CC) do { if (all_org1 && NLM_ORIGIN_F32) NLM_LAUNCH((nlmeans_lanes_kernel<NN, (NN <= 7 ? 3 : 2), CC, false, true>)); \
-                             else NLM_GO(NN, (NN <= 7 ? 3 : 2), CC, false); } while (0)
-#define NLM_PRE(NN, FF, CC) do { if (pre) NLM_GO(NN, FF, CC, true); else NLM_GO(NN, FF, CC, false); } while (0)
-#define NLM_16P(NN, FF, PP) do { if (cpd == 76) NLM_LAUNCH((nlmeans_lanes16_kernel<NN, FF, 76, PP>)); \
-                                else NLM_LAUNCH((nlmeans_lanes16_kernel<NN, FF, 84, PP>)); } while (0)
-#define NLM_16(NN, FF) do { if (pre) NLM_16P(NN, FF, true); else NLM_16P(NN, FF, false); } while (0)
-#define NLM_16S(NN) NLM_LAUNCH((nlmeans_lanes16_kernel<NN, (NN <= 7 ? 3 : 2), 76, false, NLM16_SYM_PAIRS>))
-#define NLM_VAR(NN) do { const char *kname = "nlmeans_plane_n" #NN; \
-                     if (wide) { if (sym && NN <= 7 && cpd == 76) NLM_16S(NN); else if (fast && fast_int) NLM_16(NN, 2); else if (fast) NLM_16(NN, 1); else NLM_16(NN, 0); } \
-                     else if (cpd == 36) { if (sym && NN <= 7) NLM_SYM(NN, 36); else if (fast && fast_int) NLM_PRE(NN, 2, 36); else if (fast) NLM_PRE(NN, 1, 36); else NLM_PRE(NN, 0, 36); } \
-                     else { if (sym && NN <= 7) NLM_SYM(NN, 44); else if (fast && fast_int) NLM_PRE(NN, 2, 44); else if (fast) NLM_PRE(NN, 1, 44); else NLM_PRE(NN, 0, 44); } } while (0)
-            switch (n)
-            {
-                case 3: NLM_VAR(3); break;
-                case 5: NLM_VAR(5); break;
-                case 7: NLM_VAR(7); break;
-                case 9: NLM_VAR(9); break;
+                HBHIP_LAUNCH(ctx, "nlmeans_plane_n" #NN, KERNEL, grid, block, shmem, dj, nj, cmp_rows, rq, tc); \
+                launched = true; \
             }
-#undef NLM_VAR
-#undef NLM_16
-#undef NLM_16P
-#undef NLM_16S
-#undef NLM_PRE
-#undef NLM_SYM
-#undef NLM_GO
-#undef NLM_LAUNCH
+            NLM_FORMS(NLM_TRY)
+#undef NLM_TRY
+            if (!launched) return ctx->fail(hipErrorInvalidValue, "nlmeans: no kernel of the planned form");
             HBHIP_CHECK(ctx, hipGetLastError());
         }
 
@@ -1879,6 +1945,45 @@ extern "C" int hbhip_nlmeans_create(hbhip_ctx *ctx, const hbhip_nlmeans_params *
     }
     *out = f;
     return HBHIP_OK;
+}
+
+extern "C" int hbhip_nlmeans_plan(const hbhip_nlmeans_params *p, int width, int height, int depth,
+                                  int log2_chroma_w, int log2_chroma_h, hbhip_nlmeans_launch launches[3], int *n)
+{
+    if (!p || !launches || !n) return HBHIP_ERR_ARG;
+    *n = 0;
+    if (depth != 8 && depth != 10 && depth != 12) return HBHIP_ERR_UNSUPPORTED;
+    if (width < 1 || height < 1) return HBHIP_ERR_ARG;
+    PicGeometry geo;
+    geo.set(width, height, depth, log2_chroma_w, log2_chroma_h);
+    NlmPlan plan;
+    if (const int rc = nlm_plan(*p, geo, nlm_force_generic(), plan)) return rc;
+    for (int i = 0; i < plan.n; i++) launches[i] = plan.launch[i];
+    *n = plan.n;
+    return HBHIP_OK;
+}
+
+extern "C" int hbhip_nlmeans_forms(hbhip_nlmeans_launch *forms, int cap)
+{
+    int count = 0;
+    auto add = [&](int patch, int generic, int wide, int fast, int pitch, int pre, int pairs, int origin_f32)
+    {
+        if (forms && count < cap)
+        {
+            hbhip_nlmeans_launch &f = forms[count];
+            memset(&f, 0, sizeof(f));
+            f.patch_size = patch; f.generic = generic; f.wide = wide; f.fast = fast; f.pitch = pitch;
+            f.pre = pre; f.pairs = pairs; f.origin_f32 = origin_f32;
+            f.tile_w = generic ? GW : LTW; f.tile_h = generic ? GH : TH;
+        }
+        count++;
+    };
+#define NLM_LIST(KERNEL, NN, WIDE, FF, CC, PP, SP, OO) add(NN, 0, WIDE, FF, CC, PP, SP, OO);
+    NLM_FORMS(NLM_LIST)
+#undef NLM_LIST
+    add(0, 1, 0, 0, 0, 0, 0, 0);        // nlmeans_generic_kernel<uint8_t>: patch size and prefilter are kernel arguments
+    add(0, 1, 1, 0, 0, 0, 0, 0);        // nlmeans_generic_kernel<uint16_t>
+    return count;
 }
 
 extern "C" int hbhip_nlmeans_set_batch(hbhip_filter *f, int frames)

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "hbhip_filter_process_dev", "hbhip_filter_submit_async", "hbhip_filter_wait", "hbhip_filter_inflight", "hbhip_filter_flush", "hbhip_filter_pending", "hbhip_filter_defer", "hbhip_filter_kick", "hbhip_filter_destroy",
     "hbhip_filter_out_geometry",
     "hbhip_chain_create", "hbhip_chain_process_dev", "hbhip_chain_flush_dev", "hbhip_chain_pending", "hbhip_chain_sync", "hbhip_chain_destroy",
-    "hbhip_nlmeans_create", "hbhip_nlmeans_set_batch",
+    "hbhip_nlmeans_create", "hbhip_nlmeans_set_batch", "hbhip_nlmeans_plan", "hbhip_nlmeans_forms",
     "hbhip_lapsharp_create", "hbhip_unsharp_create", "hbhip_chroma_smooth_create",
     "hbhip_hqdn3d_create", "hbhip_decomb_create", "hbhip_decomb_push", "hbhip_decomb_push_dev", "hbhip_decomb_push_frame", "hbhip_decomb_debug_eedi_plane",
     "hbhip_comb_detect_create", "hbhip_comb_detect_set_gamma_lut", "hbhip_comb_detect_store",
@@ -86,6 +86,16 @@ class NLMeansParams(C.Structure):
                 ("nframes", C.c_int * 3), ("prefilter", C.c_int * 3),
                 ("exptable", (C.c_float * 128) * 3), ("weight_fact_table", C.c_float * 3),
                 ("diff_max", C.c_int * 3)]
+
+
+class NLMeansLaunch(C.Structure):
+    """hbhip_nlmeans_launch: the kernel form one launch of a frame takes (hbhip_nlmeans_plan)"""
+    _fields_ = [(n, C.c_int) for n in ("patch_size", "planes", "generic", "wide", "fast", "pitch", "pre", "pairs", "origin_f32",
+                                       "max_rh", "cmp_rows", "job_arith", "tile_w", "tile_h")] + \
+               [("lds_bytes", C.c_uint), ("diff_cap", C.c_int * 3), ("imul4", C.c_uint * 3), ("ishift", C.c_int * 3)]
+
+    def as_dict(self):
+        return {n: (getattr(self, n) if t in (C.c_int, C.c_uint) else list(getattr(self, n))) for n, t in self._fields_}
 
 
 class DeblockParams(C.Structure):
@@ -169,6 +179,8 @@ def lib() -> C.CDLL:
         L.hbhip_nlmeans_create.argtypes = [C.c_void_p, C.POINTER(NLMeansParams), C.c_int, C.c_int,
                                            C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
         L.hbhip_nlmeans_set_batch.argtypes = [C.c_void_p, C.c_int]
+        L.hbhip_nlmeans_plan.argtypes = [C.POINTER(NLMeansParams)] + [C.c_int] * 5 + [C.POINTER(NLMeansLaunch), C.POINTER(C.c_int)]
+        L.hbhip_nlmeans_forms.argtypes = [C.POINTER(NLMeansLaunch), C.c_int]
         L.hbhip_chain_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]
         L.hbhip_chain_process_dev.argtypes = [C.c_void_p, C.POINTER(DevFrame), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                               C.c_int, C.c_int64, C.POINTER(DevFrame), C.POINTER(C.c_int64), C.c_int,
@@ -583,6 +595,26 @@ class Chain:
 
 NLMEANS_MEDIUM = ("y-strength=6:y-origin-tune=1:y-patch-size=7:y-range=3:y-frame-count=2:y-prefilter=0:"
                   "cb-strength=6:cb-origin-tune=1:cb-patch-size=7:cb-range=3:cb-frame-count=2:cb-prefilter=0")
+
+
+def nlmeans_plan(settings: str, width: int, height: int, depth: int = 8, log2_chroma_w: int = 1, log2_chroma_h: int = 1):
+    """The launches a frame of this geometry takes under `settings`, as dicts of hbhip_nlmeans_launch's fields (no
+    device needed); HipError where hbhip_nlmeans_create would decline."""
+    par = NLMeansParams()
+    filters().hbhip_nlmeans_params_from_settings(settings.encode(), depth, C.byref(par))
+    out = (NLMeansLaunch * 3)()
+    n = C.c_int(0)
+    check(lib().hbhip_nlmeans_plan(C.byref(par), width, height, depth, log2_chroma_w, log2_chroma_h, out, C.byref(n)),
+          None, "hbhip_nlmeans_plan")
+    return [out[i].as_dict() for i in range(n.value)]
+
+
+def nlmeans_forms():
+    """Every kernel instantiation the NLMeans dispatcher holds (hbhip_nlmeans_forms), as dicts"""
+    n = lib().hbhip_nlmeans_forms(None, 0)
+    out = (NLMeansLaunch * n)()
+    assert lib().hbhip_nlmeans_forms(out, n) == n
+    return [out[i].as_dict() for i in range(n)]
 
 
 def nlmeans_device_filter(ctx: Ctx, settings: str, width: int, height: int, batch: int = 1,

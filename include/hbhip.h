@@ -312,6 +312,43 @@ int hbhip_nlmeans_create(hbhip_ctx *ctx, const hbhip_nlmeans_params *p,
 /* Max frames processed per kernel launch when several are queued (default 8). */
 int hbhip_nlmeans_set_batch(hbhip_filter *f, int frames);
 
+/* What a frame's launches are: one per distinct patch size among the denoised planes, in ascending patch size.  A
+ * launch runs ONE kernel form for all its planes - the widest tile pitch and the most general index form any of them
+ * needs.  hbhip_nlmeans_plan() is what the filter itself dispatches from (csrc/nlmeans.hip); it needs no device and
+ * no context. */
+typedef struct hbhip_nlmeans_launch
+{
+    int      patch_size;    /* 0 in the generic kernels' entries of hbhip_nlmeans_forms() (any size, a kernel argument) */
+    int      planes;        /* bit c: plane c is filtered by this launch */
+    int      generic;       /* nlmeans_generic_kernel: every patch size but 3 / 5 / 7 / 9; the fields down to origin_f32 are 0 */
+    int      wide;          /* the 16-bit sample kernels (depth 10 / 12) */
+    int      fast;          /* the table-index form: 0 gated float, 1 float clamp, 2 integer multiply-high, 3 paired displacements */
+    int      pitch;         /* tile pitch in dwords: 36 | 44 (bytes), 76 | 84 (16-bit samples) */
+    int      pre;           /* prefiltered compare planes: twice the staged tiles */
+    int      pairs;         /* fast 3: how many of frame 0's four displacement pairs share their distances, else 0 */
+    int      origin_f32;    /* fast 3 at 8 bits: the origin term in single precision (every origin_tune of the launch is 1) */
+    int      max_rh;        /* the largest search half-range of the launch */
+    int      cmp_rows;      /* rows of a staged tile (0: generic) */
+    int      job_arith;     /* a tile's job by arithmetic (1) or by a search of the job table (0) */
+    int      tile_w, tile_h; /* output pixels of a workgroup's tile */
+    unsigned lds_bytes;     /* dynamic LDS of the launch */
+    /* the table-index constants of each plane of the launch (-1 / 0 / 0 for a plane that is not in it): the smallest patch
+     * distance whose index is 127, or -1 where the table does not allow the clamp (then the launch is form 0); the
+     * multiplier of the integer index, or 0 where there is none, and its shift (an 8-bit launch with a multiplier that
+     * needs a shift, or without one, is form 1) */
+    int      diff_cap[3];
+    unsigned imul4[3];
+    int      ishift[3];
+} hbhip_nlmeans_launch;
+
+/* The launches of one frame for these parameters and this geometry, at most 3; *n = how many.  Returns what
+ * hbhip_nlmeans_create() would: HBHIP_ERR_ARG / HBHIP_ERR_UNSUPPORTED for parameters or planes the filter declines. */
+int hbhip_nlmeans_plan(const hbhip_nlmeans_params *p, int width, int height, int depth,
+                       int log2_chroma_w, int log2_chroma_h, hbhip_nlmeans_launch launches[3], int *n);
+/* Every kernel instantiation the dispatcher holds, as the fields of a launch that select it (patch_size ... origin_f32);
+ * writes at most `cap` entries, returns how many there are. */
+int hbhip_nlmeans_forms(hbhip_nlmeans_launch *forms, int cap);
+
 /* ---- Lapsharp  (replaces lapsharp_8, lapsharp.c:125-182) ------------------------ */
 typedef struct hbhip_lapsharp_params
 {
