@@ -1292,6 +1292,42 @@ int hbhip_frame_download_widen(hbhip_frame *fr, const hbhip_host_biplanar *dst)
     return rc != HBHIP_OK ? rc : hbhip_frame_download_wait(fr, token);
 }
 
+// A packed 32-bit RGB host picture of an 8-bit 4:2:0 frame (rgb_pack.hip): the pack into the download staging buffer and
+// the D2H copy behind it, ordered and finished like the biplanar download.  The copy moves 4 * width bytes a row and
+// nothing of the caller's row padding: one block where the caller's rows and the staging buffer's are both exactly that long.
+int hbhip_frame_download_rgb32_async(hbhip_frame *fr, uint8_t *dst, int stride, int order, int matrix, int full_range, void **token)
+{
+    if (!fr || !dst || !token) return HBHIP_ERR_ARG;
+    *token = nullptr;
+    hbhip_ctx *ctx = fr->ctx;
+    if (fr->lcw != 1 || fr->lch != 1 || fr->depth != 8 || fr->width < 2 || fr->height < 2 || (fr->width & 1) || (fr->height & 1) ||
+        !hbhip_rgb32_matrix_ok(matrix))
+        return HBHIP_ERR_UNSUPPORTED;
+    const int row = 4 * fr->width, pitch = hbhip_rgb32_pitch(fr->width), rows = fr->height;
+    if (stride < row || order < HBHIP_RGB32_BGRA || order > HBHIP_RGB32_ABGR) return HBHIP_ERR_ARG;
+    (void)hipSetDevice(ctx->device);
+    const int rc = drain_frame(fr, "download (rgb32)", [&](hipStream_t down) {
+        std::lock_guard<std::mutex> lk(ctx->bi_lock[1]);
+        uint8_t *stage = bi_stage(ctx, 1, (size_t)pitch * rows, down);
+        if (!stage) return ctx->fail(hipErrorOutOfMemory, "download (rgb32)");
+        const int launched = hbhip_rgb32_pack_launch(ctx, down, stage, pitch, fr, order, matrix, full_range);
+        if (launched != HBHIP_OK) return launched;
+        const hipError_t e = stride == row && pitch == row
+            ? hipMemcpyAsync(dst, stage, (size_t)row * rows, hipMemcpyDeviceToHost, down)
+            : hipMemcpy2DAsync(dst, stride, stage, pitch, row, rows, hipMemcpyDeviceToHost, down);
+        return hip_rc(ctx, e, "download (rgb32)");
+    }, token);
+    if (rc == HBHIP_OK) ctx->bus_d2h += (uint64_t)row * rows;
+    return rc;
+}
+
+int hbhip_frame_download_rgb32(hbhip_frame *fr, uint8_t *dst, int stride, int order, int matrix, int full_range)
+{
+    void *token = nullptr;
+    const int rc = hbhip_frame_download_rgb32_async(fr, dst, stride, order, matrix, full_range, &token);
+    return rc != HBHIP_OK ? rc : hbhip_frame_download_wait(fr, token);
+}
+
 // ---- device surfaces (NV12 / P010LE pictures in HBM) at the two ends of a run -----------------------------------------
 // No staging buffer and no bi_lock: the repack kernel reads or writes the surface where it lies.  The same ordering rule:
 // the split runs on the upload stream behind the surface's contents and is the frame's ready mark, the merge on the

@@ -334,6 +334,13 @@ int hbhip_bi_surface_launch(hbhip_ctx *ctx, hipStream_t stream, bool merge, cons
 // out for depth 10, or into a depth-10 surface of the frame's size (the caller has checked both), on `stream`
 int hbhip_bi_widen_repack_launch(hbhip_ctx *ctx, hipStream_t stream, uint8_t *stage, const hbhip_frame *fr);
 int hbhip_bi_widen_surface_launch(hbhip_ctx *ctx, hipStream_t stream, const hbhip_surface *s, const hbhip_frame *fr);
+// the packed 32-bit RGB repack (rgb_pack.hip): the 8-bit planar 4:2:0 frame `fr` of even size as HBHIP_RGB32_* `order` into
+// `dst`, rows `dpitch` apart (a multiple of 16; hbhip_rgb32_pitch: the staging buffer's), on `stream`; 4 * width bytes of each
+// row are written.  hbhip_rgb32_matrix_ok: an HB_COLR_MAT_* number with a coefficient row (the caller has checked the rest)
+bool hbhip_rgb32_matrix_ok(int matrix);
+int hbhip_rgb32_pitch(int width);
+int hbhip_rgb32_pack_launch(hbhip_ctx *ctx, hipStream_t stream, uint8_t *dst, int dpitch, const hbhip_frame *fr, int order,
+                            int matrix, int full_range);
 
 // Geometry of a planar YUV picture.
 struct PicGeometry

@@ -26,6 +26,9 @@ PIX_FMT = {("2x2", 8): 0, ("2x1", 8): 4, ("1x1", 8): 5, ("2x2", 10): 62, ("2x1",
 # samples are uint16 with their 10 bits in the high end
 AV_PIX_FMT_NV12, AV_PIX_FMT_P010LE = 23, 158
 BIPLANAR = (AV_PIX_FMT_NV12, AV_PIX_FMT_P010LE)
+# the four packed 32-bit RGB orders with alpha, FFmpeg's numbers: what hb_get_preview asks `format` for
+RGB32_BY_NAME = {"argb": 25, "rgba": 26, "abgr": 27, "bgra": 28}
+RGB32 = tuple(RGB32_BY_NAME.values())
 
 HB_COMB_NONE, HB_COMB_LIGHT, HB_COMB_HEAVY = 0, 1, 2
 
@@ -220,7 +223,8 @@ class Chain:
         self._rt.hbh_chain_pop(self._h, ptrs, strides)
         bps = 2 if info.fmt in (62, 123, 64, 68, 127, 131, AV_PIX_FMT_P010LE) else 1
         # plane 1 of a biplanar frame holds two samples, Cb and Cr, per chroma position
-        per = [2 if info.fmt in BIPLANAR and p == 1 else 1 for p in range(info.nplanes)]
+        # ... and the one plane of a packed 32-bit RGB picture four bytes a pixel
+        per = [4 if info.fmt in RGB32 else 2 if info.fmt in BIPLANAR and p == 1 else 1 for p in range(info.nplanes)]
         planes = tuple(a[:, : info.plane_width[p] * bps * per[p]] for p, a in enumerate(arrs))
         if bps == 2:                      # 10 / 12-bit samples in 16-bit containers
             planes = tuple(np.ascontiguousarray(p).view(np.uint16) for p in planes)
@@ -337,6 +341,63 @@ def run_job(filters, frames, flags: int = 0x10, pix_fmt: int = AV_PIX_FMT_YUV420
         ch.push_eof()
         out += ch.drain()
     return names, out
+
+
+class Preview(Job):
+    """A preview's filters built the way hb_get_preview builds them, with the hook of INTEGRATION.md 2b (hbh_preview_open): the
+    job's filters by id, the display rescale for `par`, `format=<pix_fmt>`; yuv420p frames in."""
+
+    def __init__(self, filters, width: int, height: int, par=(1, 1), pix_fmt="bgra", rescale: bool = True, use_hip: bool = True):
+        rt = self._rt = runtime()
+        rt.hbh_preview_open.restype = C.c_void_p
+        rt.hbh_preview_open.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_char_p)] + [C.c_int] * 5 + [C.c_char_p, C.c_int]
+        rt.hbh_chain_stage.restype = C.c_void_p
+        rt.hbh_chain_stage.argtypes = [C.c_void_p, C.c_int]
+        n = len(filters)
+        ids = (C.c_int * max(n, 1))(*[f[0] for f in filters])
+        settings = (C.c_char_p * max(n, 1))(*[(f[1] or "").encode() for f in filters])
+        self._keep = (ids, settings)
+        self.width, self.height = width, height
+        self._h = rt.hbh_preview_open(n, ids, settings, width, height, par[0], par[1], int(rescale),
+                                      pix_fmt.encode() if pix_fmt else None, int(use_hip))
+        if not self._h:
+            raise RuntimeError(f"preview init failed: {filters}")
+        self.eof = False
+
+    def entries(self):
+        """the list as initialised: [(name, {settings})]"""
+        out, i = [], 0
+        while True:
+            p = self._rt.hbh_chain_stage(self._h, i)
+            if not p:
+                return out
+            f = _FilterObject.from_address(p)
+            settings, d = {}, f.settings
+            e = C.cast(d, C.POINTER(C.c_void_p))[0] if d else None            # hbhip_dict_s { kv *head, *tail }
+            while e:
+                k, v, e = C.cast(e, C.POINTER(C.c_void_p))[0:3]                # kv_s { char *k, *v; kv *next }
+                settings[C.cast(k, C.c_char_p).value.decode()] = C.cast(v, C.c_char_p).value.decode()
+            out.append((f.name.decode(), settings))
+            i += 1
+
+
+def preview_run(filters, planes, par=(1, 1), pix_fmt="bgra", rescale: bool = True, use_hip: bool = True, run: bool = True):
+    """One yuv420p picture (Y, Cb, Cr) through a preview's list; returns ([(name, {settings})] of the list as initialised,
+    the picture that comes out - (height, width, 4) uint8 for a packed RGB format, else the planes - or None when not `run`)."""
+    h, w = planes[0].shape
+    with Preview(filters, w, h, par, pix_fmt, rescale, use_hip) as pv:
+        entries = pv.entries()
+        if not run:
+            return entries, None
+        pv.push(planes)
+        pv.push_eof()
+        out = pv.drain()
+    if len(out) != 1:
+        raise RuntimeError(f"preview: {len(out)} pictures came out of {entries}")
+    got = out[0].planes
+    if len(got) == 1 and got[0].shape[1] == 4 * out[0].width:
+        return entries, np.ascontiguousarray(got[0]).reshape(out[0].height, out[0].width, 4)
+    return entries, got
 
 
 class _FilterObject(C.Structure):

@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "hbhip_surface_alloc", "hbhip_surface_wrap", "hbhip_surface_retain", "hbhip_surface_release", "hbhip_surface_describe", "hbhip_surface_set_ready_event",
     "hbhip_frame_import_surface", "hbhip_frame_import_surface_async", "hbhip_frame_export_surface", "hbhip_frame_export_surface_async", "hbhip_ctx_bus_bytes",
     "hbhip_frame_download_widen", "hbhip_frame_download_widen_async", "hbhip_frame_export_surface_widen", "hbhip_frame_export_surface_widen_async",
+    "hbhip_frame_download_rgb32", "hbhip_frame_download_rgb32_async",
     "hbhip_filter_use_frames", "hbhip_filter_push_frame", "hbhip_filter_pull_frame", "hbhip_filter_push", "hbhip_filter_push_dev", "hbhip_filter_pull", "hbhip_filter_pull_dev",
     "hbhip_filter_process_dev", "hbhip_filter_submit_async", "hbhip_filter_wait", "hbhip_filter_inflight", "hbhip_filter_flush", "hbhip_filter_pending", "hbhip_filter_defer", "hbhip_filter_kick", "hbhip_filter_destroy",
     "hbhip_filter_out_geometry",
@@ -126,6 +127,7 @@ class ScanResult(C.Structure):
         return (self.top, self.bottom, self.left, self.right, self.recorded, tuple(self.cc), self.average_cc, self.combed)
 
 
+RGB32_ORDERS = ("bgra", "rgba", "argb", "abgr")      #: HBHIP_RGB32_*, by number
 SCAN_INFLIGHT_MAX = 32      #: HBHIP_SCAN_INFLIGHT_MAX
 SCAN_RECORD_BYTES = 48      #: HBHIP_SCAN_RECORD_BYTES: what a scanned picture sends over the bus
 JPEG_INFLIGHT_MAX = 4       #: HBHIP_JPEG_INFLIGHT_MAX
@@ -203,6 +205,8 @@ def lib() -> C.CDLL:
             getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(HostBiplanar)]
         for fn in ("hbhip_frame_upload_biplanar_async", "hbhip_frame_download_biplanar_async", "hbhip_frame_download_widen_async"):
             getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(HostBiplanar), C.POINTER(C.c_void_p)]
+        L.hbhip_frame_download_rgb32.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4
+        L.hbhip_frame_download_rgb32_async.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.POINTER(C.c_void_p)]
         L.hbhip_frame_download_wait.argtypes = [C.c_void_p, C.c_void_p]
         L.hbhip_ctx_upload_done.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.hbhip_surface_alloc.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_void_p)]
@@ -377,6 +381,15 @@ class Frame:
     def download(self):
         out = self.planes()
         check(lib().hbhip_frame_download(self.h, C.byref(host_frame(out))), self.ctx.h, "frame_download")
+        return out
+
+    def download_rgb32(self, order="bgra", matrix=1, full_range=False):
+        """the 8-bit 4:2:0 frame as a packed 32-bit RGB picture, (height, width, 4) uint8 in memory order"""
+        import numpy as np
+        w, h = self.shape[:2]
+        out = np.zeros((h, w, 4), np.uint8)
+        check(lib().hbhip_frame_download_rgb32(self.h, out.ctypes.data, 4 * w, RGB32_ORDERS.index(order), matrix, int(full_range)),
+              self.ctx.h, "frame_download_rgb32")
         return out
 
     def import_surface(self, surface: "Surface"):

@@ -228,6 +228,9 @@ static int rotate_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
  *     step passes through.
  *   - `format=p010le` on 8-bit 4:2:0 frames, when hip_common.c has marked the entry with HBHIP_FORMAT_WIDEN_STEP: the frames
  *     pass through as they are, yuv420p, and the run's download adapter widens them inside its repack.
+ *   - `format=bgra | rgba | argb | abgr` on 8-bit 4:2:0 frames of even size, when hip_common.c has marked the entry with
+ *     HBHIP_FORMAT_RGB_STEP (hb_get_preview's list, hb.c:945-959): the frames pass through likewise and the download adapter
+ *     makes the packed picture inside its repack.
  *   - planar YUV chroma UP-sampling, 4:2:0 -> 4:2:2, 4:2:2 -> 4:4:4, 4:2:0 -> 4:4:4, at equal or HIGHER depth
  *     (format_upsample_kernel), when hip_common.c has marked the entry with HBHIP_FORMAT_UP_STEP, i.e. behind another
  *     drop-in of a device-resident run.  The reference does ask for it: hb_get_best_pix_fmt chooses the pipeline's format
@@ -246,7 +249,7 @@ static int rotate_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
  * Any other target makes init() fail, which keeps the CPU filter (work.c:1861-1868): more chroma samples than the
  * stream has, or fewer at a higher depth, where nobody marked the entry (a lone `format` on host frames would pay a
  * round trip over the bus for a cheap filter), semi-planar targets that nobody marked (a lone `format=nv12` has no
- * adapter to repack for it) or above the stream's depth on 4:2:2 / 4:4:4 frames, RGB, a chroma plane too small for
+ * adapter to repack for it) or above the stream's depth on 4:2:2 / 4:4:4 frames, RGB (the four packed orders where nobody marked the entry, every other RGB target always), a chroma plane too small for
  * swscale's taps (nine down, five up). */
 static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init);
 static int format_hip_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_buffer_t **buf_out);
@@ -286,6 +289,19 @@ static int format_hip_init(hb_filter_object_t *filter, hb_filter_init_t *init)
     hb_dict_extract_bool(&widen_step, filter->settings, HBHIP_FORMAT_WIDEN_STEP);
     if (widen_step && pv->s.dev_io && dst_fmt == HBHIP_PIX_FMT_P010LE && init->pix_fmt == AV_PIX_FMT_YUV420P &&
         init->geometry.width >= 2 && init->geometry.height >= 2)
+    {
+        pv->s.output = *init;
+        return 0;
+    }
+    /* its mark on a `format=bgra | rgba | argb | abgr` entry inside a run of 8-bit 4:2:0 frames (hb_get_preview's list): nothing
+     * to do here either, the download adapter makes the packed picture inside its repack.  Declined: a frame that is not
+     * yuv420p of even size (swscale leaves its unscaled path at an odd height; the repack takes neither).  Without the mark
+     * every RGB target is declined below, as it always was. */
+    int rgb_step = 0;
+    hb_dict_extract_bool(&rgb_step, filter->settings, HBHIP_FORMAT_RGB_STEP);
+    if (rgb_step && pv->s.dev_io && hbhip_host_rgb32_order(dst_fmt) >= 0 && init->pix_fmt == AV_PIX_FMT_YUV420P &&
+        hbhip_host_rgb32_matrix_ok(init->color_matrix) &&
+        init->geometry.width >= 2 && init->geometry.height >= 2 && !(init->geometry.width & 1) && !(init->geometry.height & 1))
     {
         pv->s.output = *init;
         return 0;

@@ -302,6 +302,132 @@ hbh_chain_t *hbh_job_open(int nfilters, const int *ids, const char *const *setti
     return c;
 }
 
+/* A preview's filters the way hb_get_preview prepares them (hb.c:801-1063) WITH the hook of INTEGRATION.md 2b: the list is
+ * the job's (by id, as above), the display rescale - a crop/scale entry that starts without its sizes - and
+ * `format=<pix_fmt_name>` are added in front of the init loop, job->input_pix_fmt says yuv420p (what hb_read_preview hands
+ * over), hb_hip_setup_hw_filters swaps and brackets, and then the loop runs: its switch keeps the ids hb.c:850-861 keeps,
+ * HB_FILTER_FORMAT and the two adapters, and removes the rest; the rescale entry gets its width / height from the running
+ * geometry and `par` when the loop reaches it (:917-933); a failing init goes through hb_hip_filter_init_failed as in do_job.
+ * rescale = 0 / pix_fmt_name = NULL leave the two entries out, as hb_get_preview's arguments do.  One yuv420p frame and the
+ * EOF go in (hbh_chain_push, hbh_chain_push_eof), one picture comes out. */
+hbh_chain_t *hbh_preview_open(int nfilters, const int *ids, const char *const *settings, int width, int height,
+                              int par_num, int par_den, int rescale, const char *pix_fmt_name, int use_hip)
+{
+    hbh_chain_t *c = calloc(1, sizeof(*c));
+    if (c == NULL) return NULL;
+    hb_job_t *pjob = calloc(1, sizeof(*pjob));
+    if (pjob == NULL) { free(c); return NULL; }
+    c->job = pjob;
+    pjob->hw_pix_fmt = AV_PIX_FMT_NONE;
+    pjob->hw_device_index = g_job_device;
+    pjob->list_filter = hb_list_init();
+    for (int i = 0; i < nfilters; i++)
+    {
+        hb_filter_object_t *f = hb_filter_init(ids[i]);
+        if (f == NULL)
+        {
+            hb_error("hbh_preview_open: no filter registered for id %d", ids[i]);
+            continue;
+        }
+        hb_dict_t *d = hbhip_dict_from_string(settings && settings[i] ? settings[i] : "");
+        hb_add_filter_dict(pjob->list_filter, f, d);
+        hb_dict_free(&d);
+    }
+    /* the hook: both entries in front of the loop (hb_list_add: at the end, whatever their ids), the rescale without sizes */
+    hb_filter_object_t *f;
+    if (rescale && (f = hb_filter_init(HB_FILTER_CROP_SCALE)) != NULL)
+    {
+        hb_dict_free(&f->settings);
+        f->settings = hb_dict_init();
+        hb_list_add(pjob->list_filter, f);
+    }
+    if (pix_fmt_name != NULL && (f = hb_filter_init(HB_FILTER_FORMAT)) != NULL)
+    {
+        hb_dict_free(&f->settings);
+        f->settings = hb_dict_init();
+        hbhip_dict_set(f->settings, "format", pix_fmt_name);
+        hb_list_add(pjob->list_filter, f);
+    }
+    pjob->input_pix_fmt = AV_PIX_FMT_YUV420P;
+    if (use_hip && g_hip_setup != NULL) g_hip_setup(pjob);
+
+    hb_filter_init_t init;
+    source_init(&init, AV_PIX_FMT_YUV420P, width, height, 30000, 1001);
+    init.job = pjob;
+    c->init_in = init;
+    for (int i = 0; i < hb_list_count(pjob->list_filter);)
+    {
+        f = hb_list_item(pjob->list_filter, i);
+        f->private_data = NULL;
+        int keep = 0;
+        switch (f->id)
+        {
+            case HB_FILTER_AVFILTER: case HB_FILTER_CROP_SCALE: case HB_FILTER_PAD: case HB_FILTER_ROTATE:
+            case HB_FILTER_COLORSPACE: case HB_FILTER_DECOMB: case HB_FILTER_DETELECINE: case HB_FILTER_YADIF:
+            case HB_FILTER_GRAYSCALE:
+            case HB_FILTER_FORMAT: case HB_FILTER_HIP_UPLOAD: case HB_FILTER_HIP_DOWNLOAD:       /* the hook's three */
+                keep = 1;
+                break;
+            default:
+                break;
+        }
+        if (!keep)
+        {
+            hb_list_rem(pjob->list_filter, f);
+            hb_filter_close(&f);
+            continue;
+        }
+        int has_width = 0, unused;
+        if (f->id == HB_FILTER_CROP_SCALE && f->settings != NULL) has_width = hb_dict_extract_int(&unused, f->settings, "width");
+        if (rescale && f->id == HB_FILTER_CROP_SCALE && f->settings != NULL && !has_width)
+        {
+            /* the display rescale (:917-933): adjusts for pixel aspect */
+            int sw = init.geometry.width, sh = init.geometry.height;
+            char num[16];
+            if (par_num >= par_den) sw = sw * par_num / par_den;
+            else                    sh = sh * par_den / par_num;
+            snprintf(num, sizeof(num), "%d", sw);
+            hbhip_dict_set(f->settings, "width", num);
+            snprintf(num, sizeof(num), "%d", sh);
+            hbhip_dict_set(f->settings, "height", num);
+        }
+        if (f->init != NULL && f->init(f, &init))
+        {
+            const int back = (use_hip && g_hip_init_failed != NULL) ? g_hip_init_failed(pjob, i, &init) : 0;
+            if (back > 0)
+            {
+                i -= back - 1;
+                continue;
+            }
+            hb_log("hbh_preview_open: Failure to initialize filter '%s'", f->name);
+            hb_list_rem(pjob->list_filter, f);
+            hb_filter_close(&f);
+            continue;
+        }
+        i++;
+    }
+    for (int i = 0; i < hb_list_count(pjob->list_filter);)
+    {
+        f = hb_list_item(pjob->list_filter, i);
+        if (f->post_init != NULL && f->post_init(f, pjob))
+        {
+            hb_list_rem(pjob->list_filter, f);
+            if (f->close != NULL) f->close(f);
+            hb_filter_close(&f);
+            continue;
+        }
+        i++;
+    }
+    for (int i = 0; i < hb_list_count(pjob->list_filter) && c->nstages < HBH_MAX_STAGES; i++)
+        c->stage[c->nstages++] = hb_list_item(pjob->list_filter, i);
+    hb_list_close(&pjob->list_filter);
+    c->init = init;
+    return c;                                   /* (never threaded: hb_get_preview runs its filters one after the other) */
+}
+
+/* the address of stage i's hb_filter_object_t (tests read its name and settings), NULL beyond the last */
+void *hbh_chain_stage(hbh_chain_t *c, int i) { return c != NULL && i >= 0 && i < c->nstages ? c->stage[i] : NULL; }
+
 /* "name|name|..." of the stages, for tests that check what the swap / fallback left in the list */
 int hbh_chain_describe(hbh_chain_t *c, char *buf, int len)
 {

@@ -36,6 +36,13 @@ hbh_chain_t *hbh_chain_open(int nstages, void *const *protos, const char *const 
  * (hb_hip_setup_hw_filters) when use_hip, init with drop / CPU-fallback on failure (work.c:1820-1870). */
 hbh_chain_t *hbh_job_open(int nfilters, const int *ids, const char *const *settings, int pix_fmt, int width, int height,
                           int vrate_num, int vrate_den, int use_hip);
+/* A preview's filters built the way hb_get_preview builds them (hb.c:801-1063) with the hook of INTEGRATION.md 2b: the job's
+ * filters by id, then the display rescale for `par` (rescale != 0) and `format=<pix_fmt_name>` (not NULL), added in front of
+ * the init loop; the HIP swap when use_hip; the loop keeps what hb.c:850-861 keeps plus Format and the adapters.  The frames
+ * are yuv420p.  Never threaded.  hbh_chain_stage: stage i's hb_filter_object_t (NULL beyond the last). */
+hbh_chain_t *hbh_preview_open(int nfilters, const int *ids, const char *const *settings, int width, int height,
+                              int par_num, int par_den, int rescale, const char *pix_fmt_name, int use_hip);
+void *hbh_chain_stage(hbh_chain_t *c, int i);
 /* job->hw_device_index (common.h:991) of jobs opened from now on: which GPU the job's drop-ins run on; -1 = not set */
 void hbh_set_job_device(int index);
 /* jobs opened from now on carry one subtitle track of this source (enum subsource: 0 VOBSUB, 6 PGSSUB, ...) marked for

@@ -112,10 +112,26 @@ static const AVPixFmtDescriptor k_desc_p012 = {
     "p012le", 3, 1, 1, 0,
     { {0, 2, 0, 4, 12}, {1, 4, 0, 4, 12}, {1, 4, 2, 4, 12}, {0, 0, 0, 0, 0} } };
 
+/* The four packed 32-bit RGB orders with alpha (libavutil/pixdesc.c): one plane, four bytes a pixel, components R G B A
+ * at their byte offsets; flags AV_PIX_FMT_FLAG_RGB | AV_PIX_FMT_FLAG_ALPHA.  25 - 28 are FFmpeg's numbers, under names of
+ * this file (the filters' names for them: hbhip_host.h).  What hb_get_preview asks of `format` (AV_PIX_FMT_RGB32 is bgra on
+ * a little-endian host) and what the download adapter's packed pictures are laid out by. */
+enum { RT_PIX_FMT_ARGB = 25, RT_PIX_FMT_RGBA = 26, RT_PIX_FMT_ABGR = 27, RT_PIX_FMT_BGRA = 28 };
+#define DESC_RGB32(sym, nm, r, g, b, a) static const AVPixFmtDescriptor sym = { nm, 4, 0, 0, (1 << 5) | (1 << 7), \
+    { {0, 4, r, 0, 8}, {0, 4, g, 0, 8}, {0, 4, b, 0, 8}, {0, 4, a, 0, 8} } }
+DESC_RGB32(k_desc_argb, "argb", 1, 2, 3, 0);
+DESC_RGB32(k_desc_rgba, "rgba", 0, 1, 2, 3);
+DESC_RGB32(k_desc_abgr, "abgr", 3, 2, 1, 0);
+DESC_RGB32(k_desc_bgra, "bgra", 2, 1, 0, 3);
+
 const AVPixFmtDescriptor *av_pix_fmt_desc_get(int pix_fmt)
 {
     switch (pix_fmt)
     {
+        case RT_PIX_FMT_ARGB:        return &k_desc_argb;
+        case RT_PIX_FMT_RGBA:        return &k_desc_rgba;
+        case RT_PIX_FMT_ABGR:        return &k_desc_abgr;
+        case RT_PIX_FMT_BGRA:        return &k_desc_bgra;
         case RT_PIX_FMT_NV16:        return &k_desc_nv16;
         case RT_PIX_FMT_P012LE:      return &k_desc_p012;
         case RT_PIX_FMT_NV12:        return &k_desc_nv12;
@@ -143,7 +159,8 @@ int av_get_pix_fmt(const char *name)
                                  AV_PIX_FMT_YUVA420P, AV_PIX_FMT_YUVA422P, AV_PIX_FMT_YUVA444P,
                                  AV_PIX_FMT_YUV420P10LE, AV_PIX_FMT_YUV420P12LE, AV_PIX_FMT_YUV422P10LE, AV_PIX_FMT_YUV444P10LE,
                                  AV_PIX_FMT_YUV422P12LE, AV_PIX_FMT_YUV444P12LE, RT_PIX_FMT_NV12, RT_PIX_FMT_P010LE,
-                                 RT_PIX_FMT_NV16, RT_PIX_FMT_P012LE };
+                                 RT_PIX_FMT_NV16, RT_PIX_FMT_P012LE, RT_PIX_FMT_ARGB, RT_PIX_FMT_RGBA, RT_PIX_FMT_ABGR,
+                                 RT_PIX_FMT_BGRA };
     if (name == NULL) return AV_PIX_FMT_NONE;
     for (size_t i = 0; i < sizeof(known) / sizeof(known[0]); i++)
     {

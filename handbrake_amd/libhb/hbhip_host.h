@@ -51,6 +51,24 @@ static inline int hbhip_host_is_biplanar(int pix_fmt) { return pix_fmt == HBHIP_
  * step, the Format drop-in takes such a target only where this key stands, i.e. where the frames already are in HBM.
  * Stripped wherever the other three are. */
 #define HBHIP_FORMAT_DEEPEN_STEP "hip-deepen-step"
+/* The fifth: on a `format=bgra | rgba | argb | abgr` entry inside a run of 8-bit 4:2:0 frames - what hb_get_preview appends to
+ * the list it filters a preview picture through (hb.c:945-959, AV_PIX_FMT_RGB32).  Built like the widen step: the Format
+ * drop-in passes the frames through, and the run's download adapter, which hip_common.c gives the same `format=` value and
+ * this same key, makes the packed picture inside its repack (hbhip_frame_download_rgb32).  Only under the
+ * key does the adapter take an RGB format; stripped wherever the other four are. */
+#define HBHIP_FORMAT_RGB_STEP "hip-rgb-step"
+/* the HB_COLR_MAT_* numbers hbhip_frame_download_rgb32 has a coefficient row for (not RGB, YCgCo, ICtCp, chroma-derived) */
+static inline int hbhip_host_rgb32_matrix_ok(int m) { return m == 1 || m == 2 || (m >= 4 && m <= 7) || m == 9 || m == 10; }
+/* the four packed orders (FFmpeg's numbers, names of this project's own) and the HBHIP_RGB32_* order of one, else -1 */
+#define HBHIP_PIX_FMT_ARGB 25
+#define HBHIP_PIX_FMT_RGBA 26
+#define HBHIP_PIX_FMT_ABGR 27
+#define HBHIP_PIX_FMT_BGRA 28
+static inline int hbhip_host_rgb32_order(int pix_fmt)
+{
+    return pix_fmt == HBHIP_PIX_FMT_BGRA ? HBHIP_RGB32_BGRA : pix_fmt == HBHIP_PIX_FMT_RGBA ? HBHIP_RGB32_RGBA :
+           pix_fmt == HBHIP_PIX_FMT_ARGB ? HBHIP_RGB32_ARGB : pix_fmt == HBHIP_PIX_FMT_ABGR ? HBHIP_RGB32_ABGR : -1;
+}
 static inline void hbhip_host_biplanar_from_buf(hbhip_host_biplanar *f, const hb_buffer_t *b)
 {
     for (int p = 0; p < 2; p++)

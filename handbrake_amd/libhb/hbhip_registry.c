@@ -711,6 +711,7 @@ struct hb_filter_private_s
     int              biplanar;            /* the host side of this adapter is NV12 / P010LE: repacked on the GPU */
     int              surface;             /* download, surface=1: the NV12 / P010LE pictures it emits stay in device memory */
     int              widen;               /* download, HBHIP_FORMAT_WIDEN_STEP: P010LE from a run of 8-bit frames */
+    int              rgb_order;           /* download, HBHIP_FORMAT_RGB_STEP: the HBHIP_RGB32_* order of its packed pictures, else -1 */
     hbhip_ctx       *ctx;                 /* the job's GPU (hbhip_host_ctx_for) */
     dl_slot_t        dl[DL_DEPTH + 1];
     int              dl_head, dl_count;
@@ -727,7 +728,10 @@ struct hb_filter_private_s
  * allocator would (256-byte pitch, 16 padded rows).
  * format=p010le fits a run of 10 bits only - except under HBHIP_FORMAT_WIDEN_STEP, the key hip_common.c sets beside it behind
  * a marked `format=p010le` entry of an 8-bit 4:2:0 run: the adapter then emits P010LE, host pictures or depth-10 surfaces,
- * widened inside the repack (hbhip_frame_download_widen / hbhip_frame_export_surface_widen). */
+ * widened inside the repack (hbhip_frame_download_widen / hbhip_frame_export_surface_widen).
+ * format=bgra | rgba | argb | abgr is taken under HBHIP_FORMAT_RGB_STEP only, the key hip_common.c sets beside it behind a marked
+ * `format=bgra` entry of an 8-bit 4:2:0 run (hb_get_preview's list): the adapter then emits one-plane buffers of that format,
+ * packed inside the repack by the stream's matrix and range (hbhip_frame_download_rgb32).  Not into surfaces. */
 static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int to_device)
 {
     hb_filter_private_t *pv = calloc(1, sizeof(*pv));
@@ -746,6 +750,7 @@ static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int 
     pv->lcw = desc->log2_chroma_w;
     pv->lch = desc->log2_chroma_h;
     pv->input = *init;
+    pv->rgb_order = -1;
     int host_fmt = to_device ? init->pix_fmt : AV_PIX_FMT_NONE;
     char *want = NULL;
     if (!to_device && hb_dict_extract_string(&want, filter->settings, "format") && want != NULL && want[0] != 0)
@@ -755,8 +760,17 @@ static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int 
         int widen = 0;
         hb_dict_extract_bool(&widen, filter->settings, HBHIP_FORMAT_WIDEN_STEP);
         pv->widen = widen && host_fmt == HBHIP_PIX_FMT_P010LE && pv->depth == 8;
-        const int ok = hbhip_host_is_biplanar(host_fmt) && hbhip_host_planar_yuv(desc) && pv->lcw == 1 && pv->lch == 1 &&
-                       (pv->depth == (host_fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10) || pv->widen);
+        /* and its key beside format=bgra | rgba | argb | abgr on a run of 8-bit 4:2:0 frames of even size: the repack makes the
+         * packed picture, by the matrix and range the stream has here (never a public setting either) */
+        int rgb = 0;
+        hb_dict_extract_bool(&rgb, filter->settings, HBHIP_FORMAT_RGB_STEP);
+        if (rgb &&hbhip_host_rgb32_order(host_fmt) >= 0 && init->pix_fmt == AV_PIX_FMT_YUV420P &&
+            hbhip_host_rgb32_matrix_ok(init->color_matrix) && init->geometry.width >= 2 && init->geometry.height >= 2 &&
+            !(init->geometry.width & 1) && !(init->geometry.height & 1))
+            pv->rgb_order = hbhip_host_rgb32_order(host_fmt);
+        const int ok = pv->rgb_order >= 0 ||
+                       (hbhip_host_is_biplanar(host_fmt) && hbhip_host_planar_yuv(desc) && pv->lcw == 1 && pv->lch == 1 &&
+                        (pv->depth == (host_fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10) || pv->widen));
         if (!ok)
         {
             hb_error("hipdownload: format=%s does not fit a run of %s", want, desc->name);
@@ -769,7 +783,7 @@ static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int 
     int surface = 0;
     if (!to_device && hb_dict_extract_bool(&surface, filter->settings, "surface") && surface && !hbhip_host_is_biplanar(host_fmt))
     {
-        hb_error("hipdownload: surface=1 needs format=nv12 or format=p010le");
+        hb_error("hipdownload: surface=1 needs format=nv12 or format=p010le");      /* (packed RGB into surfaces: not built) */
         free(pv);
         return 1;
     }
@@ -784,6 +798,7 @@ static int adapter_init(hb_filter_object_t *filter, hb_filter_init_t *init, int 
         pv->biplanar = 1;
         init->pix_fmt = to_device ? (pv->depth == 8 ? AV_PIX_FMT_YUV420P : AV_PIX_FMT_YUV420P10) : host_fmt;
     }
+    if (pv->rgb_order >= 0) init->pix_fmt = host_fmt;
     init->hw_pix_fmt = to_device ? AV_PIX_FMT_HBHIP : AV_PIX_FMT_NONE;
     pv->output = *init;
     filter->private_data = pv;
@@ -943,7 +958,10 @@ static int download_work(hb_filter_object_t *filter, hb_buffer_t **buf_in, hb_bu
         hbhip_host_frame_from_buf(&hf, out);
         hbhip_host_biplanar hb;
         hbhip_host_biplanar_from_buf(&hb, out);
-        if ((pv->widen    ? hbhip_frame_download_widen_async(fr, &hb, &token) :
+        if ((pv->rgb_order >= 0 ? hbhip_frame_download_rgb32_async(fr, out->plane[0].data, out->plane[0].stride, pv->rgb_order,
+                                                                   pv->input.color_matrix, pv->input.color_range == 2 /* AVCOL_RANGE_JPEG */,
+                                                                   &token) :
+             pv->widen    ? hbhip_frame_download_widen_async(fr, &hb, &token) :
              pv->biplanar ? hbhip_frame_download_biplanar_async(fr, &hb, &token)
                           : hbhip_frame_download_async(fr, &hf, &token)) != HBHIP_OK)
         {

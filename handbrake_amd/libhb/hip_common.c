@@ -15,7 +15,9 @@
  *      marks a `format=yuv422p... | yuv444p...` entry behind a drop-in whose target has MORE chroma samples than the job's
  *      frames (HBHIP_FORMAT_UP_STEP): the Format drop-in takes such a target only there.  And `format=p010le` behind a
  *      drop-in of a yuv420p or nv12 job (HBHIP_FORMAT_WIDEN_STEP): the Format drop-in passes the 8-bit frames through and
- *      the download adapter, given format=p010le and the same key, widens them inside its repack.  And a planar
+ *      the download adapter, given format=p010le and the same key, widens them inside its repack.  And
+ *      `format=bgra | rgba | argb | abgr` behind a drop-in of a yuv420p job (HBHIP_FORMAT_RGB_STEP), what hb_get_preview appends:
+ *      built like the widen step, the adapter makes the packed picture inside its repack.  And a planar
  *      `format=yuv420p10le | yuv422p10le | ...` entry behind a drop-in whose target has FEWER chroma samples than the job's
  *      frames and a higher depth (HBHIP_FORMAT_DEEPEN_STEP), taken only there like the up step.
  * And one thing the VideoToolbox path does not need: a drop-in's init() may refuse settings it has no kernels for.
@@ -71,37 +73,46 @@ static int job_host_fmt(const hb_job_t *job)
 
 /* `host_fmt`: the job's own format when that is NV12 / P010LE.  The upload adapter sees it as the stream's format; the
  * download adapter is told to give it back (format=), so that what leaves the run is what the job's encoder expects. */
-static hb_filter_object_t *new_adapter(int id, int host_fmt, int widen)
+static hb_filter_object_t *new_adapter(int id, int host_fmt, const char *key)
 {
     hb_filter_object_t *a = hb_filter_copy(hbhip_filter_get(id));
     if (a != NULL && a->settings == NULL) a->settings = hb_dict_init();
-    if (a != NULL && id == HB_FILTER_HIP_DOWNLOAD && hbhip_host_is_biplanar(host_fmt))
+    if (a != NULL && id == HB_FILTER_HIP_DOWNLOAD && (hbhip_host_is_biplanar(host_fmt) || hbhip_host_rgb32_order(host_fmt) >= 0))
     {
-        hb_dict_set_string(a->settings, "format", host_fmt == HBHIP_PIX_FMT_NV12 ? "nv12" : "p010le");
-        if (widen) hb_dict_set_string(a->settings, HBHIP_FORMAT_WIDEN_STEP, "1");
+        const AVPixFmtDescriptor *d = av_pix_fmt_desc_get(host_fmt);
+        hb_dict_set_string(a->settings, "format", d->name);                      /* "nv12", "p010le"; "bgra", ... */
+        if (key != NULL) hb_dict_set_string(a->settings, key, "1");
     }
     return a;
 }
 
-/* the NV12 / P010LE target of a Format drop-in entry that mark_planar_steps() has marked, else AV_PIX_FMT_NONE.
- * *widen: the mark is HBHIP_FORMAT_WIDEN_STEP (the target is P010LE and the frames have 8 bits) */
-static int planar_step_target(const hb_filter_object_t *f, int *widen)
+/* the NV12 / P010LE / packed RGB target of a Format drop-in entry that mark_planar_steps() has marked, else AV_PIX_FMT_NONE.
+ * *key: the mark the download adapter shares with the entry - HBHIP_FORMAT_WIDEN_STEP (the target is P010LE and the frames
+ * have 8 bits), HBHIP_FORMAT_RGB_STEP (the target is one of the four packed orders) - or NULL (the planar step) */
+static int planar_step_target(const hb_filter_object_t *f, const char **key)
 {
     int marked = 0, fmt = AV_PIX_FMT_NONE;
     char *name = NULL;
-    *widen = 0;
+    *key = NULL;
     if (f == NULL || f->id != HB_FILTER_FORMAT || !hb_hip_filter_is_hip(f) || f->settings == NULL) return AV_PIX_FMT_NONE;
-    if (hb_dict_extract_bool(&marked, f->settings, HBHIP_FORMAT_WIDEN_STEP) && marked) *widen = 1;
+    if (hb_dict_extract_bool(&marked, f->settings, HBHIP_FORMAT_WIDEN_STEP) && marked) *key = HBHIP_FORMAT_WIDEN_STEP;
+    else if (hb_dict_extract_bool(&marked, f->settings, HBHIP_FORMAT_RGB_STEP) && marked) *key = HBHIP_FORMAT_RGB_STEP;
     else if (!hb_dict_extract_bool(&marked, f->settings, HBHIP_FORMAT_PLANAR_STEP) || !marked) return AV_PIX_FMT_NONE;
     if (hb_dict_extract_string(&name, f->settings, "format") && name != NULL) fmt = av_get_pix_fmt(name);
     free(name);
-    if (*widen && fmt != HBHIP_PIX_FMT_P010LE) { *widen = 0; return AV_PIX_FMT_NONE; }
-    return hbhip_host_is_biplanar(fmt) ? fmt : AV_PIX_FMT_NONE;
+    const int rgb = *key != NULL && strcmp(*key, HBHIP_FORMAT_RGB_STEP) == 0;
+    if (rgb ? hbhip_host_rgb32_order(fmt) < 0 : *key != NULL ? fmt != HBHIP_PIX_FMT_P010LE : !hbhip_host_is_biplanar(fmt))
+    {
+        *key = NULL;
+        return AV_PIX_FMT_NONE;
+    }
+    return fmt;
 }
 
-/* the four keys of mark_planar_steps(): nothing a CPU filter knows, and stale once the list in front has changed */
+/* the five keys of mark_planar_steps(): nothing a CPU filter knows, and stale once the list in front has changed */
 static void remove_marks(hb_dict_t *settings)
 {
+    hb_dict_remove(settings, HBHIP_FORMAT_RGB_STEP);
     hb_dict_remove(settings, HBHIP_FORMAT_PLANAR_STEP);
     hb_dict_remove(settings, HBHIP_FORMAT_UP_STEP);
     hb_dict_remove(settings, HBHIP_FORMAT_WIDEN_STEP);
@@ -139,7 +150,14 @@ static void remove_marks(hb_dict_t *settings)
  * encavcodec.c:281-289) fails work.c's first match and passes the second, match_pix_fmt(..., 1, 0): any entry with no
  * more chroma, whatever its depth.  Such an entry - a planar YUV 4:2:0 / 4:2:2 / 4:4:4 target at 10 or 12 bits that gains
  * chroma samples in no dimension, loses them in one at least and is deeper than the job - is marked under the same
- * condition, a drop-in in front of it; without the mark the Format drop-in declines it as before. */
+ * condition, a drop-in in front of it; without the mark the Format drop-in declines it as before.
+ *
+ * And the RGB step (HBHIP_FORMAT_RGB_STEP): `format=bgra` - or rgba, argb, abgr - on a job of yuv420p frames.  work.c appends no
+ * such entry, hb.c does: hb_get_preview, behind every front-end's preview window, filters its picture through the job's
+ * picture filters and a display rescale and ends the list in `format=<AV_PIX_FMT_RGB32>` (hb.c:945-959).  Under the same
+ * condition, a drop-in in front, the entry is marked; the Format drop-in passes the frames through and the run's download
+ * adapter, given the same `format=` value and key, makes the packed picture inside its repack.  yuv422p / yuv444p and deeper
+ * jobs stay unmarked (the repack takes 8-bit 4:2:0), and a lone `format=bgra` keeps its CPU filter. */
 static void mark_planar_steps(hb_job_t *job, int from)
 {
     hb_list_t *list = job->list_filter;
@@ -156,7 +174,11 @@ static void mark_planar_steps(hb_job_t *job, int from)
         const int fmt = av_get_pix_fmt(name);
         free(name);
         const char *key = NULL;
-        if (hbhip_host_is_biplanar(fmt))
+        if (hbhip_host_rgb32_order(fmt) >= 0)
+        {
+            if (job->input_pix_fmt == AV_PIX_FMT_YUV420P) key = HBHIP_FORMAT_RGB_STEP;
+        }
+        else if (hbhip_host_is_biplanar(fmt))
         {
             if (widens && fmt == HBHIP_PIX_FMT_P010LE) key = HBHIP_FORMAT_WIDEN_STEP;
             else if (planar && desc->comp[0].depth >= (fmt == HBHIP_PIX_FMT_NV12 ? 8 : 10)) key = HBHIP_FORMAT_PLANAR_STEP;
@@ -233,11 +255,11 @@ static void bracket_runs(hb_list_t *list, int from, int host_fmt)
         }
         if (n >= least)
         {
-            /* a run that ends in a marked `format=nv12 | p010le` entry leaves the device in that format */
-            int widen;
-            const int step_fmt = planar_step_target(hb_list_item(list, last), &widen);
-            hb_list_insert(list, last + 1, new_adapter(HB_FILTER_HIP_DOWNLOAD, step_fmt != AV_PIX_FMT_NONE ? step_fmt : host_fmt, widen));
-            hb_list_insert(list, i, new_adapter(HB_FILTER_HIP_UPLOAD, host_fmt, 0));
+            /* a run that ends in a marked `format=nv12 | p010le | bgra ...` entry leaves the device in that format */
+            const char *key;
+            const int step_fmt = planar_step_target(hb_list_item(list, last), &key);
+            hb_list_insert(list, last + 1, new_adapter(HB_FILTER_HIP_DOWNLOAD, step_fmt != AV_PIX_FMT_NONE ? step_fmt : host_fmt, key));
+            hb_list_insert(list, i, new_adapter(HB_FILTER_HIP_UPLOAD, host_fmt, NULL));
             last += 2;
         }
         i = last + 1;
@@ -279,12 +301,13 @@ int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
         hb_filter_close(&cpu);
         /* work.c drops the entry; a planar step that is not made leaves nothing for its download adapter to repack */
         hb_filter_object_t *next = hb_list_item(list, index + 1);
-        int widen;
-        if (planar_step_target(f, &widen) != AV_PIX_FMT_NONE && next != NULL && next->id == HB_FILTER_HIP_DOWNLOAD &&
+        const char *key;
+        if (planar_step_target(f, &key) != AV_PIX_FMT_NONE && next != NULL && next->id == HB_FILTER_HIP_DOWNLOAD &&
             next->settings != NULL)
         {
             hb_dict_remove(next->settings, "format");
             hb_dict_remove(next->settings, HBHIP_FORMAT_WIDEN_STEP);       /* (they came together) */
+            hb_dict_remove(next->settings, HBHIP_FORMAT_RGB_STEP);
         }
         return 0;
     }
@@ -327,7 +350,7 @@ int hb_hip_filter_init_failed(hb_job_t *job, int index, hb_filter_init_t *init)
             ret = 2;                                          /* the CPU filter now sits one slot earlier */
         }
         else
-            hb_list_insert(list, pos++, new_adapter(HB_FILTER_HIP_DOWNLOAD, job_host_fmt(job), 0));
+            hb_list_insert(list, pos++, new_adapter(HB_FILTER_HIP_DOWNLOAD, job_host_fmt(job), NULL));
     }
     hb_list_insert(list, pos, cpu);
     /* what follows may have lost the drop-in it stood behind: mark afresh, then bracket */

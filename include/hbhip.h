@@ -170,6 +170,19 @@ int  hbhip_frame_download_biplanar_async(hbhip_frame *fr, const hbhip_host_bipla
  * frame whose depth is not the picture's. */
 int  hbhip_frame_download_widen(hbhip_frame *fr, const hbhip_host_biplanar *dst);
 int  hbhip_frame_download_widen_async(hbhip_frame *fr, const hbhip_host_biplanar *dst, void **token);   /* finished with hbhip_frame_download_wait */
+/* A packed 32-bit RGB host picture from an 8-bit frame - what hb_get_preview's `format=bgra` asks for behind a device run:
+ * `fr` is a planar 4:2:0 frame of depth 8 and even size, `dst` a one-plane picture of its size, 4 bytes a pixel in the
+ * memory order `order` names, alpha 255.  The arithmetic is libswscale's unscaled yuv420p -> bgra path in its C form,
+ * restated (chroma nearest, every chroma term a whole number of luma steps into a clipped luma ramp; DESIGN 4.6.11,
+ * tests/rgb32_model.py), done in one kernel ahead of the copy.  `matrix` is an HB_COLR_MAT_* number (2, unspecified, is
+ * taken as BT.601 as swscale does), `full_range` the frame's range; the result is full-range RGB.  Ordering, the staging
+ * buffer and the token are hbhip_frame_download_biplanar's; 4 * width bytes of each of `dst`'s rows are written and nothing
+ * else.  HBHIP_ERR_UNSUPPORTED: a frame that is not 4:2:0 at depth 8, an odd width or height, a size under 2 x 2, a matrix
+ * with no coefficient row (RGB, YCgCo, ICtCp, the chroma-derived ones); HBHIP_ERR_ARG: a stride below 4 * width, an order
+ * outside the enum. */
+enum { HBHIP_RGB32_BGRA, HBHIP_RGB32_RGBA, HBHIP_RGB32_ARGB, HBHIP_RGB32_ABGR };
+int  hbhip_frame_download_rgb32(hbhip_frame *fr, uint8_t *dst, int stride, int order, int matrix, int full_range);
+int  hbhip_frame_download_rgb32_async(hbhip_frame *fr, uint8_t *dst, int stride, int order, int matrix, int full_range, void **token);   /* finished with hbhip_frame_download_wait */
 
 /* ---- device surfaces: NV12 / P010LE pictures that already are, or stay, in HBM ------------------------------------------
  * What AMD's decoder hands out and AMF / VCE take in, without the host copy: a surface has a pitch of its own per plane
